@@ -19,7 +19,25 @@ the same number of frames per step and `value` = world * frames per step * steps
 `python bench.py --gpus N` with WORLD_SIZE unset starts the N ranks itself (fresh child processes, created before this process
 touches the GPU runtime); under torch.distributed.run the ranks come from the environment.
 
-Extra keys on the JSON line:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, runs W warm-up steps and K timed steps, writes the outputs
+of the last timed step when `--dump-outputs DIR` is given, and prints the JSON line: `metric`, `value` (frames/s over the K timed
+steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds per timed step), the run's configuration and the mean
+keypoint / match counts of the last timed batch.
+
+--dump-outputs DIR  after the timed steps, what the last batch of every pipeline in the last timed step handed back, as DIR/<name>.npy
+                    (float32, < 64 MB in all; inputs are seeded, so equal arguments give equal inputs):
+                      counts        [n keypoints, monoIndex] of every frame of those batches, in batch order
+                      nmatches      SearchByProjection's return value per frame (not with --no-match)
+                      frames        (frame set, frame index) of a fixed, seeded sample of those frames, ascending
+                      keypoints     the sample's keypoints concatenated, columns x, y, size, angle, response, octave, class_id
+                      keypoints_un  the same after UndistortKeyPoints (EuRoC geometry only)
+                      descriptors   the sample's descriptors concatenated, 32 byte values per keypoint
+                      matches       the sample's match indices concatenated (euroc: match_of_query, one per keypoint of the frame
+                                    before; tumvi: the slot array, one per keypoint of the frame itself; -1 = none)
+                    Rank 0 writes its own shard only.
+
+--full adds everything else the benchmark measures or checks (per-kernel HIP events during the timed steps, the isolated re-run,
+the host-fed leg, the CPU oracle baseline and parity tie, the roofline); with it the line carries these extra keys:
   roofline         dominant kernel: algorithmic bytes per launch / average launch duration (HIP events on the launch stream,
                    measured over the timed region; see also profiles/), against the 8 TB/s HBM peak; `valu_issue`: the step's vector
                    instructions per second against the MEASURED issue ceiling of its opcode mix (profiles/valu_calib.json)
@@ -67,6 +85,10 @@ def parse_args(argv):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timings, isolated re-run, host-fed leg, CPU baseline with the parity tie, and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, seeded sample, < 64 MB)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="euroc")
     ap.add_argument("--batch", type=int, default=256, help="frames per batch (one launch sequence)")
     ap.add_argument("--batches-per-step", type=int, default=224, help="batches per step: a step is batch * batches_per_step frames per GPU")
@@ -78,7 +100,10 @@ def parse_args(argv):
     ap.add_argument("--distort", choices=["auto", "none", "euroc"], default="auto",
                     help="euroc: Frame::UndistortKeyPoints with the EuRoC.yaml:9-17 calibration between extraction and search, grid on the "
                          "undistorted-corner bounds (Frame.cc:837-899) - what the reference does on this configuration; auto = euroc for --config euroc")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -128,6 +153,56 @@ def algorithmic_bytes(level_shapes, n_kp):
 def stats_ms(a):
     a = np.asarray(a, dtype=np.float64)
     return {"median": round(float(np.median(a)), 3), "mean": round(float(a.mean()), 3)}
+
+
+DUMP_LIMIT = 64 << 20
+DUMP_SAMPLE = 128       # frames whose keypoints, descriptors and matches are written
+DUMP_SEED = 20240917
+
+
+def dump_outputs(dirname, lasts, B, cap, match, distort, tumvi):
+    """--dump-outputs: `lasts` = [(pipeline, frame set)] of the last timed step's final batches, in batch order.  Counts (and
+    nmatches) of every frame; keypoints, descriptors and matches of a seeded sample of frames, each block concatenated over the
+    sample in ascending order, so that two builds with equal counts give arrays of equal shape."""
+    F = len(lasts) * B
+    cnt = np.concatenate([pp.d_cnt[1:].cpu().numpy() for pp, _ in lasts]).astype(np.int64)            # (F, 2)
+    per_frame = cap * 4 * (7 + (7 if distort else 0) + 32 + (1 if match else 0)) + 2 * 4
+    always = F * 4 * (2 + (1 if match else 0))
+    nsel = min(F, DUMP_SAMPLE, (DUMP_LIMIT - always) // per_frame)
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(F, nsel, replace=False))
+    out = {"counts": cnt.astype(np.float32)}
+    if match:
+        out["nmatches"] = np.concatenate([pp.d_nm.cpu().numpy() for pp, _ in lasts]).astype(np.float32)
+    out["frames"] = np.array([(lasts[f // B][1], f % B) for f in sel], dtype=np.float32).reshape(-1, 2)
+    blocks = {"keypoints": [], "keypoints_un": [], "descriptors": [], "matches": []}
+    for f in sel:
+        pp, t = lasts[f // B][0], int(f % B)
+        n = min(int(cnt[f, 0]), cap)
+        for name, buf in (("keypoints", pp.d_kps), ("keypoints_un", pp.d_kps_un if distort else None)):
+            if buf is None:
+                continue
+            raw = buf[1 + t, :n].cpu().numpy()           # float32 columns, octave / class_id stored as int32 bits
+            kp = raw.copy()
+            kp[:, 5:7] = raw[:, 5:7].view(np.int32)
+            blocks[name].append(kp)
+        blocks["descriptors"].append(pp.d_desc[1 + t, :n].cpu().numpy().astype(np.float32))
+        if match:
+            # euroc: match_of_query of the previous frame's keypoints (slot t of the query side, wrapping); tumvi: the slot array
+            m = n if tumvi else min(int(pp.d_cnt[t, 0].item()), cap)
+            blocks["matches"].append((pp.d_slot if tumvi else pp.d_moq)[t, :m].cpu().numpy().astype(np.float32))
+    widths = {"keypoints": 7, "keypoints_un": 7, "descriptors": 32, "matches": None}
+    for name, parts in blocks.items():
+        if (name == "keypoints_un" and not distort) or (name == "matches" and not match):
+            continue
+        w = widths[name]
+        empty = np.zeros((0,) if w is None else (0, w), np.float32)
+        out[name] = np.concatenate(parts) if parts else empty
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return total
 
 
 def cpu_legs(conf, groups, g_last, gpu_last, scene_host, cap, nthreads, distort=None):
@@ -224,13 +299,16 @@ def main():
         shard.init_distributed(backend if backend != "nccl" else "gloo")
         dt = shard.timed_steps(lambda: time.sleep(0.002 * (rank + 1)), args.steps, args.warmup, world=world)
         hf = None
-        if not args.no_host_fed:   # the host-fed leg's plumbing: every rank runs it, MAX over ranks, whole-job aggregate
+        if args.full and not args.no_host_fed:   # the host-fed leg's plumbing: every rank runs it, MAX over ranks, whole-job aggregate
             tf = shard.timed_steps(lambda: time.sleep(0.003 * (rank + 1)), 1, 0, world=world)
             hf = {"value": round(world * 48 * B / tf, 2), "unit": "frames/s", "n_gpus": world, "seconds_max_over_ranks": round(tf, 5)}
         if rank == 0:
-            emit({"selftest": True, "metric": conf["metric"], "value": round(shard.aggregate_fps(frames_per_step, args.steps, world, dt), 2),
-                              "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-                              "scaling": "weak", "host_fed": hf, "data": "none (ORB_BENCH_SELFTEST: no device work, launcher / barrier / MAX plumbing only)"})
+            out = {"selftest": True, "metric": conf["metric"], "value": round(shard.aggregate_fps(frames_per_step, args.steps, world, dt), 2),
+                   "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+                   "scaling": "weak", "data": "none (ORB_BENCH_SELFTEST: no device work, launcher / barrier / MAX plumbing only)"}
+            if args.full:
+                out["host_fed"] = hf
+            emit(out)
         shard.finish_distributed()
         return
 
@@ -369,8 +447,37 @@ def main():
             pp.mt.set_profiling(True)
 
     dt = shard.timed_steps(step, args.steps, args.warmup, sync=torch.cuda.synchronize, world=world,
-                           device=dev if backend == "nccl" else None, before_timed=start_profiling)
+                           device=dev if backend == "nccl" else None, before_timed=start_profiling if args.full else None)
     fps = shard.aggregate_fps(frames_per_step, args.steps, world, dt)
+    # the last timed batch (the parity tie of --full compares it).  The dump comes first: --full's isolated and host-fed runs below
+    # reuse the pipelines' buffers
+    j_last = counter[0] - 1
+    p_last, g_last = pipes[j_last % S], (j_last // S + j_last % S) % G
+    if args.dump_outputs and rank == 0:
+        lasts = [(pipes[j % S], (j // S + j % S) % G) for j in range(counter[0] - min(NB, S), counter[0])]
+        nbytes = dump_outputs(args.dump_outputs, lasts, B, cap, not args.no_match, distort, tumvi)
+        sys.stderr.write("bench.py: outputs of the last timed step (%d batches, %.1f MB) written to %s\n"
+                         % (len(lasts), nbytes / 2 ** 20, args.dump_outputs))
+    cnt = p_last.d_cnt[1:].cpu().numpy()
+    n_kp = float(cnt[:, 0].mean())
+    nm_mean = float(p_last.d_nm.cpu().numpy().mean()) if not args.no_match else 0.0
+    out = {
+        "metric": conf["metric"] if not args.no_match else conf["metric"].replace("extract+match", "extract"),
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8", "data": "synthetic",
+        "config": {"workload": conf["workload"], "image": "%dx%d" % (W, H), "nfeatures": CFG["nfeatures"], "nlevels": CFG["nlevels"],
+                   "frames_per_step_per_gpu": frames_per_step, "batch": B, "batches_per_step": NB, "distinct_frames_per_gpu": G * B, "streams": S,
+                   "mean_keypoints_per_frame": round(n_kp, 1), "mean_matches_per_frame": round(nm_mean, 1),
+                   "frame_geometry": ("EuRoC.yaml:9-17 calibration: keypoints undistorted per batch on the device, grid bounds = undistorted corners "
+                                      "(%.2f, %.2f, %.2f, %.2f)" % bounds) if distort else "no distortion: bounds = image rectangle",
+                   "sharding": "frames round-robin, one process per GPU, no collective"},
+    }
+    if not args.full:
+        if rank == 0:
+            emit(out)
+        shard.finish_distributed()
+        return
 
     acc, nsamp = {}, 0
     for pp in pipes:
@@ -383,9 +490,6 @@ def main():
             acc[k] = acc.get(k, 0.0) + v
         nsamp += 1
     acc = {k: v / nsamp for k, v in acc.items()}
-    # the last timed batch: what the parity tie compares
-    j_last = counter[0] - 1
-    p_last, g_last = pipes[j_last % S], (j_last // S + j_last % S) % G
     gpu_last = None      # what EVERY pipeline's last batch left in HBM: [(frame set, outputs)], the pipeline of the very last batch first
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle_py as O
@@ -398,9 +502,6 @@ def main():
                 o["match"] = (pp.d_slot if tumvi else pp.d_moq).cpu().numpy()
             return o
         gpu_last = [(pp.group, grab(pp)) for pp in [p_last] + [q for q in pipes if q is not p_last and q.group >= 0]]
-    cnt = p_last.d_cnt[1:].cpu().numpy()
-    n_kp = float(cnt[:, 0].mean())
-    nm_mean = float(p_last.d_nm.cpu().numpy().mean()) if not args.no_match else 0.0
 
     # the same kernels alone on the chip (one pipeline, synchronised between batches): isolates kernel quality from sharing
     pipes[0].ex.set_profiling(True)       # resets the event ring
@@ -560,17 +661,7 @@ def main():
 
     rc = 0
     if rank == 0:
-        out = {
-            "metric": conf["metric"] if not args.no_match else conf["metric"].replace("extract+match", "extract"),
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
-            "config": {"workload": conf["workload"], "image": "%dx%d" % (W, H), "nfeatures": CFG["nfeatures"], "nlevels": CFG["nlevels"],
-                       "frames_per_step_per_gpu": frames_per_step, "batch": B, "batches_per_step": NB, "distinct_frames_per_gpu": G * B, "streams": S,
-                       "mean_keypoints_per_frame": round(n_kp, 1), "mean_matches_per_frame": round(nm_mean, 1),
-                       "frame_geometry": ("EuRoC.yaml:9-17 calibration: keypoints undistorted per batch on the device, grid bounds = undistorted corners "
-                                          "(%.2f, %.2f, %.2f, %.2f)" % bounds) if distort else "no distortion: bounds = image rectangle",
-                       "sharding": "frames round-robin, one process per GPU, no collective"},
+        out.update({
             "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic,
                          "algorithmic_bytes_per_launch": round(launch_bytes), "avg_launch_ms": round(per_launch[dom], 4),
@@ -581,7 +672,7 @@ def main():
                                       "frac": round(launch_bytes / (iso[dom] / nl * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                                       "stage_ms_per_batch": {k: round(v, 4) for k, v in iso.items()}},
                          "pipeline_algorithmic_GBps": round(fps / world * total_bytes / 1e9, 2)},
-        }
+        })
         if valu is not None and world == 1:
             out["roofline"]["valu_issue"] = valu
         if host_fed is not None:

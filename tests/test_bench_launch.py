@@ -20,7 +20,7 @@ def _run(extra_args, extra_env):
 
 
 def test_gpus_2_spawns_two_ranks():
-    p = _run(["--gpus", "2", "--steps", "5", "--warmup", "1"], {})
+    p = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full"], {})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{")      # ONE line on stdout, nothing else (library chatter such as Gloo's goes to stderr)
@@ -37,7 +37,7 @@ def test_gpus_2_spawns_two_ranks():
 
 
 def test_no_host_fed_flag():
-    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--no-host-fed"], {})
+    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--no-host-fed", "--full"], {})
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert out["host_fed"] is None
@@ -48,6 +48,22 @@ def test_gpus_1_is_a_single_process():
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1
+
+
+def test_plain_run_is_the_headline_only():
+    """Without --full the line carries the headline and nothing measured beside it; --steps is the number of timed steps."""
+    p = _run(["--gpus", "2", "--steps", "4", "--warmup", "1"], {})
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] >= 4.0
+    assert "host_fed" not in out
+
+
+def test_steps_must_be_positive():
+    p = _run(["--steps", "0"], {})
+    assert p.returncode == 2 and "--steps" in p.stderr
 
 
 def test_world_size_mismatch_is_refused():

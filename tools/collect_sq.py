@@ -2,7 +2,7 @@
 """Per-kernel SQ counters with rocprofv3 (run ON THE GPU BOX, from the repo root):  python tools/collect_sq.py [pass ...]
 
 Each pass is a comma-separated counter list that fits the 8 SQ slots; passes run as separate profiles (--pmc with
---kernel-trace only).  Prints per-launch averages per kernel and writes gpurun_out/sq_counters.json.
+--kernel-trace only).  Prints per-launch averages per kernel and writes $ORB_OUT/sq_counters.json (default build/out/).
 SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles (MI355X_MICROARCH.md).
 """
 import collections
@@ -15,7 +15,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.environ.get("ORB_OUT") or os.path.join(ROOT, "build", "out")
 DEFAULT = ["SQ_WAVE_CYCLES,SQ_BUSY_CYCLES,SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_ACTIVE_INST_VALU,SQ_ACTIVE_INST_SCA,SQ_ACTIVE_INST_LDS",
            "SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_WAIT_INST_LDS,SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE,SQ_ACTIVE_INST_ANY,SQ_INSTS_SMEM,SQ_WAVES"]
 

@@ -8,7 +8,7 @@ reads by 2x and other widths are uncalibrated, so a known-traffic kernel in the 
 pattern (tools/calib, orbx_calibration_copy: 256 MiB read + 256 MiB written) runs in the same profile; its measured/known ratio is
 the correction applied to every kernel (reported alongside the raw numbers).
 
-Writes gpurun_out/traffic.json:  {kernel: {"launches", "fetch_raw_B", "write_raw_B", "fetch_B", "write_B", "hbm_B"}}
+Writes $ORB_OUT/traffic.json (default build/out/):  {kernel: {"launches", "fetch_raw_B", "write_raw_B", "fetch_B", "write_B", "hbm_B"}}
 (per-launch averages, batch 256) plus the calibration factors.
 """
 import collections
@@ -20,7 +20,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.environ.get("ORB_OUT") or os.path.join(ROOT, "build", "out")
 CALIB_BYTES = 256 << 20
 
 DRIVER = r'''
