@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 #include <mutex>
 #include <chrono>
 
@@ -1071,19 +1072,14 @@ int orbx_download_level_keypoints(orbx_t *h, int frame, int level, float *xyr, i
 struct orbm_handle {
   int device = 0;
   hipStream_t stream = nullptr;
-  DevBuf d_kp, d_desc, d_ur, d_qdesc, d_qf[4], d_qi[2], d_qfl, d_slot, d_sobs, d_moq, d_bd, d_nm, d_a, d_b, d_c, d_topk;
-  DevBuf d_partner, d_qside, d_qany;
-  DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
-  DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
+  int scan_mode = 0;        // SCAN_AUTO / SCAN_DENSE / SCAN_WALK of the projection searches (orbm_set_scan_mode)
   int hamming_engine = 2;   // orbm_set_hamming_engine: 0 vector ALU, 1 k_match_scan_mfma, 2 (default) + lists built inside k_match_resolve for all-open pairs
-  DevBuf d_block;     // inputs + outputs of one host-pointer search, one block (see search_host)
-  int scan_mode = 0;  // SCAN_AUTO / SCAN_DENSE / SCAN_WALK of the projection searches (orbm_set_scan_mode); next_scan_mode: one search only
-  int next_scan_mode = -1;
+  DevBuf d_block;     // inputs + outputs of one host-pointer entry point, one block (see stage)
   void *pin = nullptr; size_t pin_bytes = 0;   // its pinned host mirror
-  DevBuf scratch[8];  // grow-only buffers of the per-node / per-map-point entry points (SearchByBoW, ...)
-  // fisheye-stereo options of the NEXT projection search (set by the *_fisheye entry points, consumed and cleared by
-  // orbm_search_by_projection_batch_device): device pointers
-  struct { int nleft = 0; const int32_t *partner = nullptr; const uint8_t *qside = nullptr; int couple = 0; int serial = 0; uint8_t *qany = nullptr; int init_th_low = -1; const float *fuse_inv_sigma2 = nullptr; } ext;
+  DevBuf d_topk;      // per-query candidate lists of the scan / walk, for the resolve (all projection searches)
+  DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
+  DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
+  DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
   bool profiling = false;
   hipEvent_t ev[PROF_DEPTH][3] = {};
   int prof_head = 0;
@@ -1104,6 +1100,56 @@ struct orbm_handle {
 static void *getenv_ptr(const char *name) { const char *e = getenv(name); return e ? (void *)strtoull(e, nullptr, 0) : nullptr; }
 #endif
 
+// Inputs of a host-pointer entry point as ONE block: the parts lie at 256-byte offsets in m->d_block, those with a source are
+// copied into the pinned mirror m->pin and uploaded with one H2D copy (a dozen pageable copies would each stage and synchronise
+// on their own).  A part without a source reserves an output-only region.  The mirror spans the outputs too only when the caller
+// downloads them through it (mirror_outputs); a large output copied straight to the caller takes no pinned memory.
+// dev[i]: device address of part i, nullptr for an empty part.
+struct Part { const void *src; size_t bytes; };
+
+static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> parts, void **dev, bool mirror_outputs = false) {
+  size_t total = 0, upload = 0;
+  for (const Part &p : parts) {   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
+    if (p.bytes > (SIZE_MAX >> 3) - total) { m->err = "staging: inputs too large"; return ORBX_E_HIP; }
+    total += (p.bytes + 255) & ~(size_t)255;
+    if (p.src) upload = total;
+  }
+  const size_t mirror = mirror_outputs ? total : upload;
+  if (m->pin_bytes < mirror) {
+    if (m->pin) (void)hipHostFree(m->pin);
+    m->pin = nullptr; m->pin_bytes = 0;
+    MCHECK(m, hipHostMalloc(&m->pin, 2 * mirror, hipHostMallocDefault));   // grown rarely: a re-allocation costs tens of milliseconds
+    m->pin_bytes = 2 * mirror;
+  }
+  MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
+  size_t off = 0;
+  for (const Part &p : parts) {
+    if (p.src && p.bytes) memcpy((uint8_t *)m->pin + off, p.src, p.bytes);
+    *dev++ = p.bytes ? (uint8_t *)m->d_block.p + off : nullptr;
+    off += (p.bytes + 255) & ~(size_t)255;
+  }
+  if (upload) MCHECK(m, hipMemcpyAsync(m->d_block.p, m->pin, upload, hipMemcpyHostToDevice, s));
+  return 0;
+}
+
+// The pinned-mirror address of a device address inside m->d_block (entry points staged with mirror_outputs)
+static void *mirror_of(orbm_handle *m, const void *d) { return (uint8_t *)m->pin + ((const uint8_t *)d - (const uint8_t *)m->d_block.p); }
+
+// Options of one projection search beyond the arguments of orbm_search_by_projection_batch_device (see MatchProblemSet); the
+// defaults are a plain search.  Pointers are device addresses.
+struct SearchOpts {
+  int scan_mode = SCAN_AUTO;   // SCAN_AUTO / SCAN_DENSE / SCAN_WALK; frames beyond 2048 keypoints are scanned whatever it says
+  int nleft = 0, couple = 0, serial = 0;   // fisheye-stereo frames
+  const int32_t *partner = nullptr;
+  const uint8_t *qside = nullptr;
+  uint8_t *qany = nullptr;
+  int init_th_low = -1;        // >= 0: SearchForInitialization's resolve instead of the claim loop
+  bool fuse = false;           // Fuse: the chi-square gate with inv_sigma2[level]
+  float inv_sigma2[16] = {};
+};
+
+template <int V> using ScanKind = std::integral_constant<int, V>;
+
 extern "C" {
 
 orbm_t *orbm_create(int device) {
@@ -1122,9 +1168,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_kp, &m->d_desc, &m->d_ur, &m->d_qdesc, &m->d_qf[0], &m->d_qf[1], &m->d_qf[2], &m->d_qf[3], &m->d_qi[0], &m->d_qi[1],
-                    &m->d_qfl, &m->d_slot, &m->d_sobs, &m->d_moq, &m->d_bd, &m->d_nm, &m->d_a, &m->d_b, &m->d_c, &m->d_topk, &m->d_partner, &m->d_qside, &m->d_qany, &m->scratch[0], &m->scratch[1], &m->scratch[2], &m->scratch[3],
-                    &m->scratch[4], &m->scratch[5], &m->scratch[6], &m->scratch[7], &m->d_block, &m->d_lfq, &m->d_rank};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_lfq, &m->d_tri_count, &m->d_tri_keys};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -1295,18 +1339,15 @@ void orbm_project(int cam_type, const float *p, float X, float Y, float Z, float
   }
 }
 
-int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int frame_stride, const int32_t *d_frame_n,
-                                           int frame_n_stride, const orbm_queries_t *q, int query_stride,
-                                           const int32_t *d_query_n, int query_n_stride, int npairs, float nnratio,
-                                           int th_dist, int use_second, int32_t *d_slot, uint8_t *d_slot_obs,
-                                           int32_t *d_moq, int32_t *d_bd, int32_t *d_nm, void *stream_) {
+static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, const int32_t *d_frame_n, int frame_n_stride, const orbm_queries_t *q,
+                        int query_stride, const int32_t *d_query_n, int query_n_stride, int npairs, float nnratio, int th_dist, int use_second,
+                        int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_bd, int32_t *d_nm, hipStream_t s, const SearchOpts &o) {
   if (!m || !f || !q || npairs <= 0 || !d_slot || !d_slot_obs) return ORBX_E_ARG;
   if (!f->keys_un || !f->descriptors || !q->descriptors || !q->u || !q->v || !q->radius || !q->min_level || !q->max_level) return ORBX_E_ARG;
   if (!(f->max_x > f->min_x) || !(f->max_y > f->min_y)) return ORBX_E_ARG;
   // bestDist starts at 256 in the reference: a threshold >= 256 would "accept" a query without any candidate (index -1 there)
   if (th_dist < 0 || th_dist > 255) { m->err = "th_dist must be in [0, 255]"; return ORBX_E_ARG; }
   MCHECK(m, hipSetDevice(m->device));
-  hipStream_t s = (hipStream_t)stream_;  // verbatim: NULL is the device's default stream
   MatchProblemSet M;
   memset(&M, 0, sizeof(M));
   M.kp = reinterpret_cast<const float *>(f->keys_un);
@@ -1326,12 +1367,8 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
 #if defined(RESOLVE_STAMPS) || defined(WALK_STAMPS) || defined(SCAN_STAMPS) || defined(MF_STAMPS) || defined(WIDE_STAMPS)
   M.dbg = (long long *)getenv_ptr("ORBHIP_DBG_PTR");
 #endif
-  M.nleft = m->ext.nleft; M.partner = m->ext.partner; M.qside = m->ext.qside; M.couple = m->ext.couple;
-  M.serial = m->ext.serial; M.qany = m->ext.qany;
-  const int init_th_low = m->ext.init_th_low;  // >= 0: SearchForInitialization's resolve instead of the claim loop
-  const bool fuse = m->ext.fuse_inv_sigma2 != nullptr;
-  if (fuse) for (int i = 0; i < 16; i++) M.inv_sigma2[i] = m->ext.fuse_inv_sigma2[i];
-  m->ext = {};
+  M.nleft = o.nleft; M.partner = o.partner; M.qside = o.qside; M.couple = o.couple; M.serial = o.serial; M.qany = o.qany;
+  for (int i = 0; i < 16; i++) M.inv_sigma2[i] = o.inv_sigma2[i];
   const int maxn = d_frame_n ? frame_stride : f->n;
   const int maxq = d_query_n ? query_stride : q->nq;
   if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
@@ -1349,9 +1386,11 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
     MCHECK(m, hipStreamSynchronize(s));
     MCHECK(m, m->d_topk.reserve(need));
   }
+  // Window walk (k_match_walk) or full scan (k_match_scan): decided per pair on the device unless a mode is forced; frames beyond
+  // 2048 keypoints (Key64) are always scanned.
+  const int force = !k32 ? SCAN_DENSE : o.scan_mode;
   // matrix-pipe scan of the open-window query blocks (monocular Key32 problems, batch mode): rank tables for it
-  const int force0 = !k32 ? SCAN_DENSE : (m->next_scan_mode >= 0 ? m->next_scan_mode : m->scan_mode);
-  const bool mfma = m->hamming_engine >= 1 && k32 && !fuse && !M.qside && !M.partner && !M.u_right && nslices == 1 && force0 != SCAN_WALK;
+  const bool mfma = m->hamming_engine >= 1 && k32 && !o.fuse && !M.qside && !M.partner && !M.u_right && nslices == 1 && force != SCAN_WALK;
   const size_t nrank = (size_t)(npairs - 1) * frame_stride + maxn;
   if (mfma && sizeof(uint32_t) * (2 * nrank + (size_t)npairs) > m->d_rank.bytes) {
     MCHECK(m, hipStreamSynchronize(s));
@@ -1368,30 +1407,26 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
   const size_t big = small + sizeof(uint32_t) * (size_t)((maxn + 3) / 4) + 48 * (size_t)maxn;   // + octave bytes, records, descriptors
   const bool ldscand = big <= 136 * 1024;   // + the kernel's static LDS (Key32: wide list array 16 KiB, chunk lists, requests)
   // fused form: + one accumulator seed per keypoint; serial / coupled problems never take the wide form
-  const bool fused = mfma && m->hamming_engine >= 2 && init_th_low < 0 && !M.serial && M.couple == 0 && big + sizeof(uint32_t) * (size_t)maxn <= 138 * 1024;
+  const bool fused = mfma && m->hamming_engine >= 2 && o.init_th_low < 0 && !M.serial && M.couple == 0 && big + sizeof(uint32_t) * (size_t)maxn <= 138 * 1024;
   const size_t lds = fused ? big + sizeof(uint32_t) * (size_t)maxn : ldscand ? big : small;
   if (lds > 152 * 1024) { m->err = "too many keypoints per frame for the search kernels' LDS state (fisheye-stereo frames: at most 13000)"; return ORBX_E_ARG; }
   const dim3 rblock(64 * RESOLVE_NW_OF(fused));
-  // Window walk (k_match_walk) or full scan (k_match_scan): decided per pair on the device unless a mode is forced; frames beyond
-  // 2048 keypoints (Key64) are always scanned.  The walk's workgroups come first: they are the short ones.
-  const int force = !k32 ? SCAN_DENSE : (m->next_scan_mode >= 0 ? m->next_scan_mode : m->scan_mode);
-  m->next_scan_mode = -1;
+  // The walk's workgroups come first: they are the short ones.
   const int capn = std::min((maxn + 7) & ~7, WALK_MAX_N);
   // few pairs in flight: four lanes per query and four times the workgroups (see k_match_walk)
   const int lpq = (long long)npairs * qblocks <= 32 ? 4 : 1;
   const int wqblocks = (maxq + MATCH_NT / lpq - 1) / (MATCH_NT / lpq);
-  const size_t wlds = sizeof(uint32_t) * (GRID_CELLS + 4) + (12 + (fuse || M.u_right ? 4 : 0)) * (size_t)capn + 2 * WALK_LIST * MATCH_NT +
+  const size_t wlds = sizeof(uint32_t) * (GRID_CELLS + 4) + (12 + (o.fuse || M.u_right ? 4 : 0)) * (size_t)capn + 2 * WALK_LIST * MATCH_NT +
                       (lpq > 1 ? sizeof(uint32_t) * MATCH_TOPK * MATCH_NT : 0);
   const dim3 wgrid(8 * wqblocks * ((npairs + 7) / 8));
-#define LAUNCH_WALK(MODE)                                                                                                                                    \
-  do {                                                                                                                                                        \
-    if (lpq > 1) hipLaunchKernelGGL((k_match_walk<Key32, MODE, 4>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);      \
-    else hipLaunchKernelGGL((k_match_walk<Key32, MODE, 1>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);               \
-  } while (0)
+  auto walk = [&](auto kind) {
+    constexpr int K = decltype(kind)::value;
+    if (lpq > 1) hipLaunchKernelGGL((k_match_walk<Key32, K, 4>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
+    else hipLaunchKernelGGL((k_match_walk<Key32, K, 1>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
+  };
   if (force != SCAN_DENSE) {
-    if (fuse) LAUNCH_WALK(SCAN_FUSE); else if (M.qside) LAUNCH_WALK(SCAN_FISHEYE); else if (M.u_right) LAUNCH_WALK(SCAN_UR); else LAUNCH_WALK(SCAN_PLAIN);
+    if (o.fuse) walk(ScanKind<SCAN_FUSE>()); else if (M.qside) walk(ScanKind<SCAN_FISHEYE>()); else if (M.u_right) walk(ScanKind<SCAN_UR>()); else walk(ScanKind<SCAN_PLAIN>());
   }
-#undef LAUNCH_WALK
   uint32_t *rec = mfma ? (uint32_t *)m->d_rank.p : nullptr, *keyrec = mfma ? rec + nrank : nullptr, *pairflag = mfma ? keyrec + nrank : nullptr;
   // Engine 2 (fused): the pairs k_match_rank flags make their lists inside k_match_resolve; what is left (pairs with windowed queries)
   // goes to the walk / the vector-ALU scan.  k_match_scan_mfma is not launched then: a launch whose workgroups only read a flag and
@@ -1402,46 +1437,58 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
       hipLaunchKernelGGL(k_match_scan_mfma, dim3(sgrid.x), dim3(MF_NT), 0, s, M, (uint32_t *)m->d_topk.p, (const uint32_t *)rec, (const uint32_t *)keyrec, (const uint32_t *)pairflag);
   }
   const int mf = mfma && !fused ? 1 : 0;
-#define LAUNCH_MATCH(KT, LC)                                                                                              \
-  do {                                                                                                                    \
-    if (force == SCAN_WALK) {}                                                                                            \
-    else if (fuse) hipLaunchKernelGGL((k_match_scan<KT, SCAN_FUSE>), sgrid, dim3(MATCH_NT), 0, s, M, (KT::T *)m->d_topk.p, slice_stride, force, 0, (const uint32_t *)nullptr);             \
-    else if (M.qside) hipLaunchKernelGGL((k_match_scan<KT, SCAN_FISHEYE>), sgrid, dim3(MATCH_NT), 0, s, M, (KT::T *)m->d_topk.p, slice_stride, force, 0, (const uint32_t *)nullptr);  \
-    else if (M.u_right) hipLaunchKernelGGL((k_match_scan<KT, SCAN_UR>), sgrid, dim3(MATCH_NT), 0, s, M, (KT::T *)m->d_topk.p, slice_stride, force, 0, (const uint32_t *)nullptr);     \
-    else hipLaunchKernelGGL((k_match_scan<KT, SCAN_PLAIN>), sgrid, dim3(MATCH_NT), 0, s, M, (KT::T *)m->d_topk.p, slice_stride, force, mf, (const uint32_t *)pairflag);                 \
-    if (nslices > 1 && force != SCAN_WALK) hipLaunchKernelGGL((k_topk_merge<KT>), dim3(qblocks, npairs), dim3(MATCH_NT), 0, s, M, (KT::T *)m->d_topk.p, slice_stride, nslices, force); \
-    if (prof) MCHECK(m, hipEventRecord(pev[1], s));                                                                     \
-    if (init_th_low >= 0)                                                                                                 \
-      hipLaunchKernelGGL((k_init_resolve<KT>), dim3(npairs), dim3(64), 2 * (size_t)maxn + 16, s, M, (const KT::T *)m->d_topk.p, init_th_low); \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((k_match_resolve<KT, LC>), dim3(npairs), rblock, lds, s, M, (const KT::T *)m->d_topk.p, maxn, force, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr);   \
-  } while (0)
+  // scan (+ merge of the slices), then the resolve: key width KT, candidates in LDS or not (LC)
+  auto match = [&](auto kt, auto lc) -> int {
+    using KT = decltype(kt);
+    constexpr bool LC = decltype(lc)::value;
+    typename KT::T *topk = (typename KT::T *)m->d_topk.p;
+    if (force != SCAN_WALK) {
+      if (o.fuse) hipLaunchKernelGGL((k_match_scan<KT, SCAN_FUSE>), sgrid, dim3(MATCH_NT), 0, s, M, topk, slice_stride, force, 0, (const uint32_t *)nullptr);
+      else if (M.qside) hipLaunchKernelGGL((k_match_scan<KT, SCAN_FISHEYE>), sgrid, dim3(MATCH_NT), 0, s, M, topk, slice_stride, force, 0, (const uint32_t *)nullptr);
+      else if (M.u_right) hipLaunchKernelGGL((k_match_scan<KT, SCAN_UR>), sgrid, dim3(MATCH_NT), 0, s, M, topk, slice_stride, force, 0, (const uint32_t *)nullptr);
+      else hipLaunchKernelGGL((k_match_scan<KT, SCAN_PLAIN>), sgrid, dim3(MATCH_NT), 0, s, M, topk, slice_stride, force, mf, (const uint32_t *)pairflag);
+      if (nslices > 1) hipLaunchKernelGGL((k_topk_merge<KT>), dim3(qblocks, npairs), dim3(MATCH_NT), 0, s, M, topk, slice_stride, nslices, force);
+    }
+    if (prof) MCHECK(m, hipEventRecord(pev[1], s));
+    if (o.init_th_low >= 0)
+      hipLaunchKernelGGL((k_init_resolve<KT>), dim3(npairs), dim3(64), 2 * (size_t)maxn + 16, s, M, (const typename KT::T *)topk, o.init_th_low);
+    else
+      hipLaunchKernelGGL((k_match_resolve<KT, LC>), dim3(npairs), rblock, lds, s, M, (const typename KT::T *)topk, maxn, force, (const uint32_t *)nullptr,
+                         (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    return 0;
+  };
   if (fused) {   // Key32, candidates in LDS: the scan launches as above (they return at once for fused pairs), then the fused resolve
     hipLaunchKernelGGL((k_match_scan<Key32, SCAN_PLAIN>), sgrid, dim3(MATCH_NT), 0, s, M, (Key32::T *)m->d_topk.p, slice_stride, force, mf, (const uint32_t *)pairflag);
     if (prof) MCHECK(m, hipEventRecord(pev[1], s));
     hipLaunchKernelGGL((k_match_resolve<Key32, true, true>), dim3(npairs), rblock, lds, s, M, (const Key32::T *)m->d_topk.p, maxn, force, (const uint32_t *)rec,
                        (const uint32_t *)keyrec, (const uint32_t *)pairflag);
-  } else if (k32) { if (ldscand) LAUNCH_MATCH(Key32, true); else LAUNCH_MATCH(Key32, false); }
-  else     { if (ldscand) LAUNCH_MATCH(Key64, true); else LAUNCH_MATCH(Key64, false); }
-#undef LAUNCH_MATCH
+  } else {
+    const int rc = k32 ? (ldscand ? match(Key32(), std::true_type()) : match(Key32(), std::false_type()))
+                       : (ldscand ? match(Key64(), std::true_type()) : match(Key64(), std::false_type()));
+    if (rc < 0) return rc;
+  }
   if (prof) { MCHECK(m, hipEventRecord(pev[2], s)); m->prof_head++; m->ms_valid = true; }
   MCHECK(m, hipGetLastError());
   return 0;
 }
 
-// host-pointer fisheye-stereo options of one search (see MatchProblemSet)
-struct StereoExt { int nleft; const int32_t *partner; const uint8_t *qside; int couple; int serial; int init_th_low = -1; const float *fuse_inv_sigma2 = nullptr; };
-
-static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist, int use_second,
-                       int32_t *slot, uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist, const StereoExt *ext);
-
-int orbm_search_by_projection(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist,
-                              int use_second, int32_t *slot, uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist) {
-  return search_host(m, f, q, nnratio, th_dist, use_second, slot, slot_obs, match_of_query, best_dist, nullptr);
+int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int frame_stride, const int32_t *d_frame_n,
+                                           int frame_n_stride, const orbm_queries_t *q, int query_stride,
+                                           const int32_t *d_query_n, int query_n_stride, int npairs, float nnratio,
+                                           int th_dist, int use_second, int32_t *d_slot, uint8_t *d_slot_obs,
+                                           int32_t *d_moq, int32_t *d_bd, int32_t *d_nm, void *stream_) {
+  if (!m) return ORBX_E_ARG;
+  SearchOpts o;
+  o.scan_mode = m->scan_mode;
+  return search_batch(m, f, frame_stride, d_frame_n, frame_n_stride, q, query_stride, d_query_n, query_n_stride, npairs, nnratio, th_dist,
+                      use_second, d_slot, d_slot_obs, d_moq, d_bd, d_nm, (hipStream_t)stream_, o);   // verbatim: NULL is the device's default stream
 }
 
-static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist, int use_second,
-                       int32_t *slot, uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist, const StereoExt *ext) {
+// One host-pointer search: inputs up as one staged block, outputs down as one block, one synchronisation.  partner / qside: host
+// arrays of a fisheye-stereo search, staged here; o carries the rest of its options (o.scan_mode is set here).
+static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist, int use_second, int32_t *slot,
+                       uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist, SearchOpts o = {}, const int32_t *partner = nullptr,
+                       const uint8_t *qside = nullptr) {
   if (!m || !f || !q || !slot || !slot_obs) return ORBX_E_ARG;
   const int n = f->n, nq = q->nq;
   if (n < 0 || nq < 0) return ORBX_E_ARG;
@@ -1451,63 +1498,25 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
   }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  // All inputs travel as ONE pinned block -> one H2D copy, all outputs as one block -> one D2H copy, one synchronisation
-  // (a dozen pageable copies would each stage and synchronise on their own).
-  struct Part { const void *src; size_t bytes, off; };
-  size_t total = 0;
-  auto part = [&](const void *src, size_t bytes) { Part p{src, bytes, total}; total += (bytes + 255) & ~(size_t)255; return p; };
-  const Part pKp = part(f->keys_un, sizeof(orbx_keypoint_t) * (size_t)n), pDesc = part(f->descriptors, 32 * (size_t)n);
-  const Part pUr = part(f->u_right, f->u_right ? sizeof(float) * (size_t)n : 0);
-  const Part pQd = part(q->descriptors, 32 * (size_t)nq), pQu = part(q->u, sizeof(float) * (size_t)nq), pQv = part(q->v, sizeof(float) * (size_t)nq);
-  const Part pQr = part(q->radius, sizeof(float) * (size_t)nq), pQur = part(q->u_r, q->u_r ? sizeof(float) * (size_t)nq : 0);
-  const Part pMinl = part(q->min_level, sizeof(int32_t) * (size_t)nq), pMaxl = part(q->max_level, sizeof(int32_t) * (size_t)nq);
-  const Part pFl = part(q->flags, q->flags ? (size_t)nq : 0);
-  const Part pPartner = part(ext ? ext->partner : nullptr, ext && ext->partner ? sizeof(int32_t) * (size_t)n : 0);
-  const Part pSide = part(ext ? ext->qside : nullptr, ext && ext->qside ? (size_t)nq : 0);
-  const size_t in_total = total;
-  // in/out and out-only arrays behind the inputs (same device block; downloaded as one range)
-  const size_t out_off = total;
-  const Part pSlot = part(slot, sizeof(int32_t) * (size_t)n), pSobs = part(slot_obs, (size_t)n);
-  const size_t upload_total = total;
-  const Part pMoq = part(nullptr, sizeof(int32_t) * (size_t)nq), pBd = part(nullptr, sizeof(int32_t) * (size_t)nq), pNm = part(nullptr, sizeof(int32_t));
-  const Part pAny = part(nullptr, ext && ext->couple == 2 ? (size_t)nq : 0);
-  (void)in_total;
-  if (m->pin_bytes < total) {
-    if (m->pin) (void)hipHostFree(m->pin);
-    m->pin = nullptr; m->pin_bytes = 0;
-    MCHECK(m, hipHostMalloc(&m->pin, 2 * total, hipHostMallocDefault));   // grown rarely: a re-allocation costs tens of milliseconds
-    m->pin_bytes = 2 * total;
-  }
-  MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
-  uint8_t *hp = (uint8_t *)m->pin, *dp = (uint8_t *)m->d_block.p;
-  for (const Part *p : {&pKp, &pDesc, &pUr, &pQd, &pQu, &pQv, &pQr, &pQur, &pMinl, &pMaxl, &pFl, &pPartner, &pSide, &pSlot, &pSobs})
-    if (p->bytes) memcpy(hp + p->off, p->src, p->bytes);
-  MCHECK(m, hipMemcpyAsync(dp, hp, upload_total, hipMemcpyHostToDevice, s));
-  m->ext = {};
-  if (ext) {
-    m->ext.nleft = ext->nleft;
-    m->ext.partner = ext->partner ? (const int32_t *)(dp + pPartner.off) : nullptr;
-    m->ext.qside = ext->qside ? (const uint8_t *)(dp + pSide.off) : nullptr;
-    m->ext.couple = ext->couple;
-    m->ext.serial = ext->serial;
-    m->ext.qany = ext->couple == 2 ? (uint8_t *)(dp + pAny.off) : nullptr;
-    m->ext.init_th_low = ext->init_th_low;
-    m->ext.fuse_inv_sigma2 = ext->fuse_inv_sigma2;   // host array of 16 floats, copied into the kernel arguments at launch
-  }
+  const size_t fn = sizeof(float) * (size_t)n, fq = sizeof(float) * (size_t)nq, iq = sizeof(int32_t) * (size_t)nq;
+  // the inputs, then the in/out and out-only arrays (downloaded as one range)
+  enum { KP, DESC, UR, QD, QU, QV, QR, QUR, MINL, MAXL, FL, PARTNER, SIDE, SLOT, SOBS, MOQ, BD, NM, ANY, NPARTS };
+  void *d[NPARTS];
+  const int rc = stage(m, s, {{f->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {f->descriptors, 32 * (size_t)n}, {f->u_right, f->u_right ? fn : 0},
+                              {q->descriptors, 32 * (size_t)nq}, {q->u, fq}, {q->v, fq}, {q->radius, fq}, {q->u_r, q->u_r ? fq : 0},
+                              {q->min_level, iq}, {q->max_level, iq}, {q->flags, q->flags ? (size_t)nq : 0},
+                              {partner, partner ? sizeof(int32_t) * (size_t)n : 0}, {qside, qside ? (size_t)nq : 0},
+                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n},
+                              {nullptr, iq}, {nullptr, iq}, {nullptr, sizeof(int32_t)}, {nullptr, o.couple == 2 ? (size_t)nq : 0}}, d, true);
+  if (rc < 0) return rc;
+  o.partner = (const int32_t *)d[PARTNER]; o.qside = (const uint8_t *)d[SIDE]; o.qany = (uint8_t *)d[ANY];
   orbm_frame_t df = *f;
-  df.keys_un = (const orbx_keypoint_t *)(dp + pKp.off);
-  df.descriptors = dp + pDesc.off;
-  df.u_right = f->u_right ? (const float *)(dp + pUr.off) : nullptr;
+  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
   orbm_queries_t dq = *q;
-  dq.descriptors = dp + pQd.off;
-  dq.u = (const float *)(dp + pQu.off);
-  dq.v = (const float *)(dp + pQv.off);
-  dq.radius = (const float *)(dp + pQr.off);
-  dq.u_r = q->u_r ? (const float *)(dp + pQur.off) : nullptr;
-  dq.min_level = (const int32_t *)(dp + pMinl.off);
-  dq.max_level = (const int32_t *)(dp + pMaxl.off);
-  dq.flags = q->flags ? (const uint8_t *)(dp + pFl.off) : nullptr;
+  dq.descriptors = (const uint8_t *)d[QD]; dq.u = (const float *)d[QU]; dq.v = (const float *)d[QV]; dq.radius = (const float *)d[QR];
+  dq.u_r = (const float *)d[QUR]; dq.min_level = (const int32_t *)d[MINL]; dq.max_level = (const int32_t *)d[MAXL]; dq.flags = (const uint8_t *)d[FL];
   // The radii are on the host here: the walk-or-scan decision (pair_walks) is taken now and only the chosen kernels are launched.
+  o.scan_mode = m->scan_mode;
   if (m->scan_mode == SCAN_AUTO) {
     const float iw = (float)ORBM_GRID_COLS / (f->max_x - f->min_x), ih = (float)ORBM_GRID_ROWS / (f->max_y - f->min_y);
     bool big = n > WALK_MAX_N;
@@ -1518,21 +1527,25 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
       const int cy0 = std::max(0, (int)floorf((v - f->min_y - r) * ih)), cy1 = std::min(47, (int)ceilf((v - f->min_y + r) * ih));
       if (cx0 < 64 && cx1 >= 0 && cy0 < 48 && cy1 >= 0 && (cx1 - cx0 + 1) * (cy1 - cy0 + 1) > WALK_MAX_CELLS) big = true;
     }
-    m->next_scan_mode = big ? SCAN_DENSE : SCAN_WALK;
+    o.scan_mode = big ? SCAN_DENSE : SCAN_WALK;
   }
-  int rc = orbm_search_by_projection_batch_device(m, &df, n, nullptr, 0, &dq, nq, nullptr, 0, 1, nnratio, th_dist, use_second,
-                                                  (int32_t *)(dp + pSlot.off), dp + pSobs.off, (int32_t *)(dp + pMoq.off),
-                                                  (int32_t *)(dp + pBd.off), (int32_t *)(dp + pNm.off), s);
-  if (rc < 0) return rc;
-  MCHECK(m, hipMemcpyAsync(hp + out_off, dp + out_off, pNm.off + sizeof(int32_t) - out_off, hipMemcpyDeviceToHost, s));
+  const int rs = search_batch(m, &df, n, nullptr, 0, &dq, nq, nullptr, 0, 1, nnratio, th_dist, use_second, (int32_t *)d[SLOT], (uint8_t *)d[SOBS],
+                              (int32_t *)d[MOQ], (int32_t *)d[BD], (int32_t *)d[NM], s, o);
+  if (rs < 0) return rs;
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[SLOT]), d[SLOT], (uint8_t *)d[NM] + sizeof(int32_t) - (uint8_t *)d[SLOT], hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
-  memcpy(slot, hp + pSlot.off, pSlot.bytes);
-  memcpy(slot_obs, hp + pSobs.off, pSobs.bytes);
-  if (match_of_query) memcpy(match_of_query, hp + pMoq.off, pMoq.bytes);
-  if (best_dist) memcpy(best_dist, hp + pBd.off, pBd.bytes);
+  memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
+  memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
+  if (match_of_query) memcpy(match_of_query, mirror_of(m, d[MOQ]), iq);
+  if (best_dist) memcpy(best_dist, mirror_of(m, d[BD]), iq);
   int32_t nm = 0;
-  memcpy(&nm, hp + pNm.off, sizeof(nm));
+  memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
   return nm;
+}
+
+int orbm_search_by_projection(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist,
+                              int use_second, int32_t *slot, uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist) {
+  return search_host(m, f, q, nnratio, th_dist, use_second, slot, slot_obs, match_of_query, best_dist);
 }
 
 // cv::Mat products of ORBmatcher.cc:2038-2047, :2072 restated: a 3x3 * 3x1 `A*B + C` MatExpr is a single
@@ -1545,19 +1558,17 @@ static void mat3_mul_add(const float *R, const float *x, const float *t, float *
   }
 }
 
-int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
-                                                      int frame_n_stride, const orbm_last_frame_t *last0, int last_stride,
-                                                      const int32_t *d_last_n, int last_n_stride, int npairs, const float *sf, int nlevels,
-                                                      int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
-                                                      int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
-                                                      int32_t *d_nmatches, void *stream_) {
+static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
+                                  const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n, int last_n_stride, int npairs,
+                                  const float *sf, int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
+                                  int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches, hipStream_t s,
+                                  int scan_mode) {
   if (!m || !cur0 || !last0 || !sf || !cam_params || npairs <= 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
   if (!last0->has_mp || !last0->Xw || !last0->mpdesc || !last0->last_keys || !last0->Tcw || !last0->Tlw) return ORBX_E_ARG;
   const int maxq = d_last_n ? last_stride : last0->n;
   if (maxq <= 0 || last_stride < maxq) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
-  hipStream_t s = (hipStream_t)stream_;
   // scratch: the query arrays the projection kernel writes (29 B per query) - grows on demand, not on the steady-state path
   const size_t nqa = (size_t)(npairs - 1) * last_stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
   const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
@@ -1586,8 +1597,10 @@ int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_fram
   orbm_queries_t q;
   q.nq = last0->n; q.descriptors = last0->mpdesc; q.u = P.qu; q.v = P.qv; q.radius = P.qr;
   q.min_level = P.qminl; q.max_level = P.qmaxl; q.u_r = cur0->u_right ? P.qur : nullptr; q.flags = P.qflags;
-  int rc = orbm_search_by_projection_batch_device(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, last_stride, d_last_n, last_n_stride, npairs,
-                                                  0.f, ORBM_TH_HIGH, 0, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s);   // :2148-2162
+  SearchOpts o;
+  o.scan_mode = scan_mode;
+  int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, last_stride, d_last_n, last_n_stride, npairs, 0.f, ORBM_TH_HIGH, 0,
+                        d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // :2148-2162
   if (rc < 0) return rc;
   if (checkOri) {                                                                                                            // :2177-2185, :2263-2286
     RotPruneParams R;
@@ -1600,6 +1613,18 @@ int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_fram
   }
   MCHECK(m, hipGetLastError());
   return 0;
+}
+
+int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                                      int frame_n_stride, const orbm_last_frame_t *last0, int last_stride,
+                                                      const int32_t *d_last_n, int last_n_stride, int npairs, const float *sf, int nlevels,
+                                                      int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
+                                                      int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
+                                                      int32_t *d_nmatches, void *stream_) {
+  if (!m) return ORBX_E_ARG;
+  return search_last_frame_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, last0, last_stride, d_last_n, last_n_stride, npairs, sf, nlevels,
+                                 cam_type, cam_params, mb, mbf, th, bMono, checkOri, d_slot, d_slot_obs, d_moq, d_nmatches, (hipStream_t)stream_,
+                                 m->scan_mode);
 }
 
 int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, int nLast,
@@ -1618,62 +1643,42 @@ int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, con
     if (has_mp[i] && (last_keys[i].octave < 0 || last_keys[i].octave >= nlevels)) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  // one pinned block up, one block down, one synchronisation (as search_host); projection, search and pruning on the device
-  struct Part { const void *src; size_t bytes, off; };
-  size_t total = 0;
-  auto part = [&](const void *src, size_t bytes) { Part p{src, bytes, total}; total += (bytes + 255) & ~(size_t)255; return p; };
-  const Part pKp = part(cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n), pDesc = part(cur->descriptors, 32 * (size_t)n);
-  const Part pUr = part(cur->u_right, cur->u_right ? sizeof(float) * (size_t)n : 0);
-  const Part pHas = part(has_mp, (size_t)nLast), pXw = part(Xw, 3 * sizeof(float) * (size_t)nLast), pMd = part(mpdesc, 32 * (size_t)nLast);
-  const Part pLk = part(last_keys, sizeof(orbx_keypoint_t) * (size_t)nLast), pObs = part(obs, obs ? (size_t)nLast : 0);
-  const Part pTc = part(Tcw, 16 * sizeof(float)), pTl = part(Tlw, 16 * sizeof(float));
-  const size_t out_off = total;
-  const Part pSlot = part(slot, sizeof(int32_t) * (size_t)n), pSobs = part(slot_obs, (size_t)n);
-  const size_t upload_total = total;
-  const Part pNm = part(nullptr, sizeof(int32_t));
-  if (m->pin_bytes < total) {
-    if (m->pin) (void)hipHostFree(m->pin);
-    m->pin = nullptr; m->pin_bytes = 0;
-    MCHECK(m, hipHostMalloc(&m->pin, 2 * total, hipHostMallocDefault));   // grown rarely: a re-allocation costs tens of milliseconds
-    m->pin_bytes = 2 * total;
-  }
-  MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
-  uint8_t *hp = (uint8_t *)m->pin, *dp = (uint8_t *)m->d_block.p;
-  for (const Part *p : {&pKp, &pDesc, &pUr, &pHas, &pXw, &pMd, &pLk, &pObs, &pTc, &pTl, &pSlot, &pSobs})
-    if (p->bytes) memcpy(hp + p->off, p->src, p->bytes);
-  MCHECK(m, hipMemcpyAsync(dp, hp, upload_total, hipMemcpyHostToDevice, s));
+  // one staged block up, one block down, one synchronisation (as search_host); projection, search and pruning on the device
+  enum { KP, DESC, UR, HAS, XW, MD, LK, OBS, TC, TL, SLOT, SOBS, NM, NPARTS };
+  void *d[NPARTS];
+  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
+                              {cur->u_right, cur->u_right ? sizeof(float) * (size_t)n : 0}, {has_mp, (size_t)nLast}, {Xw, 3 * sizeof(float) * (size_t)nLast},
+                              {mpdesc, 32 * (size_t)nLast}, {last_keys, sizeof(orbx_keypoint_t) * (size_t)nLast}, {obs, obs ? (size_t)nLast : 0},
+                              {Tcw, 16 * sizeof(float)}, {Tlw, 16 * sizeof(float)},
+                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t)}}, d, true);
+  if (rc < 0) return rc;
   orbm_frame_t df = *cur;
-  df.keys_un = (const orbx_keypoint_t *)(dp + pKp.off);
-  df.descriptors = dp + pDesc.off;
-  df.u_right = cur->u_right ? (const float *)(dp + pUr.off) : nullptr;
+  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
   orbm_last_frame_t dl;
   memset(&dl, 0, sizeof(dl));
   dl.n = nLast;
-  dl.has_mp = dp + pHas.off; dl.Xw = (const float *)(dp + pXw.off); dl.mpdesc = dp + pMd.off;
-  dl.last_keys = (const orbx_keypoint_t *)(dp + pLk.off);
-  dl.obs = obs ? dp + pObs.off : nullptr;
-  dl.Tcw = (const float *)(dp + pTc.off); dl.Tlw = (const float *)(dp + pTl.off);
-  m->ext = {};
+  dl.has_mp = (const uint8_t *)d[HAS]; dl.Xw = (const float *)d[XW]; dl.mpdesc = (const uint8_t *)d[MD];
+  dl.last_keys = (const orbx_keypoint_t *)d[LK]; dl.obs = (const uint8_t *)d[OBS]; dl.Tcw = (const float *)d[TC]; dl.Tlw = (const float *)d[TL];
   // The windows are th * scale factor of the last keypoint's octave (ORBmatcher.cc:2109): known here, so the walk-or-scan decision
   // is taken on the host from the largest one (an upper bound of every query's cell window) and only the chosen kernels are launched
+  int scan_mode = m->scan_mode;
   if (m->scan_mode == SCAN_AUTO && n <= WALK_MAX_N && cur->max_x > cur->min_x && cur->max_y > cur->min_y) {
     float rmax = 0.f;
     for (int i = 0; i < nLast; i++)
       if (has_mp[i]) rmax = std::max(rmax, th * sf[last_keys[i].octave]);
     const float iw = (float)ORBM_GRID_COLS / (cur->max_x - cur->min_x), ih = (float)ORBM_GRID_ROWS / (cur->max_y - cur->min_y);
     const long long cx = std::min<long long>(ORBM_GRID_COLS, (long long)ceilf(2.f * rmax * iw) + 2), cy = std::min<long long>(ORBM_GRID_ROWS, (long long)ceilf(2.f * rmax * ih) + 2);
-    if (cx * cy <= WALK_MAX_CELLS) m->next_scan_mode = SCAN_WALK;
+    if (cx * cy <= WALK_MAX_CELLS) scan_mode = SCAN_WALK;
   }
-  int rc = orbm_search_by_projection_last_frame_batch_device(m, &df, n, nullptr, 0, &dl, nLast, nullptr, 0, 1, sf, nlevels, cam_type, cam_params, mb, mbf,
-                                                             th, bMono, checkOri, (int32_t *)(dp + pSlot.off), dp + pSobs.off, nullptr,
-                                                             (int32_t *)(dp + pNm.off), s);
-  if (rc < 0) return rc;
-  MCHECK(m, hipMemcpyAsync(hp + out_off, dp + out_off, pNm.off + sizeof(int32_t) - out_off, hipMemcpyDeviceToHost, s));
+  const int rs = search_last_frame_batch(m, &df, n, nullptr, 0, &dl, nLast, nullptr, 0, 1, sf, nlevels, cam_type, cam_params, mb, mbf, th, bMono,
+                                         checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
+  if (rs < 0) return rs;
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[SLOT]), d[SLOT], (uint8_t *)d[NM] + sizeof(int32_t) - (uint8_t *)d[SLOT], hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
-  memcpy(slot, hp + pSlot.off, pSlot.bytes);
-  memcpy(slot_obs, hp + pSobs.off, pSobs.bytes);
+  memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
+  memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
   int32_t nm = 0;
-  memcpy(&nm, hp + pNm.off, sizeof(nm));
+  memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
   return nm;
 }
 
@@ -1707,8 +1712,9 @@ int orbm_search_by_projection_fisheye(orbm_t *m, const orbm_frame_t *f, int n_le
     const uint8_t fl = q->flags ? q->flags[i] : (uint8_t)3;
     if ((fl & 1) && !(fl & 2)) release = true;
   }
-  StereoExt ext{n_left, anyp ? partner.data() : nullptr, side.data(), 1, (anyp && release) ? 1 : 0};
-  return search_host(m, f, q, nnratio, th_dist, 1, slot, slot_obs, match_of_query, best_dist, &ext);
+  SearchOpts o;
+  o.nleft = n_left; o.couple = 1; o.serial = (anyp && release) ? 1 : 0;
+  return search_host(m, f, q, nnratio, th_dist, 1, slot, slot_obs, match_of_query, best_dist, o, anyp ? partner.data() : nullptr, side.data());
 }
 
 int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const float *sf, int nlevels,
@@ -1767,8 +1773,9 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
   q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = nullptr; q.flags = flags.data();
   orbm_frame_t f = *cur;
   f.u_right = nullptr;  // Nleft != -1: no mvuRight test (:2139)
-  StereoExt ext{n_left, nullptr, side.data(), 2, 0};
-  int nmatches = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot, slot_obs, moq.data(), nullptr, &ext);
+  SearchOpts o;
+  o.nleft = n_left; o.couple = 2;
+  int nmatches = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot, slot_obs, moq.data(), nullptr, o, nullptr, side.data());
   if (nmatches < 0) return nmatches;
   for (int j = 0; j < nq; j++)  // the device stored query indices; the caller's ids are last-frame indices (in order: last writer wins)
     if (moq[j] >= 0) slot[moq[j]] = j >> 1;
@@ -1962,11 +1969,11 @@ static int fuse_core(orbm_t *m, const orbm_frame_t *kf, const float *sf, const f
   if (!chi2) f.u_right = nullptr;
   std::vector<int32_t> slot((size_t)std::max(kf->n, 1), -1);
   std::vector<uint8_t> sobs((size_t)std::max(kf->n, 1), 0);
-  float is2[16] = {0};
-  StereoExt ext{};
-  ext.nleft = kf->n;
-  if (chi2) { for (int l = 0; l < nlevels && l < 16; l++) is2[l] = inv_sigma2[l]; ext.fuse_inv_sigma2 = is2; }
-  const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_LOW, 0, slot.data(), sobs.data(), best_idx, best_dist, &ext);
+  SearchOpts o;
+  o.nleft = kf->n;
+  o.fuse = chi2;
+  if (chi2) for (int l = 0; l < nlevels && l < 16; l++) o.inv_sigma2[l] = inv_sigma2[l];
+  const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_LOW, 0, slot.data(), sobs.data(), best_idx, best_dist, o);
   if (rc < 0) return rc;
   int nFused = 0;
   for (int i = 0; i < nP; i++) nFused += best_idx[i] >= 0 ? 1 : 0;           // bestDist <= TH_LOW, :1622 / :1767
@@ -2096,7 +2103,7 @@ int orbm_search_by_sim3(orbm_t *m, const orbm_frame_t *kf1, const float *sf1, in
     f.u_right = nullptr;
     std::vector<int32_t> slot((size_t)r.kf->n, -1);
     std::vector<uint8_t> sobs((size_t)r.kf->n, 0);
-    const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot.data(), sobs.data(), r.S->best.data(), nullptr, nullptr);  // :1895, :1967
+    const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot.data(), sobs.data(), r.S->best.data(), nullptr);  // :1895, :1967
     if (rc < 0) return rc;
   }
   int nFound = 0;                                                              // :1973-1987
@@ -2166,20 +2173,18 @@ static int triangulation_candidates(orbm_t *m, const orbm_keyframe_t *k1, const 
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
-  DevBuf *B[] = {&m->d_desc, &m->d_ur, &m->d_qdesc, &m->d_qf[0], &m->d_qf[1], &m->d_qfl, &m->d_qi[0], &m->d_qi[1]};
-  const void *src[] = {k1->descriptors, k1->u_right, k2->descriptors, k2->keys_un, k2->u_right, k2->has_mappoint, k2->node_idx, items.data()};
-  const size_t bytes[] = {32 * (size_t)k1->n, sizeof(float) * (size_t)k1->n, 32 * (size_t)k2->n, sizeof(orbx_keypoint_t) * (size_t)k2->n,
-                          sizeof(float) * (size_t)k2->n, (size_t)k2->n, sizeof(int32_t) * nidx2, sizeof(TriItem) * items.size()};
-  for (int i = 0; i < 8; i++) {
-    MCHECK(m, B[i]->reserve(std::max<size_t>(bytes[i], 4)));
-    MCHECK(m, hipMemcpyAsync(B[i]->p, src[i], bytes[i], hipMemcpyHostToDevice, s));
-  }
+  enum { DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, NPARTS };
+  void *d[NPARTS];
+  const int rs = stage(m, s, {{k1->descriptors, 32 * (size_t)k1->n}, {k1->u_right, sizeof(float) * (size_t)k1->n}, {k2->descriptors, 32 * (size_t)k2->n},
+                              {k2->keys_un, sizeof(orbx_keypoint_t) * (size_t)k2->n}, {k2->u_right, sizeof(float) * (size_t)k2->n},
+                              {k2->has_mappoint, (size_t)k2->n}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * items.size()}}, d);
+  if (rs < 0) return rs;
   TriCandParams T;
   memset(&T, 0, sizeof(T));
-  T.desc1 = (const uint32_t *)m->d_desc.p; T.ur1 = (const float *)m->d_ur.p;
-  T.desc2 = (const uint32_t *)m->d_qdesc.p; T.kp2 = (const float *)m->d_qf[0].p; T.ur2 = (const float *)m->d_qf[1].p;
-  T.hasmp2 = (const uint8_t *)m->d_qfl.p; T.node_idx2 = (const int32_t *)m->d_qi[0].p;
-  T.items = (const TriItem *)m->d_qi[1].p; T.nitems = (int)items.size();
+  T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
+  T.desc2 = (const uint32_t *)d[DESC2]; T.kp2 = (const float *)d[KP2]; T.ur2 = (const float *)d[UR2];
+  T.hasmp2 = (const uint8_t *)d[HASMP2]; T.node_idx2 = (const int32_t *)d[NODE_IDX2];
+  T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)items.size();
   for (int l = 0; l < ORBX_MAX_LEVELS; l++) T.sf2[l] = l < k2->nlevels ? k2->scale_factors[l] : 0.f;
   T.epx = ep_x; T.epy = ep_y; T.epipole_gate = epipole_gate; T.bOnlyStereo = bOnlyStereo;
   const size_t ni = items.size();
@@ -2187,10 +2192,10 @@ static int triangulation_candidates(orbm_t *m, const orbm_keyframe_t *k1, const 
   std::vector<uint32_t> keys;
   size_t cap = std::max<size_t>(16 * ni, 1024);
   for (int attempt = 0; attempt < 2; attempt++) {   // the second attempt knows the exact total
-    MCHECK(m, m->scratch[0].reserve(sizeof(int32_t) * (2 * ni + 1)));
-    MCHECK(m, m->scratch[1].reserve(sizeof(uint32_t) * cap));
-    T.item_off = (int32_t *)m->scratch[0].p; T.item_cnt = T.item_off + ni; T.total = T.item_cnt + ni;
-    T.keys = (uint32_t *)m->scratch[1].p; T.cap = (int)std::min<size_t>(cap, 0x7fffffff);
+    MCHECK(m, m->d_tri_count.reserve(sizeof(int32_t) * (2 * ni + 1)));
+    MCHECK(m, m->d_tri_keys.reserve(sizeof(uint32_t) * cap));
+    T.item_off = (int32_t *)m->d_tri_count.p; T.item_cnt = T.item_off + ni; T.total = T.item_cnt + ni;
+    T.keys = (uint32_t *)m->d_tri_keys.p; T.cap = (int)std::min<size_t>(cap, 0x7fffffff);
     MCHECK(m, hipMemsetAsync(T.total, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(k_triangulation_candidates, dim3((T.nitems + 3) / 4), dim3(256), 0, s, T);
     MCHECK(m, hipGetLastError());
@@ -2306,27 +2311,26 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
   if (!items.empty()) {
     MCHECK(m, hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
-    DevBuf *B[] = {&m->d_kp, &m->d_desc, &m->d_ur, &m->d_qdesc, &m->d_qf[0], &m->d_qf[1], &m->d_qfl, &m->d_qi[0], &m->d_qi[1], &m->d_moq};
-    const void *src[] = {k1->keys_un, k1->descriptors, k1->u_right, k2->descriptors, k2->keys_un, k2->u_right, k2->has_mappoint, k2->node_idx, items.data(), nullptr};
-    const size_t bytes[] = {sizeof(orbx_keypoint_t) * (size_t)k1->n, 32 * (size_t)k1->n, sizeof(float) * (size_t)k1->n, 32 * (size_t)k2->n,
-                            sizeof(orbx_keypoint_t) * (size_t)k2->n, sizeof(float) * (size_t)k2->n, (size_t)k2->n, sizeof(int32_t) * nidx2,
-                            sizeof(TriItem) * items.size(), sizeof(int32_t) * (size_t)k1->n};
-    for (int i = 0; i < 10; i++) {
-      MCHECK(m, B[i]->reserve(std::max<size_t>(bytes[i], 4)));
-      if (src[i]) MCHECK(m, hipMemcpyAsync(B[i]->p, src[i], bytes[i], hipMemcpyHostToDevice, s));
-    }
-    MCHECK(m, hipMemsetAsync(m->d_moq.p, 0xff, bytes[9], s));
-    T.kp1 = (const float *)m->d_kp.p; T.desc1 = (const uint32_t *)m->d_desc.p; T.ur1 = (const float *)m->d_ur.p;
-    T.desc2 = (const uint32_t *)m->d_qdesc.p; T.kp2 = (const float *)m->d_qf[0].p; T.ur2 = (const float *)m->d_qf[1].p;
-    T.hasmp2 = (const uint8_t *)m->d_qfl.p; T.node_idx2 = (const int32_t *)m->d_qi[0].p;
-    T.items = (const TriItem *)m->d_qi[1].p; T.nitems = (int)items.size();
+    const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes], out_bytes = sizeof(int32_t) * (size_t)k1->n;
+    enum { KP1, DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, MATCHES12, NPARTS };
+    void *d[NPARTS];
+    const int rs = stage(m, s, {{k1->keys_un, sizeof(orbx_keypoint_t) * (size_t)k1->n}, {k1->descriptors, 32 * (size_t)k1->n},
+                                {k1->u_right, sizeof(float) * (size_t)k1->n}, {k2->descriptors, 32 * (size_t)k2->n},
+                                {k2->keys_un, sizeof(orbx_keypoint_t) * (size_t)k2->n}, {k2->u_right, sizeof(float) * (size_t)k2->n},
+                                {k2->has_mappoint, (size_t)k2->n}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * items.size()},
+                                {nullptr, out_bytes}}, d);
+    if (rs < 0) return rs;
+    MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, out_bytes, s));
+    T.kp1 = (const float *)d[KP1]; T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
+    T.desc2 = (const uint32_t *)d[DESC2]; T.kp2 = (const float *)d[KP2]; T.ur2 = (const float *)d[UR2];
+    T.hasmp2 = (const uint8_t *)d[HASMP2]; T.node_idx2 = (const int32_t *)d[NODE_IDX2];
+    T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)items.size();
     for (int l = 0; l < k2->nlevels; l++) { T.sf2[l] = k2->scale_factors[l]; T.sigma2_2[l] = k2->level_sigma2[l]; }
     T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
-    T.matches12 = (int32_t *)m->d_moq.p;
+    T.matches12 = (int32_t *)d[MATCHES12];
     hipLaunchKernelGGL(k_triangulation_match, dim3((T.nitems + 3) / 4), dim3(256), 0, s, T);
     MCHECK(m, hipGetLastError());
-    MCHECK(m, hipMemcpyAsync(matches12, m->d_moq.p, bytes[9], hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
     MCHECK(m, hipStreamSynchronize(s));
     for (int i = 0; i < k1->n; i++) nmatches += matches12[i] >= 0;
   }
@@ -2384,9 +2388,9 @@ int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm
   f.u_right = nullptr;
   std::vector<int32_t> slot((size_t)f2->n, -1);
   std::vector<uint8_t> sobs((size_t)f2->n, 0);
-  StereoExt ext{};
-  ext.nleft = f2->n; ext.init_th_low = ORBM_TH_LOW;
-  const int rc = search_host(m, &f, &q, nnratio, ORBM_TH_LOW, 1, slot.data(), sobs.data(), acc.data(), nullptr, &ext);
+  SearchOpts o;
+  o.nleft = f2->n; o.init_th_low = ORBM_TH_LOW;
+  const int rc = search_host(m, &f, &q, nnratio, ORBM_TH_LOW, 1, slot.data(), sobs.data(), acc.data(), nullptr, o);
   if (rc < 0) return rc;
   // replay of the bookkeeping the device leaves to the host: steals (:781-785) and the rotation histogram (:791-801)
   int nmatches = 0;
@@ -2517,26 +2521,25 @@ static int bow_core(orbm_t *m, const orbm_keyframe_t *kf, const orbm_keyframe_t 
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   const size_t nidxKF = (size_t)kf->node_start[kf->n_nodes], nidxF = (size_t)f->node_start[f->n_nodes];
-  DevBuf *bufs = m->scratch;
-  const size_t sz[8] = {32 * (size_t)kf->n, 32 * (size_t)f->n, (size_t)kf->n, sizeof(int32_t) * nidxKF, sizeof(int32_t) * nidxF,
-                        sizeof(BowItem) * items.size(), sizeof(int32_t) * (size_t)nout, kf_kf ? (size_t)f->n : 0};
-  const void *src[8] = {kf->descriptors, f->descriptors, kf->has_mappoint, kf->node_idx, f->node_idx, items.data(), out, kf_kf ? f->has_mappoint : nullptr};
-  for (int i = 0; i < 8; i++) {
-    MCHECK(m, bufs[i].reserve(std::max<size_t>(sz[i], 4)));
-    if (sz[i]) MCHECK(m, hipMemcpyAsync(bufs[i].p, src[i], sz[i], hipMemcpyHostToDevice, s));
-  }
+  const size_t out_bytes = sizeof(int32_t) * (size_t)nout;
+  enum { DESC_KF, DESC_F, HASMP_KF, NODE_IDX_KF, NODE_IDX_F, ITEMS, OUT, HASMP_F, NPARTS };
+  void *d[NPARTS];
+  const int rs = stage(m, s, {{kf->descriptors, 32 * (size_t)kf->n}, {f->descriptors, 32 * (size_t)f->n}, {kf->has_mappoint, (size_t)kf->n},
+                              {kf->node_idx, sizeof(int32_t) * nidxKF}, {f->node_idx, sizeof(int32_t) * nidxF}, {items.data(), sizeof(BowItem) * items.size()},
+                              {out, out_bytes}, {f->has_mappoint, kf_kf ? (size_t)f->n : 0}}, d);
+  if (rs < 0) return rs;
   BowParams B;
   memset(&B, 0, sizeof(B));
-  B.descKF = (const uint32_t *)bufs[0].p; B.descF = (const uint32_t *)bufs[1].p; B.hasmpKF = (const uint8_t *)bufs[2].p;
-  B.node_idxKF = (const int32_t *)bufs[3].p; B.node_idxF = (const int32_t *)bufs[4].p;
-  B.items = (const BowItem *)bufs[5].p; B.nitems = (int)items.size();
+  B.descKF = (const uint32_t *)d[DESC_KF]; B.descF = (const uint32_t *)d[DESC_F]; B.hasmpKF = (const uint8_t *)d[HASMP_KF];
+  B.node_idxKF = (const int32_t *)d[NODE_IDX_KF]; B.node_idxF = (const int32_t *)d[NODE_IDX_F];
+  B.items = (const BowItem *)d[ITEMS]; B.nitems = (int)items.size();
   B.nnratio = nnratio;
   B.nleftF = nleftF >= 0 ? nleftF : 0x7fffffff;
-  if (kf_kf) { B.match12 = (int32_t *)bufs[6].p; B.hasmpF = (const uint8_t *)bufs[7].p; B.strict = 1; }
-  else B.matchF = (int32_t *)bufs[6].p;
+  if (kf_kf) { B.match12 = (int32_t *)d[OUT]; B.hasmpF = (const uint8_t *)d[HASMP_F]; B.strict = 1; }
+  else B.matchF = (int32_t *)d[OUT];
   hipLaunchKernelGGL(k_bow_match, dim3((B.nitems + 3) / 4), dim3(256), 0, s, B);
   MCHECK(m, hipGetLastError());
-  MCHECK(m, hipMemcpyAsync(out, bufs[6].p, sz[6], hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipMemcpyAsync(out, d[OUT], out_bytes, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   int nmatches = 0;
   for (int i = 0; i < nout; i++) nmatches += out[i] >= 0 ? 1 : 0;
@@ -2586,17 +2589,15 @@ int orbm_distinctive_descriptors(orbm_t *m, int nmp, const int32_t *start, const
     const int n = start[i + 1] - start[i];
     if (n < 0 || n > 64 * DISTINCT_MAXT) { m->err = "ComputeDistinctiveDescriptors: more than 1024 observations of one map point"; return ORBX_E_ARG; }
   }
-  if (total > 0 && !desc) return ORBX_E_ARG;
+  if (start[0] < 0 || (total > 0 && !desc)) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  MCHECK(m, m->d_a.reserve(std::max<size_t>(32 * (size_t)total, 4)));
-  MCHECK(m, m->d_b.reserve(sizeof(int32_t) * (size_t)(nmp + 1)));
-  MCHECK(m, m->d_c.reserve(sizeof(int32_t) * (size_t)nmp));
-  if (total > 0) MCHECK(m, hipMemcpyAsync(m->d_a.p, desc, 32 * (size_t)total, hipMemcpyHostToDevice, s));
-  MCHECK(m, hipMemcpyAsync(m->d_b.p, start, sizeof(int32_t) * (size_t)(nmp + 1), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, s, (const uint32_t *)m->d_a.p, (const int32_t *)m->d_b.p, nmp, (int32_t *)m->d_c.p);
+  void *d[3];   // descriptors, start, best
+  const int rs = stage(m, s, {{desc, 32 * (size_t)total}, {start, sizeof(int32_t) * (size_t)(nmp + 1)}, {nullptr, sizeof(int32_t) * (size_t)nmp}}, d);
+  if (rs < 0) return rs;
+  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, s, (const uint32_t *)d[0], (const int32_t *)d[1], nmp, (int32_t *)d[2]);
   MCHECK(m, hipGetLastError());
-  MCHECK(m, hipMemcpyAsync(best, m->d_c.p, sizeof(int32_t) * (size_t)nmp, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipMemcpyAsync(best, d[2], sizeof(int32_t) * (size_t)nmp, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   return 0;
 }
@@ -2607,17 +2608,16 @@ int orbm_knn_match2(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, int n
   if (nc == 0) { for (int i = 0; i < 2 * nq; i++) { idx2[i] = -1; dist2[i] = -1; } return 0; }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  MCHECK(m, m->d_a.reserve(32 * (size_t)nq));
-  MCHECK(m, m->d_b.reserve(32 * (size_t)nc));
-  MCHECK(m, m->d_c.reserve(sizeof(int32_t) * 4 * (size_t)nq));
-  MCHECK(m, hipMemcpyAsync(m->d_a.p, q, 32 * (size_t)nq, hipMemcpyHostToDevice, s));
-  MCHECK(m, hipMemcpyAsync(m->d_b.p, c, 32 * (size_t)nc, hipMemcpyHostToDevice, s));
-  int32_t *d_idx = (int32_t *)m->d_c.p, *d_dist = d_idx + 2 * (size_t)nq;
+  void *d[3];   // queries, candidates, (idx, dist)
+  const int rs = stage(m, s, {{q, 32 * (size_t)nq}, {c, 32 * (size_t)nc}, {nullptr, sizeof(int32_t) * 4 * (size_t)nq}}, d);
+  if (rs < 0) return rs;
+  const uint32_t *d_q = (const uint32_t *)d[0], *d_c = (const uint32_t *)d[1];
+  int32_t *d_idx = (int32_t *)d[2], *d_dist = d_idx + 2 * (size_t)nq;
   // matrix-pipe form (orb_match_mfma.h) unless the vector-ALU engine is selected; its keys carry the train index in 20 bits
   if (m->hamming_engine >= 1 && nc < (1 << 20))
-    hipLaunchKernelGGL(k_knn2_mfma, dim3((nq + MF_NT - 1) / MF_NT), dim3(MF_NT), 0, s, (const uint32_t *)m->d_a.p, nq, (const uint32_t *)m->d_b.p, nc, d_idx, d_dist);
+    hipLaunchKernelGGL(k_knn2_mfma, dim3((nq + MF_NT - 1) / MF_NT), dim3(MF_NT), 0, s, d_q, nq, d_c, nc, d_idx, d_dist);
   else
-    hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, s, (const uint32_t *)m->d_a.p, nq, (const uint32_t *)m->d_b.p, nc, d_idx, d_dist);
+    hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, s, d_q, nq, d_c, nc, d_idx, d_dist);
   MCHECK(m, hipGetLastError());
   MCHECK(m, hipMemcpyAsync(idx2, d_idx, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipMemcpyAsync(dist2, d_dist, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
@@ -2629,20 +2629,18 @@ int orbm_hamming_matrix(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, i
   if (!m || !q || !c || !dist || nq <= 0 || nc <= 0) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  MCHECK(m, m->d_a.reserve(32 * (size_t)nq));
-  MCHECK(m, m->d_b.reserve(32 * (size_t)nc));
-  MCHECK(m, m->d_c.reserve(sizeof(uint16_t) * (size_t)nq * nc));
-  MCHECK(m, hipMemcpyAsync(m->d_a.p, q, 32 * (size_t)nq, hipMemcpyHostToDevice, s));
-  MCHECK(m, hipMemcpyAsync(m->d_b.p, c, 32 * (size_t)nc, hipMemcpyHostToDevice, s));
+  void *d[3];   // queries, candidates, the nq x nc matrix (downloaded straight to the caller)
+  const int rs = stage(m, s, {{q, 32 * (size_t)nq}, {c, 32 * (size_t)nc}, {nullptr, sizeof(uint16_t) * (size_t)nq * nc}}, d);
+  if (rs < 0) return rs;
+  const uint32_t *d_q = (const uint32_t *)d[0], *d_c = (const uint32_t *)d[1];
+  uint16_t *d_dist = (uint16_t *)d[2];
   constexpr int QSLAB = 128;   // query rows per workgroup of the matrix-pipe form: four tiles behind one expansion of its 256 candidates
   if (m->hamming_engine >= 1 && (nq + QSLAB - 1) / QSLAB <= 65535)
-    hipLaunchKernelGGL(k_hamming_matrix_mfma, dim3((nc + MF_NT - 1) / MF_NT, (nq + QSLAB - 1) / QSLAB), dim3(MF_NT), 0, s, (const uint32_t *)m->d_a.p, nq,
-                       (const uint32_t *)m->d_b.p, nc, (uint16_t *)m->d_c.p, QSLAB);
+    hipLaunchKernelGGL(k_hamming_matrix_mfma, dim3((nc + MF_NT - 1) / MF_NT, (nq + QSLAB - 1) / QSLAB), dim3(MF_NT), 0, s, d_q, nq, d_c, nc, d_dist, QSLAB);
   else
-    hipLaunchKernelGGL(k_hamming_matrix, dim3((nq + 255) / 256), dim3(256), 0, s, (const uint32_t *)m->d_a.p, nq, (const uint32_t *)m->d_b.p, nc,
-                       (uint16_t *)m->d_c.p);
+    hipLaunchKernelGGL(k_hamming_matrix, dim3((nq + 255) / 256), dim3(256), 0, s, d_q, nq, d_c, nc, d_dist);
   MCHECK(m, hipGetLastError());
-  MCHECK(m, hipMemcpyAsync(dist, m->d_c.p, sizeof(uint16_t) * (size_t)nq * nc, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipMemcpyAsync(dist, d_dist, sizeof(uint16_t) * (size_t)nq * nc, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   return 0;
 }

@@ -658,12 +658,15 @@ def test_search_by_bow_fisheye_n3(pkg, oracle, synth, nodes):
         m.close()
 
 
-@pytest.mark.parametrize("npairs", [2, 12])
-def test_batch_pairs_vote_independently(pkg, oracle, synth, npairs):
+@pytest.mark.parametrize("npairs,refused_first", [pytest.param(2, False, id="2"), pytest.param(12, False, id="12"),
+                                                   pytest.param(2, True, id="2-refused_first"), pytest.param(12, True, id="12-refused_first")])
+def test_batch_pairs_vote_independently(pkg, oracle, synth, npairs, refused_first):
     """orbm_search_by_projection_batch_device with frame pairs of BOTH kinds in one launch: even pairs search tracking-sized
     windows (the device vote sends them to k_match_walk and the wide resolve), odd pairs a window covering the frame
     (k_match_scan, chunked resolve).  Every pair must equal the oracle run on that pair alone: the vote is taken per pair and must
-    come out the same in the walk, the scan, the list merge (2 pairs: the sliced scan of few-pair launches) and the resolve."""
+    come out the same in the walk, the scan, the list merge (2 pairs: the sliced scan of few-pair launches) and the resolve.
+    refused_first: the same matcher has first refused a fisheye-stereo search (th_dist 256) and a Fuse (empty keyframe bounds);
+    neither may leave options behind for the batch launch."""
     import ctypes as C
     import torch
     frames, offs = synth.make_stream(4200, npairs + 1)
@@ -697,6 +700,29 @@ def test_batch_pairs_vote_independently(pkg, oracle, synth, npairs):
     nm = torch.zeros((npairs,), dtype=torch.int32, device=dev)
     m = pkg.ORBmatcher(0.8, True)
     try:
+        if refused_first:
+            (k1, d1), (k0, d0) = ext[1], ext[0]
+            n1, nmp = len(k1), len(k0) // 2
+            F = pkg.FrameView(k1, d1, (0.0, 752.0, 0.0, 480.0))
+            l2r = np.arange(n1 // 2, dtype=np.int32)   # left keypoint i <-> right keypoint i: a partner array is staged
+            qd = np.repeat(d0[:nmp], 2, axis=0).copy()
+            qu, qv = np.repeat(k0["x"][:nmp], 2).astype(np.float32), np.repeat(k0["y"][:nmp], 2).astype(np.float32)
+            qr, ql = np.full(2 * nmp, 15.0, np.float32), np.zeros(2 * nmp, np.int32)
+            qs = pkg.QueryStruct(2 * nmp, qd.ctypes.data, qu.ctypes.data, qv.ctypes.data, qr.ctypes.data, ql.ctypes.data, ql.ctypes.data, None, None)
+            fsh, moq_f = F.struct(), np.full(2 * nmp, -1, np.int32)
+            with pytest.raises((pkg.OrbError, ValueError)):
+                m._check(m.L.orbm_search_by_projection_fisheye(m.m, C.byref(fsh), n1 // 2, l2r.ctypes.data, None, C.byref(qs), C.c_float(0.8), 256,
+                                                               F.slot.ctypes.data, F.slot_obs.ctypes.data, moq_f.ctypes.data, None),
+                         "orbm_search_by_projection_fisheye")
+            KF = pkg.FrameView(k1, d1, (100.0, 100.0, 0.0, 480.0))    # max_x == min_x
+            npt = 16
+            Xw = np.stack([np.linspace(-1, 1, npt), np.zeros(npt), np.full(npt, 5.0)], axis=1).astype(np.float32)
+            Tcw, Ow = np.eye(4, dtype=np.float32), np.zeros(3, np.float32)
+            normal = np.tile(np.float32([0, 0, 1]), (npt, 1))
+            with pytest.raises((pkg.OrbError, ValueError)):
+                m.Fuse(KF, sf, (1.0 / (sf * sf)).astype(np.float32), float(np.log(np.float32(1.2))), np.ones(npt, np.uint8), Xw, normal,
+                       d0[:npt], np.full(npt, 10.0, np.float32), np.full(npt, 1.0, np.float32), Tcw, Ow, 0, np.float32([458.0, 457.0, 367.0, 248.0]),
+                       47.9, 3.0)
         fs = pkg.FrameStruct(cap, d_kp[1:].data_ptr(), d_de[1:].data_ptr(), None, 0.0, 752.0, 0.0, 480.0)
         qs = pkg.QueryStruct(cap, d_de.data_ptr(), d_u.data_ptr(), d_v.data_ptr(), d_r.data_ptr(), d_lo.data_ptr(), d_hi.data_ptr(), None, None)
         rc = m.L.orbm_search_by_projection_batch_device(m.m, C.byref(fs), cap, C.c_void_p(d_cnt[1:].data_ptr()), 2, C.byref(qs), cap,
