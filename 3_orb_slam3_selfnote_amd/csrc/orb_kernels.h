@@ -3,7 +3,7 @@
 // Kernel inventory (roofline per kernel in DESIGN.md):
 //   k_resize    K1  cv::resize INTER_LINEAR 8U, one pyramid level of every frame per launch
 //   k_pyramid_chain K1  the same planes in ONE launch for single-frame calls (a tile recomputes the levels below it in LDS)
-//   k_fast      K2  FAST-9/16 score + per-cell NMS, cell detected at iniThFAST and again at minThFAST if empty, one workgroup per 30-px cell
+//   k_fast      K2  FAST-9/16 score + per-cell NMS, cell detected at iniThFAST and again at minThFAST if empty, one wavefront per 30-px cell
 //   k_octree    K3  DistributeOctTree, one workgroup per (frame, level), node list in LDS
 //   k_blur      K5  7x7 sigma-2 fixed-point Gaussian as two int8 MFMA products, 128x32 tiles staged through LDS
 //   k_describe  K4+K6+K7  IC_Angle + steered BRIEF + lapping-order scatter + frame totals, one wavefront (64 lanes) per keypoint
@@ -417,9 +417,9 @@ __global__ __launch_bounds__(CHAIN_NT) void k_pyramid_chain(FrameParams P) {
 // same cell (neighbours outside the cell's detection interior count as 0), again independent of t.  So one pass
 // gives the keypoints for iniThFAST and, if that set is empty, for minThFAST (decided per cell, after NMS).
 //
-// One 256-thread workgroup per cell: tile (<=65x65 B) in LDS, score plane in LDS, wave ballots for the
-// "any corner at iniTh" vote and for the raster-order compaction.  Output: per-cell slot list, packed
-// (response<<24 | y<<12 | x) in detection-rectangle coordinates, raster order inside the cell.
+// One 256-thread workgroup per group of up to 2 x 2 cells, one wavefront per cell: tile (<=76x80 B) and score plane in LDS,
+// wave ballots for the raster-order compaction.  Output: per-cell slot list, packed (response<<24 | y<<12 | x) in
+// detection-rectangle coordinates, raster order inside the cell.
 // ------------------------------------------------------------------------------------------------------------
 // number of set bits of a wave ballot below this lane (v_mbcnt_lo / v_mbcnt_hi)
 __device__ __forceinline__ int lane_rank(unsigned long long b) {
@@ -474,9 +474,10 @@ __device__ __forceinline__ int fast_compass_sign(const uint8_t *c, int t) {  // 
 #ifndef FAST_NT
 #define FAST_NT 256
 #endif
-#define FAST_LIST_SEG 888   // list entries per wavefront: 15 rows x 59 columns (64-lane rows), 16 rows x 32 (32-lane rows)
-static_assert(FAST_NT == 256, "k_fast's list segments assume four wavefronts");
-// Diagnostic builds (-DFAST_STAMPS, tools/fast_stamps.py): cycles per section, thread 0 of every workgroup.
+#define FAST_QUEUE 128   // per-wavefront ring of pre-test survivors waiting for the 16-pixel score; a row step adds at most 64
+static_assert(FAST_NT == 4 * WAVE, "k_fast gives each cell of a 2 x 2 group a wavefront of its own");
+static_assert(FAST_TILE_ROWS * FAST_TILE_PITCH <= 65536, "queue entries are 16-bit tile offsets");
+// Diagnostic builds (-DFAST_STAMPS, tools/fast_stamps.py): cycles per section, thread 0 of every workgroup (wavefront 0's cell).
 #if defined(FAST_STAMPS) || defined(OCT_STAMPS)
 __device__ unsigned int *g_fast_stamps;  // [workgroup][8] cycle deltas, set by orbx_debug_fast_stamps
 #endif
@@ -485,19 +486,25 @@ __device__ unsigned int *g_fast_stamps;  // [workgroup][8] cycle deltas, set by 
 #else
 #define FSTAMP(i) do {} while (0)
 #endif
+// LDS written by some lanes of a wavefront and read by other lanes of the SAME wavefront: the hardware executes one
+// wavefront's LDS instructions in order, so only the compiler has to be kept from moving the accesses across each other.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
+}
 __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
 #ifdef FAST_STAMPS
   long long ft0 = __builtin_readcyclecounter();
 #endif
   __shared__ __align__(16) uint8_t sTile[FAST_TILE_ROWS * FAST_TILE_PITCH];
-  __shared__ __align__(16) uint8_t sS[62 * FAST_S_PITCH];
-  __shared__ uint16_t sList[4 * FAST_LIST_SEG];
-  __shared__ __align__(16) uint32_t sWCount[12];   // [0..3] pass-1 list segments, [4..11] two count buffers of the ordered compactions
+  __shared__ __align__(16) uint8_t sS[FAST_TILE_ROWS * FAST_TILE_PITCH];   // the group's score plane, indexed like the tile
+  __shared__ uint16_t sQ[4 * FAST_QUEUE];
   const int tid = threadIdx.x, lane = tid & 63;
-  // A workgroup takes a GROUP of up to 2 x 2 neighbouring cells (late round 3; one cell before): their windows overlap by six pixels and
-  // the 80-byte tile rows always carried the right-hand neighbour's columns, so one staged tile - one HBM round trip, one set of
-  // address arithmetic - now serves four cells, which are then detected one after the other with the per-cell code unchanged (the
-  // reference decides iniThFAST / minThFAST per cell, ORBextractor.cc:820-828).  Group records come from orbx_configure.
+  // A workgroup takes a GROUP of up to 2 x 2 neighbouring cells: their windows overlap by six pixels and the 80-byte tile rows carry
+  // the right-hand neighbour's columns, so one staged tile - one HBM round trip, one set of address arithmetic - serves four
+  // cells.  Wavefront w then detects cell w of the group on its own, with no workgroup barrier after the tile has landed: the
+  // reference decides iniThFAST / minThFAST per cell (ORBextractor.cc:820-828), and a cell that needs the second detection
+  // holds up no other.  Group records come from orbx_configure.
   int groupId, frame;
   xcd_map(P.totalGroups, P.magicGroups, P.nframes, frame, groupId);
   const uint4 gr = reinterpret_cast<const uint4 *>(P.groups)[groupId];
@@ -505,11 +512,11 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   const int tileX = (int)(gr.z & 0xffffu), tileY = (int)(gr.z >> 16);
   const int gtw = (int)(gr.w & 0xffu), gth = (int)((gr.w >> 8) & 0xffu), level = (int)((gr.w >> 16) & 0xffu);
   const bool gvalid = (gr.w >> 24) != 0u;
-  int pitch = 0;
-  const uint8_t *img = nullptr;
   const int ax = tileX & ~3;                          // tile column 0 = image column ax, tile row 0 = image row tileY
   if (gvalid) {
     const uint4 r1f = reinterpret_cast<const uint4 *>(P.cells)[2 * firstCell + 1];
+    int pitch;
+    const uint8_t *img;
     if (level == 0) { pitch = (int)P.img0_stride; img = P.img0 + (size_t)frame * P.img0_frame_stride; }
     else { pitch = (int)r1f.y; img = P.pyr + (size_t)frame * P.pyr_fs + (((size_t)r1f.w << 32) | r1f.z); }
     // ---- tile -> LDS.  Aligned path: the columns [tileX & ~3, ...) of the group's rows.
@@ -536,9 +543,13 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
       }
     }
   }
-  auto do_cell = [&](const int cellId) {
+  __syncthreads();   // the only workgroup barrier: the tile has landed (its fence waits for the LDS-DMA)
+  FSTAMP(0);
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; tells the compiler so (scalar control flow)
+  if (wave >= gx * gy) return;                                  // groups at the right / bottom edge of a level: fewer cells
+  const int cellId = firstCell + (gx == 2 ? (wave >> 1) * gStride + (wave & 1) : wave * gStride);
   // cell record (orbx_configure, ORBextractor.cc:787-803): one 32-byte scalar load instead of a level search plus
-  // a dozen dependent geometry loads per workgroup
+  // a dozen dependent geometry loads
   const uint4 r0 = reinterpret_cast<const uint4 *>(P.cells)[2 * cellId], r1 = reinterpret_cast<const uint4 *>(P.cells)[2 * cellId + 1];
   const int iniX = (int)(r0.x & 0xffffu), iniY = (int)(r0.x >> 16);
   const int tw = (int)(r0.y & 0xffu), th = (int)((r0.y >> 8) & 0xffu), cw = tw - 6, ch = th - 6;
@@ -546,53 +557,42 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   const uint32_t cellCap = r1.x;
   uint32_t *cellCnt = P.cellCnt + (size_t)frame * P.cell_fs + cellId;
   if (!(r0.y >> 24)) {  // cell outside the detection rectangle
-    if (tid == 0) *cellCnt = 0;
+    if (lane == 0) *cellCnt = 0;
     return;
   }
-  const int ox = iniX - ax;                                          // offset of the cell's first column inside the tile
-  const uint8_t *sT = sTile + (iniY - tileY) * FAST_TILE_PITCH;      // the cell's first row inside the tile
-  // score plane rows 0 .. ch+1 to zero: (ch + 2) * 64 bytes = at most 244 sixteen-byte stores, one per thread, no loop
-  static_assert(62 * FAST_S_PITCH / 16 <= FAST_NT, "one 16-byte store per thread must cover the score plane");
-  if (tid < ((ch + 2) * FAST_S_PITCH) / 16) reinterpret_cast<uint4 *>(sS)[tid] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
-  FSTAMP(0);
   // The reference runs cv::FAST on the cell at iniThFAST and, only if that returns nothing, again at minThFAST
   // (ORBextractor.cc:820-828).  The score S is threshold-free, so "FAST at threshold t with non-maximum suppression" is: S > t
-  // and S strictly above the S of the 8 neighbours (a neighbour that is no corner at t has S <= t < S and can be left at 0).
-  // The kernel follows the same order - detect at iniThFAST, and again at minThFAST when the cell stayed empty - because the
-  // compass pre-test at the higher threshold passes far fewer pixels to the 16-pixel score (synthetic EuRoC frames: 81-125 per
-  // 30x30 cell instead of 227-360 at minThFAST 7, and 2 % of the cells need the second detection).
+  // and S strictly above the S of the 8 neighbours inside the cell (a neighbour that is no corner at t has S <= t < S and can be
+  // left at 0; one outside the cell counts as 0, as on the cell's own Mat).  The kernel follows the same order - detect at
+  // iniThFAST, and again at minThFAST when the cell stayed empty - because the compass pre-test at the higher threshold passes
+  // far fewer pixels to the 16-pixel score (synthetic EuRoC frames: 81-125 per 30x30 cell instead of 227-360 at minThFAST 7,
+  // and 2 % of the cells need the second detection).
+  // Lanes form rows of 32 (cells up to 32 interior columns, the usual 30) or 64 and step down the cell, so the per-pixel index
+  // arithmetic is one add; a step visits its pixels in raster order.  Cell interiors are disjoint, so the four wavefronts share
+  // one score plane; a wavefront reads the plane only inside its own cell.
   const int xsh = cw <= 32 ? 5 : 6;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; tells the compiler so (scalar loop bounds)
-  const int px = lane & ((1 << xsh) - 1), sub = lane >> xsh, rpi = 64 >> xsh;   // rows per wave-instruction: 2 or 1
-  const int R = (ch + 3) >> 2;
-  const int rowBeg = wave * R, rowEnd = min(rowBeg + R, ch);
+  const int px = lane & ((1 << xsh) - 1), sub = lane >> xsh, rpi = 64 >> xsh;   // rows per step: 2 or 1
   const bool xin = px < cw;
-  uint16_t *myList = sList + wave * FAST_LIST_SEG;
-  uint32_t *sCnt2 = sWCount + 4;   // [2][4]
+  const int off0 = (iniY - tileY + 3 + sub) * FAST_TILE_PITCH + (iniX - ax) + 3 + px;   // tile offset of this lane's first pixel
+  // validity as a sign bit: row - ch is negative inside the cell; columns outside the cell start from a value that stays positive
+  const int yr0 = xin ? sub - ch : 0x40000000;
+  const uint32_t yx0 = ((baseY + (uint32_t)sub + 3u) << 12) | (baseX + (uint32_t)px + 3u);   // packed output coordinates
+  uint16_t *q = sQ + wave * FAST_QUEUE;
   uint32_t *slots = P.slots + (size_t)frame * P.slot_fs + r0.w;
-  int turn = 0, nkept = 0;
+  int nkept = 0;
   int t = P.iniTh;
   for (int detection = 0;; detection++) {
-    // ---- pass 1: compass pre-test at t, survivors go to a dense work list as y << 6 | x (raster order = numeric order).
-    // Threads form rows of 32 (cells up to 32 interior columns, the usual 30) or 64 lanes and step down the cell, so the
-    // per-pixel index arithmetic is one add; a linear pixel index would need a division per pixel.
-    // Wavefront w owns the CONTIGUOUS rows [w * R, (w + 1) * R), R = ceil(ch / 4): its list segment is in raster order and so
-    // is the concatenation of the four segments - every later pass can keep that order with ballots and never has to sort.
-    // Every wavefront appends to its own segment of the list (at most R rows x cw entries <= 15 x 59 <= FAST_LIST_SEG) and
-    // keeps its count in a scalar register: no atomics.
-    int wcount = 0;
+    // ---- passes 1 + 2: compass pre-test at t; survivors join the wavefront's queue as tile offsets, and every time the queue
+    // holds a full wavefront's worth, 64 of them get the 16-pixel score (a second detection recomputes the first one's
+    // entries: same values).  In-cell pixels that fail the pre-test get score 0 in the plane, so the plane needs no clearing.
+    int qh = 0, qn = 0;   // queue head and length, wave-uniform
     {
-      const uint8_t *c = &sT[(rowBeg + sub + 3) * FAST_TILE_PITCH + ox + px + 3];
-      int yv = ((rowBeg + sub) << 6) | px;
-      // validity as a sign bit: row - rowEnd is negative inside the wavefront's rows; columns outside the cell start from a value
-      // that stays positive.  The pass condition is then ONE integer compare, which is also the ballot (no select / re-compare).
-      int yr = xin ? rowBeg + sub - rowEnd : 0x40000000;
-      for (int y0 = rowBeg; y0 < rowEnd; y0 += rpi, c += rpi * FAST_TILE_PITCH, yv += rpi << 6, yr += rpi) {
+      int off = off0, yr = yr0;
+      for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi) {
         // lanes outside the cell read LDS bytes that mean nothing (or zero past the allocation) and are masked out by yr
 #ifdef FAST_PAD   // diagnostic builds only (tools/fast_sensitivity.sh): 16 extra instructions of one class per pass-1 trip, results unused
         {
-          int pad0 = yv, pad1 = yr;
+          int pad0 = off, pad1 = yr;
 #if FAST_PAD == 1   // full-rate VALU
           asm volatile("v_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\n"
                        "v_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\nv_add_u32 %0, %0, %1\nv_add_u32 %1, %1, %0\n" : "+v"(pad0), "+v"(pad1));
@@ -606,79 +606,64 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
           asm volatile("" ::"v"(pad0), "v"(pad1));
         }
 #endif
-        const bool pass = (fast_compass_sign(c, t) & yr) < 0;
+        const bool pass = (fast_compass_sign(&sTile[off], t) & yr) < 0;
         const unsigned long long b = __builtin_amdgcn_ballot_w64(pass);
-        if (pass) myList[wcount + lane_rank(b)] = (uint16_t)yv;
-        wcount += __popcll(b);
+        if ((yr < 0) & !pass) sS[off] = 0;
+        if (pass) q[(qh + qn + lane_rank(b)) & (FAST_QUEUE - 1)] = (uint16_t)off;
+        qn += __popcll(b);
+        if (qn >= WAVE) {
+          wave_lds_order();
+          const int o = q[(qh + lane) & (FAST_QUEUE - 1)];
+          sS[o] = (uint8_t)fast_score_S(&sTile[o]);
+          qh = (qh + WAVE) & (FAST_QUEUE - 1);
+          qn -= WAVE;
+          wave_lds_order();   // these queue entries are free again
+        }
+      }
+      wave_lds_order();
+      if (lane < qn) {
+        const int o = q[(qh + lane) & (FAST_QUEUE - 1)];
+        sS[o] = (uint8_t)fast_score_S(&sTile[o]);
       }
     }
-    if (lane == 0) sWCount[wave] = (uint32_t)wcount;
-    __syncthreads();
+    wave_lds_order();
     FSTAMP(1);
-    // The four segments are walked as one list by all 256 threads (a wavefront walking only its own segment would need a
-    // second trip whenever that segment alone exceeds 64 entries): entry e lives in segment #(prefix sums <= e).
-    const uint4 wc = *reinterpret_cast<const uint4 *>(sWCount);
-    const int pre1 = (int)wc.x, pre2 = pre1 + (int)wc.y, pre3 = pre2 + (int)wc.z, nlist = pre3 + (int)wc.w;
-    auto entry = [&](int e) -> int {
-      const int seg = (e >= pre1) + (e >= pre2) + (e >= pre3);
-      const int start = e >= pre2 ? (e >= pre3 ? pre3 : pre2) : (e >= pre1 ? pre1 : 0);
-      return sList[seg * FAST_LIST_SEG + (e - start)];
-    };
-    // ---- pass 2: full 16-pixel score for the survivors only (a second detection recomputes the first one's entries: same
-    // values, the plane needs no clearing in between)
-    for (int e = tid; e < nlist; e += FAST_NT) {
-      const int p = entry(e);
-      const int y = p >> 6, x = p & 63;
-      const int S = fast_score_S(&sT[(y + 3) * FAST_TILE_PITCH + ox + x + 3]);
-      sS[(y + 1) * FAST_S_PITCH + x + 1] = (uint8_t)S;
-    }
-    __syncthreads();
-    FSTAMP(2);
-    // ---- pass 3 (survivors only): S > t and 3x3 strict maximum inside the cell; cv::FAST emits rows ascending, x ascending = the
-    // list's own order, so a kept entry's output slot is its rank among the kept ones and it is written on the spot.
-    // Non-survivors have score 0 in the plane, exactly what cv::FAST's NMS sees for non-corners.  Order-preserving ranks of
-    // each 256-entry chunk: a ballot + lane rank inside a wavefront, the four wavefronts' counts through LDS - two count
-    // buffers in turn, so one barrier per chunk.  No atomics, no sorting afterwards, no kept list.
-    for (int e0 = 0; e0 < nlist; e0 += FAST_NT) {
-      const int e = e0 + tid;
-      bool keep = false;
-      uint32_t kv = 0;
-      if (e < nlist) {
-        const int p = entry(e);
-        const int y = p >> 6, x = p & 63;
-        const uint8_t *s = &sS[(y + 1) * FAST_S_PITCH + x + 1];
-        const int S = s[0];
-        const int m0 = max(max((int)s[-FAST_S_PITCH - 1], (int)s[-FAST_S_PITCH]), (int)s[-FAST_S_PITCH + 1]);
-        const int m1 = max(max((int)s[FAST_S_PITCH - 1], (int)s[FAST_S_PITCH]), (int)s[FAST_S_PITCH + 1]);
-        const int m2 = max(max((int)s[-1], (int)s[1]), max(m0, m1));
-        keep = (S > t) & (S >= 2) & (S > m2);
-        kv = ((uint32_t)(S - 1) << 24) | ((baseY + (uint32_t)y + 3u) << 12) | (baseX + (uint32_t)x + 3u);
+    // ---- pass 3: the cell's plane rows in raster order; only lanes with S > t (and S >= 2: the response S - 1 must be positive)
+    // look at their neighbours.  cv::FAST emits rows ascending, x ascending = the order of the steps and of the lanes inside a
+    // step, so a kept corner's output slot is the wavefront's running count plus its lane rank: no atomics, no sorting.
+    {
+      const int tt = max(t, 1);
+      int off = off0, yr = yr0;
+      uint32_t yx = yx0;
+      for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi, yx += (uint32_t)rpi << 12) {
+        const int S = sS[off];
+        const bool cand = ((tt - S) & yr) < 0;
+        if (__builtin_amdgcn_ballot_w64(cand) == 0ull) continue;
+        bool keep = false;
+        if (cand) {
+          const int y = y0 + sub;
+          const uint8_t *s = &sS[off];
+          const bool l = px > 0, r = px < cw - 1, u = y > 0, d = y < ch - 1;   // neighbours outside the cell count as 0
+          const int mu = u ? max(max(l ? (int)s[-FAST_TILE_PITCH - 1] : 0, (int)s[-FAST_TILE_PITCH]), r ? (int)s[-FAST_TILE_PITCH + 1] : 0) : 0;
+          const int md = d ? max(max(l ? (int)s[FAST_TILE_PITCH - 1] : 0, (int)s[FAST_TILE_PITCH]), r ? (int)s[FAST_TILE_PITCH + 1] : 0) : 0;
+          const int m = max(max(l ? (int)s[-1] : 0, r ? (int)s[1] : 0), max(mu, md));
+          keep = S > m;
+        }
+        const unsigned long long bK = __builtin_amdgcn_ballot_w64(keep);
+        const uint32_t rank = (uint32_t)nkept + (uint32_t)lane_rank(bK);
+        if (keep && rank < cellCap) slots[rank] = ((uint32_t)(S - 1) << 24) | yx;
+        nkept += __popcll(bK);
       }
-      const unsigned long long bK = __builtin_amdgcn_ballot_w64(keep);
-      uint32_t *cnt = sCnt2 + 4 * turn;
-      turn ^= 1;
-      if (lane == 0) cnt[wave] = (uint32_t)__popcll(bK);
-      __syncthreads();
-      const uint4 c4 = *reinterpret_cast<const uint4 *>(cnt);
-      const uint32_t pre = (wave > 0 ? c4.x : 0u) + (wave > 1 ? c4.y : 0u) + (wave > 2 ? c4.z : 0u);
-      const uint32_t rank = (uint32_t)nkept + pre + (uint32_t)lane_rank(bK);
-      if (keep && rank < cellCap) slots[rank] = kv;
-      nkept += (int)(c4.x + c4.y + c4.z + c4.w);
     }
-    FSTAMP(3);
+    FSTAMP(2);
     // ORBextractor.cc:825: the second detection runs only if the first returned nothing (with minThFAST >= iniThFAST it could
     // only return a subset of nothing)
     if (nkept > 0 || detection == 1 || P.minTh >= P.iniTh) break;
     t = P.minTh;
+    wave_lds_order();   // pass 3 is done with the plane, the queue is empty
   }
-  if (tid == 0) *cellCnt = (uint32_t)min(nkept, (int)cellCap);
+  if (lane == 0) *cellCnt = (uint32_t)min(nkept, (int)cellCap);
   FSTAMP(7);
-  };
-  for (int cy = 0; cy < gy; cy++)
-    for (int cx = 0; cx < gx; cx++) {
-      if (cy | cx) __syncthreads();      // the previous cell is done with the score plane, the lists and the counters
-      do_cell(firstCell + cy * gStride + cx);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------

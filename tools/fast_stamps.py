@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Cycle shares of k_fast's sections (diagnostic build -DFAST_STAMPS, ORBHIP_LIB=build/liborbhip_fast.so).  GPU box only."""
+"""Cycle shares of k_fast's sections (diagnostic build -DFAST_STAMPS, ORBHIP_LIB=build/liborbhip_fast.so).  GPU box only.
+The stamps are thread 0's, so they time wavefront 0's cell of each group."""
 import ctypes as C
 import importlib
 import os
@@ -21,7 +22,23 @@ d_kps = torch.zeros((B, cap, 7), dtype=torch.float32, device="cuda")
 d_desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device="cuda")
 d_cnt = torch.zeros((B, 2), dtype=torch.int32, device="cuda")
 L = pkg.load()
-nwg = 982 * B
+
+
+def groups_per_frame():
+    """k_fast's workgroups per frame: orbx_configure's groups of up to 2 x 2 cells (ORBextractor.cc:771-785 grid)."""
+    n = 0
+    for l in range(8):
+        h, w = ex.level_shape(l)
+        width, height = w - 32, h - 32
+        nCols, nRows = width // 30, height // 30
+        wCell, hCell = -(-width // nCols), -(-height // nRows)
+        sx = 2 if 3 + 2 * wCell + 6 <= 80 else 1
+        sy = 2 if 2 * hCell + 6 <= 76 else 1
+        n += -(-nRows // sy) * -(-nCols // sx)
+    return n
+
+
+nwg = groups_per_frame() * B
 buf = torch.zeros((nwg, 8), dtype=torch.int32, device="cuda")
 L.orbx_debug_fast_stamps(C.c_void_p(buf.data_ptr()))
 for it in range(3):
@@ -30,7 +47,8 @@ for it in range(3):
     torch.cuda.synchronize()
 v = buf.cpu().numpy().astype(np.float64)
 live = v[:, 0] > 0
-names = ["prologue+tile load", "pass1 compass+list", "pass2 score", "pass3 NMS + emit", "(unused)", "(unused)", "(unused)", "cell count"]
+# wavefront 0's cell (thread 0 stamps); a cell's second detection overwrites sections 1 and 2 with its own
+names = ["prologue+tile load", "pass1+2 compass+queue+score", "pass3 NMS + emit", "(unused)", "(unused)", "(unused)", "(unused)", "cell count"]
 m = v[live].mean(axis=0)
 for n, x in zip(names, m):
     print("%-22s %6.1f %%   %.0f cycles/workgroup" % (n, 100 * x / m.sum(), x))
