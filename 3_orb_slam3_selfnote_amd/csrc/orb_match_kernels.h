@@ -66,7 +66,9 @@ struct MatchProblemSet {
 // 256 frame pairs = every CU of the chip.  With one wavefront per SIMD half the registers stay free (four k_fast wavefronts per SIMD): alone
 // the kernel is 5 % slower (0.281 -> 0.296 ms, the list build is spread over half the wavefronts), the four-pipeline bench 5 % faster
 // (190.8 k -> 200.5 k frames/s); two wavefronts: 0.39 ms, 193 k.  The other forms (115-119 registers: two wavefronts per SIMD leave half the file
-// free as well) keep eight: the wide form's lanes ARE the workgroup's threads (512 queries per super-chunk).
+// free as well) keep eight: the wide form's lanes ARE the workgroup's threads (512 queries per super-chunk).  Since the fused form keeps its
+// descriptors and records in global memory and its query fragments packed, it takes 184 registers, no scratch and 15.4 + 15 B x maxn of
+// LDS (31 KB at the bench's 1032 keypoints, was 83 KB); the two- and eight-wavefront forms were not measured again at this footprint.
 #define RESOLVE_NW_OF(fused) ((fused) ? 4 : 8)
 
 struct Key32 {
@@ -750,7 +752,8 @@ __device__ __forceinline__ uint32_t decide(const MatchProblemSet &M, const typen
 //                  during a round, 0xffffffff free; word n is a dummy that stays free (target of empty list entries).
 //      sSlot[k]  = max over accepted queries of (query<<1 | obs), i.e. the LAST query that took keypoint k; -1 none.
 //      sTk[j][lane] = entry j of lane's current list.
-//      LDSCAND: descriptors + positions staged in LDS once (48 B per keypoint) so that refreshes never leave the CU.
+//      LDSCAND: descriptors + positions staged in LDS once (48 B per keypoint) so that refreshes never leave the CU; the FUSED form
+//               stages them in the same order in global memory instead (`cand`, read back through L2).
 #define RESOLVE_FREE 0xffffffffu
 #define REFRESH_K 4
 #define REQ_WORDS 16  // lane, flags, u, v, r, ur, minl, maxl, descriptor[8]
@@ -760,12 +763,13 @@ __device__ __forceinline__ uint32_t decide(const MatchProblemSet &M, const typen
 // only those NO COMMITTED CLAIM HOLDS (compacted, so the work shrinks as the frame fills up: by the last chunks nine keypoints in
 // ten are taken), runs them as 32-row A tiles against the chunk's queries (two B tiles built from the posted descriptors) with
 // the keypoint's rank as accumulator seed, and keeps a top-4 per query and wavefront; the requesting lane folds the wavefronts' sorted
-// shares.  The same pass serves the (now rare) lists exhausted inside a chunk.  The keypoints sit in LDS at position = rank, so
-// a key's low 11 bits are the position and sPerm gives the index.  What this replaces: the all-pairs scan kernel (0.23 ms per 256
+// shares.  The same pass serves the (now rare) lists exhausted inside a chunk.  The keypoints sit at position = rank (records and
+// descriptors in the global table `cand`, seeds in LDS), so a key's low 11 bits are the position and sPerm gives the index.  What this replaces: the all-pairs scan kernel (0.23 ms per 256
 // frame pairs) and the 36 refresh passes per pair that re-scanned the frame on the vector ALU (70 % of k_match_resolve's 0.29 ms).
 template <typename KT, bool LDSCAND, bool FUSED = false>
 __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(MatchProblemSet M, const typename KT::T *topk, int maxn, int rforce,
-                                                                   const uint32_t *rec = nullptr, const uint32_t *keyrec = nullptr, const uint32_t *pairflag = nullptr) {
+                                                                   const uint32_t *rec = nullptr, const uint32_t *keyrec = nullptr, const uint32_t *pairflag = nullptr,
+                                                                   uint4 *cand = nullptr /* FUSED: 3 * maxn records per pair, see the carve */) {
   constexpr int NW_ = RESOLVE_NW_OF(FUSED);   // wavefronts of this workgroup (see RESOLVE_NW_OF)
   typedef typename KT::T K;
   extern __shared__ __align__(16) uint32_t smem_resolve[];
@@ -785,9 +789,12 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
   uint8_t *slot_obs = M.slot_obs + fo;
   // carve: [desc 8*maxn words][meta 4*maxn words] (LDSCAND only, both in sPerm order: the refresh scan then reads them
   // sequentially, conflict-free, instead of at random) [owner maxn+1][slot maxn][perm: maxn u16][partner][octave: maxn u8 (LDSCAND only)]
-  uint4 *sDesc = reinterpret_cast<uint4 *>(smem_resolve);
-  CandMeta *sMeta = reinterpret_cast<CandMeta *>(smem_resolve + (LDSCAND ? 8 * (size_t)maxn : 0));
-  uint32_t *sOwner = smem_resolve + (LDSCAND ? 12 * (size_t)maxn : 0);
+  // [seed maxn words (FUSED only)].  FUSED: descriptors and records, in the same sPerm order, live in global memory instead (`cand`: this
+  // pair's 2 * maxn descriptor halves, then maxn records, written once below and read back through L2 by the list builds), so the
+  // carve is 15 B per keypoint instead of 63 and the kernel leaves most of its CU's LDS to the pipelines running beside it.
+  uint4 *cDesc = FUSED ? cand + (size_t)p * 3 * maxn : reinterpret_cast<uint4 *>(smem_resolve);
+  CandMeta *cMeta = FUSED ? reinterpret_cast<CandMeta *>(cDesc + 2 * (size_t)maxn) : reinterpret_cast<CandMeta *>(smem_resolve + (LDSCAND ? 8 * (size_t)maxn : 0));
+  uint32_t *sOwner = smem_resolve + (LDSCAND && !FUSED ? 12 * (size_t)maxn : 0);
   int32_t *sSlot = reinterpret_cast<int32_t *>(sOwner + maxn + 1);
   uint16_t *sPerm = reinterpret_cast<uint16_t *>(sSlot + maxn);
   uint16_t *sPartner = sPerm + ((maxn + 1) & ~1);   // stereo partner of each keypoint, 0xffff = none (only if M.partner)
@@ -830,10 +837,10 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
       CandMeta c;
       c.x = x; c.y = y; c.bits = bits;
       c.ur = M.u_right ? M.u_right[fo + i] : -1.f;
-      sMeta[pos] = c;
+      cMeta[pos] = c;
       const uint4 *gd = reinterpret_cast<const uint4 *>(M.desc + fo * 32);
-      sDesc[2 * pos] = gd[2 * i];
-      sDesc[2 * pos + 1] = gd[2 * i + 1];
+      cDesc[2 * pos] = gd[2 * i];
+      cDesc[2 * pos + 1] = gd[2 * i + 1];
     }
     if (FUSED && fusedPair) sRank[pos] = seed;
   }
@@ -882,7 +889,7 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
       const int c = valid ? k.c : 0;
       const bool cl = sOwner[valid ? c : n] == 0u;
       if (LDSCAND) {
-        const CandMeta cmeta = sMeta[k.pos];
+        const CandMeta cmeta = cMeta[k.pos];
         k.x = cmeta.x; k.y = cmeta.y; k.ur = cmeta.ur;
         k.bits = cl ? (cmeta.bits & ~(1u << 24)) : cmeta.bits;
       } else {
@@ -905,7 +912,7 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
     auto score = [&](const Probe &k) {
       uint32_t d[8];
       if (LDSCAND) {
-        const uint4 a = sDesc[2 * k.pos], b = sDesc[2 * k.pos + 1];
+        const uint4 a = cDesc[2 * k.pos], b = cDesc[2 * k.pos + 1];
         d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
       } else {
 #pragma unroll
@@ -1167,7 +1174,10 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
   uint32_t *sPartF = sReqD + 64 * 8;
   uint16_t *sCmpF = reinterpret_cast<uint16_t *>(sPartF + 64 * NW_ * REFRESH_K);
   uint32_t *sSeedF = reinterpret_cast<uint32_t *>(sCmpF + NW_ * CMP_CAP);
-  auto serve_mfma = [&](int m) {   // all wavefronts; m <= 64 requests posted in sReqD (their queries are open: every usable keypoint is a candidate)
+  // Inlined at both call sites by force: left to itself the compiler made it a real call, and the closure it passed by address turned
+  // every LDS pointer the kernel shares with it into a flat pointer (192 flat loads, stores and atomics, the claim rounds' included)
+  // kept in 160 B of scratch per lane.
+  auto serve_mfma = [&](int m) __attribute__((always_inline)) {   // all wavefronts; m <= 64 requests posted in sReqD (their queries are open: every usable keypoint is a candidate)
     if constexpr (FUSED) {
       const int col = lane & 31, h = lane >> 5;
       const int nin = sCol[64];                               // the keypoints PosInGrid accepts are positions [0, nin)
@@ -1183,27 +1193,43 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
         kw += __popcll(mk);
       }
       const bool two = m > 32;
-      mf_v4i B0[8], B1[8];
+      // The chunk's query fragments stay packed: bits [32 s + 16 h, 32 s + 16 h + 16) of query col (q0) and 32 + col (q1), two K-steps
+      // per register, each expanded right before its MFMA.  Holding them expanded took 64 registers for the whole pass.
+      uint32_t q0[4], q1[4];
       {
         const uint4 *r0 = reinterpret_cast<const uint4 *>(sReqD + col * 8), *r1 = reinterpret_cast<const uint4 *>(sReqD + (32 + col) * 8);
         const uint4 a0 = r0[0], b0 = r0[1], a1 = r1[0], b1 = r1[1];
         const uint32_t d0[8] = {a0.x, a0.y, a0.z, a0.w, b0.x, b0.y, b0.z, b0.w}, d1[8] = {a1.x, a1.y, a1.z, a1.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
-        for (int s = 0; s < 8; s++) {
-          B0[s] = mf_expand16((d0[s] >> (16 * h)) & 0xffffu, MF_LUT_QUERY);
-          B1[s] = mf_expand16((d1[s] >> (16 * h)) & 0xffffu, MF_LUT_QUERY);
+        for (int s = 0; s < 4; s++) {
+          q0[s] = ((d0[2 * s] >> (16 * h)) & 0xffffu) | ((d0[2 * s + 1] >> (16 * h)) << 16);
+          q1[s] = ((d1[2 * s] >> (16 * h)) & 0xffffu) | ((d1[2 * s + 1] >> (16 * h)) << 16);
         }
       }
+      auto bq = [](const uint32_t *q, int s) { return mf_expand16((q[s >> 1] >> (16 * (s & 1))) & 0xffffu, MF_LUT_QUERY); };
       MfList<REFRESH_K> L0, L1;
       L0.init(); L1.init();
       uint32_t *seedw = sSeedF + wid * MF_TILE;
+      // the candidates' descriptors come from L2: the next tile's are loaded while this one runs (8 registers)
+      int npos = 0;
+      uint4 na = make_uint4(0u, 0u, 0u, 0u), nb = na;
+      if (kw > 0) {
+        npos = col < kw ? (int)cmp[col] : 0;
+        na = cDesc[2 * npos]; nb = cDesc[2 * npos + 1];
+      }
       for (int t0 = 0; t0 < kw; t0 += MF_TILE) {
-        const int e = t0 + col;
-        const bool have = e < kw;
-        const int pos = have ? (int)cmp[e] : 0;
+        const bool have = t0 + col < kw;
+#pragma unroll
+        for (int s = 0; s < 4; s++) asm("" : "+v"(q0[s]), "+v"(q1[s]));   // opaque per tile: keeps the expansions from being hoisted out of the loop
+        const int pos = npos;
+        const uint4 da = na, db = nb;
+        if (t0 + MF_TILE < kw) {
+          const int e2 = t0 + MF_TILE + col;
+          npos = e2 < kw ? (int)cmp[e2] : 0;
+          na = cDesc[2 * npos]; nb = cDesc[2 * npos + 1];
+        }
         if (h == 0) seedw[col] = have ? sRank[pos] : MF_REC_UNUSABLE;
         // A fragments straight from the keypoint's descriptor: bits [32 s + 16 h, 32 s + 16 h + 16) of row `col` per K-step s
-        const uint4 da = sDesc[2 * pos], db = sDesc[2 * pos + 1];
         const uint32_t dd[8] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
         mf_v4i A[8];
 #pragma unroll
@@ -1216,12 +1242,12 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
         }
         mf_v16i acc0 = c;
 #pragma unroll
-        for (int s = 0; s < 8; s++) acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], B0[s], acc0, 0, 0, 0);
+        for (int s = 0; s < 8; s++) acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], bq(q0, s), acc0, 0, 0, 0);
         L0.take(acc0);
         if (two) {
           mf_v16i acc1 = c;
 #pragma unroll
-          for (int s = 0; s < 8; s++) acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], B1[s], acc1, 0, 0, 0);
+          for (int s = 0; s < 8; s++) acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], bq(q1, s), acc1, 0, 0, 0);
           L1.take(acc1);
         }
       }

@@ -1078,6 +1078,7 @@ struct orbm_handle {
   void *pin = nullptr; size_t pin_bytes = 0;   // its pinned host mirror
   DevBuf d_topk;      // per-query candidate lists of the scan / walk, for the resolve (all projection searches)
   DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
+  DevBuf d_cand;      // fused k_match_resolve: every pair's descriptors and candidate records in sorted order (48 B per keypoint)
   DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
   bool profiling = false;
@@ -1168,7 +1169,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_lfq, &m->d_tri_count, &m->d_tri_keys};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_tri_count, &m->d_tri_keys};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -1406,9 +1407,18 @@ static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, cons
   const size_t small = sizeof(uint32_t) * (size_t)((maxn + 1) + maxn + (maxn + 1) / 2 + (M.partner ? (maxn + 1) / 2 + 1 : 0) + 2);
   const size_t big = small + sizeof(uint32_t) * (size_t)((maxn + 3) / 4) + 48 * (size_t)maxn;   // + octave bytes, records, descriptors
   const bool ldscand = big <= 136 * 1024;   // + the kernel's static LDS (Key32: wide list array 16 KiB, chunk lists, requests)
-  // fused form: + one accumulator seed per keypoint; serial / coupled problems never take the wide form
-  const bool fused = mfma && m->hamming_engine >= 2 && o.init_th_low < 0 && !M.serial && M.couple == 0 && big + sizeof(uint32_t) * (size_t)maxn <= 138 * 1024;
-  const size_t lds = fused ? big + sizeof(uint32_t) * (size_t)maxn : ldscand ? big : small;
+  // fused form: octave bytes + one accumulator seed per keypoint (15 B per keypoint in all); its records and descriptors live in d_cand.
+  // Admission is what it was (the Key32 bound, 2048 keypoints, decides it: with the records in LDS the carve was 129 KB there), but the
+  // LDS condition is now slack: 31 KB at 2048 keypoints.  Serial / coupled problems never take the wide form.
+  const size_t fused_lds = small + sizeof(uint32_t) * (size_t)((maxn + 3) / 4) + sizeof(uint32_t) * (size_t)maxn;
+  const bool fused = mfma && m->hamming_engine >= 2 && o.init_th_low < 0 && !M.serial && M.couple == 0 && fused_lds <= 138 * 1024;
+  const size_t lds = fused ? fused_lds : ldscand ? big : small;
+  // ORBHIP_PRINT_RESOLVE_LDS (measurements, tests/test_gpu_fused_footprint.py): the form and the dynamic LDS of every search launch
+  if (getenv("ORBHIP_PRINT_RESOLVE_LDS")) fprintf(stderr, "orbhip: resolve maxn %d fused %d dynamic LDS %zu bytes\n", maxn, (int)fused, lds);
+  if (fused && 3 * sizeof(uint4) * (size_t)maxn * (size_t)npairs > m->d_cand.bytes) {
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, m->d_cand.reserve(3 * sizeof(uint4) * (size_t)maxn * (size_t)npairs));
+  }
   if (lds > 152 * 1024) { m->err = "too many keypoints per frame for the search kernels' LDS state (fisheye-stereo frames: at most 13000)"; return ORBX_E_ARG; }
   const dim3 rblock(64 * RESOLVE_NW_OF(fused));
   // The walk's workgroups come first: they are the short ones.
@@ -1461,7 +1471,7 @@ static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, cons
     hipLaunchKernelGGL((k_match_scan<Key32, SCAN_PLAIN>), sgrid, dim3(MATCH_NT), 0, s, M, (Key32::T *)m->d_topk.p, slice_stride, force, mf, (const uint32_t *)pairflag);
     if (prof) MCHECK(m, hipEventRecord(pev[1], s));
     hipLaunchKernelGGL((k_match_resolve<Key32, true, true>), dim3(npairs), rblock, lds, s, M, (const Key32::T *)m->d_topk.p, maxn, force, (const uint32_t *)rec,
-                       (const uint32_t *)keyrec, (const uint32_t *)pairflag);
+                       (const uint32_t *)keyrec, (const uint32_t *)pairflag, (uint4 *)m->d_cand.p);
   } else {
     const int rc = k32 ? (ldscand ? match(Key32(), std::true_type()) : match(Key32(), std::false_type()))
                        : (ldscand ? match(Key64(), std::true_type()) : match(Key64(), std::false_type()));
