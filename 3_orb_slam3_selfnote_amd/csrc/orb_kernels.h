@@ -475,7 +475,12 @@ __device__ __forceinline__ int fast_compass_sign(const uint8_t *c, int t) {  // 
 #define FAST_NT 256
 #endif
 #define FAST_QUEUE 128   // per-wavefront ring of pre-test survivors waiting for the 16-pixel score; a row step adds at most 64
+#ifndef FAST_LIST
+#define FAST_LIST 384    // per-wavefront list of a detection's corners (S > t) for the NMS; a cell with more takes the full-cell walk
+#endif
 static_assert(FAST_NT == 4 * WAVE, "k_fast gives each cell of a 2 x 2 group a wavefront of its own");
+static_assert(FAST_LIST % WAVE == 0, "pass 3 reads the corner list 64 entries at a time, all inside the list");
+static_assert((FAST_TILE_ROWS * FAST_TILE_PITCH) % 16 == 0, "the score plane is cleared in 16-byte stores");
 static_assert(FAST_TILE_ROWS * FAST_TILE_PITCH <= 65536, "queue entries are 16-bit tile offsets");
 // Diagnostic builds (-DFAST_STAMPS, tools/fast_stamps.py): cycles per section, thread 0 of every workgroup (wavefront 0's cell).
 #if defined(FAST_STAMPS) || defined(OCT_STAMPS)
@@ -499,6 +504,7 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   __shared__ __align__(16) uint8_t sTile[FAST_TILE_ROWS * FAST_TILE_PITCH];
   __shared__ __align__(16) uint8_t sS[FAST_TILE_ROWS * FAST_TILE_PITCH];   // the group's score plane, indexed like the tile
   __shared__ uint16_t sQ[4 * FAST_QUEUE];
+  __shared__ uint16_t sL[4 * FAST_LIST];   // per-wavefront corner lists (tile offsets, raster order)
   const int tid = threadIdx.x, lane = tid & 63;
   // A workgroup takes a GROUP of up to 2 x 2 neighbouring cells: their windows overlap by six pixels and the 80-byte tile rows carry
   // the right-hand neighbour's columns, so one staged tile - one HBM round trip, one set of address arithmetic - serves four
@@ -543,7 +549,10 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
       }
     }
   }
-  __syncthreads();   // the only workgroup barrier: the tile has landed (its fence waits for the LDS-DMA)
+  // Score 0 everywhere, while the LDS-DMA is in flight: a pixel the pre-test never passes keeps it.  S does not depend on the
+  // threshold and the minThFAST survivors include the iniThFAST ones, so a second detection rewrites the same values.
+  for (int i = tid; i < FAST_TILE_ROWS * FAST_TILE_PITCH / 16; i += FAST_NT) reinterpret_cast<uint4 *>(sS)[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();   // the only workgroup barrier: the tile has landed (its fence waits for the LDS-DMA), the plane is clear
   FSTAMP(0);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; tells the compiler so (scalar control flow)
   if (wave >= gx * gy) return;                                  // groups at the right / bottom edge of a level: fewer cells
@@ -578,14 +587,28 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   const int yr0 = xin ? sub - ch : 0x40000000;
   const uint32_t yx0 = ((baseY + (uint32_t)sub + 3u) << 12) | (baseX + (uint32_t)px + 3u);   // packed output coordinates
   uint16_t *q = sQ + wave * FAST_QUEUE;
+  uint16_t *list = sL + wave * FAST_LIST;
+  const int base00 = (iniY - tileY + 3) * FAST_TILE_PITCH + (iniX - ax) + 3;   // tile offset of the interior's first pixel
   uint32_t *slots = P.slots + (size_t)frame * P.slot_fs + r0.w;
   int nkept = 0;
   int t = P.iniTh;
   for (int detection = 0;; detection++) {
     // ---- passes 1 + 2: compass pre-test at t; survivors join the wavefront's queue as tile offsets, and every time the queue
     // holds a full wavefront's worth, 64 of them get the 16-pixel score (a second detection recomputes the first one's
-    // entries: same values).  In-cell pixels that fail the pre-test get score 0 in the plane, so the plane needs no clearing.
-    int qh = 0, qn = 0;   // queue head and length, wave-uniform
+    // entries: same values).  Lanes whose score is above t append their offset to the corner list: the queue is filled and
+    // drained in raster order, so the list is in raster order too.  A second detection starts a new list.
+    const int tt = max(t, 1);   // S > t, and S >= 2: the response S - 1 must be positive
+    int qh = 0, qn = 0, nl = 0;   // queue head and length, list length: wave-uniform
+    auto score = [&](bool act) {
+      const int o = act ? (int)q[(qh + lane) & (FAST_QUEUE - 1)] : base00;   // idle lanes of the tail: a pixel of the cell
+      const int S = fast_score_S(&sTile[o]);
+      if (act) sS[o] = (uint8_t)S;
+      const bool c = act && S > tt;
+      const unsigned long long bc = __builtin_amdgcn_ballot_w64(c);
+      const int li = nl + lane_rank(bc);
+      if (c && li < FAST_LIST) list[li] = (uint16_t)o;
+      nl += __popcll(bc);
+    };
     {
       int off = off0, yr = yr0;
       for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi) {
@@ -608,31 +631,48 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
 #endif
         const bool pass = (fast_compass_sign(&sTile[off], t) & yr) < 0;
         const unsigned long long b = __builtin_amdgcn_ballot_w64(pass);
-        if ((yr < 0) & !pass) sS[off] = 0;
         if (pass) q[(qh + qn + lane_rank(b)) & (FAST_QUEUE - 1)] = (uint16_t)off;
         qn += __popcll(b);
         if (qn >= WAVE) {
           wave_lds_order();
-          const int o = q[(qh + lane) & (FAST_QUEUE - 1)];
-          sS[o] = (uint8_t)fast_score_S(&sTile[o]);
+          score(true);
           qh = (qh + WAVE) & (FAST_QUEUE - 1);
           qn -= WAVE;
           wave_lds_order();   // these queue entries are free again
         }
       }
       wave_lds_order();
-      if (lane < qn) {
-        const int o = q[(qh + lane) & (FAST_QUEUE - 1)];
-        sS[o] = (uint8_t)fast_score_S(&sTile[o]);
-      }
+      if (qn > 0) score(lane < qn);
     }
-    wave_lds_order();
+    wave_lds_order();   // the plane and the list are complete
     FSTAMP(1);
-    // ---- pass 3: the cell's plane rows in raster order; only lanes with S > t (and S >= 2: the response S - 1 must be positive)
-    // look at their neighbours.  cv::FAST emits rows ascending, x ascending = the order of the steps and of the lanes inside a
-    // step, so a kept corner's output slot is the wavefront's running count plus its lane rank: no atomics, no sorting.
-    {
-      const int tt = max(t, 1);
+    // ---- pass 3: NMS + emit.  cv::FAST emits rows ascending, x ascending = the order of the corner list, so a kept corner's
+    // output slot is the wavefront's running count plus its lane rank: no atomics, no sorting.
+    if (nl <= FAST_LIST) {
+      // 64 corners per trip: all nine plane reads issued at once, neighbours outside the cell masked to 0 by selects
+      for (int i0 = 0; i0 < nl; i0 += WAVE) {
+        const bool act = i0 + lane < nl;
+        const int o = act ? (int)list[i0 + lane] : FAST_TILE_PITCH + 1;   // idle lanes: any offset whose 3 x 3 lies in the plane
+        const uint32_t rel = (uint32_t)(o - base00);
+        const int y = (int)(mul24(rel, 52429u) >> 22), x = (int)rel - y * FAST_TILE_PITCH;   // rel / 80, exact for rel < 2^18
+        const uint8_t *s = &sS[o];
+        const int S = s[0];
+        int n0 = s[-FAST_TILE_PITCH - 1], n1 = s[-FAST_TILE_PITCH], n2 = s[-FAST_TILE_PITCH + 1], n3 = s[-1];
+        int n4 = s[1], n5 = s[FAST_TILE_PITCH - 1], n6 = s[FAST_TILE_PITCH], n7 = s[FAST_TILE_PITCH + 1];
+        asm("" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(n4), "+v"(n5), "+v"(n6), "+v"(n7));   // keeps the reads out of branches
+        const bool l = x > 0, r = x < cw - 1, u = y > 0, d = y < ch - 1;   // neighbours outside the cell count as 0
+        const int mu = u ? max(max(l ? n0 : 0, n1), r ? n2 : 0) : 0;
+        const int md = d ? max(max(l ? n5 : 0, n6), r ? n7 : 0) : 0;
+        const int m = max(max(l ? n3 : 0, r ? n4 : 0), max(mu, md));
+        const bool keep = act && S > m;
+        const unsigned long long bK = __builtin_amdgcn_ballot_w64(keep);
+        const uint32_t rank = (uint32_t)nkept + (uint32_t)lane_rank(bK);
+        if (keep && rank < cellCap) slots[rank] = ((uint32_t)(S - 1) << 24) | (((baseY + (uint32_t)y + 3u) << 12) | (baseX + (uint32_t)x + 3u));
+        nkept += __popcll(bK);
+      }
+    } else {
+      // more corners than the list holds (dense texture or noise): the cell's plane rows in raster order; only lanes with
+      // S > t look at their neighbours
       int off = off0, yr = yr0;
       uint32_t yx = yx0;
       for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi, yx += (uint32_t)rpi << 12) {
@@ -660,7 +700,7 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
     // only return a subset of nothing)
     if (nkept > 0 || detection == 1 || P.minTh >= P.iniTh) break;
     t = P.minTh;
-    wave_lds_order();   // pass 3 is done with the plane, the queue is empty
+    wave_lds_order();   // pass 3 is done with the plane and the list, the queue is empty
   }
   if (lane == 0) *cellCnt = (uint32_t)min(nkept, (int)cellCap);
   FSTAMP(7);

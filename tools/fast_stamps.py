@@ -48,7 +48,7 @@ for it in range(3):
 v = buf.cpu().numpy().astype(np.float64)
 live = v[:, 0] > 0
 # wavefront 0's cell (thread 0 stamps); a cell's second detection overwrites sections 1 and 2 with its own
-names = ["prologue+tile load", "pass1+2 compass+queue+score", "pass3 NMS + emit", "(unused)", "(unused)", "(unused)", "(unused)", "cell count"]
+names = ["prologue+tile load", "pass1+2 compass+queue+score+list", "pass3 NMS + emit", "(unused)", "(unused)", "(unused)", "(unused)", "cell count"]
 m = v[live].mean(axis=0)
 for n, x in zip(names, m):
     print("%-22s %6.1f %%   %.0f cycles/workgroup" % (n, 100 * x / m.sum(), x))
