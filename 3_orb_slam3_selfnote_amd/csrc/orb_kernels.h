@@ -189,7 +189,9 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
     const int nsrc = min(syLast - syFirst + 1, maxSrc);
     uint8_t *sRows = smem_rs;                                  // [maxSrc][smemRowBytes]
     uint8_t *sT = sRows + (size_t)maxSrc * smemRowBytes;       // [maxSrc][tPitch] bytes, u16 entries
-    uint4 *sRowRec = reinterpret_cast<uint4 *>(sT + (size_t)maxSrc * tPitch);   // [RESIZE_ROWS_MAX]
+    // [RESIZE_ROWS_MAX], 16-byte aligned for its ds_read_b128 / ds_write_b128 (tPitch is a multiple of 8 only; the host's LDS size
+    // counts the same padding)
+    uint4 *sRowRec = reinterpret_cast<uint4 *>(sT + (((size_t)maxSrc * tPitch + 15) & ~(size_t)15));
     // this thread's first two column pairs of pass 1, loaded ahead of the staging (a level up to 1024 columns wide needs no more)
     const int4 *xtab4 = reinterpret_cast<const int4 *>(P.xtab + G.xtabBase);
     int4 xtPre[2];

@@ -688,7 +688,10 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   // One workgroup per (frame, level) in k_octree and one launch per level here: a batch fills the chip that way; a single frame is
   // all launch gaps and one long workgroup, so few-frame calls ("wide") take the one-launch pyramid and 1024-thread octree.
   const bool wide = (long long)h->nlevels * nframes <= 32;
-  if (wide && h->chainTiles > 0) hipLaunchKernelGGL(k_pyramid_chain, dim3(h->chainTiles * nframes), dim3(CHAIN_NT), h->chainLds, s, P);
+  // ORBHIP_PRINT_EXTRACT_FORMS (tests/test_gpu_batch_layouts.py): one stderr line per call with the host's choices below
+  const bool printForms = getenv("ORBHIP_PRINT_EXTRACT_FORMS") != nullptr;
+  std::string pyrForm = h->nlevels == 1 ? "none" : "";
+  if (wide && h->chainTiles > 0) { hipLaunchKernelGGL(k_pyramid_chain, dim3(h->chainTiles * nframes), dim3(CHAIN_NT), h->chainLds, s, P); pyrForm = "chain"; }
   else
   for (int l = 1; l < h->nlevels; l++) {
     const LevelGeom &G = h->geom[l], &Gs = h->geom[l - 1];
@@ -698,11 +701,12 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
     // otherwise the one-pass form straight from global memory (tPitch 0), which stages the x table only.
     const int wq = (G.w + 3) & ~3;
     const int tPitch2 = (int)align_up((size_t)wq * 2, 8);                  // horizontally interpolated rows, 16 bits per column
-    const size_t lds2 = (size_t)G.resizeSrcRows * (rowBytes + tPitch2) + 16 * RESIZE_ROWS_MAX;
+    const size_t lds2 = (size_t)G.resizeSrcRows * rowBytes + align_up((size_t)G.resizeSrcRows * tPitch2, 16) + 16 * RESIZE_ROWS_MAX;   // + the row records, 16-byte aligned
     const bool twoPass = G.resizeSrcRows <= RESIZE_MAXSRC && (double)Gs.w / G.w < 3.0 && lds2 <= ORB_LDS_LIMIT - 1024;   // (very wide images: one-pass)
     const int tPitch = twoPass ? tPitch2 : 0;
     const size_t lds = twoPass ? lds2 : (size_t)wq * 8;
     hipLaunchKernelGGL(k_resize, dim3(((G.h + G.resizeRows - 1) / G.resizeRows) * nframes), dim3(256), lds, s, P, l, rowBytes, tPitch, G.resizeSrcRows);
+    if (printForms) pyrForm += std::string(l > 1 ? "," : "") + (!twoPass ? "1p" : G.resizeRows == 16 ? "2p16" : "2p8");
   }
   if (prof) XCHECK(h, hipEventRecord(pev[1], s));
   if (h->totalGroups > 0) hipLaunchKernelGGL(k_fast, dim3(h->totalGroups * nframes), dim3(FAST_NT), 0, s, P);
@@ -722,6 +726,16 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   hipLaunchKernelGGL(k_describe, dim3(std::max((h->totalKp + 3) / 4, 1) * nframes), dim3(256), 0, s, P);   // also writes the frame totals (>= 1 workgroup per frame: nfeatures == 0)
   if (prof) { XCHECK(h, hipEventRecord(pev[5], s)); h->prof_head++; h->stage_valid = true; }
   XCHECK(h, hipGetLastError());
+  if (printForms) {
+    // level 0 is the caller's plane: k_fast, k_resize, k_blur and k_describe take their dword / LDS-DMA paths on it only when its base
+    // and stride are multiples of 4, k_blur's DMA tile load also needs a width that is a multiple of 16 and a level of 160 x 40 or more
+    int aligned0 = 0;
+    for (int f = 0; f < nframes; f++) aligned0 += (((uintptr_t)(d_images + (size_t)f * frame_stride) | (uintptr_t)stride) & 3u) == 0;
+    const LevelGeom &G0 = h->geom[0];
+    const int blur0dma = G0.w >= 160 && G0.h >= 40 && (G0.w & 15) == 0 ? aligned0 : 0;
+    fprintf(stderr, "orbhip: extract nframes %d pyramid %s octree %d/%s aligned0 %d blur0dma %d\n", nframes, pyrForm.c_str(), wide ? 1024 : 256,
+            h->octCellsLds ? "lds" : "global", aligned0, blur0dma);
+  }
   h->last = P;
   h->have_last = true;
   // consumers of this batch on OTHER streams (orbx_compute_stereo_matches, orbx_download_*) order themselves behind it

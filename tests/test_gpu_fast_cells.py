@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import EUROC
+from extract_forms import read_forms
 
 pytestmark = pytest.mark.gpu
 
@@ -118,11 +119,40 @@ def test_partial_groups_coverage():
 
 
 @pytest.mark.parametrize("pad", [1, 3])
-def test_unaligned_rows(pkg, oracle, frame, pad):
-    """A row pitch that is not a multiple of 4 and an unaligned first row: level 0 takes the byte-wise tile path."""
+def test_unaligned_rows(pkg, oracle, frame, capfd, monkeypatch, pad):
+    """A row pitch that is not a multiple of 4 and an unaligned first row.  orbx_extract copies such a view into its aligned staging
+    buffer, so the same view also goes through the batch API, which reads level 0 in place: there level 0 takes the byte-wise tile
+    path (the library's form line reports no aligned level-0 frame)."""
+    import torch
     src = frame(1006)
     big = np.zeros((480, 752 + 2 * pad + 1), np.uint8)
     view = big[:, pad:pad + 752]
     view[:] = src
     assert view.strides[0] % 4 != 0
     check_levels(pkg, oracle, view)
+    monkeypatch.setenv("ORBHIP_PRINT_EXTRACT_FORMS", "1")
+    e = pkg.ORBextractor(**EUROC)
+    o = oracle.OracleExtractor(**EUROC)
+    try:
+        cap = e.configure(480, 752, 1)
+        d_big = torch.from_numpy(big).cuda()
+        d_kps = torch.zeros((cap, 7), dtype=torch.int32, device="cuda")
+        d_desc = torch.zeros((cap, 32), dtype=torch.uint8, device="cuda")
+        d_cnt = torch.zeros((2,), dtype=torch.int32, device="cuda")
+        capfd.readouterr()
+        e.extract_batch_device(d_big.data_ptr() + pad, 480, 752, view.strides[0], 480 * view.strides[0], 1, d_kps.data_ptr(), d_desc.data_ptr(),
+                               d_cnt.data_ptr(), cap, (0, 1000), stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        forms = read_forms(capfd.readouterr().err)
+        assert len(forms) == 1 and forms[0]["aligned0"] == 0 and forms[0]["blur0dma"] == 0, forms
+        img = np.ascontiguousarray(view)
+        pyr = o.pyramid(img)
+        for l in range(EUROC["nlevels"]):
+            assert np.array_equal(e.level_candidates(l), o.level_candidates(pyr[l])), "batch API: FAST candidates level %d" % l
+        mono_r, kps_r, desc_r = o.extract(img, (0, 1000))
+        n = int(d_cnt[0])
+        assert n == len(kps_r) and int(d_cnt[1]) == mono_r
+        assert d_kps[:n].cpu().numpy().tobytes() == kps_r.tobytes()
+        assert np.array_equal(d_desc[:n].cpu().numpy(), desc_r)
+    finally:
+        e.close()
