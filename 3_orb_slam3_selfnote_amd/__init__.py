@@ -32,10 +32,10 @@ ABI_SYMBOLS = [
     "orbx_get_scale_tables", "orbx_get_features_per_level", "orbx_configure", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_get_host_us", "orbx_level_info", "orbx_download_level", "orbx_download_pyramid", "orbx_download_blurred_level",
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
-    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_compute_stereo_matches", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
+    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -54,6 +54,16 @@ class KeyFrameStruct(C.Structure):  # orbm_keyframe_t
 class LastFrameStruct(C.Structure):  # orbm_last_frame_t
     _fields_ = [("n", C.c_int32), ("has_mp", C.c_void_p), ("Xw", C.c_void_p), ("mpdesc", C.c_void_p), ("last_keys", C.c_void_p),
                 ("obs", C.c_void_p), ("Tcw", C.c_void_p), ("Tlw", C.c_void_p)]
+
+
+class LocalMapStruct(C.Structure):  # orbm_local_map_t
+    _fields_ = [("n", C.c_int32), ("eligible", C.c_void_p), ("Xw", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("mpdesc", C.c_void_p), ("obs", C.c_void_p), ("Tcw", C.c_void_p)]
+
+
+class TrackStruct(C.Structure):  # orbm_track_t
+    _fields_ = [("in_view", C.c_void_p), ("proj_x", C.c_void_p), ("proj_y", C.c_void_p), ("proj_xr", C.c_void_p), ("depth", C.c_void_p),
+                ("view_cos", C.c_void_p), ("level", C.c_void_p)]
 
 
 class QueryStruct(C.Structure):  # orbm_queries_t
@@ -124,6 +134,9 @@ def load(build_if_needed=True):
     L.orbx_ref_atanf.argtypes = [f32]
     L.orbx_ref_atan2f.restype = f32
     L.orbx_ref_atan2f.argtypes = [f32, f32]
+    L.orbx_ref_logf.restype = f32
+    L.orbx_ref_logf.argtypes = [f32]
+    L.orbx_logf_device.argtypes = [vp, i32, vp, vp]
     L.orbm_create.restype = vp
     L.orbm_create.argtypes = [i32]
     L.orbm_destroy.argtypes = [vp]
@@ -157,6 +170,9 @@ def load(build_if_needed=True):
                                                        i32, i32, vp, vp]
     L.orbm_search_by_projection_last_frame_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, vp, f32, f32, f32,
                                                                     i32, i32, vp, vp, vp, vp, vp]
+    L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, f32, vp, i32, vp, f32, f32, f32, i32, f32, f32, vp, vp, vp, vp]
+    L.orbm_search_local_points_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, f32, i32, vp, f32, f32, f32,
+                                                        i32, f32, f32, vp, vp, vp, vp, vp, vp]
     L.orbm_three_maxima.argtypes = [vp, i32, vp, vp, vp]
     L.orbm_radius_by_viewing_cos.restype = f32
     L.orbm_radius_by_viewing_cos.argtypes = [f32]
@@ -555,6 +571,37 @@ class ORBmatcher:
             raise OrbError("orbm_search_by_projection_last_frame rc=%d" % rc)
         return rc
 
+    def SearchLocalPoints(self, CurrentFrame, scale_factors, log_scale_factor, eligible, Xw, normal, max_dist, min_dist, mp_desc, Tcw,
+                          cam_type, cam_params, th, bFarPoints=False, thFarPoints=0.0, mbf=0.0, viewing_cos_limit=0.5, mp_obs=None):
+        """Tracking::SearchLocalPoints (Tracking.cc:3449-3539) after the frame's own points are marked: Frame::isInFrustum
+        (Frame.cc:572-661) of every local map point, then SearchByProjection(Frame&, const vector<MapPoint*>&, th, bFarPoints,
+        thFarPoints) (ORBmatcher.cc:44-143), both on the device.  MapPoint fields arrive as arrays: eligible = !isBad() &&
+        mnLastFrameSeen != CurrentFrame.mnId, GetWorldPos(), GetNormal(), raw mfMaxDistance / mfMinDistance, GetDescriptor(),
+        Observations()>0.  CurrentFrame.slot / slot_obs are updated in place.  Returns (nmatches, match_of_point, track): track
+        holds what isInFrustum writes (in_view, proj_x, proj_y, proj_xr, depth, view_cos, level); entries it does not write are 0."""
+        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
+        sf = a(scale_factors, np.float32)
+        elig, Xw, normal = a(eligible, np.uint8), a(Xw, np.float32), a(normal, np.float32)
+        max_dist, min_dist, mp_desc = a(max_dist, np.float32), a(min_dist, np.float32), a(mp_desc, np.uint8)
+        Tcw, cam_params = a(Tcw, np.float32), a(cam_params, np.float32)
+        obs = None if mp_obs is None else a(mp_obs, np.uint8)
+        nmp = len(elig)
+        track = dict(in_view=np.zeros(nmp, np.uint8), proj_x=np.zeros(nmp, np.float32), proj_y=np.zeros(nmp, np.float32),
+                     proj_xr=np.zeros(nmp, np.float32), depth=np.zeros(nmp, np.float32), view_cos=np.zeros(nmp, np.float32),
+                     level=np.zeros(nmp, np.int32))
+        ts = TrackStruct(*[_p(track[k]) for k in ("in_view", "proj_x", "proj_y", "proj_xr", "depth", "view_cos", "level")])
+        ms = LocalMapStruct(nmp, _p(elig), _p(Xw), _p(normal), _p(max_dist), _p(min_dist), _p(mp_desc), _p(obs), _p(Tcw))
+        moq = np.full(nmp, -1, dtype=np.int32)
+        fs = CurrentFrame.struct()
+        rc = self.L.orbm_search_local_points(self.m, C.byref(fs), _p(sf), len(sf), C.c_float(log_scale_factor), C.byref(ms), int(cam_type),
+                                             _p(cam_params), C.c_float(mbf), C.c_float(viewing_cos_limit), C.c_float(th), int(bool(bFarPoints)),
+                                             C.c_float(thFarPoints), C.c_float(self.mfNNratio), _p(CurrentFrame.slot), _p(CurrentFrame.slot_obs),
+                                             _p(moq), C.byref(ts))
+        self._check(rc, "orbm_search_local_points")
+        if rc < 0:
+            raise OrbError("orbm_search_local_points rc=%d" % rc)
+        return rc, moq, track
+
     def SearchByProjectionFisheye(self, F, n_left, left_to_right, right_to_left, mp_desc, scale_factors, th,
                                   in_view, projX, projY, viewCos, level, in_view_r, projXR, projYR, viewCosR, levelR, mp_obs=None):
         """SearchByProjection(Frame &F, const vector<MapPoint*>&, th, ...) for a fisheye-stereo frame (Nleft != -1) --
@@ -835,6 +882,25 @@ class ORBmatcher:
         self._check(rc, "orbm_undistort_keypoints_batch_device")
         if rc < 0:
             raise OrbError("orbm_undistort_keypoints_batch_device rc=%d" % rc)
+
+    def search_local_points_batch_device(self, cur0, frame_stride, d_frame_n, frame_n_stride, map0, map_stride, d_map_n, map_n_stride,
+                                         npairs, scale_factors, log_scale_factor, cam_type, cam_params, th, d_slot, d_slot_obs,
+                                         d_match_of_point, track0, d_nmatches, bFarPoints=False, thFarPoints=0.0, mbf=0.0,
+                                         viewing_cos_limit=0.5, stream=None):
+        """Tracking::SearchLocalPoints for `npairs` (frame, local map) problems resident in HBM (orbm_search_local_points_batch_device).
+        cur0 / map0 / track0: FrameStruct / LocalMapStruct / TrackStruct of problem 0 holding device addresses; the other pointers are
+        device addresses (ints, d_frame_n / d_map_n / d_match_of_point may be None); asynchronous on `stream`."""
+        sf, cam_params = np.ascontiguousarray(scale_factors, dtype=np.float32), np.ascontiguousarray(cam_params, dtype=np.float32)
+        v = lambda x: C.c_void_p(x) if x else None
+        rc = self.L.orbm_search_local_points_batch_device(self.m, C.byref(cur0), int(frame_stride), v(d_frame_n), int(frame_n_stride), C.byref(map0),
+                                                          int(map_stride), v(d_map_n), int(map_n_stride), int(npairs), _p(sf), len(sf),
+                                                          C.c_float(log_scale_factor), int(cam_type), _p(cam_params), C.c_float(mbf),
+                                                          C.c_float(viewing_cos_limit), C.c_float(th), int(bool(bFarPoints)), C.c_float(thFarPoints),
+                                                          C.c_float(self.mfNNratio), v(d_slot), v(d_slot_obs), v(d_match_of_point), C.byref(track0),
+                                                          v(d_nmatches), v(stream))
+        self._check(rc, "orbm_search_local_points_batch_device")
+        if rc < 0:
+            raise OrbError("orbm_search_local_points_batch_device rc=%d" % rc)
 
     def set_profiling(self, on=True):
         self.L.orbm_set_profiling(self.m, 1 if on else 0)

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "orb_atan2f.h"
+#include "orb_logf.h"
 #include "orb_sincos.h"
 
 struct LastFrameParams {
@@ -39,6 +40,18 @@ __device__ __forceinline__ void dev_mat3_mul_add(const float *R, const float *x,
   for (int i = 0; i < 3; i++) {
     const float t0 = R[i * 4 + 0] * x[0] + R[i * 4 + 1] * x[1] + R[i * 4 + 2] * x[2];
     out[i] = (float)((double)t0 + (double)t[i]);
+  }
+}
+
+// -Rcw.t()*tcw (ORBmatcher.cc:2041, Frame::UpdatePoseMatrices Frame.cc:538): the generic gemm path, double accumulation, alpha = -1.
+// T: row-major 4x4, tcw = column 3.
+__device__ __forceinline__ void dev_camera_centre(const float *T, float *Ow) {
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) s += (double)T[k * 4 + a] * (double)T[k * 4 + 3];
+    Ow[a] = (float)(s * -1.0);
   }
 }
 
@@ -79,13 +92,7 @@ __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
     const float *Tcw = P.Tcw + (size_t)p * 16, *Tlw = P.Tlw + (size_t)p * 16;
     const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, tlw[3] = {Tlw[3], Tlw[7], Tlw[11]};
     float twc[3], tlc[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {  // twc = -Rcw.t()*tcw (:2041): generic gemm path, double accumulation, alpha = -1
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) s += (double)Tcw[k * 4 + a] * (double)tcw[k];
-      twc[a] = (float)(s * -1.0);
-    }
+    dev_camera_centre(Tcw, twc);           // :2041
     dev_mat3_mul_add(Tlw, twc, tlw, tlc);  // :2047
     const bool bForward = tlc[2] > P.mb && !P.bMono, bBackward = -tlc[2] > P.mb && !P.bMono;  // :2051-2052
     const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
@@ -110,6 +117,127 @@ __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
   }
   P.qu[o] = u; P.qv[o] = v; P.qr[o] = rad; P.qur[o] = ur;
   P.qminl[o] = minl; P.qmaxl[o] = maxl; P.qflags[o] = fl;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Tracking::SearchLocalPoints (Tracking.cc:3449-3539): Frame::isInFrustum(pMP, viewingCosLimit) for every local map point
+// (Frame.cc:572-661, Nleft == -1) with MapPoint::PredictScale (MapPoint.cc:587-602) through the glibc logf replica
+// (orb_logf.h), then the query preparation of SearchByProjection(Frame&, const vector<MapPoint*>&, th, bFarPoints,
+// thFarPoints) (ORBmatcher.cc:44-73) in front of k_match_walk / k_match_scan / k_match_resolve.  One thread per local map
+// point; the frame's pose is read per problem.
+// ------------------------------------------------------------------------------------------------------------
+struct LocalMapParams {
+  // local map side; problem p is at element offset p * map_stride
+  const uint8_t *eligible;          // !pMP->isBad() && pMP->mnLastFrameSeen != CurrentFrame.mnId
+  const float *Xw, *normal;         // GetWorldPos(), GetNormal(): 3 floats per point
+  const float *max_dist, *min_dist; // raw mfMaxDistance / mfMinDistance
+  const uint8_t *obs;               // Observations() > 0, or NULL = all 1
+  const float *Tcw;                 // CurrentFrame.mTcw, row-major 4x4 per problem
+  int map_stride;
+  const int32_t *map_n; int map_n_stride; int map_n_const;
+  // current frame: image bounds, scale factors, camera
+  float min_x, max_x, min_y, max_y;
+  float sf[16]; int nlevels; float log_sf;
+  int cam_type; float cam[8];
+  float mbf, view_cos_limit, th; int bFarPoints; float th_far;
+  // out: the MapPoint fields isInFrustum writes (caller arrays, same stride)
+  uint8_t *in_view; float *proj_x, *proj_y, *proj_xr, *depth, *view_cos; int32_t *level;
+  // out: the query arrays of the projection search (same stride)
+  float *qu, *qv, *qr, *qur;
+  int32_t *qminl, *qmaxl;
+  uint8_t *qflags;
+};
+
+// (int) of a float as the reference build converts it (x86 cvttss2si): NaN and values outside the int range give INT_MIN,
+// where gfx950's v_cvt_i32_f32 would saturate
+__device__ __forceinline__ int x86_cvtt_f32_i32(float x) {
+  return (x != x || x >= 2147483648.0f || x < -2147483648.0f) ? (int)0x80000000u : (int)x;
+}
+
+// cv::norm of a 3-vector of floats (NORM_L2: squares summed in double, sqrt in double)
+__device__ __forceinline__ float dev_norm3(const float *a) {
+  double s = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) s += (double)a[k] * (double)a[k];
+  return (float)sqrt(s);
+}
+
+__global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
+  const int p = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = P.map_n ? min(P.map_n[(size_t)p * P.map_n_stride], P.map_stride) : P.map_n_const;
+  if (i >= P.map_stride) return;
+  const size_t o = (size_t)p * P.map_stride + i;
+  float u = 0.f, v = 0.f, rad = 0.f, ur = 0.f;
+  int minl = -1, maxl = -1;
+  uint8_t fl = 0;
+  if (i < n) {
+    if (!P.eligible[o]) {
+      P.in_view[o] = 0;
+    } else {
+      const float *T = P.Tcw + (size_t)p * 16;
+      const float tcw[3] = {T[3], T[7], T[11]};
+      float Ow[3];
+      dev_camera_centre(T, Ow);                                   // mOw, Frame.cc:538
+      const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
+      float pc[3];
+      dev_mat3_mul_add(T, xw, tcw, pc);                           // Pc = mRcw*P + mtcw (Frame.cc:586)
+      const float pc_dist = dev_norm3(pc);                        // :587
+      const float invz = 1.0f / pc[2];                            // :591, float division
+      bool in_view = false;
+      float px = -1.f, py = -1.f;                                 // :577-578
+      float vcos = 0.f;
+      int lvl = 0;
+      if (!(pc[2] < 0.0f)) {                                      // :592 (-0 and +0 pass)
+        float ux, vy;
+        dev_project(P.cam_type, P.cam, pc[0], pc[1], pc[2], ux, vy);   // :595
+        if (!(ux < P.min_x || ux > P.max_x) && !(vy < P.min_y || vy > P.max_y)) {   // :599-602; a NaN projection passes
+          px = ux; py = vy;                                       // :605-606
+          const float po[3] = {xw[0] - Ow[0], xw[1] - Ow[1], xw[2] - Ow[2]};
+          const float dist = dev_norm3(po);                       // :612
+          const float maxD = 1.2f * P.max_dist[o], minD = 0.8f * P.min_dist[o];   // MapPoint.cc:555-565
+          if (!(dist < minD || dist > maxD)) {                    // :614
+            const float pn[3] = {P.normal[3 * o], P.normal[3 * o + 1], P.normal[3 * o + 2]};
+            double d = 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) d += (double)po[k] * (double)pn[k];
+            vcos = (float)(d / (double)dist);                     // :624, Mat::dot in double
+            if (!(vcos < P.view_cos_limit)) {                     // :626
+              const float ratio = P.max_dist[o] / dist;           // PredictScale, MapPoint.cc:593-596
+              lvl = x86_cvtt_f32_i32(ceilf(orblg::ref_logf(ratio) / P.log_sf));
+              if (lvl < 0) lvl = 0;
+              else if (lvl >= P.nlevels) lvl = P.nlevels - 1;
+              in_view = true;
+            }
+          }
+        }
+      }
+      P.in_view[o] = in_view ? 1 : 0;
+      P.proj_x[o] = px; P.proj_y[o] = py;
+      if (in_view) {                                              // :635-644
+        const float xr = px - P.mbf * invz;
+        P.proj_xr[o] = xr; P.depth[o] = pc_dist; P.level[o] = lvl; P.view_cos[o] = vcos;
+        // ORBmatcher.cc:52-73.  A NaN projection finds no candidate in the reference (every |dx| < r test is false): left out.
+        if (!(P.bFarPoints && pc_dist > P.th_far) && px == px && py == py) {
+          float r = ((double)vcos > 0.998) ? 2.5f : 4.0f;         // RadiusByViewingCos, :216-222
+          if (P.th != 1.0f) r *= P.th;                            // :47, :69-70
+          u = px; v = py; rad = r * P.sf[lvl];                    // :73
+          minl = lvl - 1; maxl = lvl;
+          ur = xr;
+          fl = (uint8_t)(1u | ((P.obs ? (P.obs[o] & 1u) : 1u) << 1));
+        }
+      }
+    }
+  }
+  P.qu[o] = u; P.qv[o] = v; P.qr[o] = rad; P.qur[o] = ur;
+  P.qminl[o] = minl; P.qmaxl[o] = maxl; P.qflags[o] = fl;
+}
+
+// The device build of the logf replica on n floats (orbx_logf_device): lets the tests compare it with the host build, which
+// tests/test_logf_replica.py compares with the host libm.
+__global__ __launch_bounds__(256) void k_ref_logf(const float *x, int n, float *y) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) y[i] = orblg::ref_logf(x[i]);
 }
 
 struct RotPruneParams {

@@ -180,6 +180,13 @@ float orbx_ref_cosf(float x) { return orbsc::ref_cosf(x); }
 float orbx_ref_sinf(float x) { return orbsc::ref_sinf(x); }
 float orbx_ref_atanf(float x) { return orbat::ref_atanf(x); }
 float orbx_ref_atan2f(float y, float x) { return orbat::ref_atan2f(y, x); }
+float orbx_ref_logf(float x) { return orblg::ref_logf(x); }
+int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream) {
+  if (n < 0 || (n > 0 && (!d_x || !d_y))) return ORBX_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_ref_logf, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, n, d_y);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
 
 orbx_t *orbx_create(int nfeatures, float scaleFactor_, int nlevels, int iniThFAST, int minThFAST, int device) {
   if (nfeatures < 0 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !(scaleFactor_ > 1.0f)) return nullptr;
@@ -1094,6 +1101,7 @@ struct orbm_handle {
   DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
   DevBuf d_cand;      // fused k_match_resolve: every pair's descriptors and candidate records in sorted order (48 B per keypoint)
   DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
+  DevBuf d_lmq;       // query arrays written by k_local_map_project (orbm_search_local_points*): never shared with d_lfq
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
   bool profiling = false;
   hipEvent_t ev[PROF_DEPTH][3] = {};
@@ -1183,7 +1191,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_tri_count, &m->d_tri_keys};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_tri_count, &m->d_tri_keys};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -1703,6 +1711,142 @@ int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, con
   memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
   int32_t nm = 0;
   memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
+  return nm;
+}
+
+// Tracking::SearchLocalPoints on the device: k_local_map_project (isInFrustum + the query preparation of M2), then the M2 search
+// (use_second, nnratio, TH_HIGH) with sequential claims in local-map order.  Arguments are checked before anything is launched.
+static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
+                              const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs, const float *sf,
+                              int nlevels, float log_sf, int cam_type, const float *cam_params, float mbf, float view_cos_limit, float th,
+                              int bFarPoints, float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
+                              const orbm_track_t *track0, int32_t *d_nmatches, hipStream_t s, bool search) {
+  if (!m || !cur0 || !map0 || !track0 || !sf || !cam_params || npairs <= 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
+  if (!map0->eligible || !map0->Xw || !map0->normal || !map0->max_dist || !map0->min_dist || !map0->mpdesc || !map0->Tcw) return ORBX_E_ARG;
+  if (!track0->in_view || !track0->proj_x || !track0->proj_y || !track0->proj_xr || !track0->depth || !track0->view_cos || !track0->level)
+    return ORBX_E_ARG;
+  if (search && (!cur0->keys_un || !cur0->descriptors)) return ORBX_E_ARG;
+  const int maxq = d_map_n ? map_stride : map0->n;
+  const int maxn = d_frame_n ? frame_stride : cur0->n;
+  if (maxq <= 0 || map_stride < maxq || map0->n < 0 || (!d_map_n && map_stride < map0->n)) return ORBX_E_ARG;
+  if (search && (maxn <= 0 || frame_stride < maxn || (!d_frame_n && frame_stride < cur0->n))) return ORBX_E_ARG;
+  if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
+  if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
+  MCHECK(m, hipSetDevice(m->device));
+  // scratch: the query arrays the projection kernel writes (29 B per query) - grows on demand, not on the steady-state path
+  const size_t nqa = (size_t)(npairs - 1) * map_stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
+  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
+  if (need > m->d_lmq.bytes) {
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, m->d_lmq.reserve(need + (need >> 2)));
+  }
+  float *qf = (float *)m->d_lmq.p;
+  int32_t *qi = (int32_t *)(qf + 4 * nq4);
+  uint8_t *qfl = (uint8_t *)(qi + 3 * nq4);
+  LocalMapParams P;
+  memset(&P, 0, sizeof(P));
+  P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
+  P.obs = map0->obs; P.Tcw = map0->Tcw;
+  P.map_stride = map_stride; P.map_n = d_map_n; P.map_n_stride = map_n_stride; P.map_n_const = map0->n;
+  P.min_x = cur0->min_x; P.max_x = cur0->max_x; P.min_y = cur0->min_y; P.max_y = cur0->max_y;
+  for (int l = 0; l < nlevels; l++) P.sf[l] = sf[l];
+  P.nlevels = nlevels; P.log_sf = log_sf;
+  P.cam_type = cam_type;
+  for (int k = 0; k < (cam_type == 0 ? 4 : 8); k++) P.cam[k] = cam_params[k];
+  P.mbf = mbf; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
+  P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
+  P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
+  P.qu = qf; P.qv = qf + nq4; P.qr = qf + 2 * nq4; P.qur = qf + 3 * nq4;
+  P.qminl = qi; P.qmaxl = qi + nq4; P.qflags = qfl;
+  hipLaunchKernelGGL(k_local_map_project, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P);
+  if (search) {
+    orbm_queries_t q;
+    q.nq = map0->n; q.descriptors = map0->mpdesc; q.u = P.qu; q.v = P.qv; q.radius = P.qr;
+    q.min_level = P.qminl; q.max_level = P.qmaxl; q.u_r = cur0->u_right ? P.qur : nullptr; q.flags = P.qflags;
+    SearchOpts o;
+    o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
+    const int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, map_stride, d_map_n, map_n_stride, npairs, nnratio,
+                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, d_moq ? d_moq : qi + 2 * nq4, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-139
+    if (rc < 0) return rc;
+  }
+  MCHECK(m, hipGetLastError());
+  return 0;
+}
+
+int orbm_search_local_points_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
+                                          const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs,
+                                          const float *sf, int nlevels, float log_sf, int cam_type, const float *cam_params, float mbf,
+                                          float view_cos_limit, float th, int bFarPoints, float th_far, float nnratio, int32_t *d_slot,
+                                          uint8_t *d_slot_obs, int32_t *d_moq, const orbm_track_t *track0, int32_t *d_nmatches, void *stream_) {
+  if (!m) return ORBX_E_ARG;
+  return search_local_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, map0, map_stride, d_map_n, map_n_stride, npairs, sf, nlevels, log_sf,
+                            cam_type, cam_params, mbf, view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, track0,
+                            d_nmatches, (hipStream_t)stream_, true);
+}
+
+int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, float log_sf, const orbm_local_map_t *map,
+                             int cam_type, const float *cam_params, float mbf, float view_cos_limit, float th, int bFarPoints, float th_far,
+                             float nnratio, int32_t *slot, uint8_t *slot_obs, int32_t *match_of_point, const orbm_track_t *track) {
+  if (!m || !cur || !map || !track || !sf || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
+  if (!map->eligible || !map->Xw || !map->normal || !map->max_dist || !map->min_dist || !map->mpdesc || !map->Tcw) return ORBX_E_ARG;
+  if (!track->in_view || !track->proj_x || !track->proj_y || !track->proj_xr || !track->depth || !track->view_cos || !track->level) return ORBX_E_ARG;
+  const int n = cur->n, nmp = map->n;
+  if (n < 0 || nmp < 0) return ORBX_E_ARG;
+  if (n > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
+  if (n > 0 && (!cur->keys_un || !cur->descriptors || !(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y))) return ORBX_E_ARG;
+  if (nmp == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  // one staged block up, one block down, one synchronisation; a frame without keypoints still gets its track fields
+  const size_t fp = sizeof(float) * (size_t)nmp;
+  enum { KP, DESC, UR, ELIG, XW, NRM, MAXD, MIND, MD, OBS, TC, SLOT, SOBS, MOQ, INV, PX, PY, PXR, DEP, VC, LVL, NM, NPARTS };
+  void *d[NPARTS];
+  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
+                              {cur->u_right, cur->u_right ? sizeof(float) * (size_t)n : 0}, {map->eligible, (size_t)nmp}, {map->Xw, 3 * fp},
+                              {map->normal, 3 * fp}, {map->max_dist, fp}, {map->min_dist, fp}, {map->mpdesc, 32 * (size_t)nmp},
+                              {map->obs, map->obs ? (size_t)nmp : 0}, {map->Tcw, 16 * sizeof(float)},
+                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t) * (size_t)nmp},
+                              {nullptr, (size_t)nmp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp},
+                              {nullptr, sizeof(int32_t)}}, d, true);
+  if (rc < 0) return rc;
+  orbm_frame_t df = *cur;
+  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
+  orbm_local_map_t dm = *map;
+  dm.eligible = (const uint8_t *)d[ELIG]; dm.Xw = (const float *)d[XW]; dm.normal = (const float *)d[NRM]; dm.max_dist = (const float *)d[MAXD];
+  dm.min_dist = (const float *)d[MIND]; dm.mpdesc = (const uint8_t *)d[MD]; dm.obs = (const uint8_t *)d[OBS]; dm.Tcw = (const float *)d[TC];
+  orbm_track_t dt;
+  dt.in_view = (uint8_t *)d[INV]; dt.proj_x = (float *)d[PX]; dt.proj_y = (float *)d[PY]; dt.proj_xr = (float *)d[PXR];
+  dt.depth = (float *)d[DEP]; dt.view_cos = (float *)d[VC]; dt.level = (int32_t *)d[LVL];
+  int32_t *dslot = n > 0 ? (int32_t *)d[SLOT] : (int32_t *)d[MOQ], *dnm = (int32_t *)d[NM];   // n == 0: no search, any non-null pointer
+  uint8_t *dsobs = n > 0 ? (uint8_t *)d[SOBS] : (uint8_t *)d[INV];
+  const int rs = search_local_batch(m, &df, n, nullptr, 0, &dm, nmp, nullptr, 0, 1, sf, nlevels, log_sf, cam_type, cam_params, mbf, view_cos_limit,
+                                    th, bFarPoints, th_far, nnratio, dslot, dsobs, (int32_t *)d[MOQ], &dt, dnm, s, n > 0);
+  if (rs < 0) return rs;
+  uint8_t *first = n > 0 ? (uint8_t *)d[SLOT] : (uint8_t *)d[MOQ];
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, first), first, (uint8_t *)d[NM] + sizeof(int32_t) - first, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  int32_t nm = 0;
+  if (n > 0) {
+    memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
+    memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
+    memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
+  }
+  const int32_t *moq = (const int32_t *)mirror_of(m, d[MOQ]);
+  const uint8_t *inv = (const uint8_t *)mirror_of(m, d[INV]);
+  const float *px = (const float *)mirror_of(m, d[PX]), *py = (const float *)mirror_of(m, d[PY]), *pxr = (const float *)mirror_of(m, d[PXR]);
+  const float *dep = (const float *)mirror_of(m, d[DEP]), *vc = (const float *)mirror_of(m, d[VC]);
+  const int32_t *lvl = (const int32_t *)mirror_of(m, d[LVL]);
+  // only what isInFrustum writes: in_view always, the projection of eligible points, the rest where in view
+  for (int i = 0; i < nmp; i++) {
+    if (match_of_point) match_of_point[i] = n > 0 ? moq[i] : -1;
+    track->in_view[i] = inv[i];
+    if (!map->eligible[i]) continue;
+    track->proj_x[i] = px[i]; track->proj_y[i] = py[i];
+    if (!inv[i]) continue;
+    track->proj_xr[i] = pxr[i]; track->depth[i] = dep[i]; track->view_cos[i] = vc[i]; track->level[i] = lvl[i];
+  }
   return nm;
 }
 

@@ -183,3 +183,62 @@ def make_last_frame_scene(cam_type, params, kx, ky, shift, seed, tz=0.0):
     Tcw[:3, :3] = R.astype(np.float32)
     Tcw[:3, 3] = t.astype(np.float32)
     return np.ascontiguousarray(Xw.astype(np.float32)), Tcw, np.eye(4, dtype=np.float32)
+
+
+def make_local_map_scene(cam_type, params, k0, d0, k1, shift, seed, scale_factors, W, H, nmap=3000, mbf=0.0):
+    """Inputs of Tracking::SearchLocalPoints (Tracking.cc:3449-3539) over a shifted synthetic stream: k0 / d0 = the previous frame's
+    keypoints and descriptors, k1 = the current frame's keypoints, shift = where k0's content moved to.  The first local map points
+    sit on the rays of k0's keypoints (make_last_frame_scene: they reproject onto the current frame's keypoints), the rest are random
+    points in and around the view (5 % behind the camera) with random descriptors.  mfMaxDistance = distance x scale factor of the
+    keypoint's octave x U(0.93, 1.02), mfMinDistance = mfMaxDistance / scale factor of the last level, 3 % of the points beyond each
+    distance gate; normals tilted from the viewing ray (a quarter of them by up to 80 degrees); 90 % eligible, 90 % observed.  The
+    current frame already holds 8 % of its keypoints (half of them with observations).  mbf > 0: mvuRight of the current frame,
+    consistent with the depth of the point seen there for 80 % of the keypoints.  Draws from numpy's PCG64 seeded with `seed`.
+    Returns a dict: Xw, desc, normal, max_dist, min_dist, eligible, obs (local-map order), Tcw, slot, slot_obs, u_right (or None)."""
+    Xw0, Tcw, _ = make_last_frame_scene(cam_type, params, k0["x"], k0["y"], shift, seed)
+    sf = np.asarray(scale_factors, np.float32)
+    rng = np.random.default_rng(seed)
+    n0 = min(len(k0), nmap)
+    ne = nmap - n0
+    R, t = Tcw[:3, :3].astype(np.float64), Tcw[:3, 3].astype(np.float64)
+    u, v = rng.uniform(-60, W + 60, ne), rng.uniform(-60, H + 60, ne)
+    rays = kb8_unproject(params, u, v) if cam_type == 1 else pinhole_unproject(params, u, v)
+    Xc = rays * rng.uniform(0.5, 12.0, ne)[:, None]
+    Xc[rng.random(ne) < 0.05, 2] *= -1                                # behind the camera
+    Xe = ((Xc - t[None, :]) @ R).astype(np.float32)
+    Xw = np.concatenate([Xw0[:n0], Xe]).astype(np.float32)
+    desc = np.concatenate([d0[:n0], rng.integers(0, 256, (ne, 32), dtype=np.uint8)])
+    octv = np.concatenate([k0["octave"][:n0], rng.integers(0, 8, ne)]).astype(np.int64)
+    Ow = np.array([-sum(float(Tcw[k, a]) * float(Tcw[k, 3]) for k in range(3)) for a in range(3)], np.float32).astype(np.float64)
+    PO = Xw.astype(np.float64) - Ow[None, :]
+    dist = np.linalg.norm(PO, axis=1)
+    maxd = dist * sf[octv] * rng.uniform(0.93, 1.02, nmap)
+    gate = rng.random(nmap)
+    maxd[gate < 0.03] *= 0.6                                          # beyond 1.2 x mfMaxDistance
+    near = (gate >= 0.03) & (gate < 0.06)
+    mind = maxd / sf[len(sf) - 1]
+    mind[near] = dist[near] * 1.5                                     # below 0.8 x mfMinDistance
+    dirn = PO / dist[:, None]
+    tilt = np.where(rng.random(nmap) < 0.25, rng.uniform(0, 1.4, nmap), rng.uniform(0, 0.08, nmap))
+    perp = np.cross(dirn, rng.normal(size=(nmap, 3)))
+    perp /= np.linalg.norm(perp, axis=1)[:, None]
+    normal = (dirn * np.cos(tilt)[:, None] + perp * np.sin(tilt)[:, None]).astype(np.float32)
+    eligible = (rng.random(nmap) < 0.9).astype(np.uint8)
+    obs = (rng.random(nmap) < 0.9).astype(np.uint8)
+    perm = rng.permutation(nmap)                                      # local-map order mixes both kinds (claims are sequential)
+    n1 = len(k1)
+    slot = np.full(n1, -1, np.int32)
+    pre = rng.random(n1) < 0.08
+    slot[pre] = rng.integers(0, 5000, pre.sum())
+    slot_obs = (pre & (rng.random(n1) < 0.5)).astype(np.uint8)
+    u_right = None
+    if mbf > 0:
+        zc = (Xw0[:n0].astype(np.float64) @ R.T + t[None, :])[:, 2]
+        px, py = k0["x"][:n0] + shift[0], k0["y"][:n0] + shift[1]
+        d2 = (k1["x"][:, None] - px[None, :]) ** 2 + (k1["y"][:, None] - py[None, :]) ** 2
+        j = np.argmin(d2, axis=1)
+        ur = np.where(d2[np.arange(n1), j] < 1.0, k1["x"] - mbf / zc[j] + rng.uniform(-1.5, 1.5, n1), k1["x"] - rng.uniform(3, 30, n1))
+        u_right = np.where(rng.random(n1) < 0.8, ur, -1.0).astype(np.float32)
+    c = lambda a: np.ascontiguousarray(a[perm])
+    return dict(Xw=c(Xw), desc=c(desc), normal=c(normal), max_dist=c(maxd.astype(np.float32)), min_dist=c(mind.astype(np.float32)),
+                eligible=c(eligible), obs=c(obs), Tcw=Tcw, slot=slot, slot_obs=slot_obs, u_right=u_right)

@@ -129,6 +129,12 @@ float orbx_ref_sinf(float x);
  * KannalaBrandt8::project (KannalaBrandt8.cpp:31-32), csrc/orb_atan2f.h. */
 float orbx_ref_atanf(float x);
 float orbx_ref_atan2f(float y, float x);
+/* ... and of glibc's logf (ARM optimized-routines, glibc >= 2.28) that MapPoint::PredictScale calls (MapPoint.cc:587-602),
+ * csrc/orb_logf.h: the level prediction of orbm_search_local_points on the device. */
+float orbx_ref_logf(float x);
+/* The same replica evaluated by the DEVICE: d_y[i] = logf(d_x[i]) for i < n, device pointers, asynchronous on `stream`
+ * (tests/test_gpu_local_points.py compares it with orbx_ref_logf).  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
+int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream);
 
 /* cv::cvtColor(im, gray, CV_RGB2GRAY | CV_BGR2GRAY | CV_RGBA2GRAY | CV_BGRA2GRAY) of Tracking::GrabImageMonocular / Stereo / RGBD
  * (Tracking.cc:1122-1135) for 8-bit input: channels = 3 or 4, rgb_order != 0 for RGB(A), 0 for BGR(A).
@@ -278,6 +284,63 @@ int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_fram
                                                       int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th,
                                                       int bMono, int checkOri, int32_t *d_slot, uint8_t *d_slot_obs,
                                                       int32_t *d_match_of_query, int32_t *d_nmatches, void *stream);
+
+/* void Tracking::SearchLocalPoints()  (Tracking.cc:3449-3539, Frame::Nleft == -1) after its first loop (the frame's own points
+ * marked, :3453-3471): Frame::isInFrustum(pMP, viewing_cos_limit) (Frame.cc:572-661) for every local map point, then
+ * int ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, th, bFarPoints, thFarPoints)
+ * (ORBmatcher.cc:44-143) over the same points, all on the device.  MapPoint::PredictScale (MapPoint.cc:587-602) goes through
+ * the bit-exact replica of glibc's logf (csrc/orb_logf.h, orbx_ref_logf).
+ * Local map point i, problem p at element offset p * map_stride (Tracking::mvpLocalMapPoints, flattened): */
+typedef struct {
+  int32_t n;                        /* mvpLocalMapPoints.size(); the live count when d_map_n is NULL */
+  const uint8_t *eligible;          /* !pMP->isBad() && pMP->mnLastFrameSeen != CurrentFrame.mnId (Tracking.cc:3455-3468, :3483-3487) */
+  const float *Xw;                  /* pMP->GetWorldPos(), 3 floats per point (Frame.cc:581) */
+  const float *normal;              /* pMP->GetNormal(), 3 floats per point (Frame.cc:620) */
+  const float *max_dist, *min_dist; /* raw mfMaxDistance / mfMinDistance: the 1.2 / 0.8 factors of GetMax/MinDistanceInvariance
+                                       (MapPoint.cc:555-565) and PredictScale's ratio (MapPoint.cc:593) are applied inside */
+  const uint8_t *mpdesc;            /* pMP->GetDescriptor(), 32 bytes per point (ORBmatcher.cc:76) */
+  const uint8_t *obs;               /* pMP->Observations() > 0 (ORBmatcher.cc:89-91), or NULL = all 1 */
+  const float *Tcw;                 /* CurrentFrame.mTcw (the pose after Optimizer::PoseOptimization), row-major 4x4 per problem */
+} orbm_local_map_t;
+/* What isInFrustum writes into the MapPoint, per local map point (same indexing, caller arrays).  Eligible points: in_view =
+ * mbTrackInView (Frame.cc:576, :635), proj_x / proj_y = mTrackProjX / Y (-1 unless the projection is inside the image bounds,
+ * :577-578, :605-606), and where in_view is set proj_xr = mTrackProjXR = u - mbf / z, depth = mTrackDepth = |Pc|,
+ * level = mnTrackScaleLevel, view_cos = mTrackViewCos (:636-644); the other fields of an eligible point and every field but
+ * in_view = 0 of an ineligible one are left as they were. */
+typedef struct {
+  uint8_t *in_view;
+  float *proj_x, *proj_y, *proj_xr, *depth, *view_cos;
+  int32_t *level;
+} orbm_track_t;
+/* Host pointers.  cur: the current frame (u_right = mvuRight or NULL; bounds mnMinX..mnMaxY); scale_factors /
+ * log_scale_factor / nlevels = mvScaleFactors / mfLogScaleFactor / mnScaleLevels; cam_type / cam_params as in orbm_project;
+ * mbf = CurrentFrame.mbf; viewing_cos_limit = 0.5 in the reference (Tracking.cc:3490); th, bFarPoints, thFarPoints, nnratio as
+ * passed to SearchByProjection (th picked at Tracking.cc:3509-3534, nnratio 0.8 at :3508).  A map point takes part in the
+ * search iff it is in view, eligible and not a far point (:52-59); the window is RadiusByViewingCos(mTrackViewCos) (x th when
+ * th != 1) x mvScaleFactors[level], levels [level - 1, level] (:63-73); with u_right, the right-coordinate check uses proj_xr
+ * (:93-98).  Claims are sequential in local-map order; slot / slot_obs (in/out) as in orbm_search_by_projection (the frame's
+ * mvpMapPoints after the last-frame / reference-keyframe search and the outlier removal).  match_of_point[n] (out, may be
+ * NULL) = keypoint matched by local map point i or -1.  One staged upload, the projection kernel and the search kernels, one
+ * download, one synchronisation.  Returns nmatches; ORBX_E_ARG for nlevels outside [1, 16], cam_type not 0 / 1, a missing
+ * required pointer (every field of map but obs, every field of track, slot, slot_obs) or a frame above ORBM_MAX_KEYPOINTS. */
+int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *scale_factors, int nlevels, float log_scale_factor,
+                             const orbm_local_map_t *map, int cam_type, const float *cam_params, float mbf, float viewing_cos_limit,
+                             float th, int bFarPoints, float thFarPoints, float nnratio, int32_t *slot, uint8_t *slot_obs,
+                             int32_t *match_of_point, const orbm_track_t *track);
+/* Batched device form: `npairs` independent (current frame, local map) problems resident in HBM, asynchronous on `stream`,
+ * nothing touches the host.  The keypoint-indexed arrays of problem p at element offset p * frame_stride (live counts
+ * d_frame_n[p * frame_n_stride], or cur0->n when d_frame_n is NULL), the arrays of map0 and track0 at element offset
+ * p * map_stride (live counts d_map_n[p * map_n_stride], or map0->n), Tcw 16 floats per problem.  scale_factors / cam_params
+ * are HOST arrays (copied into the kernel arguments).  d_slot / d_slot_obs [npairs][frame_stride] in/out,
+ * d_match_of_point [npairs][map_stride] (out, may be NULL), d_nmatches[npairs] out.  The search windows only exist after the
+ * projection kernel has run, so walk or scan is voted per problem on the device (unless orbm_set_scan_mode forces it).
+ * ORBX_E_ARG as the host form, and when map_stride / frame_stride is below map0->n / cur0->n without device counts. */
+int orbm_search_local_points_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                          int frame_n_stride, const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n,
+                                          int map_n_stride, int npairs, const float *scale_factors, int nlevels, float log_scale_factor,
+                                          int cam_type, const float *cam_params, float mbf, float viewing_cos_limit, float th,
+                                          int bFarPoints, float thFarPoints, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs,
+                                          int32_t *d_match_of_point, const orbm_track_t *track0, int32_t *d_nmatches, void *stream);
 
 /* The same two members for a fisheye-stereo frame (Frame::Nleft != -1): ORBmatcher.cc:44-214 with its second half
  * (:145-211, right camera) and ORBmatcher.cc:2027-2289 with its extra pass (:2189-2256).
