@@ -17,6 +17,13 @@
 #define FAST_TILE_ROWS 76      // tallest group window: two cells of up to 35 rows + 6 (a single cell: up to 59 + 6)
 #define FAST_S_PITCH 64  // score plane incl. 1-px zero ring: <= 61 columns
 
+// k_describe: keypoint slots per wavefront in batch calls (few-frame calls: 1), and the workgroups (four wavefronts) a frame's totalKp
+// slots then take; at least one, which writes the frame's totals.  4, 8 or 16: 8 measured best (open item 6).
+#ifndef ORB_DESCRIBE_K
+#define ORB_DESCRIBE_K 8
+#endif
+#define ORB_DESCRIBE_GROUPS(totalKp, K) ((((totalKp) + (K) - 1) / (K) + 3) / 4 > 1 ? (((totalKp) + (K) - 1) / (K) + 3) / 4 : 1)
+
 // Geometry of one pyramid level; filled on the host (orbx_configure), read by every kernel.
 struct LevelGeom {
   int w, h;          // level image size (ORBextractor.cc:1192-1193)

@@ -6,7 +6,8 @@
 //   k_fast      K2  FAST-9/16 score + per-cell NMS, cell detected at iniThFAST and again at minThFAST if empty, one wavefront per 30-px cell
 //   k_octree    K3  DistributeOctTree, one workgroup per (frame, level), node list in LDS
 //   k_blur      K5  7x7 sigma-2 fixed-point Gaussian as two int8 MFMA products, 128x32 tiles staged through LDS
-//   k_describe  K4+K6+K7  IC_Angle + steered BRIEF + lapping-order scatter + frame totals, one wavefront (64 lanes) per keypoint
+//   k_describe  K4+K6+K7  IC_Angle + steered BRIEF + lapping-order scatter + frame totals, one wavefront per block of 8 keypoint slots
+//                         (one per keypoint in few-frame calls)
 // All arithmetic is integer or non-contracted IEEE fp32/fp64 (hipcc -ffp-contract=off) so results are bit-exact
 // against the CPU restatement the tests use.  No MFMA: this is byte/bit work bound by HBM, LDS and VALU integer rate.
 #pragma once
@@ -1352,7 +1353,9 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {  // cv::fast
 
 struct KpOut { float x, y, size, angle, response; int32_t octave, class_id; };
 
-__global__ __launch_bounds__(256) void k_describe(FrameParams P) {
+// K = 1, one keypoint per wavefront: the form of few-frame ("wide") calls, whose ~1000 keypoints per frame have to spread over the
+// whole chip.  Four wavefronts per workgroup, grid = ceil(totalKp / 4) workgroups per frame.
+__device__ __forceinline__ void describe_one(const FrameParams &P) {
   const int lane = threadIdx.x & 63;
   int frame, blk;
   xcd_map((P.totalKp + 3) / 4, P.magicKpBlk, P.nframes, frame, blk);
@@ -1493,6 +1496,267 @@ __global__ __launch_bounds__(256) void k_describe(FrameParams P) {
       reinterpret_cast<KpOut *>(P.out_kps)[(size_t)frame * P.cap + dst] = k;
     }
   }
+}
+
+// K = 4, 8 or 16 (ORB_DESCRIBE_K), the batch form: a wavefront owns K consecutive keypoint slots of one frame.  Whatever has one value per keypoint (level,
+// lapping slot, angle, cosine, sine, the KpOut record) is computed once for the block with lane = keypoint, whatever depends on the lane
+// only (disc offsets, chunk coordinates of the DMA, the BRIEF pattern) once per wavefront, and only the pixel work runs per keypoint, 64
+// lanes wide: 12 disc reads + 6 dot products, 8 rotated offsets + 8 patch reads + 4 ballots.  Every keypoint sees the operations of
+// describe_one() on the same operands in the same order; the moment sums are integer, hence order-independent.
+//
+// One step of the transpose-reduce over partial sums: a and b are the partials of two keypoints (or keypoint groups); lanes whose bit
+// LANEBIT is clear keep a, the others keep b, and each adds its partner lane's partial of the one it keeps.  The partner of bit 3 is the
+// mirrored lane of the 16-lane row (lane ^ 15), of bit 2 the mirrored lane of the 8-lane half row (lane ^ 7), of bits 1 and 0 lane ^ 2
+// and lane ^ 1: taken in that order, the partner agrees with the lane in every bit decided before, so both hold the same keypoints.
+template <int LANEBIT>
+__device__ __forceinline__ int tr_step(int a, int b, int lane) {
+  constexpr int CTRL = LANEBIT == 3 ? 0x140 : LANEBIT == 2 ? 0x141 : LANEBIT == 1 ? 0x4e : 0xb1;   // row_mirror, row_half_mirror, quad_perm
+  const bool hi = ((lane >> LANEBIT) & 1) != 0;
+  const int keep = hi ? b : a, give = hi ? a : b;
+  return keep + dpp_or_zero<CTRL, 0xf>(give);
+}
+// Keypoints LO .. LO + N - 1 of a block of 2^LOG, in order, combined as soon as two neighbouring groups are complete (at most
+// 2 (LOG + 1) partials are live).  Index bit s of the keypoint is decided by lane bit LOG - 1 - s: afterwards lane l holds, summed over
+// its group of 2^LOG lanes, the moments of keypoint bitreverse(l mod 2^LOG).
+template <int LOG, int LO, int N, class F>
+__device__ __forceinline__ void tr_range(F &one, int lane, int &r10, int &r01) {
+  if constexpr (N == 1) one(std::integral_constant<int, LO>{}, r10, r01);
+  else {
+    int a10, a01, b10, b01;
+    tr_range<LOG, LO, N / 2>(one, lane, a10, a01);
+    tr_range<LOG, LO + N / 2, N / 2>(one, lane, b10, b01);
+    constexpr int S = N == 2 ? 0 : N == 4 ? 1 : N == 8 ? 2 : 3;
+    r10 = tr_step<LOG - 1 - S>(a10, b10, lane);
+    r01 = tr_step<LOG - 1 - S>(a01, b01, lane);
+  }
+}
+
+// (explicit address spaces: through generic pointers the two disc paths of the block form are merged into one set of flat loads)
+typedef const __attribute__((address_space(3))) uint8_t *LdsBytes;
+typedef const __attribute__((address_space(1))) uint8_t *GlobalBytes;
+#define DESC_BUF (37 * 48)                  // a wave-private staging buffer: the 31 x 48 disc window, later the 37 x 48 blurred patch
+#define DESC_WAVE_LDS (2 * DESC_BUF + 512)    // two of them (keypoint k + 1 arrives while k is read) + the 64 x 8 bytes of the reduction
+
+template <int K>
+__device__ __forceinline__ void describe_block(const FrameParams &P) {
+  static_assert(K == 4 || K == 8 || K == 16, "a block is a quad, a half row or a row of DPP lanes");
+  constexpr int LOG = K == 16 ? 4 : K == 8 ? 3 : 2;
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int frame, wg;
+  xcd_map(ORB_DESCRIBE_GROUPS(P.totalKp, K), P.magicKpBlk, P.nframes, frame, wg);
+  const int j0 = (wg * 4 + wid) * K;   // first slot of this wavefront's block
+  if (j0 >= P.totalKp) return;
+  // all LDS of the kernel is ONE array (a second object beside a DMA target makes the compiler drain the DMA before reading either)
+  __shared__ __align__(16) uint8_t sDesc[4][DESC_WAVE_LDS];
+  uint8_t *myLds = sDesc[wid];
+
+  // ---- header, lane = keypoint (lanes >= K idle along).  The frame's level counts come in with one load: lane l holds level l's.
+  // So does its first slot; the walk over the levels below then waits for memory once, not once per level.
+  int cL = 0, lpL = 0, kbL = 0;
+  if (lane < P.nlevels) {
+    const int2 v = reinterpret_cast<const int2 *>(P.lcnt + (size_t)frame * P.nlevels * 2)[lane];
+    cL = v.x; lpL = v.y;
+    kbL = P.geom[lane].kpBase;
+  }
+  const int j = j0 + lane;
+  int level = 0, kb = __builtin_amdgcn_readlane(kbL, 0), myCount = __builtin_amdgcn_readlane(cL, 0);
+  int lapBefore = 0, monoBefore = 0, nTot = myCount, lapTot = __builtin_amdgcn_readlane(lpL, 0);
+  for (int l = 1; l < P.nlevels; l++) {
+    const int c = __builtin_amdgcn_readlane(cL, l), lp = __builtin_amdgcn_readlane(lpL, l), base = __builtin_amdgcn_readlane(kbL, l);
+    const bool ge = j >= base;   // bases ascend: the last level whose base is not above j is the lane's
+    level = ge ? l : level; kb = ge ? base : kb; myCount = ge ? c : myCount;
+    lapBefore = ge ? lapTot : lapBefore; monoBefore = ge ? nTot - lapTot : monoBefore;
+    nTot += c; lapTot += lp;
+  }
+  // the frame's totals (keypoints, monoIndex of operator(): ORBextractor.cc:1169-1182) are written by its first wavefront
+  if (j0 == 0 && lane == 0) { P.out_counts[frame * 2] = nTot; P.out_counts[frame * 2 + 1] = nTot - lapTot; }
+  const bool valid = lane < K && j < P.totalKp && j - kb < myCount;
+  const uint32_t validMask = (uint32_t)__ballot(valid);
+  if (validMask == 0) return;
+  uint32_t packed = 0, rk = 0;
+  if (valid) { packed = P.lkp[(size_t)frame * P.lkp_fs + j]; rk = P.lrank[(size_t)frame * P.lkp_fs + j]; }
+  const int X = (int)(packed & 0xfff) + ORB_MIN_BORDER, Y = (int)((packed >> 12) & 0xfff) + ORB_MIN_BORDER;
+  const int dst = (rk & 0x8000u) ? nTot - 1 - (lapBefore + (int)(rk & 0x7fff)) : monoBefore + (int)(rk & 0x7fff);
+  int pitch = (int)P.img0_stride;
+  const uint8_t *img = P.img0 + (size_t)frame * P.img0_frame_stride;
+  if (level != 0) { pitch = P.geom[level].pitch; img = P.pyr + (size_t)frame * P.pyr_fs + P.geom[level].off; }
+  // Both windows are addressed from their centre pixel: the planes that take the DMA path have a dword-aligned base and pitch, so the
+  // low two bits of (centre - 15) are those of X - 15, and the aligned window start follows by masking them off.
+  const uint8_t *centre = img + (size_t)Y * pitch + X;
+  // level 0 is the caller's buffer: when it is not dword-aligned its keypoints gather their disc bytes from global memory
+  const uint32_t dmaMask = (uint32_t)__ballot(valid && ((((uintptr_t)img) | (uintptr_t)pitch) & 3u) == 0);
+  const uint32_t cenLo = (uint32_t)(uintptr_t)centre, cenHi = (uint32_t)((uintptr_t)centre >> 32);
+
+  // ---- lane only: my 12 disc pixels (offsets kept packed: they are the dot products' operands), their places in the 48-byte-pitch
+  // window, my two 16-byte chunks of a window (chunk idx = row 3 r + c; idx / 3 as (idx * 21846) >> 16, exact below 111)
+  const uint4 dw0 = *reinterpret_cast<const uint4 *>(&c_disc.w[lane][0]);
+  const uint2 dw1 = *reinterpret_cast<const uint2 *>(&c_disc.w[lane][4]);
+  const uint32_t uw[3] = {dw0.x, dw0.y, dw0.z}, vw[3] = {dw0.w, dw1.x, dw1.y};
+  uint32_t doff2[6];   // two 16-bit places per register (the adds below select the half word: no unpacking, six registers fewer)
+#pragma unroll
+  for (int t = 0; t < 12; t += 2) {
+    auto place = [&](int tt) { return (uint32_t)((int)(int8_t)(vw[tt >> 2] >> (8 * (tt & 3))) * 48 + (int)(int8_t)(uw[tt >> 2] >> (8 * (tt & 3))) + 15 * 48 + 15); };
+    doff2[t >> 1] = place(t) | (place(t + 1) << 16);
+    asm volatile("" : "+v"(doff2[t >> 1]));   // opaque: otherwise every keypoint re-derives it from the packed offsets
+  }
+  const uint32_t cr0 = ((uint32_t)lane * 21846u) >> 16, cc0 = 16u * ((uint32_t)lane - 3u * cr0);
+  const uint32_t cr1 = ((uint32_t)(lane + 64) * 21846u) >> 16, cc1 = 16u * ((uint32_t)(lane + 64) - 3u * cr1);
+  // nchunks (93 or 111) chunks of the window whose first row starts at row0 (uniform, dword-aligned) into staging buffer `which`.
+  // Always two instructions.  The buffer's previous reads must have returned before the DMA may overwrite it.
+  auto issue = [&](const uint8_t *row0, uint32_t rowPitch, int which, uint32_t nchunks) {
+    uint8_t *buf = myLds + which * DESC_BUF;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(row0 + (mul24(cr0, rowPitch) + cc0)),
+                                     (__attribute__((address_space(3))) void *)&buf[lane * 16], 16, 0, 0);
+    if ((uint32_t)lane + 64u < nchunks)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(row0 + (mul24(cr1, rowPitch) + cc1)),
+                                       (__attribute__((address_space(3))) void *)&buf[(lane + 64) * 16], 16, 0, 0);
+  };
+  auto centre_of = [&](uint32_t lo, uint32_t hi, int k) {
+    return (uintptr_t)(uint32_t)__builtin_amdgcn_readlane((int)lo, k) | ((uintptr_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, k) << 32);
+  };
+  auto issue_disc = [&](int k) {   // rows Y - 15 .. Y + 15, 48 bytes from the aligned column at or below X - 15
+    const uintptr_t c15 = centre_of(cenLo, cenHi, k) - 15;
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readlane(pitch, k);
+    issue(reinterpret_cast<const uint8_t *>(c15 & ~(uintptr_t)3) - 15 * (size_t)p, p, k & 1, 93u);
+  };
+
+  // ---- moments (IC_Angle).  Keypoint k's window is requested while k - 1's is read; the waits are counted: two DMA instructions
+  // per window, loads retire in order.  With d = pixel - 128 as a signed byte, sum u * d differs from sum u * pixel by 128 * sum u,
+  // and the disc's offsets sum to zero over the wavefront, so the signed dot products give m10 and m01 exactly.
+  if (dmaMask & 1u) issue_disc(0);
+  auto one = [&](auto kc, int &p10, int &p01) {
+    constexpr int k = decltype(kc)::value;
+    const bool nextDma = k + 1 < K && ((dmaMask >> ((k + 1) & 31)) & 1u) != 0;
+    if (nextDma) issue_disc(k + 1);
+    p10 = 0; p01 = 0;
+    if ((validMask >> k) & 1u) {
+      uint32_t dval[12], dpk[3];   // my 12 pixels, and packed four to a word (inside each path: the loads' zero extension is known there)
+      const uintptr_t cen = centre_of(cenLo, cenHi, k);
+      if ((dmaMask >> k) & 1u) {
+        if (nextDma) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const LdsBytes dc = (LdsBytes)(myLds + (k & 1) * DESC_BUF + ((cen - 15) & 3));
+#pragma unroll
+        for (int t = 0; t < 12; t++) dval[t] = dc[(t & 1) ? doff2[t >> 1] >> 16 : doff2[t >> 1] & 0xffffu];
+#pragma unroll
+        for (int g = 0; g < 3; g++) dpk[g] = (dval[4 * g] | (dval[4 * g + 1] << 8)) | ((dval[4 * g + 2] | (dval[4 * g + 3] << 8)) << 16);
+      } else {
+        const GlobalBytes cp = (GlobalBytes)cen;
+        const int p = __builtin_amdgcn_readlane(pitch, k);
+        // (unpacked from opaque copies: shared with the other keypoints' copies of this rare path, the 24 offsets would live in
+        // registers of their own through the whole block)
+        uint32_t uo[3], vo[3];
+#pragma unroll
+        for (int g = 0; g < 3; g++) { uo[g] = uw[g]; vo[g] = vw[g]; asm volatile("" : "+v"(uo[g]), "+v"(vo[g])); }
+#pragma unroll
+        for (int t = 0; t < 12; t++)
+          dval[t] = cp[(int)(int8_t)(vo[t >> 2] >> (8 * (t & 3))) * p + (int)(int8_t)(uo[t >> 2] >> (8 * (t & 3)))];
+#pragma unroll
+        for (int g = 0; g < 3; g++) dpk[g] = (dval[4 * g] | (dval[4 * g + 1] << 8)) | ((dval[4 * g + 2] | (dval[4 * g + 3] << 8)) << 16);
+      }
+#pragma unroll
+      for (int g = 0; g < 3; g++) {
+        const uint32_t d = dpk[g] ^ 0x80808080u;
+        p10 = __builtin_amdgcn_sdot4((int)uw[g], (int)d, p10, false);
+        p01 = __builtin_amdgcn_sdot4((int)vw[g], (int)d, p01, false);
+      }
+    }
+  };
+  int r10, r01;
+  tr_range<LOG, 0, K>(one, lane, r10, r01);
+  // the groups' sums meet through LDS: lane k < K adds up the 64 / K entries of keypoint k
+  int2 *sRed = reinterpret_cast<int2 *>(myLds + 2 * DESC_BUF);
+  sRed[lane] = make_int2(r10, r01);
+  int m10 = 0, m01 = 0;
+  if (lane < K) {
+    const int q = (int)(__builtin_bitreverse32((uint32_t)lane) >> (32 - LOG));
+#pragma unroll
+    for (int g = 0; g < 64 / K; g++) { const int2 v = sRed[q + K * g]; m10 += v.x; m01 += v.y; }
+  }
+  // the blurred patches (their addresses only now: fewer registers live across the moments); the first travels during the trigonometry
+  const int bpitch = P.geom[level].bpitch;
+  const uint8_t *bcentre = P.blur + (size_t)frame * P.blur_fs + P.geom[level].boff + (size_t)Y * bpitch + X;
+  const uint32_t bcenLo = (uint32_t)(uintptr_t)bcentre, bcenHi = (uint32_t)((uintptr_t)bcentre >> 32);
+  auto issue_patch = [&](int k, int which) {   // rows Y - 18 .. Y + 18 of the blurred plane (always dword-aligned: workspace)
+    const uintptr_t c18 = centre_of(bcenLo, bcenHi, k) - 18;
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readlane(bpitch, k);
+    issue(reinterpret_cast<const uint8_t *>(c18 & ~(uintptr_t)3) - 18 * (size_t)p, p, which, 111u);
+  };
+  issue_patch(__builtin_ctz(validMask), 0);
+
+  // ---- angle and rotation, lane = keypoint (idle lanes compute on zeros); the branches inside are per lane here
+  const float angle = fast_atan2_deg((float)m01, (float)m10);
+  const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
+  const float arad = angle * factorPI;
+  const float ca = orbsc::ref_cosf(arad), sb = orbsc::ref_sinf(arad);
+
+  // ---- steered BRIEF, one keypoint at a time: a, b are scalar operands, the pattern stays in registers
+  float pf[16];
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const uint32_t pw = reinterpret_cast<const uint32_t *>(c_pattern)[r * 64 + lane];  // x0, y0, x1, y1 as int8
+    pf[4 * r] = (float)(int8_t)(pw & 0xff); pf[4 * r + 1] = (float)(int8_t)((pw >> 8) & 0xff);
+    pf[4 * r + 2] = (float)(int8_t)((pw >> 16) & 0xff); pf[4 * r + 3] = (float)(int8_t)(pw >> 24);
+  }
+  constexpr int bp = 48;
+  int which = 0;
+  for (uint32_t m = validMask; m != 0; which ^= 1) {
+    const int k = __builtin_ctz(m);
+    m &= m - 1;
+    if (m != 0) issue_patch(__builtin_ctz(m), which ^ 1);
+    const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ca), k));
+    const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sb), k));
+    // cvRound as the bits of v + 1.5 * 2^23: for |v| < 2^22 the sum is rounded to the nearest-even integer n exactly as rint does,
+    // and its low 24 bits are 2^22 + n.  The 24-bit multiply-add reads just those, so row * 48 + column costs one instruction (the
+    // 32-bit multiply issues at a quarter rate) and the constant RN_BIAS too much comes off with the patch's base address.
+    auto rn_bits = [](float v) { return __float_as_uint(v + 12582912.0f); };
+    constexpr uint32_t RN_BIAS = 48u * 0x400000u + 0x4b400000u;
+    uint32_t o0[4], o1[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const float x0 = pf[4 * r], y0 = pf[4 * r + 1], x1 = pf[4 * r + 2], y1 = pf[4 * r + 3];
+      o0[r] = __umul24(rn_bits(x0 * b + y0 * a), (uint32_t)bp) + rn_bits(x0 * a - y0 * b);
+      o1[r] = __umul24(rn_bits(x1 * b + y1 * a), (uint32_t)bp) + rn_bits(x1 * a - y1 * b);
+    }
+    // (a store of the previous keypoint may still be in flight: the count only relies on loads retiring in order among themselves)
+    if (m != 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // patch centre (a 32-bit LDS address), less the bias of the offsets
+    const uint32_t bc = (uint32_t)(uintptr_t)(LdsBytes)myLds + (uint32_t)(which * DESC_BUF + 18 * 48 + 18) + (uint32_t)((centre_of(bcenLo, bcenHi, k) - 18) & 3) - RN_BIAS;
+    int v0[4], v1[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) { v0[r] = *(LdsBytes)(uintptr_t)(bc + o0[r]); v1[r] = *(LdsBytes)(uintptr_t)(bc + o1[r]); }
+    unsigned long long bits[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) bits[r] = __ballot(v0[r] < v1[r]);
+    const int d = __builtin_amdgcn_readlane(dst, k);
+    if (d < P.cap && lane < 8) {
+      const unsigned long long w = bits[lane >> 1];
+      reinterpret_cast<uint32_t *>(P.out_desc + ((size_t)frame * P.cap + d) * 32)[lane] = (uint32_t)((lane & 1) ? (w >> 32) : w);
+    }
+  }
+  // ---- the keypoint records, one per lane
+  if (valid && dst < P.cap) {
+    KpOut o;
+    o.x = (float)X;
+    o.y = (float)Y;
+    if (level != 0) { const float sc = P.geom[level].scale; o.x = o.x * sc; o.y = o.y * sc; }
+    o.size = P.geom[level].kpsize;
+    o.angle = angle;
+    o.response = (float)(packed >> 24);
+    o.octave = level;
+    o.class_id = -1;
+    reinterpret_cast<KpOut *>(P.out_kps)[(size_t)frame * P.cap + dst] = o;
+  }
+}
+
+// (the block form is held to eight wavefronts per SIMD: left alone, the scheduler spreads K = 16 over 118 registers, i.e. four)
+template <int K>
+__global__ __launch_bounds__(256, K == 1 ? 1 : 8) void k_describe(FrameParams P) {
+  if constexpr (K == 1) describe_one(P);
+  else describe_block<K>(P);
 }
 
 // cv::cvtColor(im, gray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) as called by Tracking::GrabImage*

@@ -681,7 +681,12 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   P.tiles = (const uint32_t *)h->d_tiles.p;
   P.magicCells = magic_div((uint32_t)std::max(h->totalCells, 1));
   P.magicTiles = magic_div((uint32_t)std::max(h->totalTiles, 1));
-  P.magicKpBlk = magic_div((uint32_t)std::max((h->totalKp + 3) / 4, 1));
+  // One workgroup per (frame, level) in k_octree and one launch per level of the pyramid: a batch fills the chip that way; a single frame
+  // is all launch gaps and one long workgroup, so few-frame calls ("wide") take the one-launch pyramid, the 1024-thread octree and
+  // k_describe with one keypoint per wavefront (blocks of 8 in sequence would leave a 1000-keypoint frame ~130 wavefronts).
+  const bool wide = (long long)h->nlevels * nframes <= 32;
+  const int describeGroups = wide ? ORB_DESCRIBE_GROUPS(h->totalKp, 1) : ORB_DESCRIBE_GROUPS(h->totalKp, ORB_DESCRIBE_K);
+  P.magicKpBlk = magic_div((uint32_t)describeGroups);
   P.totalKp = h->totalKp;
   P.octCap = h->octCap;
   P.chain = (const ChainTile *)h->d_chain.p; P.chainBuf0 = h->chainBuf0; P.chainBuf1 = h->chainBuf1;
@@ -692,9 +697,6 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   const bool prof = h->profiling && h->ev_ok;
   hipEvent_t *pev = h->ev[h->prof_head % PROF_DEPTH];
   if (prof) XCHECK(h, hipEventRecord(pev[0], s));
-  // One workgroup per (frame, level) in k_octree and one launch per level here: a batch fills the chip that way; a single frame is
-  // all launch gaps and one long workgroup, so few-frame calls ("wide") take the one-launch pyramid and 1024-thread octree.
-  const bool wide = (long long)h->nlevels * nframes <= 32;
   // ORBHIP_PRINT_EXTRACT_FORMS (tests/test_gpu_batch_layouts.py): one stderr line per call with the host's choices below
   const bool printForms = getenv("ORBHIP_PRINT_EXTRACT_FORMS") != nullptr;
   std::string pyrForm = h->nlevels == 1 ? "none" : "";
@@ -730,7 +732,9 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   if (prof) XCHECK(h, hipEventRecord(pev[3], s));
   hipLaunchKernelGGL(k_blur, dim3(h->totalTiles * nframes), dim3(256), 0, s, P);
   if (prof) XCHECK(h, hipEventRecord(pev[4], s));
-  hipLaunchKernelGGL(k_describe, dim3(std::max((h->totalKp + 3) / 4, 1) * nframes), dim3(256), 0, s, P);   // also writes the frame totals (>= 1 workgroup per frame: nfeatures == 0)
+  // also writes the frame totals (>= 1 workgroup per frame: nfeatures == 0)
+  if (wide) hipLaunchKernelGGL(k_describe<1>, dim3(describeGroups * nframes), dim3(256), 0, s, P);
+  else hipLaunchKernelGGL(k_describe<ORB_DESCRIBE_K>, dim3(describeGroups * nframes), dim3(256), 0, s, P);
   if (prof) { XCHECK(h, hipEventRecord(pev[5], s)); h->prof_head++; h->stage_valid = true; }
   XCHECK(h, hipGetLastError());
   if (printForms) {
@@ -740,8 +744,8 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
     for (int f = 0; f < nframes; f++) aligned0 += (((uintptr_t)(d_images + (size_t)f * frame_stride) | (uintptr_t)stride) & 3u) == 0;
     const LevelGeom &G0 = h->geom[0];
     const int blur0dma = G0.w >= 160 && G0.h >= 40 && (G0.w & 15) == 0 ? aligned0 : 0;
-    fprintf(stderr, "orbhip: extract nframes %d pyramid %s octree %d/%s aligned0 %d blur0dma %d\n", nframes, pyrForm.c_str(), wide ? 1024 : 256,
-            h->octCellsLds ? "lds" : "global", aligned0, blur0dma);
+    fprintf(stderr, "orbhip: extract nframes %d pyramid %s octree %d/%s aligned0 %d blur0dma %d describe %d\n", nframes, pyrForm.c_str(), wide ? 1024 : 256,
+            h->octCellsLds ? "lds" : "global", aligned0, blur0dma, wide ? 1 : ORB_DESCRIBE_K);
   }
   h->last = P;
   h->have_last = true;
