@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "orbx_get_scale_tables", "orbx_get_features_per_level", "orbx_configure", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_get_host_us", "orbx_level_info", "orbx_download_level", "orbx_download_pyramid", "orbx_download_blurred_level",
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
-    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
+    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
     "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
@@ -120,6 +120,7 @@ def load(build_if_needed=True):
     L.orbx_set_profiling.argtypes = [vp, i32]
     L.orbx_get_stage_ms.argtypes = [vp, vp, i32]
     L.orbx_compute_stereo_matches.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, f32, f32, vp, vp]
+    L.orbx_compute_stereo_matches_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp]
     L.orbx_cvt_color_gray.argtypes = [vp, vp, i32, i32, sz, i32, i32, vp, sz]
     L.orbx_cvt_color_gray_device.argtypes = [vp, i32, i32, sz, i32, i32, vp, sz, vp]
     L.orbx_clahe.argtypes = [vp, vp, i32, i32, sz, C.c_double, i32, i32, vp, sz]
@@ -351,6 +352,21 @@ class ORBextractor:
         if rc < 0:
             raise OrbError("orbx_compute_stereo_matches rc=%d: %s" % (rc, self.L.orbx_last_error(self.h).decode()))
         return uR, depth
+
+    def compute_stereo_matches_batch_device(self, right, nframes, d_keysL, d_descL, d_countsL, d_keysR, d_descR, d_countsR, cap, mb, mbf,
+                                            d_uRight, d_depth, d_nstereo=None, stream=None):
+        """Frame::ComputeStereoMatches (Frame.cc:901-1079) for the `nframes` pairs of the last two extract_batch_device calls of self
+        (left) and right, everything resident: all pointers are device addresses (ints), asynchronous on `stream`.  d_uRight /
+        d_depth [nframes][cap] float32 receive mvuRight / mvDepth (entries beyond a frame's left count are left alone), d_nstereo
+        [nframes] int32 (optional) the number of stereo matches after the median filter."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        rc = self.L.orbx_compute_stereo_matches_batch_device(self.h, right.h if right is not None else None, int(nframes), vp(d_keysL), vp(d_descL),
+                                                             vp(d_countsL), vp(d_keysR), vp(d_descR), vp(d_countsR), int(cap), C.c_float(mb),
+                                                             C.c_float(mbf), vp(d_uRight), vp(d_depth), vp(d_nstereo), vp(stream))
+        self._check(rc, "orbx_compute_stereo_matches_batch_device")
+        if rc < 0:
+            raise OrbError("orbx_compute_stereo_matches_batch_device rc=%d" % rc)
+        return rc
 
     def extract_batch_device(self, d_images, rows, cols, stride, frame_stride, nframes, d_kps, d_desc, d_counts, cap,
                              vLappingArea=(0, 1000), stream=None):

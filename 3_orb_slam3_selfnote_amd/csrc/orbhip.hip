@@ -23,6 +23,7 @@
 #include "orb_match_kernels.h"
 #include "orb_match_mfma.h"
 #include "orb_project_kernels.h"
+#include "orb_stereo_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -98,6 +99,7 @@ struct orbx_handle {
   bool last_pending = false;        // ... and not yet known to have completed
   bool in_capture = false;          // orbx_extract is capturing its per-frame graph: nothing but the frame's own work is enqueued
   DevBuf stereo[7];  // grow-only buffers of orbx_compute_stereo_matches
+  DevBuf stereo_batch[3];  // ... of orbx_compute_stereo_matches_batch_device: row-table records, band starts, SADs
   DevBuf maps[2];    // rectification maps of orbx_remap_linear, kept between calls
   int maps_rows = 0, maps_cols = 0;
   // pinned host staging of the single-frame entry point (orbx_extract): pageable copies would serialise on HIP's own staging
@@ -272,6 +274,7 @@ void orbx_destroy(orbx_t *h) {
                     &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_cells, &h->d_groups, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
   for (DevBuf *b : bufs) b->release();
   for (DevBuf &b : h->stereo) b.release();
+  for (DevBuf &b : h->stereo_batch) b.release();
   for (DevBuf &b : h->maps) b.release();
   if (h->graph) (void)hipGraphExecDestroy(h->graph);
   if (h->last_done) (void)hipEventDestroy(h->last_done);
@@ -2662,6 +2665,73 @@ int orbx_compute_stereo_matches(orbx_t *hl, int frame_l, orbx_t *hr, int frame_r
       depth[vDistIdx[i].second] = -1;
     }
   }
+  return 0;
+}
+
+int orbx_compute_stereo_matches_batch_device(orbx_t *hl, orbx_t *hr, int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL,
+                                             const int32_t *d_countsL, const orbx_keypoint_t *d_keysR, const uint8_t *d_descR,
+                                             const int32_t *d_countsR, int cap, float mb, float mbf, float *d_uRight, float *d_depth,
+                                             int32_t *d_nstereo, void *stream_) {
+  if (!hl || !hr) return ORBX_E_ARG;
+  if (!d_keysL || !d_descL || !d_countsL || !d_keysR || !d_descR || !d_countsR || !d_uRight || !d_depth) {
+    hl->err = "orbx_compute_stereo_matches_batch_device: NULL array";
+    return ORBX_E_ARG;
+  }
+  if (!hl->have_last || !hr->have_last) { hl->err = "orbx_compute_stereo_matches_batch_device: extract both batches first"; return ORBX_E_ARG; }
+  if (nframes <= 0 || nframes > hl->last.nframes || nframes > hr->last.nframes) {
+    hl->err = "orbx_compute_stereo_matches_batch_device: nframes outside the two extractors' last batches";
+    return ORBX_E_ARG;
+  }
+  if (hl->device != hr->device || hl->rows != hr->rows || hl->cols != hr->cols || hl->nlevels != hr->nlevels ||
+      hl->mvScaleFactor != hr->mvScaleFactor) {
+    hl->err = "orbx_compute_stereo_matches_batch_device: the two extractors must share device, image size and pyramid";
+    return ORBX_E_ARG;
+  }
+  if (!(mb > 0.f)) { hl->err = "orbx_compute_stereo_matches_batch_device: mb must be positive"; return ORBX_E_ARG; }
+  if (cap < hl->maxKeypoints || cap < hr->maxKeypoints || cap > 65535) {
+    hl->err = "orbx_compute_stereo_matches_batch_device: cap must be in [orbx_max_keypoints, 65535]";
+    return ORBX_E_ARG;
+  }
+  XCHECK(hl, hipSetDevice(hl->device));
+  hipStream_t s = (hipStream_t)stream_;   // verbatim: NULL is the device's default stream
+  StereoBatchParams S;
+  memset(&S, 0, sizeof(S));
+  S.imgL0 = hl->last.img0; S.strideL0 = hl->last.img0_stride; S.fsL0 = hl->last.img0_frame_stride;
+  S.imgR0 = hr->last.img0; S.strideR0 = hr->last.img0_stride; S.fsR0 = hr->last.img0_frame_stride;
+  S.pyrL = hl->last.pyr; S.pyrFsL = hl->last.pyr_fs;
+  S.pyrR = hr->last.pyr; S.pyrFsR = hr->last.pyr_fs;
+  float sfMax = 0.f;
+  for (int l = 0; l < hl->nlevels; l++) {
+    const LevelGeom &G = hl->geom[l];
+    S.w[l] = G.w; S.h[l] = G.h; S.pitch[l] = G.pitch; S.off[l] = G.off;
+    S.sf[l] = hl->mvScaleFactor[l]; S.invsf[l] = hl->mvInvScaleFactor[l];
+    sfMax = std::max(sfMax, S.sf[l]);
+  }
+  S.nlevels = hl->nlevels; S.rows = hl->rows;
+  S.nbands = (hl->rows + STEREO_BAND - 1) / STEREO_BAND;
+  if (S.nbands > STEREO_MAX_BANDS) { hl->err = "orbx_compute_stereo_matches_batch_device: more than 4096 rows"; return ORBX_E_ARG; }
+  // a right keypoint covers the rows floor(y - r) .. ceil(y + r), r = 2 * scale (:916-918): at most 2r + 3 of them (+ 1 for the
+  // rounding of y +- r), and S consecutive rows touch at most (S + 6) / 8 + 1 bands of 8
+  const int spanRows = (int)(4.0f * sfMax) + 4;
+  const int bandsPerKp = std::min(S.nbands, (spanRows + 6) / STEREO_BAND + 1);
+  S.cap = cap; S.recCap = cap * bandsPerKp;
+  S.kpL = (const float *)d_keysL; S.kpR = (const float *)d_keysR;
+  S.descL = (const uint32_t *)d_descL; S.descR = (const uint32_t *)d_descR;
+  S.countsL = d_countsL; S.countsR = d_countsR;
+  S.mb = mb; S.mbf = mbf;
+  DevBuf *bufs = hl->stereo_batch;   // grow-only; a growth is the one step that blocks (hipFree / hipMalloc)
+  XCHECK(hl, bufs[0].reserve(sizeof(StereoRec) * (size_t)S.recCap * nframes));
+  XCHECK(hl, bufs[1].reserve(sizeof(int32_t) * (size_t)(S.nbands + 1) * nframes));
+  XCHECK(hl, bufs[2].reserve(sizeof(int32_t) * (size_t)cap * nframes));
+  S.recs = (StereoRec *)bufs[0].p; S.bandStart = (int32_t *)bufs[1].p; S.sad = (int32_t *)bufs[2].p;
+  S.uRight = d_uRight; S.depth = d_depth; S.nstereo = d_nstereo;
+  // the two extractions may have run on any stream: ordered behind the last kernel of both, as the host form does
+  if (hl->last_pending) XCHECK(hl, hipStreamWaitEvent(s, hl->last_done, 0));
+  if (hr->last_pending) XCHECK(hl, hipStreamWaitEvent(s, hr->last_done, 0));
+  hipLaunchKernelGGL(k_stereo_rows, dim3(nframes), dim3(256), 0, s, S);
+  hipLaunchKernelGGL(k_stereo_search, dim3((cap + STEREO_KPB - 1) / STEREO_KPB, nframes), dim3(256), 0, s, S);
+  hipLaunchKernelGGL(k_stereo_median, dim3(nframes), dim3(256), 0, s, S);
+  XCHECK(hl, hipGetLastError());
   return 0;
 }
 

@@ -175,6 +175,27 @@ int orbx_compute_stereo_matches(orbx_t *left, int frame_l, orbx_t *right, int fr
                                 const uint8_t *descL, int nR, const orbx_keypoint_t *keysR, const uint8_t *descR, float mb,
                                 float mbf, float *uRight, float *depth);
 
+/* The same member (Frame.cc:901-1079) for `nframes` frame pairs resident in HBM, asynchronous on `stream`: no host
+ * synchronisation, no host copy, no host arithmetic.  left / right: the two extractors after orbx_extract_batch_device of
+ * nframes (or more) left and right images with lapping area {0, 0} (Frame.cc:120-121); frame f of one is paired with frame f of
+ * the other.  d_keysL / d_descL / d_countsL and d_keysR / d_descR / d_countsR are exactly what those two calls wrote
+ * ([nframes][cap], [nframes][cap][32], [nframes][2]); the pyramids are read from the handles' last batch, level 0 in place from
+ * the caller's images (lifetime rule of orbx_extract_batch_device), ordered behind both extractions by their events.
+ * d_uRight / d_depth [nframes][cap] = mvuRight / mvDepth: entries i < n_left(f) are written (-1 where the reference leaves -1),
+ * entries beyond are left alone.  d_nstereo[f] (may be NULL) = number of entries >= 0 after the median filter.
+ * Three kernels: the row table of :911-928 as 8-row bands on the device, the descriptor search over the band of each left
+ * keypoint (:941-979) with the 11x11 SAD refinement and parabola fit (:982-1062), and the median filter (:1065-1078) as a rank
+ * selection by two 256-bin histogram passes (no sort; no accepted match = nothing to do, as in the host form).  Same bits as
+ * orbx_compute_stereo_matches per frame.  Scratch is grow-only device memory of `left` (growing it on a first, larger call is the
+ * one step that blocks); calls on the same `left` handle share it, so issue them on one stream or order them yourself.
+ * ORBX_E_ARG (with orbx_last_error(left)): NULL handle or required pointer, nframes outside the two handles' last batches, handles
+ * that differ in device / image size / pyramid, mb <= 0, cap below orbx_max_keypoints, cap > 65535 (the 16-bit right index of
+ * the search key, the host form's nR limit).  Returns 0. */
+int orbx_compute_stereo_matches_batch_device(orbx_t *left, orbx_t *right, int nframes, const orbx_keypoint_t *d_keysL,
+                                             const uint8_t *d_descL, const int32_t *d_countsL, const orbx_keypoint_t *d_keysR,
+                                             const uint8_t *d_descR, const int32_t *d_countsR, int cap, float mb, float mbf,
+                                             float *d_uRight, float *d_depth, int32_t *d_nstereo, void *stream);
+
 /* ---- ORBmatcher -------------------------------------------------------------------------------------------- */
 
 #define ORBM_TH_HIGH 100 /* ORBmatcher.cc:36 */
