@@ -1,7 +1,13 @@
-// orb_stereo_kernels.h -- Frame::ComputeStereoMatches (Frame.cc:901-1079) for a batch of frame pairs resident in HBM:
-// the kernels of orbx_compute_stereo_matches_batch_device.  Included by orbhip.hip after orb_match_kernels.h (wave helpers,
-// ORBM_TH_*).  The arithmetic that decides results is k_stereo_match's, expression for expression; what differs is who looks at
-// what:
+// orb_stereo_kernels.h -- Frame::ComputeStereoMatches (Frame.cc:901-1079), rectified stereo: the whole stereo path.  Included by
+// orbhip.hip after orb_match_kernels.h (wave helpers, ORBM_TH_*).  Two forms share the arithmetic that decides results - the row range
+// of a right keypoint, the candidate gates and key, the window test, the sub-pixel fit (the stereo_* device functions below, each
+// stated once) - and differ in who looks at what:
+//  host arrays, one frame pair (orbx_compute_stereo_matches):
+//   k_stereo_match   one wavefront per LEFT keypoint.  Lanes over all right keypoints: row range, octave window, disparity window,
+//                    Hamming; wave minimum of (dist << 16 | iR) = first minimum in iR order (:966).  Then the 11x11 SAD at 11
+//                    horizontal offsets on the two level images (lanes over the 121 pixels, global reads, DPP wave sums).  The median
+//                    filter over the accepted matches (:1060-1073) needs a sort of <= N pairs and stays on the host.
+//  a batch of frame pairs resident in HBM (orbx_compute_stereo_matches_batch_device):
 //   k_stereo_rows    the reference's row table (vRowIndices, :911-928) as a CSR table of STEREO_BAND-row bands, one workgroup per
 //                    frame pair.  A record is 16 bytes (u, the exact row range, octave | index): a candidate is rejected without
 //                    touching its 28-byte keypoint or its descriptor.  Order inside a band is whatever the LDS atomics give: the
@@ -38,6 +44,138 @@ struct StereoBatchParams {
 
 __device__ __forceinline__ int stereo_live(const int32_t *counts, int f, int cap) { return min(max(counts[2 * f], 0), cap); }
 
+#define STEREO_W 5   // half width of the SAD window (w, :991)
+#define STEREO_L 5   // half width of the sliding range (L, :998)
+
+// The rows a right keypoint is a candidate for (:916-918).  maxOct bounds the index into sf: k_stereo_match passes ORB_MAXL - 1,
+// k_stereo_rows nlevels - 1; the two differ only for octaves no extractor produces, and each kernel keeps its own.
+__device__ __forceinline__ void stereo_row_range(const float *sf, int maxOct, float yR, int oR, int *minr, int *maxr) {
+  const float r = 2.0f * sf[min(max(oR, 0), maxOct)];                       // :916
+  *maxr = (int)ceilf(yR + r); *minr = (int)floorf(yR - r);                  // :917-918
+}
+
+// The two gates of a right keypoint in the left keypoint's row: the octave window (:954) and the disparity window (:959)
+__device__ __forceinline__ bool stereo_octave_outside(int oR, int levelL) { return oR < levelL - 1 || oR > levelL + 1; }
+__device__ __forceinline__ bool stereo_u_outside(float uR, float minU, float maxU) { return !(uR >= minU && uR <= maxU); }
+// bestDist starts at TH_HIGH and is replaced on strict <; the minimum of dist << 16 | iR is the first best in iR order (:966-978)
+__device__ __forceinline__ uint32_t stereo_take_best(uint32_t best, int dist, int iR) {
+  return dist < ORBM_TH_HIGH ? min(best, ((uint32_t)dist << 16) | (uint32_t)iR) : best;
+}
+
+// The left window and the sliding range of the right one lie inside the lw x lh level image.  cv::Mat::rowRange / colRange throw
+// outside the matrix: such keypoints are skipped (same rule in the test oracle).
+__device__ __forceinline__ bool stereo_window_inside(int cuL, int cvL, int cuR, float scaleduR0, int lw, int lh) {
+  constexpr int w = STEREO_W, L = STEREO_L;
+  const float iniu = scaleduR0 + L - w, endu = scaleduR0 + L + w + 1;
+  return cvL - w >= 0 && cvL + w + 1 <= lh && cuL - w >= 0 && cuL + w + 1 <= lw && !(iniu < 0 || endu >= (float)lw) && cuR - L - w >= 0;
+}
+
+// SAD argmin over the 2L + 1 offsets, parabola fit, disparity and depth in the reference's fp32 expressions (:1006-1047).  The outputs
+// are written only for an accepted match.
+__device__ __forceinline__ void stereo_subpixel(const int *sadv, float uL, float scaleduR0, float sfLevel, float minD, float maxD, float mbf,
+                                                float *outU, float *outD, int *outSad) {
+  constexpr int L = STEREO_L;
+  int bestSad = 0x7fffffff, bestincR = 0;
+#pragma unroll
+  for (int k = 0; k <= 2 * L; k++)
+    if ((float)sadv[k] < (float)bestSad) { bestSad = sadv[k]; bestincR = k - L; }       // :1006
+  if (bestincR == -L || bestincR == L) return;
+  float dist1 = 0.f, dist2 = 0.f, dist3 = 0.f;
+#pragma unroll
+  for (int k = 1; k < 2 * L; k++)
+    if (k == bestincR + L) { dist1 = (float)sadv[k - 1]; dist2 = (float)sadv[k]; dist3 = (float)sadv[k + 1]; }
+  const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));      // :1024
+  if (deltaR < -1 || deltaR > 1) return;
+  float bestuR = sfLevel * ((float)scaleduR0 + (float)bestincR + deltaR);               // :1030
+  float disparity = uL - bestuR;
+  if (disparity >= minD && disparity < maxD) {
+    if (disparity <= 0) { disparity = (float)0.01; bestuR = (float)((double)uL - 0.01); }
+    *outD = mbf / disparity;
+    *outU = bestuR;
+    *outSad = bestSad;
+  }
+}
+
+struct StereoParams {
+  const uint8_t *imgL0, *imgR0; size_t strideL0, strideR0;   // level 0 of the chosen frames
+  const uint8_t *pyrL, *pyrR;                                 // pyramid blocks of the chosen frames (levels >= 1)
+  int w[ORB_MAXL], h[ORB_MAXL], pitch[ORB_MAXL]; size_t off[ORB_MAXL];
+  float sf[ORB_MAXL], invsf[ORB_MAXL];
+  int nlevels, rows;
+  const float *kpL, *kpR;                                     // 7 floats per keypoint (mvKeys / mvKeysRight)
+  const uint32_t *descL, *descR;
+  int nL, nR;
+  float mb, mbf;
+  float *uRight, *depth; int32_t *sad;                        // per left keypoint; sad = -1: no match
+};
+
+__global__ __launch_bounds__(256) void k_stereo_match(StereoParams S) {
+  const int lane = threadIdx.x & 63;
+  const int iL = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (iL >= S.nL) return;
+  const float uL = S.kpL[(size_t)iL * 7], vL = S.kpL[(size_t)iL * 7 + 1];
+  const int levelL = __float_as_int(S.kpL[(size_t)iL * 7 + 5]);
+  float outU = -1.0f, outD = -1.0f;
+  int outSad = -1;
+  const float minD = 0.f, maxD = S.mbf / S.mb;                // :933-935
+  const float minU = uL - maxD, maxU = uL - minD;
+  const int row = (int)vL;
+  uint32_t best = 0xffffffffu;
+  if (row >= 0 && row < S.rows && !(maxU < 0) && levelL >= 0 && levelL < S.nlevels) {
+    uint32_t dl[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) dl[t] = S.descL[(size_t)iL * 8 + t];
+    for (int iR = lane; iR < S.nR; iR += 64) {
+      const float uR = S.kpR[(size_t)iR * 7], yR = S.kpR[(size_t)iR * 7 + 1];
+      const int oR = __float_as_int(S.kpR[(size_t)iR * 7 + 5]);
+      int minr, maxr;
+      stereo_row_range(S.sf, ORB_MAXL - 1, yR, oR, &minr, &maxr);
+      if (row < minr || row > maxr) continue;
+      if (stereo_octave_outside(oR, levelL)) continue;
+      if (stereo_u_outside(uR, minU, maxU)) continue;
+      int dist = 0;
+#pragma unroll
+      for (int t = 0; t < 8; t++) dist += __popc(dl[t] ^ S.descR[(size_t)iR * 8 + t]);
+      best = stereo_take_best(best, dist, iR);
+    }
+  }
+  best = wave_min_key(best);
+  const int thOrbDist = (ORBM_TH_HIGH + ORBM_TH_LOW) / 2;
+  if (best != 0xffffffffu && (int)(best >> 16) < thOrbDist) {
+    const int bestIdxR = (int)(best & 0xffffu);
+    const float uR0 = S.kpR[(size_t)bestIdxR * 7];
+    const float scaleFactor = S.invsf[levelL];
+    const float scaleduL = roundf(uL * scaleFactor), scaledvL = roundf(vL * scaleFactor), scaleduR0 = roundf(uR0 * scaleFactor);
+    constexpr int w = STEREO_W, L = STEREO_L;
+    const int lw = S.w[levelL], lh = S.h[levelL];
+    const int cuL = (int)scaleduL, cvL = (int)scaledvL, cuR = (int)scaleduR0;
+    if (stereo_window_inside(cuL, cvL, cuR, scaleduR0, lw, lh)) {
+      const uint8_t *IL, *IR;
+      int pL, pR;
+      if (levelL == 0) { IL = S.imgL0; IR = S.imgR0; pL = (int)S.strideL0; pR = (int)S.strideR0; }
+      else { IL = S.pyrL + S.off[levelL]; IR = S.pyrR + S.off[levelL]; pL = pR = S.pitch[levelL]; }
+      const int cL = IL[(size_t)cvL * pL + cuL];
+      // my pixels of the 11x11 window: p = lane and lane + 64
+      const int p0 = lane, p1 = lane + 64;
+      const int y0 = p0 / 11 - w, x0 = p0 % 11 - w, y1 = p1 / 11 - w, x1 = p1 % 11 - w;
+      const bool has1 = p1 < 121;
+      const int a0 = (int)IL[(size_t)(cvL + y0) * pL + cuL + x0] - cL;
+      const int a1 = has1 ? (int)IL[(size_t)(cvL + y1) * pL + cuL + x1] - cL : 0;
+      int sadv[2 * L + 1];
+#pragma unroll
+      for (int k = 0; k <= 2 * L; k++) {
+        const int incR = k - L;
+        const int cR = IR[(size_t)cvL * pR + cuR + incR];
+        const int b0 = (int)IR[(size_t)(cvL + y0) * pR + cuR + incR + x0] - cR;
+        const int b1 = has1 ? (int)IR[(size_t)(cvL + y1) * pR + cuR + incR + x1] - cR : 0;
+        sadv[k] = wave_sum_i32(abs(a0 - b0) + (has1 ? abs(a1 - b1) : 0));
+      }
+      stereo_subpixel(sadv, uL, scaleduR0, S.sf[levelL], minD, maxD, S.mbf, &outU, &outD, &outSad);
+    }
+  }
+  if (lane == 0) { S.uRight[iL] = outU; S.depth[iL] = outD; S.sad[iL] = outSad; }
+}
+
 __global__ __launch_bounds__(256) void k_stereo_rows(StereoBatchParams S) {
   __shared__ uint32_t sCnt[STEREO_MAX_BANDS];
   __shared__ uint32_t sFill[STEREO_MAX_BANDS];
@@ -50,8 +188,8 @@ __global__ __launch_bounds__(256) void k_stereo_rows(StereoBatchParams S) {
   for (int iR = tid; iR < nR; iR += 256) {
     const float yR = kp[(size_t)iR * 7 + 1];
     const int oR = __float_as_int(kp[(size_t)iR * 7 + 5]);
-    const float r = 2.0f * S.sf[min(max(oR, 0), S.nlevels - 1)];           // :916
-    const int maxr = (int)ceilf(yR + r), minr = (int)floorf(yR - r);        // :917-918
+    int minr, maxr;
+    stereo_row_range(S.sf, S.nlevels - 1, yR, oR, &minr, &maxr);
     const int lo = max(minr, 0), hi = min(maxr, S.rows - 1);
     if (lo <= hi)
       for (int b = lo >> STEREO_BAND_SHIFT; b <= (hi >> STEREO_BAND_SHIFT); b++) atomicAdd(&sCnt[b], 1u);
@@ -66,8 +204,8 @@ __global__ __launch_bounds__(256) void k_stereo_rows(StereoBatchParams S) {
   for (int iR = tid; iR < nR; iR += 256) {
     const float uR = kp[(size_t)iR * 7], yR = kp[(size_t)iR * 7 + 1];
     const int oR = __float_as_int(kp[(size_t)iR * 7 + 5]);
-    const float r = 2.0f * S.sf[min(max(oR, 0), S.nlevels - 1)];
-    const int maxr = (int)ceilf(yR + r), minr = (int)floorf(yR - r);
+    int minr, maxr;
+    stereo_row_range(S.sf, S.nlevels - 1, yR, oR, &minr, &maxr);
     const int lo = max(minr, 0), hi = min(maxr, S.rows - 1);
     if (lo > hi) continue;
     StereoRec rec;
@@ -107,15 +245,13 @@ __global__ __launch_bounds__(256) void k_stereo_search(StereoBatchParams S) {
     for (int e = e0 + sub; e < e1; e += 8) {
       const uint4 rc = recs[e];
       if (row < (int)rc.y || row > (int)rc.z) continue;       // the exact row test of the table (:919-920)
-      const int oR = (int)rc.w >> 16;
-      if (oR < levelL - 1 || oR > levelL + 1) continue;       // :954
-      const float uR = __uint_as_float(rc.x);
-      if (!(uR >= minU && uR <= maxU)) continue;              // :959
+      if (stereo_octave_outside((int)rc.w >> 16, levelL)) continue;
+      if (stereo_u_outside(__uint_as_float(rc.x), minU, maxU)) continue;
       const int iR = (int)(rc.w & 0xffffu);
       int dist = 0;
 #pragma unroll
       for (int t = 0; t < 8; t++) dist += __popc(dl[t] ^ descR[(size_t)iR * 8 + t]);
-      if (dist < ORBM_TH_HIGH) best = min(best, ((uint32_t)dist << 16) | (uint32_t)iR);   // bestDist starts at TH_HIGH, strict <
+      best = stereo_take_best(best, dist, iR);
     }
   }
   best = min(best, (uint32_t)__shfl_xor((int)best, 1));
@@ -139,13 +275,10 @@ __global__ __launch_bounds__(256) void k_stereo_search(StereoBatchParams S) {
     const float uR0 = kpR[(size_t)bestIdxR * 7];
     const float scaleFactor = S.invsf[qlevel];
     const float scaleduL = roundf(quL * scaleFactor), scaledvL = roundf(qvL * scaleFactor), scaleduR0 = roundf(uR0 * scaleFactor);
-    constexpr int w = 5, L = 5;
+    constexpr int w = STEREO_W, L = STEREO_L;
     const int lw = S.w[qlevel], lh = S.h[qlevel];
     const int cuL = (int)scaleduL, cvL = (int)scaledvL, cuR = (int)scaleduR0;
-    const float iniu = scaleduR0 + L - w, endu = scaleduR0 + L + w + 1;
-    // cv::Mat::rowRange / colRange throw outside the matrix: such keypoints are skipped (same rule in the test oracle)
-    const bool inside = cvL - w >= 0 && cvL + w + 1 <= lh && cuL - w >= 0 && cuL + w + 1 <= lw && !(iniu < 0 || endu >= (float)lw) && cuR - L - w >= 0;
-    if (inside) {                                             // wave-uniform
+    if (stereo_window_inside(cuL, cvL, cuR, scaleduR0, lw, lh)) {   // wave-uniform
       const uint8_t *IL, *IR;
       int pL, pR;
       if (qlevel == 0) { IL = S.imgL0 + (size_t)f * S.fsL0; IR = S.imgR0 + (size_t)f * S.fsR0; pL = (int)S.strideL0; pR = (int)S.strideR0; }
@@ -179,27 +312,7 @@ __global__ __launch_bounds__(256) void k_stereo_search(StereoBatchParams S) {
         sadv[k] = packed & 0xffff;
         sadv[k + 1] = (int)((uint32_t)packed >> 16);
       }
-      int bestSad = 0x7fffffff, bestincR = 0;
-#pragma unroll
-      for (int k = 0; k <= 2 * L; k++)
-        if ((float)sadv[k] < (float)bestSad) { bestSad = sadv[k]; bestincR = k - L; }       // :1006
-      if (!(bestincR == -L || bestincR == L)) {
-        float dist1 = 0.f, dist2 = 0.f, dist3 = 0.f;
-#pragma unroll
-        for (int k = 1; k < 2 * L; k++)
-          if (k == bestincR + L) { dist1 = (float)sadv[k - 1]; dist2 = (float)sadv[k]; dist3 = (float)sadv[k + 1]; }
-        const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));    // :1024
-        if (!(deltaR < -1 || deltaR > 1)) {
-          float bestuR = S.sf[qlevel] * ((float)scaleduR0 + (float)bestincR + deltaR);       // :1030
-          float disparity = quL - bestuR;
-          if (disparity >= minD && disparity < maxD) {
-            if (disparity <= 0) { disparity = (float)0.01; bestuR = (float)((double)quL - 0.01); }
-            outD = S.mbf / disparity;
-            outU = bestuR;
-            outSad = bestSad;
-          }
-        }
-      }
+      stereo_subpixel(sadv, quL, scaleduR0, S.sf[qlevel], minD, maxD, S.mbf, &outU, &outD, &outSad);
     }
     if (lane == src) { resU = outU; resD = outD; resSad = outSad; }
   }

@@ -1180,6 +1180,40 @@ struct SearchOpts {
 
 template <int V> using ScanKind = std::integral_constant<int, V>;
 
+// ---- helpers of the C entry points below that are templates (C++ linkage) ----------------------------------------------------
+// Rotation-consistency check of every matcher with checkOri (e.g. ORBmatcher.cc:2177-2185 + :2263-2286): a match goes into the bin
+// of the angle difference of its two keypoints; matches outside the three fullest bins (orbm_three_maxima) are pruned.  What an id
+// is and what pruning does to it stay with the caller.
+struct RotHist {
+  std::vector<int> bins[ORBM_HISTO_LENGTH];
+  void add(float rot, int id) {
+    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    if ((double)rot < 0.0) rot += 360.0f;
+    int bin = (int)roundf(rot * factor);
+    if (bin == ORBM_HISTO_LENGTH) bin = 0;
+    if (bin >= 0 && bin < ORBM_HISTO_LENGTH) bins[bin].push_back(id);
+  }
+  template <class F> void for_each_pruned(F fn) const {
+    int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
+    for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)bins[i].size();
+    orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
+    for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
+      if (i == ind1 || i == ind2 || i == ind3) continue;
+      for (int id : bins[i]) fn(id);
+    }
+  }
+};
+
+// per-level geometry and scale of StereoParams / StereoBatchParams
+template <class Params> static void fill_stereo_levels(const orbx_t *hl, Params &S) {
+  for (int l = 0; l < hl->nlevels; l++) {
+    const LevelGeom &G = hl->geom[l];
+    S.w[l] = G.w; S.h[l] = G.h; S.pitch[l] = G.pitch; S.off[l] = G.off;
+    S.sf[l] = hl->mvScaleFactor[l]; S.invsf[l] = hl->mvInvScaleFactor[l];
+  }
+  S.nlevels = hl->nlevels; S.rows = hl->rows;
+}
+
 extern "C" {
 
 orbm_t *orbm_create(int device) {
@@ -1523,6 +1557,20 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
                       use_second, d_slot, d_slot_obs, d_moq, d_bd, d_nm, (hipStream_t)stream_, o);   // verbatim: NULL is the device's default stream
 }
 
+// The tail of a host search whose outputs were staged as [first .. d_nm]: that range comes down through the pinned mirror in one copy
+// and one synchronisation; slot / slot_obs (n entries; nothing when n == 0) are copied out and the match count is returned.
+static int download_slots(orbm_t *m, hipStream_t s, void *first, void *d_slot, void *d_sobs, void *d_nm, int n, int32_t *slot, uint8_t *slot_obs) {
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, first), first, (uint8_t *)d_nm + sizeof(int32_t) - (uint8_t *)first, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  int32_t nm = 0;
+  if (n > 0) {
+    memcpy(slot, mirror_of(m, d_slot), sizeof(int32_t) * (size_t)n);
+    memcpy(slot_obs, mirror_of(m, d_sobs), (size_t)n);
+    memcpy(&nm, mirror_of(m, d_nm), sizeof(nm));
+  }
+  return nm;
+}
+
 // One host-pointer search: inputs up as one staged block, outputs down as one block, one synchronisation.  partner / qside: host
 // arrays of a fisheye-stereo search, staged here; o carries the rest of its options (o.scan_mode is set here).
 static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q, float nnratio, int th_dist, int use_second, int32_t *slot,
@@ -1571,14 +1619,10 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
   const int rs = search_batch(m, &df, n, nullptr, 0, &dq, nq, nullptr, 0, 1, nnratio, th_dist, use_second, (int32_t *)d[SLOT], (uint8_t *)d[SOBS],
                               (int32_t *)d[MOQ], (int32_t *)d[BD], (int32_t *)d[NM], s, o);
   if (rs < 0) return rs;
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[SLOT]), d[SLOT], (uint8_t *)d[NM] + sizeof(int32_t) - (uint8_t *)d[SLOT], hipMemcpyDeviceToHost, s));
-  MCHECK(m, hipStreamSynchronize(s));
-  memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
-  memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
+  const int nm = download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  if (nm < 0) return nm;
   if (match_of_query) memcpy(match_of_query, mirror_of(m, d[MOQ]), iq);
   if (best_dist) memcpy(best_dist, mirror_of(m, d[BD]), iq);
-  int32_t nm = 0;
-  memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
   return nm;
 }
 
@@ -1597,6 +1641,112 @@ static void mat3_mul_add(const float *R, const float *x, const float *t, float *
   }
 }
 
+// ---- reference expressions the host paths share, each stated once --------------------------------------------------------------
+// Camera centre of a row-major 4x4 [Rcw | tcw]: Ow = -Rcw.t()*tcw (e.g. ORBmatcher.cc:2041, :2297), the generic cv::gemm path:
+// accumulated in double, negated there, rounded once.
+static void camera_centre(const float *T, float *Ow) {
+  for (int i = 0; i < 3; i++) {
+    double acc = 0;
+    for (int k = 0; k < 3; k++) acc += (double)T[4 * k + i] * (double)T[4 * k + 3];
+    Ow[i] = (float)(-acc);
+  }
+}
+
+// Decompose Scw (ORBmatcher.cc:498-503, :1668-1673): scw = sqrt(row0 . row0) (Mat::dot accumulates in double); Rcw = sRcw/scw,
+// tcw = t/scw, as a row-major 4x4 T = [Rcw | tcw] so that mat3_mul_add applies; and the camera centre of T.
+static void decompose_sim3(const float *Scw, float *T, float *Ow) {
+  double dot = 0;
+  for (int k = 0; k < 3; k++) dot += (double)Scw[k] * (double)Scw[k];
+  const float scw = (float)sqrt(dot);
+  const double inv = 1. / (double)scw;
+  for (int i = 0; i < 16; i++) T[i] = 0.f;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) T[4 * i + j] = (float)((double)Scw[4 * i + j] * inv);
+  camera_centre(T, Ow);
+}
+
+// cv::norm of a 3-vector: the squares are accumulated in double, the root is rounded to float
+static float norm3(const float *p) {
+  double n2 = 0;
+  for (int k = 0; k < 3; k++) n2 += (double)p[k] * (double)p[k];
+  return (float)sqrt(n2);
+}
+
+// The scale-invariance gate of the projection searches: true when `dist` lies outside [0.8 * min_dist, 1.2 * max_dist]
+// (MapPoint::GetMinDistanceInvariance / GetMaxDistanceInvariance, MapPoint.cc:552-563)
+static bool outside_scale_range(float dist, float min_dist, float max_dist) { return dist < 0.8f * min_dist || dist > 1.2f * max_dist; }
+
+// The viewing-angle gate: true when PO . Pn < 0.5 * dist, the dot product in double (Mat::dot)
+static bool views_too_obliquely(const float *PO, const float *Pn, float dist) {
+  double pd = 0;
+  for (int k = 0; k < 3; k++) pd += (double)PO[k] * (double)Pn[k];
+  return pd < 0.5 * (double)dist;
+}
+
+// MapPoint::PredictScale, MapPoint.cc:570-602: ceil(log(max_dist / dist) / log(scale factor)) clamped to the pyramid.  (The device form in
+// k_local_map_project rounds through its cvttss2si emulation and is a separate statement on purpose.)
+static int predict_level(float max_dist, float dist, float log_sf, int nlevels) {
+  const float ratio = max_dist / dist;
+  int lvl = (int)ceilf(logf(ratio) / log_sf);
+  return lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
+}
+
+// Rotation pruning of the projection searches: ids are keypoints of the searched frame, a pruned one gives its map point back.
+static int prune_by_rotation(int nq, const int32_t *moq, const float *query_angle, const orbx_keypoint_t *keys, int32_t *slot,
+                             uint8_t *slot_obs, int nmatches) {
+  RotHist H;
+  for (int i = 0; i < nq; i++)
+    if (moq[i] >= 0) H.add(query_angle[i] - keys[moq[i]].angle, moq[i]);
+  H.for_each_pruned([&](int idx) { slot[idx] = -1; slot_obs[idx] = 0; nmatches--; });
+  return nmatches;
+}
+
+// The query arrays of a host-side projection loop and their orbm_queries_t view: queries that fail a gate stay at flags = 0.
+struct QueryArrays {
+  std::vector<float> u, v, rad, ur;   // ur only with_ur (Fuse's mvuRight test)
+  std::vector<int32_t> minl, maxl;
+  std::vector<uint8_t> flags;
+  bool with_ur;
+  explicit QueryArrays(int nq, bool with_ur = false)
+      : u(nq, 0.f), v(nq, 0.f), rad(nq, 0.f), ur(with_ur ? nq : 0, 0.f), minl(nq, -1), maxl(nq, -1), flags(nq, 0), with_ur(with_ur) {}
+  orbm_queries_t view(const uint8_t *desc) const {
+    orbm_queries_t q;
+    q.nq = (int)u.size(); q.descriptors = desc; q.u = u.data(); q.v = v.data(); q.radius = rad.data();
+    q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = with_ur ? ur.data() : nullptr; q.flags = flags.data();
+    return q;
+  }
+};
+
+// The query arrays a projection kernel writes, carved out of `buf` (29 B per query, in blocks of 64 queries) - grows on demand, not
+// on the steady-state path.  moq: where the search may put match_of_query when the caller has no array for it.
+struct QueryScratch { float *u, *v, *r, *ur; int32_t *minl, *maxl, *moq; uint8_t *flags; };
+static int carve_query_scratch(orbm_t *m, DevBuf &buf, hipStream_t s, int npairs, int stride, int maxq, QueryScratch &Q) {
+  const size_t nqa = (size_t)(npairs - 1) * stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
+  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
+  if (need > buf.bytes) {
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, buf.reserve(need + (need >> 2)));
+  }
+  float *qf = (float *)buf.p;
+  int32_t *qi = (int32_t *)(qf + 4 * nq4);
+  Q.u = qf; Q.v = qf + nq4; Q.r = qf + 2 * nq4; Q.ur = qf + 3 * nq4;
+  Q.minl = qi; Q.maxl = qi + nq4; Q.moq = qi + 2 * nq4; Q.flags = (uint8_t *)(qi + 3 * nq4);
+  return 0;
+}
+static orbm_queries_t scratch_view(const QueryScratch &Q, int nq, const uint8_t *desc, bool with_ur) {
+  orbm_queries_t q;
+  q.nq = nq; q.descriptors = desc; q.u = Q.u; q.v = Q.v; q.radius = Q.r;
+  q.min_level = Q.minl; q.max_level = Q.maxl; q.u_r = with_ur ? Q.ur : nullptr; q.flags = Q.flags;
+  return q;
+}
+
+static bool valid_local_map(const orbm_local_map_t *map) {
+  return map->eligible && map->Xw && map->normal && map->max_dist && map->min_dist && map->mpdesc && map->Tcw;
+}
+static bool valid_track(const orbm_track_t *t) {
+  return t->in_view && t->proj_x && t->proj_y && t->proj_xr && t->depth && t->view_cos && t->level;
+}
+
 static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
                                   const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n, int last_n_stride, int npairs,
                                   const float *sf, int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
@@ -1608,17 +1758,10 @@ static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int fram
   const int maxq = d_last_n ? last_stride : last0->n;
   if (maxq <= 0 || last_stride < maxq) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
-  // scratch: the query arrays the projection kernel writes (29 B per query) - grows on demand, not on the steady-state path
-  const size_t nqa = (size_t)(npairs - 1) * last_stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
-  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
-  if (need > m->d_lfq.bytes) {
-    MCHECK(m, hipStreamSynchronize(s));
-    MCHECK(m, m->d_lfq.reserve(need + (need >> 2)));
-  }
-  float *qf = (float *)m->d_lfq.p;
-  int32_t *qi = (int32_t *)(qf + 4 * nq4);
-  uint8_t *qfl = (uint8_t *)(qi + 3 * nq4);
-  int32_t *moq = d_moq ? d_moq : qi + 2 * nq4;
+  QueryScratch Q;
+  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, last_stride, maxq, Q);
+  if (rq < 0) return rq;
+  int32_t *moq = d_moq ? d_moq : Q.moq;
   LastFrameParams P;
   memset(&P, 0, sizeof(P));
   P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
@@ -1630,12 +1773,10 @@ static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int fram
   P.cam_type = cam_type;
   for (int k = 0; k < (cam_type == 0 ? 4 : 8); k++) P.cam[k] = cam_params[k];
   P.mb = mb; P.mbf = mbf; P.th = th; P.bMono = bMono ? 1 : 0;
-  P.qu = qf; P.qv = qf + nq4; P.qr = qf + 2 * nq4; P.qur = qf + 3 * nq4;
-  P.qminl = qi; P.qmaxl = qi + nq4; P.qflags = qfl;
+  P.qu = Q.u; P.qv = Q.v; P.qr = Q.r; P.qur = Q.ur;
+  P.qminl = Q.minl; P.qmaxl = Q.maxl; P.qflags = Q.flags;
   hipLaunchKernelGGL(k_lastframe_project, dim3((last_stride + 255) / 256, npairs), dim3(256), 0, s, P);
-  orbm_queries_t q;
-  q.nq = last0->n; q.descriptors = last0->mpdesc; q.u = P.qu; q.v = P.qv; q.radius = P.qr;
-  q.min_level = P.qminl; q.max_level = P.qmaxl; q.u_r = cur0->u_right ? P.qur : nullptr; q.flags = P.qflags;
+  const orbm_queries_t q = scratch_view(Q, last0->n, last0->mpdesc, cur0->u_right != nullptr);
   SearchOpts o;
   o.scan_mode = scan_mode;
   int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, last_stride, d_last_n, last_n_stride, npairs, 0.f, ORBM_TH_HIGH, 0,
@@ -1712,13 +1853,7 @@ int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, con
   const int rs = search_last_frame_batch(m, &df, n, nullptr, 0, &dl, nLast, nullptr, 0, 1, sf, nlevels, cam_type, cam_params, mb, mbf, th, bMono,
                                          checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
   if (rs < 0) return rs;
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[SLOT]), d[SLOT], (uint8_t *)d[NM] + sizeof(int32_t) - (uint8_t *)d[SLOT], hipMemcpyDeviceToHost, s));
-  MCHECK(m, hipStreamSynchronize(s));
-  memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
-  memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
-  int32_t nm = 0;
-  memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
-  return nm;
+  return download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
 }
 
 // Tracking::SearchLocalPoints on the device: k_local_map_project (isInFrustum + the query preparation of M2), then the M2 search
@@ -1730,9 +1865,7 @@ static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_str
                               const orbm_track_t *track0, int32_t *d_nmatches, hipStream_t s, bool search) {
   if (!m || !cur0 || !map0 || !track0 || !sf || !cam_params || npairs <= 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
-  if (!map0->eligible || !map0->Xw || !map0->normal || !map0->max_dist || !map0->min_dist || !map0->mpdesc || !map0->Tcw) return ORBX_E_ARG;
-  if (!track0->in_view || !track0->proj_x || !track0->proj_y || !track0->proj_xr || !track0->depth || !track0->view_cos || !track0->level)
-    return ORBX_E_ARG;
+  if (!valid_local_map(map0) || !valid_track(track0)) return ORBX_E_ARG;
   if (search && (!cur0->keys_un || !cur0->descriptors)) return ORBX_E_ARG;
   const int maxq = d_map_n ? map_stride : map0->n;
   const int maxn = d_frame_n ? frame_stride : cur0->n;
@@ -1741,16 +1874,9 @@ static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_str
   if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
   if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
-  // scratch: the query arrays the projection kernel writes (29 B per query) - grows on demand, not on the steady-state path
-  const size_t nqa = (size_t)(npairs - 1) * map_stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
-  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
-  if (need > m->d_lmq.bytes) {
-    MCHECK(m, hipStreamSynchronize(s));
-    MCHECK(m, m->d_lmq.reserve(need + (need >> 2)));
-  }
-  float *qf = (float *)m->d_lmq.p;
-  int32_t *qi = (int32_t *)(qf + 4 * nq4);
-  uint8_t *qfl = (uint8_t *)(qi + 3 * nq4);
+  QueryScratch Q;
+  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, maxq, Q);
+  if (rq < 0) return rq;
   LocalMapParams P;
   memset(&P, 0, sizeof(P));
   P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
@@ -1764,17 +1890,15 @@ static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_str
   P.mbf = mbf; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
   P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
   P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
-  P.qu = qf; P.qv = qf + nq4; P.qr = qf + 2 * nq4; P.qur = qf + 3 * nq4;
-  P.qminl = qi; P.qmaxl = qi + nq4; P.qflags = qfl;
+  P.qu = Q.u; P.qv = Q.v; P.qr = Q.r; P.qur = Q.ur;
+  P.qminl = Q.minl; P.qmaxl = Q.maxl; P.qflags = Q.flags;
   hipLaunchKernelGGL(k_local_map_project, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P);
   if (search) {
-    orbm_queries_t q;
-    q.nq = map0->n; q.descriptors = map0->mpdesc; q.u = P.qu; q.v = P.qv; q.radius = P.qr;
-    q.min_level = P.qminl; q.max_level = P.qmaxl; q.u_r = cur0->u_right ? P.qur : nullptr; q.flags = P.qflags;
+    const orbm_queries_t q = scratch_view(Q, map0->n, map0->mpdesc, cur0->u_right != nullptr);
     SearchOpts o;
     o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
     const int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, map_stride, d_map_n, map_n_stride, npairs, nnratio,
-                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, d_moq ? d_moq : qi + 2 * nq4, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-139
+                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, d_moq ? d_moq : Q.moq, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-139
     if (rc < 0) return rc;
   }
   MCHECK(m, hipGetLastError());
@@ -1797,8 +1921,7 @@ int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf
                              float nnratio, int32_t *slot, uint8_t *slot_obs, int32_t *match_of_point, const orbm_track_t *track) {
   if (!m || !cur || !map || !track || !sf || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
-  if (!map->eligible || !map->Xw || !map->normal || !map->max_dist || !map->min_dist || !map->mpdesc || !map->Tcw) return ORBX_E_ARG;
-  if (!track->in_view || !track->proj_x || !track->proj_y || !track->proj_xr || !track->depth || !track->view_cos || !track->level) return ORBX_E_ARG;
+  if (!valid_local_map(map) || !valid_track(track)) return ORBX_E_ARG;
   const int n = cur->n, nmp = map->n;
   if (n < 0 || nmp < 0) return ORBX_E_ARG;
   if (n > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
@@ -1831,15 +1954,8 @@ int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf
   const int rs = search_local_batch(m, &df, n, nullptr, 0, &dm, nmp, nullptr, 0, 1, sf, nlevels, log_sf, cam_type, cam_params, mbf, view_cos_limit,
                                     th, bFarPoints, th_far, nnratio, dslot, dsobs, (int32_t *)d[MOQ], &dt, dnm, s, n > 0);
   if (rs < 0) return rs;
-  uint8_t *first = n > 0 ? (uint8_t *)d[SLOT] : (uint8_t *)d[MOQ];
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, first), first, (uint8_t *)d[NM] + sizeof(int32_t) - first, hipMemcpyDeviceToHost, s));
-  MCHECK(m, hipStreamSynchronize(s));
-  int32_t nm = 0;
-  if (n > 0) {
-    memcpy(slot, mirror_of(m, d[SLOT]), sizeof(int32_t) * (size_t)n);
-    memcpy(slot_obs, mirror_of(m, d[SOBS]), (size_t)n);
-    memcpy(&nm, mirror_of(m, d[NM]), sizeof(nm));
-  }
+  const int nm = download_slots(m, s, n > 0 ? d[SLOT] : d[MOQ], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  if (nm < 0) return nm;
   const int32_t *moq = (const int32_t *)mirror_of(m, d[MOQ]);
   const uint8_t *inv = (const uint8_t *)mirror_of(m, d[INV]);
   const float *px = (const float *)mirror_of(m, d[PX]), *py = (const float *)mirror_of(m, d[PY]), *pxr = (const float *)mirror_of(m, d[PXR]);
@@ -1856,9 +1972,6 @@ int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf
   }
   return nm;
 }
-
-static int prune_by_rotation(int nq, const int32_t *moq, const float *query_angle, const orbx_keypoint_t *keys, int32_t *slot,
-                             uint8_t *slot_obs, int nmatches);
 
 // ---- fisheye-stereo frames (Nleft != -1) -------------------------------------------------------------------------
 // One problem over the concatenated keypoints [left ; right] with two queries per map point (even = left image,
@@ -1902,17 +2015,14 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
   if (nLast > 0 && (!has_mp || !Xw || !mpdesc || !last_keys)) return ORBX_E_ARG;
   const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, tlw[3] = {Tlw[3], Tlw[7], Tlw[11]}, trl[3] = {Trl[3], Trl[7], Trl[11]};
   float twc[3], tlc[3];
-  for (int i = 0; i < 3; i++) {  // twc = -Rcw.t()*tcw, :2041
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)Tcw[k * 4 + i] * (double)tcw[k];
-    twc[i] = (float)(s * -1.0);
-  }
+  camera_centre(Tcw, twc);  // twc = -Rcw.t()*tcw, :2041
   mat3_mul_add(Tlw, twc, tlw, tlc);
   const bool bForward = tlc[2] > mb && !bMono, bBackward = -tlc[2] > mb && !bMono;
   const int nq = 2 * nLast;
-  std::vector<float> u(nq, 0.f), v(nq, 0.f), rad(nq, 0.f), qangle(nq, 0.f);
-  std::vector<int32_t> minl(nq, -1), maxl(nq, -1), moq(nq, -1);
-  std::vector<uint8_t> flags(nq, 0), side(nq), qd((size_t)nq * 32);
+  QueryArrays A(nq);
+  std::vector<float> qangle(nq, 0.f);
+  std::vector<int32_t> moq(nq, -1);
+  std::vector<uint8_t> side(nq), qd((size_t)nq * 32);
   for (int i = 0; i < nLast; i++) {
     side[2 * i] = 0; side[2 * i + 1] = 1;
     memcpy(&qd[(size_t)(2 * i) * 32], mpdesc + (size_t)i * 32, 32);
@@ -1935,17 +2045,15 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
     const uint8_t fl = (uint8_t)(1u | ((obs ? (obs[i] & 1u) : 1u) << 1));
     for (int h = 0; h < 2; h++) {
       const int j = 2 * i + h;
-      u[j] = h ? uxr : ux; v[j] = h ? vyr : vy;
-      rad[j] = th * sf[nLastOctave];                           // :2105, :2197
-      if (bForward) { minl[j] = nLastOctave; maxl[j] = -1; }   // :2113-2118, :2201-2206
-      else if (bBackward) { minl[j] = 0; maxl[j] = nLastOctave; }
-      else { minl[j] = nLastOctave - 1; maxl[j] = nLastOctave + 1; }
-      flags[j] = fl;
+      A.u[j] = h ? uxr : ux; A.v[j] = h ? vyr : vy;
+      A.rad[j] = th * sf[nLastOctave];                             // :2105, :2197
+      if (bForward) { A.minl[j] = nLastOctave; A.maxl[j] = -1; }   // :2113-2118, :2201-2206
+      else if (bBackward) { A.minl[j] = 0; A.maxl[j] = nLastOctave; }
+      else { A.minl[j] = nLastOctave - 1; A.maxl[j] = nLastOctave + 1; }
+      A.flags[j] = fl;
     }
   }
-  orbm_queries_t q;
-  q.nq = nq; q.descriptors = qd.data(); q.u = u.data(); q.v = v.data(); q.radius = rad.data();
-  q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = nullptr; q.flags = flags.data();
+  const orbm_queries_t q = A.view(qd.data());
   orbm_frame_t f = *cur;
   f.u_right = nullptr;  // Nleft != -1: no mvuRight test (:2139)
   SearchOpts o;
@@ -1958,29 +2066,6 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
   return prune_by_rotation(nq, moq.data(), qangle.data(), cur->keys_un, slot, slot_obs, nmatches);
 }
 
-// Rotation-consistency pruning shared by the projection searches (e.g. ORBmatcher.cc:2177-2185 + :2263-2286).
-static int prune_by_rotation(int nq, const int32_t *moq, const float *query_angle, const orbx_keypoint_t *keys, int32_t *slot,
-                             uint8_t *slot_obs, int nmatches) {
-  std::vector<std::vector<int>> rotHist(ORBM_HISTO_LENGTH);
-  const float factor = 1.0f / ORBM_HISTO_LENGTH;
-  for (int i = 0; i < nq; i++) {
-    if (moq[i] < 0) continue;
-    float rot = query_angle[i] - keys[moq[i]].angle;
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORBM_HISTO_LENGTH) bin = 0;
-    if (bin >= 0 && bin < ORBM_HISTO_LENGTH) rotHist[bin].push_back(moq[i]);
-  }
-  int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)rotHist[i].size();
-  orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
-    if (i == ind1 || i == ind2 || i == ind3) continue;
-    for (int idx : rotHist[i]) { slot[idx] = -1; slot_obs[idx] = 0; nmatches--; }
-  }
-  return nmatches;
-}
-
 int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, float logScaleFactor, int nKF,
                                        const uint8_t *valid, const float *Xw, const uint8_t *mpdesc, const float *kf_angle,
                                        const float *max_dist, const float *min_dist, const float *Tcw, int cam_type,
@@ -1988,15 +2073,10 @@ int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const
   if (!m || !cur || !sf || nlevels < 1 || nKF < 0 || !Tcw || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
   if (nKF > 0 && (!valid || !Xw || !mpdesc || !kf_angle || !max_dist || !min_dist)) return ORBX_E_ARG;
   const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
-  float Ow[3];  // Ow = -Rcw.t()*tcw, :2297
-  for (int i = 0; i < 3; i++) {
-    double acc = 0;
-    for (int k = 0; k < 3; k++) acc += (double)Tcw[4 * k + i] * (double)tcw[k];
-    Ow[i] = (float)(-acc);
-  }
-  std::vector<float> u(nKF, 0.f), v(nKF, 0.f), rad(nKF, 0.f);
-  std::vector<int32_t> minl(nKF, -1), maxl(nKF, -1), moq(nKF, -1);
-  std::vector<uint8_t> flags(nKF, 0);
+  float Ow[3];
+  camera_centre(Tcw, Ow);  // Ow = -Rcw.t()*tcw, :2297
+  QueryArrays A(nKF);
+  std::vector<int32_t> moq(nKF, -1);
   for (int i = 0; i < nKF; i++) {
     if (!valid[i]) continue;
     const float *x3Dw = Xw + 3 * i;
@@ -2006,22 +2086,17 @@ int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const
     orbm_project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], &ux, &vy);     // :2319
     if (ux < cur->min_x || ux > cur->max_x) continue;                           // :2321-2324
     if (vy < cur->min_y || vy > cur->max_y) continue;
-    double n2 = 0;                                                               // cv::norm(x3Dw-Ow), :2327-2328
-    for (int k = 0; k < 3; k++) { const float po = x3Dw[k] - Ow[k]; n2 += (double)po * (double)po; }
-    const float dist3D = (float)sqrt(n2);
-    const float maxDistance = 1.2f * max_dist[i], minDistance = 0.8f * min_dist[i];
-    if (dist3D < minDistance || dist3D > maxDistance) continue;                 // :2334-2335
-    const float ratio = max_dist[i] / dist3D;                                    // MapPoint::PredictScale, MapPoint.cc:587-602
-    int lvl = (int)ceilf(logf(ratio) / logScaleFactor);
-    lvl = lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
-    u[i] = ux; v[i] = vy;
-    rad[i] = th * sf[lvl];                                                       // :2340
-    minl[i] = lvl - 1; maxl[i] = lvl + 1;                                        // :2342
-    flags[i] = 3;
+    float PO[3];
+    for (int k = 0; k < 3; k++) PO[k] = x3Dw[k] - Ow[k];
+    const float dist3D = norm3(PO);                                              // cv::norm(x3Dw-Ow), :2327-2328
+    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;         // :2334-2335
+    const int lvl = predict_level(max_dist[i], dist3D, logScaleFactor, nlevels); // MapPoint::PredictScale, MapPoint.cc:587-602
+    A.u[i] = ux; A.v[i] = vy;
+    A.rad[i] = th * sf[lvl];                                                     // :2340
+    A.minl[i] = lvl - 1; A.maxl[i] = lvl + 1;                                    // :2342
+    A.flags[i] = 3;
   }
-  orbm_queries_t q;
-  q.nq = nKF; q.descriptors = mpdesc; q.u = u.data(); q.v = v.data(); q.radius = rad.data();
-  q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = nullptr; q.flags = flags.data();
+  const orbm_queries_t q = A.view(mpdesc);
   orbm_frame_t f = *cur;
   f.u_right = nullptr;  // no stereo gate in this overload
   int nmatches = orbm_search_by_projection(m, &f, &q, 0.f, ORBdist, 0, slot, slot_obs, moq.data(), nullptr);
@@ -2043,26 +2118,10 @@ int orbm_search_by_projection_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const 
                                        float ratioHamming, int32_t *slot, uint8_t *slot_obs) {
   if (!m || !kf || !sf || nlevels < 1 || nP < 0 || !Scw || !cam || !slot || !slot_obs || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
   if (nP > 0 && (!valid || !Xw || !normal || !mpdesc || !max_dist || !min_dist)) return ORBX_E_ARG;
-  // Decompose Scw, :498-503: scw = sqrt(row0 . row0) (Mat::dot accumulates in double); Rcw = sRcw/scw, tcw = t/scw
-  double dot = 0;
-  for (int k = 0; k < 3; k++) dot += (double)Scw[k] * (double)Scw[k];
-  const float scw = (float)sqrt(dot);
-  const double inv = 1. / (double)scw;
-  float T[16] = {0};  // row-major [Rcw | tcw] so that the shared 3x3*3x1+t helper applies
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) T[4 * i + j] = (float)((double)Scw[4 * i + j] * inv);
-    T[4 * i + 3] = (float)((double)Scw[4 * i + 3] * inv);
-  }
+  float T[16], Ow[3];
+  decompose_sim3(Scw, T, Ow);                                                 // :498-503
   const float tcw[3] = {T[3], T[7], T[11]};
-  float Ow[3];
-  for (int i = 0; i < 3; i++) {
-    double acc = 0;
-    for (int k = 0; k < 3; k++) acc += (double)T[4 * k + i] * (double)tcw[k];
-    Ow[i] = (float)(-acc);
-  }
-  std::vector<float> u(nP, 0.f), v(nP, 0.f), rad(nP, 0.f);
-  std::vector<int32_t> minl(nP, -1), maxl(nP, -1);
-  std::vector<uint8_t> flags(nP, 0);
+  QueryArrays A(nP);
   for (int i = 0; i < nP; i++) {
     if (!valid[i]) continue;
     const float *p3Dw = Xw + 3 * i;
@@ -2073,23 +2132,17 @@ int orbm_search_by_projection_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const 
     orbm_project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], &ux, &vy);         // :534, pKF->mpCamera->project
     if (!(ux >= kf->min_x && ux < kf->max_x && vy >= kf->min_y && vy < kf->max_y)) continue;  // KeyFrame::IsInImage, KeyFrame.cc:844-847
     float PO[3];
-    double n2 = 0, pd = 0;
-    for (int k = 0; k < 3; k++) { PO[k] = p3Dw[k] - Ow[k]; n2 += (double)PO[k] * (double)PO[k]; }
-    const float dist = (float)sqrt(n2);                                       // cv::norm, :544
-    if (dist < 0.8f * min_dist[i] || dist > 1.2f * max_dist[i]) continue;     // :546
-    for (int k = 0; k < 3; k++) pd += (double)PO[k] * (double)normal[3 * i + k];
-    if (pd < 0.5 * (double)dist) continue;                                    // :552
-    const float ratio = max_dist[i] / dist;                                   // MapPoint::PredictScale(dist, pKF), MapPoint.cc:570-585
-    int lvl = (int)ceilf(logf(ratio) / logScaleFactor);
-    lvl = lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
-    u[i] = ux; v[i] = vy;
-    rad[i] = (float)th * sf[lvl];                                             // :558
-    minl[i] = lvl - 1; maxl[i] = lvl;                                         // :579-580
-    flags[i] = 3;
+    for (int k = 0; k < 3; k++) PO[k] = p3Dw[k] - Ow[k];
+    const float dist = norm3(PO);                                             // cv::norm, :544
+    if (outside_scale_range(dist, min_dist[i], max_dist[i])) continue;        // :546
+    if (views_too_obliquely(PO, normal + 3 * i, dist)) continue;              // :552
+    const int lvl = predict_level(max_dist[i], dist, logScaleFactor, nlevels);   // MapPoint::PredictScale(dist, pKF), MapPoint.cc:570-585
+    A.u[i] = ux; A.v[i] = vy;
+    A.rad[i] = (float)th * sf[lvl];                                           // :558
+    A.minl[i] = lvl - 1; A.maxl[i] = lvl;                                     // :579-580
+    A.flags[i] = 3;
   }
-  orbm_queries_t q;
-  q.nq = nP; q.descriptors = mpdesc; q.u = u.data(); q.v = v.data(); q.radius = rad.data();
-  q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = nullptr; q.flags = flags.data();
+  const orbm_queries_t q = A.view(mpdesc);
   orbm_frame_t f = *kf;
   f.u_right = nullptr;
   // bestDist <= TH_LOW*ratioHamming with an int on the left: same as bestDist <= floor(50.f*ratioHamming)
@@ -2106,9 +2159,7 @@ static int fuse_core(orbm_t *m, const orbm_frame_t *kf, const float *sf, const f
                      const float *min_dist, const float *T /* row-major 4x4 [Rcw | tcw] */, const float *Ow, int cam_type,
                      const float *cam, float bf, float th, bool chi2, int32_t *best_idx, int32_t *best_dist) {
   const float tcw[3] = {T[3], T[7], T[11]};
-  std::vector<float> u(nP, 0.f), v(nP, 0.f), rad(nP, 0.f), ur(nP, 0.f);
-  std::vector<int32_t> minl(nP, -1), maxl(nP, -1);
-  std::vector<uint8_t> flags(nP, 0);
+  QueryArrays A(nP, true);
   for (int i = 0; i < nP; i++) {
     best_idx[i] = -1; best_dist[i] = 256;
     if (!valid[i]) continue;
@@ -2121,23 +2172,17 @@ static int fuse_core(orbm_t *m, const orbm_frame_t *kf, const float *sf, const f
     orbm_project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], &ux, &vy);         // :1487 / :1704
     if (!(ux >= kf->min_x && ux < kf->max_x && vy >= kf->min_y && vy < kf->max_y)) continue;  // KeyFrame::IsInImage, KeyFrame.cc:844-847
     float PO[3];
-    double n2 = 0, pd = 0;
-    for (int k = 0; k < 3; k++) { PO[k] = p3Dw[k] - Ow[k]; n2 += (double)PO[k] * (double)PO[k]; }
-    const float dist3D = (float)sqrt(n2);                                     // cv::norm, :1502 / :1715
-    if (dist3D < 0.8f * min_dist[i] || dist3D > 1.2f * max_dist[i]) continue; // MapPoint.cc:552-563, :1505 / :1718
-    for (int k = 0; k < 3; k++) pd += (double)PO[k] * (double)normal[3 * i + k];
-    if (pd < 0.5 * (double)dist3D) continue;                                  // :1514 / :1724
-    const float ratio = max_dist[i] / dist3D;                                 // MapPoint::PredictScale, MapPoint.cc:570-585
-    int lvl = (int)ceilf(logf(ratio) / logScaleFactor);
-    lvl = lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
-    u[i] = ux; v[i] = vy; ur[i] = ux - bf * invz;                             // :1495
-    rad[i] = th * sf[lvl];                                                    // :1524 / :1731
-    minl[i] = lvl - 1; maxl[i] = lvl;                                         // :1555 / :1752
-    flags[i] = 1;                                                             // takes part, never claims
+    for (int k = 0; k < 3; k++) PO[k] = p3Dw[k] - Ow[k];
+    const float dist3D = norm3(PO);                                           // cv::norm, :1502 / :1715
+    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;      // MapPoint.cc:552-563, :1505 / :1718
+    if (views_too_obliquely(PO, normal + 3 * i, dist3D)) continue;            // :1514 / :1724
+    const int lvl = predict_level(max_dist[i], dist3D, logScaleFactor, nlevels);   // MapPoint::PredictScale, MapPoint.cc:570-585
+    A.u[i] = ux; A.v[i] = vy; A.ur[i] = ux - bf * invz;                       // :1495
+    A.rad[i] = th * sf[lvl];                                                  // :1524 / :1731
+    A.minl[i] = lvl - 1; A.maxl[i] = lvl;                                     // :1555 / :1752
+    A.flags[i] = 1;                                                           // takes part, never claims
   }
-  orbm_queries_t q;
-  q.nq = nP; q.descriptors = mpdesc; q.u = u.data(); q.v = v.data(); q.radius = rad.data();
-  q.min_level = minl.data(); q.max_level = maxl.data(); q.u_r = ur.data(); q.flags = flags.data();
+  const orbm_queries_t q = A.view(mpdesc);
   orbm_frame_t f = *kf;
   std::vector<float> no_ur;
   if (chi2 && !f.u_right) { no_ur.assign((size_t)std::max(kf->n, 1), -1.0f); f.u_right = no_ur.data(); }
@@ -2179,23 +2224,8 @@ int orbm_fuse_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const float *scale_fac
   if (!m || !kf || !scale_factors || nlevels < 1 || nP < 0 || !Scw || !cam || !best_idx || !best_dist || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
   if (nP > 0 && (!valid || !Xw || !normal || !mpdesc || !max_dist || !min_dist)) return ORBX_E_ARG;
   if (nP == 0) return 0;
-  // Decompose Scw, :1668-1673 (as in orbm_search_by_projection_sim3)
-  double dot = 0;
-  for (int k = 0; k < 3; k++) dot += (double)Scw[k] * (double)Scw[k];
-  const float scw = (float)sqrt(dot);
-  const double inv = 1. / (double)scw;
-  float T[16] = {0};
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) T[4 * i + j] = (float)((double)Scw[4 * i + j] * inv);
-    T[4 * i + 3] = (float)((double)Scw[4 * i + 3] * inv);
-  }
-  const float tcw[3] = {T[3], T[7], T[11]};
-  float Ow[3];
-  for (int i = 0; i < 3; i++) {
-    double acc = 0;
-    for (int k = 0; k < 3; k++) acc += (double)T[4 * k + i] * (double)tcw[k];
-    Ow[i] = (float)(-acc);
-  }
+  float T[16], Ow[3];
+  decompose_sim3(Scw, T, Ow);                                                 // :1668-1673
   return fuse_core(m, kf, scale_factors, nullptr, nlevels, log_scale_factor, nP, valid, Xw, normal, mpdesc, max_dist, min_dist, T, Ow, cam_type, cam,
                    0.f, th, false, best_idx, best_dist);
 }
@@ -2205,17 +2235,10 @@ int orbm_fuse_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const float *scale_fac
 // SURVEY.md A.8 [OPENCV-UNVERIFIED]: scalar * Mat scales in double; a product with a transposed or scaled operand
 // accumulates in double; plain 3x3 * 3x1 + 3x1 takes the small-matrix float path (mat3_mul_add).
 namespace {
-struct Sim3Side {  // queries of one direction
-  std::vector<float> u, v, rad;
-  std::vector<int32_t> minl, maxl, best;
-  std::vector<uint8_t> flags;
-};
-// Points of keyframe A (world Xw, pose RAw/tAw) into keyframe B through p_B = sRBA * p_A + tBA.
+// Points of keyframe A (world Xw, pose RAw/tAw) into keyframe B through p_B = sRBA * p_A + tBA: the queries of one direction.
 void sim3_project(const orbm_frame_t *kfB, const float *sfB, int nlevelsB, float logSfB, int nA, const uint8_t *valid, const float *Xw,
                   const float *max_dist, const float *min_dist, const float *RAw, const float *tAw, const float *sRBA, const float *tBA,
-                  const float *cam, float th, Sim3Side &S) {
-  S.u.assign(nA, 0.f); S.v.assign(nA, 0.f); S.rad.assign(nA, 0.f);
-  S.minl.assign(nA, -1); S.maxl.assign(nA, -1); S.best.assign(nA, -1); S.flags.assign(nA, 0);
+                  const float *cam, float th, QueryArrays &S) {
   float TA[16] = {0}, TB[16] = {0};
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { TA[4 * i + j] = RAw[3 * i + j]; TB[4 * i + j] = sRBA[3 * i + j]; }
   for (int i = 0; i < nA; i++) {
@@ -2228,13 +2251,9 @@ void sim3_project(const orbm_frame_t *kfB, const float *sfB, int nlevelsB, float
     const float x = pB[0] * invz, y = pB[1] * invz;
     const float u = cam[0] * x + cam[2], v = cam[1] * y + cam[3];              // :1846-1847, pKF1's intrinsics in both directions
     if (!(u >= kfB->min_x && u < kfB->max_x && v >= kfB->min_y && v < kfB->max_y)) continue;  // KeyFrame::IsInImage
-    double n2 = 0;
-    for (int k = 0; k < 3; k++) n2 += (double)pB[k] * (double)pB[k];
-    const float dist3D = (float)sqrt(n2);                                      // cv::norm, :1855
-    if (dist3D < 0.8f * min_dist[i] || dist3D > 1.2f * max_dist[i]) continue;  // :1858
-    const float ratio = max_dist[i] / dist3D;                                  // MapPoint::PredictScale, MapPoint.cc:570-585
-    int lvl = (int)ceilf(logf(ratio) / logSfB);
-    lvl = lvl < 0 ? 0 : (lvl >= nlevelsB ? nlevelsB - 1 : lvl);
+    const float dist3D = norm3(pB);                                            // cv::norm, :1855
+    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;       // :1858
+    const int lvl = predict_level(max_dist[i], dist3D, logSfB, nlevelsB);      // MapPoint::PredictScale, MapPoint.cc:570-585
     S.u[i] = u; S.v[i] = v; S.rad[i] = th * sfB[lvl];                          // :1865
     S.minl[i] = lvl - 1; S.maxl[i] = lvl;                                      // :1884
     S.flags[i] = 1;
@@ -2266,25 +2285,25 @@ int orbm_search_by_sim3(orbm_t *m, const orbm_frame_t *kf1, const float *sf1, in
     for (int k = 0; k < 3; k++) acc += (double)sR21[3 * i + k] * (double)t12[k];
     t21[i] = (float)(acc * -1.0);
   }
-  Sim3Side A, B;
+  QueryArrays A(N1), B(N2);
+  std::vector<int32_t> bestA(N1, -1), bestB(N2, -1);
   sim3_project(kf2, sf2, nlevels2, log_sf2, N1, valid1, Xw1, max_dist1, min_dist1, R1w, t1w, sR21, t21, cam1, th, A);
   sim3_project(kf1, sf1, nlevels1, log_sf1, N2, valid2, Xw2, max_dist2, min_dist2, R2w, t2w, sR12, t12, cam1, th, B);
-  struct Run { const orbm_frame_t *kf; Sim3Side *S; const uint8_t *desc; int nq; } runs[2] = {{kf2, &A, mpdesc1, N1}, {kf1, &B, mpdesc2, N2}};
+  struct Run { const orbm_frame_t *kf; QueryArrays *S; const uint8_t *desc; int32_t *best; } runs[2] = {{kf2, &A, mpdesc1, bestA.data()},
+                                                                                                        {kf1, &B, mpdesc2, bestB.data()}};
   for (const Run &r : runs) {
-    orbm_queries_t q;
-    q.nq = r.nq; q.descriptors = r.desc; q.u = r.S->u.data(); q.v = r.S->v.data(); q.radius = r.S->rad.data();
-    q.min_level = r.S->minl.data(); q.max_level = r.S->maxl.data(); q.u_r = nullptr; q.flags = r.S->flags.data();
+    const orbm_queries_t q = r.S->view(r.desc);
     orbm_frame_t f = *r.kf;
     f.u_right = nullptr;
     std::vector<int32_t> slot((size_t)r.kf->n, -1);
     std::vector<uint8_t> sobs((size_t)r.kf->n, 0);
-    const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot.data(), sobs.data(), r.S->best.data(), nullptr);  // :1895, :1967
+    const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot.data(), sobs.data(), r.best, nullptr);  // :1895, :1967
     if (rc < 0) return rc;
   }
   int nFound = 0;                                                              // :1973-1987
   for (int i1 = 0; i1 < N1; i1++) {
-    const int idx2 = A.best[i1];
-    if (idx2 >= 0 && B.best[idx2] == i1) { matches12[i1] = idx2; nFound++; }
+    const int idx2 = bestA[i1];
+    if (idx2 >= 0 && bestB[idx2] == i1) { matches12[i1] = idx2; nFound++; }
   }
   return nFound;
 }
@@ -2420,7 +2439,14 @@ int orbm_triangulation_candidates(orbm_t *m, const orbm_keyframe_t *k1, const or
   return total;   // > cap: nothing but cand_start was written; call again with that capacity
 }
 
-static int prune_pairs_by_rotation(const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, int32_t *matches12, int nmatches);
+// rotation-histogram pruning of SearchForTriangulation's pairs, ORBmatcher.cc:1162-1172, :1191-1207
+static int prune_pairs_by_rotation(const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, int32_t *matches12, int nmatches) {
+  RotHist H;   // the reference fills the histogram in merge-walk order; only the bin sizes matter afterwards
+  for (int i = 0; i < k1->n; i++)
+    if (matches12[i] >= 0) H.add(k1->keys_un[i].angle - k2->keys_un[matches12[i]].angle, i);
+  H.for_each_pruned([&](int i1) { matches12[i1] = -1; nmatches--; });
+  return nmatches;
+}
 
 int orbm_search_for_triangulation_pred(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, float ep_x, float ep_y, int epipole_gate,
                                        int bOnlyStereo, int bCoarse, int checkOri, orbm_pair_predicate_t pred, void *user, int32_t *matches12) {
@@ -2513,29 +2539,6 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
   return nmatches;
 }
 
-// rotation-histogram pruning of SearchForTriangulation's pairs, ORBmatcher.cc:1162-1172, :1191-1207
-static int prune_pairs_by_rotation(const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, int32_t *matches12, int nmatches) {
-  std::vector<std::vector<int>> rotHist(ORBM_HISTO_LENGTH);
-  const float factor = 1.0f / ORBM_HISTO_LENGTH;
-  // the reference fills the histogram in merge-walk order; only the bin sizes matter afterwards
-  for (int i = 0; i < k1->n; i++) {
-    if (matches12[i] < 0) continue;
-    float rot = k1->keys_un[i].angle - k2->keys_un[matches12[i]].angle;
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORBM_HISTO_LENGTH) bin = 0;
-    if (bin >= 0 && bin < ORBM_HISTO_LENGTH) rotHist[bin].push_back(i);
-  }
-  int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)rotHist[i].size();
-  orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
-    if (i == ind1 || i == ind2 || i == ind3) continue;
-    for (int idx : rotHist[i]) { matches12[idx] = -1; nmatches--; }
-  }
-  return nmatches;
-}
-
 int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm_frame_t *f2, float *prev_matched, int window_size,
                                    float nnratio, int checkOri, int32_t *matches12) {
   if (!m || !f1 || !f2 || !matches12 || f1->n < 0 || f2->n < 0) return ORBX_E_ARG;
@@ -2570,35 +2573,32 @@ int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm
   // replay of the bookkeeping the device leaves to the host: steals (:781-785) and the rotation histogram (:791-801)
   int nmatches = 0;
   std::vector<int32_t> m21((size_t)f2->n, -1);
-  std::vector<std::vector<int>> rotHist(ORBM_HISTO_LENGTH);
-  const float factor = 1.0f / ORBM_HISTO_LENGTH;
+  RotHist H;
   for (int k = 0; k < nq; k++) {
     const int i2 = acc[k];
     if (i2 < 0) continue;
     const int i1 = qi[k];
     if (m21[i2] >= 0) { matches12[m21[i2]] = -1; nmatches--; }
     matches12[i1] = i2; m21[i2] = i1; nmatches++;
-    if (checkOri) {
-      float rot = f1->keys_un[i1].angle - f2->keys_un[i2].angle;
-      if ((double)rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == ORBM_HISTO_LENGTH) bin = 0;
-      if (bin >= 0 && bin < ORBM_HISTO_LENGTH) rotHist[bin].push_back(i1);
-    }
+    if (checkOri) H.add(f1->keys_un[i1].angle - f2->keys_un[i2].angle, i1);
   }
-  if (checkOri) {
-    int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
-    for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)rotHist[i].size();
-    orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
-    for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int idx1 : rotHist[i])
-        if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; }   // :815-819
-    }
-  }
+  if (checkOri)   // a stolen match stays in its bin (it counts for the maxima) and is skipped here, :815-819
+    H.for_each_pruned([&](int idx1) { if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; } });
   for (int i = 0; i < n1; i++)                                     // :826-828
     if (matches12[i] >= 0) { prev_matched[2 * i] = f2->keys_un[matches12[i]].x; prev_matched[2 * i + 1] = f2->keys_un[matches12[i]].y; }
   return nmatches;
+}
+
+// ---- ComputeStereoMatches: what the two entry points ask of a pair of extractors -----------------------------------------------
+// Same device, image size and pyramid depth; same_scale: also the same scale factors, which the batch form asks for and the host
+// form never did (it goes on accepting what it accepted).
+static int stereo_check_pair(orbx_t *hl, orbx_t *hr, const char *what, bool same_scale) {
+  if (hl->device != hr->device || hl->rows != hr->rows || hl->cols != hr->cols || hl->nlevels != hr->nlevels ||
+      (same_scale && hl->mvScaleFactor != hr->mvScaleFactor)) {
+    hl->err = std::string(what) + ": the two extractors must share device, image size and pyramid";
+    return ORBX_E_ARG;
+  }
+  return 0;
 }
 
 int orbx_compute_stereo_matches(orbx_t *hl, int frame_l, orbx_t *hr, int frame_r, int nL, const orbx_keypoint_t *keysL,
@@ -2607,10 +2607,7 @@ int orbx_compute_stereo_matches(orbx_t *hl, int frame_l, orbx_t *hr, int frame_r
   if (!hl || !hr || nL < 0 || nR < 0 || !uRight || !depth) return ORBX_E_ARG;
   if (!hl->have_last || !hr->have_last) { hl->err = "orbx_compute_stereo_matches: extract both images first"; return ORBX_E_ARG; }
   if (frame_l < 0 || frame_l >= hl->last.nframes || frame_r < 0 || frame_r >= hr->last.nframes) return ORBX_E_ARG;
-  if (hl->device != hr->device || hl->rows != hr->rows || hl->cols != hr->cols || hl->nlevels != hr->nlevels) {
-    hl->err = "orbx_compute_stereo_matches: the two extractors must share device, image size and pyramid";
-    return ORBX_E_ARG;
-  }
+  if (stereo_check_pair(hl, hr, "orbx_compute_stereo_matches", false) < 0) return ORBX_E_ARG;
   for (int i = 0; i < nL; i++) { uRight[i] = -1.0f; depth[i] = -1.0f; }   // Frame.cc:903-904
   if (nL == 0 || nR == 0) return 0;
   if (!keysL || !descL || !keysR || !descR || nR > 65535) return ORBX_E_ARG;
@@ -2633,12 +2630,7 @@ int orbx_compute_stereo_matches(orbx_t *hl, int frame_l, orbx_t *hr, int frame_r
   S.imgR0 = hr->last.img0 + (size_t)frame_r * hr->last.img0_frame_stride; S.strideR0 = hr->last.img0_stride;
   S.pyrL = hl->last.pyr + (size_t)frame_l * hl->last.pyr_fs;
   S.pyrR = hr->last.pyr + (size_t)frame_r * hr->last.pyr_fs;
-  for (int l = 0; l < hl->nlevels; l++) {
-    const LevelGeom &G = hl->geom[l];
-    S.w[l] = G.w; S.h[l] = G.h; S.pitch[l] = G.pitch; S.off[l] = G.off;
-    S.sf[l] = hl->mvScaleFactor[l]; S.invsf[l] = hl->mvInvScaleFactor[l];
-  }
-  S.nlevels = hl->nlevels; S.rows = hl->rows;
+  fill_stereo_levels(hl, S);
   S.kpL = (const float *)bufs[0].p; S.kpR = (const float *)bufs[1].p;
   S.descL = (const uint32_t *)bufs[2].p; S.descR = (const uint32_t *)bufs[3].p;
   S.nL = nL; S.nR = nR; S.mb = mb; S.mbf = mbf;
@@ -2682,11 +2674,7 @@ int orbx_compute_stereo_matches_batch_device(orbx_t *hl, orbx_t *hr, int nframes
     hl->err = "orbx_compute_stereo_matches_batch_device: nframes outside the two extractors' last batches";
     return ORBX_E_ARG;
   }
-  if (hl->device != hr->device || hl->rows != hr->rows || hl->cols != hr->cols || hl->nlevels != hr->nlevels ||
-      hl->mvScaleFactor != hr->mvScaleFactor) {
-    hl->err = "orbx_compute_stereo_matches_batch_device: the two extractors must share device, image size and pyramid";
-    return ORBX_E_ARG;
-  }
+  if (stereo_check_pair(hl, hr, "orbx_compute_stereo_matches_batch_device", true) < 0) return ORBX_E_ARG;
   if (!(mb > 0.f)) { hl->err = "orbx_compute_stereo_matches_batch_device: mb must be positive"; return ORBX_E_ARG; }
   if (cap < hl->maxKeypoints || cap < hr->maxKeypoints || cap > 65535) {
     hl->err = "orbx_compute_stereo_matches_batch_device: cap must be in [orbx_max_keypoints, 65535]";
@@ -2700,14 +2688,9 @@ int orbx_compute_stereo_matches_batch_device(orbx_t *hl, orbx_t *hr, int nframes
   S.imgR0 = hr->last.img0; S.strideR0 = hr->last.img0_stride; S.fsR0 = hr->last.img0_frame_stride;
   S.pyrL = hl->last.pyr; S.pyrFsL = hl->last.pyr_fs;
   S.pyrR = hr->last.pyr; S.pyrFsR = hr->last.pyr_fs;
+  fill_stereo_levels(hl, S);
   float sfMax = 0.f;
-  for (int l = 0; l < hl->nlevels; l++) {
-    const LevelGeom &G = hl->geom[l];
-    S.w[l] = G.w; S.h[l] = G.h; S.pitch[l] = G.pitch; S.off[l] = G.off;
-    S.sf[l] = hl->mvScaleFactor[l]; S.invsf[l] = hl->mvInvScaleFactor[l];
-    sfMax = std::max(sfMax, S.sf[l]);
-  }
-  S.nlevels = hl->nlevels; S.rows = hl->rows;
+  for (int l = 0; l < S.nlevels; l++) sfMax = std::max(sfMax, S.sf[l]);
   S.nbands = (hl->rows + STEREO_BAND - 1) / STEREO_BAND;
   if (S.nbands > STEREO_MAX_BANDS) { hl->err = "orbx_compute_stereo_matches_batch_device: more than 4096 rows"; return ORBX_E_ARG; }
   // a right keypoint covers the rows floor(y - r) .. ceil(y + r), r = 2 * scale (:916-918): at most 2r + 3 of them (+ 1 for the
@@ -2787,24 +2770,13 @@ static int bow_core(orbm_t *m, const orbm_keyframe_t *kf, const orbm_keyframe_t 
   for (int i = 0; i < nout; i++) nmatches += out[i] >= 0 ? 1 : 0;
   if (!checkOri) return nmatches;
   // rotation histogram (:391-404, :451-466 resp. :929-939, :960-975): bins hold the index `out` is addressed with
-  std::vector<std::vector<int>> rotHist(ORBM_HISTO_LENGTH);
-  const float factor = 1.0f / ORBM_HISTO_LENGTH;
+  RotHist H;
   for (int i = 0; i < nout; i++) {
     if (out[i] < 0) continue;
     const int idxKF = kf_kf ? i : out[i], idxF = kf_kf ? out[i] : i;
-    float rot = kf->keys_un[idxKF].angle - f->keys_un[idxF].angle;
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORBM_HISTO_LENGTH) bin = 0;
-    if (bin >= 0 && bin < ORBM_HISTO_LENGTH) rotHist[bin].push_back(i);
+    H.add(kf->keys_un[idxKF].angle - f->keys_un[idxF].angle, i);
   }
-  int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)rotHist[i].size();
-  orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
-  for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
-    if (i == ind1 || i == ind2 || i == ind3) continue;
-    for (int idx : rotHist[i]) { out[idx] = -1; nmatches--; }
-  }
+  H.for_each_pruned([&](int idx) { out[idx] = -1; nmatches--; });
   return nmatches;
 }
 
