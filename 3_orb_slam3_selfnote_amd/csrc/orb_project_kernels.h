@@ -6,13 +6,29 @@
 //
 // Every operation is the IEEE-754 single / double operation of the reference's expression in source order (no contraction),
 // and the libm calls of KannalaBrandt8::project go through the bit-exact replicas of glibc's atan2f (orb_atan2f.h) and
-// sinf / cosf (orb_sincos.h), so u, v - and with them the search windows - carry the same bits as on the host.
+// sinf / cosf (orb_sincos.h), so u, v - and with them the search windows - carry the same bits as on the host.  The expressions
+// themselves are the host loops' own functions (orb_ref_geometry.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "orb_atan2f.h"
 #include "orb_logf.h"
-#include "orb_sincos.h"
+#include "orb_ref_geometry.h"
+
+// The current frame of a projection search: image bounds, scale factors, camera (host: fill_view)
+struct ViewParams {
+  float min_x, max_x, min_y, max_y;
+  float sf[16]; int nlevels;
+  int cam_type; float cam[8];
+};
+
+// The query arrays a projection kernel writes for the search behind it (same stride as its input side; host: carve_query_scratch).
+// moq: where the search may put match_of_query when the caller has no array for it.
+struct QueryScratch { float *u, *v, *r, *ur; int32_t *minl, *maxl, *moq; uint8_t *flags; };
+
+__device__ __forceinline__ void store_query(const QueryScratch &Q, size_t o, float u, float v, float rad, float ur, int minl, int maxl, uint8_t fl) {
+  Q.u[o] = u; Q.v[o] = v; Q.r[o] = rad; Q.ur[o] = ur;
+  Q.minl[o] = minl; Q.maxl[o] = maxl; Q.flags[o] = fl;
+}
 
 struct LastFrameParams {
   // last-frame side; problem p is at element offset p * last_stride
@@ -23,59 +39,10 @@ struct LastFrameParams {
   const float *Tcw, *Tlw;  // row-major 4x4 per problem (16 floats)
   int last_stride;
   const int32_t *last_n; int last_n_stride; int last_n_const;
-  // current frame: image bounds, scale factors, camera
-  float min_x, max_x, min_y, max_y;
-  float sf[16]; int nlevels;
-  int cam_type; float cam[8];
+  ViewParams V;
   float mb, mbf, th; int bMono;
-  // out: the query arrays of the projection search (same stride)
-  float *qu, *qv, *qr, *qur;
-  int32_t *qminl, *qmaxl;
-  uint8_t *qflags;
+  QueryScratch Q;          // out
 };
-
-// cv::Mat `A*B + C` for a 3x3 * 3x1 product: float products summed in float, then C added (as on the host path)
-__device__ __forceinline__ void dev_mat3_mul_add(const float *R, const float *x, const float *t, float *out) {  // R: row stride 4
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const float t0 = R[i * 4 + 0] * x[0] + R[i * 4 + 1] * x[1] + R[i * 4 + 2] * x[2];
-    out[i] = (float)((double)t0 + (double)t[i]);
-  }
-}
-
-// -Rcw.t()*tcw (ORBmatcher.cc:2041, Frame::UpdatePoseMatrices Frame.cc:538): the generic gemm path, double accumulation, alpha = -1.
-// T: row-major 4x4, tcw = column 3.
-__device__ __forceinline__ void dev_camera_centre(const float *T, float *Ow) {
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) s += (double)T[k * 4 + a] * (double)T[k * 4 + 3];
-    Ow[a] = (float)(s * -1.0);
-  }
-}
-
-// GeometricCamera::project(cv::Point3f): 0 Pinhole (Pinhole.cpp:46-49), 1 KannalaBrandt8 (KannalaBrandt8.cpp:29-45)
-__device__ __forceinline__ void dev_project(int cam_type, const float *p, float X, float Y, float Z, float &u, float &v) {
-  if (cam_type == 0) {
-    u = p[0] * X / Z + p[2];
-    v = p[1] * Y / Z + p[3];
-  } else {
-    const float x2_plus_y2 = X * X + Y * Y;
-    const float theta = orbat::ref_atan2f(sqrtf(x2_plus_y2), Z);
-    const float psi = orbat::ref_atan2f(Y, X);
-    const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2, theta9 = theta7 * theta2;
-    const float r = theta + p[4] * theta3 + p[5] * theta5 + p[6] * theta7 + p[7] * theta9;
-#ifdef ORB_KB8_DOUBLE_TRIG   // see orbm_project (orbhip.hip).  The device's fp64 cos / sin are ROCm's, within 1 ulp of glibc's but NOT verified equal:
-                             // with this switch the windows of config 5 are no longer covered by the bit-exact replicas (parity unpinned)
-    u = (float)((double)(p[0] * r) * cos((double)psi) + (double)p[2]);
-    v = (float)((double)(p[1] * r) * sin((double)psi) + (double)p[3]);
-#else
-    u = p[0] * r * orbsc::ref_cosf(psi) + p[2];   // cos / sin on a float: the <math.h> overloads -> cosf / sinf (libm choices)
-    v = p[1] * r * orbsc::ref_sinf(psi) + p[3];
-#endif
-  }
-}
 
 // One thread per last-frame keypoint: ORBmatcher.cc:2038-2052 (per pair, recomputed by every thread from scalar loads) and
 // :2062-2118 -> (u, v, radius, level window, right coordinate, flags) of query i.
@@ -92,31 +59,28 @@ __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
     const float *Tcw = P.Tcw + (size_t)p * 16, *Tlw = P.Tlw + (size_t)p * 16;
     const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, tlw[3] = {Tlw[3], Tlw[7], Tlw[11]};
     float twc[3], tlc[3];
-    dev_camera_centre(Tcw, twc);           // :2041
-    dev_mat3_mul_add(Tlw, twc, tlw, tlc);  // :2047
+    camera_centre(Tcw, twc);           // :2041
+    mat3_mul_add(Tlw, twc, tlw, tlc);  // :2047
     const bool bForward = tlc[2] > P.mb && !P.bMono, bBackward = -tlc[2] > P.mb && !P.bMono;  // :2051-2052
     const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
     float xc[3];
-    dev_mat3_mul_add(Tcw, xw, tcw, xc);                      // :2072
+    mat3_mul_add(Tcw, xw, tcw, xc);                          // :2072
     const float invzc = (float)(1.0 / (double)xc[2]);        // :2076
     if (!(invzc < 0)) {
       float ux, vy;
-      dev_project(P.cam_type, P.cam, xc[0], xc[1], xc[2], ux, vy);  // :2091
-      const bool inside = !(ux < P.min_x || ux > P.max_x) && !(vy < P.min_y || vy > P.max_y);  // :2094-2097
+      project(P.V.cam_type, P.V.cam, xc[0], xc[1], xc[2], ux, vy);  // :2091
+      const bool inside = inside_bounds(ux, vy, P.V.min_x, P.V.max_x, P.V.min_y, P.V.max_y);  // :2094-2097
       const int oct = __float_as_int(P.last_kp[7 * o + 5]);
-      if (inside && oct >= 0 && oct < P.nlevels) {
+      if (inside && oct >= 0 && oct < P.V.nlevels) {
         u = ux; v = vy;
-        rad = P.th * P.sf[oct];                                   // :2105
-        if (bForward) { minl = oct; maxl = -1; }                  // :2113-2118
-        else if (bBackward) { minl = 0; maxl = oct; }
-        else { minl = oct - 1; maxl = oct + 1; }
+        rad = P.th * P.V.sf[oct];                                 // :2105
+        lastframe_level_window(bForward, bBackward, oct, minl, maxl);   // :2113-2118
         ur = ux - P.mbf * invzc;                                  // :2141
-        fl = (uint8_t)(1u | ((P.obs ? (P.obs[o] & 1u) : 1u) << 1));
+        fl = query_flags(P.obs, o);
       }
     }
   }
-  P.qu[o] = u; P.qv[o] = v; P.qr[o] = rad; P.qur[o] = ur;
-  P.qminl[o] = minl; P.qmaxl[o] = maxl; P.qflags[o] = fl;
+  store_query(P.Q, o, u, v, rad, ur, minl, maxl, fl);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -135,32 +99,12 @@ struct LocalMapParams {
   const float *Tcw;                 // CurrentFrame.mTcw, row-major 4x4 per problem
   int map_stride;
   const int32_t *map_n; int map_n_stride; int map_n_const;
-  // current frame: image bounds, scale factors, camera
-  float min_x, max_x, min_y, max_y;
-  float sf[16]; int nlevels; float log_sf;
-  int cam_type; float cam[8];
+  ViewParams V; float log_sf;
   float mbf, view_cos_limit, th; int bFarPoints; float th_far;
   // out: the MapPoint fields isInFrustum writes (caller arrays, same stride)
   uint8_t *in_view; float *proj_x, *proj_y, *proj_xr, *depth, *view_cos; int32_t *level;
-  // out: the query arrays of the projection search (same stride)
-  float *qu, *qv, *qr, *qur;
-  int32_t *qminl, *qmaxl;
-  uint8_t *qflags;
+  QueryScratch Q;                   // out: the queries of the projection search
 };
-
-// (int) of a float as the reference build converts it (x86 cvttss2si): NaN and values outside the int range give INT_MIN,
-// where gfx950's v_cvt_i32_f32 would saturate
-__device__ __forceinline__ int x86_cvtt_f32_i32(float x) {
-  return (x != x || x >= 2147483648.0f || x < -2147483648.0f) ? (int)0x80000000u : (int)x;
-}
-
-// cv::norm of a 3-vector of floats (NORM_L2: squares summed in double, sqrt in double)
-__device__ __forceinline__ float dev_norm3(const float *a) {
-  double s = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) s += (double)a[k] * (double)a[k];
-  return (float)sqrt(s);
-}
 
 __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
   const int p = blockIdx.y;
@@ -178,11 +122,11 @@ __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
       const float *T = P.Tcw + (size_t)p * 16;
       const float tcw[3] = {T[3], T[7], T[11]};
       float Ow[3];
-      dev_camera_centre(T, Ow);                                   // mOw, Frame.cc:538
+      camera_centre(T, Ow);                                       // mOw, Frame.cc:538
       const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
       float pc[3];
-      dev_mat3_mul_add(T, xw, tcw, pc);                           // Pc = mRcw*P + mtcw (Frame.cc:586)
-      const float pc_dist = dev_norm3(pc);                        // :587
+      mat3_mul_add(T, xw, tcw, pc);                               // Pc = mRcw*P + mtcw (Frame.cc:586)
+      const float pc_dist = norm3(pc);                            // :587
       const float invz = 1.0f / pc[2];                            // :591, float division
       bool in_view = false;
       float px = -1.f, py = -1.f;                                 // :577-578
@@ -190,23 +134,17 @@ __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
       int lvl = 0;
       if (!(pc[2] < 0.0f)) {                                      // :592 (-0 and +0 pass)
         float ux, vy;
-        dev_project(P.cam_type, P.cam, pc[0], pc[1], pc[2], ux, vy);   // :595
-        if (!(ux < P.min_x || ux > P.max_x) && !(vy < P.min_y || vy > P.max_y)) {   // :599-602; a NaN projection passes
+        project(P.V.cam_type, P.V.cam, pc[0], pc[1], pc[2], ux, vy);   // :595
+        if (inside_bounds(ux, vy, P.V.min_x, P.V.max_x, P.V.min_y, P.V.max_y)) {   // :599-602; a NaN projection passes
           px = ux; py = vy;                                       // :605-606
           const float po[3] = {xw[0] - Ow[0], xw[1] - Ow[1], xw[2] - Ow[2]};
-          const float dist = dev_norm3(po);                       // :612
-          const float maxD = 1.2f * P.max_dist[o], minD = 0.8f * P.min_dist[o];   // MapPoint.cc:555-565
-          if (!(dist < minD || dist > maxD)) {                    // :614
+          const float dist = norm3(po);                           // :612
+          if (!outside_scale_range(dist, P.min_dist, P.max_dist, o)) {   // :614
             const float pn[3] = {P.normal[3 * o], P.normal[3 * o + 1], P.normal[3 * o + 2]};
-            double d = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) d += (double)po[k] * (double)pn[k];
-            vcos = (float)(d / (double)dist);                     // :624, Mat::dot in double
+            vcos = (float)(dot3_double(po, pn) / (double)dist);   // :624, Mat::dot in double
             if (!(vcos < P.view_cos_limit)) {                     // :626
               const float ratio = P.max_dist[o] / dist;           // PredictScale, MapPoint.cc:593-596
-              lvl = x86_cvtt_f32_i32(ceilf(orblg::ref_logf(ratio) / P.log_sf));
-              if (lvl < 0) lvl = 0;
-              else if (lvl >= P.nlevels) lvl = P.nlevels - 1;
+              lvl = level_from_log(orblg::ref_logf(ratio), P.log_sf, P.V.nlevels);
               in_view = true;
             }
           }
@@ -219,18 +157,17 @@ __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
         P.proj_xr[o] = xr; P.depth[o] = pc_dist; P.level[o] = lvl; P.view_cos[o] = vcos;
         // ORBmatcher.cc:52-73.  A NaN projection finds no candidate in the reference (every |dx| < r test is false): left out.
         if (!(P.bFarPoints && pc_dist > P.th_far) && px == px && py == py) {
-          float r = ((double)vcos > 0.998) ? 2.5f : 4.0f;         // RadiusByViewingCos, :216-222
+          float r = radius_by_viewing_cos(vcos);                  // :216-222
           if (P.th != 1.0f) r *= P.th;                            // :47, :69-70
-          u = px; v = py; rad = r * P.sf[lvl];                    // :73
+          u = px; v = py; rad = r * P.V.sf[lvl];                  // :73
           minl = lvl - 1; maxl = lvl;
           ur = xr;
-          fl = (uint8_t)(1u | ((P.obs ? (P.obs[o] & 1u) : 1u) << 1));
+          fl = query_flags(P.obs, o);
         }
       }
     }
   }
-  P.qu[o] = u; P.qv[o] = v; P.qr[o] = rad; P.qur[o] = ur;
-  P.qminl[o] = minl; P.qmaxl[o] = maxl; P.qflags[o] = fl;
+  store_query(P.Q, o, u, v, rad, ur, minl, maxl, fl);
 }
 
 // The device build of the logf replica on n floats (orbx_logf_device): lets the tests compare it with the host build, which
@@ -264,27 +201,16 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
   if (t < 32) hist[t] = 0;
   if (t == 0) removed = 0;
   __syncthreads();
-  const float factor = 1.0f / 30;
   for (int i = t; i < n; i += 256) {
     const int m = R.moq[qo + i];
     if (m < 0) continue;
-    float rot = R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3];
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == 30) bin = 0;
-    if (bin >= 0 && bin < 30) atomicAdd(&hist[bin], 1);
+    const int bin = rot_bin(R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3]);
+    if (bin >= 0 && bin < ORBM_HISTO_LENGTH) atomicAdd(&hist[bin], 1);
   }
   __syncthreads();
   if (t == 0) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < 30; i++) {
-      const int s = hist[i];
-      if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-      else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-      else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    int ind1, ind2, ind3;
+    three_maxima(hist, ORBM_HISTO_LENGTH, ind1, ind2, ind3);
     keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
   }
   __syncthreads();
@@ -293,11 +219,8 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
   for (int i = t; i < n; i += 256) {
     const int m = R.moq[qo + i];
     if (m < 0) continue;
-    float rot = R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3];
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == 30) bin = 0;
-    if (bin < 0 || bin >= 30 || bin == k0 || bin == k1 || bin == k2) continue;
+    const int bin = rot_bin(R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3]);
+    if (bin < 0 || bin >= ORBM_HISTO_LENGTH || bin == k0 || bin == k1 || bin == k2) continue;
     R.slot[ko + m] = -1;
     R.slot_obs[ko + m] = 0;
     R.moq[qo + i] = -1;
@@ -312,8 +235,8 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
 // G0: Frame::UndistortKeyPoints (Frame.cc:837-870) for frames resident in HBM - the step between operator() and the
 // searches in the Frame constructor.  cv::undistortPoints(pts, K, D, R = I, P = K) restated: five
 // fixed-point iterations in double, every operation in source order (no contraction; fp64 division and the
-// double -> float conversions are IEEE on gfx950), i.e. the same bits as the host function orbm_undistort_keypoints,
-// which tests/test_gpu_distort.py checks.  One thread per keypoint; only pt changes (:862-868).
+// double -> float conversions are IEEE on gfx950), i.e. the same bits as the host function orbm_undistort_keypoints
+// through the same undistort_point (orb_ref_geometry.h), which tests/test_gpu_distort.py checks.  One thread per keypoint; only pt changes (:862-868).
 // ------------------------------------------------------------------------------------------------------------
 struct UndistortParams {
   const float *keys;           // orbx_keypoint_t AoS viewed as floats, frame f at element offset f * key_stride
@@ -322,23 +245,6 @@ struct UndistortParams {
   const int32_t *counts; int count_stride; int count_const;
   float K[4], D[5]; int nD;
 };
-
-__host__ __device__ __forceinline__ void undistort_point(double u, double v, const float *K, const float *D, int nD, float *ou, float *ov) {
-  const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-  const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = nD > 4 ? D[4] : 0.0;
-  double x = (u - cx) * (1. / fx), y = (v - cy) * (1. / fy);
-  const double x0 = x, y0 = y;
-  for (int it = 0; it < 5; it++) {
-    const double r2 = x * x + y * y;
-    const double icdist = 1. / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
-    const double dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
-    const double dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
-    x = (x0 - dx) * icdist;
-    y = (y0 - dy) * icdist;
-  }
-  *ou = (float)(x * fx + cx);
-  *ov = (float)(y * fy + cy);
-}
 
 __global__ __launch_bounds__(256) void k_undistort(UndistortParams U) {
   const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;

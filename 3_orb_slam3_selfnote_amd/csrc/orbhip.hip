@@ -1182,21 +1182,18 @@ template <int V> using ScanKind = std::integral_constant<int, V>;
 
 // ---- helpers of the C entry points below that are templates (C++ linkage) ----------------------------------------------------
 // Rotation-consistency check of every matcher with checkOri (e.g. ORBmatcher.cc:2177-2185 + :2263-2286): a match goes into the bin
-// of the angle difference of its two keypoints; matches outside the three fullest bins (orbm_three_maxima) are pruned.  What an id
+// of the angle difference of its two keypoints (rot_bin); matches outside the three fullest bins (three_maxima) are pruned.  What an id
 // is and what pruning does to it stay with the caller.
 struct RotHist {
   std::vector<int> bins[ORBM_HISTO_LENGTH];
   void add(float rot, int id) {
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORBM_HISTO_LENGTH) bin = 0;
+    const int bin = rot_bin(rot);
     if (bin >= 0 && bin < ORBM_HISTO_LENGTH) bins[bin].push_back(id);
   }
   template <class F> void for_each_pruned(F fn) const {
     int sizes[ORBM_HISTO_LENGTH], ind1, ind2, ind3;
     for (int i = 0; i < ORBM_HISTO_LENGTH; i++) sizes[i] = (int)bins[i].size();
-    orbm_three_maxima(sizes, ORBM_HISTO_LENGTH, &ind1, &ind2, &ind3);
+    three_maxima(sizes, ORBM_HISTO_LENGTH, ind1, ind2, ind3);
     for (int i = 0; i < ORBM_HISTO_LENGTH; i++) {
       if (i == ind1 || i == ind2 || i == ind3) continue;
       for (int id : bins[i]) fn(id);
@@ -1316,30 +1313,16 @@ int orbm_descriptor_distance(const uint8_t *a, const uint8_t *b) {
 
 void orbm_three_maxima(const int *histo, int L, int *ind1, int *ind2, int *ind3) {  // ORBmatcher.cc:2416-2458
   if (!ind1 || !ind2 || !ind3) return;
-  int max1 = 0, max2 = 0, max3 = 0;
-  *ind1 = *ind2 = *ind3 = -1;
-  if (!histo) return;
-  for (int i = 0; i < L; i++) {
-    const int s = histo[i];
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; *ind3 = *ind2; *ind2 = *ind1; *ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; *ind3 = *ind2; *ind2 = i; }
-    else if (s > max3) { max3 = s; *ind3 = i; }
-  }
-  if ((float)max2 < 0.1f * (float)max1) { *ind2 = -1; *ind3 = -1; }
-  else if ((float)max3 < 0.1f * (float)max1) { *ind3 = -1; }
+  three_maxima(histo, histo ? L : 0, *ind1, *ind2, *ind3);   // no histogram: -1, -1, -1
 }
 
-float orbm_radius_by_viewing_cos(float viewCos) { return ((double)viewCos > 0.998) ? 2.5f : 4.0f; }  // ORBmatcher.cc:216-222
-
-// cv::undistortPoints with R = I, P = K (Frame.cc:856, :883): 5 fixed-point iterations in double; one source
-// for the host functions below and k_undistort (orb_project_kernels.h)
-static void undistort_one(double u, double v, const float *K, const float *D, int nD, float *ou, float *ov) { undistort_point(u, v, K, D, nD, ou, ov); }
+float orbm_radius_by_viewing_cos(float viewCos) { return radius_by_viewing_cos(viewCos); }
 
 void orbm_undistort_keypoints(int n, const orbx_keypoint_t *keys, const float *K, const float *D, int nD, orbx_keypoint_t *keys_un) {
   if (!keys || !keys_un || !K || !D) return;
   for (int i = 0; i < n; i++) {
     orbx_keypoint_t k = keys[i];
-    if (D[0] != 0.0f) undistort_one((double)keys[i].x, (double)keys[i].y, K, D, nD, &k.x, &k.y);
+    if (D[0] != 0.0f) undistort_point((double)keys[i].x, (double)keys[i].y, K, D, nD, &k.x, &k.y);
     keys_un[i] = k;
   }
 }
@@ -1349,7 +1332,7 @@ void orbm_image_bounds(int cols, int rows, const float *K, const float *D, int n
   if (D[0] != 0.0f) {
     const float c[4][2] = {{0.f, 0.f}, {(float)cols, 0.f}, {0.f, (float)rows}, {(float)cols, (float)rows}};
     float o[4][2];
-    for (int i = 0; i < 4; i++) undistort_one((double)c[i][0], (double)c[i][1], K, D, nD, &o[i][0], &o[i][1]);
+    for (int i = 0; i < 4; i++) undistort_point((double)c[i][0], (double)c[i][1], K, D, nD, &o[i][0], &o[i][1]);
     *min_x = std::min(o[0][0], o[2][0]);
     *max_x = std::max(o[1][0], o[3][0]);
     *min_y = std::min(o[0][1], o[1][1]);
@@ -1380,27 +1363,7 @@ int orbm_undistort_keypoints_batch_device(orbm_t *m, const orbx_keypoint_t *d_ke
 
 void orbm_project(int cam_type, const float *p, float X, float Y, float Z, float *u, float *v) {
   if (!p || !u || !v) return;
-  if (cam_type == 0) {  // Pinhole.cpp:46-49
-    *u = p[0] * X / Z + p[2];
-    *v = p[1] * Y / Z + p[3];
-  } else {  // KannalaBrandt8.cpp:29-45
-    const float x2_plus_y2 = X * X + Y * Y;
-    const float theta = orbat::ref_atan2f(sqrtf(x2_plus_y2), Z);
-    const float psi = orbat::ref_atan2f(Y, X);
-    const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2,
-                theta9 = theta7 * theta2;
-    const float r = theta + p[4] * theta3 + p[5] * theta5 + p[6] * theta7 + p[7] * theta9;
-    // cos / sin on a float resolve to the float overloads (cosf / sinf) once <math.h> is in the translation unit, which
-    // opencv2/opencv.hpp brings (libm choices) - the same assumption MapPoint::PredictScale's log(float) rests on;
-    // evaluated through the bit-exact glibc replicas the device uses (tests/test_libm_replicas.py: equal to the host libm)
-#ifdef ORB_KB8_DOUBLE_TRIG   // build switch for reference builds in which cos(psi) / sin(psi) bind ::cos(double) (GCC 5, or no <math.h> wrapper)
-    *u = (float)((double)(p[0] * r) * ::cos((double)psi) + (double)p[2]);
-    *v = (float)((double)(p[1] * r) * ::sin((double)psi) + (double)p[3]);
-#else
-    *u = p[0] * r * orbsc::ref_cosf(psi) + p[2];
-    *v = p[1] * r * orbsc::ref_sinf(psi) + p[3];
-#endif
-  }
+  project(cam_type, p, X, Y, Z, *u, *v);
 }
 
 static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, const int32_t *d_frame_n, int frame_n_stride, const orbm_queries_t *q,
@@ -1631,33 +1594,11 @@ int orbm_search_by_projection(orbm_t *m, const orbm_frame_t *f, const orbm_queri
   return search_host(m, f, q, nnratio, th_dist, use_second, slot, slot_obs, match_of_query, best_dist);
 }
 
-// cv::Mat products of ORBmatcher.cc:2038-2047, :2072 restated: a 3x3 * 3x1 `A*B + C` MatExpr is a single
-// cv::gemm whose small-matrix float path forms a0*b0 + a1*b1 + a2*b2 in float, then adds C; `-A.t()*B` takes the
-// generic path that accumulates in double.  [OPENCV-UNVERIFIED], identical in the test oracle.
-static void mat3_mul_add(const float *R, const float *x, const float *t, float *out) {  // R: row-major, row stride 4
-  for (int i = 0; i < 3; i++) {
-    float t0 = R[i * 4 + 0] * x[0] + R[i * 4 + 1] * x[1] + R[i * 4 + 2] * x[2];
-    out[i] = (float)((double)t0 + (double)t[i]);
-  }
-}
-
-// ---- reference expressions the host paths share, each stated once --------------------------------------------------------------
-// Camera centre of a row-major 4x4 [Rcw | tcw]: Ow = -Rcw.t()*tcw (e.g. ORBmatcher.cc:2041, :2297), the generic cv::gemm path:
-// accumulated in double, negated there, rounded once.
-static void camera_centre(const float *T, float *Ow) {
-  for (int i = 0; i < 3; i++) {
-    double acc = 0;
-    for (int k = 0; k < 3; k++) acc += (double)T[4 * k + i] * (double)T[4 * k + 3];
-    Ow[i] = (float)(-acc);
-  }
-}
-
+// ---- reference expressions of the host paths on top of the shared ones (orb_ref_geometry.h) -----------------------------------------
 // Decompose Scw (ORBmatcher.cc:498-503, :1668-1673): scw = sqrt(row0 . row0) (Mat::dot accumulates in double); Rcw = sRcw/scw,
 // tcw = t/scw, as a row-major 4x4 T = [Rcw | tcw] so that mat3_mul_add applies; and the camera centre of T.
 static void decompose_sim3(const float *Scw, float *T, float *Ow) {
-  double dot = 0;
-  for (int k = 0; k < 3; k++) dot += (double)Scw[k] * (double)Scw[k];
-  const float scw = (float)sqrt(dot);
+  const float scw = norm3(Scw);
   const double inv = 1. / (double)scw;
   for (int i = 0; i < 16; i++) T[i] = 0.f;
   for (int i = 0; i < 3; i++)
@@ -1665,31 +1606,11 @@ static void decompose_sim3(const float *Scw, float *T, float *Ow) {
   camera_centre(T, Ow);
 }
 
-// cv::norm of a 3-vector: the squares are accumulated in double, the root is rounded to float
-static float norm3(const float *p) {
-  double n2 = 0;
-  for (int k = 0; k < 3; k++) n2 += (double)p[k] * (double)p[k];
-  return (float)sqrt(n2);
-}
-
-// The scale-invariance gate of the projection searches: true when `dist` lies outside [0.8 * min_dist, 1.2 * max_dist]
-// (MapPoint::GetMinDistanceInvariance / GetMaxDistanceInvariance, MapPoint.cc:552-563)
-static bool outside_scale_range(float dist, float min_dist, float max_dist) { return dist < 0.8f * min_dist || dist > 1.2f * max_dist; }
-
 // The viewing-angle gate: true when PO . Pn < 0.5 * dist, the dot product in double (Mat::dot)
-static bool views_too_obliquely(const float *PO, const float *Pn, float dist) {
-  double pd = 0;
-  for (int k = 0; k < 3; k++) pd += (double)PO[k] * (double)Pn[k];
-  return pd < 0.5 * (double)dist;
-}
+static bool views_too_obliquely(const float *PO, const float *Pn, float dist) { return dot3_double(PO, Pn) < 0.5 * (double)dist; }
 
-// MapPoint::PredictScale, MapPoint.cc:570-602: ceil(log(max_dist / dist) / log(scale factor)) clamped to the pyramid.  (The device form in
-// k_local_map_project rounds through its cvttss2si emulation and is a separate statement on purpose.)
-static int predict_level(float max_dist, float dist, float log_sf, int nlevels) {
-  const float ratio = max_dist / dist;
-  int lvl = (int)ceilf(logf(ratio) / log_sf);
-  return lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
-}
+// MapPoint::PredictScale, MapPoint.cc:570-602, with libm's logf
+static int predict_level(float max_dist, float dist, float log_sf, int nlevels) { return level_from_log(logf(max_dist / dist), log_sf, nlevels); }
 
 // Rotation pruning of the projection searches: ids are keypoints of the searched frame, a pruned one gives its map point back.
 static int prune_by_rotation(int nq, const int32_t *moq, const float *query_angle, const orbx_keypoint_t *keys, int32_t *slot,
@@ -1718,8 +1639,7 @@ struct QueryArrays {
 };
 
 // The query arrays a projection kernel writes, carved out of `buf` (29 B per query, in blocks of 64 queries) - grows on demand, not
-// on the steady-state path.  moq: where the search may put match_of_query when the caller has no array for it.
-struct QueryScratch { float *u, *v, *r, *ur; int32_t *minl, *maxl, *moq; uint8_t *flags; };
+// on the steady-state path.
 static int carve_query_scratch(orbm_t *m, DevBuf &buf, hipStream_t s, int npairs, int stride, int maxq, QueryScratch &Q) {
   const size_t nqa = (size_t)(npairs - 1) * stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
   const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
@@ -1740,6 +1660,15 @@ static orbm_queries_t scratch_view(const QueryScratch &Q, int nq, const uint8_t 
   return q;
 }
 
+// The current frame's part of a projection kernel's parameters (V zeroed by the caller)
+static void fill_view(ViewParams &V, const orbm_frame_t *cur, const float *sf, int nlevels, int cam_type, const float *cam_params) {
+  V.min_x = cur->min_x; V.max_x = cur->max_x; V.min_y = cur->min_y; V.max_y = cur->max_y;
+  for (int l = 0; l < nlevels; l++) V.sf[l] = sf[l];
+  V.nlevels = nlevels;
+  V.cam_type = cam_type;
+  for (int k = 0; k < (cam_type == 0 ? 4 : 8); k++) V.cam[k] = cam_params[k];
+}
+
 static bool valid_local_map(const orbm_local_map_t *map) {
   return map->eligible && map->Xw && map->normal && map->max_dist && map->min_dist && map->mpdesc && map->Tcw;
 }
@@ -1758,23 +1687,17 @@ static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int fram
   const int maxq = d_last_n ? last_stride : last0->n;
   if (maxq <= 0 || last_stride < maxq) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
-  QueryScratch Q;
+  LastFrameParams P;
+  memset(&P, 0, sizeof(P));
+  QueryScratch &Q = P.Q;
   const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, last_stride, maxq, Q);
   if (rq < 0) return rq;
   int32_t *moq = d_moq ? d_moq : Q.moq;
-  LastFrameParams P;
-  memset(&P, 0, sizeof(P));
   P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
   P.Tcw = last0->Tcw; P.Tlw = last0->Tlw;
   P.last_stride = last_stride; P.last_n = d_last_n; P.last_n_stride = last_n_stride; P.last_n_const = last0->n;
-  P.min_x = cur0->min_x; P.max_x = cur0->max_x; P.min_y = cur0->min_y; P.max_y = cur0->max_y;
-  for (int l = 0; l < nlevels; l++) P.sf[l] = sf[l];
-  P.nlevels = nlevels;
-  P.cam_type = cam_type;
-  for (int k = 0; k < (cam_type == 0 ? 4 : 8); k++) P.cam[k] = cam_params[k];
+  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
   P.mb = mb; P.mbf = mbf; P.th = th; P.bMono = bMono ? 1 : 0;
-  P.qu = Q.u; P.qv = Q.v; P.qr = Q.r; P.qur = Q.ur;
-  P.qminl = Q.minl; P.qmaxl = Q.maxl; P.qflags = Q.flags;
   hipLaunchKernelGGL(k_lastframe_project, dim3((last_stride + 255) / 256, npairs), dim3(256), 0, s, P);
   const orbm_queries_t q = scratch_view(Q, last0->n, last0->mpdesc, cur0->u_right != nullptr);
   SearchOpts o;
@@ -1874,24 +1797,19 @@ static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_str
   if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
   if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
-  QueryScratch Q;
-  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, maxq, Q);
-  if (rq < 0) return rq;
   LocalMapParams P;
   memset(&P, 0, sizeof(P));
+  QueryScratch &Q = P.Q;
+  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, maxq, Q);
+  if (rq < 0) return rq;
   P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
   P.obs = map0->obs; P.Tcw = map0->Tcw;
   P.map_stride = map_stride; P.map_n = d_map_n; P.map_n_stride = map_n_stride; P.map_n_const = map0->n;
-  P.min_x = cur0->min_x; P.max_x = cur0->max_x; P.min_y = cur0->min_y; P.max_y = cur0->max_y;
-  for (int l = 0; l < nlevels; l++) P.sf[l] = sf[l];
-  P.nlevels = nlevels; P.log_sf = log_sf;
-  P.cam_type = cam_type;
-  for (int k = 0; k < (cam_type == 0 ? 4 : 8); k++) P.cam[k] = cam_params[k];
+  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
+  P.log_sf = log_sf;
   P.mbf = mbf; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
   P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
   P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
-  P.qu = Q.u; P.qv = Q.v; P.qr = Q.r; P.qur = Q.ur;
-  P.qminl = Q.minl; P.qmaxl = Q.maxl; P.qflags = Q.flags;
   hipLaunchKernelGGL(k_local_map_project, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P);
   if (search) {
     const orbm_queries_t q = scratch_view(Q, map0->n, map0->mpdesc, cur0->u_right != nullptr);
@@ -2034,22 +1952,19 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
     const float invzc = (float)(1.0 / (double)x3Dc[2]);        // :2076
     if (invzc < 0) continue;
     float ux, vy;
-    orbm_project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], &ux, &vy);
-    if (ux < cur->min_x || ux > cur->max_x) continue;          // :2094-2097
-    if (vy < cur->min_y || vy > cur->max_y) continue;
+    project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], ux, vy);
+    if (!inside_bounds(ux, vy, cur->min_x, cur->max_x, cur->min_y, cur->max_y)) continue;   // :2094-2097
     const int nLastOctave = last_keys[i].octave;
     if (nLastOctave < 0 || nLastOctave >= nlevels) return ORBX_E_ARG;
     mat3_mul_add(Trl, x3Dc, trl, x3Dr);                        // :2190
     float uxr, vyr;
-    orbm_project(cam_type, cam_params, x3Dr[0], x3Dr[1], x3Dr[2], &uxr, &vyr);
-    const uint8_t fl = (uint8_t)(1u | ((obs ? (obs[i] & 1u) : 1u) << 1));
+    project(cam_type, cam_params, x3Dr[0], x3Dr[1], x3Dr[2], uxr, vyr);
+    const uint8_t fl = query_flags(obs, i);
     for (int h = 0; h < 2; h++) {
       const int j = 2 * i + h;
       A.u[j] = h ? uxr : ux; A.v[j] = h ? vyr : vy;
       A.rad[j] = th * sf[nLastOctave];                             // :2105, :2197
-      if (bForward) { A.minl[j] = nLastOctave; A.maxl[j] = -1; }   // :2113-2118, :2201-2206
-      else if (bBackward) { A.minl[j] = 0; A.maxl[j] = nLastOctave; }
-      else { A.minl[j] = nLastOctave - 1; A.maxl[j] = nLastOctave + 1; }
+      lastframe_level_window(bForward, bBackward, nLastOctave, A.minl[j], A.maxl[j]);   // :2113-2118, :2201-2206
       A.flags[j] = fl;
     }
   }
@@ -2083,13 +1998,12 @@ int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const
     float x3Dc[3];
     mat3_mul_add(Tcw, x3Dw, tcw, x3Dc);                                        // :2317
     float ux, vy;
-    orbm_project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], &ux, &vy);     // :2319
-    if (ux < cur->min_x || ux > cur->max_x) continue;                           // :2321-2324
-    if (vy < cur->min_y || vy > cur->max_y) continue;
+    project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], ux, vy);           // :2319
+    if (!inside_bounds(ux, vy, cur->min_x, cur->max_x, cur->min_y, cur->max_y)) continue;   // :2321-2324
     float PO[3];
     for (int k = 0; k < 3; k++) PO[k] = x3Dw[k] - Ow[k];
     const float dist3D = norm3(PO);                                              // cv::norm(x3Dw-Ow), :2327-2328
-    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;         // :2334-2335
+    if (outside_scale_range(dist3D, min_dist, max_dist, i)) continue;            // :2334-2335
     const int lvl = predict_level(max_dist[i], dist3D, logScaleFactor, nlevels); // MapPoint::PredictScale, MapPoint.cc:587-602
     A.u[i] = ux; A.v[i] = vy;
     A.rad[i] = th * sf[lvl];                                                     // :2340
@@ -2129,12 +2043,12 @@ int orbm_search_by_projection_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const 
     mat3_mul_add(T, p3Dw, tcw, p3Dc);                                         // :523
     if ((double)p3Dc[2] < 0.0) continue;                                      // :526
     float ux, vy;
-    orbm_project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], &ux, &vy);         // :534, pKF->mpCamera->project
-    if (!(ux >= kf->min_x && ux < kf->max_x && vy >= kf->min_y && vy < kf->max_y)) continue;  // KeyFrame::IsInImage, KeyFrame.cc:844-847
+    project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], ux, vy);                // :534, pKF->mpCamera->project
+    if (!is_in_image(ux, vy, kf->min_x, kf->max_x, kf->min_y, kf->max_y)) continue;
     float PO[3];
     for (int k = 0; k < 3; k++) PO[k] = p3Dw[k] - Ow[k];
     const float dist = norm3(PO);                                             // cv::norm, :544
-    if (outside_scale_range(dist, min_dist[i], max_dist[i])) continue;        // :546
+    if (outside_scale_range(dist, min_dist, max_dist, i)) continue;           // :546
     if (views_too_obliquely(PO, normal + 3 * i, dist)) continue;              // :552
     const int lvl = predict_level(max_dist[i], dist, logScaleFactor, nlevels);   // MapPoint::PredictScale(dist, pKF), MapPoint.cc:570-585
     A.u[i] = ux; A.v[i] = vy;
@@ -2169,12 +2083,12 @@ static int fuse_core(orbm_t *m, const orbm_frame_t *kf, const float *sf, const f
     if (p3Dc[2] < 0.0f) continue;                                             // :1475 / :1697
     const float invz = 1 / p3Dc[2];                                           // :1481
     float ux, vy;
-    orbm_project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], &ux, &vy);         // :1487 / :1704
-    if (!(ux >= kf->min_x && ux < kf->max_x && vy >= kf->min_y && vy < kf->max_y)) continue;  // KeyFrame::IsInImage, KeyFrame.cc:844-847
+    project(cam_type, cam, p3Dc[0], p3Dc[1], p3Dc[2], ux, vy);                // :1487 / :1704
+    if (!is_in_image(ux, vy, kf->min_x, kf->max_x, kf->min_y, kf->max_y)) continue;
     float PO[3];
     for (int k = 0; k < 3; k++) PO[k] = p3Dw[k] - Ow[k];
     const float dist3D = norm3(PO);                                           // cv::norm, :1502 / :1715
-    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;      // MapPoint.cc:552-563, :1505 / :1718
+    if (outside_scale_range(dist3D, min_dist, max_dist, i)) continue;         // MapPoint.cc:552-563, :1505 / :1718
     if (views_too_obliquely(PO, normal + 3 * i, dist3D)) continue;            // :1514 / :1724
     const int lvl = predict_level(max_dist[i], dist3D, logScaleFactor, nlevels);   // MapPoint::PredictScale, MapPoint.cc:570-585
     A.u[i] = ux; A.v[i] = vy; A.ur[i] = ux - bf * invz;                       // :1495
@@ -2250,9 +2164,9 @@ void sim3_project(const orbm_frame_t *kfB, const float *sfB, int nlevelsB, float
     const float invz = (float)(1.0 / (double)pB[2]);                           // :1842
     const float x = pB[0] * invz, y = pB[1] * invz;
     const float u = cam[0] * x + cam[2], v = cam[1] * y + cam[3];              // :1846-1847, pKF1's intrinsics in both directions
-    if (!(u >= kfB->min_x && u < kfB->max_x && v >= kfB->min_y && v < kfB->max_y)) continue;  // KeyFrame::IsInImage
+    if (!is_in_image(u, v, kfB->min_x, kfB->max_x, kfB->min_y, kfB->max_y)) continue;
     const float dist3D = norm3(pB);                                            // cv::norm, :1855
-    if (outside_scale_range(dist3D, min_dist[i], max_dist[i])) continue;       // :1858
+    if (outside_scale_range(dist3D, min_dist, max_dist, i)) continue;          // :1858
     const int lvl = predict_level(max_dist[i], dist3D, logSfB, nlevelsB);      // MapPoint::PredictScale, MapPoint.cc:570-585
     S.u[i] = u; S.v[i] = v; S.rad[i] = th * sfB[lvl];                          // :1865
     S.minl[i] = lvl - 1; S.maxl[i] = lvl;                                      // :1884
@@ -2481,7 +2395,7 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
     const float t0 = R2w[3 * i] * Cw1[0] + R2w[3 * i + 1] * Cw1[1] + R2w[3 * i + 2] * Cw1[2];
     C2[i] = (float)((double)t0 + (double)t2w[i]);
   }
-  orbm_project(0, cam2, C2[0], C2[1], C2[2], &T.epx, &T.epy);
+  project(0, cam2, C2[0], C2[1], C2[2], T.epx, T.epy);
   // R12 = R1w*R2w.t(); t12 = -R1w*R2w.t()*t2w+t1w, :1008-1010
   float R12[9], nR[9], t12[3];
   for (int i = 0; i < 3; i++)

@@ -584,7 +584,7 @@ void orbm_image_bounds(int cols, int rows, const float *K, const float *D, int n
 /* Frame::UndistortKeyPoints (Frame.cc:837-870) for `nframes` frames whose keypoints are resident in HBM (the output of
  * orbx_extract_batch_device): frame f's keypoints at d_keys + f * key_stride, its count at d_counts[f * count_stride]
  * (d_counts == NULL: n_const keypoints per frame).  Same arithmetic, same bits as orbm_undistort_keypoints (one source,
- * csrc/orb_project_kernels.h).  d_keys_un may alias d_keys.  Asynchronous on `stream`; returns 0 or an ORBX_E_* code. */
+ * undistort_point in csrc/orb_ref_geometry.h).  d_keys_un may alias d_keys.  Asynchronous on `stream`; returns 0 or an ORBX_E_* code. */
 int orbm_undistort_keypoints_batch_device(orbm_t *m, const orbx_keypoint_t *d_keys, int key_stride, const int32_t *d_counts,
                                           int count_stride, int n_const, int nframes, const float *K, const float *D, int nD,
                                           orbx_keypoint_t *d_keys_un, void *stream);

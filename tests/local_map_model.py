@@ -60,7 +60,7 @@ def is_in_frustum(Xw, normal, max_dist, min_dist, eligible, Tcw, cam_type, cam, 
     Ow = camera_centre(T)
     R, t = T[:3, :3], T[:3, 3]
     with np.errstate(all="ignore"):
-        # Pc = mRcw*P + mtcw: products summed in float, then + t in double (dev_mat3_mul_add)
+        # Pc = mRcw*P + mtcw: products summed in float, then + t in double (mat3_mul_add)
         Pc = np.stack([((R[i, 0] * Xw[:, 0] + R[i, 1] * Xw[:, 1]) + R[i, 2] * Xw[:, 2]).astype(np.float64) + np.float64(t[i])
                        for i in range(3)], axis=1).astype(f32)
         for j in range(n):

@@ -271,6 +271,59 @@ def test_search_by_projection_keyframe_m4(pkg, oracle, synth, matcher, cam):
     assert total > (100 if cam == 0 else 300)
 
 
+def _pyramid_ends_scene(pkg):
+    """32 map points in front of a pinhole camera, each projecting between two keypoints that carry its descriptor: one of octave
+    0 / 1, one of octave 6 / 7.  max_dist / dist3D is 0.84 ... 0.99 for the even points (negative logarithm, above the 1 / 1.2 of
+    the range gate: level 0) and 4.5 ... 9 for the odd ones (beyond 1.2^8 = 4.2998: levels 9 ... 13, clamped to 7), so which of
+    the two keypoints a point takes is decided by the predicted level alone."""
+    rng = np.random.default_rng(4100)
+    fx, fy, cx, cy = 458.654, 457.296, 367.215, 248.375            # Examples/Monocular/EuRoC.yaml:9-12
+    params = np.array([fx, fy, cx, cy], np.float32)
+    nP = 32
+    px = (60 + 90 * (np.arange(nP) % 8)).astype(np.float32)         # windows of th * 1.2^7 = 35.8 px do not overlap
+    py = (60 + 120 * (np.arange(nP) // 8)).astype(np.float32)
+    z = rng.uniform(4.0, 6.0, nP).astype(np.float32)
+    Xw = np.stack([(px - np.float32(cx)) / np.float32(fx) * z, (py - np.float32(cy)) / np.float32(fy) * z, z], axis=1).astype(np.float32)
+    Tcw = np.eye(4, dtype=np.float32)                               # Ow = 0: dist3D = |Xw|
+    dist = np.sqrt((Xw.astype(np.float64) ** 2).sum(axis=1))
+    ratio = np.where(np.arange(nP) % 2 == 0, np.linspace(0.84, 0.99, nP), np.linspace(4.5, 9.0, nP))
+    max_dist = (dist * ratio).astype(np.float32)
+    min_dist = (max_dist / np.float32(100)).astype(np.float32)      # 0.8 * min_dist < dist3D for every point
+    mpdesc = rng.integers(0, 256, (nP, 32), dtype=np.uint8)
+    kf_angle = rng.uniform(0, 360, nP).astype(np.float32)
+    kps = np.zeros(2 * nP, dtype=pkg.KP_DTYPE)
+    desc = np.zeros((2 * nP, 32), np.uint8)
+    for i in range(nP):
+        for h in (0, 1):                                            # keypoint 2i: low octave, 2i + 1: high octave
+            j = 2 * i + h
+            kps["x"][j] = px[i] + (2.0 if h else -2.0)
+            kps["y"][j] = py[i] + (1.0 if h else -1.0)
+            kps["octave"][j] = (6 if h else 0) + (i // 2) % 2
+            kps["angle"][j] = kf_angle[i]                           # rot = 0: nothing for the rotation check to prune
+            desc[j] = mpdesc[i]
+            desc[j, h] ^= 1 << (i % 8)                              # Hamming distance 1
+    expect = np.full(2 * nP, -1, np.int32)
+    taken = 2 * np.arange(nP) + np.arange(nP) % 2                   # even points: the low keypoint, odd points: the high one
+    expect[taken] = np.arange(nP)
+    return kps, desc, params, Xw, Tcw, mpdesc, kf_angle, max_dist, min_dist, expect
+
+
+def test_search_by_projection_keyframe_pyramid_ends(pkg, oracle, matcher):
+    """MapPoint::PredictScale at both ends of the pyramid in a host-staged search.  Ratios just below 1: level 0 from a negative
+    logarithm (ceil gives -0; the range gate keeps finite ratios above 1 / 1.2, so the `lvl < 0` clamp itself is not reached).
+    Ratios beyond 1.2^8: ceil gives 9 ... 13 and the upper clamp must bring the window to level nlevels - 1.  Finite ratios only."""
+    kps, desc, params, Xw, Tcw, mpdesc, kf_angle, max_dist, min_dist, expect = _pyramid_ends_scene(pkg)
+    sf = np.array([1.2 ** i for i in range(8)], dtype=np.float32)
+    F, OF = both_frames(pkg, oracle, kps, desc, sf)
+    valid = np.ones(len(Xw), np.uint8)
+    log_sf = float(np.log(np.float32(1.2)))
+    n_gpu = matcher.SearchByProjectionKeyFrame(F, sf, log_sf, valid, Xw, mpdesc, kf_angle, max_dist, min_dist, Tcw, 0, params, 10.0, 100)
+    n_ref = oracle.search_by_projection_kf(OF, valid, Xw, mpdesc, kf_angle, max_dist, min_dist, Tcw, 0, params, log_sf, 10.0, 100, True)
+    assert n_ref == len(Xw) and np.array_equal(OF.slot, expect)     # the construction: every point takes the keypoint of its level
+    assert n_gpu == n_ref
+    assert np.array_equal(F.slot, OF.slot) and np.array_equal(F.slot_obs, OF.slot_obs)
+
+
 @pytest.mark.parametrize("cam", [0, 1])
 @pytest.mark.parametrize("ratio", [1.0, 0.75])
 def test_search_by_projection_sim3_m5(pkg, oracle, synth, matcher, ratio, cam):
