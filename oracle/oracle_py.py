@@ -644,3 +644,129 @@ def bench_stream(ex, frames, offs, count, threads=1, warmup=50, lap=(0, 1000), c
     c = int(count)
     return dict(kps=kps, desc=desc, counts=counts, moq=moq, nmatch=nmatch, ms_extract=ms_e[:c], ms_match=ms_m[:c], wall_extract=float(wall[0]),
                 wall_match=float(wall[1]), count=c, threads=int(threads), cap=int(cap))
+
+
+# --- the reference's own ORBextractor.cc, compiled (oracle/Makefile `ref`, oracle/ref_driver.cc) -----------------------------------
+_REF_DIR = os.path.join(_HERE, "_ref")
+_REF_LIB = os.path.join(_REF_DIR, "libref_extractor.so")
+_REF_SOURCES = ("ref_driver.cc", "ref_extractor.map", os.path.join("ref_shim", "opencv", "cv.h"), "orb_oracle.h", "Makefile")
+_ref_lib = None
+
+
+def reference_tree():
+    """The reference checkout `make ref` reads (ORB_REFERENCE, default /root/reference), or None where there is none."""
+    d = os.environ.get("ORB_REFERENCE", "/root/reference")
+    return d if os.path.isfile(os.path.join(d, "src", "ORBextractor.cc")) else None
+
+
+def build_ref(force=False):
+    """Build oracle/_ref/libref_extractor.so where the reference tree exists; elsewhere an already built library is used as it is.
+    Returns the library's path, or None when there is neither."""
+    tree = reference_tree()
+    if tree is not None:
+        build()
+        stale = force or not os.path.exists(_REF_LIB) or any(
+            os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_REF_LIB) for f in _REF_SOURCES + ("liborb_oracle.so",))
+        if stale and os.path.exists(_REF_LIB):
+            os.remove(_REF_LIB)   # not `make -B`: that would also rebuild liborb_oracle.so, which may be loaded
+        subprocess.check_call(["make", "-C", _HERE, "-s", "ref", "ORB_REFERENCE=" + tree])
+    return _REF_LIB if os.path.exists(_REF_LIB) else None
+
+
+def ref_lib(build_if_possible=True):
+    """The loaded library.  build_if_possible=False never looks at the reference tree: what is under oracle/_ref/ is loaded as it is."""
+    global _ref_lib
+    if _ref_lib is None:
+        path = build_ref() if build_if_possible else (_REF_LIB if os.path.exists(_REF_LIB) else None)
+        if path is None:
+            raise RuntimeError("oracle/_ref/libref_extractor.so is missing and there is no reference tree to build it from: "
+                               "run __graft_entry__.build() where the reference exists")
+        lib()  # liborb_oracle.so first: the reference library resolves the orc_* primitives from it
+        L = C.CDLL(path)
+        cfg = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+        img = [C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+        L.ref_extract.argtypes = cfg + img + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ref_pyramid_sizes.argtypes = cfg + img + [C.c_void_p, C.c_void_p]
+        L.ref_pyramid.argtypes = cfg + img + [C.c_int, C.c_void_p]
+        L.ref_level_keypoints.argtypes = cfg + img + [C.c_void_p, C.c_int, C.c_void_p]
+        L.ref_distribute_octtree.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.ref_features_per_level.argtypes = cfg + [C.c_void_p]
+        _ref_lib = L
+    return _ref_lib
+
+
+class RefExtractor:
+    """The reference's ORBextractor, compiled from its own text against stand-in containers, with the oracle's primitives and a
+    monotone allocator (pointer ties go by creation order).  Same results layout as OracleExtractor."""
+
+    def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7):
+        self.L = ref_lib()
+        self.cfg = (int(nfeatures), C.c_float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+        self.nlevels, self.nfeatures = int(nlevels), int(nfeatures)
+
+    @staticmethod
+    def _img(img):
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        rows, cols = img.shape
+        return img, (_p(img), rows, cols, C.c_size_t(img.strides[0]))
+
+    @staticmethod
+    def _ok(rc, what):
+        if rc == -3:
+            raise RuntimeError("%s: the reference threw a C++ exception" % what)
+        return rc
+
+    @property
+    def features_per_level(self):
+        a = np.zeros(self.nlevels, np.int32)
+        self._ok(self.L.ref_features_per_level(*self.cfg, _p(a)), "ref_features_per_level")
+        return a.tolist()
+
+    def level_sizes(self, img):
+        """(cols, rows) of every level of mvImagePyramid."""
+        img, args = self._img(img)
+        lc, lr = np.zeros(self.nlevels, np.int32), np.zeros(self.nlevels, np.int32)
+        self._ok(self.L.ref_pyramid_sizes(*self.cfg, *args, _p(lc), _p(lr)), "ref_pyramid_sizes")
+        return list(zip(lc.tolist(), lr.tolist()))
+
+    def pyramid(self, img, border=0):
+        sizes = self.level_sizes(img)
+        img, args = self._img(img)
+        levels = [np.zeros((r + 2 * border, c + 2 * border), np.uint8) for c, r in sizes]
+        arr = (C.c_void_p * self.nlevels)(*[_p(a) for a in levels])
+        rc = self._ok(self.L.ref_pyramid(*self.cfg, *args, int(border), arr), "ref_pyramid")
+        assert rc == self.nlevels
+        return levels
+
+    def level_keypoints(self, img):
+        """allKeypoints of ComputeKeyPointsOctTree: one KP_DTYPE array per level, level coordinates, angle set."""
+        img, args = self._img(img)
+        cap = self.nfeatures + 64 * self.nlevels + 64
+        while True:
+            kps, counts = np.zeros(cap, KP_DTYPE), np.zeros(self.nlevels, np.int32)
+            rc = self._ok(self.L.ref_level_keypoints(*self.cfg, *args, _p(kps), cap, _p(counts)), "ref_level_keypoints")
+            if rc >= 0:
+                break
+            cap = -2 - rc + 8
+        edges = np.concatenate([[0], np.cumsum(counts)])
+        return [kps[edges[l]:edges[l + 1]].copy() for l in range(self.nlevels)]
+
+    def extract(self, img, lap=(0, 1000), cap=None):
+        img, args = self._img(img)
+        if cap is None:
+            cap = self.nfeatures + 3 * self.nlevels + 64
+        kps, desc, n = np.zeros(cap, KP_DTYPE), np.zeros((cap, 32), np.uint8), C.c_int(0)
+        mono = self._ok(self.L.ref_extract(*self.cfg, *args, int(lap[0]), int(lap[1]), _p(kps), _p(desc), cap, C.byref(n)), "ref_extract")
+        if mono == -2:
+            return self.extract(img, lap, cap=n.value + 8)
+        return mono, kps[:n.value].copy(), desc[:n.value].copy()
+
+
+def ref_distribute_octtree(xyr, minX, maxX, minY, maxY, N):
+    xyr = np.ascontiguousarray(xyr, dtype=np.float32).reshape(-1, 3)
+    n = xyr.shape[0]
+    out = np.zeros((n + 8, 3), dtype=np.float32)
+    m = ref_lib().ref_distribute_octtree(_p(xyr), n, minX, maxX, minY, maxY, N, _p(out), n + 8)
+    if m == -3:
+        raise RuntimeError("ref_distribute_octtree: the reference threw a C++ exception")
+    return out[:m].copy()

@@ -10,9 +10,14 @@
  * fastAtan2, cvRound), restated from their published algorithms because OpenCV is an
  * external, un-vendored dependency of the reference (CMakeLists.txt:43-56).
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for this
- * path, and neither it nor OpenCV can be built in this image, so this restatement is
- * the oracle of record (see DESIGN.md "Oracle").
+ * PARITY: the reference ships no tests, golden vectors or fixtures for this path, and
+ * neither it nor OpenCV can be built in this image, so this restatement is the oracle of
+ * record (see DESIGN.md "Oracle").  PINNED: the extractor part (control flow, geometry,
+ * octree, orientation, descriptor, ordering) equals the reference's own ORBextractor.cc
+ * compiled against stand-in containers (`make ref`, ref_driver.cc), under the
+ * creation-order definition of the pointer tie.  STILL UNPINNED: the OpenCV primitives
+ * below (the compiled text calls these very functions), the libm overloads, and all of
+ * the ORBmatcher, Frame and camera-model restatements.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this.
  * The shipped library (liborbhip.so) never links, loads or calls anything in oracle/.

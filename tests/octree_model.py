@@ -7,9 +7,12 @@ ORBextractor.cc:537-761 without a GPU.
 import numpy as np
 
 
-def distribute(xs, ys, resp, minX, maxX, minY, maxY, N):
+def distribute(xs, ys, resp, minX, maxX, minY, maxY, N, tie_newest_first=True):
     """xs, ys: integer coordinates relative to (minX, minY); resp: integer responses.  Returns list of key indices
-    in the reference's output (list) order."""
+    in the reference's output (list) order.
+    tie_newest_first: among nodes of equal size the reference's sort of pair<int, ExtractorNode*> (ORBextractor.cc:682) splits the
+    node with the greatest address first, which under the creation-order definition of the pointer tie is the newest one = the one
+    nearest the list's front.  False reverses that rule: what tests use to show that a case depends on it."""
     n = len(xs)
     if n == 0:
         return []
@@ -49,7 +52,7 @@ def distribute(xs, ys, resp, minX, maxX, minY, maxY, N):
         if not careful:
             order = X  # processing order = list order
         else:
-            order = np.array(sorted(X.tolist(), key=lambda i: (-cnt[i], i)), dtype=np.int64)
+            order = np.array(sorted(X.tolist(), key=lambda i: (-cnt[i], i if tie_newest_first else -i)), dtype=np.int64)
         nX = len(order)
         incl = np.cumsum(c[order]) if nX else np.zeros(0, dtype=np.int64)
         mstar = nX - 1
