@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "orb_common.h"
+#include "orb_fast_score.h"
 #include "orb_sincos.h"
 
 #define WAVE 64
@@ -428,34 +429,7 @@ __global__ __launch_bounds__(CHAIN_NT) void k_pyramid_chain(FrameParams P) {
 __device__ __forceinline__ int lane_rank(unsigned long long b) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
 }
-typedef short pk16 __attribute__((ext_vector_type(2)));  // two signed 16-bit lanes in one VGPR (v_pk_*_i16)
-__device__ __forceinline__ int fast_score_S(const uint8_t *c /* tile centre, pitch FAST_TILE_PITCH */) {
-  constexpr int Pt = FAST_TILE_PITCH;
-  const int v = c[0];
-  // d[k] = (v - c_k, c_k - v) as two signed 16-bit halves: ONE packed min/max network yields the bright-centre margin
-  // (low half) and the dark-centre margin (high half).
-  const pk16 V2 = {(short)v, (short)-v};
-  const pk16 K = {(short)-1, (short)1};
-  pk16 d[16];
-#define ORB_RING(k, off) { const short cc = (short)c[off]; const pk16 C = {cc, cc}; d[k] = C * K + V2; }
-  ORB_RING(0, 3 * Pt + 0)   ORB_RING(1, 3 * Pt + 1)   ORB_RING(2, 2 * Pt + 2)    ORB_RING(3, 1 * Pt + 3)
-  ORB_RING(4, 3)            ORB_RING(5, -1 * Pt + 3)  ORB_RING(6, -2 * Pt + 2)   ORB_RING(7, -3 * Pt + 1)
-  ORB_RING(8, -3 * Pt)      ORB_RING(9, -3 * Pt - 1)  ORB_RING(10, -2 * Pt - 2)  ORB_RING(11, -1 * Pt - 3)
-  ORB_RING(12, -3)          ORB_RING(13, 1 * Pt - 3)  ORB_RING(14, 2 * Pt - 2)   ORB_RING(15, 3 * Pt - 1)
-#undef ORB_RING
-  // sliding window minimum of length 9 on the circular sequence by doubling: 2, 4, then three windows of 4 (k, k+4, k+5)
-  pk16 m2[16], m4[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) m2[k] = __builtin_elementwise_min(d[k], d[(k + 1) & 15]);
-#pragma unroll
-  for (int k = 0; k < 16; k++) m4[k] = __builtin_elementwise_min(m2[k], m2[(k + 2) & 15]);
-  pk16 A = {(short)-255, (short)-255};
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    A = __builtin_elementwise_max(A, __builtin_elementwise_min(__builtin_elementwise_min(m4[k], m4[(k + 4) & 15]), m4[(k + 5) & 15]));   // k .. k+8: the third window overlaps the second, so d and m2 are dead by now (registers)
-  const int S = max((int)A.x, (int)A.y);  // all of some arc darker by A.x, or brighter by A.y
-  return min(max(S, 0), 255);
-}
+// fast_score_S: orb_fast_score.h (one host/device definition)
 
 // Necessary condition for "corner at threshold t" on the 4 compass pixels (k = 0, 4, 8, 12): every arc of 9 contiguous
 // circle pixels contains two ADJACENT compass pixels, so two adjacent ones must both be darker than v-t or both
