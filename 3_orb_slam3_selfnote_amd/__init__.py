@@ -25,6 +25,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 assert KP_DTYPE.itemsize == 28
 
 E_EMPTY, E_ARG, E_HIP, E_CAP = -1, -2, -3, -4
+CLOSE_MAX_KEYPOINTS = 4096  # ORBX_CLOSE_MAX_KEYPOINTS
 
 # every symbol include/orbhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -32,7 +33,7 @@ ABI_SYMBOLS = [
     "orbx_get_scale_tables", "orbx_get_features_per_level", "orbx_configure", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_get_host_us", "orbx_level_info", "orbx_download_level", "orbx_download_pyramid", "orbx_download_blurred_level",
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
-    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
+    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
     "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
@@ -121,6 +122,8 @@ def load(build_if_needed=True):
     L.orbx_get_stage_ms.argtypes = [vp, vp, i32]
     L.orbx_compute_stereo_matches.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, f32, f32, vp, vp]
     L.orbx_compute_stereo_matches_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp]
+    L.orbx_stereo_from_rgbd_batch_device.argtypes = [i32, vp, vp, vp, i32, i32, vp, i32, i32, i32, sz, sz, f32, f32, vp, vp, vp, vp]
+    L.orbx_close_points_batch_device.argtypes = [i32, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp]
     L.orbx_cvt_color_gray.argtypes = [vp, vp, i32, i32, sz, i32, i32, vp, sz]
     L.orbx_cvt_color_gray_device.argtypes = [vp, i32, i32, sz, i32, i32, vp, sz, vp]
     L.orbx_clahe.argtypes = [vp, vp, i32, i32, sz, C.c_double, i32, i32, vp, sz]
@@ -962,3 +965,41 @@ def project(cam_type, params, X, Y, Z):
     u, v = C.c_float(), C.c_float()
     load().orbm_project(int(cam_type), _p(params), C.c_float(X), C.c_float(Y), C.c_float(Z), C.byref(u), C.byref(v))
     return u.value, v.value
+
+
+def _dp(a):
+    return C.c_void_p(a) if a else None
+
+
+def _check_free(rc, what):
+    if rc == E_ARG:
+        raise ValueError("%s: bad argument" % what)
+    if rc < 0:
+        raise OrbError("%s rc=%d" % (what, rc))
+    return rc
+
+
+def stereo_from_rgbd_batch_device(nframes, d_keys, d_keys_un, d_counts, count_stride, cap, d_depth_image, depth_type, rows, cols, row_stride,
+                                  frame_stride, depth_factor, mbf, d_uRight, d_depth, d_nstereo=None, stream=None):
+    """Frame::ComputeStereoFromRGBD (Frame.cc:1082-1103) for `nframes` resident RGB-D frames (orbx_stereo_from_rgbd_batch_device):
+    all pointers are device addresses (ints), asynchronous on `stream`.  depth_type 0 = uint16, 1 = float32; strides in bytes;
+    depth_factor = mDepthMapFactor (already the reciprocal).  d_uRight / d_depth [nframes][cap] float32 receive mvuRight / mvDepth
+    for i < N, d_nstereo [nframes] int32 (optional) the number of keypoints with depth."""
+    rc = load().orbx_stereo_from_rgbd_batch_device(int(nframes), _dp(d_keys), _dp(d_keys_un), _dp(d_counts), int(count_stride), int(cap),
+                                                   _dp(d_depth_image), int(depth_type), int(rows), int(cols), C.c_size_t(row_stride),
+                                                   C.c_size_t(frame_stride), C.c_float(depth_factor), C.c_float(mbf), _dp(d_uRight), _dp(d_depth),
+                                                   _dp(d_nstereo), _dp(stream))
+    return _check_free(rc, "orbx_stereo_from_rgbd_batch_device")
+
+
+def close_points_batch_device(nframes, d_depth, d_counts, count_stride, cap, th_depth, max_point, d_order, d_nvisit, d_tracked=None, d_close=None,
+                              d_keys_un=None, fx=0.0, fy=0.0, cx=0.0, cy=0.0, d_x3Dc=None, d_pose=None, d_x3Dw=None, stream=None):
+    """The depth-ordered close-point rule of Tracking::UpdateLastFrame / CreateNewKeyFrame (Tracking.cc:2808-2860, :3345-3416) for
+    `nframes` resident frames (orbx_close_points_batch_device): d_order [nframes][cap] int32 receives the keypoint indices in
+    visiting order, d_nvisit [nframes] their number.  Optional: d_close [nframes][2] (nTrackedClose, nNonTrackedClose, from the bytes
+    d_tracked), d_x3Dc / d_x3Dw [nframes][cap][3] (Frame::UnprojectStereo; need d_keys_un, fx, fy, cx, cy and, for d_x3Dw, d_pose
+    [nframes][12] = [Rwc | Ow])."""
+    rc = load().orbx_close_points_batch_device(int(nframes), _dp(d_depth), _dp(d_counts), int(count_stride), int(cap), C.c_float(th_depth), int(max_point),
+                                               _dp(d_order), _dp(d_nvisit), _dp(d_tracked), _dp(d_close), _dp(d_keys_un), C.c_float(fx), C.c_float(fy),
+                                               C.c_float(cx), C.c_float(cy), _dp(d_x3Dc), _dp(d_pose), _dp(d_x3Dw), _dp(stream))
+    return _check_free(rc, "orbx_close_points_batch_device")

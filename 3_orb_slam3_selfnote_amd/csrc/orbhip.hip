@@ -24,6 +24,7 @@
 #include "orb_match_mfma.h"
 #include "orb_project_kernels.h"
 #include "orb_stereo_kernels.h"
+#include "orb_depth_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -2630,6 +2631,44 @@ int orbx_compute_stereo_matches_batch_device(orbx_t *hl, orbx_t *hr, int nframes
   hipLaunchKernelGGL(k_stereo_median, dim3(nframes), dim3(256), 0, s, S);
   XCHECK(hl, hipGetLastError());
   return 0;
+}
+
+int orbx_stereo_from_rgbd_batch_device(int nframes, const orbx_keypoint_t *d_keys, const orbx_keypoint_t *d_keys_un, const int32_t *d_counts,
+                                       int count_stride, int cap, const void *d_depth_image, int depth_type, int rows, int cols, size_t row_stride,
+                                       size_t frame_stride, float depth_factor, float mbf, float *d_uRight, float *d_depth, int32_t *d_nstereo,
+                                       void *stream) {
+  if (!d_keys || !d_keys_un || !d_counts || !d_depth_image || !d_uRight || !d_depth) return ORBX_E_ARG;
+  if (nframes < 0 || cap <= 0 || count_stride <= 0 || rows <= 0 || cols <= 0 || (depth_type != 0 && depth_type != 1)) return ORBX_E_ARG;
+  const size_t elem = depth_type == 0 ? sizeof(uint16_t) : sizeof(float);
+  if (row_stride < (size_t)cols * elem || row_stride % elem || frame_stride % elem) return ORBX_E_ARG;
+  if (nframes > 1 && frame_stride < row_stride * (size_t)rows) return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  RgbdParams P;
+  P.keys = reinterpret_cast<const float *>(d_keys); P.keys_un = reinterpret_cast<const float *>(d_keys_un);
+  P.counts = d_counts; P.count_stride = count_stride; P.cap = cap;
+  P.img = (const uint8_t *)d_depth_image; P.depth_type = depth_type; P.rows = rows; P.cols = cols; P.row_stride = row_stride; P.frame_stride = frame_stride;
+  P.factor = depth_factor; P.mbf = mbf;
+  P.uRight = d_uRight; P.depth = d_depth; P.nstereo = d_nstereo;
+  hipLaunchKernelGGL(k_stereo_from_rgbd, dim3(nframes), dim3(256), 0, (hipStream_t)stream, P);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
+int orbx_close_points_batch_device(int nframes, const float *d_depth, const int32_t *d_counts, int count_stride, int cap, float th_depth, int max_point,
+                                   int32_t *d_order, int32_t *d_nvisit, const uint8_t *d_tracked, int32_t *d_close, const orbx_keypoint_t *d_keys_un,
+                                   float fx, float fy, float cx, float cy, float *d_x3Dc, const float *d_pose, float *d_x3Dw, void *stream) {
+  if (!d_depth || !d_counts || !d_order || !d_nvisit) return ORBX_E_ARG;
+  if (nframes < 0 || cap <= 0 || cap > ORBX_CLOSE_MAX_KEYPOINTS || count_stride <= 0) return ORBX_E_ARG;
+  if ((d_x3Dc && !d_keys_un) || (d_x3Dw && (!d_x3Dc || !d_pose)) || (d_pose && !d_x3Dw)) return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  CloseParams P;
+  P.depth = d_depth; P.counts = d_counts; P.count_stride = count_stride; P.cap = cap;
+  P.th_depth = th_depth; P.max_point = max_point; P.tracked = d_tracked;
+  P.order = d_order; P.nvisit = d_nvisit; P.close = d_close;
+  P.keys_un = reinterpret_cast<const float *>(d_keys_un); P.cx = cx; P.cy = cy;
+  P.invfx = 1.0f / fx; P.invfy = 1.0f / fy;   // Frame.cc:275-276
+  P.x3Dc = d_x3Dc; P.pose = d_pose; P.x3Dw = d_x3Dw;
+  hipLaunchKernelGGL(k_close_points, dim3(nframes), dim3(CLOSE_THREADS), 0, (hipStream_t)stream, P);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
 }
 
 // Shared by the two SearchByBoW overloads.  kf_kf: second operand is a keyframe (candidates need a good map point, strict

@@ -196,6 +196,50 @@ int orbx_compute_stereo_matches_batch_device(orbx_t *left, orbx_t *right, int nf
                                              const uint8_t *d_descR, const int32_t *d_countsR, int cap, float mb, float mbf,
                                              float *d_uRight, float *d_depth, int32_t *d_nstereo, void *stream);
 
+/* void Frame::ComputeStereoFromRGBD(const cv::Mat &imDepth)  (Frame.cc:1082-1103) for `nframes` RGB-D frames resident in HBM,
+ * with the imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) of Tracking::GrabImageRGBD (Tracking.cc:1075-1076) evaluated only
+ * at the keypoints.  No handle: device pointers, asynchronous on `stream`, no host synchronisation, copy or allocation.
+ * d_keys / d_keys_un [nframes][cap] = mvKeys / mvKeysUn as orbx_extract_batch_device and orbm_undistort_keypoints_batch_device
+ * wrote them; N of frame f = d_counts[f * count_stride].  Depth image of frame f at d_depth_image + f * frame_stride, rows x cols,
+ * row_stride bytes per row; depth_type 0 = 16-bit unsigned (the TUM PNGs), 1 = float.  depth_factor = mDepthMapFactor as
+ * Tracking.cc:751-755 leaves it (already the reciprocal; 1 for a float image the reference does not convert, :1075: the
+ * product with 1.0f is exact).  mbf = Frame::mbf.
+ * Per keypoint i < N: d = (float)raw * depth_factor at the pixel ((int)kp.pt.y, (int)kp.pt.x) of the DISTORTED keypoint, both
+ * truncated as at<float>(v, u) converts its float arguments; d > 0: d_depth = d, d_uRight = kpU.pt.x - mbf / d; otherwise both
+ * -1 (so NaN gives -1, +inf gives depth inf and uRight = kpU.pt.x).  Entries beyond N are left alone.  d_nstereo[f] (may be
+ * NULL) = number of entries with depth > 0.  One deviation: a pixel outside rows x cols, undefined behaviour in the reference,
+ * gives -1 here and is never read.
+ * ORBX_E_ARG: a NULL required pointer, nframes < 0, cap <= 0, count_stride <= 0, rows / cols <= 0, depth_type not 0 / 1, a
+ * row_stride smaller than a row or not a multiple of the element size, a frame_stride that is not such a multiple or (for
+ * nframes > 1) smaller than an image.  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
+int orbx_stereo_from_rgbd_batch_device(int nframes, const orbx_keypoint_t *d_keys, const orbx_keypoint_t *d_keys_un, const int32_t *d_counts,
+                                       int count_stride, int cap, const void *d_depth_image, int depth_type, int rows, int cols, size_t row_stride,
+                                       size_t frame_stride, float depth_factor, float mbf, float *d_uRight, float *d_depth, int32_t *d_nstereo,
+                                       void *stream);
+
+/* The depth-ordered close-point rule of Tracking::UpdateLastFrame (Tracking.cc:2808-2860) and Tracking::CreateNewKeyFrame
+ * (:3345-3416) for `nframes` frames, on d_depth [nframes][cap] = mvDepth from the call above or from
+ * orbx_compute_stereo_matches_batch_device; same calling rules as above.  Per frame, with N = d_counts[f * count_stride]:
+ * the keypoints i < N with z > 0 in the order of sort(vDepthIdx) (z ascending, then i), visited up to and including the first
+ * position with z > th_depth (mThDepth) and position + 1 > max_point (100 in the reference) - nPoints grows on every iteration
+ * of both loops (:2849-2853, :3405-3409), so the break does not depend on the map.  With c = #{0 < z <= th_depth} and
+ * m = #{z > 0} that is nvisit = min(m, max(c, max_point) + 1); the one point beyond is the reference's behaviour.
+ * d_order[f][0 .. nvisit) = the keypoint indices in visiting order (later entries are left alone), d_nvisit[f] = nvisit.
+ * d_close[f][2] (may be NULL) = nTrackedClose, nNonTrackedClose of Tracking::NeedNewKeyFrame (:3190-3200: 0 < z < th_depth),
+ * from d_tracked [nframes][cap] = mvpMapPoints[i] && !mvbOutlier[i] (NULL: every point is untracked).
+ * d_x3Dc [nframes][cap][3] (may be NULL; needs d_keys_un = mvKeysUn): Frame::UnprojectStereo (Frame.cc:1105-1116) in camera
+ * coordinates for every i < N with z > 0, x = (u - cx) * z * invfx with invfx = 1.0f / fx (Frame.cc:275-276), y likewise; other
+ * entries are left alone.  d_pose [nframes][12] = [mRwc | mOw] row-major 3x4 and d_x3Dw [nframes][cap][3] (both or neither;
+ * need d_x3Dc): mRwc * x3Dc + mOw.
+ * One workgroup per frame, the keys (bits(z) << 32 | i: positive floats order as their bit patterns) sorted in LDS, which holds
+ * ORBX_CLOSE_MAX_KEYPOINTS of them.  ORBX_E_ARG: a NULL required pointer (d_depth, d_counts, d_order, d_nvisit), nframes < 0,
+ * cap <= 0 or above ORBX_CLOSE_MAX_KEYPOINTS, count_stride <= 0, an incomplete unprojection set.  Returns 0, ORBX_E_ARG or
+ * ORBX_E_HIP. */
+#define ORBX_CLOSE_MAX_KEYPOINTS 4096 /* per frame: 32 KB of 8-byte keys; extractors of up to ~4000 features stay below it */
+int orbx_close_points_batch_device(int nframes, const float *d_depth, const int32_t *d_counts, int count_stride, int cap, float th_depth, int max_point,
+                                   int32_t *d_order, int32_t *d_nvisit, const uint8_t *d_tracked, int32_t *d_close, const orbx_keypoint_t *d_keys_un,
+                                   float fx, float fy, float cx, float cy, float *d_x3Dc, const float *d_pose, float *d_x3Dw, void *stream);
+
 /* ---- ORBmatcher -------------------------------------------------------------------------------------------- */
 
 #define ORBM_TH_HIGH 100 /* ORBmatcher.cc:36 */
