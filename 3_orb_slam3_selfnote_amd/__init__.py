@@ -26,6 +26,7 @@ assert KP_DTYPE.itemsize == 28
 
 E_EMPTY, E_ARG, E_HIP, E_CAP = -1, -2, -3, -4
 CLOSE_MAX_KEYPOINTS = 4096  # ORBX_CLOSE_MAX_KEYPOINTS
+FISHEYE_MAX_KEYPOINTS = 12960  # ORBM_FISHEYE_MAX_KEYPOINTS
 
 # every symbol include/orbhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -36,7 +37,7 @@ ABI_SYMBOLS = [
     "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -153,6 +154,9 @@ def load(build_if_needed=True):
     L.orbm_search_by_projection_fisheye.argtypes = [vp, vp, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp]
     L.orbm_search_by_projection_last_frame_fisheye.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32,
                                                                i32, i32, vp, vp]
+    L.orbm_search_by_projection_last_frame_fisheye_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp, i32,
+                                                                            vp, f32, f32, i32, i32, vp, vp, vp, vp, vp]
+    L.orbm_rig_concat_batch_device.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.orbm_search_for_initialization.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp]
     L.orbm_fuse.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, vp, vp]
     L.orbm_fuse_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
@@ -921,6 +925,39 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_search_local_points_batch_device rc=%d" % rc)
 
+    def search_by_projection_last_frame_fisheye_batch_device(self, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride,
+                                                             last0, last_stride, d_last_n, last_n_stride, npairs, scale_factors, Trl,
+                                                             cam_type, cam_params, th, d_slot, d_slot_obs, d_match_of_query, d_nmatches,
+                                                             n_left=0, bMono=False, mb=0.0, stream=None):
+        """SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) for `npairs` fisheye-stereo current frames
+        resident in HBM (orbm_search_by_projection_last_frame_fisheye_batch_device).  cur0 / last0: FrameStruct / LastFrameStruct of
+        problem 0 holding device addresses; the other pointers are device addresses (ints; d_frame_n / d_n_left / d_last_n /
+        d_match_of_query may be None, n_left is the constant Nleft when d_n_left is None); Trl, scale_factors and cam_params are host
+        arrays; asynchronous on `stream`.  The refusals that need no device raise ValueError before the library is called."""
+        sf, cam_params = np.ascontiguousarray(scale_factors, dtype=np.float32), np.ascontiguousarray(cam_params, dtype=np.float32)
+        if Trl is None:
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: Trl is missing")
+        Trl = np.ascontiguousarray(Trl, dtype=np.float32).reshape(-1)
+        if Trl.size not in (12, 16):
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: Trl must hold 12 or 16 floats")
+        if npairs < 0 or not d_slot or not d_slot_obs or not d_nmatches:
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: npairs < 0 or a missing output")
+        if not 1 <= len(sf) <= 16 or int(cam_type) not in (0, 1) or len(cam_params) < (4 if int(cam_type) == 0 else 8):
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: nlevels outside [1, 16] or an unknown camera")
+        if not d_n_left and not 0 <= int(n_left) <= cur0.n:
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: n_left outside [0, N]")
+        if frame_stride > FISHEYE_MAX_KEYPOINTS:
+            raise ValueError("orbm_search_by_projection_last_frame_fisheye_batch_device: frame_stride above %d" % FISHEYE_MAX_KEYPOINTS)
+        v = lambda x: C.c_void_p(x) if x else None
+        rc = self.L.orbm_search_by_projection_last_frame_fisheye_batch_device(
+            self.m, C.byref(cur0), int(frame_stride), v(d_frame_n), int(frame_n_stride), v(d_n_left), int(n_left_stride), int(n_left), C.byref(last0),
+            int(last_stride), v(d_last_n), int(last_n_stride), int(npairs), _p(sf), len(sf), _p(Trl), int(cam_type), _p(cam_params), C.c_float(mb),
+            C.c_float(th), int(bool(bMono)), int(self.mbCheckOrientation), v(d_slot), v(d_slot_obs), v(d_match_of_query), v(d_nmatches), v(stream))
+        self._check(rc, "orbm_search_by_projection_last_frame_fisheye_batch_device")
+        if rc < 0:
+            raise OrbError("orbm_search_by_projection_last_frame_fisheye_batch_device rc=%d" % rc)
+        return rc
+
     def set_profiling(self, on=True):
         self.L.orbm_set_profiling(self.m, 1 if on else 0)
 
@@ -1003,3 +1040,13 @@ def close_points_batch_device(nframes, d_depth, d_counts, count_stride, cap, th_
                                                _dp(d_order), _dp(d_nvisit), _dp(d_tracked), _dp(d_close), _dp(d_keys_un), C.c_float(fx), C.c_float(fy),
                                                C.c_float(cx), C.c_float(cy), _dp(d_x3Dc), _dp(d_pose), _dp(d_x3Dw), _dp(stream))
     return _check_free(rc, "orbx_close_points_batch_device")
+
+
+def rig_concat_batch_device(nframes, d_keysL, d_descL, d_countsL, d_keysR, d_descR, d_countsR, cap, d_keys, d_desc, d_n, stream=None):
+    """The Frame of a two-camera fisheye rig from two resident extractions (Frame.cc:1162-1164, :1201; orbm_rig_concat_batch_device):
+    per frame the nL left keypoints / descriptors and the nR right ones directly behind them in d_keys [nframes][2 * cap] /
+    d_desc [nframes][2 * cap][32], d_n [nframes][2] = {nL + nR, nL}.  All pointers are device addresses (ints), asynchronous on
+    `stream`."""
+    rc = load().orbm_rig_concat_batch_device(int(nframes), _dp(d_keysL), _dp(d_descL), _dp(d_countsL), _dp(d_keysR), _dp(d_descR), _dp(d_countsR),
+                                             int(cap), _dp(d_keys), _dp(d_desc), _dp(d_n), _dp(stream))
+    return _check_free(rc, "orbm_rig_concat_batch_device")

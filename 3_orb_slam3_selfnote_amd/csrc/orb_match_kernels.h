@@ -32,6 +32,7 @@ struct MatchProblemSet {
   // couple 2 = ... when the left one's window was empty (:2126); qany[q] = window of query q non-empty (scan -> resolve);
   // serial = resolve one query at a time from a fresh list (exact when a partner write can release a claim).
   int nleft; const uint8_t *qside; const int32_t *partner; int couple; uint8_t *qany; int serial;
+  const int32_t *nleft_dev; int nleft_stride;  // Nleft per problem from device memory (nleft_dev[p * nleft_stride]); NULL: the constant nleft
   // ORBmatcher::Fuse (ORBmatcher.cc:1425-1658): per-candidate chi-square gate on the reprojection error, :1585-1608
   // (k_match_scan mode SCAN_FUSE); u_right = mvuRight of the keyframe, qur = projected right coordinate
   float inv_sigma2[16];
@@ -96,6 +97,11 @@ __device__ __forceinline__ int popc_acc(uint32_t x, int acc) {
   int d;
   asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(x), "v"(acc));
   return d;
+}
+
+// Nleft of problem p (n for a frame that is no fisheye-stereo one); a count read from device memory is taken into [0, n]
+__device__ __forceinline__ int nleft_of(const MatchProblemSet &M, int p, int n) {
+  return !M.qside ? n : M.nleft_dev ? min(max(M.nleft_dev[(size_t)p * M.nleft_stride], 0), n) : M.nleft;
 }
 
 struct CandMeta { float x, y; uint32_t bits; float ur; };  // bits: octave | gx<<8 | gy<<16 | usable<<24 | in-grid<<25
@@ -232,7 +238,7 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_scan(MatchProblemSet M, type
   for (int j = 0; j < MATCH_TOPK; j++) top[j] = KT::NONE;
   // fisheye-stereo: a query sees only the keypoints of its own image
   constexpr bool STEREO = MODE == SCAN_FISHEYE, UR = MODE == SCAN_UR;
-  const int nleft = STEREO && M.qside ? M.nleft : n;
+  const int nleft = STEREO ? nleft_of(M, p, n) : n;
   const bool sideR = STEREO && M.qside && q < nq && M.qside[qo + q] != 0;
   const bool wantAny = STEREO && M.qany != nullptr;
   bool any = false;
@@ -523,7 +529,7 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_walk(MatchProblemSet M, type
   const int q = qb * QW + tid / LPQ, sub = tid % LPQ;
   if (q >= nq) return;
   const QueryWin w = load_query(M, qo, q);
-  const int nleft = STEREO && M.qside ? M.nleft : n;
+  const int nleft = STEREO ? nleft_of(M, p, n) : n;
   const bool sideR = STEREO && M.qside && M.qside[qo + q] != 0;
   const bool wantAny = STEREO && M.qany != nullptr;
   bool any = false;
@@ -783,6 +789,7 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
   const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
   const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;
+  const int nleft = nleft_of(M, p, n);   // once per problem: a scalar select for frames that are no fisheye-stereo ones
   const float *kp = M.kp + fo * 7;
   const uint32_t *desc = reinterpret_cast<const uint32_t *>(M.desc + fo * 32);
   int32_t *slot = M.slot + fo;
@@ -866,7 +873,6 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
     w.cy0 = max(0, (int)floorf((w.v - M.min_y - w.r) * M.inv_h));
     w.cy1 = min(47, (int)ceilf((w.v - M.min_y + w.r) * M.inv_h));
     w.live = (R[1] & 1u) && w.cx0 < 64 && w.cx1 >= 0 && w.cy0 < 48 && w.cy1 >= 0 && w.cx0 <= w.cx1;
-    const int nleft = M.qside ? M.nleft : n;
     const bool sideR = (R[1] >> 8) & 1u;             // fisheye-stereo: the query sees only the keypoints of its own image
     w.checkLevels = (w.minl > 0) || (w.maxl >= 0);
     w.stereo = M.u_right != nullptr;

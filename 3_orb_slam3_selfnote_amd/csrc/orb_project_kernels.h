@@ -1,5 +1,5 @@
 // orb_project_kernels.h -- the parts of SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono)
-// (ORBmatcher.cc:2027-2289, Nleft == -1) that surround the Hamming search: the projection of the last frame's map points into
+// (ORBmatcher.cc:2027-2289, Nleft == -1 and Nleft != -1) that surround the Hamming search: the projection of the last frame's map points into
 // the current frame (:2038-2118) in front of k_match_scan / k_match_resolve, and the rotation-histogram pruning (:2177-2185,
 // :2263-2286) behind them.  With both on the device a whole batch of frame pairs runs without touching the host
 // (BASELINE config 5: KannalaBrandt8 projection inside the search).
@@ -44,17 +44,13 @@ struct LastFrameParams {
   QueryScratch Q;          // out
 };
 
-// One thread per last-frame keypoint: ORBmatcher.cc:2038-2052 (per pair, recomputed by every thread from scalar loads) and
-// :2062-2118 -> (u, v, radius, level window, right coordinate, flags) of query i.
-__global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
-  const int p = blockIdx.y;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = P.last_n ? min(P.last_n[(size_t)p * P.last_n_stride], P.last_stride) : P.last_n_const;
-  if (i >= P.last_stride) return;
-  const size_t o = (size_t)p * P.last_stride + i;
-  float u = 0.f, v = 0.f, rad = 0.f, ur = 0.f;
-  int minl = -1, maxl = -1;
-  uint8_t fl = 0;
+// ORBmatcher.cc:2038-2052 (per pair, recomputed by every thread from scalar loads) and :2062-2118 for last-frame keypoint i of
+// problem p (o = p * last_stride + i, n = the problem's live count): (u, v, radius, level window, right coordinate, flags) of
+// its query in the (left) image; fl = 0: the point takes no part.  xc = x3Dc (:2072), valid where fl != 0.
+struct LastFrameQuery { float u, v, rad, ur; int minl, maxl; uint8_t fl; };
+
+__device__ __forceinline__ LastFrameQuery lastframe_query(const LastFrameParams &P, int p, int i, int n, size_t o, float *xc) {
+  LastFrameQuery q = {0.f, 0.f, 0.f, 0.f, -1, -1, 0};
   if (i < n && P.has_mp[o]) {
     const float *Tcw = P.Tcw + (size_t)p * 16, *Tlw = P.Tlw + (size_t)p * 16;
     const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, tlw[3] = {Tlw[3], Tlw[7], Tlw[11]};
@@ -63,7 +59,6 @@ __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
     mat3_mul_add(Tlw, twc, tlw, tlc);  // :2047
     const bool bForward = tlc[2] > P.mb && !P.bMono, bBackward = -tlc[2] > P.mb && !P.bMono;  // :2051-2052
     const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
-    float xc[3];
     mat3_mul_add(Tcw, xw, tcw, xc);                          // :2072
     const float invzc = (float)(1.0 / (double)xc[2]);        // :2076
     if (!(invzc < 0)) {
@@ -72,15 +67,66 @@ __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
       const bool inside = inside_bounds(ux, vy, P.V.min_x, P.V.max_x, P.V.min_y, P.V.max_y);  // :2094-2097
       const int oct = __float_as_int(P.last_kp[7 * o + 5]);
       if (inside && oct >= 0 && oct < P.V.nlevels) {
-        u = ux; v = vy;
-        rad = P.th * P.V.sf[oct];                                 // :2105
-        lastframe_level_window(bForward, bBackward, oct, minl, maxl);   // :2113-2118
-        ur = ux - P.mbf * invzc;                                  // :2141
-        fl = query_flags(P.obs, o);
+        q.u = ux; q.v = vy;
+        q.rad = P.th * P.V.sf[oct];                                 // :2105
+        lastframe_level_window(bForward, bBackward, oct, q.minl, q.maxl);   // :2113-2118
+        q.ur = ux - P.mbf * invzc;                                  // :2141
+        q.fl = query_flags(P.obs, o);
       }
     }
   }
-  store_query(P.Q, o, u, v, rad, ur, minl, maxl, fl);
+  return q;
+}
+
+// One thread per last-frame keypoint -> query i.
+__global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
+  const int p = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = P.last_n ? min(P.last_n[(size_t)p * P.last_n_stride], P.last_stride) : P.last_n_const;
+  if (i >= P.last_stride) return;
+  const size_t o = (size_t)p * P.last_stride + i;
+  float xc[3];
+  const LastFrameQuery q = lastframe_query(P, p, i, n, o, xc);
+  store_query(P.Q, o, q.u, q.v, q.rad, q.ur, q.minl, q.maxl, q.fl);
+}
+
+// The same loop for a fisheye-stereo current frame (CurrentFrame.Nleft != -1, :2027-2289 with the right-camera pass :2189-2256):
+// last-frame keypoint i makes the queries 2i (left image, the arithmetic above) and 2i + 1 (right image: x3Dr = Rrl * x3Dc + trl
+// through the frame's own camera, :2190-2192; radius and level window of the left query, :2197-2207; no bounds or depth test,
+// the reference has none).  A point the left half drops makes neither.  The search reads 32 descriptor bytes per QUERY, so the
+// point's descriptor is written twice here (qdesc) next to the side bytes; query_n[p] = 2 * the live count.
+struct RigProjectParams {
+  float Trl[12];           // CurrentFrame.mTrl, row-major 3x4
+  const uint8_t *mpdesc;   // 32 bytes per last-frame keypoint (16-byte aligned)
+  uint8_t *qdesc, *qside;  // out: 32 bytes and one byte per query, problem p at query offset p * 2 * last_stride
+  int32_t *query_n;        // out: [npairs]
+};
+
+__global__ __launch_bounds__(256) void k_lastframe_project_rig(LastFrameParams P, RigProjectParams G) {
+  const int p = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = P.last_n ? max(0, min(P.last_n[(size_t)p * P.last_n_stride], P.last_stride)) : P.last_n_const;
+  if (i == 0) G.query_n[p] = 2 * n;
+  if (i >= P.last_stride) return;
+  const size_t o = (size_t)p * P.last_stride + i;
+  float xc[3];
+  const LastFrameQuery q = lastframe_query(P, p, i, n, o, xc);
+  float ur = 0.f, vr = 0.f;
+  if (q.fl) {
+    const float trl[3] = {G.Trl[3], G.Trl[7], G.Trl[11]};
+    float xr[3];
+    mat3_mul_add(G.Trl, xc, trl, xr);                                  // :2190
+    project(P.V.cam_type, P.V.cam, xr[0], xr[1], xr[2], ur, vr);       // :2192 (mpCamera, not mpCamera2)
+  }
+  store_query(P.Q, 2 * o, q.u, q.v, q.rad, 0.f, q.minl, q.maxl, q.fl);     // Nleft != -1: no mvuRight test (:2139)
+  store_query(P.Q, 2 * o + 1, ur, vr, q.rad, 0.f, q.minl, q.maxl, q.fl);
+  G.qside[2 * o] = 0; G.qside[2 * o + 1] = 1;
+  if (i < n) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(G.mpdesc + 32 * o);
+    uint4 *dst = reinterpret_cast<uint4 *>(G.qdesc + 64 * o);
+    const uint4 a = src[0], b = src[1];
+    dst[0] = a; dst[1] = b; dst[2] = a; dst[3] = b;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -186,25 +232,46 @@ struct RotPruneParams {
   int32_t *moq;          // match_of_query (in/out: pruned matches become -1)
   int32_t *slot; uint8_t *slot_obs;
   int32_t *nmatches;     // per problem (in/out)
+  int prune;             // 0: no histogram (checkOri off); only read by the two-queries-per-point form, which always runs
 };
 
 // ORBmatcher.cc:2177-2185 (histogram of the rotation between the matched keypoints) + ComputeThreeMaxima (:2416-2458) +
 // :2263-2286 (matches outside the three dominant bins are undone).  One workgroup per frame pair; the bins only need their
 // sizes (integer LDS atomics), the order inside a bin does not matter for what is kept.
+// QS = 1: fisheye-stereo current frame, two queries (2i, 2i + 1) per last-frame keypoint i, moq [2 * last_stride] per problem.
+// The search left QUERY ids in the slots it wrote; callers hold last-frame indices, so the slots are converted first: the holder
+// of keypoint k is the LAST query that matched it, which is the one the search left there (slot[k] == j).  Two steps with a
+// barrier between them - holder j marks its slot with -2 - (j >> 1), then marked slots become j >> 1 - because a converted
+// value could equal another query's id.  Every accepted query has its histogram entry (:2185, :2252) and every pruned entry
+// decrements nmatches (:2281-2282), so a keypoint matched by two queries counts twice, as in the reference.
+template <int QS>
 __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
   __shared__ int hist[32];
   __shared__ int keep[3];
   __shared__ int removed;
   const int p = blockIdx.x, t = threadIdx.x;
-  const int n = R.last_n ? min(R.last_n[(size_t)p * R.last_n_stride], R.last_stride) : R.last_n_const;
-  const size_t qo = (size_t)p * R.last_stride, ko = (size_t)p * R.frame_stride;
+  const int n = max(0, R.last_n ? min(R.last_n[(size_t)p * R.last_n_stride], R.last_stride) : R.last_n_const) << QS;
+  const size_t lo = (size_t)p * R.last_stride, qo = lo << QS, ko = (size_t)p * R.frame_stride;
+  if (QS) {
+    for (int j = t; j < n; j += 256) {
+      const int m = R.moq[qo + j];
+      if (m >= 0 && R.slot[ko + m] == j) R.slot[ko + m] = -2 - (j >> QS);
+    }
+    __syncthreads();
+    for (int j = t; j < n; j += 256) {
+      const int m = R.moq[qo + j];
+      if (m >= 0 && R.slot[ko + m] == -2 - (j >> QS)) R.slot[ko + m] = j >> QS;
+    }
+    if (!R.prune) return;
+    __syncthreads();
+  }
   if (t < 32) hist[t] = 0;
   if (t == 0) removed = 0;
   __syncthreads();
   for (int i = t; i < n; i += 256) {
     const int m = R.moq[qo + i];
     if (m < 0) continue;
-    const int bin = rot_bin(R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3]);
+    const int bin = rot_bin(R.last_kp[7 * (lo + (i >> QS)) + 3] - R.cur_kp[7 * (ko + m) + 3]);
     if (bin >= 0 && bin < ORBM_HISTO_LENGTH) atomicAdd(&hist[bin], 1);
   }
   __syncthreads();
@@ -219,7 +286,7 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
   for (int i = t; i < n; i += 256) {
     const int m = R.moq[qo + i];
     if (m < 0) continue;
-    const int bin = rot_bin(R.last_kp[7 * (qo + i) + 3] - R.cur_kp[7 * (ko + m) + 3]);
+    const int bin = rot_bin(R.last_kp[7 * (lo + (i >> QS)) + 3] - R.cur_kp[7 * (ko + m) + 3]);
     if (bin < 0 || bin >= ORBM_HISTO_LENGTH || bin == k0 || bin == k1 || bin == k2) continue;
     R.slot[ko + m] = -1;
     R.slot_obs[ko + m] = 0;
@@ -257,4 +324,36 @@ __global__ __launch_bounds__(256) void k_undistort(UndistortParams U) {
   if (U.D[0] != 0.0f) undistort_point((double)k[0], (double)k[1], U.K, U.D, U.nD, &k[0], &k[1]);   // :839-843: D[0] == 0 copies
 #pragma unroll
   for (int t = 0; t < 7; t++) U.keys_un[o + t] = k[t];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The Frame of a two-camera fisheye rig (Frame.cc:1162-1164, :1201) from two resident extractions: mvKeys followed by
+// mvKeysRight, mDescriptors = vconcat(left, right), N = Nleft + Nright.  Frame f: the nL left entries, then the nR right
+// entries directly behind them; entries beyond nL + nR are not written.  One thread per 16-byte half of a descriptor, then
+// one per dword of a keypoint: the right image's keypoints land at (f * 2 * cap + nL) * 28 bytes, which is a multiple of 4
+// only, so the key array moves as dwords (a wavefront still moves 256 contiguous bytes per instruction).
+// ------------------------------------------------------------------------------------------------------------
+struct RigConcatParams {
+  const uint32_t *keysL, *keysR;   // [nframes][cap] keypoints as 7 dwords each
+  const uint4 *descL, *descR;      // [nframes][cap] descriptors as 2 x 16 bytes each
+  const int32_t *countsL, *countsR;   // [nframes][2], element 0 = n
+  int cap;
+  uint32_t *keys; uint4 *desc;     // out: [nframes][2 * cap]
+  int32_t *n;                      // out: [nframes][2] = {nL + nR, nL}
+};
+
+__global__ __launch_bounds__(256) void k_rig_concat(RigConcatParams R) {
+  const int f = blockIdx.y;
+  const int nL = max(0, min(R.countsL[2 * (size_t)f], R.cap)), nR = max(0, min(R.countsR[2 * (size_t)f], R.cap));
+  const int N = nL + nR;   // <= 2 * cap
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t == 0) { R.n[2 * (size_t)f] = N; R.n[2 * (size_t)f + 1] = nL; }
+  const size_t src = (size_t)f * R.cap, dst = (size_t)f * 2 * R.cap;
+  if (t < 2LL * N) {                     // descriptor halves [0, 2 N)
+    const int e = (int)(t >> 1), h = (int)(t & 1);
+    R.desc[2 * (dst + e) + h] = e < nL ? R.descL[2 * (src + e) + h] : R.descR[2 * (src + (e - nL)) + h];
+  } else if (t < 9LL * N) {              // keypoint dwords [0, 7 N)
+    const long long w = t - 2LL * N;
+    R.keys[7 * dst + w] = w < 7LL * nL ? R.keysL[7 * src + w] : R.keysR[7 * src + (w - 7LL * nL)];
+  }
 }

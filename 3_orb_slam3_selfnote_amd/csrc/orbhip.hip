@@ -1171,6 +1171,7 @@ static void *mirror_of(orbm_handle *m, const void *d) { return (uint8_t *)m->pin
 struct SearchOpts {
   int scan_mode = SCAN_AUTO;   // SCAN_AUTO / SCAN_DENSE / SCAN_WALK; frames beyond 2048 keypoints are scanned whatever it says
   int nleft = 0, couple = 0, serial = 0;   // fisheye-stereo frames
+  const int32_t *nleft_dev = nullptr; int nleft_stride = 0;   // Nleft per problem on the device instead of nleft
   const int32_t *partner = nullptr;
   const uint8_t *qside = nullptr;
   uint8_t *qany = nullptr;
@@ -1396,6 +1397,7 @@ static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, cons
   M.dbg = (long long *)getenv_ptr("ORBHIP_DBG_PTR");
 #endif
   M.nleft = o.nleft; M.partner = o.partner; M.qside = o.qside; M.couple = o.couple; M.serial = o.serial; M.qany = o.qany;
+  M.nleft_dev = o.nleft_dev; M.nleft_stride = o.nleft_stride;
   for (int i = 0; i < 16; i++) M.inv_sigma2[i] = o.inv_sigma2[i];
   const int maxn = d_frame_n ? frame_stride : f->n;
   const int maxq = d_query_n ? query_stride : q->nq;
@@ -1639,11 +1641,16 @@ struct QueryArrays {
   }
 };
 
-// The query arrays a projection kernel writes, carved out of `buf` (29 B per query, in blocks of 64 queries) - grows on demand, not
-// on the steady-state path.
-static int carve_query_scratch(orbm_t *m, DevBuf &buf, hipStream_t s, int npairs, int stride, int maxq, QueryScratch &Q) {
-  const size_t nqa = (size_t)(npairs - 1) * stride + maxq, nq4 = (nqa + 63) & ~(size_t)63;
-  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1);
+// What a fisheye-stereo projection kernel writes besides: the descriptor of every query, its side byte, the window-non-empty
+// byte the search keeps per query, the query count per problem.
+struct RigScratch { uint8_t *qdesc, *qside, *qany; int32_t *query_n; };
+
+// The query arrays a projection kernel writes, carved out of `buf` (29 B per query, in blocks of 64 queries; with G 34 B more and
+// 4 B per problem) - grows on demand, not on the steady-state path.
+static int carve_query_scratch(orbm_t *m, DevBuf &buf, hipStream_t s, int npairs, int stride, QueryScratch &Q, RigScratch *G = nullptr) {
+  // every problem gets its full stride: the projection kernels write (dead) queries up to the stride, whatever the live counts are
+  const size_t nqa = (size_t)npairs * stride, nq4 = (nqa + 63) & ~(size_t)63;
+  const size_t need = nq4 * (4 * sizeof(float) + 3 * sizeof(int32_t) + 1 + (G ? 34 : 0)) + (G ? sizeof(int32_t) * (size_t)npairs : 0);
   if (need > buf.bytes) {
     MCHECK(m, hipStreamSynchronize(s));
     MCHECK(m, buf.reserve(need + (need >> 2)));
@@ -1652,6 +1659,10 @@ static int carve_query_scratch(orbm_t *m, DevBuf &buf, hipStream_t s, int npairs
   int32_t *qi = (int32_t *)(qf + 4 * nq4);
   Q.u = qf; Q.v = qf + nq4; Q.r = qf + 2 * nq4; Q.ur = qf + 3 * nq4;
   Q.minl = qi; Q.maxl = qi + nq4; Q.moq = qi + 2 * nq4; Q.flags = (uint8_t *)(qi + 3 * nq4);
+  if (G) {   // every part starts at a multiple of 64 bytes
+    G->qdesc = Q.flags + nq4; G->qside = G->qdesc + 32 * nq4; G->qany = G->qside + nq4;
+    G->query_n = (int32_t *)(G->qany + nq4);
+  }
   return 0;
 }
 static orbm_queries_t scratch_view(const QueryScratch &Q, int nq, const uint8_t *desc, bool with_ur) {
@@ -1677,6 +1688,20 @@ static bool valid_track(const orbm_track_t *t) {
   return t->in_view && t->proj_x && t->proj_y && t->proj_xr && t->depth && t->view_cos && t->level;
 }
 
+// The host forms of the last-frame searches: the windows are th * scale factor of the last keypoint's octave (ORBmatcher.cc:2109),
+// known on the host, so the walk-or-scan decision is taken there from the largest one (an upper bound of every query's cell window)
+// and only the chosen kernels are launched.  Octaves are in [0, nlevels) where has_mp is set (checked by the callers).
+static int host_scan_mode(const orbm_t *m, const orbm_frame_t *cur, const float *sf, int nLast, const uint8_t *has_mp,
+                          const orbx_keypoint_t *last_keys, float th) {
+  if (m->scan_mode != SCAN_AUTO || cur->n > WALK_MAX_N || !(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) return m->scan_mode;
+  float rmax = 0.f;
+  for (int i = 0; i < nLast; i++)
+    if (has_mp[i]) rmax = std::max(rmax, th * sf[last_keys[i].octave]);
+  const float iw = (float)ORBM_GRID_COLS / (cur->max_x - cur->min_x), ih = (float)ORBM_GRID_ROWS / (cur->max_y - cur->min_y);
+  const long long cx = std::min<long long>(ORBM_GRID_COLS, (long long)ceilf(2.f * rmax * iw) + 2), cy = std::min<long long>(ORBM_GRID_ROWS, (long long)ceilf(2.f * rmax * ih) + 2);
+  return cx * cy <= WALK_MAX_CELLS ? SCAN_WALK : m->scan_mode;
+}
+
 static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
                                   const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n, int last_n_stride, int npairs,
                                   const float *sf, int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
@@ -1691,7 +1716,7 @@ static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int fram
   LastFrameParams P;
   memset(&P, 0, sizeof(P));
   QueryScratch &Q = P.Q;
-  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, last_stride, maxq, Q);
+  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, last_stride, Q);
   if (rq < 0) return rq;
   int32_t *moq = d_moq ? d_moq : Q.moq;
   P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
@@ -1712,8 +1737,8 @@ static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int fram
     R.last_kp = reinterpret_cast<const float *>(last0->last_keys);
     R.last_stride = last_stride; R.last_n = d_last_n; R.last_n_stride = last_n_stride; R.last_n_const = last0->n;
     R.cur_kp = reinterpret_cast<const float *>(cur0->keys_un); R.frame_stride = frame_stride;
-    R.moq = moq; R.slot = d_slot; R.slot_obs = d_slot_obs; R.nmatches = d_nmatches;
-    hipLaunchKernelGGL(k_rot_prune, dim3(npairs), dim3(256), 0, s, R);
+    R.moq = moq; R.slot = d_slot; R.slot_obs = d_slot_obs; R.nmatches = d_nmatches; R.prune = 1;
+    hipLaunchKernelGGL(k_rot_prune<0>, dim3(npairs), dim3(256), 0, s, R);
   }
   MCHECK(m, hipGetLastError());
   return 0;
@@ -1763,17 +1788,7 @@ int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, con
   dl.n = nLast;
   dl.has_mp = (const uint8_t *)d[HAS]; dl.Xw = (const float *)d[XW]; dl.mpdesc = (const uint8_t *)d[MD];
   dl.last_keys = (const orbx_keypoint_t *)d[LK]; dl.obs = (const uint8_t *)d[OBS]; dl.Tcw = (const float *)d[TC]; dl.Tlw = (const float *)d[TL];
-  // The windows are th * scale factor of the last keypoint's octave (ORBmatcher.cc:2109): known here, so the walk-or-scan decision
-  // is taken on the host from the largest one (an upper bound of every query's cell window) and only the chosen kernels are launched
-  int scan_mode = m->scan_mode;
-  if (m->scan_mode == SCAN_AUTO && n <= WALK_MAX_N && cur->max_x > cur->min_x && cur->max_y > cur->min_y) {
-    float rmax = 0.f;
-    for (int i = 0; i < nLast; i++)
-      if (has_mp[i]) rmax = std::max(rmax, th * sf[last_keys[i].octave]);
-    const float iw = (float)ORBM_GRID_COLS / (cur->max_x - cur->min_x), ih = (float)ORBM_GRID_ROWS / (cur->max_y - cur->min_y);
-    const long long cx = std::min<long long>(ORBM_GRID_COLS, (long long)ceilf(2.f * rmax * iw) + 2), cy = std::min<long long>(ORBM_GRID_ROWS, (long long)ceilf(2.f * rmax * ih) + 2);
-    if (cx * cy <= WALK_MAX_CELLS) scan_mode = SCAN_WALK;
-  }
+  const int scan_mode = host_scan_mode(m, cur, sf, nLast, has_mp, last_keys, th);
   const int rs = search_last_frame_batch(m, &df, n, nullptr, 0, &dl, nLast, nullptr, 0, 1, sf, nlevels, cam_type, cam_params, mb, mbf, th, bMono,
                                          checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
   if (rs < 0) return rs;
@@ -1801,7 +1816,7 @@ static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_str
   LocalMapParams P;
   memset(&P, 0, sizeof(P));
   QueryScratch &Q = P.Q;
-  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, maxq, Q);
+  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, Q);
   if (rq < 0) return rq;
   P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
   P.obs = map0->obs; P.Tcw = map0->Tcw;
@@ -1924,6 +1939,92 @@ int orbm_search_by_projection_fisheye(orbm_t *m, const orbm_frame_t *f, int n_le
   return search_host(m, f, q, nnratio, th_dist, 1, slot, slot_obs, match_of_query, best_dist, o, anyp ? partner.data() : nullptr, side.data());
 }
 
+// The device core of the last-frame search of a fisheye-stereo current frame: k_lastframe_project_rig (two queries per last-frame
+// keypoint, their descriptors and side bytes), the search with couple = 2, k_rot_prune<1> (slot conversion, then the pruning).
+// Arguments are checked before anything is launched.
+static int search_last_frame_rig_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
+                                       const int32_t *d_n_left, int n_left_stride, int n_left, const orbm_last_frame_t *last0, int last_stride,
+                                       const int32_t *d_last_n, int last_n_stride, int npairs, const float *sf, int nlevels, const float *Trl,
+                                       int cam_type, const float *cam_params, float mb, float th, int bMono, int checkOri, int32_t *d_slot,
+                                       uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches, hipStream_t s, int scan_mode) {
+  if (!m || !cur0 || !last0 || !sf || !cam_params || !Trl || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
+  if (!last0->has_mp || !last0->Xw || !last0->mpdesc || !last0->last_keys || !last0->Tcw || !last0->Tlw) return ORBX_E_ARG;
+  if (!cur0->keys_un || !cur0->descriptors || !(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y)) return ORBX_E_ARG;
+  const int maxq = d_last_n ? last_stride : last0->n;
+  const int maxn = d_frame_n ? frame_stride : cur0->n;
+  if (maxq <= 0 || last_stride < maxq || maxn <= 0 || frame_stride < maxn) return ORBX_E_ARG;
+  if (!d_n_left && (n_left < 0 || n_left > cur0->n)) return ORBX_E_ARG;
+  if ((long long)last_stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
+  if (npairs == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  LastFrameParams P;
+  memset(&P, 0, sizeof(P));
+  QueryScratch &Q = P.Q;
+  RigScratch G;
+  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, 2 * last_stride, Q, &G);
+  if (rq < 0) return rq;
+  int32_t *moq = d_moq ? d_moq : Q.moq;
+  P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
+  P.Tcw = last0->Tcw; P.Tlw = last0->Tlw;
+  P.last_stride = last_stride; P.last_n = d_last_n; P.last_n_stride = last_n_stride; P.last_n_const = last0->n;
+  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
+  P.mb = mb; P.mbf = 0.f; P.th = th; P.bMono = bMono ? 1 : 0;
+  RigProjectParams R;
+  memset(&R, 0, sizeof(R));
+  for (int i = 0; i < 12; i++) R.Trl[i] = Trl[i];
+  R.mpdesc = last0->mpdesc; R.qdesc = G.qdesc; R.qside = G.qside; R.query_n = G.query_n;
+  hipLaunchKernelGGL(k_lastframe_project_rig, dim3((last_stride + 255) / 256, npairs), dim3(256), 0, s, P, R);
+  const orbm_queries_t q = scratch_view(Q, 2 * last0->n, G.qdesc, false);
+  orbm_frame_t f = *cur0;
+  f.u_right = nullptr;  // Nleft != -1: no mvuRight test (:2139)
+  SearchOpts o;
+  o.scan_mode = scan_mode;
+  o.nleft = n_left; o.nleft_dev = d_n_left; o.nleft_stride = n_left_stride;
+  o.couple = 2; o.qside = G.qside; o.qany = G.qany;   // :2126: an empty left window drops the right pass
+  const int rc = search_batch(m, &f, frame_stride, d_frame_n, frame_n_stride, &q, 2 * last_stride, d_last_n ? G.query_n : nullptr, 1, npairs, 0.f,
+                              ORBM_TH_HIGH, 0, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // :2128-2162, :2208-2256
+  if (rc < 0) return rc;
+  RotPruneParams H;
+  memset(&H, 0, sizeof(H));
+  H.last_kp = reinterpret_cast<const float *>(last0->last_keys);   // :2169-2171
+  H.last_stride = last_stride; H.last_n = d_last_n; H.last_n_stride = last_n_stride; H.last_n_const = last0->n;
+  H.cur_kp = reinterpret_cast<const float *>(cur0->keys_un); H.frame_stride = frame_stride;
+  H.moq = moq; H.slot = d_slot; H.slot_obs = d_slot_obs; H.nmatches = d_nmatches; H.prune = checkOri ? 1 : 0;
+  hipLaunchKernelGGL(k_rot_prune<1>, dim3(npairs), dim3(256), 0, s, H);
+  MCHECK(m, hipGetLastError());
+  return 0;
+}
+
+int orbm_search_by_projection_last_frame_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                                              int frame_n_stride, const int32_t *d_n_left, int n_left_stride, int n_left,
+                                                              const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n,
+                                                              int last_n_stride, int npairs, const float *sf, int nlevels, const float *Trl,
+                                                              int cam_type, const float *cam_params, float mb, float th, int bMono, int checkOri,
+                                                              int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches,
+                                                              void *stream_) {
+  if (!m) return ORBX_E_ARG;
+  if (frame_stride > ORBM_FISHEYE_MAX_KEYPOINTS) { m->err = "more than 12960 keypoints (left + right) per fisheye-stereo frame not supported by the resident search"; return ORBX_E_ARG; }
+  return search_last_frame_rig_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride, n_left, last0, last_stride, d_last_n,
+                                     last_n_stride, npairs, sf, nlevels, Trl, cam_type, cam_params, mb, th, bMono, checkOri, d_slot, d_slot_obs, d_moq,
+                                     d_nmatches, (hipStream_t)stream_, m->scan_mode);
+}
+
+int orbm_rig_concat_batch_device(int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
+                                 const orbx_keypoint_t *d_keysR, const uint8_t *d_descR, const int32_t *d_countsR, int cap,
+                                 orbx_keypoint_t *d_keys, uint8_t *d_desc, int32_t *d_n, void *stream_) {
+  if (!d_keysL || !d_descL || !d_countsL || !d_keysR || !d_descR || !d_countsR || !d_keys || !d_desc || !d_n) return ORBX_E_ARG;
+  if (nframes < 0 || nframes > 65535 || cap <= 0 || cap > ORBM_FISHEYE_MAX_KEYPOINTS / 2) return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  RigConcatParams R;
+  R.keysL = reinterpret_cast<const uint32_t *>(d_keysL); R.keysR = reinterpret_cast<const uint32_t *>(d_keysR);
+  R.descL = reinterpret_cast<const uint4 *>(d_descL); R.descR = reinterpret_cast<const uint4 *>(d_descR);
+  R.countsL = d_countsL; R.countsR = d_countsR; R.cap = cap;
+  R.keys = reinterpret_cast<uint32_t *>(d_keys); R.desc = reinterpret_cast<uint4 *>(d_desc); R.n = d_n;
+  hipLaunchKernelGGL(k_rig_concat, dim3((18 * cap + 255) / 256, nframes), dim3(256), 0, (hipStream_t)stream_, R);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
 int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const float *sf, int nlevels,
                                                  int nLast, const uint8_t *has_mp, const float *Xw, const uint8_t *mpdesc,
                                                  const orbx_keypoint_t *last_keys, const uint8_t *obs, const float *Tcw,
@@ -1932,54 +2033,34 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
   if (!m || !cur || !sf || nLast < 0 || !Tcw || !Tlw || !Trl || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
   if (n_left < 0 || n_left > cur->n) return ORBX_E_ARG;
   if (nLast > 0 && (!has_mp || !Xw || !mpdesc || !last_keys)) return ORBX_E_ARG;
-  const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, tlw[3] = {Tlw[3], Tlw[7], Tlw[11]}, trl[3] = {Trl[3], Trl[7], Trl[11]};
-  float twc[3], tlc[3];
-  camera_centre(Tcw, twc);  // twc = -Rcw.t()*tcw, :2041
-  mat3_mul_add(Tlw, twc, tlw, tlc);
-  const bool bForward = tlc[2] > mb && !bMono, bBackward = -tlc[2] > mb && !bMono;
-  const int nq = 2 * nLast;
-  QueryArrays A(nq);
-  std::vector<float> qangle(nq, 0.f);
-  std::vector<int32_t> moq(nq, -1);
-  std::vector<uint8_t> side(nq), qd((size_t)nq * 32);
-  for (int i = 0; i < nLast; i++) {
-    side[2 * i] = 0; side[2 * i + 1] = 1;
-    memcpy(&qd[(size_t)(2 * i) * 32], mpdesc + (size_t)i * 32, 32);
-    memcpy(&qd[(size_t)(2 * i + 1) * 32], mpdesc + (size_t)i * 32, 32);
-    qangle[2 * i] = qangle[2 * i + 1] = last_keys[i].angle;
-    if (!has_mp[i]) continue;
-    float x3Dc[3], x3Dr[3];
-    mat3_mul_add(Tcw, Xw + 3 * i, tcw, x3Dc);                  // :2072
-    const float invzc = (float)(1.0 / (double)x3Dc[2]);        // :2076
-    if (invzc < 0) continue;
-    float ux, vy;
-    project(cam_type, cam_params, x3Dc[0], x3Dc[1], x3Dc[2], ux, vy);
-    if (!inside_bounds(ux, vy, cur->min_x, cur->max_x, cur->min_y, cur->max_y)) continue;   // :2094-2097
-    const int nLastOctave = last_keys[i].octave;
-    if (nLastOctave < 0 || nLastOctave >= nlevels) return ORBX_E_ARG;
-    mat3_mul_add(Trl, x3Dc, trl, x3Dr);                        // :2190
-    float uxr, vyr;
-    project(cam_type, cam_params, x3Dr[0], x3Dr[1], x3Dr[2], uxr, vyr);
-    const uint8_t fl = query_flags(obs, i);
-    for (int h = 0; h < 2; h++) {
-      const int j = 2 * i + h;
-      A.u[j] = h ? uxr : ux; A.v[j] = h ? vyr : vy;
-      A.rad[j] = th * sf[nLastOctave];                             // :2105, :2197
-      lastframe_level_window(bForward, bBackward, nLastOctave, A.minl[j], A.maxl[j]);   // :2113-2118, :2201-2206
-      A.flags[j] = fl;
-    }
-  }
-  const orbm_queries_t q = A.view(qd.data());
-  orbm_frame_t f = *cur;
-  f.u_right = nullptr;  // Nleft != -1: no mvuRight test (:2139)
-  SearchOpts o;
-  o.nleft = n_left; o.couple = 2;
-  int nmatches = search_host(m, &f, &q, 0.f, ORBM_TH_HIGH, 0, slot, slot_obs, moq.data(), nullptr, o, nullptr, side.data());
-  if (nmatches < 0) return nmatches;
-  for (int j = 0; j < nq; j++)  // the device stored query indices; the caller's ids are last-frame indices (in order: last writer wins)
-    if (moq[j] >= 0) slot[moq[j]] = j >> 1;
-  if (!checkOri) return nmatches;
-  return prune_by_rotation(nq, moq.data(), qangle.data(), cur->keys_un, slot, slot_obs, nmatches);
+  if (nlevels < 1 || nlevels > 16) return ORBX_E_ARG;
+  const int n = cur->n;
+  if (n == 0 || nLast == 0) return 0;
+  if (!cur->keys_un || !cur->descriptors) return ORBX_E_ARG;
+  for (int i = 0; i < nLast; i++)
+    if (has_mp[i] && (last_keys[i].octave < 0 || last_keys[i].octave >= nlevels)) return ORBX_E_ARG;
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  // one staged block up, one block down, one synchronisation (as orbm_search_by_projection_last_frame); the batch form's kernels, npairs = 1
+  enum { KP, DESC, HAS, XW, MD, LK, OBS, TC, TL, SLOT, SOBS, NM, NPARTS };
+  void *d[NPARTS];
+  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n}, {has_mp, (size_t)nLast},
+                              {Xw, 3 * sizeof(float) * (size_t)nLast}, {mpdesc, 32 * (size_t)nLast}, {last_keys, sizeof(orbx_keypoint_t) * (size_t)nLast},
+                              {obs, obs ? (size_t)nLast : 0}, {Tcw, 16 * sizeof(float)}, {Tlw, 16 * sizeof(float)},
+                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t)}}, d, true);
+  if (rc < 0) return rc;
+  orbm_frame_t df = *cur;
+  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = nullptr;
+  orbm_last_frame_t dl;
+  memset(&dl, 0, sizeof(dl));
+  dl.n = nLast;
+  dl.has_mp = (const uint8_t *)d[HAS]; dl.Xw = (const float *)d[XW]; dl.mpdesc = (const uint8_t *)d[MD];
+  dl.last_keys = (const orbx_keypoint_t *)d[LK]; dl.obs = (const uint8_t *)d[OBS]; dl.Tcw = (const float *)d[TC]; dl.Tlw = (const float *)d[TL];
+  const int scan_mode = host_scan_mode(m, cur, sf, nLast, has_mp, last_keys, th);
+  const int rs = search_last_frame_rig_batch(m, &df, n, nullptr, 0, nullptr, 0, n_left, &dl, nLast, nullptr, 0, 1, sf, nlevels, Trl, cam_type, cam_params,
+                                             mb, th, bMono, checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
+  if (rs < 0) return rs;
+  return download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
 }
 
 int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, float logScaleFactor, int nKF,

@@ -249,7 +249,10 @@ int orbx_close_points_batch_device(int nframes, const float *d_depth, const int3
 #define ORBM_GRID_ROWS 48 /* Frame.h:39 */
 #define ORBM_MAX_KEYPOINTS 15360 /* per frame, projection search: its claim state lives in one CU's LDS */
 /* Fisheye-stereo searches (orbm_search_by_projection_fisheye, ..._last_frame_fisheye) keep a partner list in LDS as well and
- * take up to about 13 000 keypoints (left + right); beyond that they return ORBX_E_ARG. */
+ * take up to about 13 000 keypoints (left + right); beyond that they return ORBX_E_ARG.  The resident forms
+ * (orbm_rig_concat_batch_device, orbm_search_by_projection_last_frame_fisheye_batch_device) refuse a frame stride above
+ * the count at which that list still fits: */
+#define ORBM_FISHEYE_MAX_KEYPOINTS 12960
 
 typedef struct orbm_handle orbm_t;
 orbm_t *orbm_create(int device);
@@ -422,13 +425,62 @@ int orbm_search_by_projection_fisheye(orbm_t *m, const orbm_frame_t *frame, int 
                                       const int32_t *right_to_left, const orbm_queries_t *q, float nnratio, int th_dist,
                                       int32_t *slot, uint8_t *slot_obs, int32_t *match_of_query, int32_t *best_dist);
 /* Trl = CurrentFrame.mTrl (row-major 3x4 or 4x4, row stride 4).  slot values are last-frame indices i.  The right
- * pass of a map point is skipped when its left window is empty (:2126). */
+ * pass of a map point is skipped when its left window is empty (:2126).  One staged upload, the kernels of the batched form
+ * below with npairs = 1 (projection of both cameras, search, slot conversion and rotation pruning on the device), one
+ * download, one synchronisation.  ORBX_E_ARG also for nlevels outside [1, 16] and for a point with has_mp whose octave is
+ * outside [0, nlevels). */
 int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const float *scale_factors,
                                                  int nlevels, int nLast, const uint8_t *has_mp, const float *Xw,
                                                  const uint8_t *mpdesc, const orbx_keypoint_t *last_keys, const uint8_t *obs,
                                                  const float *Tcw, const float *Tlw, const float *Trl, int cam_type,
                                                  const float *cam_params, float mb, float th, int bMono, int checkOri,
                                                  int32_t *slot, uint8_t *slot_obs);
+
+/* The Frame of a two-camera fisheye rig from two resident extractions: Frame.cc:1162-1164 (N = Nleft + Nright, mvKeys and
+ * mvKeysRight as the searches address them: keypoint k < Nleft is mvKeys[k], the others mvKeysRight[k - Nleft]) and :1201
+ * (mDescriptors = vconcat(mDescriptors, mDescriptorsRight)).  No handle: device pointers, asynchronous on `stream`, no host
+ * synchronisation, copy or allocation.  d_keysL / d_descL / d_countsL and d_keysR / d_descR / d_countsR are what two
+ * orbx_extract_batch_device calls of the same cap wrote ([nframes][cap], [nframes][cap][32], [nframes][2]; the descriptors
+ * 16-byte aligned).  Per frame f with nL = d_countsL[2 f], nR = d_countsR[2 f] (each taken as 0 below 0 and cap above cap):
+ * d_keys [nframes][2 * cap] and d_desc [nframes][2 * cap][32] receive the nL left entries and the nR right entries directly
+ * behind them; entries beyond nL + nR are left alone; d_n [nframes][2] = {nL + nR, nL}, which is what the search below reads
+ * as d_frame_n and d_n_left with stride 2.  One kernel: descriptors as 16-byte accesses, keypoints (28 bytes, the right
+ * image's at an offset that is a multiple of 4 only) as dwords.
+ * ORBX_E_ARG: a NULL pointer, nframes < 0 or above 65535, cap <= 0, 2 * cap above ORBM_FISHEYE_MAX_KEYPOINTS.  nframes == 0
+ * returns 0 and launches nothing.  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
+int orbm_rig_concat_batch_device(int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
+                                 const orbx_keypoint_t *d_keysR, const uint8_t *d_descR, const int32_t *d_countsR, int cap,
+                                 orbx_keypoint_t *d_keys, uint8_t *d_desc, int32_t *d_n, void *stream);
+
+/* Batched device form of orbm_search_by_projection_last_frame_fisheye (ORBmatcher.cc:2027-2289 for CurrentFrame.Nleft != -1,
+ * with the right-camera pass :2189-2256): `npairs` independent (current rig frame, last frame) problems, everything resident
+ * in HBM, asynchronous on `stream`, nothing touches the host.  Structs, strides and live counts as in
+ * orbm_search_by_projection_last_frame_batch_device, with these differences:
+ * cur0: keys_un = the concatenated RAW keypoints [mvKeys ; mvKeysRight], descriptors = mDescriptors, as the per-frame form;
+ * u_right is ignored (:2139).  N of problem p = d_frame_n[p * frame_n_stride] (or cur0->n), Nleft = d_n_left[p *
+ * n_left_stride] (taken into [0, N]), or the constant n_left when d_n_left is NULL; d_n of orbm_rig_concat_batch_device feeds both with stride 2.
+ * last0->last_keys = the last frame's concatenated keypoints: octave (:2100-2101) and angle (:2169-2171) of point i.
+ * Trl = CurrentFrame.mTrl, row-major with row stride 4 (12 or 16 floats), a HOST array like scale_factors and cam_params.
+ * Device work: k_lastframe_project_rig makes the queries 2i (left image: the arithmetic of the monocular form) and 2i + 1
+ * (right image: x3Dr = Rrl * x3Dc + trl projected with the frame's own camera, :2190-2192; same radius and level window,
+ * :2197-2207; no bounds or depth test; a point the left half drops - invzc < 0, outside the bounds, !has_mp, an octave
+ * outside [0, nlevels) - makes neither), their side bytes and descriptors; the search kernels with the image restriction per
+ * query and the rule that an empty left window drops the right pass (:2126); k_rot_prune with two queries per point: the
+ * slots the search wrote become last-frame indices i (a keypoint's holder is the LAST query that matched it), then the
+ * rotation histogram gets one entry per accepted query (:2185, :2252) and every pruned entry decrements nmatches
+ * (:2281-2282), so a keypoint matched by two queries counts twice, as in the reference.
+ * d_slot / d_slot_obs [npairs][frame_stride] in/out (entries the call does not write keep the caller's values),
+ * d_match_of_query [npairs][2 * last_stride] (out, may be NULL): entry 2i = the left-image match of last point i, 2i + 1 its
+ * right-image match, indices into the concatenated frame or -1, after pruning.  d_nmatches[npairs] out.
+ * ORBX_E_ARG: what the monocular batch form refuses (npairs < 0 here), NULL Trl, a constant n_left outside [0, cur0->n],
+ * frame_stride above ORBM_FISHEYE_MAX_KEYPOINTS.  npairs == 0 returns 0 and launches nothing. */
+int orbm_search_by_projection_last_frame_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                                              int frame_n_stride, const int32_t *d_n_left, int n_left_stride, int n_left,
+                                                              const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n,
+                                                              int last_n_stride, int npairs, const float *scale_factors, int nlevels,
+                                                              const float *Trl, int cam_type, const float *cam_params, float mb, float th,
+                                                              int bMono, int checkOri, int32_t *d_slot, uint8_t *d_slot_obs,
+                                                              int32_t *d_match_of_query, int32_t *d_nmatches, void *stream);
 
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound,
  *                                    const float th, const int ORBdist)                       (ORBmatcher.cc:2291-2413)
