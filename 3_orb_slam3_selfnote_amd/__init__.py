@@ -27,6 +27,8 @@ assert KP_DTYPE.itemsize == 28
 E_EMPTY, E_ARG, E_HIP, E_CAP = -1, -2, -3, -4
 CLOSE_MAX_KEYPOINTS = 4096  # ORBX_CLOSE_MAX_KEYPOINTS
 FISHEYE_MAX_KEYPOINTS = 12960  # ORBM_FISHEYE_MAX_KEYPOINTS
+CLAHE_BAND_ROWS = 32  # ORBX_CLAHE_BAND_ROWS
+REMAP_FRAME_CHUNK = 16  # ORBX_REMAP_FRAME_CHUNK
 
 # every symbol include/orbhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -36,6 +38,7 @@ ABI_SYMBOLS = [
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
     "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
+    "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
     "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
@@ -131,6 +134,9 @@ def load(build_if_needed=True):
     L.orbx_clahe_device.argtypes = [vp, i32, i32, sz, C.c_double, i32, i32, vp, vp, sz, vp]
     L.orbx_remap_linear.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, i32, vp, sz]
     L.orbx_remap_linear_device.argtypes = [vp, i32, i32, sz, vp, vp, sz, i32, i32, vp, sz, vp]
+    L.orbx_clahe_batch_device.argtypes = [i32, vp, i32, i32, sz, sz, C.c_double, i32, i32, vp, vp, sz, sz, vp]
+    L.orbx_remap_linear_batch_device.argtypes = [i32, vp, i32, i32, sz, sz, vp, vp, sz, i32, i32, vp, sz, sz, vp]
+    L.orbx_clahe_band_lut_rows.argtypes = [i32, i32, i32, i32, vp, vp]
     L.orbx_ref_cosf.restype = f32
     L.orbx_ref_cosf.argtypes = [f32]
     L.orbx_ref_sinf.restype = f32
@@ -1027,6 +1033,37 @@ def stereo_from_rgbd_batch_device(nframes, d_keys, d_keys_un, d_counts, count_st
                                                    C.c_size_t(frame_stride), C.c_float(depth_factor), C.c_float(mbf), _dp(d_uRight), _dp(d_depth),
                                                    _dp(d_nstereo), _dp(stream))
     return _check_free(rc, "orbx_stereo_from_rgbd_batch_device")
+
+
+def clahe_batch_device(nframes, d_src, rows, cols, src_stride, src_frame_stride, clip_limit, tiles_x, tiles_y, d_lut, d_dst, dst_stride,
+                       dst_frame_stride, stream=None):
+    """createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply of the TUM-VI examples (mono_tum_vi.cc:101-109) for `nframes` resident
+    frames (orbx_clahe_batch_device): all pointers are device addresses (ints), asynchronous on `stream`, strides in bytes.  Frame f at
+    d_src + f * src_frame_stride, result at d_dst + f * dst_frame_stride; d_dst == d_src with equal strides is the in-place form.
+    d_lut: nframes * tiles_x * tiles_y * 256 bytes of scratch."""
+    rc = load().orbx_clahe_batch_device(int(nframes), _dp(d_src), int(rows), int(cols), C.c_size_t(src_stride), C.c_size_t(src_frame_stride),
+                                        C.c_double(clip_limit), int(tiles_x), int(tiles_y), _dp(d_lut), _dp(d_dst), C.c_size_t(dst_stride),
+                                        C.c_size_t(dst_frame_stride), _dp(stream))
+    return _check_free(rc, "orbx_clahe_batch_device")
+
+
+def remap_linear_batch_device(nframes, d_src, src_rows, src_cols, src_stride, src_frame_stride, d_mapx, d_mapy, map_stride_elems, rows, cols,
+                              d_dst, dst_stride, dst_frame_stride, stream=None):
+    """cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) of the stereo examples (stereo_euroc.cc:166-167) for `nframes` resident frames
+    with one float map pair (orbx_remap_linear_batch_device): all pointers are device addresses (ints), asynchronous on `stream`,
+    image strides in bytes, map_stride_elems in floats.  The destination must not overlap the source.  A thread serves
+    REMAP_FRAME_CHUNK frames with one decoded map entry."""
+    rc = load().orbx_remap_linear_batch_device(int(nframes), _dp(d_src), int(src_rows), int(src_cols), C.c_size_t(src_stride),
+                                               C.c_size_t(src_frame_stride), _dp(d_mapx), _dp(d_mapy), C.c_size_t(map_stride_elems), int(rows), int(cols),
+                                               _dp(d_dst), C.c_size_t(dst_stride), C.c_size_t(dst_frame_stride), _dp(stream))
+    return _check_free(rc, "orbx_remap_linear_batch_device")
+
+
+def clahe_band_lut_rows(rows, tiles_y, y0, y1):
+    """(first, count) of the table rows orbx_clahe_batch_device stages for the image rows y0 .. y1 (orbx_clahe_band_lut_rows)."""
+    first, count = C.c_int(), C.c_int()
+    _check_free(load().orbx_clahe_band_lut_rows(int(rows), int(tiles_y), int(y0), int(y1), C.byref(first), C.byref(count)), "orbx_clahe_band_lut_rows")
+    return first.value, count.value
 
 
 def close_points_batch_device(nframes, d_depth, d_counts, count_stride, cap, th_depth, max_point, d_order, d_nvisit, d_tracked=None, d_close=None,

@@ -1760,23 +1760,9 @@ __global__ __launch_bounds__(256) void k_cvt_gray(const uint8_t *src, int rows, 
 // LUT saturate_cast<uchar>(sum * lutScale); then every pixel blends the LUTs of its four neighbouring tiles bilinearly
 // in float.  When the image size is not a multiple of the tile grid the histogram runs over the image extended to the
 // next multiple with BORDER_REFLECT_101 (tw, th are the tile sizes of the extended image).
-// k_clahe_lut: one workgroup per tile, thread b owns histogram bin b.
-__global__ __launch_bounds__(256) void k_clahe_lut(const uint8_t *src, int rows, int cols, size_t sstride, int tilesX, int tw, int th, int clipLimit,
-                                                   float lutScale, uint8_t *lut) {
-  __shared__ uint32_t hist[256];
-  __shared__ int part[4];
-  const int t = threadIdx.x, tile = blockIdx.x, tx = tile % tilesX, ty = tile / tilesX;
-  hist[t] = 0;
-  __syncthreads();
-  const int x0 = tx * tw, y0 = ty * th;
-  for (int i = t; i < tw * th; i += 256) {
-    int y = y0 + i / tw, x = x0 + i % tw;
-    if (y >= rows) y = 2 * (rows - 1) - y;   // BORDER_REFLECT_101, the extension is narrower than the image
-    if (x >= cols) x = 2 * (cols - 1) - x;
-    atomicAdd(&hist[src[(size_t)y * sstride + x]], 1u);
-  }
-  __syncthreads();
-  int v = (int)hist[t];
+// clahe_lut_entry: bin t's histogram count v -> its LUT byte (clip, redistribution, inclusive scan, lutScale rounding).  Called by all
+// 256 threads of a workgroup; hist[256] and part[4] are its LDS scratch (hist may still be read by others on entry).
+__device__ __forceinline__ uint8_t clahe_lut_entry(int v, int t, int clipLimit, float lutScale, uint32_t *hist, int *part) {
   if (clipLimit > 0) {
     int excess = v > clipLimit ? v - clipLimit : 0;
     if (v > clipLimit) v = clipLimit;
@@ -1802,7 +1788,53 @@ __global__ __launch_bounds__(256) void k_clahe_lut(const uint8_t *src, int rows,
     __syncthreads();
   }
   const int r = __float2int_rn(__fmul_rn((float)(int)hist[t], lutScale));
-  lut[(size_t)tile * 256 + t] = (uint8_t)min(max(r, 0), 255);
+  return (uint8_t)min(max(r, 0), 255);
+}
+
+// k_clahe_lut: one workgroup per tile, thread b owns histogram bin b.
+__global__ __launch_bounds__(256) void k_clahe_lut(const uint8_t *src, int rows, int cols, size_t sstride, int tilesX, int tw, int th, int clipLimit,
+                                                   float lutScale, uint8_t *lut) {
+  __shared__ uint32_t hist[256];
+  __shared__ int part[4];
+  const int t = threadIdx.x, tile = blockIdx.x, tx = tile % tilesX, ty = tile / tilesX;
+  hist[t] = 0;
+  __syncthreads();
+  const int x0 = tx * tw, y0 = ty * th;
+  for (int i = t; i < tw * th; i += 256) {
+    int y = y0 + i / tw, x = x0 + i % tw;
+    if (y >= rows) y = 2 * (rows - 1) - y;   // BORDER_REFLECT_101, the extension is narrower than the image
+    if (x >= cols) x = 2 * (cols - 1) - x;
+    atomicAdd(&hist[src[(size_t)y * sstride + x]], 1u);
+  }
+  __syncthreads();
+  lut[(size_t)tile * 256 + t] = clahe_lut_entry((int)hist[t], t, clipLimit, lutScale, hist, part);
+}
+
+// Tile coordinate of pixel index v along one axis (clahe.cpp, CLAHE_Interpolation_Body): t1 / t2 the two neighbouring tiles
+// (clamped), a / a1 the weights of t2 / t1.  Every product and sum is rounded on its own.  Host and device: the launch code sizes
+// the staged part of the table with it.
+__host__ __device__ __forceinline__ void clahe_tile_coord(int v, float inv_t, int ntiles, int &t1, int &t2, float &a, float &a1) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const float tf = __fsub_rn(__fmul_rn((float)v, inv_t), 0.5f);
+  t1 = (int)floorf(tf);
+  a = __fsub_rn(tf, (float)t1);
+  a1 = __fsub_rn(1.0f, a);
+#else
+  const float tf = (float)v * inv_t - 0.5f;
+  t1 = (int)floorf(tf);
+  a = tf - (float)t1;
+  a1 = 1.0f - a;
+#endif
+  t2 = t1 + 1 < ntiles - 1 ? t1 + 1 : ntiles - 1;
+  t1 = t1 > 0 ? t1 : 0;
+}
+
+// The blend of the four tables' entries for one pixel: p1 / p2 the table rows of ty1 / ty2, i1 / i2 = tx1 * 256 + value, tx2 * 256 + value.
+__device__ __forceinline__ uint32_t clahe_blend(const uint8_t *p1, const uint8_t *p2, int i1, int i2, float xa, float xa1, float ya, float ya1) {
+  const float top = __fadd_rn(__fmul_rn((float)p1[i1], xa1), __fmul_rn((float)p1[i2], xa));
+  const float bot = __fadd_rn(__fmul_rn((float)p2[i1], xa1), __fmul_rn((float)p2[i2], xa));
+  const float res = __fadd_rn(__fmul_rn(top, ya1), __fmul_rn(bot, ya));
+  return (uint32_t)min(max(__float2int_rn(res), 0), 255);
 }
 
 // k_clahe_interp: the whole LUT (tilesX*tilesY*256 bytes, 16 KB for 8x8) sits in LDS; four pixels per thread.
@@ -1817,11 +1849,9 @@ __global__ __launch_bounds__(256) void k_clahe_interp(const uint8_t *src, int ro
   const int nq = (cols + 3) >> 2;
   for (int i = threadIdx.x; i < (ye - yb) * nq; i += 256) {
     const int y = yb + i / nq, xq = (i % nq) * 4;
-    const float tyf = __fsub_rn(__fmul_rn((float)y, inv_th), 0.5f);
-    int ty1 = (int)floorf(tyf);
-    const float ya = __fsub_rn(tyf, (float)ty1), ya1 = __fsub_rn(1.0f, ya);
-    const int ty2 = min(ty1 + 1, tilesY - 1);
-    ty1 = max(ty1, 0);
+    int ty1, ty2;
+    float ya, ya1;
+    clahe_tile_coord(y, inv_th, tilesY, ty1, ty2, ya, ya1);
     const uint8_t *p1 = sLut + ty1 * tilesX * 256, *p2 = sLut + ty2 * tilesX * 256;
     const uint8_t *srow = src + (size_t)y * sstride;
     uint8_t *drow = dst + (size_t)y * dstride;
@@ -1829,17 +1859,11 @@ __global__ __launch_bounds__(256) void k_clahe_interp(const uint8_t *src, int ro
     uint32_t packed = 0;
     for (int j = 0; j < n; j++) {
       const int x = xq + j;
-      const float txf = __fsub_rn(__fmul_rn((float)x, inv_tw), 0.5f);
-      int tx1 = (int)floorf(txf);
-      const float xa = __fsub_rn(txf, (float)tx1), xa1 = __fsub_rn(1.0f, xa);
-      const int tx2 = min(tx1 + 1, tilesX - 1);
-      tx1 = max(tx1, 0);
+      int tx1, tx2;
+      float xa, xa1;
+      clahe_tile_coord(x, inv_tw, tilesX, tx1, tx2, xa, xa1);
       const int sv = srow[x];
-      const int i1 = tx1 * 256 + sv, i2 = tx2 * 256 + sv;
-      const float top = __fadd_rn(__fmul_rn((float)p1[i1], xa1), __fmul_rn((float)p1[i2], xa));
-      const float bot = __fadd_rn(__fmul_rn((float)p2[i1], xa1), __fmul_rn((float)p2[i2], xa));
-      const float res = __fadd_rn(__fmul_rn(top, ya1), __fmul_rn(bot, ya));
-      packed |= (uint32_t)min(max(__float2int_rn(res), 0), 255) << (8 * j);
+      packed |= clahe_blend(p1, p2, tx1 * 256 + sv, tx2 * 256 + sv, xa, xa1, ya, ya1) << (8 * j);
     }
     if (n == 4 && ((((uintptr_t)dst) | dstride) & 3u) == 0) *reinterpret_cast<uint32_t *>(drow + xq) = packed;
     else for (int j = 0; j < n; j++) drow[xq + j] = (uint8_t)(packed >> (8 * j));
@@ -1852,18 +1876,224 @@ __global__ __launch_bounds__(256) void k_clahe_interp(const uint8_t *src, int ro
 // 15-bit fixed-point products -- for the linear kernel exactly 32 * (32-fx|fx) * (32-fy|fy); the one saturated entry of the table
 // (fx = fy = 0: {32767, 0, 0, 1} after its correction step) yields the same pixel as {32768, 0, 0, 0} for 8-bit taps -- and rounds
 // with (sum + (1 << 14)) >> 15.  A tap outside the source contributes the border value.
-__global__ __launch_bounds__(256) void k_remap_linear(const uint8_t *src, int srows, int scols, size_t sstride, const float *mapx, const float *mapy,
-                                                      size_t mstride, int rows, int cols, uint8_t *dst, size_t dstride) {
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= cols || y >= rows) return;
-  const float mx = mapx[(size_t)y * mstride + x], my = mapy[(size_t)y * mstride + x];
+struct RemapEntry {
+  int ix, iy;               // top-left tap, saturate_cast<short>
+  int w00, w01, w10, w11;   // 15-bit weights of the taps (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1)
+};
+
+__device__ __forceinline__ RemapEntry remap_decode(float mx, float my) {
   // cvRound = cvtss2si: out-of-range and NaN inputs give INT_MIN there; __float2int_rn saturates, NaN is patched to match
   const int sx = (mx != mx || fabsf(mx) >= 67108864.0f) ? INT_MIN : __float2int_rn(__fmul_rn(mx, 32.0f));
   const int sy = (my != my || fabsf(my) >= 67108864.0f) ? INT_MIN : __float2int_rn(__fmul_rn(my, 32.0f));
   const int fx = sx & 31, fy = sy & 31;
-  const int ix = min(max(sx >> 5, -32768), 32767), iy = min(max(sy >> 5, -32768), 32767);   // saturate_cast<short>
+  RemapEntry e;
+  e.ix = min(max(sx >> 5, -32768), 32767);   // saturate_cast<short>
+  e.iy = min(max(sy >> 5, -32768), 32767);
+  e.w00 = 32 * (32 - fx) * (32 - fy); e.w01 = 32 * fx * (32 - fy); e.w10 = 32 * (32 - fx) * fy; e.w11 = 32 * fx * fy;
+  return e;
+}
+
+__global__ __launch_bounds__(256) void k_remap_linear(const uint8_t *src, int srows, int scols, size_t sstride, const float *mapx, const float *mapy,
+                                                      size_t mstride, int rows, int cols, uint8_t *dst, size_t dstride) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= cols || y >= rows) return;
+  const RemapEntry e = remap_decode(mapx[(size_t)y * mstride + x], mapy[(size_t)y * mstride + x]);
   auto tap = [&](int yy, int xx) -> int { return ((unsigned)xx < (unsigned)scols && (unsigned)yy < (unsigned)srows) ? src[(size_t)yy * sstride + xx] : 0; };
-  const int w00 = 32 * (32 - fx) * (32 - fy), w01 = 32 * fx * (32 - fy), w10 = 32 * (32 - fx) * fy, w11 = 32 * fx * fy;
-  const int acc = tap(iy, ix) * w00 + tap(iy, ix + 1) * w01 + tap(iy + 1, ix) * w10 + tap(iy + 1, ix + 1) * w11;
+  const int acc = tap(e.iy, e.ix) * e.w00 + tap(e.iy, e.ix + 1) * e.w01 + tap(e.iy + 1, e.ix) * e.w10 + tap(e.iy + 1, e.ix + 1) * e.w11;
   dst[(size_t)y * dstride + x] = (uint8_t)((acc + (1 << 14)) >> 15);
+}
+
+// ---- CLAHE and remap for a batch of resident frames (orbx_clahe_batch_device, orbx_remap_linear_batch_device) ----
+// Same expressions as the three kernels above (clahe_lut_entry, clahe_tile_coord, clahe_blend, remap_decode), so the same bytes.
+#ifndef CLAHE_BAND_ROWS
+#define CLAHE_BAND_ROWS ORBX_CLAHE_BAND_ROWS
+#endif
+#ifndef REMAP_FRAME_CHUNK
+#define REMAP_FRAME_CHUNK ORBX_REMAP_FRAME_CHUNK
+#endif
+#ifndef CLAHE_SUBHIST
+#define CLAHE_SUBHIST 8   // sub-histograms of k_clahe_lut_batch: a multiple of its 4 wavefronts; with 8, even and odd lanes of a wavefront have their own
+#endif
+
+struct ClaheBatch {
+  const uint8_t *src;
+  uint8_t *dst, *lut;
+  size_t sstride, sframe, dstride, dframe;
+  int nframes, rows, cols, tilesX, tilesY, tw, th, clipLimit;
+  float lutScale, inv_tw, inv_th;
+};
+
+// The table rows (tile rows) the image rows y0 .. y1 read in the blend: ty1 of y0 through ty2 of y1, both clamped as the blend clamps
+// them.  ty1 does not decrease with y (a float product with a positive constant, a float difference and floor are all monotone).
+__host__ __device__ __forceinline__ void clahe_band_lut_rows(int y0, int y1, float inv_th, int tilesY, int &first, int &count) {
+  int a1, a2, b1, b2;
+  float w, w1;
+  clahe_tile_coord(y0, inv_th, tilesY, a1, a2, w, w1);
+  clahe_tile_coord(y1, inv_th, tilesY, b1, b2, w, w1);
+  first = a1;
+  count = b2 - a1 + 1;
+}
+
+// k_clahe_lut_batch: grid (tile, frame), thread b owns bin b.  The part of the tile inside the image is read as aligned dwords with
+// bytes at the two ends of a row; the columns of the reflect-101 extension (last tile columns only) have a loop of their own, the
+// rows of the extension are a row index.  CLAHE_SUBHIST sub-histograms (each wavefront has its own), merged before the clip.
+__global__ __launch_bounds__(256) void k_clahe_lut_batch(ClaheBatch P) {
+  __shared__ uint32_t hist[CLAHE_SUBHIST][256];
+  __shared__ int part[4];
+  const int t = threadIdx.x, tile = blockIdx.x, tx = tile % P.tilesX, ty = tile / P.tilesX;
+  const int x0 = tx * P.tw, y0 = ty * P.th;
+  const int w = max(0, min(P.tw, P.cols - x0)), ext = P.tw - w;   // columns inside the image, columns of the extension
+  const int nslot = ((w + 3) >> 2) + 1;                           // dword slots that cover a row of w bytes at any alignment
+  uint32_t *h = hist[(t >> 6) * (CLAHE_SUBHIST / 4) + (t & (CLAHE_SUBHIST / 4 - 1))];
+  for (int f = blockIdx.y; f < P.nframes; f += gridDim.y) {
+    const uint8_t *base = P.src + (size_t)f * P.sframe;
+    for (int k = 0; k < CLAHE_SUBHIST; k++) hist[k][t] = 0;
+    __syncthreads();
+    if (w > 0) {
+      for (int i = t; i < P.th * nslot; i += 256) {
+        const int r = i / nslot, k = i - r * nslot;
+        int y = y0 + r;
+        if (y >= P.rows) y = 2 * (P.rows - 1) - y;   // BORDER_REFLECT_101, the extension is narrower than the image
+        const uint8_t *row = base + (size_t)y * P.sstride + x0;
+        const int b = 4 * k - (int)((uintptr_t)row & 3u);   // first byte of this slot, relative to the row start
+        if (b >= w) continue;
+        if (b >= 0 && b + 4 <= w) {
+          const uint32_t v = *reinterpret_cast<const uint32_t *>(row + b);
+          atomicAdd(&h[v & 255u], 1u);
+          atomicAdd(&h[(v >> 8) & 255u], 1u);
+          atomicAdd(&h[(v >> 16) & 255u], 1u);
+          atomicAdd(&h[v >> 24], 1u);
+        } else {
+          for (int j = max(b, 0); j < min(b + 4, w); j++) atomicAdd(&h[row[j]], 1u);
+        }
+      }
+    }
+    for (int i = t; i < P.th * ext; i += 256) {
+      int y = y0 + i / ext;
+      const int x = 2 * (P.cols - 1) - (x0 + w + i % ext);
+      if (y >= P.rows) y = 2 * (P.rows - 1) - y;
+      atomicAdd(&h[base[(size_t)y * P.sstride + x]], 1u);
+    }
+    __syncthreads();
+    uint32_t v = 0;
+    for (int k = 0; k < CLAHE_SUBHIST; k++) v += hist[k][t];
+    P.lut[((size_t)f * P.tilesX * P.tilesY + tile) * 256 + t] = clahe_lut_entry((int)v, t, P.clipLimit, P.lutScale, hist[0], part);
+    __syncthreads();
+  }
+}
+
+// k_clahe_interp_batch: grid (band of CLAHE_BAND_ROWS rows, frame).  Only the table rows the band reads are staged in LDS
+// (clahe_band_lut_rows: two inside a tile row, more when the tiles are shorter than the band).  A thread owns a quad of four columns
+// and walks down the band: the column terms are computed once per quad, the row terms once per row.  With fewer quads than threads
+// the threads split into row phases.
+__global__ __launch_bounds__(256) void k_clahe_interp_batch(ClaheBatch P) {
+  extern __shared__ uint8_t sLut[];
+  const int yb = blockIdx.x * CLAHE_BAND_ROWS, ye = min(yb + CLAHE_BAND_ROWS, P.rows);
+  int first, count;
+  clahe_band_lut_rows(yb, ye - 1, P.inv_th, P.tilesY, first, count);
+  const int rowBytes = P.tilesX * 256, nstage = count * rowBytes;
+  const int nq = (P.cols + 3) >> 2, T = (int)blockDim.x;
+  const int qstep = nq >= T ? T : nq, nphase = nq >= T ? 1 : T / nq;
+  const int phase = (int)threadIdx.x / qstep, q0 = (int)threadIdx.x - phase * qstep;
+  for (int f = blockIdx.y; f < P.nframes; f += gridDim.y) {
+    const uint8_t *lut = P.lut + ((size_t)f * P.tilesY + first) * rowBytes;
+    if (((uintptr_t)P.lut & 3u) == 0)
+      for (int i = threadIdx.x * 4; i < nstage; i += 4 * T) *reinterpret_cast<uint32_t *>(sLut + i) = *reinterpret_cast<const uint32_t *>(lut + i);
+    else
+      for (int i = threadIdx.x; i < nstage; i += T) sLut[i] = lut[i];
+    __syncthreads();
+    const uint8_t *sbase = P.src + (size_t)f * P.sframe;
+    uint8_t *dbase = P.dst + (size_t)f * P.dframe;
+    const bool salign = ((((uintptr_t)sbase) | P.sstride) & 3u) == 0, dalign = ((((uintptr_t)dbase) | P.dstride) & 3u) == 0;
+    if (phase < nphase) {
+      for (int q = q0; q < nq; q += qstep) {
+        const int xq = 4 * q, n = min(4, P.cols - xq);
+        int o1[4], o2[4];
+        float xa[4], xa1[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          int tx1, tx2;
+          clahe_tile_coord(xq + j, P.inv_tw, P.tilesX, tx1, tx2, xa[j], xa1[j]);
+          o1[j] = tx1 * 256;
+          o2[j] = tx2 * 256;
+        }
+        for (int y = yb + phase; y < ye; y += nphase) {
+          int ty1, ty2;
+          float ya, ya1;
+          clahe_tile_coord(y, P.inv_th, P.tilesY, ty1, ty2, ya, ya1);
+          const uint8_t *p1 = sLut + (ty1 - first) * rowBytes, *p2 = sLut + (ty2 - first) * rowBytes;
+          const uint8_t *s = sbase + (size_t)y * P.sstride + xq;
+          uint8_t *d = dbase + (size_t)y * P.dstride + xq;
+          uint32_t sv = 0;
+          if (n == 4 && salign) sv = *reinterpret_cast<const uint32_t *>(s);
+          else for (int j = 0; j < n; j++) sv |= (uint32_t)s[j] << (8 * j);
+          uint32_t packed = 0;
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            const int v = (int)((sv >> (8 * j)) & 255u);
+            if (j < n) packed |= clahe_blend(p1, p2, o1[j] + v, o2[j] + v, xa[j], xa1[j], ya, ya1) << (8 * j);
+          }
+          if (n == 4 && dalign) *reinterpret_cast<uint32_t *>(d) = packed;
+          else for (int j = 0; j < n; j++) d[j] = (uint8_t)(packed >> (8 * j));
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+struct RemapBatch {
+  const uint8_t *src;
+  uint8_t *dst;
+  const float *mapx, *mapy;
+  size_t sstride, sframe, mstride, dstride, dframe;
+  int nframes, srows, scols, rows, cols;
+};
+
+// k_remap_linear_batch: one map pair for all frames.  grid (256-pixel run, row, chunk of REMAP_FRAME_CHUNK frames): a thread decodes
+// the map entry of its output pixel once and then does only the taps, the sum and the store for every frame of the chunk.  A tap
+// outside the source gets weight 0, which gives the sum the border value 0 gives.  PAIR (sources of two columns or more): the two taps
+// of a source row come from ONE 16-bit load at the column pair [ixc, ixc + 1], ixc = ix clamped to [0, scols - 2], so both bytes lie
+// inside the row whatever ix is; a tap in range is byte ix - ixc or ix + 1 - ixc of it (0 or 1), a row out of range reads row 0.  The
+// load has byte alignment (the packed struct says so); gfx950 takes it as one global_load_ushort.  Without PAIR: four byte loads.
+struct __attribute__((packed)) RemapPair { uint16_t v; };
+
+template <bool PAIR>
+__global__ __launch_bounds__(256) void k_remap_linear_batch(RemapBatch P) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= P.cols) return;
+  const RemapEntry e = remap_decode(P.mapx[(size_t)y * P.mstride + x], P.mapy[(size_t)y * P.mstride + x]);
+  const bool x0in = (unsigned)e.ix < (unsigned)P.scols, x1in = (unsigned)(e.ix + 1) < (unsigned)P.scols;
+  const bool y0in = (unsigned)e.iy < (unsigned)P.srows, y1in = (unsigned)(e.iy + 1) < (unsigned)P.srows;
+  const int w00 = x0in && y0in ? e.w00 : 0, w01 = x1in && y0in ? e.w01 : 0, w10 = x0in && y1in ? e.w10 : 0, w11 = x1in && y1in ? e.w11 : 0;
+  const ptrdiff_t down = (ptrdiff_t)P.sstride;
+  const size_t dpix = (size_t)y * P.dstride + x;
+  const int nchunks = (P.nframes + REMAP_FRAME_CHUNK - 1) / REMAP_FRAME_CHUNK;
+  if constexpr (PAIR) {
+    const int ixc = min(max(e.ix, 0), P.scols - 2);
+    const ptrdiff_t oT = (y0in ? (ptrdiff_t)e.iy * down : 0) + ixc, oB = (y1in ? (ptrdiff_t)(e.iy + 1) * down : 0) + ixc;
+    const int sh0 = x0in ? 8 * (e.ix - ixc) : 0, sh1 = x1in ? 8 * (e.ix + 1 - ixc) : 0;
+    for (int c = blockIdx.z; c < nchunks; c += gridDim.z) {
+      const int f1 = min((c + 1) * REMAP_FRAME_CHUNK, P.nframes);
+#pragma unroll 4
+      for (int f = c * REMAP_FRAME_CHUNK; f < f1; f++) {
+        const uint8_t *s = P.src + (size_t)f * P.sframe;
+        const uint32_t vT = reinterpret_cast<const RemapPair *>(s + oT)->v, vB = reinterpret_cast<const RemapPair *>(s + oB)->v;
+        const int acc = (int)((vT >> sh0) & 255u) * w00 + (int)((vT >> sh1) & 255u) * w01 + (int)((vB >> sh0) & 255u) * w10 + (int)((vB >> sh1) & 255u) * w11;
+        P.dst[(size_t)f * P.dframe + dpix] = (uint8_t)((acc + (1 << 14)) >> 15);
+      }
+    }
+  } else {
+    const ptrdiff_t off = (ptrdiff_t)e.iy * down + e.ix;
+    const ptrdiff_t o00 = x0in && y0in ? off : 0, o01 = x1in && y0in ? off + 1 : 0, o10 = x0in && y1in ? off + down : 0, o11 = x1in && y1in ? off + down + 1 : 0;
+    for (int c = blockIdx.z; c < nchunks; c += gridDim.z) {
+      const int f1 = min((c + 1) * REMAP_FRAME_CHUNK, P.nframes);
+#pragma unroll 4
+      for (int f = c * REMAP_FRAME_CHUNK; f < f1; f++) {
+        const uint8_t *s = P.src + (size_t)f * P.sframe;
+        const int acc = (int)s[o00] * w00 + (int)s[o01] * w01 + (int)s[o10] * w10 + (int)s[o11] * w11;
+        P.dst[(size_t)f * P.dframe + dpix] = (uint8_t)((acc + (1 << 14)) >> 15);
+      }
+    }
+  }
 }

@@ -967,6 +967,95 @@ int orbx_remap_linear(orbx_t *h, const uint8_t *src, int src_rows, int src_cols,
   return 0;
 }
 
+// Tile size of the (possibly extended) image, lutScale and the integer clip limit of CLAHE_Impl::apply, as orbx_clahe_device has them.
+static void clahe_batch_geometry(ClaheBatch &P, double clip_limit) {
+  const int ecols = P.cols % P.tilesX == 0 ? P.cols : P.cols + P.tilesX - P.cols % P.tilesX;
+  const int erows = P.rows % P.tilesY == 0 ? P.rows : P.rows + P.tilesY - P.rows % P.tilesY;
+  P.tw = ecols / P.tilesX;
+  P.th = erows / P.tilesY;
+  const int tileSizeTotal = P.tw * P.th;
+  P.lutScale = (float)255 / (float)tileSizeTotal;
+  P.clipLimit = 0;
+  if (clip_limit > 0.0) {
+    P.clipLimit = (int)(clip_limit * tileSizeTotal / 256);
+    if (P.clipLimit < 1) P.clipLimit = 1;
+  }
+  P.inv_tw = 1.0f / (float)P.tw;
+  P.inv_th = 1.0f / (float)P.th;
+}
+
+// Bytes from the first byte of frame 0 to one past the last byte of the last frame.
+static size_t batch_extent(int nframes, int rows, int cols, size_t stride, size_t frame_stride) {
+  return (size_t)(nframes - 1) * frame_stride + (size_t)(rows - 1) * stride + (size_t)cols;
+}
+
+static bool ranges_intersect(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+
+int orbx_clahe_band_lut_rows(int rows, int tiles_y, int y0, int y1, int *first, int *count) {
+  if (!first || !count || tiles_y <= 0 || rows < tiles_y || y0 < 0 || y1 < y0 || y1 >= rows) return ORBX_E_ARG;
+  const int erows = rows % tiles_y == 0 ? rows : rows + tiles_y - rows % tiles_y;
+  clahe_band_lut_rows(y0, y1, 1.0f / (float)(erows / tiles_y), tiles_y, *first, *count);
+  return 0;
+}
+
+int orbx_clahe_batch_device(int nframes, const uint8_t *d_src, int rows, int cols, size_t src_stride, size_t src_frame_stride, double clip_limit,
+                            int tiles_x, int tiles_y, uint8_t *d_lut, uint8_t *d_dst, size_t dst_stride, size_t dst_frame_stride, void *stream) {
+  if (!d_src || !d_dst || !d_lut || nframes < 0 || rows <= 0 || cols <= 0 || tiles_x <= 0 || tiles_y <= 0 || tiles_x * tiles_y > 256 || cols < tiles_x ||
+      rows < tiles_y || src_stride < (size_t)cols || dst_stride < (size_t)cols || !(clip_limit >= 0.0))
+    return ORBX_E_ARG;
+  if (nframes > 1 && (src_frame_stride < batch_extent(1, rows, cols, src_stride, 0) || dst_frame_stride < batch_extent(1, rows, cols, dst_stride, 0)))
+    return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  const bool in_place = d_dst == d_src && dst_stride == src_stride && (nframes == 1 || dst_frame_stride == src_frame_stride);
+  if (!in_place && ranges_intersect(d_src, batch_extent(nframes, rows, cols, src_stride, src_frame_stride), d_dst,
+                                    batch_extent(nframes, rows, cols, dst_stride, dst_frame_stride)))
+    return ORBX_E_ARG;
+  ClaheBatch P;
+  P.src = d_src; P.dst = d_dst; P.lut = d_lut;
+  P.sstride = src_stride; P.sframe = src_frame_stride; P.dstride = dst_stride; P.dframe = dst_frame_stride;
+  P.nframes = nframes; P.rows = rows; P.cols = cols; P.tilesX = tiles_x; P.tilesY = tiles_y;
+  clahe_batch_geometry(P, clip_limit);
+  const int nbands = (rows + CLAHE_BAND_ROWS - 1) / CLAHE_BAND_ROWS, gridF = std::min(nframes, 65535);
+  int maxRows = 0;   // the most table rows any band stages
+  for (int b = 0; b < nbands; b++) {
+    int first, count;
+    clahe_band_lut_rows(b * CLAHE_BAND_ROWS, std::min((b + 1) * CLAHE_BAND_ROWS, rows) - 1, P.inv_th, tiles_y, first, count);
+    maxRows = std::max(maxRows, count);
+  }
+  // threads of the blend: one per column quad, the rest of the workgroup as row phases, whole wavefronts
+  const int nq = (cols + 3) / 4;
+  const int threads = nq >= 256 ? 256 : std::min(256, (nq * (256 / nq) + 63) / 64 * 64);
+  hipLaunchKernelGGL(k_clahe_lut_batch, dim3(tiles_x * tiles_y, gridF), dim3(256), 0, (hipStream_t)stream, P);
+  hipLaunchKernelGGL(k_clahe_interp_batch, dim3(nbands, gridF), dim3(threads), (size_t)maxRows * tiles_x * 256, (hipStream_t)stream, P);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
+int orbx_remap_linear_batch_device(int nframes, const uint8_t *d_src, int src_rows, int src_cols, size_t src_stride, size_t src_frame_stride,
+                                   const float *d_mapx, const float *d_mapy, size_t map_stride_elems, int rows, int cols, uint8_t *d_dst,
+                                   size_t dst_stride, size_t dst_frame_stride, void *stream) {
+  if (!d_src || !d_mapx || !d_mapy || !d_dst || nframes < 0 || src_rows <= 0 || src_cols <= 0 || rows <= 0 || cols <= 0 || src_stride < (size_t)src_cols ||
+      map_stride_elems < (size_t)cols || dst_stride < (size_t)cols || src_cols > 32767 || src_rows > 32767 || rows > 65535)
+    return ORBX_E_ARG;
+  if (nframes > 1 && (src_frame_stride < batch_extent(1, src_rows, src_cols, src_stride, 0) || dst_frame_stride < batch_extent(1, rows, cols, dst_stride, 0)))
+    return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  if (ranges_intersect(d_src, batch_extent(nframes, src_rows, src_cols, src_stride, src_frame_stride), d_dst,
+                       batch_extent(nframes, rows, cols, dst_stride, dst_frame_stride)))
+    return ORBX_E_ARG;
+  RemapBatch P;
+  P.src = d_src; P.dst = d_dst; P.mapx = d_mapx; P.mapy = d_mapy;
+  P.sstride = src_stride; P.sframe = src_frame_stride; P.mstride = map_stride_elems; P.dstride = dst_stride; P.dframe = dst_frame_stride;
+  P.nframes = nframes; P.srows = src_rows; P.scols = src_cols; P.rows = rows; P.cols = cols;
+  const int nchunks = (nframes + REMAP_FRAME_CHUNK - 1) / REMAP_FRAME_CHUNK;
+  const dim3 grid((cols + 255) / 256, rows, std::min(nchunks, 65535));
+  if (src_cols >= 2) hipLaunchKernelGGL(k_remap_linear_batch<true>, grid, dim3(256), 0, (hipStream_t)stream, P);
+  else hipLaunchKernelGGL(k_remap_linear_batch<false>, grid, dim3(256), 0, (hipStream_t)stream, P);   // no column pair in a one-column source
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
 int orbx_level_info(const orbx_t *h, int level, int *rows, int *cols) {
   if (!h || level < 0 || level >= h->nlevels || h->geom.empty()) return ORBX_E_ARG;
   if (rows) *rows = h->geom[level].h;

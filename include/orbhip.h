@@ -164,6 +164,34 @@ int orbx_remap_linear_device(const uint8_t *d_src, int src_rows, int src_cols, s
 int orbx_remap_linear(orbx_t *h, const uint8_t *src, int src_rows, int src_cols, size_t src_stride, const float *mapx, const float *mapy, int rows,
                       int cols, uint8_t *dst, size_t dst_stride);
 
+/* orbx_clahe_device / orbx_remap_linear_device for `nframes` frames resident in HBM, one call per batch.  No handle: device
+ * pointers, asynchronous on `stream`, no host synchronisation, copy or allocation.  Frame f is at d_src + f * src_frame_stride, its
+ * result goes to d_dst + f * dst_frame_stride; per frame the bytes are those of the per-image call.  Bytes of d_dst outside the
+ * rows x cols of each frame (row padding, padding between frames) are not written.  nframes == 0 returns 0 and launches nothing.
+ *
+ * orbx_clahe_batch_device: d_lut is nframes * tiles_x * tiles_y * 256 bytes of device scratch.  In place (d_dst == d_src with equal
+ * row and frame strides, as the examples do) is allowed.  Two kernels: the tables of all tiles of all frames (grid tile x frame,
+ * one sub-histogram per wavefront), then the blend in bands of ORBX_CLAHE_BAND_ROWS image rows (grid band x frame) that stage only
+ * the table rows a band reads.  ORBX_E_ARG: what orbx_clahe_device refuses, nframes < 0, for nframes > 1 a frame stride smaller than
+ * (rows - 1) * stride + cols, and source and destination ranges that intersect in any way other than the in-place form.
+ *
+ * orbx_remap_linear_batch_device: one map pair serves all frames (it is fixed per camera).  One kernel: a thread decodes the map
+ * entry of its output pixel once and applies it to ORBX_REMAP_FRAME_CHUNK frames.  ORBX_E_ARG: what orbx_remap_linear_device
+ * refuses, nframes < 0, for nframes > 1 a frame stride smaller than (rows - 1) * stride + cols of its side, and a destination range
+ * that intersects the source range (cv::remap goes through a temporary when called in place; this call has none).
+ * Both return 0, ORBX_E_ARG or ORBX_E_HIP. */
+#define ORBX_CLAHE_BAND_ROWS 32
+#define ORBX_REMAP_FRAME_CHUNK 16
+int orbx_clahe_batch_device(int nframes, const uint8_t *d_src, int rows, int cols, size_t src_stride, size_t src_frame_stride, double clip_limit,
+                            int tiles_x, int tiles_y, uint8_t *d_lut, uint8_t *d_dst, size_t dst_stride, size_t dst_frame_stride, void *stream);
+int orbx_remap_linear_batch_device(int nframes, const uint8_t *d_src, int src_rows, int src_cols, size_t src_stride, size_t src_frame_stride,
+                                   const float *d_mapx, const float *d_mapy, size_t map_stride_elems, int rows, int cols, uint8_t *d_dst,
+                                   size_t dst_stride, size_t dst_frame_stride, void *stream);
+/* Host arithmetic of the launch code above, exposed for tests/test_preops_batch_abi.py: the table rows (tile rows) the blend reads for
+ * the image rows y0 .. y1 of a rows-high image with tiles_y tile rows: *first, *count.  ORBX_E_ARG unless 0 <= y0 <= y1 < rows,
+ * 0 < tiles_y <= rows and both pointers are given.  Returns 0. */
+int orbx_clahe_band_lut_rows(int rows, int tiles_y, int y0, int y1, int *first, int *count);
+
 /* void Frame::ComputeStereoMatches()  (Frame.cc:901-1079), rectified stereo - the consumer of mvImagePyramid.
  * left / right: the two extractors (mpORBextractorLeft / Right) AFTER orbx_extract / orbx_extract_batch_device of the
  * two images: their pyramids are still on the device (frame_l / frame_r = index in their last batch), so no image
