@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -69,6 +69,16 @@ class LocalMapStruct(C.Structure):  # orbm_local_map_t
 class TrackStruct(C.Structure):  # orbm_track_t
     _fields_ = [("in_view", C.c_void_p), ("proj_x", C.c_void_p), ("proj_y", C.c_void_p), ("proj_xr", C.c_void_p), ("depth", C.c_void_p),
                 ("view_cos", C.c_void_p), ("level", C.c_void_p)]
+
+
+class TrackRigStruct(C.Structure):  # orbm_track_rig_t
+    _fields_ = [(k, C.c_void_p) for k in ("in_view", "in_view_r", "proj_x", "proj_y", "depth", "view_cos", "proj_xr", "proj_yr", "depth_r",
+                                          "view_cos_r", "level", "level_r")]
+
+
+TRACK_RIG_FIELDS = (("in_view", np.uint8), ("in_view_r", np.uint8), ("proj_x", np.float32), ("proj_y", np.float32), ("depth", np.float32),
+                    ("view_cos", np.float32), ("proj_xr", np.float32), ("proj_yr", np.float32), ("depth_r", np.float32),
+                    ("view_cos_r", np.float32), ("level", np.int32), ("level_r", np.int32))
 
 
 class QueryStruct(C.Structure):  # orbm_queries_t
@@ -187,6 +197,12 @@ def load(build_if_needed=True):
     L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, f32, vp, i32, vp, f32, f32, f32, i32, f32, f32, vp, vp, vp, vp]
     L.orbm_search_local_points_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, f32, i32, vp, f32, f32, f32,
                                                         i32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.orbm_search_local_points_fisheye.argtypes = [vp, vp, i32, vp, vp, vp, i32, f32, vp, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, f32,
+                                                   vp, vp, vp, vp]
+    L.orbm_search_local_points_fisheye_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, i32, f32,
+                                                                vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.orbm_rig_right_camera.restype = None
+    L.orbm_rig_right_camera.argtypes = [vp, vp, vp, vp, vp]
     L.orbm_three_maxima.argtypes = [vp, i32, vp, vp, vp]
     L.orbm_radius_by_viewing_cos.restype = f32
     L.orbm_radius_by_viewing_cos.argtypes = [f32]
@@ -631,6 +647,43 @@ class ORBmatcher:
             raise OrbError("orbm_search_local_points rc=%d" % rc)
         return rc, moq, track
 
+    def SearchLocalPointsFisheye(self, CurrentFrame, n_left, left_to_right, right_to_left, scale_factors, log_scale_factor, eligible, Xw,
+                                 normal, max_dist, min_dist, mp_desc, Tcw, Trl, tlr, cam_type, cam_params, cam_type2, cam_params2, th,
+                                 bFarPoints=False, thFarPoints=0.0, viewing_cos_limit=0.5, mp_obs=None, track=None):
+        """Tracking::SearchLocalPoints for a fisheye-stereo frame (Nleft != -1): Frame::isInFrustumChecks per camera
+        (Frame.cc:650-660, :1270-1343), then both halves of SearchByProjection(Frame&, const vector<MapPoint*>&, ...)
+        (ORBmatcher.cc:44-214), on the device (orbm_search_local_points_fisheye).  CurrentFrame: FrameView over the raw keypoints
+        mvKeys ++ mvKeysRight / mDescriptors; left_to_right / right_to_left = mvLeftToRightMatch / mvRightToLeftMatch or None; Trl =
+        mTrl (3x4 or 4x4), tlr = mTlr.col(3); cam_type2 / cam_params2 = mpCamera2.  track: dict of the twelve arrays of
+        orbm_track_rig_t holding the MapPoints' current values (updated in place; depth is read by the far-point test where the left
+        check fails), default all 0.  Returns (nmatches, match_of_point[2 * nmp], track); slots written hold local-map indices."""
+        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
+        sf = a(scale_factors, np.float32)
+        elig, Xw, normal = a(eligible, np.uint8), a(Xw, np.float32), a(normal, np.float32)
+        max_dist, min_dist, mp_desc = a(max_dist, np.float32), a(min_dist, np.float32), a(mp_desc, np.uint8)
+        Tcw, cam_params, cam_params2 = a(Tcw, np.float32), a(cam_params, np.float32), a(cam_params2, np.float32)
+        Trl, tlr = a(Trl, np.float32).reshape(-1), a(tlr, np.float32).reshape(-1)
+        if Trl.size not in (12, 16) or tlr.size < 3:
+            raise ValueError("orbm_search_local_points_fisheye: Trl must hold 12 or 16 floats and tlr 3")
+        obs = None if mp_obs is None else a(mp_obs, np.uint8)
+        l2r = None if left_to_right is None else a(left_to_right, np.int32)
+        r2l = None if right_to_left is None else a(right_to_left, np.int32)
+        nmp = len(elig)
+        if track is None:
+            track = {k: np.zeros(nmp, t) for k, t in TRACK_RIG_FIELDS}
+        ts = TrackRigStruct(*[_p(track[k]) for k, _ in TRACK_RIG_FIELDS])
+        ms = LocalMapStruct(nmp, _p(elig), _p(Xw), _p(normal), _p(max_dist), _p(min_dist), _p(mp_desc), _p(obs), _p(Tcw))
+        mop = np.full(2 * nmp, -1, dtype=np.int32)
+        fs = CurrentFrame.struct()
+        rc = self.L.orbm_search_local_points_fisheye(self.m, C.byref(fs), int(n_left), _p(l2r), _p(r2l), _p(sf), len(sf), C.c_float(log_scale_factor),
+                                                     C.byref(ms), _p(Trl), _p(tlr), int(cam_type), _p(cam_params), int(cam_type2), _p(cam_params2),
+                                                     C.c_float(viewing_cos_limit), C.c_float(th), int(bool(bFarPoints)), C.c_float(thFarPoints),
+                                                     C.c_float(self.mfNNratio), _p(CurrentFrame.slot), _p(CurrentFrame.slot_obs), _p(mop), C.byref(ts))
+        self._check(rc, "orbm_search_local_points_fisheye")
+        if rc < 0:
+            raise OrbError("orbm_search_local_points_fisheye rc=%d" % rc)
+        return rc, mop, track
+
     def SearchByProjectionFisheye(self, F, n_left, left_to_right, right_to_left, mp_desc, scale_factors, th,
                                   in_view, projX, projY, viewCos, level, in_view_r, projXR, projYR, viewCosR, levelR, mp_obs=None):
         """SearchByProjection(Frame &F, const vector<MapPoint*>&, th, ...) for a fisheye-stereo frame (Nleft != -1) --
@@ -931,6 +984,44 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_search_local_points_batch_device rc=%d" % rc)
 
+    def search_local_points_fisheye_batch_device(self, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride, d_left_to_right,
+                                                 d_right_to_left, map0, map_stride, d_map_n, map_n_stride, npairs, scale_factors,
+                                                 log_scale_factor, Trl, tlr, cam_type, cam_params, cam_type2, cam_params2, th, d_slot, d_slot_obs,
+                                                 d_match_of_point, track0, d_nmatches, n_left=0, bFarPoints=False, thFarPoints=0.0,
+                                                 viewing_cos_limit=0.5, stream=None):
+        """Tracking::SearchLocalPoints for `npairs` (fisheye-stereo frame, local map) problems resident in HBM
+        (orbm_search_local_points_fisheye_batch_device).  cur0 / map0 / track0: FrameStruct / LocalMapStruct / TrackRigStruct of
+        problem 0 holding device addresses; the other pointers are device addresses (ints; d_frame_n / d_n_left / d_left_to_right /
+        d_right_to_left / d_map_n / d_match_of_point may be None, n_left is the constant Nleft when d_n_left is None); Trl, tlr,
+        scale_factors and both cam_params are host arrays; asynchronous on `stream`."""
+        a = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        sf, cam_params, cam_params2 = a(scale_factors), a(cam_params), a(cam_params2)
+        Trl, tlr = None if Trl is None else a(Trl), None if tlr is None else a(tlr)
+        what = "orbm_search_local_points_fisheye_batch_device: "
+        if Trl is None or tlr is None:
+            raise ValueError(what + "Trl or tlr is missing")
+        if Trl.size not in (12, 16) or tlr.size < 3:
+            raise ValueError(what + "Trl must hold 12 or 16 floats and tlr 3")
+        if npairs < 0 or not d_slot or not d_slot_obs or not d_nmatches:
+            raise ValueError(what + "npairs < 0 or a missing output")
+        if not 1 <= len(sf) <= 16 or any(int(t) not in (0, 1) or len(q) < (4 if int(t) == 0 else 8) for t, q in ((cam_type, cam_params), (cam_type2, cam_params2))):
+            raise ValueError(what + "nlevels outside [1, 16] or an unknown camera")
+        if not d_n_left and not 0 <= int(n_left) <= cur0.n:
+            raise ValueError(what + "n_left outside [0, N]")
+        if frame_stride > FISHEYE_MAX_KEYPOINTS:
+            raise ValueError(what + "frame_stride above %d" % FISHEYE_MAX_KEYPOINTS)
+        v = lambda x: C.c_void_p(x) if x else None
+        rc = self.L.orbm_search_local_points_fisheye_batch_device(
+            self.m, C.byref(cur0), int(frame_stride), v(d_frame_n), int(frame_n_stride), v(d_n_left), int(n_left_stride), int(n_left),
+            v(d_left_to_right), v(d_right_to_left), C.byref(map0), int(map_stride), v(d_map_n), int(map_n_stride), int(npairs), _p(sf), len(sf),
+            C.c_float(log_scale_factor), _p(Trl), _p(tlr), int(cam_type), _p(cam_params), int(cam_type2), _p(cam_params2),
+            C.c_float(viewing_cos_limit), C.c_float(th), int(bool(bFarPoints)), C.c_float(thFarPoints), C.c_float(self.mfNNratio), v(d_slot),
+            v(d_slot_obs), v(d_match_of_point), C.byref(track0), v(d_nmatches), v(stream))
+        self._check(rc, "orbm_search_local_points_fisheye_batch_device")
+        if rc < 0:
+            raise OrbError("orbm_search_local_points_fisheye_batch_device rc=%d" % rc)
+        return rc
+
     def search_by_projection_last_frame_fisheye_batch_device(self, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride,
                                                              last0, last_stride, d_last_n, last_n_stride, npairs, scale_factors, Trl,
                                                              cam_type, cam_params, th, d_slot, d_slot_obs, d_match_of_query, d_nmatches,
@@ -1008,6 +1099,14 @@ def project(cam_type, params, X, Y, Z):
     u, v = C.c_float(), C.c_float()
     load().orbm_project(int(cam_type), _p(params), C.c_float(X), C.c_float(Y), C.c_float(Z), C.byref(u), C.byref(v))
     return u.value, v.value
+
+
+def rig_right_camera(Tcw, Trl, tlr):
+    """The right camera of Frame::isInFrustumChecks (Frame.cc:1276-1280) as the kernels form it: ([mR | mt] as 3x4, twc)."""
+    a = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    Tr, twc = np.zeros(12, np.float32), np.zeros(3, np.float32)
+    load().orbm_rig_right_camera(_p(a(Tcw)), _p(a(Trl)), _p(a(tlr)), _p(Tr), _p(twc))
+    return Tr.reshape(3, 4), twc
 
 
 def _dp(a):

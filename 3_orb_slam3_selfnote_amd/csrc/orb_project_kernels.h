@@ -216,6 +216,153 @@ __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
   store_query(P.Q, o, u, v, rad, ur, minl, maxl, fl);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The same member for a fisheye-stereo frame (Frame::Nleft != -1): Frame::isInFrustum's else branch (Frame.cc:650-660), i.e.
+// Frame::isInFrustumChecks (Frame.cc:1270-1343) once per camera, then the query preparation of both halves of
+// SearchByProjection(Frame&, const vector<MapPoint*>&, th, bFarPoints, thFarPoints) (ORBmatcher.cc:44-73 left, :145-151 right).
+// Local map point i makes the queries 2i (left image) and 2i + 1 (right image), their side bytes and the doubled descriptor,
+// as k_lastframe_project_rig does; query_n[p] = 2 * the live count.  The launch also builds MatchParams::partner from the
+// frame's mvLeftToRightMatch / mvRightToLeftMatch (:132-133, :199-200).
+// ------------------------------------------------------------------------------------------------------------
+struct RigLocalParams {
+  float Trl[12], tlr[3];     // Frame::mTrl (row-major 3x4) and mTlr.col(3)
+  int cam_type2; float cam2[8];   // mpCamera2 (Frame.cc:1299)
+  const uint8_t *mpdesc;     // 32 bytes per local map point (16-byte aligned)
+  // out: the R fields of isInFrustumChecks (caller arrays, map stride); proj_xr is LocalMapParams::proj_xr
+  uint8_t *in_view_r; float *proj_yr, *depth_r, *view_cos_r; int32_t *level_r;
+  uint8_t *qdesc, *qside; int32_t *query_n;   // out, as RigProjectParams
+  // partner table: keypoint k < Nleft -> Nleft + l2r[k], k >= Nleft -> r2l[k - Nleft]; an entry outside the other image's live
+  // range counts as -1.  partner == NULL: none is built.
+  const int32_t *l2r, *r2l;  // [npairs][frame_stride], either may be NULL
+  int32_t *partner;          // out: [npairs][frame_stride]
+  int frame_stride;
+  const int32_t *frame_n; int frame_n_stride; int frame_n_const;
+  const int32_t *nleft_dev; int nleft_stride; int nleft_const;
+};
+
+// Frame::isInFrustumChecks (Frame.cc:1289-1325) for one camera: T = [mR | mt] (row stride 4), twc, the camera, point o.
+struct FrustumSide { bool ok; float u, v, depth, vcos; int level; };
+
+__device__ __forceinline__ FrustumSide frustum_side(const LocalMapParams &P, const float *T, const float *twc, int cam_type, const float *cam,
+                                                    const float *xw, size_t o) {
+  FrustumSide s = {false, 0.f, 0.f, 0.f, 0.f, -1};
+  const float t[3] = {T[3], T[7], T[11]};
+  float pc[3];
+  mat3_mul_add(T, xw, t, pc);                                     // Pc = mR*P + mt (:1289)
+  s.depth = norm3(pc);                                            // :1290
+  if (pc[2] < 0.0f) return s;                                     // :1294 (-0 and +0 pass)
+  project(cam_type, cam, pc[0], pc[1], pc[2], s.u, s.v);          // :1299-1300
+  if (!inside_bounds(s.u, s.v, P.V.min_x, P.V.max_x, P.V.min_y, P.V.max_y)) return s;   // :1302-1305; a NaN projection passes
+  const float po[3] = {xw[0] - twc[0], xw[1] - twc[1], xw[2] - twc[2]};
+  const float dist = norm3(po);                                   // :1311
+  if (outside_scale_range(dist, P.min_dist, P.max_dist, o)) return s;   // :1313
+  const float pn[3] = {P.normal[3 * o], P.normal[3 * o + 1], P.normal[3 * o + 2]};
+  s.vcos = (float)(dot3_double(po, pn) / (double)dist);           // :1319, Mat::dot in double
+  if (s.vcos < P.view_cos_limit) return s;                        // :1321
+  const float ratio = P.max_dist[o] / dist;                       // PredictScale, MapPoint.cc:593-596
+  s.level = level_from_log(orblg::ref_logf(ratio), P.log_sf, P.V.nlevels);   // :1325
+  s.ok = true;
+  return s;
+}
+
+__global__ __launch_bounds__(256) void k_local_map_project_rig(LocalMapParams P, RigLocalParams G) {
+  const int p = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = P.map_n ? max(0, min(P.map_n[(size_t)p * P.map_n_stride], P.map_stride)) : P.map_n_const;
+  if (i == 0) G.query_n[p] = 2 * n;
+  if (G.partner) {
+    const int fn = max(0, min(G.frame_n ? G.frame_n[(size_t)p * G.frame_n_stride] : G.frame_n_const, G.frame_stride));
+    const int nl = max(0, min(G.nleft_dev ? G.nleft_dev[(size_t)p * G.nleft_stride] : G.nleft_const, fn));
+    const size_t fo = (size_t)p * G.frame_stride;
+    for (int k = i; k < G.frame_stride; k += gridDim.x * 256) {
+      int pr = -1;
+      if (k < nl) {
+        const int r = G.l2r ? G.l2r[fo + k] : -1;
+        if (r >= 0 && r < fn - nl) pr = nl + r;
+      } else if (k < fn) {
+        const int l = G.r2l ? G.r2l[fo + (k - nl)] : -1;
+        if (l >= 0 && l < nl) pr = l;
+      }
+      G.partner[fo + k] = pr;
+    }
+  }
+  if (i >= P.map_stride) return;
+  const size_t o = (size_t)p * P.map_stride + i;
+  float uL = 0.f, vL = 0.f, radL = 0.f, uR = 0.f, vR = 0.f, radR = 0.f;
+  int lvlL = 0, lvlR = 0;
+  uint8_t flL = 0, flR = 0;
+  if (i < n) {
+    if (!P.eligible[o]) {
+      P.in_view[o] = 0; G.in_view_r[o] = 0;
+    } else {
+      const float *T = P.Tcw + (size_t)p * 16;
+      float Ow[3], Tr[12], Or[3];
+      camera_centre(T, Ow);                                       // mOw, Frame.cc:538
+      rig_right_pose(T, G.Trl, Tr);                               // Frame.cc:1278-1279
+      rig_right_centre(T, G.tlr, Ow, Or);                         // Frame.cc:1280
+      const float xw[3] = {P.Xw[3 * o], P.Xw[3 * o + 1], P.Xw[3 * o + 2]};
+      const FrustumSide L = frustum_side(P, T, Ow, P.V.cam_type, P.V.cam, xw, o);       // Frame.cc:656
+      const FrustumSide R = frustum_side(P, Tr, Or, G.cam_type2, G.cam2, xw, o);        // Frame.cc:657
+      P.in_view[o] = L.ok ? 1 : 0; G.in_view_r[o] = R.ok ? 1 : 0;  // :651-652, :656-657
+      P.level[o] = L.level; G.level_r[o] = R.level;               // :653-654 (-1), :1330, :1337
+      float depth = 0.f;
+      if (L.ok) { P.proj_x[o] = L.u; P.proj_y[o] = L.v; P.view_cos[o] = L.vcos; P.depth[o] = depth = L.depth; }   // :1335-1339
+      else if (P.bFarPoints && R.ok) depth = P.depth[o];          // mTrackDepth as the MapPoint held it (ORBmatcher.cc:56)
+      if (R.ok) { P.proj_xr[o] = R.u; G.proj_yr[o] = R.v; G.view_cos_r[o] = R.vcos; G.depth_r[o] = R.depth; }     // :1328-1332
+      // ORBmatcher.cc:53-56.  A NaN projection finds no candidate in the reference (every |dx| < r test is false): left out.
+      if ((L.ok || R.ok) && !(P.bFarPoints && depth > P.th_far)) {
+        if (L.ok && L.u == L.u && L.v == L.v) {                   // :62-73
+          float r = radius_by_viewing_cos(L.vcos);
+          if (P.th != 1.0f) r *= P.th;
+          uL = L.u; vL = L.v; radL = r * P.V.sf[L.level]; lvlL = L.level;
+          flL = query_flags(P.obs, o);
+        }
+        if (R.ok && R.level != -1 && R.u == R.u && R.v == R.v) {  // :145-151: no th factor (:148)
+          uR = R.u; vR = R.v; radR = radius_by_viewing_cos(R.vcos) * P.V.sf[R.level]; lvlR = R.level;
+          flR = query_flags(P.obs, o);
+        }
+      }
+    }
+  }
+  store_query(P.Q, 2 * o, uL, vL, radL, 0.f, flL ? lvlL - 1 : -1, flL ? lvlL : -1, flL);   // Nleft != -1: no mvuRight test (:93)
+  store_query(P.Q, 2 * o + 1, uR, vR, radR, 0.f, flR ? lvlR - 1 : -1, flR ? lvlR : -1, flR);
+  G.qside[2 * o] = 0; G.qside[2 * o + 1] = 1;
+  if (i < n) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(G.mpdesc + 32 * o);
+    uint4 *dst = reinterpret_cast<uint4 *>(G.qdesc + 64 * o);
+    const uint4 a = src[0], b = src[1];
+    dst[0] = a; dst[1] = b; dst[2] = a; dst[3] = b;
+  }
+}
+
+// The search leaves QUERY ids (2i, 2i + 1) in the slots it writes; callers of this member hold local-map indices i.  The slot part
+// of k_rot_prune<1> (two steps with a barrier: a converted value could equal another query's id), extended to the stereo partner's
+// slot: query j with moq[j] = m owns slot[m] and slot[partner[m]] where it was the last writer.  Slots the search did not write
+// are not touched.  One workgroup per problem.
+struct RigSlotParams {
+  const int32_t *moq; int map_stride;
+  const int32_t *map_n; int map_n_stride; int map_n_const;
+  const int32_t *partner;   // or NULL
+  int32_t *slot; int frame_stride;
+};
+
+__global__ __launch_bounds__(256) void k_rig_slot_convert(RigSlotParams S) {
+  const int p = blockIdx.x, t = threadIdx.x;
+  const int n = 2 * (S.map_n ? max(0, min(S.map_n[(size_t)p * S.map_n_stride], S.map_stride)) : S.map_n_const);
+  const size_t qo = 2 * (size_t)p * S.map_stride, ko = (size_t)p * S.frame_stride;
+  for (int step = 0; step < 2; step++) {
+    for (int j = t; j < n; j += 256) {
+      const int m = S.moq[qo + j];
+      if (m < 0) continue;
+      const int from = step ? -2 - (j >> 1) : j, to = step ? j >> 1 : -2 - (j >> 1);
+      if (S.slot[ko + m] == from) S.slot[ko + m] = to;
+      const int pr = S.partner ? S.partner[ko + m] : -1;
+      if (pr >= 0 && S.slot[ko + pr] == from) S.slot[ko + pr] = to;
+    }
+    __syncthreads();
+  }
+}
+
 // The device build of the logf replica on n floats (orbx_logf_device): lets the tests compare it with the host build, which
 // tests/test_logf_replica.py compares with the host libm.
 __global__ __launch_bounds__(256) void k_ref_logf(const float *x, int n, float *y) {

@@ -36,6 +36,32 @@ ORB_REF void camera_centre(const float *T, float *Ow) {
   }
 }
 
+// The right camera of a fisheye-stereo rig in Frame::isInFrustumChecks (Frame.cc:1276-1280), from Tcw = [mRcw | mtcw] and
+// Trl = mTrl (both row-major, row stride 4) and tlr = mTlr.col(3).  [OPENCV-UNVERIFIED] like mat3_mul_add / camera_centre:
+//   mR = Rrl * mRcw (:1278): a 3x3 * 3x3 cv::gemm, per entry a0*b0 + a1*b1 + a2*b2 in float (the small-matrix path);
+//   mt = Rrl * mtcw + trl (:1279): mat3_mul_add;
+// written as Tr = [mR | mt], 12 floats with row stride 4, so that mat3_mul_add applies to it (:1289).
+ORB_REF void rig_right_pose(const float *Tcw, const float *Trl, float *Tr) {
+  const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]}, trl[3] = {Trl[3], Trl[7], Trl[11]};
+  float t[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) Tr[4 * i + j] = Trl[4 * i + 0] * Tcw[j] + Trl[4 * i + 1] * Tcw[4 + j] + Trl[4 * i + 2] * Tcw[8 + j];
+  mat3_mul_add(Trl, tcw, trl, t);
+  Tr[3] = t[0]; Tr[7] = t[1]; Tr[11] = t[2];
+}
+
+//   twc = mRwc * tlr + mOw (:1280) with mRwc = mRcw.t() (Frame.cc:536) and mOw = camera_centre(Tcw): one `A*B + C` gemm over the
+//   stored transpose, the form of mat3_mul_add.
+ORB_REF void rig_right_centre(const float *Tcw, const float *tlr, const float *Ow, float *twc) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const float t0 = Tcw[i] * tlr[0] + Tcw[4 + i] * tlr[1] + Tcw[8 + i] * tlr[2];
+    twc[i] = (float)((double)t0 + (double)Ow[i]);
+  }
+}
+
 // Mat::dot of two 3-vectors of floats: products and sum in double
 ORB_REF double dot3_double(const float *a, const float *b) {
   double d = 0;

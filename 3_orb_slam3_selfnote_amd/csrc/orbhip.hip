@@ -1199,6 +1199,7 @@ struct orbm_handle {
   DevBuf d_cand;      // fused k_match_resolve: every pair's descriptors and candidate records in sorted order (48 B per keypoint)
   DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
   DevBuf d_lmq;       // query arrays written by k_local_map_project (orbm_search_local_points*): never shared with d_lfq
+  DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
   bool profiling = false;
   hipEvent_t ev[PROF_DEPTH][3] = {};
@@ -1320,7 +1321,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_tri_count, &m->d_tri_keys};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_partner, &m->d_tri_count, &m->d_tri_keys};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -2150,6 +2151,191 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
                                              mb, th, bMono, checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
   if (rs < 0) return rs;
   return download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+}
+
+// ---- Tracking::SearchLocalPoints for a fisheye-stereo frame (Frame.cc:650-660, :1270-1343; ORBmatcher.cc:44-214) ------------------
+static bool valid_track_rig(const orbm_track_rig_t *t) {
+  return t->in_view && t->in_view_r && t->proj_x && t->proj_y && t->depth && t->view_cos && t->proj_xr && t->proj_yr && t->depth_r &&
+         t->view_cos_r && t->level && t->level_r;
+}
+
+// The device core: k_local_map_project_rig (both frustum tests, two queries per local map point, the partner table), the search with
+// couple = 1 (ORBmatcher.cc:127), k_rig_slot_convert.  d_l2r / d_r2l: device arrays [npairs][frame_stride] or NULL.  serial: see
+// orbm_search_local_points_fisheye_batch_device.  Arguments are checked before anything is launched.
+static int search_local_rig_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
+                                  const int32_t *d_n_left, int n_left_stride, int n_left, const int32_t *d_l2r, const int32_t *d_r2l,
+                                  const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs,
+                                  const float *sf, int nlevels, float log_sf, const float *Trl, const float *tlr, int cam_type,
+                                  const float *cam_params, int cam_type2, const float *cam_params2, float view_cos_limit, float th, int bFarPoints,
+                                  float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, const orbm_track_rig_t *track0,
+                                  int32_t *d_nmatches, hipStream_t s, bool search, int serial) {
+  if (!m || !cur0 || !map0 || !track0 || !sf || !cam_params || !cam_params2 || !Trl || !tlr || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches)
+    return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1) || (cam_type2 != 0 && cam_type2 != 1)) return ORBX_E_ARG;
+  if (!valid_local_map(map0) || !valid_track_rig(track0)) return ORBX_E_ARG;
+  if (search && (!cur0->keys_un || !cur0->descriptors)) return ORBX_E_ARG;
+  const int maxq = d_map_n ? map_stride : map0->n;
+  const int maxn = d_frame_n ? frame_stride : cur0->n;
+  if (maxq <= 0 || map_stride < maxq || map0->n < 0 || (!d_map_n && map_stride < map0->n)) return ORBX_E_ARG;
+  if (search && (maxn <= 0 || frame_stride < maxn || (!d_frame_n && frame_stride < cur0->n))) return ORBX_E_ARG;
+  if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
+  if (search && !d_n_left && (n_left < 0 || n_left > cur0->n)) return ORBX_E_ARG;
+  if ((long long)map_stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
+  if (npairs == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  LocalMapParams P;
+  memset(&P, 0, sizeof(P));
+  QueryScratch &Q = P.Q;
+  RigScratch S;
+  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, 2 * map_stride, Q, &S);
+  if (rq < 0) return rq;
+  const bool partners = search && (d_l2r || d_r2l);
+  const size_t pbytes = sizeof(int32_t) * (size_t)npairs * (size_t)frame_stride;
+  if (partners && pbytes > m->d_partner.bytes) {
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, m->d_partner.reserve(pbytes + (pbytes >> 2)));
+  }
+  int32_t *moq = d_moq ? d_moq : Q.moq;
+  P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
+  P.obs = map0->obs; P.Tcw = map0->Tcw;
+  P.map_stride = map_stride; P.map_n = d_map_n; P.map_n_stride = map_n_stride; P.map_n_const = map0->n;
+  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
+  P.log_sf = log_sf;
+  P.mbf = 0.f; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
+  P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
+  P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
+  RigLocalParams G;
+  memset(&G, 0, sizeof(G));
+  for (int i = 0; i < 12; i++) G.Trl[i] = Trl[i];
+  for (int i = 0; i < 3; i++) G.tlr[i] = tlr[i];
+  G.cam_type2 = cam_type2;
+  for (int k = 0; k < (cam_type2 == 0 ? 4 : 8); k++) G.cam2[k] = cam_params2[k];
+  G.mpdesc = map0->mpdesc;
+  G.in_view_r = track0->in_view_r; G.proj_yr = track0->proj_yr; G.depth_r = track0->depth_r; G.view_cos_r = track0->view_cos_r;
+  G.level_r = track0->level_r;
+  G.qdesc = S.qdesc; G.qside = S.qside; G.query_n = S.query_n;
+  G.l2r = d_l2r; G.r2l = d_r2l; G.partner = partners ? (int32_t *)m->d_partner.p : nullptr;
+  G.frame_stride = frame_stride; G.frame_n = d_frame_n; G.frame_n_stride = frame_n_stride; G.frame_n_const = cur0->n;
+  G.nleft_dev = d_n_left; G.nleft_stride = n_left_stride; G.nleft_const = n_left;
+  hipLaunchKernelGGL(k_local_map_project_rig, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P, G);
+  if (search) {
+    const orbm_queries_t q = scratch_view(Q, 2 * map0->n, S.qdesc, false);
+    orbm_frame_t f = *cur0;
+    f.u_right = nullptr;  // Nleft != -1: no mvuRight test (ORBmatcher.cc:93)
+    SearchOpts o;
+    o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
+    o.nleft = n_left; o.nleft_dev = d_n_left; o.nleft_stride = n_left_stride;
+    o.couple = 1; o.qside = S.qside;   // ORBmatcher.cc:127
+    o.partner = G.partner; o.serial = partners ? serial : 0;
+    const int rc = search_batch(m, &f, frame_stride, d_frame_n, frame_n_stride, &q, 2 * map_stride, d_map_n ? S.query_n : nullptr, 1, npairs, nnratio,
+                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-141, :153-209
+    if (rc < 0) return rc;
+    RigSlotParams C;
+    memset(&C, 0, sizeof(C));
+    C.moq = moq; C.map_stride = map_stride; C.map_n = d_map_n; C.map_n_stride = map_n_stride; C.map_n_const = map0->n;
+    C.partner = G.partner; C.slot = d_slot; C.frame_stride = frame_stride;
+    hipLaunchKernelGGL(k_rig_slot_convert, dim3(npairs), dim3(256), 0, s, C);
+  }
+  MCHECK(m, hipGetLastError());
+  return 0;
+}
+
+int orbm_search_local_points_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                                  int frame_n_stride, const int32_t *d_n_left, int n_left_stride, int n_left,
+                                                  const int32_t *d_left_to_right, const int32_t *d_right_to_left, const orbm_local_map_t *map0,
+                                                  int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs, const float *sf,
+                                                  int nlevels, float log_sf, const float *Trl, const float *tlr, int cam_type,
+                                                  const float *cam_params, int cam_type2, const float *cam_params2, float view_cos_limit, float th,
+                                                  int bFarPoints, float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs,
+                                                  int32_t *d_moq, const orbm_track_rig_t *track0, int32_t *d_nmatches, void *stream_) {
+  if (!m) return ORBX_E_ARG;
+  if (frame_stride > ORBM_FISHEYE_MAX_KEYPOINTS) { m->err = "more than 12960 keypoints (left + right) per fisheye-stereo frame not supported by the resident search"; return ORBX_E_ARG; }
+  // obs lives on the device: whether a taking query without observations exists is not known here, so the search is serial whenever
+  // one can exist and a partner table is passed (exact in either mode)
+  const int serial = map0 && map0->obs ? 1 : 0;
+  return search_local_rig_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride, n_left, d_left_to_right, d_right_to_left,
+                                map0, map_stride, d_map_n, map_n_stride, npairs, sf, nlevels, log_sf, Trl, tlr, cam_type, cam_params, cam_type2,
+                                cam_params2, view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, track0, d_nmatches,
+                                (hipStream_t)stream_, true, serial);
+}
+
+int orbm_search_local_points_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const int32_t *left_to_right, const int32_t *right_to_left,
+                                     const float *sf, int nlevels, float log_sf, const orbm_local_map_t *map, const float *Trl, const float *tlr,
+                                     int cam_type, const float *cam_params, int cam_type2, const float *cam_params2, float view_cos_limit, float th,
+                                     int bFarPoints, float th_far, float nnratio, int32_t *slot, uint8_t *slot_obs, int32_t *match_of_point,
+                                     const orbm_track_rig_t *track) {
+  if (!m || !cur || !map || !track || !sf || !cam_params || !cam_params2 || !Trl || !tlr || !slot || !slot_obs) return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1) || (cam_type2 != 0 && cam_type2 != 1)) return ORBX_E_ARG;
+  if (!valid_local_map(map) || !valid_track_rig(track)) return ORBX_E_ARG;
+  const int n = cur->n, nmp = map->n;
+  if (n < 0 || nmp < 0 || n_left < 0 || n_left > n) return ORBX_E_ARG;
+  if (n > ORBM_FISHEYE_MAX_KEYPOINTS) { m->err = "more than 12960 keypoints (left + right) per fisheye-stereo frame not supported"; return ORBX_E_ARG; }
+  if (n > 0 && (!cur->keys_un || !cur->descriptors || !(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y))) return ORBX_E_ARG;
+  bool anyp = false;   // a bad partner index is refused, as orbm_search_by_projection_fisheye does (build_partner)
+  for (int i = 0; left_to_right && i < n_left; i++)
+    if (left_to_right[i] >= 0) { if (left_to_right[i] >= n - n_left) return ORBX_E_ARG; anyp = true; }
+  for (int j = 0; right_to_left && j < n - n_left; j++)
+    if (right_to_left[j] >= 0) { if (right_to_left[j] >= n_left) return ORBX_E_ARG; anyp = true; }
+  if (nmp == 0) return 0;
+  // a partner write releases a claim only when its query has no observations (k_match_resolve): serial mode only then
+  bool release = false;
+  for (int i = 0; map->obs && i < nmp && !release; i++) release = map->eligible[i] && !map->obs[i];
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  // one staged block up (depth is in/out: it goes up with the slots), one block down, one synchronisation; a frame without keypoints
+  // still gets its track fields
+  const size_t fp = sizeof(float) * (size_t)nmp, ip = sizeof(int32_t) * (size_t)nmp;
+  enum { KP, DESC, L2R, R2L, ELIG, XW, NRM, MAXD, MIND, MD, OBS, TC, SLOT, SOBS, DEP, MOQ, INV, INVR, PX, PY, VC, PXR, PYR, DEPR, VCR, LVL, LVLR, NM, NPARTS };
+  void *d[NPARTS];
+  const int32_t *l2r = anyp ? left_to_right : nullptr, *r2l = anyp ? right_to_left : nullptr;
+  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
+                              {l2r, l2r ? sizeof(int32_t) * (size_t)n_left : 0}, {r2l, r2l ? sizeof(int32_t) * (size_t)(n - n_left) : 0},
+                              {map->eligible, (size_t)nmp}, {map->Xw, 3 * fp}, {map->normal, 3 * fp}, {map->max_dist, fp}, {map->min_dist, fp},
+                              {map->mpdesc, 32 * (size_t)nmp}, {map->obs, map->obs ? (size_t)nmp : 0}, {map->Tcw, 16 * sizeof(float)},
+                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {track->depth, fp}, {nullptr, 2 * ip},
+                              {nullptr, (size_t)nmp}, {nullptr, (size_t)nmp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp},
+                              {nullptr, fp}, {nullptr, fp}, {nullptr, ip}, {nullptr, ip}, {nullptr, sizeof(int32_t)}}, d, true);
+  if (rc < 0) return rc;
+  orbm_frame_t df = *cur;
+  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = nullptr;
+  orbm_local_map_t dm = *map;
+  dm.eligible = (const uint8_t *)d[ELIG]; dm.Xw = (const float *)d[XW]; dm.normal = (const float *)d[NRM]; dm.max_dist = (const float *)d[MAXD];
+  dm.min_dist = (const float *)d[MIND]; dm.mpdesc = (const uint8_t *)d[MD]; dm.obs = (const uint8_t *)d[OBS]; dm.Tcw = (const float *)d[TC];
+  orbm_track_rig_t dt;
+  dt.in_view = (uint8_t *)d[INV]; dt.in_view_r = (uint8_t *)d[INVR]; dt.proj_x = (float *)d[PX]; dt.proj_y = (float *)d[PY];
+  dt.depth = (float *)d[DEP]; dt.view_cos = (float *)d[VC]; dt.proj_xr = (float *)d[PXR]; dt.proj_yr = (float *)d[PYR];
+  dt.depth_r = (float *)d[DEPR]; dt.view_cos_r = (float *)d[VCR]; dt.level = (int32_t *)d[LVL]; dt.level_r = (int32_t *)d[LVLR];
+  int32_t *dslot = n > 0 ? (int32_t *)d[SLOT] : (int32_t *)d[MOQ];   // n == 0: no search, any non-null pointer
+  uint8_t *dsobs = n > 0 ? (uint8_t *)d[SOBS] : (uint8_t *)d[INV];
+  const int rs = search_local_rig_batch(m, &df, std::max(n, 1), nullptr, 0, nullptr, 0, n_left, (const int32_t *)d[L2R], (const int32_t *)d[R2L], &dm, nmp,
+                                        nullptr, 0, 1, sf, nlevels, log_sf, Trl, tlr, cam_type, cam_params, cam_type2, cam_params2, view_cos_limit, th,
+                                        bFarPoints, th_far, nnratio, dslot, dsobs, (int32_t *)d[MOQ], &dt, (int32_t *)d[NM], s, n > 0, release ? 1 : 0);
+  if (rs < 0) return rs;
+  const int nm = download_slots(m, s, n > 0 ? d[SLOT] : d[DEP], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  if (nm < 0) return nm;
+  const int32_t *moq = (const int32_t *)mirror_of(m, d[MOQ]), *lvl = (const int32_t *)mirror_of(m, d[LVL]), *lvlr = (const int32_t *)mirror_of(m, d[LVLR]);
+  const uint8_t *inv = (const uint8_t *)mirror_of(m, d[INV]), *invr = (const uint8_t *)mirror_of(m, d[INVR]);
+  const float *px = (const float *)mirror_of(m, d[PX]), *py = (const float *)mirror_of(m, d[PY]), *dep = (const float *)mirror_of(m, d[DEP]);
+  const float *vc = (const float *)mirror_of(m, d[VC]), *pxr = (const float *)mirror_of(m, d[PXR]), *pyr = (const float *)mirror_of(m, d[PYR]);
+  const float *depr = (const float *)mirror_of(m, d[DEPR]), *vcr = (const float *)mirror_of(m, d[VCR]);
+  // only what isInFrustum writes (Frame.cc:651-657): the flags always, the levels of eligible points, a side's fields where it is in view
+  for (int i = 0; i < nmp; i++) {
+    if (match_of_point) { match_of_point[2 * i] = n > 0 ? moq[2 * i] : -1; match_of_point[2 * i + 1] = n > 0 ? moq[2 * i + 1] : -1; }
+    track->in_view[i] = inv[i]; track->in_view_r[i] = invr[i];
+    if (!map->eligible[i]) continue;
+    track->level[i] = lvl[i]; track->level_r[i] = lvlr[i];
+    if (inv[i]) { track->proj_x[i] = px[i]; track->proj_y[i] = py[i]; track->depth[i] = dep[i]; track->view_cos[i] = vc[i]; }
+    if (invr[i]) { track->proj_xr[i] = pxr[i]; track->proj_yr[i] = pyr[i]; track->depth_r[i] = depr[i]; track->view_cos_r[i] = vcr[i]; }
+  }
+  return nm;
+}
+
+void orbm_rig_right_camera(const float *Tcw, const float *Trl, const float *tlr, float *Tr, float *twc) {
+  if (!Tcw || !Trl || !tlr || !Tr || !twc) return;
+  float Ow[3];
+  camera_centre(Tcw, Ow);
+  rig_right_pose(Tcw, Trl, Tr);          // Frame.cc:1278-1279
+  rig_right_centre(Tcw, tlr, Ow, twc);   // Frame.cc:1280
 }
 
 int orbm_search_by_projection_keyframe(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, float logScaleFactor, int nKF,

@@ -510,6 +510,74 @@ int orbm_search_by_projection_last_frame_fisheye_batch_device(orbm_t *m, const o
                                                               int bMono, int checkOri, int32_t *d_slot, uint8_t *d_slot_obs,
                                                               int32_t *d_match_of_query, int32_t *d_nmatches, void *stream);
 
+/* void Tracking::SearchLocalPoints() for a fisheye-stereo frame (Frame::Nleft != -1): Frame::isInFrustum's else branch
+ * (Frame.cc:650-660), i.e. Frame::isInFrustumChecks (Frame.cc:1270-1343) once per camera with MapPoint::PredictScale
+ * (MapPoint.cc:587-602), then both halves of SearchByProjection(Frame&, const vector<MapPoint*>&, th, bFarPoints, thFarPoints)
+ * (ORBmatcher.cc:44-214), all on the device.
+ * What the frustum test writes per local map point (caller arrays, indexed like orbm_local_map_t).  An eligible point gets
+ * in_view = in_view_r = 0 and level = level_r = -1 first (Frame.cc:651-654); then a side whose checks all pass gets its five
+ * fields - left (:1335-1339): proj_x, proj_y, level, view_cos, depth = |Pc|; right (:1328-1332): proj_xr, proj_yr, level_r,
+ * view_cos_r, depth_r - and its flag (:656-657).  There is no reset of the projection to -1 in this branch: the fields of a side
+ * that fails keep the caller's values.  An ineligible point gets in_view = in_view_r = 0 and nothing else.
+ * depth is IN/OUT: the far-point test (ORBmatcher.cc:56) reads mTrackDepth, the LEFT depth, as it stands after the frustum step,
+ * so for a point whose left check fails and whose right check passes it reads the value the caller passed in. */
+typedef struct {
+  uint8_t *in_view, *in_view_r;                      /* mbTrackInView, mbTrackInViewR */
+  float *proj_x, *proj_y, *depth, *view_cos;         /* mTrackProjX / Y, mTrackDepth, mTrackViewCos */
+  float *proj_xr, *proj_yr, *depth_r, *view_cos_r;   /* mTrackProjXR / YR, mTrackDepthR, mTrackViewCosR */
+  int32_t *level, *level_r;                          /* mnTrackScaleLevel, mnTrackScaleLevelR */
+} orbm_track_rig_t;
+/* Host pointers.  cur as in orbm_search_by_projection_fisheye: keys_un = the RAW keypoints [mvKeys ; mvKeysRight], descriptors =
+ * mDescriptors, n = Nleft + Nright, u_right ignored (ORBmatcher.cc:93); one set of bounds for both cameras (Frame.cc:1302-1305).
+ * left_to_right[n_left] / right_to_left[n - n_left] = mvLeftToRightMatch / mvRightToLeftMatch (NULL = none).  map: unchanged.
+ * Trl = mTrl, row-major with row stride 4 (12 or 16 floats); tlr = mTlr.col(3).  The right camera is mR = Rrl * mRcw,
+ * mt = Rrl * mtcw + trl, twc = mRwc * tlr + mOw (Frame.cc:1276-1280).  cam_type / cam_params = mpCamera projects the left side,
+ * cam_type2 / cam_params2 = mpCamera2 the right side (Frame.cc:1299-1300; the last-frame search uses mpCamera for both).
+ * A point takes part iff it is eligible, in_view || in_view_r (ORBmatcher.cc:53) and not a far point (:56, see depth above).
+ * Left query (:62-73) where in_view: radius RadiusByViewingCos(view_cos) (x th when th != 1) x mvScaleFactors[level], levels
+ * [level - 1, level], left keypoints.  Right query (:145-151) where in_view_r && level_r != -1: RadiusByViewingCos(view_cos_r)
+ * WITHOUT th (:148) x mvScaleFactors[level_r] around (proj_xr, proj_yr), right keypoints.  A NaN projection makes no query.  A left
+ * half that fails the ratio test drops the right half (:127); an empty left window does not (:75).  An accepted match also writes
+ * its stereo partner's slot, unconditionally, and counts it (:132-136, :199-203).  Claims are sequential in local-map order, left
+ * half before right half.  slot / slot_obs [n] in/out: slots this call writes hold local-map indices i.  match_of_point[2 nmp]
+ * (out, may be NULL): entry 2i the left match of point i, 2i + 1 its right match, indices into the concatenated frame or -1.
+ * One staged upload, the kernels of the batched form below with npairs = 1, one download, one synchronisation; a frame without
+ * keypoints still gets its track fields.  Returns nmatches including the partner increments.  ORBX_E_ARG as
+ * orbm_search_local_points, and for NULL Trl / tlr / cam_params2, cam_type2 not 0 / 1, n_left outside [0, n], n above
+ * ORBM_FISHEYE_MAX_KEYPOINTS, a partner index beyond the other image's count. */
+int orbm_search_local_points_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const int32_t *left_to_right,
+                                     const int32_t *right_to_left, const float *scale_factors, int nlevels, float log_scale_factor,
+                                     const orbm_local_map_t *map, const float *Trl, const float *tlr, int cam_type,
+                                     const float *cam_params, int cam_type2, const float *cam_params2, float viewing_cos_limit, float th,
+                                     int bFarPoints, float thFarPoints, float nnratio, int32_t *slot, uint8_t *slot_obs,
+                                     int32_t *match_of_point, const orbm_track_rig_t *track);
+/* Batched device form: layout, strides and live counts as in orbm_search_local_points_batch_device; d_n_left / n_left_stride /
+ * n_left as in orbm_search_by_projection_last_frame_fisheye_batch_device (d_n of orbm_rig_concat_batch_device feeds d_frame_n and
+ * d_n_left with stride 2).  d_left_to_right / d_right_to_left [npairs][frame_stride] (either may be NULL): the first Nleft resp.
+ * N - Nleft entries of a problem are live; an entry outside the other image's live range counts as -1 (ORBmatcher.cc:132, :199;
+ * the per-frame form refuses it).  d_match_of_point [npairs][2 * map_stride] (out, may be NULL); the arrays of track0 at element
+ * offset p * map_stride; Trl, tlr, both cam_params and scale_factors are HOST arrays.  Device work: k_local_map_project_rig (both
+ * frustum tests, the queries 2i / 2i + 1 with side bytes and descriptors, the partner table), the search kernels with the image
+ * restriction per query, the :127 rule and the partner writes, k_rig_slot_convert (query ids in the written slots, partner slots
+ * included, become local-map indices; a slot's holder is the LAST query that wrote it).  With partner tables AND map0->obs the
+ * claims are resolved one query at a time (a partner write of a point without observations can release a claim, and whether such
+ * a point exists is only known on the device); the result is exact in either mode.  Entries the call does not write, in every
+ * array, keep the caller's values.  Asynchronous on `stream`: no host synchronisation, copy or allocation beyond the growth of the
+ * handle's scratch.  ORBX_E_ARG as orbm_search_local_points_batch_device (npairs < 0 here) and as the per-frame form, and for
+ * frame_stride above ORBM_FISHEYE_MAX_KEYPOINTS.  npairs == 0 returns 0 and launches nothing. */
+int orbm_search_local_points_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
+                                                  int frame_n_stride, const int32_t *d_n_left, int n_left_stride, int n_left,
+                                                  const int32_t *d_left_to_right, const int32_t *d_right_to_left,
+                                                  const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride,
+                                                  int npairs, const float *scale_factors, int nlevels, float log_scale_factor,
+                                                  const float *Trl, const float *tlr, int cam_type, const float *cam_params, int cam_type2,
+                                                  const float *cam_params2, float viewing_cos_limit, float th, int bFarPoints,
+                                                  float thFarPoints, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs,
+                                                  int32_t *d_match_of_point, const orbm_track_rig_t *track0, int32_t *d_nmatches, void *stream);
+/* The right camera of isInFrustumChecks (Frame.cc:1276-1280) as the kernels form it, host: Tr[12] = [Rrl * mRcw | Rrl * mtcw + trl]
+ * (row stride 4), twc[3] = mRwc * tlr + mOw.  Tcw: row-major 4x4; Trl: row stride 4. */
+void orbm_rig_right_camera(const float *Tcw, const float *Trl, const float *tlr, float *Tr, float *twc);
+
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound,
  *                                    const float th, const int ORBdist)                       (ORBmatcher.cc:2291-2413)
  * flattened, host pointers.  i in [0, nKF): valid[i] = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP);
