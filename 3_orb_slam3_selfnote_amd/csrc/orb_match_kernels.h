@@ -1199,8 +1199,9 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
         kw += __popcll(mk);
       }
       const bool two = m > 32;
-      // The chunk's query fragments stay packed: bits [32 s + 16 h, 32 s + 16 h + 16) of query col (q0) and 32 + col (q1), two K-steps
-      // per register, each expanded right before its MFMA.  Holding them expanded took 64 registers for the whole pass.
+      // FP4 form (orb_mfma_util.h): lane half h of K-step s holds descriptor dword 2 s + h of query col (q0) and 32 + col (q1),
+      // complemented (the query's sign is the inverted bit).  The fragments stay packed (8 registers) and are expanded right before
+      // their MFMA, 64 instructions per tile: held expanded (32 registers, 187 in all) the kernel ran the batch 1 % slower.
       uint32_t q0[4], q1[4];
       {
         const uint4 *r0 = reinterpret_cast<const uint4 *>(sReqD + col * 8), *r1 = reinterpret_cast<const uint4 *>(sReqD + (32 + col) * 8);
@@ -1208,14 +1209,13 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
         const uint32_t d0[8] = {a0.x, a0.y, a0.z, a0.w, b0.x, b0.y, b0.z, b0.w}, d1[8] = {a1.x, a1.y, a1.z, a1.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-          q0[s] = ((d0[2 * s] >> (16 * h)) & 0xffffu) | ((d0[2 * s + 1] >> (16 * h)) << 16);
-          q1[s] = ((d1[2 * s] >> (16 * h)) & 0xffffu) | ((d1[2 * s + 1] >> (16 * h)) << 16);
+          q0[s] = ~(h ? d0[2 * s + 1] : d0[2 * s]);
+          q1[s] = ~(h ? d1[2 * s + 1] : d1[2 * s]);
         }
       }
-      auto bq = [](const uint32_t *q, int s) { return mf_expand16((q[s >> 1] >> (16 * (s & 1))) & 0xffffu, MF_LUT_QUERY); };
       MfList<REFRESH_K> L0, L1;
       L0.init(); L1.init();
-      uint32_t *seedw = sSeedF + wid * MF_TILE;
+      float *seedw = reinterpret_cast<float *>(sSeedF + wid * MF_TILE);
       // the candidates' descriptors come from L2: the next tile's are loaded while this one runs (8 registers)
       int npos = 0;
       uint4 na = make_uint4(0u, 0u, 0u, 0u), nb = na;
@@ -1234,26 +1234,26 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
           npos = e2 < kw ? (int)cmp[e2] : 0;
           na = cDesc[2 * npos]; nb = cDesc[2 * npos + 1];
         }
-        if (h == 0) seedw[col] = have ? sRank[pos] : MF_REC_UNUSABLE;
-        // A fragments straight from the keypoint's descriptor: bits [32 s + 16 h, 32 s + 16 h + 16) of row `col` per K-step s
+        if (h == 0) seedw[col] = mf4_seed(have ? sRank[pos] : MF_REC_UNUSABLE);
+        // A fragments straight from the keypoint's descriptor: dword 2 s + h of row `col` per K-step s
         const uint32_t dd[8] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
-        mf_v4i A[8];
+        mf_v4i A[4];
 #pragma unroll
-        for (int s = 0; s < 8; s++) A[s] = mf_expand16((dd[s] >> (16 * h)) & 0xffffu, MF_LUT_CAND);
-        mf_v16i c;
+        for (int s = 0; s < 4; s++) A[s] = mf4_expand32(h ? dd[2 * s + 1] : dd[2 * s]);
+        mf_v16f c;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-          const mf_v4i v4 = *reinterpret_cast<const mf_v4i *>(&seedw[8 * g + 4 * h]);
-          c[4 * g] = v4[0]; c[4 * g + 1] = v4[1]; c[4 * g + 2] = v4[2]; c[4 * g + 3] = v4[3];
+          const float4 v4 = *reinterpret_cast<const float4 *>(&seedw[8 * g + 4 * h]);
+          c[4 * g] = v4.x; c[4 * g + 1] = v4.y; c[4 * g + 2] = v4.z; c[4 * g + 3] = v4.w;
         }
-        mf_v16i acc0 = c;
+        mf_v16f acc0 = c;
 #pragma unroll
-        for (int s = 0; s < 8; s++) acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], bq(q0, s), acc0, 0, 0, 0);
+        for (int s = 0; s < 4; s++) acc0 = mf4_mfma(A[s], mf4_expand32(q0[s]), acc0);
         L0.take(acc0);
         if (two) {
-          mf_v16i acc1 = c;
+          mf_v16f acc1 = c;
 #pragma unroll
-          for (int s = 0; s < 8; s++) acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], bq(q1, s), acc1, 0, 0, 0);
+          for (int s = 0; s < 4; s++) acc1 = mf4_mfma(A[s], mf4_expand32(q1[s]), acc1);
           L1.take(acc1);
         }
       }
@@ -1291,7 +1291,8 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
 #pragma unroll
       for (int j = 0; j < MATCH_TOPK; j++) {
         K o = KT::NONE;
-        if (j < REFRESH_K && a[j] < MF_KEY_LIMIT) o = (K)(((a[j] >> 11) << 23) | (uint32_t)sPerm[a[j] & 0x7ffu]);
+        const uint32_t key = j < REFRESH_K ? mf4_key(a[j]) : 0xffffffffu;   // a[j]: bit pattern of float(distance << 11 | position)
+        if (key < MF_KEY_LIMIT) o = (K)(((key >> 11) << 23) | (uint32_t)sPerm[key & 0x7ffu]);
         colp[64 * j] = o;
       }
     }
