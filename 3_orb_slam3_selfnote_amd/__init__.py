@@ -36,11 +36,11 @@ ABI_SYMBOLS = [
     "orbx_get_scale_tables", "orbx_get_features_per_level", "orbx_configure", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_get_host_us", "orbx_level_info", "orbx_download_level", "orbx_download_pyramid", "orbx_download_blurred_level",
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
-    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
+    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_ref_tanf", "orbx_tanf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -158,6 +158,9 @@ def load(build_if_needed=True):
     L.orbx_ref_logf.restype = f32
     L.orbx_ref_logf.argtypes = [f32]
     L.orbx_logf_device.argtypes = [vp, i32, vp, vp]
+    L.orbx_ref_tanf.restype = f32
+    L.orbx_ref_tanf.argtypes = [f32]
+    L.orbx_tanf_device.argtypes = [vp, i32, vp, vp]
     L.orbm_create.restype = vp
     L.orbm_create.argtypes = [i32]
     L.orbm_destroy.argtypes = [vp]
@@ -173,6 +176,12 @@ def load(build_if_needed=True):
     L.orbm_search_by_projection_last_frame_fisheye_batch_device.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp, i32,
                                                                             vp, f32, f32, i32, i32, vp, vp, vp, vp, vp]
     L.orbm_rig_concat_batch_device.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.orbm_unproject.argtypes = [vp, i32, vp, vp]
+    L.orbm_fisheye_ratio_test.argtypes = [i32, i32]
+    L.orbm_fisheye_triangulate.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_fisheye_triangulate_device.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_stereo_fisheye_matches_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbm_stereo_fisheye_matches.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_search_for_initialization.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp]
     L.orbm_fuse.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, vp, vp]
     L.orbm_fuse_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
@@ -854,6 +863,60 @@ class ORBmatcher:
             raise OrbError("orbm_distinctive_descriptors rc=%d" % rc)
         return best[:len(groups)]
 
+    def ComputeStereoFishEyeMatches(self, keysL, descL, monoL, keysR, descR, monoR, level_sigma2, Tlr, cam_params, cam_params2, p3d=None):
+        """Frame::ComputeStereoFishEyeMatches (Frame.cc:1228-1268) of one rig frame from host arrays (orbm_stereo_fisheye_matches).
+        keysL / keysR: KP_DTYPE arrays (mvKeys / mvKeysRight), lapping rows from monoL / monoR; Tlr: 3x4 [mRlr | mtlr].  Returns
+        (mvLeftToRightMatch, mvRightToLeftMatch, mvDepth, mvStereo3Dpoints [Nleft, 3], (nMatches, descMatches)); p3d: initial contents of
+        the 3-D points, kept where unmatched (zeros by default)."""
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        keysL, keysR = np.ascontiguousarray(keysL, dtype=KP_DTYPE), np.ascontiguousarray(keysR, dtype=KP_DTYPE)
+        descL, descR = np.ascontiguousarray(descL, dtype=np.uint8), np.ascontiguousarray(descR, dtype=np.uint8)
+        nL, nR = len(keysL), len(keysR)
+        sig = f(level_sigma2)
+        l2r, r2l = np.full(max(nL, 1), -1, np.int32), np.full(max(nR, 1), -1, np.int32)
+        depth = np.full(max(nL, 1), -1.0, np.float32)
+        p3 = np.zeros((max(nL, 1), 3), np.float32) if p3d is None else np.array(p3d, dtype=np.float32, order="C").reshape(-1, 3)
+        nm = np.zeros(2, np.int32)
+        rc = self.L.orbm_stereo_fisheye_matches(self.m, _p(keysL), _p(descL), nL, int(monoL), _p(keysR), _p(descR), nR, int(monoR), _p(sig), len(sig),
+                                                _p(f(Tlr)), _p(f(cam_params)), _p(f(cam_params2)), _p(l2r), _p(r2l), _p(depth), _p(p3), _p(nm))
+        self._check(rc, "orbm_stereo_fisheye_matches")
+        if rc < 0:
+            raise OrbError("orbm_stereo_fisheye_matches rc=%d" % rc)
+        return l2r[:nL], r2l[:nR], depth[:nL], p3[:nL], (int(nm[0]), int(nm[1]))
+
+    def stereo_fisheye_matches_batch_device(self, nframes, d_keysL, d_descL, d_countsL, d_keysR, d_descR, d_countsR, cap, level_sigma2, Tlr,
+                                            cam_params, cam_params2, out_stride, d_left_to_right, d_right_to_left, d_depth, d_p3d, d_nmatches=None,
+                                            stream=None):
+        """Frame::ComputeStereoFishEyeMatches for `nframes` resident rig frames (orbm_stereo_fisheye_matches_batch_device): the d_*
+        arguments are device addresses (ints): what two extract_batch_device calls of the same cap wrote, and the output tables of
+        out_stride entries per frame; level_sigma2, Tlr and the parameter sets are host arrays.  Asynchronous on `stream`."""
+        what = "orbm_stereo_fisheye_matches_batch_device: "
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if level_sigma2 is None or Tlr is None or cam_params is None or cam_params2 is None:
+            raise ValueError(what + "missing level_sigma2, Tlr or camera parameters")
+        sig = f(level_sigma2)
+        if f(Tlr).size != 12 or f(cam_params).size != 8 or f(cam_params2).size != 8:
+            raise ValueError(what + "Tlr needs 12 floats, each KannalaBrandt8 parameter set 8")
+        if not (d_keysL and d_descL and d_countsL and d_keysR and d_descR and d_countsR):
+            raise ValueError(what + "missing input")
+        if not (d_left_to_right and d_right_to_left and d_depth and d_p3d):
+            raise ValueError(what + "missing output")
+        if not 0 <= nframes <= 65535:
+            raise ValueError(what + "nframes outside [0, 65535]")
+        if cap <= 0 or 2 * cap > FISHEYE_MAX_KEYPOINTS:
+            raise ValueError(what + "cap outside (0, %d]" % (FISHEYE_MAX_KEYPOINTS // 2))
+        if out_stride < cap:
+            raise ValueError(what + "out_stride below cap")
+        if not 1 <= len(sig) <= 16:
+            raise ValueError(what + "nlevels outside [1, 16]")
+        rc = self.L.orbm_stereo_fisheye_matches_batch_device(self.m, int(nframes), _dp(d_keysL), _dp(d_descL), _dp(d_countsL), _dp(d_keysR), _dp(d_descR),
+                                                             _dp(d_countsR), int(cap), _p(sig), len(sig), _p(f(Tlr)), _p(f(cam_params)), _p(f(cam_params2)),
+                                                             int(out_stride), _dp(d_left_to_right), _dp(d_right_to_left), _dp(d_depth), _dp(d_p3d),
+                                                             _dp(d_nmatches), _dp(stream))
+        self._check(rc, "orbm_stereo_fisheye_matches_batch_device")
+        if rc < 0:
+            raise OrbError("orbm_stereo_fisheye_matches_batch_device rc=%d" % rc)
+
     def knnMatch2(self, query, train):
         """cv::BFMatcher(NORM_HAMMING).knnMatch(query, train, matches, 2) (Frame.cc:1246).  Returns (idx[nq, 2], dist[nq, 2])."""
         query, train = np.ascontiguousarray(query, dtype=np.uint8), np.ascontiguousarray(train, dtype=np.uint8)
@@ -1186,3 +1249,30 @@ def rig_concat_batch_device(nframes, d_keysL, d_descL, d_countsL, d_keysR, d_des
     rc = load().orbm_rig_concat_batch_device(int(nframes), _dp(d_keysL), _dp(d_descL), _dp(d_countsL), _dp(d_keysR), _dp(d_descR), _dp(d_countsR),
                                              int(cap), _dp(d_keys), _dp(d_desc), _dp(d_n), _dp(stream))
     return _check_free(rc, "orbm_rig_concat_batch_device")
+
+
+def unproject(cam_params, xy):
+    """KannalaBrandt8::unproject (KannalaBrandt8.cpp:112-139) of the pixels xy [n, 2]: rays [n, 3] (orbm_unproject, host)."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    rays = np.zeros((max(len(xy), 1), 3), np.float32)
+    _check_free(load().orbm_unproject(_p(np.ascontiguousarray(cam_params, dtype=np.float32)), len(xy), _p(xy), _p(rays)), "orbm_unproject")
+    return rays[:len(xy)]
+
+
+def fisheye_triangulate(kp1, kp2, sigma1, sigma2, Tlr, cam_params, cam_params2, p3d_fill=0.0):
+    """KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:343-412) of the keypoint pairs kp1 / kp2 [n, 2] on the host
+    (orbm_fisheye_triangulate): (depth [n] = z1 or -1, p3D [n, 3], p3d_fill where the function returns early)."""
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    n = len(f(kp1)) // 2
+    depth, p3 = np.zeros(max(n, 1), np.float32), np.full((max(n, 1), 3), p3d_fill, np.float32)
+    _check_free(load().orbm_fisheye_triangulate(n, _p(f(kp1)), _p(f(kp2)), _p(f(sigma1)), _p(f(sigma2)), _p(f(Tlr)), _p(f(cam_params)),
+                                                _p(f(cam_params2)), _p(depth), _p(p3)), "orbm_fisheye_triangulate")
+    return depth[:n], p3[:n]
+
+
+def fisheye_triangulate_device(n, d_kp1, d_kp2, d_sigma1, d_sigma2, Tlr, cam_params, cam_params2, d_depth, d_p3d, stream=None):
+    """The same over device arrays (addresses as ints), asynchronous on `stream` (orbm_fisheye_triangulate_device)."""
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    rc = load().orbm_fisheye_triangulate_device(int(n), _dp(d_kp1), _dp(d_kp2), _dp(d_sigma1), _dp(d_sigma2), _p(f(Tlr)), _p(f(cam_params)),
+                                                _p(f(cam_params2)), _dp(d_depth), _dp(d_p3d), _dp(stream))
+    return _check_free(rc, "orbm_fisheye_triangulate_device")

@@ -298,10 +298,11 @@ __global__ __launch_bounds__(MF_NT) void k_hamming_matrix_mfma(const uint32_t *q
 // inside a super-block the accumulator seed 2^18 + (row index in the block) makes D = ham << 11 | index, a ready (distance, train
 // index) key for the per-lane sorted pair (MfList<2>: one v_min and one v_med3 per key); at the end of a super-block the pair is
 // rewritten with the global train index (ham << 20 | index, nc < 2^20) and merged into the running pair.
-__global__ __launch_bounds__(MF_NT) void k_knn2_mfma(const uint32_t *q, int nq, const uint32_t *c, int nc, int32_t *idx2, int32_t *dist2) {
-  __shared__ __align__(16) uint8_t sA[2][MF_TILE * 256];
+// The product and selection for workgroup `qblock` of MF_NT queries (nq >= 1): returns the query this lane reports and its two keys
+// ham << 20 | train index in `mine`, 0xffffffff where the train set has no such row.  All MF_NT threads call it.
+__device__ __forceinline__ int knn2_mfma_pairs(const uint32_t *q, int nq, const uint32_t *c, int nc, int qblock, uint8_t (*sA)[MF_TILE * 256], uint32_t mine[2]) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, col = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * MF_NT + wid * 64 + col, q1 = q0 + 32;
+  const int q0 = qblock * MF_NT + wid * 64 + col, q1 = q0 + 32;
   mf_v4i B0[8], B1[8];
   mf_b_frags(q + (size_t)min(q0, nq - 1) * 8, h, B0);
   mf_b_frags(q + (size_t)min(q1, nq - 1) * 8, h, B1);
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(MF_NT) void k_knn2_mfma(const uint32_t *q, int nq, 
     fold(g1, L1, sb);
   }
   // the two lanes of a column saw the two halves of every tile: lane h reports tile h's query and merges the partner's pair for it
-  uint32_t mine[2], other[2];
+  uint32_t other[2];
 #pragma unroll
   for (int j = 0; j < 2; j++) {
     mine[j] = h ? g1[j] : g0[j];
@@ -349,7 +350,13 @@ __global__ __launch_bounds__(MF_NT) void k_knn2_mfma(const uint32_t *q, int nq, 
   }
 #pragma unroll
   for (int j = 0; j < 2; j++) { mine[1] = mf_med3(mine[0], mine[1], other[j]); mine[0] = min(mine[0], other[j]); }
-  const int qi = h ? q1 : q0;
+  return h ? q1 : q0;
+}
+
+__global__ __launch_bounds__(MF_NT) void k_knn2_mfma(const uint32_t *q, int nq, const uint32_t *c, int nc, int32_t *idx2, int32_t *dist2) {
+  __shared__ __align__(16) uint8_t sA[2][MF_TILE * 256];
+  uint32_t mine[2];
+  const int qi = knn2_mfma_pairs(q, nq, c, nc, blockIdx.x, sA, mine);
   if (qi < nq) {
 #pragma unroll
     for (int j = 0; j < 2; j++) {

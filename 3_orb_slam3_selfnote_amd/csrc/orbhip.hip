@@ -25,6 +25,7 @@
 #include "orb_project_kernels.h"
 #include "orb_stereo_kernels.h"
 #include "orb_depth_kernels.h"
+#include "orb_rig_stereo_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -184,6 +185,13 @@ float orbx_ref_sinf(float x) { return orbsc::ref_sinf(x); }
 float orbx_ref_atanf(float x) { return orbat::ref_atanf(x); }
 float orbx_ref_atan2f(float y, float x) { return orbat::ref_atan2f(y, x); }
 float orbx_ref_logf(float x) { return orblg::ref_logf(x); }
+float orbx_ref_tanf(float x) { return orbtn::ref_tanf(x); }
+int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream) {
+  if (n < 0 || (n > 0 && (!d_x || !d_y))) return ORBX_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_ref_tanf, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, n, d_y);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
 int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream) {
   if (n < 0 || (n > 0 && (!d_x || !d_y))) return ORBX_E_ARG;
   if (n == 0) return 0;
@@ -1199,6 +1207,7 @@ struct orbm_handle {
   DevBuf d_cand;      // fused k_match_resolve: every pair's descriptors and candidate records in sorted order (48 B per keypoint)
   DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
   DevBuf d_lmq;       // query arrays written by k_local_map_project (orbm_search_local_points*): never shared with d_lfq
+  DevBuf d_knn;       // the two nearest right rows of every left lapping row (orbm_stereo_fisheye_matches*)
   DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
   bool profiling = false;
@@ -1321,7 +1330,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_partner, &m->d_tri_count, &m->d_tri_keys};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_knn, &m->d_partner, &m->d_tri_count, &m->d_tri_keys};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -2113,6 +2122,123 @@ int orbm_rig_concat_batch_device(int nframes, const orbx_keypoint_t *d_keysL, co
   R.keys = reinterpret_cast<uint32_t *>(d_keys); R.desc = reinterpret_cast<uint4 *>(d_desc); R.n = d_n;
   hipLaunchKernelGGL(k_rig_concat, dim3((18 * cap + 255) / 256, nframes), dim3(256), 0, (hipStream_t)stream_, R);
   return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
+// ---- Frame::ComputeStereoFishEyeMatches (Frame.cc:1228-1268) -------------------------------------------------------------------
+int orbm_unproject(const float *cam_params, int n, const float *xy, float *rays) {
+  if (!cam_params || n < 0 || (n > 0 && (!xy || !rays))) return ORBX_E_ARG;
+  for (int i = 0; i < n; i++) kb8_unproject(cam_params, xy[2 * i], xy[2 * i + 1], rays + 3 * (size_t)i);
+  return 0;
+}
+
+int orbm_fisheye_ratio_test(int d0, int d1) { return fisheye_ratio_test(d0, d1) ? 1 : 0; }
+
+static bool fill_triangulate(TriangulateParams &P, int n, const float *kp1, const float *kp2, const float *sigma1, const float *sigma2,
+                             const float *Tlr, const float *cam_params, const float *cam_params2, float *depth, float *p3D) {
+  if (n < 0 || !Tlr || !cam_params || !cam_params2 || (n > 0 && (!kp1 || !kp2 || !sigma1 || !sigma2 || !depth || !p3D))) return false;
+  P.kp1 = kp1; P.kp2 = kp2; P.sigma1 = sigma1; P.sigma2 = sigma2; P.depth = depth; P.p3d = p3D; P.n = n;
+  for (int i = 0; i < 12; i++) P.Tlr[i] = Tlr[i];
+  rig_Tcw2(P.Tlr, P.Tcw2);
+  for (int k = 0; k < 8; k++) { P.cam1[k] = cam_params[k]; P.cam2[k] = cam_params2[k]; }
+  return true;
+}
+
+int orbm_fisheye_triangulate(int n, const float *kp1, const float *kp2, const float *sigma1, const float *sigma2, const float *Tlr,
+                             const float *cam_params, const float *cam_params2, float *depth, float *p3D) {
+  TriangulateParams P;
+  if (!fill_triangulate(P, n, kp1, kp2, sigma1, sigma2, Tlr, cam_params, cam_params2, depth, p3D)) return ORBX_E_ARG;
+  for (int i = 0; i < n; i++)
+    depth[i] = kb8_triangulate_matches(P.cam1, P.cam2, kp1[2 * i], kp1[2 * i + 1], kp2[2 * i], kp2[2 * i + 1], P.Tlr, P.Tcw2, sigma1[i], sigma2[i],
+                                       p3D + 3 * (size_t)i);
+  return 0;
+}
+
+int orbm_fisheye_triangulate_device(int n, const float *d_kp1, const float *d_kp2, const float *d_sigma1, const float *d_sigma2, const float *Tlr,
+                                    const float *cam_params, const float *cam_params2, float *d_depth, float *d_p3D, void *stream) {
+  TriangulateParams P;
+  if (!fill_triangulate(P, n, d_kp1, d_kp2, d_sigma1, d_sigma2, Tlr, cam_params, cam_params2, d_depth, d_p3D)) return ORBX_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_fisheye_triangulate, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
+int orbm_stereo_fisheye_matches_batch_device(orbm_t *m, int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
+                                             const orbx_keypoint_t *d_keysR, const uint8_t *d_descR, const int32_t *d_countsR, int cap,
+                                             const float *level_sigma2, int nlevels, const float *Tlr, const float *cam_params,
+                                             const float *cam_params2, int out_stride, int32_t *d_left_to_right, int32_t *d_right_to_left,
+                                             float *d_depth, float *d_p3d, int32_t *d_nmatches, void *stream_) {
+  if (!m || !d_keysL || !d_descL || !d_countsL || !d_keysR || !d_descR || !d_countsR || !level_sigma2 || !Tlr || !cam_params || !cam_params2 ||
+      !d_left_to_right || !d_right_to_left || !d_depth || !d_p3d)
+    return ORBX_E_ARG;
+  if (nframes < 0 || nframes > 65535 || cap <= 0 || cap > ORBM_FISHEYE_MAX_KEYPOINTS / 2 || out_stride < cap || nlevels < 1 || nlevels > 16) return ORBX_E_ARG;
+  if (nframes == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream_;
+  const size_t kbytes = sizeof(uint32_t) * 2 * (size_t)nframes * (size_t)cap;
+  if (kbytes > m->d_knn.bytes) {   // growth only (as d_partner)
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, m->d_knn.reserve(kbytes + (kbytes >> 2)));
+  }
+  RigStereoParams P;
+  memset(&P, 0, sizeof(P));
+  P.keysL = reinterpret_cast<const uint32_t *>(d_keysL); P.keysR = reinterpret_cast<const uint32_t *>(d_keysR);
+  P.descL = reinterpret_cast<const uint32_t *>(d_descL); P.descR = reinterpret_cast<const uint32_t *>(d_descR);
+  P.countsL = d_countsL; P.countsR = d_countsR; P.cap = cap; P.out_stride = out_stride; P.nlevels = nlevels;
+  for (int l = 0; l < nlevels; l++) P.sigma2[l] = level_sigma2[l];
+  for (int i = 0; i < 12; i++) P.Tlr[i] = Tlr[i];
+  rig_Tcw2(P.Tlr, P.Tcw2);
+  for (int k = 0; k < 8; k++) { P.cam1[k] = cam_params[k]; P.cam2[k] = cam_params2[k]; }
+  P.l2r = d_left_to_right; P.r2l = d_right_to_left; P.depth = d_depth; P.p3d = d_p3d; P.nmatches = d_nmatches;
+  P.knn = (uint32_t *)m->d_knn.p;
+  hipLaunchKernelGGL(k_rig_stereo_knn2, dim3((cap + MF_NT - 1) / MF_NT, nframes), dim3(MF_NT), 0, s, P);
+  hipLaunchKernelGGL(k_rig_stereo_triangulate, dim3((cap + 255) / 256, nframes), dim3(256), 0, s, P);
+  MCHECK(m, hipGetLastError());
+  return 0;
+}
+
+int orbm_stereo_fisheye_matches(orbm_t *m, const orbx_keypoint_t *keysL, const uint8_t *descL, int nL, int monoL, const orbx_keypoint_t *keysR,
+                                const uint8_t *descR, int nR, int monoR, const float *level_sigma2, int nlevels, const float *Tlr,
+                                const float *cam_params, const float *cam_params2, int32_t *left_to_right, int32_t *right_to_left, float *depth,
+                                float *p3d, int32_t *nmatches) {
+  if (!m || !level_sigma2 || !Tlr || !cam_params || !cam_params2 || nL < 0 || nR < 0 || monoL < 0 || monoL > nL || monoR < 0 || monoR > nR) return ORBX_E_ARG;
+  if ((nL > 0 && (!keysL || !descL || !left_to_right || !depth || !p3d)) || (nR > 0 && (!keysR || !descR || !right_to_left))) return ORBX_E_ARG;
+  if (nlevels < 1 || nlevels > 16) return ORBX_E_ARG;
+  const int cap = std::max(std::max(nL, nR), 1);
+  if (cap > ORBM_FISHEYE_MAX_KEYPOINTS / 2) { m->err = "more than 12960 keypoints (left + right) per fisheye-stereo frame not supported"; return ORBX_E_ARG; }
+  // mvLevelSigma2[octave] (:1257) of a lapping keypoint outside the pyramid: refused here, a non-match in the batch form
+  for (int i = monoL; i < nL; i++) if (keysL[i].octave < 0 || keysL[i].octave >= nlevels) return ORBX_E_ARG;
+  for (int j = monoR; j < nR; j++) if (keysR[j].octave < 0 || keysR[j].octave >= nlevels) return ORBX_E_ARG;
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  // one staged block up (p3d is in/out: unmatched entries keep the caller's values), one block down, one synchronisation
+  const int32_t counts[4] = {nL, monoL, nR, monoR};
+  enum { KL, DL, KR, DR, CNT, P3D, L2R, R2L, DEP, NM, NPARTS };
+  void *d[NPARTS];
+  const int rc = stage(m, s, {{keysL, sizeof(orbx_keypoint_t) * (size_t)nL}, {descL, 32 * (size_t)nL}, {keysR, sizeof(orbx_keypoint_t) * (size_t)nR},
+                              {descR, 32 * (size_t)nR}, {counts, sizeof(counts)}, {p3d, 3 * sizeof(float) * (size_t)nL},
+                              {nullptr, sizeof(int32_t) * (size_t)cap}, {nullptr, sizeof(int32_t) * (size_t)cap}, {nullptr, sizeof(float) * (size_t)cap},
+                              {nullptr, 2 * sizeof(int32_t)}}, d, true);
+  if (rc < 0) return rc;
+  const int32_t *cnt = (const int32_t *)d[CNT];
+  // an empty side has no device part: any non-null address stands in, its count keeps every access away
+  const void *kl = d[KL] ? d[KL] : d[CNT], *dl = d[DL] ? d[DL] : d[CNT], *kr = d[KR] ? d[KR] : d[CNT], *dr = d[DR] ? d[DR] : d[CNT];
+  float *dp3 = d[P3D] ? (float *)d[P3D] : (float *)d[DEP];
+  const int rs = orbm_stereo_fisheye_matches_batch_device(m, 1, (const orbx_keypoint_t *)kl, (const uint8_t *)dl, cnt, (const orbx_keypoint_t *)kr,
+                                                          (const uint8_t *)dr, cnt + 2, cap, level_sigma2, nlevels, Tlr, cam_params, cam_params2, cap,
+                                                          (int32_t *)d[L2R], (int32_t *)d[R2L], (float *)d[DEP], dp3, (int32_t *)d[NM], s);
+  if (rs < 0) return rs;
+  const uint8_t *lo = (const uint8_t *)d[P3D] ? (const uint8_t *)d[P3D] : (const uint8_t *)d[L2R];
+  const size_t down = ((const uint8_t *)d[NM] + 2 * sizeof(int32_t)) - lo;
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, down, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  if (nL > 0) {
+    memcpy(p3d, mirror_of(m, d[P3D]), 3 * sizeof(float) * (size_t)nL);
+    memcpy(left_to_right, mirror_of(m, d[L2R]), sizeof(int32_t) * (size_t)nL);
+    memcpy(depth, mirror_of(m, d[DEP]), sizeof(float) * (size_t)nL);
+  }
+  if (nR > 0) memcpy(right_to_left, mirror_of(m, d[R2L]), sizeof(int32_t) * (size_t)nR);
+  if (nmatches) memcpy(nmatches, mirror_of(m, d[NM]), 2 * sizeof(int32_t));
+  return 0;
 }
 
 int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const float *sf, int nlevels,

@@ -135,6 +135,11 @@ float orbx_ref_logf(float x);
 /* The same replica evaluated by the DEVICE: d_y[i] = logf(d_x[i]) for i < n, device pointers, asynchronous on `stream`
  * (tests/test_gpu_local_points.py compares it with orbx_ref_logf).  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
 int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream);
+/* ... and of glibc's tanf (fdlibm's single-precision kernel behind the double reduction of sinf / cosf, glibc 2.28 - 2.40) that
+ * KannalaBrandt8::unproject calls (KannalaBrandt8.cpp:135), csrc/orb_tanf.h, for |x| < 120 (NaN beyond); orbx_tanf_device is the
+ * device's evaluation, as orbx_logf_device. */
+float orbx_ref_tanf(float x);
+int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream);
 
 /* cv::cvtColor(im, gray, CV_RGB2GRAY | CV_BGR2GRAY | CV_RGBA2GRAY | CV_BGRA2GRAY) of Tracking::GrabImageMonocular / Stereo / RGBD
  * (Tracking.cc:1122-1135) for 8-bit input: channels = 3 or 4, rgb_order != 0 for RGB(A), 0 for BGR(A).
@@ -479,6 +484,52 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
 int orbm_rig_concat_batch_device(int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
                                  const orbx_keypoint_t *d_keysR, const uint8_t *d_descR, const int32_t *d_countsR, int cap,
                                  orbx_keypoint_t *d_keys, uint8_t *d_desc, int32_t *d_n, void *stream);
+
+/* ---- Frame::ComputeStereoFishEyeMatches (Frame.cc:1228-1268) ----
+ * The arithmetic, one host/device definition each (csrc/orb_ref_triangulate.h); cameras are KannalaBrandt8 parameter sets
+ * {fx, fy, cx, cy, k0..k3}, Tlr = [mRlr | mtlr] as 12 floats with row stride 4 (a host array, like Trl of the other rig calls).
+ * orbm_unproject: KannalaBrandt8::unproject (KannalaBrandt8.cpp:112-139) of n pixels xy [n][2] into rays [n][3].  Host only.
+ * orbm_fisheye_ratio_test: Lowe's test of Frame.cc:1253 on two Hamming distances, `(float)d0 < (float)d1 * 0.7` in double.
+ * orbm_fisheye_triangulate: KannalaBrandt8::TriangulateMatches (:343-412) of n keypoint pairs kp1 / kp2 [n][2] with
+ * sigma1[i] / sigma2[i] = mvLevelSigma2 of their octaves: depth[i] = z1 or -1, p3D [n][3] written where the function reaches its
+ * end.  No GPU call.  cv::SVD is restated as OpenCV's own float one-sided Jacobi [OPENCV-UNVERIFIED].
+ * orbm_fisheye_triangulate_device: the same over device arrays, asynchronous on `stream`.
+ * All return 0 or ORBX_E_ARG (a NULL pointer, n < 0), the device form also ORBX_E_HIP. */
+int orbm_unproject(const float *cam_params, int n, const float *xy, float *rays);
+int orbm_fisheye_ratio_test(int d0, int d1);
+int orbm_fisheye_triangulate(int n, const float *kp1, const float *kp2, const float *sigma1, const float *sigma2, const float *Tlr,
+                             const float *cam_params, const float *cam_params2, float *depth, float *p3D);
+int orbm_fisheye_triangulate_device(int n, const float *d_kp1, const float *d_kp2, const float *d_sigma1, const float *d_sigma2, const float *Tlr,
+                                    const float *cam_params, const float *cam_params2, float *d_depth, float *d_p3D, void *stream);
+
+/* The whole member for `nframes` resident rig frames: asynchronous on `stream`, no host synchronisation, copy or allocation beyond
+ * growth of the handle's scratch (8 bytes per frame and cap entry).  d_keysL .. d_countsR are what two orbx_extract_batch_device
+ * calls of the same cap wrote; d_counts[f] = {N, monoIndex}, taken into [0, cap] and [0, N]; the lapping rows are [monoIndex, N)
+ * (Frame.cc:1230-1234).  level_sigma2 [nlevels] = mvLevelSigma2, Tlr and both parameter sets are host arrays.
+ * Outputs, `out_stride` entries per frame (2 * cap feeds orbm_search_local_points_fisheye_batch_device directly):
+ *   d_left_to_right[0 .. Nleft), d_right_to_left[0 .. Nright): index in the other image or -1; where several accepted left
+ *     keypoints share a right one, the right one keeps the last in left order (the reference's loop is sequential);
+ *   d_depth[0 .. Nleft) = mvDepth, -1.0f where unmatched (the d_depth of orbx_close_points_batch_device);
+ *   d_p3d [..][3] = mvStereo3Dpoints, written only where matched;
+ *   d_nmatches [nframes][2] = {nMatches, descMatches}, may be NULL.
+ * Live entries are reset before any match is written; entries beyond them are left alone.  A frame without a left lapping row or
+ * with fewer than two right lapping rows has no matches.  A keypoint octave outside [0, nlevels) makes its pair a non-match.
+ * Two kernels: knnMatch(k = 2) on the matrix pipe, one grid over all frames; ratio test + TriangulateMatches, one match per lane.
+ * ORBX_E_ARG: a NULL required pointer, nframes outside [0, 65535], cap <= 0, 2 * cap above ORBM_FISHEYE_MAX_KEYPOINTS,
+ * out_stride < cap, nlevels outside [1, 16].  nframes == 0 returns 0 and launches nothing. */
+int orbm_stereo_fisheye_matches_batch_device(orbm_t *m, int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
+                                             const orbx_keypoint_t *d_keysR, const uint8_t *d_descR, const int32_t *d_countsR, int cap,
+                                             const float *level_sigma2, int nlevels, const float *Tlr, const float *cam_params,
+                                             const float *cam_params2, int out_stride, int32_t *d_left_to_right, int32_t *d_right_to_left,
+                                             float *d_depth, float *d_p3d, int32_t *d_nmatches, void *stream);
+/* One frame from host pointers: one staged upload, the same kernels with nframes = 1, one download, one synchronisation on the
+ * handle's stream.  keysL / descL: mvKeys / mDescriptors (nL rows, lapping from monoL), likewise the right image; the outputs have
+ * nL, nR, nL and nL * 3 entries (p3d is in/out: unmatched entries keep the caller's values); nmatches [2] may be NULL.
+ * ORBX_E_ARG also for a lapping keypoint whose octave is outside [0, nlevels). */
+int orbm_stereo_fisheye_matches(orbm_t *m, const orbx_keypoint_t *keysL, const uint8_t *descL, int nL, int monoL, const orbx_keypoint_t *keysR,
+                                const uint8_t *descR, int nR, int monoR, const float *level_sigma2, int nlevels, const float *Tlr,
+                                const float *cam_params, const float *cam_params2, int32_t *left_to_right, int32_t *right_to_left, float *depth,
+                                float *p3d, int32_t *nmatches);
 
 /* Batched device form of orbm_search_by_projection_last_frame_fisheye (ORBmatcher.cc:2027-2289 for CurrentFrame.Nleft != -1,
  * with the right-camera pass :2189-2256): `npairs` independent (current rig frame, last frame) problems, everything resident
