@@ -30,12 +30,12 @@ __constant__ __attribute__((aligned(16))) int8_t c_pattern[1024] = {
 // Stored per lane: lane L handles disc pixels L, 64+L, ..., 704+L; its twelve u offsets are bytes 0..11 and its twelve
 // v offsets bytes 12..23 of w[L][0..5], so one lane fetches its share of the table with two wide loads.
 struct DiscTab { uint32_t w[64][6]; };
+constexpr int kDiscUmax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
 constexpr DiscTab make_disc_tab() {
   DiscTab t{};
-  const int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
   int n = 0;
   for (int v = -15; v <= 15; v++) {
-    const int d = umax[v < 0 ? -v : v];
+    const int d = kDiscUmax[v < 0 ? -v : v];
     for (int u = -d; u <= d; u++) {
       const int lane = n & 63, k = n >> 6;  // pixel n = k * 64 + lane
       t.w[lane][k >> 2] |= (uint32_t)(uint8_t)(int8_t)u << (8 * (k & 3));
@@ -46,6 +46,12 @@ constexpr DiscTab make_disc_tab() {
   return t;  // pixels 749..767 stay (0, 0)
 }
 __constant__ __attribute__((aligned(16))) DiscTab c_disc = make_disc_tab();
+// the same umax, four bits per row distance |v|: the block form of k_describe derives its per-row weights from it in registers
+constexpr uint64_t make_disc_umax_nibbles() {
+  uint64_t p = 0;
+  for (int v = 0; v < 16; v++) p |= (uint64_t)kDiscUmax[v] << (4 * v);
+  return p;
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // small helpers
@@ -1562,17 +1568,30 @@ __device__ __forceinline__ void describe_block(const FrameParams &P) {
   const uint32_t dmaMask = (uint32_t)__ballot(valid && ((((uintptr_t)img) | (uintptr_t)pitch) & 3u) == 0);
   const uint32_t cenLo = (uint32_t)(uintptr_t)centre, cenHi = (uint32_t)((uintptr_t)centre >> 32);
 
-  // ---- lane only: my 12 disc pixels (offsets kept packed: they are the dot products' operands), their places in the 48-byte-pitch
-  // window, my two 16-byte chunks of a window (chunk idx = row 3 r + c; idx / 3 as (idx * 21846) >> 16, exact below 111)
-  const uint4 dw0 = *reinterpret_cast<const uint4 *>(&c_disc.w[lane][0]);
-  const uint2 dw1 = *reinterpret_cast<const uint2 *>(&c_disc.w[lane][4]);
-  const uint32_t uw[3] = {dw0.x, dw0.y, dw0.z}, vw[3] = {dw0.w, dw1.x, dw1.y};
-  uint32_t doff2[6];   // two 16-bit places per register (the adds below select the half word: no unpacking, six registers fewer)
+  // ---- lane only: my share of a disc window, and my two 16-byte chunks of a window (chunk idx = row 3 r + c; idx / 3 as
+  // (idx * 21846) >> 16, exact below 111).
+  // A window holds the disc as 31 rows of 48 bytes, disc column c = u + 15 at byte o + c of its row, o = (X - 15) & 3.  Lane L < 62
+  // takes row L >> 1 and the columns 16 (L & 1) .. + 15 of it (column 31 lies outside the disc): bytes 16 (L & 1) .. + 19 of the row
+  // come in with one aligned 16-byte read and one dword, four v_alignbyte_b32 by the wave-uniform o bring the 16 columns to byte 0,
+  // and eight signed dot products against per-lane weights sum u * pixel and v * pixel: wu holds the column's u where (u, v) is
+  // inside the disc (|u| <= umax[|v|], the definition behind c_disc) and 0 elsewhere, wv the row's v or 0.  |u|, |v| <= 15: signed bytes.
+  const int drow = min(lane >> 1, 30), dhalf = lane & 1, dvv = drow - 15;
+  const uint32_t rowOff = (uint32_t)(drow * 48 + 16 * dhalf);
+  uint32_t wu[4], wv[4];
+  {
+    const int d = (int)((make_disc_umax_nibbles() >> (4 * (dvv < 0 ? -dvv : dvv))) & 15u);
+    // my columns inside the disc are the bytes [first, end) of my 16: u = byte - 15 >= -d in the left half, u = byte + 1 <= d in the right
+    const int first = dhalf ? 0 : 15 - d, end = lane < 62 ? (dhalf ? d : 16) : first;
+    const uint32_t vrep = (uint32_t)(dvv & 0xff) * 0x01010101u;
 #pragma unroll
-  for (int t = 0; t < 12; t += 2) {
-    auto place = [&](int tt) { return (uint32_t)((int)(int8_t)(vw[tt >> 2] >> (8 * (tt & 3))) * 48 + (int)(int8_t)(uw[tt >> 2] >> (8 * (tt & 3))) + 15 * 48 + 15); };
-    doff2[t >> 1] = place(t) | (place(t + 1) << 16);
-    asm volatile("" : "+v"(doff2[t >> 1]));   // opaque: otherwise every keypoint re-derives it from the packed offsets
+    for (int i = 0; i < 4; i++) {
+      const int lo = min(max(first - 4 * i, 0), 4), hi = min(max(end - 4 * i, 0), 4);
+      const uint32_t inside = (uint32_t)(0xffffffffull << (8 * lo)) & ~(uint32_t)(0xffffffffull << (8 * hi));
+      auto ub = [](int u0) { return (uint32_t)(uint8_t)u0 | ((uint32_t)(uint8_t)(u0 + 1) << 8) | ((uint32_t)(uint8_t)(u0 + 2) << 16) | ((uint32_t)(uint8_t)(u0 + 3) << 24); };
+      wu[i] = (dhalf ? ub(4 * i + 1) : ub(4 * i - 15)) & inside;
+      wv[i] = vrep & inside;
+      asm volatile("" : "+v"(wu[i]), "+v"(wv[i]));   // opaque: otherwise every keypoint re-derives them
+    }
   }
   const uint32_t cr0 = ((uint32_t)lane * 21846u) >> 16, cc0 = 16u * ((uint32_t)lane - 3u * cr0);
   const uint32_t cr1 = ((uint32_t)(lane + 64) * 21846u) >> 16, cc1 = 16u * ((uint32_t)(lane + 64) - 3u * cr1);
@@ -1598,7 +1617,8 @@ __device__ __forceinline__ void describe_block(const FrameParams &P) {
 
   // ---- moments (IC_Angle).  Keypoint k's window is requested while k - 1's is read; the waits are counted: two DMA instructions
   // per window, loads retire in order.  With d = pixel - 128 as a signed byte, sum u * d differs from sum u * pixel by 128 * sum u,
-  // and the disc's offsets sum to zero over the wavefront, so the signed dot products give m10 and m01 exactly.
+  // and the disc's offsets - in either form, the row weights or c_disc's twelve pixels per lane - sum to zero over the wavefront,
+  // so the signed dot products give m10 and m01 exactly.
   if (dmaMask & 1u) issue_disc(0);
   auto one = [&](auto kc, int &p10, int &p01) {
     constexpr int k = decltype(kc)::value;
@@ -1606,35 +1626,47 @@ __device__ __forceinline__ void describe_block(const FrameParams &P) {
     if (nextDma) issue_disc(k + 1);
     p10 = 0; p01 = 0;
     if ((validMask >> k) & 1u) {
-      uint32_t dval[12], dpk[3];   // my 12 pixels, and packed four to a word (inside each path: the loads' zero extension is known there)
       const uintptr_t cen = centre_of(cenLo, cenHi, k);
       if ((dmaMask >> k) & 1u) {
         if (nextDma) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const LdsBytes dc = (LdsBytes)(myLds + (k & 1) * DESC_BUF + ((cen - 15) & 3));
+        // (in assembly: on a ds_read_b128 of its own making the compiler drains the DMA queue first, window k + 1 included, which
+        // the counted wait above has just let travel on)
+        const uint32_t rp = (uint32_t)(uintptr_t)(LdsBytes)myLds + rowOff;   // a 32-bit LDS address
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 q;
+        uint32_t q4;
+        asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b32 %1, %2 offset:%4\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(q), "=&v"(q4) : "v"(rp), "n"((k & 1) * DESC_BUF), "n"((k & 1) * DESC_BUF + 16) : "memory");
+        const uint32_t raw[5] = {q.x, q.y, q.z, q.w, q4};
+        const uint32_t o = (uint32_t)((cen - 15) & 3);
 #pragma unroll
-        for (int t = 0; t < 12; t++) dval[t] = dc[(t & 1) ? doff2[t >> 1] >> 16 : doff2[t >> 1] & 0xffffu];
-#pragma unroll
-        for (int g = 0; g < 3; g++) dpk[g] = (dval[4 * g] | (dval[4 * g + 1] << 8)) | ((dval[4 * g + 2] | (dval[4 * g + 3] << 8)) << 16);
+        for (int g = 0; g < 4; g++) {
+          const uint32_t d = __builtin_amdgcn_alignbyte(raw[g + 1], raw[g], o) ^ 0x80808080u;
+          p10 = __builtin_amdgcn_sdot4((int)wu[g], (int)d, p10, false);
+          p01 = __builtin_amdgcn_sdot4((int)wv[g], (int)d, p01, false);
+        }
       } else {
-        const GlobalBytes cp = (GlobalBytes)cen;
-        const int p = __builtin_amdgcn_readlane(pitch, k);
-        // (unpacked from opaque copies: shared with the other keypoints' copies of this rare path, the 24 offsets would live in
-        // registers of their own through the whole block)
-        uint32_t uo[3], vo[3];
-#pragma unroll
-        for (int g = 0; g < 3; g++) { uo[g] = uw[g]; vo[g] = vw[g]; asm volatile("" : "+v"(uo[g]), "+v"(vo[g])); }
+        // a level 0 that is not dword-aligned (the caller's buffer): the lane's twelve disc pixels of c_disc, gathered from global
+        // memory (the table is read here, inside the rare path, through an opaque copy of the lane index: read once for all keypoints,
+        // its six registers would be live through the whole block)
+        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane(pitch, k);
+        const GlobalBytes cp = (GlobalBytes)cen - (15 * (size_t)p + 15);   // the window's first pixel: uniform base, unsigned 32-bit offsets
+        int tl = lane;
+        asm volatile("" : "+v"(tl));
+        const uint4 dw0 = *reinterpret_cast<const uint4 *>(&c_disc.w[tl][0]);
+        const uint2 dw1 = *reinterpret_cast<const uint2 *>(&c_disc.w[tl][4]);
+        const uint32_t uw[3] = {dw0.x, dw0.y, dw0.z}, vw[3] = {dw0.w, dw1.x, dw1.y};
+        uint32_t dval[12];
 #pragma unroll
         for (int t = 0; t < 12; t++)
-          dval[t] = cp[(int)(int8_t)(vo[t >> 2] >> (8 * (t & 3))) * p + (int)(int8_t)(uo[t >> 2] >> (8 * (t & 3)))];
+          dval[t] = cp[(uint32_t)((int)(int8_t)(vw[t >> 2] >> (8 * (t & 3))) + 15) * p + (uint32_t)((int)(int8_t)(uw[t >> 2] >> (8 * (t & 3))) + 15)];
 #pragma unroll
-        for (int g = 0; g < 3; g++) dpk[g] = (dval[4 * g] | (dval[4 * g + 1] << 8)) | ((dval[4 * g + 2] | (dval[4 * g + 3] << 8)) << 16);
-      }
-#pragma unroll
-      for (int g = 0; g < 3; g++) {
-        const uint32_t d = dpk[g] ^ 0x80808080u;
-        p10 = __builtin_amdgcn_sdot4((int)uw[g], (int)d, p10, false);
-        p01 = __builtin_amdgcn_sdot4((int)vw[g], (int)d, p01, false);
+        for (int g = 0; g < 3; g++) {
+          const uint32_t d = ((dval[4 * g] | (dval[4 * g + 1] << 8)) | ((dval[4 * g + 2] | (dval[4 * g + 3] << 8)) << 16)) ^ 0x80808080u;
+          p10 = __builtin_amdgcn_sdot4((int)uw[g], (int)d, p10, false);
+          p01 = __builtin_amdgcn_sdot4((int)vw[g], (int)d, p01, false);
+        }
       }
     }
   };

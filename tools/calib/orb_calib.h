@@ -77,6 +77,10 @@ enum CalibOp {
   CAL_DS_READ_U8,     // ds_read_u8 with a per-lane address (LDS issue rate as k_fast's gathers see it)
   CAL_XOR_SGPR,       // v_xor_b32 with a scalar-register source (k_match_scan: candidate descriptor words in SGPRs)
   CAL_BCNT_SGPR,      // v_bcnt_u32_b32 fed by such a xor is VGPR-only; this one counts a scalar source directly
+  CAL_PK_MINIMUM3_F16,  // v_pk_minimum3_f16 (gfx950; k_fast score network, operands held to positive normal numbers as there)
+  CAL_PK_MAXIMUM3_F16,  // v_pk_maximum3_f16
+  CAL_MAD_U32_U16,      // v_mad_u32_u16        16-bit factors, 32-bit result (k_resize pass 2)
+  CAL_MAD_U32_U16_HI,   // v_mad_u32_u16 op_sel:[0,1,0,0]: the second factor is the high half of its register
   CAL_NUM_OPS
 };
 
@@ -89,7 +93,8 @@ static const char *const kCalibOpNames[CAL_NUM_OPS] = {
     "v_bitop3_b32", "v_cndmask_b32 (SGPR-pair mask)", "v_cndmask_b32 (vcc, scalar-written)", "v_add_f32", "v_mul_f32", "v_cvt_f32_u32",
     "v_add_co_u32", "v_min_f32/v_max_f32", "v_min3_f32", "v_max3_f32", "v_med3_f32", "v_pk_min_f16/v_pk_max_f16", "v_pk_fma_f16", "v_pk_add_f16",
     "v_min_f16/v_max_f16", "v_min_u16/v_max_u16", "v_cvt_f32_ubyte0", "v_sub_f32", "v_max3_u32", "v_pk_min_u16/v_pk_max_u16", "v_addc_co_u32",
-    "s_add_u32", "s_and_b64/s_bcnt1_i32_b64", "ds_read_u8", "v_xor_b32 (SGPR source)", "v_bcnt_u32_b32 (SGPR source)"};
+    "s_add_u32", "s_and_b64/s_bcnt1_i32_b64", "ds_read_u8", "v_xor_b32 (SGPR source)", "v_bcnt_u32_b32 (SGPR source)", "v_pk_minimum3_f16", "v_pk_maximum3_f16",
+    "v_mad_u32_u16", "v_mad_u32_u16 op_sel:[0,1,0,0]"};
 
 #define CAL_INSTR_PER_TRIP 128
 
@@ -169,6 +174,10 @@ static const char *const kCalibOpNames[CAL_NUM_OPS] = {
 #define I_PKMINU(d) "v_pk_min_u16 %" #d ", %" #d ", %16\n"
 #define I_PKMAXU(d) "v_pk_max_u16 %" #d ", %" #d ", %17\n"
 #define I_ADDC(d) "v_addc_co_u32 %" #d ", vcc, %" #d ", %16, vcc\n"
+#define I_PKMIN3H(d) "v_pk_minimum3_f16 %" #d ", %" #d ", %16, %17\n"
+#define I_PKMAX3H(d) "v_pk_maximum3_f16 %" #d ", %" #d ", %16, %17\n"
+#define I_MAD16(d) "v_mad_u32_u16 %" #d ", %16, %" #d ", %17\n"
+#define I_MAD16HI(d) "v_mad_u32_u16 %" #d ", %16, %" #d ", %17 op_sel:[0,1,0,0]\n"
 #define I_LSHLADD64(d) "v_lshl_add_u64 %" #d ", %" #d ", 1, %16\n"
 
 // stamps[block] = {shader-clock ticks, 100 MHz reference ticks} of the block's first wavefront around its loop
@@ -203,6 +212,10 @@ __global__ __launch_bounds__(256) void k_calib_valu(uint32_t *sink, unsigned lon
     uint32_t r[16], a = t * 2654435761u + 12345u, b = (t ^ 0x9e3779b9u) * 40503u + 7u;
     for (int i = 0; i < 16; i++) r[i] = (t + i) * 747796405u + 2891336453u;
     if constexpr (OP == CAL_PERM) b = 0x06010400u | ((t & 1) << 8);  // a valid byte selector
+    if constexpr (OP == CAL_PK_MINIMUM3_F16 || OP == CAL_PK_MAXIMUM3_F16) {   // both halves of every operand in [0x0701, 0x08ff]
+      a = 0x07010701u + (a & 0x01ff01ffu); b = 0x07010701u + (b & 0x01ff01ffu);
+      for (int i = 0; i < 16; i++) r[i] = 0x07010701u + (r[i] & 0x01ff01ffu);
+    }
     for (int it = 0; it < trips; ++it) {
       if constexpr (OP == CAL_ADD_U32) asm volatile(CAL_TRIP(I_ADD) CAL_OPERANDS);
       if constexpr (OP == CAL_XOR_B32) asm volatile(CAL_TRIP(I_XOR) CAL_OPERANDS);
@@ -285,6 +298,10 @@ __global__ __launch_bounds__(256) void k_calib_valu(uint32_t *sink, unsigned lon
       }
       if constexpr (OP == CAL_XOR_SGPR) asm volatile("s_mov_b32 s20, 0x5bd1e995\n" CAL_TRIP(I_XORS) CAL_OPERANDS, "s20");
       if constexpr (OP == CAL_BCNT_SGPR) asm volatile("s_mov_b32 s20, 0x5bd1e995\n" CAL_TRIP(I_BCNTS) CAL_OPERANDS, "s20");
+      if constexpr (OP == CAL_PK_MINIMUM3_F16) asm volatile(CAL_TRIP(I_PKMIN3H) CAL_OPERANDS);
+      if constexpr (OP == CAL_PK_MAXIMUM3_F16) asm volatile(CAL_TRIP(I_PKMAX3H) CAL_OPERANDS);
+      if constexpr (OP == CAL_MAD_U32_U16) asm volatile(CAL_TRIP(I_MAD16) CAL_OPERANDS);
+      if constexpr (OP == CAL_MAD_U32_U16_HI) asm volatile(CAL_TRIP(I_MAD16HI) CAL_OPERANDS);
       if constexpr (OP == CAL_FAST_MIX)
         asm volatile(CAL_R16(I_PKMIN) CAL_R16(I_PKMIN) CAL_R16(I_PKMAX) CAL_R16(I_PKMIN) CAL_R16(I_PKMAD) CAL_R16(I_PKMIN) CAL_R16(I_ADD)
                          CAL_R16(I_ADD) CAL_OPERANDS);

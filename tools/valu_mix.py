@@ -33,6 +33,7 @@ CLASS_OF = {
     "v_fmac_f32": "v_fma_f32", "v_add_f32": "v_add_f32", "v_sub_f32": "v_sub_f32", "v_subrev_f32": "v_sub_f32", "v_mul_f32": "v_mul_f32",
     "v_bitop3_b32": "v_bitop3_b32", "v_min_u32": "v_min_u32/v_max_u32", "v_max_u32": "v_min_u32/v_max_u32", "v_min_i32": "v_min_i32/v_max_i32",
     "v_max_i32": "v_min_i32/v_max_i32", "v_pk_min_i16": "v_pk_min_i16/v_pk_max_i16", "v_pk_max_i16": "v_pk_min_i16/v_pk_max_i16",
+    "v_pk_minimum3_f16": "v_pk_minimum3_f16", "v_pk_maximum3_f16": "v_pk_maximum3_f16", "v_mad_u32_u16": "v_mad_u32_u16",
     "v_pk_mad_u16": "v_pk_mad_u16", "v_pk_add_u16": "v_pk_add_u16", "v_pk_sub_i16": "v_pk_sub_i16", "v_bcnt_u32_b32": "v_bcnt_u32_b32",
     "v_dot4_u32_u8": "v_dot4_u32_u8", "v_dot2_u32_u16": "v_dot2_u32_u16", "v_perm_b32": "v_perm_b32", "v_alignbyte_b32": "v_alignbyte_b32",
     "v_alignbit_b32": "v_alignbyte_b32", "v_mul_u32_u24": "v_mul_u32_u24", "v_mul_i32_i24": "v_mul_u32_u24", "v_mad_u32_u24": "v_mad_u32_u24",
