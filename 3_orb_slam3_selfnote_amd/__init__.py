@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -197,6 +197,7 @@ def load(build_if_needed=True):
     L.orbm_search_for_triangulation.argtypes = [vp] * 10 + [i32, i32, i32, vp]
     L.orbm_triangulation_candidates.argtypes = [vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, i32]
     L.orbm_search_for_triangulation_pred.argtypes = [vp, vp, vp, f32, f32, i32, i32, i32, i32, PAIR_PRED, vp, vp]
+    L.orbm_search_for_triangulation_kb8.argtypes = [vp, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, i32, i32, vp]
     L.orbm_search_by_projection_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp]
     L.orbm_search_by_projection_keyframe.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32, i32, vp, vp]
     L.orbm_search_by_projection_last_frame.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32,
@@ -1007,6 +1008,29 @@ class ORBmatcher:
         self._check(rc, "orbm_search_for_triangulation_pred")
         if rc < 0:
             raise OrbError("orbm_search_for_triangulation_pred rc=%d" % rc)
+        m12 = m12[:KF1.N]
+        i1 = np.nonzero(m12 >= 0)[0]
+        return rc, np.stack([i1, m12[i1]], axis=1).astype(np.int64)
+
+    def SearchForTriangulationKB8(self, KF1, KF2, ep, cams1, cams2, T12, n_left1=-1, n_left2=-1, bOnlyStereo=False, bCoarse=False):
+        """SearchForTriangulation between KannalaBrandt8 keyframes (n_left == -1) or two-camera KannalaBrandt8 rigs (n_left = NLeft, the
+        views hold [mvKeys; mvKeysRight]) with KannalaBrandt8::epipolarConstrain on the device (orbm_search_for_triangulation_kb8).
+        cams? [8] or [2, 8], T12 [12] or [4, 12] = [R12 | t12] per camera pair ll, lr, rl, rr.  Returns (nmatches, vMatchedPairs [k, 2])."""
+        rig = n_left1 != -1 or n_left2 != -1
+        a = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1) if x is not None else None   # None: the ABI's refusal
+        cams1, cams2, T12 = a(cams1), a(cams2), a(T12)
+        for v, per in ((cams1, 8), (cams2, 8), (T12, 12)):
+            if v is not None and len(v) != per * ((2 if per == 8 else 4) if rig else 1):
+                raise ValueError("SearchForTriangulationKB8: %d floats where %s are expected" % (len(v), "2 x 8 / 4 x 12" if rig else "8 / 12"))
+        s1, s2 = KF1.struct(), KF2.struct()
+        m12 = np.full(max(KF1.N, 1), -1, dtype=np.int32)
+        rc = self.L.orbm_search_for_triangulation_kb8(self.m, C.byref(s1), int(n_left1), C.byref(s2), int(n_left2), C.c_float(ep[0]), C.c_float(ep[1]),
+                                                      _p(cams1) if cams1 is not None else None, _p(cams2) if cams2 is not None else None,
+                                                      _p(T12) if T12 is not None else None, int(bool(bOnlyStereo)), int(bool(bCoarse)),
+                                                      int(self.mbCheckOrientation), _p(m12))
+        self._check(rc, "orbm_search_for_triangulation_kb8")
+        if rc < 0:
+            raise OrbError("orbm_search_for_triangulation_kb8 rc=%d" % rc)
         m12 = m12[:KF1.N]
         i1 = np.nonzero(m12 >= 0)[0]
         return rc, np.stack([i1, m12[i1]], axis=1).astype(np.int64)

@@ -17,15 +17,16 @@
 //   SearchByProjection(KeyFrame*, cv::Mat Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, ...)  :604-720
 //   SearchByBoW(KeyFrame*, Frame&, ...) / SearchByBoW(KeyFrame*, KeyFrame*, ...)                    :273-469 / :839-979
 //   SearchForInitialization                                                                         :722-837
-//   SearchForTriangulation(..., bOnlyStereo, bCoarse)                                               :981-1222  (Pinhole keyframes)
+//   SearchForTriangulation(..., bOnlyStereo, bCoarse)                                               :981-1222  (Pinhole / KannalaBrandt8 keyframes, KannalaBrandt8 rigs)
 //   SearchForTriangulation(..., bOnlyStereo, vMatchedPoints)                                        :1224-1413 (no call site)
 //   SearchBySim3                                                                                    :1788-2012
 //   Fuse(KeyFrame*, vpMapPoints, th, bRight) / Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)   :1425-1658 / :1660-1786
 //   DescriptorDistance, ComputeThreeMaxima, RadiusByViewingCos                                      :2463-2483, :2416-2458, :216-222
 //   CheckDistEpipolarLine, CheckDistEpipolarLine2                                                   :225-267   (no call site)
-// SearchForTriangulation between keyframes whose camera is not a Pinhole model or that carry a second camera: the epipolar test is the
-// reference's own virtual pCamera1->epipolarConstrain (KannalaBrandt8's triangulates with cv::SVD), called
-// as a predicate on the candidate pairs the device delivers (SearchForTriangulationGeneric below); everything else is on the device.
+// SearchForTriangulation between keyframes whose camera is not a Pinhole model or that carry a second camera (SearchForTriangulationGeneric
+// below): with KannalaBrandt8 cameras throughout the whole member runs on the device (orbm_search_for_triangulation_kb8); with any other
+// model the epipolar test is the reference's own virtual pCamera1->epipolarConstrain, called as a predicate on the candidate pairs the
+// device delivers, and everything else is on the device.
 #include "ORBmatcher.h"  // the reference's header, unmodified
 
 #include <cmath>
@@ -485,10 +486,11 @@ int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint
 }
 
 // SearchForTriangulation for KannalaBrandt8 keyframes and two-camera rigs (ORBmatcher.cc:981-1222 with a non-Pinhole
-// epipolarConstrain at :1148).  KannalaBrandt8::epipolarConstrain triangulates with cv::SVD and stays the reference's own code
-// (SURVEY.md section 2 row 4); everything in front of it - the vocabulary-node walk, the Hamming distances, TH_LOW, the stereo
-// filter, the epipole gate - runs on the device (orbm_search_for_triangulation_pred), which then asks this predicate about the
-// surviving pairs in the reference's order of preference.
+// epipolarConstrain at :1148).  With KannalaBrandt8 cameras on both sides the library also evaluates the test itself
+// (orbm_search_for_triangulation_kb8: TriangulateMatches on the device, cv::SVD restated, [OPENCV-UNVERIFIED]).  For any other camera
+// model the test stays the reference's own code: everything in front of it - the vocabulary-node walk, the Hamming distances, TH_LOW,
+// the stereo filter, the epipole gate - runs on the device (orbm_search_for_triangulation_pred), which then asks this predicate about
+// the surviving pairs in the reference's order of preference.
 namespace {
 struct TriangulationPredicate {
   KeyFrame *pKF1, *pKF2;
@@ -561,8 +563,32 @@ int SearchForTriangulationGeneric(ORBmatcher *self, KeyFrame *pKF1, KeyFrame *pK
   };
   Side A(pKF1), B(pKF2);
   std::vector<int32_t> m12(pKF1->N > 0 ? pKF1->N : 1, -1);
-  const int n = checked(orbm_search_for_triangulation_pred(matcher(), &A.k, &B.k, ep.x, ep.y, pKF1->mpCamera2 ? 0 : 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0,
-                                                           checkOri ? 1 : 0, &TriangulationPredicate::call, &P, m12.data()));
+  // Every camera involved a KannalaBrandt8 (CAM_FISHEYE = 1) and both keyframes of one kind: epipolarConstrain is
+  // TriangulateMatches(...) > 0.0001f (KannalaBrandt8.cpp:244-247), which the library evaluates on the device.
+  const bool rig = pKF1->mpCamera2 && pKF2->mpCamera2;
+  bool fisheye = (pKF1->mpCamera2 != NULL) == (pKF2->mpCamera2 != NULL) && (pKF1->NLeft != -1) == rig && (pKF2->NLeft != -1) == rig &&
+                 pKF1->mpCamera->GetType() == 1 && pKF2->mpCamera->GetType() == 1;
+  if (fisheye && rig) fisheye = pKF1->mpCamera2->GetType() == 1 && pKF2->mpCamera2->GetType() == 1;
+  int n;
+  if (fisheye) {
+    float cams1[2][8] = {}, cams2[2][8] = {}, T12[4][12] = {};
+    for (int k = 0; k < 8; k++) {
+      cams1[0][k] = pKF1->mpCamera->getParameter(k); cams2[0][k] = pKF2->mpCamera->getParameter(k);
+      if (rig) { cams1[1][k] = pKF1->mpCamera2->getParameter(k); cams2[1][k] = pKF2->mpCamera2->getParameter(k); }
+    }
+    const cv::Mat *R[4] = {&P.Rll, &P.Rlr, &P.Rrl, &P.Rrr}, *t[4] = {&P.tll, &P.tlr, &P.trl, &P.trr};   // the order of :1011-1019
+    if (!rig) { R[0] = &P.R12; t[0] = &P.t12; }
+    for (int p = 0; p < (rig ? 4 : 1); p++)
+      for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) T12[p][4 * r + c] = R[p]->at<float>(r, c);
+        T12[p][4 * r + 3] = t[p]->at<float>(r);
+      }
+    n = checked(orbm_search_for_triangulation_kb8(matcher(), &A.k, rig ? pKF1->NLeft : -1, &B.k, rig ? pKF2->NLeft : -1, ep.x, ep.y, &cams1[0][0], &cams2[0][0],
+                                                  &T12[0][0], bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, checkOri ? 1 : 0, m12.data()));
+  } else {
+    n = checked(orbm_search_for_triangulation_pred(matcher(), &A.k, &B.k, ep.x, ep.y, pKF1->mpCamera2 ? 0 : 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0,
+                                                   checkOri ? 1 : 0, &TriangulationPredicate::call, &P, m12.data()));
+  }
   vMatchedPairs.clear();
   vMatchedPairs.reserve(n);
   for (int i = 0; i < pKF1->N; i++)

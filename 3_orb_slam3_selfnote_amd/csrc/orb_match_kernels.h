@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "orb_mfma_util.h"
+#include "orb_ref_triangulate.h"
 
 #define MATCH_NT 256
 
@@ -1734,25 +1735,48 @@ __global__ __launch_bounds__(256) void k_triangulation_match(TriParams T) {
 }
 
 // SearchForTriangulation for keyframes whose epipolar test is NOT Pinhole's (KannalaBrandt8, two-camera rigs; ORBmatcher.cc:1096-1153
-// with pCamera1->epipolarConstrain(...) a virtual call into code outside this path): the device delivers, per unmatched keypoint of KF1,
-// EVERY keypoint of KF2 in the same vocabulary node that passes the gates in front of the predicate - no map point (:1083), stereo
-// filter (:1088-1090), distance <= TH_LOW (:1096), epipole distance (:1105-1113) - as keys dist << 16 | (0xffff - position); the host
-// orders them and the caller's predicate picks (orbm_search_for_triangulation_pred).  One wavefront per item; the segment of the
-// output buffer comes from one atomicAdd per wavefront, a segment that would not fit is counted but not written.
+// with pCamera1->epipolarConstrain(...) a virtual call): the device delivers, per unmatched keypoint of KF1, EVERY keypoint of KF2 in
+// the same vocabulary node that passes the gates in front of the predicate - no map point (:1083), stereo filter (:1088-1090),
+// distance <= TH_LOW (:1096), epipole distance (:1105-1113) - as keys dist << 16 | (0xffff - position).  Two consumers:
+//   * orbm_search_for_triangulation_pred: the host orders each item's segment and the caller's predicate picks;
+//   * orbm_search_for_triangulation_kb8: k_triangulation_kb8_predicate evaluates KannalaBrandt8's test on every key of the compact
+//     list (key_item = the item of each key) and keeps the minimum accepted key per item.
+// One wavefront per item; the segment of the output buffer comes from one atomicAdd per wavefront, a segment that would not fit is
+// counted but not written.
 struct TriCandParams {
   const float *kp2;
   const uint32_t *desc1, *desc2;
-  const float *ur1, *ur2;
+  const float *ur1, *ur2;         // mvuRight; NULL for a two-camera rig: bStereo is false for every keypoint (:1057, :1086)
   const uint8_t *hasmp2;
   const int32_t *node_idx2;
   const TriItem *items; int nitems;
   float sf2[ORBX_MAX_LEVELS];
   float epx, epy;
   int epipole_gate, bOnlyStereo;
-  int32_t *item_off, *item_cnt;   // per item
+  int32_t *item_off, *item_cnt;   // per item, or NULL
   uint32_t *keys; int cap;        // output buffer
+  int32_t *key_item;              // [cap] item of every key, or NULL
   int32_t *total;                 // running total (allocation counter)
 };
+
+// The candidate key of member j of the item's node of KF2, 0xffffffff: not a candidate
+__device__ __forceinline__ uint32_t tri_key_of(const TriCandParams &T, const TriItem &item, const uint32_t (&d1)[8], bool bStereo1, int j) {
+  const int idx2 = T.node_idx2[item.start2 + j];
+  if (T.hasmp2[idx2]) return 0xffffffffu;                               // :1083 (vbMatched2 is never set)
+  const bool bStereo2 = T.ur2 && T.ur2[idx2] >= 0.f;
+  if (T.bOnlyStereo && !bStereo2) return 0xffffffffu;                   // :1088-1090
+  int dist = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) dist += __popc(d1[w] ^ T.desc2[(size_t)idx2 * 8 + w]);
+  if (dist > ORBM_TH_LOW) return 0xffffffffu;                           // :1096
+  if (T.epipole_gate && !bStereo1 && !bStereo2) {                       // :1105-1113
+    const float x2 = T.kp2[(size_t)idx2 * 7], y2 = T.kp2[(size_t)idx2 * 7 + 1];
+    const int oct2 = __float_as_int(T.kp2[(size_t)idx2 * 7 + 5]);
+    const float distex = T.epx - x2, distey = T.epy - y2;
+    if (distex * distex + distey * distey < 100 * T.sf2[oct2 & (ORBX_MAX_LEVELS - 1)]) return 0xffffffffu;
+  }
+  return ((uint32_t)dist << 16) | (uint32_t)(0xffff - j);
+}
 
 __global__ __launch_bounds__(256) void k_triangulation_candidates(TriCandParams T) {
   const int lane = threadIdx.x & 63;
@@ -1763,41 +1787,82 @@ __global__ __launch_bounds__(256) void k_triangulation_candidates(TriCandParams 
   uint32_t d1[8];
 #pragma unroll
   for (int w = 0; w < 8; w++) d1[w] = T.desc1[(size_t)idx1 * 8 + w];
-  const bool bStereo1 = T.ur1[idx1] >= 0.f;
-  auto key_of = [&](int j) -> uint32_t {      // 0xffffffff: not a candidate
-    const int idx2 = T.node_idx2[item.start2 + j];
-    if (T.hasmp2[idx2]) return 0xffffffffu;                               // :1083 (vbMatched2 is never set)
-    const bool bStereo2 = T.ur2[idx2] >= 0.f;
-    if (T.bOnlyStereo && !bStereo2) return 0xffffffffu;                   // :1088-1090
-    int dist = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) dist += __popc(d1[w] ^ T.desc2[(size_t)idx2 * 8 + w]);
-    if (dist > ORBM_TH_LOW) return 0xffffffffu;                           // :1096
-    if (T.epipole_gate && !bStereo1 && !bStereo2) {                       // :1105-1113
-      const float x2 = T.kp2[(size_t)idx2 * 7], y2 = T.kp2[(size_t)idx2 * 7 + 1];
-      const int oct2 = __float_as_int(T.kp2[(size_t)idx2 * 7 + 5]);
-      const float distex = T.epx - x2, distey = T.epy - y2;
-      if (distex * distex + distey * distey < 100 * T.sf2[oct2 & (ORBX_MAX_LEVELS - 1)]) return 0xffffffffu;
-    }
-    return ((uint32_t)dist << 16) | (uint32_t)(0xffff - j);
-  };
+  const bool bStereo1 = T.ur1 && T.ur1[idx1] >= 0.f;
   int cnt = 0;
   for (int j0 = 0; j0 < item.len2; j0 += 64) {
     const int j = j0 + lane;
-    cnt += __popcll(__ballot(j < item.len2 && key_of(j) != 0xffffffffu));
+    cnt += __popcll(__ballot(j < item.len2 && tri_key_of(T, item, d1, bStereo1, j) != 0xffffffffu));
   }
   int base = 0;
-  if (lane == 0) { base = cnt ? atomicAdd(T.total, cnt) : 0; T.item_off[it] = base; T.item_cnt[it] = cnt; }
+  if (lane == 0) {
+    base = cnt ? atomicAdd(T.total, cnt) : 0;
+    if (T.item_off) { T.item_off[it] = base; T.item_cnt[it] = cnt; }
+  }
   base = __builtin_amdgcn_readfirstlane(base);
   if (cnt == 0 || base + cnt > T.cap) return;
   int w0 = 0;
   for (int j0 = 0; j0 < item.len2; j0 += 64) {
     const int j = j0 + lane;
-    const uint32_t k = j < item.len2 ? key_of(j) : 0xffffffffu;
+    const uint32_t k = j < item.len2 ? tri_key_of(T, item, d1, bStereo1, j) : 0xffffffffu;
     const unsigned long long mk = __ballot(k != 0xffffffffu);
-    if (k != 0xffffffffu) T.keys[base + w0 + __popcll(mk & ((1ull << lane) - 1ull))] = k;
+    if (k != 0xffffffffu) {
+      const int o = base + w0 + __popcll(mk & ((1ull << lane) - 1ull));
+      T.keys[o] = k;
+      if (T.key_item) T.key_item[o] = it;
+    }
     w0 += __popcll(mk);
   }
+}
+
+// KannalaBrandt8::epipolarConstrain (KannalaBrandt8.cpp:244-247: TriangulateMatches(...) > 0.0001f) on the compact candidate list of
+// k_triangulation_candidates, one candidate per lane; the grid covers the host's bound on the list, lanes beyond the device-side total
+// leave.  The reference's answer for an item is the first entry of the order (distance ascending, node position descending) that the
+// test accepts = the minimum accepted key: atomicMin into best[item].  bCoarse accepts without the test (:1148).
+struct TriKb8Consts {             // constant per call, in device memory
+  float T12[4][12], Tcw2[4][12];  // [R12 | t12] and rig_Tcw2 of it, pairs ll, lr, rl, rr (a keyframe pair without second cameras: [0])
+  float cams1[2][8], cams2[2][8]; // KannalaBrandt8 parameters of mpCamera, mpCamera2 of the two keyframes
+};
+struct TriKb8Params {
+  const float *kp1, *kp2;         // keypoint AoS (7 floats each); rigs: [mvKeys; mvKeysRight]
+  const int32_t *node_idx2;
+  const TriItem *items; int nitems;
+  const uint32_t *keys; const int32_t *key_item; const int32_t *total; int cap;
+  const TriKb8Consts *consts;
+  float sigma2_1[ORBX_MAX_LEVELS], sigma2_2[ORBX_MAX_LEVELS];
+  int n_left1, n_left2;           // -1: no second camera
+  int bCoarse;
+  uint32_t *best;                 // [nitems], pre-filled with 0xffffffff
+  int32_t *matches12;             // pre-filled with -1
+};
+
+__global__ __launch_bounds__(256) void k_triangulation_kb8_predicate(TriKb8Params T) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= min(*T.total, T.cap)) return;
+  const uint32_t key = T.keys[c];
+  const int it = T.key_item[c];
+  bool ok = T.bCoarse != 0;
+  if (!ok) {
+    const TriItem item = T.items[it];
+    const int idx1 = item.idx1, idx2 = T.node_idx2[item.start2 + (0xffff - (int)(key & 0xffffu))];
+    const float *k1 = T.kp1 + (size_t)idx1 * 7, *k2 = T.kp2 + (size_t)idx2 * 7;
+    const int r1 = T.n_left1 >= 0 && idx1 >= T.n_left1, r2 = T.n_left2 >= 0 && idx2 >= T.n_left2;   // bRight1, bRight2 (:1068, :1102)
+    const int pair = 2 * r1 + r2;                                                                   // :1115-1145
+    const int oct1 = __float_as_int(k1[5]) & (ORBX_MAX_LEVELS - 1), oct2 = __float_as_int(k2[5]) & (ORBX_MAX_LEVELS - 1);
+    float p3D[3];
+    ok = kb8_triangulate_matches(T.consts->cams1[r1], T.consts->cams2[r2], k1[0], k1[1], k2[0], k2[1], T.consts->T12[pair], T.consts->Tcw2[pair],
+                                 T.sigma2_1[oct1], T.sigma2_2[oct2], p3D) > 0.0001f;
+  }
+  if (ok) atomicMin(&T.best[it], key);
+}
+
+// best[item] -> vMatches12[idx1] (:1160)
+__global__ __launch_bounds__(256) void k_triangulation_kb8_result(TriKb8Params T) {
+  const int it = blockIdx.x * 256 + threadIdx.x;
+  if (it >= T.nitems) return;
+  const uint32_t best = T.best[it];
+  if (best == 0xffffffffu) return;
+  const TriItem item = T.items[it];
+  T.matches12[item.idx1] = T.node_idx2[item.start2 + (0xffff - (int)(best & 0xffffu))];
 }
 
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) inner loops (ORBmatcher.cc:303-438, Nleft == -1): the

@@ -2726,7 +2726,9 @@ void inv33(const float *S, float *D) {
 }  // namespace
 
 // merge-walk of the two feature vectors (ORBmatcher.cc:1036-1188): one work item per unmatched keypoint of KF1 in a shared node
-static int triangulation_items(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, int bOnlyStereo, std::vector<TriItem> &items) {
+// ur1 = KF1's mvuRight, NULL for a two-camera rig (bStereo1 is false there, :1057)
+static int triangulation_items(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, const float *ur1, int bOnlyStereo,
+                               std::vector<TriItem> &items) {
   int f1 = 0, f2 = 0;
   while (f1 < k1->n_nodes && f2 < k2->n_nodes) {
     if (k1->node_id[f1] == k2->node_id[f2]) {
@@ -2736,7 +2738,7 @@ static int triangulation_items(orbm_t *m, const orbm_keyframe_t *k1, const orbm_
         const int idx1 = k1->node_idx[i1];
         if (idx1 < 0 || idx1 >= k1->n) return ORBX_E_ARG;
         if (k1->has_mappoint[idx1]) continue;                          // :1050-1055
-        if (bOnlyStereo && !(k1->u_right[idx1] >= 0)) continue;        // :1057-1061
+        if (bOnlyStereo && !(ur1 && ur1[idx1] >= 0)) continue;         // :1057-1061
         if (l2 > 0) items.push_back(TriItem{idx1, s2, l2});
       }
       f1++; f2++;
@@ -2758,7 +2760,7 @@ static int triangulation_candidates(orbm_t *m, const orbm_keyframe_t *k1, const 
   idx2.clear(); dist.clear();
   if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
   std::vector<TriItem> items;
-  const int rc = triangulation_items(m, k1, k2, bOnlyStereo, items);
+  const int rc = triangulation_items(m, k1, k2, k1->u_right, bOnlyStereo, items);
   if (rc < 0) return rc;
   if (items.empty()) return 0;
   MCHECK(m, hipSetDevice(m->device));
@@ -2904,7 +2906,7 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
     mul33(B, K2i, T.F12);
   }
   std::vector<TriItem> items;
-  { const int rc = triangulation_items(m, k1, k2, bOnlyStereo, items); if (rc < 0) return rc; }
+  { const int rc = triangulation_items(m, k1, k2, k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
   int nmatches = 0;
   if (!items.empty()) {
     MCHECK(m, hipSetDevice(m->device));
@@ -2927,6 +2929,92 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
     T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
     T.matches12 = (int32_t *)d[MATCHES12];
     hipLaunchKernelGGL(k_triangulation_match, dim3((T.nitems + 3) / 4), dim3(256), 0, s, T);
+    MCHECK(m, hipGetLastError());
+    MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    for (int i = 0; i < k1->n; i++) nmatches += matches12[i] >= 0;
+  }
+  if (checkOri && nmatches > 0) nmatches = prune_pairs_by_rotation(k1, k2, matches12, nmatches);
+  return nmatches;
+}
+
+// SearchForTriangulation with KannalaBrandt8's epipolarConstrain on the device (ORBmatcher.cc:981-1222, KannalaBrandt8.cpp:244-247):
+// candidates -> predicate on every candidate -> minimum accepted key per item -> vMatches12, one upload and one download.
+int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, const orbm_keyframe_t *k2, int n_left2, float ep_x, float ep_y,
+                                      const float *cams1, const float *cams2, const float *T12, int bOnlyStereo, int bCoarse, int checkOri,
+                                      int32_t *matches12) {
+  if (!m || !k1 || !k2 || !cams1 || !cams2 || !T12 || !matches12) return ORBX_E_ARG;
+  const bool rig = n_left1 != -1;
+  auto refuse = [&](const char *why) { m->err = why; return ORBX_E_ARG; };
+  if ((n_left1 == -1) != (n_left2 == -1)) return refuse("n_left: one keyframe with and one without a second camera");
+  if (k1->n < 0 || k2->n < 0 || n_left1 < -1 || n_left1 > k1->n || n_left2 < -1 || n_left2 > k2->n) return refuse("n or n_left out of range");
+  if (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return refuse("nlevels out of range");
+  for (const orbm_keyframe_t *k : {k1, k2}) {
+    if (!k->level_sigma2 || !k->scale_factors || k->n_nodes < 0) return refuse("keyframe: NULL scale table");
+    if (k->n > 0 && (!k->keys_un || !k->descriptors || !k->has_mappoint || (!rig && !k->u_right))) return refuse("keyframe: NULL array");
+    if (k->n_nodes > 0 && (!k->node_id || !k->node_start || !k->node_idx || k->node_start[0] < 0)) return refuse("keyframe: NULL feature vector");
+    for (int i = 0; i < k->n; i++)   // mvLevelSigma2[kp.octave], :1148
+      if (k->keys_un[i].octave < 0 || k->keys_un[i].octave >= k->nlevels) return refuse("keypoint octave outside [0, nlevels)");
+    for (int f = 0; f < k->n_nodes; f++)
+      if (k->node_start[f + 1] < k->node_start[f]) return refuse("feature vector: node_start decreases");
+  }
+  for (int i = 0; i < k1->n; i++) matches12[i] = -1;
+  if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
+  const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
+  for (size_t i = 0; i < nidx2; i++)
+    if (k2->node_idx[i] < 0 || k2->node_idx[i] >= k2->n) return refuse("feature vector: keypoint index out of range");
+  std::vector<TriItem> items;
+  { const int rc = triangulation_items(m, k1, k2, rig ? nullptr : k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
+  int nmatches = 0;
+  if (!items.empty()) {
+    size_t cap = 0;   // every member of an item's node can be a candidate: the list never outgrows this
+    for (const TriItem &it : items) cap += (size_t)it.len2;
+    if (cap > 0x7fffffffu) return refuse("more than 2^31 - 1 keypoint pairs in shared vocabulary nodes");
+    TriKb8Consts K;
+    memset(&K, 0, sizeof(K));
+    for (int p = 0; p < (rig ? 4 : 1); p++) {
+      memcpy(K.T12[p], T12 + 12 * p, sizeof(K.T12[p]));
+      rig_Tcw2(K.T12[p], K.Tcw2[p]);
+    }
+    memcpy(K.cams1, cams1, sizeof(float) * (rig ? 16 : 8));
+    memcpy(K.cams2, cams2, sizeof(float) * (rig ? 16 : 8));
+    MCHECK(m, hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t n1 = (size_t)k1->n, n2 = (size_t)k2->n, ni = items.size(), out_bytes = sizeof(int32_t) * n1;
+    enum { KP1, DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, CONSTS, MATCHES12, BEST, TOTAL, KEYS, KEY_ITEM, NPARTS };
+    void *d[NPARTS];
+    const int rs = stage(m, s, {{k1->keys_un, sizeof(orbx_keypoint_t) * n1}, {k1->descriptors, 32 * n1}, {rig ? nullptr : k1->u_right, rig ? 0 : sizeof(float) * n1},
+                                {k2->descriptors, 32 * n2}, {k2->keys_un, sizeof(orbx_keypoint_t) * n2}, {rig ? nullptr : k2->u_right, rig ? 0 : sizeof(float) * n2},
+                                {k2->has_mappoint, n2}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * ni}, {&K, sizeof(K)},
+                                {nullptr, out_bytes}, {nullptr, sizeof(uint32_t) * ni}, {nullptr, sizeof(int32_t)}, {nullptr, sizeof(uint32_t) * cap},
+                                {nullptr, sizeof(int32_t) * cap}}, d);
+    if (rs < 0) return rs;
+    // matches12 = -1 and best = 0xffffffff in one fill (adjacent parts of the block), total = 0
+    MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, (size_t)((uint8_t *)d[TOTAL] - (uint8_t *)d[MATCHES12]), s));
+    MCHECK(m, hipMemsetAsync(d[TOTAL], 0, sizeof(int32_t), s));
+    TriCandParams C;
+    memset(&C, 0, sizeof(C));
+    C.desc1 = (const uint32_t *)d[DESC1]; C.ur1 = (const float *)d[UR1];
+    C.desc2 = (const uint32_t *)d[DESC2]; C.kp2 = (const float *)d[KP2]; C.ur2 = (const float *)d[UR2];
+    C.hasmp2 = (const uint8_t *)d[HASMP2]; C.node_idx2 = (const int32_t *)d[NODE_IDX2];
+    C.items = (const TriItem *)d[ITEMS]; C.nitems = (int)ni;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) C.sf2[l] = l < k2->nlevels ? k2->scale_factors[l] : 0.f;
+    C.epx = ep_x; C.epy = ep_y; C.epipole_gate = rig ? 0 : 1; C.bOnlyStereo = bOnlyStereo;   // !pKF1->mpCamera2, :1105
+    C.keys = (uint32_t *)d[KEYS]; C.cap = (int)cap; C.key_item = (int32_t *)d[KEY_ITEM]; C.total = (int32_t *)d[TOTAL];
+    TriKb8Params T;
+    memset(&T, 0, sizeof(T));
+    T.kp1 = (const float *)d[KP1]; T.kp2 = C.kp2; T.node_idx2 = C.node_idx2; T.items = C.items; T.nitems = C.nitems;
+    T.keys = C.keys; T.key_item = C.key_item; T.total = C.total; T.cap = C.cap;
+    T.consts = (const TriKb8Consts *)d[CONSTS];
+    for (int l = 0; l < k1->nlevels; l++) T.sigma2_1[l] = k1->level_sigma2[l];
+    for (int l = 0; l < k2->nlevels; l++) T.sigma2_2[l] = k2->level_sigma2[l];
+    T.n_left1 = n_left1; T.n_left2 = n_left2; T.bCoarse = bCoarse;
+    T.best = (uint32_t *)d[BEST]; T.matches12 = (int32_t *)d[MATCHES12];
+    hipLaunchKernelGGL(k_triangulation_candidates, dim3((C.nitems + 3) / 4), dim3(256), 0, s, C);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_triangulation_kb8_predicate, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, T);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_triangulation_kb8_result, dim3((T.nitems + 255) / 256), dim3(256), 0, s, T);
     MCHECK(m, hipGetLastError());
     MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
     MCHECK(m, hipStreamSynchronize(s));

@@ -735,8 +735,9 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *kf1, const o
 
 /* The same member for keyframes whose epipolar test is NOT Pinhole's: KannalaBrandt8 cameras and two-camera rigs
  * (pCamera1->epipolarConstrain(pCamera2, kp1, kp2, R12, t12, sigma1, sigma2) is a virtual call, ORBmatcher.cc:1148;
- * KannalaBrandt8's triangulates with cv::SVD, outside this path - SURVEY.md section 2 row 4).  The device does everything in front
- * of the predicate, the predicate stays the caller's:
+ * KannalaBrandt8's is TriangulateMatches(...) > 0.0001f, a cv::SVD triangulation, KannalaBrandt8.cpp:244-247).  Two forms:
+ * orbm_search_for_triangulation_kb8 below runs the whole member on the device when every camera involved is a KannalaBrandt8; for any
+ * other camera model the device does everything in front of the predicate and the predicate stays the caller's:
  *
  * orbm_triangulation_candidates: per keypoint idx1 of KF1 without a map point (and, with bOnlyStereo, with mvuRight >= 0) every
  * keypoint idx2 of KF2 in the same vocabulary node that has no map point (:1083), passes the stereo filter (:1088-1090), lies
@@ -751,8 +752,8 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *kf1, const o
  * orbm_search_for_triangulation_pred: the whole member around a caller-supplied predicate: candidates as above, then per idx1
  * the first listed idx2 with bCoarse || pred(user, idx1, idx2), then the rotation-histogram pruning (:1162-1172, :1191-1207).
  * pred is called on the calling thread, only for pairs that passed every other gate, in list order, and must be pure.
- * matches12[kf1->n] (out) = vMatches12.  Returns nmatches.  The adapter's KannalaBrandt8 / rig branch is this call with
- * pred = the reference's own epipolarConstrain (csrc/adapter/ORBmatcher_hip.cc). */
+ * matches12[kf1->n] (out) = vMatches12.  Returns nmatches.  The adapter takes this route, with pred = the reference's own
+ * epipolarConstrain, only when a camera involved is neither Pinhole nor KannalaBrandt8 (csrc/adapter/ORBmatcher_hip.cc). */
 typedef int (*orbm_pair_predicate_t)(void *user, int idx1, int idx2);
 int orbm_triangulation_candidates(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_t *kf2, float ep_x, float ep_y,
                                   int epipole_gate, int bOnlyStereo, int32_t *cand_start, int32_t *cand_idx2, int32_t *cand_dist,
@@ -760,6 +761,31 @@ int orbm_triangulation_candidates(orbm_t *m, const orbm_keyframe_t *kf1, const o
 int orbm_search_for_triangulation_pred(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_t *kf2, float ep_x, float ep_y,
                                        int epipole_gate, int bOnlyStereo, int bCoarse, int checkOri, orbm_pair_predicate_t pred,
                                        void *user, int32_t *matches12);
+
+/* The same member with KannalaBrandt8::epipolarConstrain on the device: orbm_search_for_triangulation_pred with
+ * pred = kb8 TriangulateMatches(cam_a, cam_b, kp1, kp2, R12, t12, kf1->level_sigma2[octave1], kf2->level_sigma2[octave2]) > 0.0001f
+ * (KannalaBrandt8.cpp:244-247, :343-412; the arithmetic of csrc/orb_ref_triangulate.h, cv::SVD restated as OpenCV's own float Jacobi,
+ * [OPENCV-UNVERIFIED]).  One upload, three kernels - candidate lists, the test on EVERY candidate with the minimum accepted key per
+ * keypoint of KF1 (= the first accepted entry of the order above), keys to indices - and one download; the rotation-histogram pruning
+ * runs on the host afterwards.  bCoarse accepts the first entry of every list without the test.
+ * n_left? == -1: a keyframe without a second camera - keys_un = mvKeysUn, bStereo = u_right >= 0, the epipole gate (:1105-1113) is on;
+ * cams? [1][8] = mpCamera's {fx, fy, cx, cy, k0..k3}; T12 [1][12] = [R12 | t12] (row stride 4) of :1007-1008.
+ * n_left? >= 0: a two-camera rig - keys_un = [mvKeys; mvKeysRight], keypoint idx is the right camera's when idx >= n_left, bStereo is false
+ * for every keypoint (u_right is not read and may be NULL), no epipole gate; cams? [2][8] = mpCamera, mpCamera2; T12 [4][12] in the order
+ * ll, lr, rl, rr of :1011-1019, the pair (bRight1, bRight2) selects cameras and pose (:1115-1145).
+ * (ep_x, ep_y) = pKF2->mpCamera->project(R2w * Cw1 + t2w) (:988-993) and T12 are the caller's: the cv::Mat algebra stays outside.
+ * Returns nmatches, ORBX_E_HIP, or ORBX_E_ARG for:
+ *   - a NULL m, kf1, kf2, cams1, cams2, T12 or matches12, a NULL scale_factors / level_sigma2, and with n > 0 a NULL keys_un,
+ *     descriptors, has_mappoint or (n_left == -1) u_right, with n_nodes > 0 a NULL node array;
+ *   - exactly one of n_left1 / n_left2 equal to -1 (the reference's R12 would be empty there);
+ *   - n < 0 or n_left outside [-1, n];
+ *   - nlevels of either keyframe outside [1, ORBX_MAX_LEVELS];
+ *   - a keypoint of either keyframe with an octave outside [0, nlevels) (checked on the host before anything is uploaded);
+ *   - a feature vector whose node_start decreases or whose node_idx holds an index outside [0, n) (kf1: in a node it shares with kf2);
+ *   - a vocabulary node of kf2 with more than 65535 members, or more than 2^31 - 1 keypoint pairs in shared nodes. */
+int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *kf1, int n_left1, const orbm_keyframe_t *kf2, int n_left2,
+                                      float ep_x, float ep_y, const float *cams1, const float *cams2, const float *T12,
+                                      int bOnlyStereo, int bCoarse, int checkOri, int32_t *matches12);
 
 /* int ORBmatcher::SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched,
  *                                         vector<int> &vnMatches12, int windowSize)              (ORBmatcher.cc:722-837)
