@@ -24,6 +24,19 @@
 #endif
 #define ORB_DESCRIBE_GROUPS(totalKp, K) ((((totalKp) + (K) - 1) / (K) + 3) / 4 > 1 ? (((totalKp) + (K) - 1) / (K) + 3) / 4 : 1)
 
+// Live counts of ragged batches.  A count from device memory is whatever an earlier kernel (or the caller) left there, so every kernel
+// takes it into [0, cap] - cap: what the host sized the problem's arrays and scratch for - before it indexes anything with it:
+__host__ __device__ constexpr int clamp_count(int n, int cap) { return (n > 0 ? n : 0) < cap ? (n > 0 ? n : 0) : cap; }   // min(max(n, 0), cap)
+static_assert(clamp_count(-1, 8) == 0 && clamp_count(0, 8) == 0 && clamp_count(5, 8) == 5 && clamp_count(8, 8) == 8 && clamp_count(9, 8) == 8, "clamp_count");
+static_assert(clamp_count(-1, 0) == 0 && clamp_count(0, 0) == 0 && clamp_count(1, 0) == 0, "clamp_count: cap == 0");
+
+// The live count of problem p of one side of a ragged batch: dev[p * stride] taken into [0, cap], or - dev == NULL - the constant
+// the host validated, as it is.  p comes from blockIdx, so the read is a scalar load: kernels resolve it once, at the top.
+struct LiveCount {
+  const int32_t *dev; int stride; int konst;
+  __device__ __forceinline__ int at(int p, int cap) const { return dev ? clamp_count(dev[(size_t)p * stride], cap) : konst; }
+};
+
 // Geometry of one pyramid level; filled on the host (orbx_configure), read by every kernel.
 struct LevelGeom {
   int w, h;          // level image size (ORBextractor.cc:1192-1193)

@@ -20,7 +20,7 @@ struct RgbdParams {
 };
 
 __device__ __forceinline__ int depth_live(const int32_t *counts, int count_stride, int f, int cap) {
-  return min(max(counts[(size_t)f * count_stride], 0), cap);
+  return clamp_count(counts[(size_t)f * count_stride], cap);
 }
 
 // One pixel of `imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor)` (Tracking.cc:1076).  [OPENCV-UNVERIFIED]: cvtScale for

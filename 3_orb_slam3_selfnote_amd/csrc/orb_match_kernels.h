@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "orb_common.h"
 #include "orb_mfma_util.h"
 #include "orb_ref_triangulate.h"
 
@@ -13,7 +14,7 @@ struct MatchProblemSet {
   const uint8_t *desc;        // n x 32
   const float *u_right;       // or NULL
   int frame_stride;
-  const int32_t *frame_n; int frame_n_stride; int frame_n_const;  // live count: device array or constant
+  LiveCount frame_n;          // live count of problem p: frame_n.at(p, frame_stride)
   float min_x, min_y, inv_w, inv_h;  // mnMinX, mnMinY, mfGridElementWidthInv/HeightInv (Frame.cc:379-380)
   // query side
   const uint8_t *qdesc;
@@ -21,7 +22,7 @@ struct MatchProblemSet {
   const int32_t *qminl, *qmaxl;
   const uint8_t *qflags;
   int query_stride;
-  const int32_t *query_n; int query_n_stride; int query_n_const;
+  LiveCount query_n;          // query_n.at(p, query_stride)
   // options
   float nnratio; int th_dist; int use_second;
   // in/out
@@ -33,7 +34,7 @@ struct MatchProblemSet {
   // couple 2 = ... when the left one's window was empty (:2126); qany[q] = window of query q non-empty (scan -> resolve);
   // serial = resolve one query at a time from a fresh list (exact when a partner write can release a claim).
   int nleft; const uint8_t *qside; const int32_t *partner; int couple; uint8_t *qany; int serial;
-  const int32_t *nleft_dev; int nleft_stride;  // Nleft per problem from device memory (nleft_dev[p * nleft_stride]); NULL: the constant nleft
+  const int32_t *nleft_dev; int nleft_stride;  // Nleft per problem: LiveCount{nleft_dev, nleft_stride, nleft}, see nleft_of (fields kept apart: the kernel-argument layout is the measured one)
   // ORBmatcher::Fuse (ORBmatcher.cc:1425-1658): per-candidate chi-square gate on the reprojection error, :1585-1608
   // (k_match_scan mode SCAN_FUSE); u_right = mvuRight of the keyframe, qur = projected right coordinate
   float inv_sigma2[16];
@@ -102,7 +103,7 @@ __device__ __forceinline__ int popc_acc(uint32_t x, int acc) {
 
 // Nleft of problem p (n for a frame that is no fisheye-stereo one); a count read from device memory is taken into [0, n]
 __device__ __forceinline__ int nleft_of(const MatchProblemSet &M, int p, int n) {
-  return !M.qside ? n : M.nleft_dev ? min(max(M.nleft_dev[(size_t)p * M.nleft_stride], 0), n) : M.nleft;
+  return !M.qside ? n : LiveCount{M.nleft_dev, M.nleft_stride, M.nleft}.at(p, n);
 }
 
 struct CandMeta { float x, y; uint32_t bits; float ur; };  // bits: octave | gx<<8 | gy<<16 | usable<<24 | in-grid<<25
@@ -214,8 +215,8 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_scan(MatchProblemSet M, type
   const unsigned b = blockIdx.x, qblocks = (unsigned)M.scan_qblocks;   // launch: grid = (8 * qblocks * ceil(npairs / 8), 1, slices)
   const int qb = (int)((b >> 3) % qblocks), p = (int)((b & 7u) + 8u * (b / (8u * qblocks)));
   if (p >= M.npairs) return;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
+  const int nq = M.query_n.at(p, M.query_stride);
   if ((int)(qb * MATCH_NT) >= nq) return;
   if (pairflag && pairflag[p]) return;
   if (force != SCAN_DENSE && pair_walks(M, p, n, nq, force, &sVote)) return;   // k_match_walk serves this pair
@@ -455,8 +456,8 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_walk(MatchProblemSet M, type
   const unsigned b = blockIdx.x, qblocks = (unsigned)wqblocks;   // same XCD-aware order as k_match_scan
   const int qb = (int)((b >> 3) % qblocks), p = (int)((b & 7u) + 8u * (b / (8u * qblocks)));
   if (p >= M.npairs) return;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
+  const int nq = M.query_n.at(p, M.query_stride);
   if ((int)(qb * QW) >= nq) return;
   if (!pair_walks(M, p, n, nq, force, &sVote)) return;
   WSTAMP(0);
@@ -642,8 +643,8 @@ __global__ __launch_bounds__(MATCH_NT) void k_topk_merge(MatchProblemSet M, type
   typedef typename KT::T K;
   __shared__ int sVote;
   const int p = blockIdx.y;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
+  const int nq = M.query_n.at(p, M.query_stride);
+  const int n = M.frame_n.at(p, M.frame_stride);
   if ((int)(blockIdx.x * MATCH_NT) >= nq) return;
   if (force != SCAN_DENSE && pair_walks(M, p, n, nq, force, &sVote)) return;   // the walk wrote one list per query: nothing to fold
   const int q = blockIdx.x * MATCH_NT + threadIdx.x;
@@ -787,8 +788,8 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
   __shared__ K sPart[NW_][NW_][REFRESH_K];   // [request][share]: each serving wavefront's REFRESH_K best keys
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int p = blockIdx.x;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
+  const int nq = M.query_n.at(p, M.query_stride);
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;
   const int nleft = nleft_of(M, p, n);   // once per problem: a scalar select for frames that are no fisheye-stereo ones
   const float *kp = M.kp + fo * 7;
@@ -1588,8 +1589,8 @@ __global__ __launch_bounds__(64) void k_init_resolve(MatchProblemSet M, const ty
   __shared__ K sTk[MATCH_TOPK * 64];
   const int lane = threadIdx.x;
   const int p = blockIdx.x;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
+  const int nq = M.query_n.at(p, M.query_stride);
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;
   const float *kp = M.kp + fo * 7;
   const uint32_t *desc = reinterpret_cast<const uint32_t *>(M.desc + fo * 32);

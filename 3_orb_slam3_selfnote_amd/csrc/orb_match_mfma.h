@@ -1,6 +1,7 @@
 // orb_match_mfma.h -- k_match_rank and k_match_scan_mfma: the open-window candidate scan of the projection searches on the matrix
 // pipe (formulation, operand layout and selection: orb_mfma_util.h).
 #pragma once
+#include "orb_common.h"
 #include "orb_mfma_util.h"
 
 // One workgroup per frame pair: rank of every keypoint in (grid cell, index) order among the keypoints PosInGrid accepts.
@@ -16,9 +17,9 @@ __global__ __launch_bounds__(MF_NT) void k_match_rank(MatchProblemSet M, uint32_
   __shared__ uint32_t sWaveSum[MF_NT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int p = blockIdx.x;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
   {
-    const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+    const int nq = M.query_n.at(p, M.query_stride);
     const size_t qo = (size_t)p * M.query_stride;
     bool anyLive = false, notOpen = false;
     if (fuse_ok && n >= 1 && n <= WALK_MAX_N)
@@ -100,8 +101,8 @@ __global__ __launch_bounds__(MF_NT) void k_match_scan_mfma(MatchProblemSet M, ui
   const unsigned b = blockIdx.x, qblocks = (unsigned)M.scan_qblocks;   // same XCD-aware order as k_match_scan
   const int qb = (int)((b >> 3) % qblocks), p = (int)((b & 7u) + 8u * (b / (8u * qblocks)));
   if (p >= M.npairs) return;
-  const int n = M.frame_n ? M.frame_n[(size_t)p * M.frame_n_stride] : M.frame_n_const;
-  const int nq = M.query_n ? M.query_n[(size_t)p * M.query_n_stride] : M.query_n_const;
+  const int n = M.frame_n.at(p, M.frame_stride);
+  const int nq = M.query_n.at(p, M.query_stride);
   if ((int)(qb * MF_NT) >= nq) return;
   if (pairflag[p]) return;                 // the fused k_match_resolve builds this pair's lists itself
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "orb_common.h"
 #include "orb_logf.h"
 #include "orb_ref_geometry.h"
 
@@ -37,8 +38,7 @@ struct LastFrameParams {
   const float *last_kp;    // LastFrame.mvKeys as 7 floats per keypoint (octave = word 5, angle = word 3)
   const uint8_t *obs;      // pMP->Observations() > 0, or NULL = all 1
   const float *Tcw, *Tlw;  // row-major 4x4 per problem (16 floats)
-  int last_stride;
-  const int32_t *last_n; int last_n_stride; int last_n_const;
+  int last_stride; LiveCount last_n;   // live count of problem p: last_n.at(p, last_stride)
   ViewParams V;
   float mb, mbf, th; int bMono;
   QueryScratch Q;          // out
@@ -82,7 +82,7 @@ __device__ __forceinline__ LastFrameQuery lastframe_query(const LastFrameParams 
 __global__ __launch_bounds__(256) void k_lastframe_project(LastFrameParams P) {
   const int p = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = P.last_n ? min(P.last_n[(size_t)p * P.last_n_stride], P.last_stride) : P.last_n_const;
+  const int n = P.last_n.at(p, P.last_stride);
   if (i >= P.last_stride) return;
   const size_t o = (size_t)p * P.last_stride + i;
   float xc[3];
@@ -105,7 +105,7 @@ struct RigProjectParams {
 __global__ __launch_bounds__(256) void k_lastframe_project_rig(LastFrameParams P, RigProjectParams G) {
   const int p = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = P.last_n ? max(0, min(P.last_n[(size_t)p * P.last_n_stride], P.last_stride)) : P.last_n_const;
+  const int n = P.last_n.at(p, P.last_stride);
   if (i == 0) G.query_n[p] = 2 * n;
   if (i >= P.last_stride) return;
   const size_t o = (size_t)p * P.last_stride + i;
@@ -143,8 +143,7 @@ struct LocalMapParams {
   const float *max_dist, *min_dist; // raw mfMaxDistance / mfMinDistance
   const uint8_t *obs;               // Observations() > 0, or NULL = all 1
   const float *Tcw;                 // CurrentFrame.mTcw, row-major 4x4 per problem
-  int map_stride;
-  const int32_t *map_n; int map_n_stride; int map_n_const;
+  int map_stride; LiveCount map_n;     // live count of problem p: map_n.at(p, map_stride)
   ViewParams V; float log_sf;
   float mbf, view_cos_limit, th; int bFarPoints; float th_far;
   // out: the MapPoint fields isInFrustum writes (caller arrays, same stride)
@@ -155,7 +154,7 @@ struct LocalMapParams {
 __global__ __launch_bounds__(256) void k_local_map_project(LocalMapParams P) {
   const int p = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = P.map_n ? min(P.map_n[(size_t)p * P.map_n_stride], P.map_stride) : P.map_n_const;
+  const int n = P.map_n.at(p, P.map_stride);
   if (i >= P.map_stride) return;
   const size_t o = (size_t)p * P.map_stride + i;
   float u = 0.f, v = 0.f, rad = 0.f, ur = 0.f;
@@ -235,9 +234,7 @@ struct RigLocalParams {
   // range counts as -1.  partner == NULL: none is built.
   const int32_t *l2r, *r2l;  // [npairs][frame_stride], either may be NULL
   int32_t *partner;          // out: [npairs][frame_stride]
-  int frame_stride;
-  const int32_t *frame_n; int frame_n_stride; int frame_n_const;
-  const int32_t *nleft_dev; int nleft_stride; int nleft_const;
+  int frame_stride; LiveCount frame_n, nleft;   // N = frame_n.at(p, frame_stride), Nleft = nleft.at(p, N)
 };
 
 // Frame::isInFrustumChecks (Frame.cc:1289-1325) for one camera: T = [mR | mt] (row stride 4), twc, the camera, point o.
@@ -268,11 +265,10 @@ __device__ __forceinline__ FrustumSide frustum_side(const LocalMapParams &P, con
 __global__ __launch_bounds__(256) void k_local_map_project_rig(LocalMapParams P, RigLocalParams G) {
   const int p = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = P.map_n ? max(0, min(P.map_n[(size_t)p * P.map_n_stride], P.map_stride)) : P.map_n_const;
+  const int n = P.map_n.at(p, P.map_stride);
   if (i == 0) G.query_n[p] = 2 * n;
   if (G.partner) {
-    const int fn = max(0, min(G.frame_n ? G.frame_n[(size_t)p * G.frame_n_stride] : G.frame_n_const, G.frame_stride));
-    const int nl = max(0, min(G.nleft_dev ? G.nleft_dev[(size_t)p * G.nleft_stride] : G.nleft_const, fn));
+    const int fn = G.frame_n.at(p, G.frame_stride), nl = G.nleft.at(p, fn);
     const size_t fo = (size_t)p * G.frame_stride;
     for (int k = i; k < G.frame_stride; k += gridDim.x * 256) {
       int pr = -1;
@@ -340,15 +336,14 @@ __global__ __launch_bounds__(256) void k_local_map_project_rig(LocalMapParams P,
 // slot: query j with moq[j] = m owns slot[m] and slot[partner[m]] where it was the last writer.  Slots the search did not write
 // are not touched.  One workgroup per problem.
 struct RigSlotParams {
-  const int32_t *moq; int map_stride;
-  const int32_t *map_n; int map_n_stride; int map_n_const;
+  const int32_t *moq; int map_stride; LiveCount map_n;
   const int32_t *partner;   // or NULL
   int32_t *slot; int frame_stride;
 };
 
 __global__ __launch_bounds__(256) void k_rig_slot_convert(RigSlotParams S) {
   const int p = blockIdx.x, t = threadIdx.x;
-  const int n = 2 * (S.map_n ? max(0, min(S.map_n[(size_t)p * S.map_n_stride], S.map_stride)) : S.map_n_const);
+  const int n = 2 * S.map_n.at(p, S.map_stride);
   const size_t qo = 2 * (size_t)p * S.map_stride, ko = (size_t)p * S.frame_stride;
   for (int step = 0; step < 2; step++) {
     for (int j = t; j < n; j += 256) {
@@ -372,8 +367,7 @@ __global__ __launch_bounds__(256) void k_ref_logf(const float *x, int n, float *
 
 struct RotPruneParams {
   const float *last_kp;  // query side: angle of LastFrame.mvKeysUn[i] (word 3 of 7)
-  int last_stride;
-  const int32_t *last_n; int last_n_stride; int last_n_const;
+  int last_stride; LiveCount last_n;
   const float *cur_kp;   // CurrentFrame.mvKeysUn, 7 floats per keypoint
   int frame_stride;
   int32_t *moq;          // match_of_query (in/out: pruned matches become -1)
@@ -397,7 +391,7 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
   __shared__ int keep[3];
   __shared__ int removed;
   const int p = blockIdx.x, t = threadIdx.x;
-  const int n = max(0, R.last_n ? min(R.last_n[(size_t)p * R.last_n_stride], R.last_stride) : R.last_n_const) << QS;
+  const int n = R.last_n.at(p, R.last_stride) << QS;
   const size_t lo = (size_t)p * R.last_stride, qo = lo << QS, ko = (size_t)p * R.frame_stride;
   if (QS) {
     for (int j = t; j < n; j += 256) {
@@ -455,14 +449,13 @@ __global__ __launch_bounds__(256) void k_rot_prune(RotPruneParams R) {
 struct UndistortParams {
   const float *keys;           // orbx_keypoint_t AoS viewed as floats, frame f at element offset f * key_stride
   float *keys_un;              // may alias keys
-  int key_stride;
-  const int32_t *counts; int count_stride; int count_const;
+  int key_stride; LiveCount count;   // N of frame f: count.at(f, key_stride)
   float K[4], D[5]; int nD;
 };
 
 __global__ __launch_bounds__(256) void k_undistort(UndistortParams U) {
   const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  const int n = U.counts ? U.counts[(size_t)f * U.count_stride] : U.count_const;
+  const int n = U.count.at(f, U.key_stride);
   if (i >= n) return;
   const size_t o = ((size_t)f * U.key_stride + i) * 7;
   float k[7];
@@ -491,7 +484,7 @@ struct RigConcatParams {
 
 __global__ __launch_bounds__(256) void k_rig_concat(RigConcatParams R) {
   const int f = blockIdx.y;
-  const int nL = max(0, min(R.countsL[2 * (size_t)f], R.cap)), nR = max(0, min(R.countsR[2 * (size_t)f], R.cap));
+  const int nL = clamp_count(R.countsL[2 * (size_t)f], R.cap), nR = clamp_count(R.countsR[2 * (size_t)f], R.cap);
   const int N = nL + nR;   // <= 2 * cap
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t == 0) { R.n[2 * (size_t)f] = N; R.n[2 * (size_t)f + 1] = nL; }

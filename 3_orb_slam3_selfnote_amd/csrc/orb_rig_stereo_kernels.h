@@ -3,6 +3,7 @@
 // then Lowe's ratio test and KannalaBrandt8::TriangulateMatches, one match per lane (k_rig_stereo_triangulate).  One grid covers all
 // frames; the per-frame row ranges are read from the extractions' own count arrays.
 #pragma once
+#include "orb_common.h"
 #include "orb_match_mfma.h"
 #include "orb_ref_triangulate.h"
 
@@ -24,8 +25,8 @@ struct RigStereoParams {
 struct RigLap { int nL, monoL, nR, monoR; };
 __device__ __forceinline__ RigLap rig_lap(const RigStereoParams &P, int f) {
   RigLap r;
-  r.nL = min(max(P.countsL[2 * f], 0), P.cap); r.monoL = min(max(P.countsL[2 * f + 1], 0), r.nL);
-  r.nR = min(max(P.countsR[2 * f], 0), P.cap); r.monoR = min(max(P.countsR[2 * f + 1], 0), r.nR);
+  r.nL = clamp_count(P.countsL[2 * f], P.cap); r.monoL = clamp_count(P.countsL[2 * f + 1], r.nL);
+  r.nR = clamp_count(P.countsR[2 * f], P.cap); r.monoR = clamp_count(P.countsR[2 * f + 1], r.nR);
   return r;
 }
 

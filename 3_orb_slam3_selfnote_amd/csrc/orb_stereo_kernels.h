@@ -42,7 +42,7 @@ struct StereoBatchParams {
   float *uRight, *depth; int32_t *sad, *nstereo;                          // [nframes][cap]; sad = -1: no match; nstereo may be NULL
 };
 
-__device__ __forceinline__ int stereo_live(const int32_t *counts, int f, int cap) { return min(max(counts[2 * f], 0), cap); }
+__device__ __forceinline__ int stereo_live(const int32_t *counts, int f, int cap) { return clamp_count(counts[2 * f], cap); }
 
 #define STEREO_W 5   // half width of the SAD window (w, :991)
 #define STEREO_L 5   // half width of the sliding range (L, :998)

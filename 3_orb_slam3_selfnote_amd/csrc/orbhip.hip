@@ -8,6 +8,7 @@
 // ORBX_E_HIP when no device is usable.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1206,7 +1207,7 @@ struct orbm_handle {
   DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
   DevBuf d_cand;      // fused k_match_resolve: every pair's descriptors and candidate records in sorted order (48 B per keypoint)
   DevBuf d_lfq;       // query arrays written by k_lastframe_project (orbm_search_by_projection_last_frame_batch_device)
-  DevBuf d_lmq;       // query arrays written by k_local_map_project (orbm_search_local_points*): never shared with d_lfq
+  DevBuf d_lmq;       // query arrays written by k_local_map_project (orbm_search_local_points*): never shared with d_lfq (kept: two buffers)
   DevBuf d_knn;       // the two nearest right rows of every left lapping row (orbm_stereo_fisheye_matches*)
   DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
@@ -1237,9 +1238,10 @@ static void *getenv_ptr(const char *name) { const char *e = getenv(name); return
 // dev[i]: device address of part i, nullptr for an empty part.
 struct Part { const void *src; size_t bytes; };
 
-static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> parts, void **dev, bool mirror_outputs = false) {
+struct Parts { const Part *b, *e; const Part *begin() const { return b; } const Part *end() const { return e; } };
+static int stage(orbm_handle *m, hipStream_t s, const Part *first, size_t nparts, void **dev, bool mirror_outputs) {
   size_t total = 0, upload = 0;
-  for (const Part &p : parts) {   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
+  for (const Part &p : Parts{first, first + nparts}) {   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
     if (p.bytes > (SIZE_MAX >> 3) - total) { m->err = "staging: inputs too large"; return ORBX_E_HIP; }
     total += (p.bytes + 255) & ~(size_t)255;
     if (p.src) upload = total;
@@ -1253,7 +1255,7 @@ static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> part
   }
   MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
   size_t off = 0;
-  for (const Part &p : parts) {
+  for (const Part &p : Parts{first, first + nparts}) {
     if (p.src && p.bytes) memcpy((uint8_t *)m->pin + off, p.src, p.bytes);
     *dev++ = p.bytes ? (uint8_t *)m->d_block.p + off : nullptr;
     off += (p.bytes + 255) & ~(size_t)255;
@@ -1262,15 +1264,78 @@ static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> part
   return 0;
 }
 
+static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> parts, void **dev, bool mirror_outputs = false) {
+  return stage(m, s, parts.begin(), parts.size(), dev, mirror_outputs);
+}
+
 // The pinned-mirror address of a device address inside m->d_block (entry points staged with mirror_outputs)
 static void *mirror_of(orbm_handle *m, const void *d) { return (uint8_t *)m->pin + ((const uint8_t *)d - (const uint8_t *)m->d_block.p); }
+
+// A staged block with typed parts: add() returns the part's handle; after upload() dev() / host() are its device / pinned-mirror address.
+template <class T> struct PartOf { int i; };
+struct Staging {
+  orbm_handle *m;
+  int n = 0;
+  Part parts[32];   // the largest block (the rig local-map form) has 29 parts; no allocation on the way
+  void *d[32];
+  template <class T> PartOf<T> add(const T *src, size_t count) { assert(n < 32); parts[n] = {src, sizeof(T) * count}; return {n++}; }
+  template <class T> PartOf<T> out(size_t count) { return add((const T *)nullptr, count); }
+  int upload(hipStream_t s) { return stage(m, s, parts, (size_t)n, d, true); }
+  template <class T> T *dev(PartOf<T> h) const { return (T *)d[h.i]; }
+  template <class T> T *host(PartOf<T> h) const { return (T *)mirror_of(m, d[h.i]); }
+};
+
+// The structs the host-pointer forms stage: stage_*() appends the parts (absent arrays as empty ones), on_device() is the device-side struct.
+struct StagedFrame { const orbm_frame_t *f; PartOf<orbx_keypoint_t> kp; PartOf<uint8_t> desc; PartOf<float> ur; };
+static StagedFrame stage_frame(Staging &S, const orbm_frame_t *f, bool with_ur = true) {   // with_ur false: u_right = NULL on the device
+  const size_t n = (size_t)f->n;
+  const float *ur = with_ur ? f->u_right : nullptr;
+  return {f, S.add(f->keys_un, n), S.add(f->descriptors, 32 * n), S.add(ur, ur ? n : 0)};
+}
+static orbm_frame_t on_device(const Staging &S, const StagedFrame &h) {
+  orbm_frame_t d = *h.f;
+  d.keys_un = S.dev(h.kp); d.descriptors = S.dev(h.desc); d.u_right = S.dev(h.ur);
+  return d;
+}
+struct StagedLast { int n; PartOf<uint8_t> has; PartOf<float> xw; PartOf<uint8_t> md; PartOf<orbx_keypoint_t> lk; PartOf<uint8_t> obs; PartOf<float> tc, tl; };
+static StagedLast stage_last_frame(Staging &S, const orbm_last_frame_t &l) {   // one problem: 16 floats of Tcw / Tlw
+  const size_t n = (size_t)l.n;
+  return {l.n, S.add(l.has_mp, n), S.add(l.Xw, 3 * n), S.add(l.mpdesc, 32 * n), S.add(l.last_keys, n), S.add(l.obs, l.obs ? n : 0),
+          S.add(l.Tcw, 16), S.add(l.Tlw, 16)};
+}
+static orbm_last_frame_t on_device(const Staging &S, const StagedLast &h) {
+  orbm_last_frame_t d;
+  d.n = h.n; d.has_mp = S.dev(h.has); d.Xw = S.dev(h.xw); d.mpdesc = S.dev(h.md); d.last_keys = S.dev(h.lk); d.obs = S.dev(h.obs);
+  d.Tcw = S.dev(h.tc); d.Tlw = S.dev(h.tl);
+  return d;
+}
+struct StagedMap { int n; PartOf<uint8_t> elig; PartOf<float> xw, nrm, maxd, mind; PartOf<uint8_t> md, obs; PartOf<float> tc; };
+static StagedMap stage_local_map(Staging &S, const orbm_local_map_t *map) {   // one problem: 16 floats of Tcw
+  const size_t n = (size_t)map->n;
+  return {map->n, S.add(map->eligible, n), S.add(map->Xw, 3 * n), S.add(map->normal, 3 * n), S.add(map->max_dist, n), S.add(map->min_dist, n),
+          S.add(map->mpdesc, 32 * n), S.add(map->obs, map->obs ? n : 0), S.add(map->Tcw, 16)};
+}
+static orbm_local_map_t on_device(const Staging &S, const StagedMap &h) {
+  orbm_local_map_t d;
+  d.n = h.n; d.eligible = S.dev(h.elig); d.Xw = S.dev(h.xw); d.normal = S.dev(h.nrm); d.max_dist = S.dev(h.maxd); d.min_dist = S.dev(h.mind);
+  d.mpdesc = S.dev(h.md); d.obs = S.dev(h.obs); d.Tcw = S.dev(h.tc);
+  return d;
+}
+
+// One side of a ragged batch: problem p at element offset p * stride, live count d_n[p * n_stride] (device) or, d_n == NULL, n.
+struct Ragged {
+  int stride; const int32_t *d_n; int n_stride; int n;
+  int max() const { return d_n ? stride : n; }                                   // what scratch and grids are sized for
+  bool valid() const { return max() > 0 && stride >= max() && n >= 0; }          // the one validity rule of a side
+  LiveCount live() const { return {d_n, n_stride, n}; }
+};
 
 // Options of one projection search beyond the arguments of orbm_search_by_projection_batch_device (see MatchProblemSet); the
 // defaults are a plain search.  Pointers are device addresses.
 struct SearchOpts {
   int scan_mode = SCAN_AUTO;   // SCAN_AUTO / SCAN_DENSE / SCAN_WALK; frames beyond 2048 keypoints are scanned whatever it says
-  int nleft = 0, couple = 0, serial = 0;   // fisheye-stereo frames
-  const int32_t *nleft_dev = nullptr; int nleft_stride = 0;   // Nleft per problem on the device instead of nleft
+  int couple = 0, serial = 0;               // fisheye-stereo frames
+  LiveCount nleft = {nullptr, 0, 0};        // Nleft per problem
   const int32_t *partner = nullptr;
   const uint8_t *qside = nullptr;
   uint8_t *qany = nullptr;
@@ -1451,7 +1516,7 @@ int orbm_undistort_keypoints_batch_device(orbm_t *m, const orbx_keypoint_t *d_ke
   UndistortParams U;
   memset(&U, 0, sizeof(U));
   U.keys = reinterpret_cast<const float *>(d_keys); U.keys_un = reinterpret_cast<float *>(d_keys_un); U.key_stride = key_stride;
-  U.counts = d_counts; U.count_stride = count_stride; U.count_const = n_const;
+  U.count = {d_counts, count_stride, n_const};
   for (int i = 0; i < 4; i++) U.K[i] = K[i];
   for (int i = 0; i < nD; i++) U.D[i] = D[i];
   U.nD = nD;
@@ -1467,41 +1532,45 @@ void orbm_project(int cam_type, const float *p, float X, float Y, float Z, float
   project(cam_type, p, X, Y, Z, *u, *v);
 }
 
-static int search_batch(orbm_t *m, const orbm_frame_t *f, int frame_stride, const int32_t *d_frame_n, int frame_n_stride, const orbm_queries_t *q,
-                        int query_stride, const int32_t *d_query_n, int query_n_stride, int npairs, float nnratio, int th_dist, int use_second,
-                        int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_bd, int32_t *d_nm, hipStream_t s, const SearchOpts &o) {
+// What every search refuses about its frame side (frame.n = f->n); the cores run it before their first launch.  No stride >= n: never asked.
+static int check_search_frame(orbm_t *m, const orbm_frame_t *f, const Ragged &frame) {
+  if (!f->keys_un || !f->descriptors || !(f->max_x > f->min_x) || !(f->max_y > f->min_y)) return ORBX_E_ARG;
+  if (frame.max() > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
+  return frame.max() <= 0 ? ORBX_E_ARG : 0;
+}
+
+// frame.n = f->n and query.n = q->nq (the callers build both from the structs).
+static int search_batch(orbm_t *m, const orbm_frame_t *f, const Ragged &frame, const orbm_queries_t *q, const Ragged &query, int npairs, float nnratio,
+                        int th_dist, int use_second, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_bd, int32_t *d_nm, hipStream_t s,
+                        const SearchOpts &o) {
   if (!m || !f || !q || npairs <= 0 || !d_slot || !d_slot_obs) return ORBX_E_ARG;
-  if (!f->keys_un || !f->descriptors || !q->descriptors || !q->u || !q->v || !q->radius || !q->min_level || !q->max_level) return ORBX_E_ARG;
-  if (!(f->max_x > f->min_x) || !(f->max_y > f->min_y)) return ORBX_E_ARG;
+  if (!q->descriptors || !q->u || !q->v || !q->radius || !q->min_level || !q->max_level) return ORBX_E_ARG;
   // bestDist starts at 256 in the reference: a threshold >= 256 would "accept" a query without any candidate (index -1 there)
   if (th_dist < 0 || th_dist > 255) { m->err = "th_dist must be in [0, 255]"; return ORBX_E_ARG; }
+  const int rf = check_search_frame(m, f, frame);
+  if (rf < 0) return rf;
+  const int frame_stride = frame.stride, query_stride = query.stride, maxn = frame.max(), maxq = query.max();
+  if (maxq <= 0) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   MatchProblemSet M;
   memset(&M, 0, sizeof(M));
   M.kp = reinterpret_cast<const float *>(f->keys_un);
   M.desc = f->descriptors;
   M.u_right = f->u_right;
-  M.frame_stride = frame_stride;
-  M.frame_n = d_frame_n; M.frame_n_stride = frame_n_stride; M.frame_n_const = f->n;
+  M.frame_stride = frame_stride; M.frame_n = frame.live();
   M.min_x = f->min_x; M.min_y = f->min_y;
   M.inv_w = (float)ORBM_GRID_COLS / (f->max_x - f->min_x);   // Frame.cc:379
   M.inv_h = (float)ORBM_GRID_ROWS / (f->max_y - f->min_y);   // Frame.cc:380
   M.qdesc = q->descriptors; M.qu = q->u; M.qv = q->v; M.qr = q->radius; M.qur = q->u_r;
   M.qminl = q->min_level; M.qmaxl = q->max_level; M.qflags = q->flags;
-  M.query_stride = query_stride;
-  M.query_n = d_query_n; M.query_n_stride = query_n_stride; M.query_n_const = q->nq;
+  M.query_stride = query_stride; M.query_n = query.live();
   M.nnratio = nnratio; M.th_dist = th_dist; M.use_second = use_second;
   M.slot = d_slot; M.slot_obs = d_slot_obs; M.match_of_query = d_moq; M.best_dist = d_bd; M.nmatches = d_nm;
 #if defined(RESOLVE_STAMPS) || defined(WALK_STAMPS) || defined(SCAN_STAMPS) || defined(MF_STAMPS) || defined(WIDE_STAMPS)
   M.dbg = (long long *)getenv_ptr("ORBHIP_DBG_PTR");
 #endif
-  M.nleft = o.nleft; M.partner = o.partner; M.qside = o.qside; M.couple = o.couple; M.serial = o.serial; M.qany = o.qany;
-  M.nleft_dev = o.nleft_dev; M.nleft_stride = o.nleft_stride;
+  M.nleft = o.nleft.konst; M.nleft_dev = o.nleft.dev; M.nleft_stride = o.nleft.stride; M.partner = o.partner; M.qside = o.qside; M.couple = o.couple; M.serial = o.serial; M.qany = o.qany;
   for (int i = 0; i < 16; i++) M.inv_sigma2[i] = o.inv_sigma2[i];
-  const int maxn = d_frame_n ? frame_stride : f->n;
-  const int maxq = d_query_n ? query_stride : q->nq;
-  if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
-  if (maxn <= 0 || maxq <= 0) return ORBX_E_ARG;
   // scratch: TOPK keys per query (grows on demand; not on the steady-state path)
   const bool k32 = maxn <= 2048;  // Key32 holds an 11-bit keypoint index
   // Latency mode: with few problems in flight the scan's candidate loop is the critical path (one workgroup per 256 queries walks
@@ -1618,8 +1687,8 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
   if (!m) return ORBX_E_ARG;
   SearchOpts o;
   o.scan_mode = m->scan_mode;
-  return search_batch(m, f, frame_stride, d_frame_n, frame_n_stride, q, query_stride, d_query_n, query_n_stride, npairs, nnratio, th_dist,
-                      use_second, d_slot, d_slot_obs, d_moq, d_bd, d_nm, (hipStream_t)stream_, o);   // verbatim: NULL is the device's default stream
+  return search_batch(m, f, {frame_stride, d_frame_n, frame_n_stride, f ? f->n : 0}, q, {query_stride, d_query_n, query_n_stride, q ? q->nq : 0}, npairs,
+                      nnratio, th_dist, use_second, d_slot, d_slot_obs, d_moq, d_bd, d_nm, (hipStream_t)stream_, o);   // verbatim: NULL is the device's default stream
 }
 
 // The tail of a host search whose outputs were staged as [first .. d_nm]: that range comes down through the pinned mirror in one copy
@@ -1650,23 +1719,25 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
   }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  const size_t fn = sizeof(float) * (size_t)n, fq = sizeof(float) * (size_t)nq, iq = sizeof(int32_t) * (size_t)nq;
+  const size_t N = (size_t)n, NQ = (size_t)nq;
   // the inputs, then the in/out and out-only arrays (downloaded as one range)
-  enum { KP, DESC, UR, QD, QU, QV, QR, QUR, MINL, MAXL, FL, PARTNER, SIDE, SLOT, SOBS, MOQ, BD, NM, ANY, NPARTS };
-  void *d[NPARTS];
-  const int rc = stage(m, s, {{f->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {f->descriptors, 32 * (size_t)n}, {f->u_right, f->u_right ? fn : 0},
-                              {q->descriptors, 32 * (size_t)nq}, {q->u, fq}, {q->v, fq}, {q->radius, fq}, {q->u_r, q->u_r ? fq : 0},
-                              {q->min_level, iq}, {q->max_level, iq}, {q->flags, q->flags ? (size_t)nq : 0},
-                              {partner, partner ? sizeof(int32_t) * (size_t)n : 0}, {qside, qside ? (size_t)nq : 0},
-                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n},
-                              {nullptr, iq}, {nullptr, iq}, {nullptr, sizeof(int32_t)}, {nullptr, o.couple == 2 ? (size_t)nq : 0}}, d, true);
+  Staging S{m};
+  const StagedFrame hf = stage_frame(S, f);
+  const auto qd = S.add(q->descriptors, 32 * NQ);
+  const auto qu = S.add(q->u, NQ), qv = S.add(q->v, NQ), qr = S.add(q->radius, NQ), qur = S.add(q->u_r, q->u_r ? NQ : 0);
+  const auto minl = S.add(q->min_level, NQ), maxl = S.add(q->max_level, NQ);
+  const auto fl = S.add(q->flags, q->flags ? NQ : 0);
+  const auto part = S.add(partner, partner ? N : 0); const auto side = S.add(qside, qside ? NQ : 0);
+  const auto dslot = S.add(slot, N); const auto dsobs = S.add(slot_obs, N);
+  const auto moq = S.out<int32_t>(NQ), bd = S.out<int32_t>(NQ), nmp = S.out<int32_t>(1);
+  const auto any = S.out<uint8_t>(o.couple == 2 ? NQ : 0);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
-  o.partner = (const int32_t *)d[PARTNER]; o.qside = (const uint8_t *)d[SIDE]; o.qany = (uint8_t *)d[ANY];
-  orbm_frame_t df = *f;
-  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
+  o.partner = S.dev(part); o.qside = S.dev(side); o.qany = S.dev(any);
+  const orbm_frame_t df = on_device(S, hf);
   orbm_queries_t dq = *q;
-  dq.descriptors = (const uint8_t *)d[QD]; dq.u = (const float *)d[QU]; dq.v = (const float *)d[QV]; dq.radius = (const float *)d[QR];
-  dq.u_r = (const float *)d[QUR]; dq.min_level = (const int32_t *)d[MINL]; dq.max_level = (const int32_t *)d[MAXL]; dq.flags = (const uint8_t *)d[FL];
+  dq.descriptors = S.dev(qd); dq.u = S.dev(qu); dq.v = S.dev(qv); dq.radius = S.dev(qr); dq.u_r = S.dev(qur);
+  dq.min_level = S.dev(minl); dq.max_level = S.dev(maxl); dq.flags = S.dev(fl);
   // The radii are on the host here: the walk-or-scan decision (pair_walks) is taken now and only the chosen kernels are launched.
   o.scan_mode = m->scan_mode;
   if (m->scan_mode == SCAN_AUTO) {
@@ -1681,13 +1752,13 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
     }
     o.scan_mode = big ? SCAN_DENSE : SCAN_WALK;
   }
-  const int rs = search_batch(m, &df, n, nullptr, 0, &dq, nq, nullptr, 0, 1, nnratio, th_dist, use_second, (int32_t *)d[SLOT], (uint8_t *)d[SOBS],
-                              (int32_t *)d[MOQ], (int32_t *)d[BD], (int32_t *)d[NM], s, o);
+  const int rs = search_batch(m, &df, {n, nullptr, 0, n}, &dq, {nq, nullptr, 0, nq}, 1, nnratio, th_dist, use_second, S.dev(dslot), S.dev(dsobs),
+                              S.dev(moq), S.dev(bd), S.dev(nmp), s, o);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  const int nm = download_slots(m, s, S.dev(dslot), S.dev(dslot), S.dev(dsobs), S.dev(nmp), n, slot, slot_obs);
   if (nm < 0) return nm;
-  if (match_of_query) memcpy(match_of_query, mirror_of(m, d[MOQ]), iq);
-  if (best_dist) memcpy(best_dist, mirror_of(m, d[BD]), iq);
+  if (match_of_query) memcpy(match_of_query, S.host(moq), sizeof(int32_t) * NQ);
+  if (best_dist) memcpy(best_dist, S.host(bd), sizeof(int32_t) * NQ);
   return nm;
 }
 
@@ -1801,43 +1872,70 @@ static int host_scan_mode(const orbm_t *m, const orbm_frame_t *cur, const float 
   return cx * cy <= WALK_MAX_CELLS ? SCAN_WALK : m->scan_mode;
 }
 
-static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
-                                  const orbm_last_frame_t *last0, int last_stride, const int32_t *d_last_n, int last_n_stride, int npairs,
-                                  const float *sf, int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono,
-                                  int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches, hipStream_t s,
-                                  int scan_mode) {
-  if (!m || !cur0 || !last0 || !sf || !cam_params || npairs <= 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
+// What a fisheye-stereo current frame (Nleft != -1) adds to the last-frame core
+struct RigLastExtras { const float *Trl; LiveCount nleft; };   // Nleft has no stride of its own: only its live count
+
+// The device core of both last-frame searches.  Nleft == -1 (rig == NULL): k_lastframe_project, the search, k_rot_prune<0>.
+// Nleft != -1: k_lastframe_project_rig (two queries per last-frame keypoint, their descriptors and side bytes), the search with
+// couple = 2, k_rot_prune<1> (slot conversion, then the pruning).  Arguments are checked before anything is launched.
+static int search_last_frame_batch(orbm_t *m, const orbm_frame_t *cur0, const Ragged &frame, const orbm_last_frame_t *last0, const Ragged &last,
+                                   int npairs, const float *sf, int nlevels, int cam_type, const float *cam_params, float mb, float mbf, float th,
+                                   int bMono, int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches, hipStream_t s,
+                                   int scan_mode, const RigLastExtras *rig = nullptr) {
+  if (!m || !cur0 || !last0 || !sf || !cam_params || (rig && !rig->Trl) || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
   if (!last0->has_mp || !last0->Xw || !last0->mpdesc || !last0->last_keys || !last0->Tcw || !last0->Tlw) return ORBX_E_ARG;
-  const int maxq = d_last_n ? last_stride : last0->n;
-  if (maxq <= 0 || last_stride < maxq) return ORBX_E_ARG;
+  if (!last.valid() || (rig && !frame.valid())) return ORBX_E_ARG;   // kept difference: Nleft == -1 never asked for frame stride >= n
+  const int rf = check_search_frame(m, cur0, frame);
+  if (rf < 0) return rf;
+  if (rig && !rig->nleft.dev && (rig->nleft.konst < 0 || rig->nleft.konst > cur0->n)) return ORBX_E_ARG;
+  if (rig && (long long)last.stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
+  if (npairs == 0) return rig ? 0 : ORBX_E_ARG;   // kept difference: an empty batch is refused for Nleft == -1 and is no work for a rig
   MCHECK(m, hipSetDevice(m->device));
+  const int qs = rig ? 2 : 1;                     // queries per last-frame keypoint
   LastFrameParams P;
   memset(&P, 0, sizeof(P));
   QueryScratch &Q = P.Q;
-  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, last_stride, Q);
+  RigScratch G = {};
+  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, qs * last.stride, Q, rig ? &G : nullptr);   // rig: 2 * stride and the RigScratch extras
   if (rq < 0) return rq;
   int32_t *moq = d_moq ? d_moq : Q.moq;
   P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
   P.Tcw = last0->Tcw; P.Tlw = last0->Tlw;
-  P.last_stride = last_stride; P.last_n = d_last_n; P.last_n_stride = last_n_stride; P.last_n_const = last0->n;
+  P.last_stride = last.stride; P.last_n = last.live();
   fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
-  P.mb = mb; P.mbf = mbf; P.th = th; P.bMono = bMono ? 1 : 0;
-  hipLaunchKernelGGL(k_lastframe_project, dim3((last_stride + 255) / 256, npairs), dim3(256), 0, s, P);
-  const orbm_queries_t q = scratch_view(Q, last0->n, last0->mpdesc, cur0->u_right != nullptr);
+  P.mb = mb; P.mbf = rig ? 0.f : mbf; P.th = th; P.bMono = bMono ? 1 : 0;   // kept difference: a rig has no mbf (no mvuRight test, :2139)
+  const dim3 pgrid((last.stride + 255) / 256, npairs);
   SearchOpts o;
   o.scan_mode = scan_mode;
-  int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, last_stride, d_last_n, last_n_stride, npairs, 0.f, ORBM_TH_HIGH, 0,
-                        d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // :2148-2162
+  orbm_frame_t f = *cur0;
+  Ragged query = last;
+  if (rig) {
+    RigProjectParams R;
+    memset(&R, 0, sizeof(R));
+    for (int i = 0; i < 12; i++) R.Trl[i] = rig->Trl[i];
+    R.mpdesc = last0->mpdesc; R.qdesc = G.qdesc; R.qside = G.qside; R.query_n = G.query_n;
+    hipLaunchKernelGGL(k_lastframe_project_rig, pgrid, dim3(256), 0, s, P, R);
+    f.u_right = nullptr;   // kept difference: Nleft != -1 passes no u_right to the search and asks for no right coordinate (with_ur false)
+    o.nleft = rig->nleft;
+    o.couple = 2; o.qside = G.qside; o.qany = G.qany;   // :2126: an empty left window drops the right pass
+    query = {2 * last.stride, last.d_n ? G.query_n : nullptr, 1, 2 * last0->n};   // the kernel wrote 2 * the live count per problem
+  } else {
+    hipLaunchKernelGGL(k_lastframe_project, pgrid, dim3(256), 0, s, P);
+  }
+  const orbm_queries_t q = scratch_view(Q, query.n, rig ? G.qdesc : last0->mpdesc, f.u_right != nullptr);
+  const int rc = search_batch(m, &f, frame, &q, query, npairs, 0.f, ORBM_TH_HIGH, 0, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // :2148-2162; rig :2128-2162, :2208-2256
   if (rc < 0) return rc;
-  if (checkOri) {                                                                                                            // :2177-2185, :2263-2286
+  // kept difference: k_rot_prune<0> only with checkOri (:2177-2185, :2263-2286); k_rot_prune<1> always (slot conversion), pruning with checkOri
+  if (rig || checkOri) {
     RotPruneParams R;
     memset(&R, 0, sizeof(R));
-    R.last_kp = reinterpret_cast<const float *>(last0->last_keys);
-    R.last_stride = last_stride; R.last_n = d_last_n; R.last_n_stride = last_n_stride; R.last_n_const = last0->n;
-    R.cur_kp = reinterpret_cast<const float *>(cur0->keys_un); R.frame_stride = frame_stride;
-    R.moq = moq; R.slot = d_slot; R.slot_obs = d_slot_obs; R.nmatches = d_nmatches; R.prune = 1;
-    hipLaunchKernelGGL(k_rot_prune<0>, dim3(npairs), dim3(256), 0, s, R);
+    R.last_kp = reinterpret_cast<const float *>(last0->last_keys);   // :2169-2171
+    R.last_stride = last.stride; R.last_n = last.live();
+    R.cur_kp = reinterpret_cast<const float *>(cur0->keys_un); R.frame_stride = frame.stride;
+    R.moq = moq; R.slot = d_slot; R.slot_obs = d_slot_obs; R.nmatches = d_nmatches; R.prune = checkOri ? 1 : 0;
+    if (rig) hipLaunchKernelGGL(k_rot_prune<1>, dim3(npairs), dim3(256), 0, s, R);
+    else hipLaunchKernelGGL(k_rot_prune<0>, dim3(npairs), dim3(256), 0, s, R);
   }
   MCHECK(m, hipGetLastError());
   return 0;
@@ -1850,16 +1948,16 @@ int orbm_search_by_projection_last_frame_batch_device(orbm_t *m, const orbm_fram
                                                       int checkOri, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
                                                       int32_t *d_nmatches, void *stream_) {
   if (!m) return ORBX_E_ARG;
-  return search_last_frame_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, last0, last_stride, d_last_n, last_n_stride, npairs, sf, nlevels,
-                                 cam_type, cam_params, mb, mbf, th, bMono, checkOri, d_slot, d_slot_obs, d_moq, d_nmatches, (hipStream_t)stream_,
-                                 m->scan_mode);
+  return search_last_frame_batch(m, cur0, {frame_stride, d_frame_n, frame_n_stride, cur0 ? cur0->n : 0}, last0,
+                                 {last_stride, d_last_n, last_n_stride, last0 ? last0->n : 0}, npairs, sf, nlevels, cam_type, cam_params, mb, mbf, th,
+                                 bMono, checkOri, d_slot, d_slot_obs, d_moq, d_nmatches, (hipStream_t)stream_, m->scan_mode);
 }
 
-int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, int nLast,
-                                         const uint8_t *has_mp, const float *Xw, const uint8_t *mpdesc,
-                                         const orbx_keypoint_t *last_keys, const uint8_t *obs, const float *Tcw,
-                                         const float *Tlw, int cam_type, const float *cam_params, float mb, float mbf,
-                                         float th, int bMono, int checkOri, int32_t *slot, uint8_t *slot_obs) {
+// The host form of both last-frame searches (the rig's own checks are its wrapper's): one block up, one down, one synchronisation; npairs = 1.
+static int search_last_frame_host(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, int nLast, const uint8_t *has_mp, const float *Xw,
+                                  const uint8_t *mpdesc, const orbx_keypoint_t *last_keys, const uint8_t *obs, const float *Tcw, const float *Tlw,
+                                  int cam_type, const float *cam_params, float mb, float mbf, float th, int bMono, int checkOri, int32_t *slot,
+                                  uint8_t *slot_obs, const RigLastExtras *rig) {
   if (!m || !cur || !sf || nLast < 0 || !Tcw || !Tlw || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
   if (nLast > 0 && (!has_mp || !Xw || !mpdesc || !last_keys)) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16) return ORBX_E_ARG;
@@ -1869,70 +1967,126 @@ int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, con
   if (!cur->keys_un || !cur->descriptors) return ORBX_E_ARG;
   for (int i = 0; i < nLast; i++)
     if (has_mp[i] && (last_keys[i].octave < 0 || last_keys[i].octave >= nlevels)) return ORBX_E_ARG;
+  orbm_last_frame_t last;
+  last.n = nLast; last.has_mp = has_mp; last.Xw = Xw; last.mpdesc = mpdesc; last.last_keys = last_keys; last.obs = obs; last.Tcw = Tcw; last.Tlw = Tlw;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  // one staged block up, one block down, one synchronisation (as search_host); projection, search and pruning on the device
-  enum { KP, DESC, UR, HAS, XW, MD, LK, OBS, TC, TL, SLOT, SOBS, NM, NPARTS };
-  void *d[NPARTS];
-  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
-                              {cur->u_right, cur->u_right ? sizeof(float) * (size_t)n : 0}, {has_mp, (size_t)nLast}, {Xw, 3 * sizeof(float) * (size_t)nLast},
-                              {mpdesc, 32 * (size_t)nLast}, {last_keys, sizeof(orbx_keypoint_t) * (size_t)nLast}, {obs, obs ? (size_t)nLast : 0},
-                              {Tcw, 16 * sizeof(float)}, {Tlw, 16 * sizeof(float)},
-                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t)}}, d, true);
+  Staging S{m};
+  const StagedFrame hf = stage_frame(S, cur, !rig);
+  const StagedLast hl = stage_last_frame(S, last);
+  const auto dslot = S.add(slot, (size_t)n); const auto dsobs = S.add(slot_obs, (size_t)n);
+  const auto nm = S.out<int32_t>(1);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
-  orbm_frame_t df = *cur;
-  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
-  orbm_last_frame_t dl;
-  memset(&dl, 0, sizeof(dl));
-  dl.n = nLast;
-  dl.has_mp = (const uint8_t *)d[HAS]; dl.Xw = (const float *)d[XW]; dl.mpdesc = (const uint8_t *)d[MD];
-  dl.last_keys = (const orbx_keypoint_t *)d[LK]; dl.obs = (const uint8_t *)d[OBS]; dl.Tcw = (const float *)d[TC]; dl.Tlw = (const float *)d[TL];
-  const int scan_mode = host_scan_mode(m, cur, sf, nLast, has_mp, last_keys, th);
-  const int rs = search_last_frame_batch(m, &df, n, nullptr, 0, &dl, nLast, nullptr, 0, 1, sf, nlevels, cam_type, cam_params, mb, mbf, th, bMono,
-                                         checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
+  const orbm_frame_t df = on_device(S, hf);
+  const orbm_last_frame_t dl = on_device(S, hl);
+  const int scan_mode = host_scan_mode(m, cur, sf, last.n, last.has_mp, last.last_keys, th);   // kept difference: decided on the host here
+  const int rs = search_last_frame_batch(m, &df, {n, nullptr, 0, n}, &dl, {last.n, nullptr, 0, last.n}, 1, sf, nlevels, cam_type, cam_params, mb, mbf,
+                                         th, bMono, checkOri, S.dev(dslot), S.dev(dsobs), nullptr, S.dev(nm), s, scan_mode, rig);
   if (rs < 0) return rs;
-  return download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  return download_slots(m, s, S.dev(dslot), S.dev(dslot), S.dev(dsobs), S.dev(nm), n, slot, slot_obs);
 }
 
-// Tracking::SearchLocalPoints on the device: k_local_map_project (isInFrustum + the query preparation of M2), then the M2 search
-// (use_second, nnratio, TH_HIGH) with sequential claims in local-map order.  Arguments are checked before anything is launched.
-static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
-                              const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs, const float *sf,
-                              int nlevels, float log_sf, int cam_type, const float *cam_params, float mbf, float view_cos_limit, float th,
-                              int bFarPoints, float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
-                              const orbm_track_t *track0, int32_t *d_nmatches, hipStream_t s, bool search) {
-  if (!m || !cur0 || !map0 || !track0 || !sf || !cam_params || npairs <= 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
+int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, int nLast,
+                                         const uint8_t *has_mp, const float *Xw, const uint8_t *mpdesc,
+                                         const orbx_keypoint_t *last_keys, const uint8_t *obs, const float *Tcw,
+                                         const float *Tlw, int cam_type, const float *cam_params, float mb, float mbf,
+                                         float th, int bMono, int checkOri, int32_t *slot, uint8_t *slot_obs) {
+  return search_last_frame_host(m, cur, sf, nlevels, nLast, has_mp, Xw, mpdesc, last_keys, obs, Tcw, Tlw, cam_type, cam_params, mb, mbf, th, bMono,
+                                checkOri, slot, slot_obs, nullptr);
+}
+
+static bool valid_track_rig(const orbm_track_rig_t *t) {
+  return t->in_view && t->in_view_r && t->proj_x && t->proj_y && t->depth && t->view_cos && t->proj_xr && t->proj_yr && t->depth_r &&
+         t->view_cos_r && t->level && t->level_r;
+}
+
+// What Nleft != -1 adds to the local-map core: right camera, stereo matches (device [npairs][frame_stride] or NULL), Nleft, serial
+// (see orbm_search_local_points_fisheye_batch_device) and the track fields of both cameras, which stand in for the core's orbm_track_t.
+struct RigLocalExtras {
+  const float *Trl, *tlr; int cam_type2; const float *cam_params2;
+  const int32_t *d_l2r, *d_r2l; LiveCount nleft; int serial;
+  const orbm_track_rig_t *track;
+};
+
+// Tracking::SearchLocalPoints on the device.  Nleft == -1 (rig == NULL): k_local_map_project (isInFrustum + M2's query preparation), then
+// the M2 search (use_second, nnratio, TH_HIGH), claims in local-map order.  Nleft != -1: k_local_map_project_rig (both frustum tests, two
+// queries per point, the partner table), the search with couple = 1 (:127), k_rig_slot_convert.  Checks come before any launch.
+static int search_local_batch(orbm_t *m, const orbm_frame_t *cur0, const Ragged &frame, const orbm_local_map_t *map0, const Ragged &map, int npairs,
+                              const float *sf, int nlevels, float log_sf, int cam_type, const float *cam_params, float mbf, float view_cos_limit,
+                              float th, int bFarPoints, float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq,
+                              const orbm_track_t *track0, int32_t *d_nmatches, hipStream_t s, bool search, const RigLocalExtras *rig = nullptr) {
+  if (!m || !cur0 || !map0 || !sf || !cam_params || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
+  if (rig ? !rig->track || !rig->cam_params2 || !rig->Trl || !rig->tlr || (rig->cam_type2 != 0 && rig->cam_type2 != 1) : !track0) return ORBX_E_ARG;
   if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
-  if (!valid_local_map(map0) || !valid_track(track0)) return ORBX_E_ARG;
-  if (search && (!cur0->keys_un || !cur0->descriptors)) return ORBX_E_ARG;
-  const int maxq = d_map_n ? map_stride : map0->n;
-  const int maxn = d_frame_n ? frame_stride : cur0->n;
-  if (maxq <= 0 || map_stride < maxq || map0->n < 0 || (!d_map_n && map_stride < map0->n)) return ORBX_E_ARG;
-  if (search && (maxn <= 0 || frame_stride < maxn || (!d_frame_n && frame_stride < cur0->n))) return ORBX_E_ARG;
-  if (maxn > ORBM_MAX_KEYPOINTS) { m->err = "more than 15360 keypoints per frame not supported by the search kernels"; return ORBX_E_ARG; }
-  if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
+  if (!valid_local_map(map0) || !(rig ? valid_track_rig(rig->track) : valid_track(track0))) return ORBX_E_ARG;
+  if (!map.valid() || (search && !frame.valid())) return ORBX_E_ARG;
+  const int rf = search ? check_search_frame(m, cur0, frame) : 0;   // no search (host forms, a frame without keypoints): the frame is not read
+  if (rf < 0) return rf;
+  if (rig && search && !rig->nleft.dev && (rig->nleft.konst < 0 || rig->nleft.konst > cur0->n)) return ORBX_E_ARG;
+  if (rig && (long long)map.stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
+  if (npairs == 0) return rig ? 0 : ORBX_E_ARG;   // kept difference: an empty batch is refused for Nleft == -1 and is no work for a rig
   MCHECK(m, hipSetDevice(m->device));
+  const int qs = rig ? 2 : 1;                     // queries per local map point
   LocalMapParams P;
   memset(&P, 0, sizeof(P));
   QueryScratch &Q = P.Q;
-  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, map_stride, Q);
+  RigScratch S = {};
+  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, qs * map.stride, Q, rig ? &S : nullptr);   // rig: 2 * stride and the RigScratch extras
   if (rq < 0) return rq;
+  const bool partners = rig && search && (rig->d_l2r || rig->d_r2l);
+  const size_t pbytes = sizeof(int32_t) * (size_t)npairs * (size_t)frame.stride;
+  if (partners && pbytes > m->d_partner.bytes) {
+    MCHECK(m, hipStreamSynchronize(s));
+    MCHECK(m, m->d_partner.reserve(pbytes + (pbytes >> 2)));
+  }
+  int32_t *moq = d_moq ? d_moq : Q.moq;
   P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
   P.obs = map0->obs; P.Tcw = map0->Tcw;
-  P.map_stride = map_stride; P.map_n = d_map_n; P.map_n_stride = map_n_stride; P.map_n_const = map0->n;
+  P.map_stride = map.stride; P.map_n = map.live();
   fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
   P.log_sf = log_sf;
-  P.mbf = mbf; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
-  P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
-  P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
-  hipLaunchKernelGGL(k_local_map_project, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P);
+  P.mbf = rig ? 0.f : mbf; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
+  const orbm_track_rig_t *r = rig ? rig->track : nullptr;
+  const orbm_track_t t = r ? orbm_track_t{r->in_view, r->proj_x, r->proj_y, r->proj_xr, r->depth, r->view_cos, r->level} : *track0;
+  P.in_view = t.in_view; P.proj_x = t.proj_x; P.proj_y = t.proj_y; P.proj_xr = t.proj_xr; P.depth = t.depth; P.view_cos = t.view_cos; P.level = t.level;
+  const dim3 pgrid((map.stride + 255) / 256, npairs);
+  SearchOpts o;
+  o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
+  orbm_frame_t f = *cur0;
+  Ragged query = map;
+  if (rig) {
+    RigLocalParams G;
+    memset(&G, 0, sizeof(G));
+    for (int i = 0; i < 12; i++) G.Trl[i] = rig->Trl[i];
+    for (int i = 0; i < 3; i++) G.tlr[i] = rig->tlr[i];
+    G.cam_type2 = rig->cam_type2;
+    for (int k = 0; k < (rig->cam_type2 == 0 ? 4 : 8); k++) G.cam2[k] = rig->cam_params2[k];
+    G.mpdesc = map0->mpdesc;
+    G.in_view_r = r->in_view_r; G.proj_yr = r->proj_yr; G.depth_r = r->depth_r; G.view_cos_r = r->view_cos_r; G.level_r = r->level_r;
+    G.qdesc = S.qdesc; G.qside = S.qside; G.query_n = S.query_n;
+    G.l2r = rig->d_l2r; G.r2l = rig->d_r2l; G.partner = partners ? (int32_t *)m->d_partner.p : nullptr;
+    G.frame_stride = frame.stride; G.frame_n = frame.live(); G.nleft = rig->nleft;
+    hipLaunchKernelGGL(k_local_map_project_rig, pgrid, dim3(256), 0, s, P, G);
+    f.u_right = nullptr;   // kept difference: Nleft != -1 has no mvuRight test (ORBmatcher.cc:93)
+    o.nleft = rig->nleft;
+    o.couple = 1; o.qside = S.qside;   // ORBmatcher.cc:127
+    o.partner = G.partner; o.serial = partners ? rig->serial : 0;
+    query = {2 * map.stride, map.d_n ? S.query_n : nullptr, 1, 2 * map0->n};   // the kernel wrote 2 * the live count per problem
+  } else {
+    hipLaunchKernelGGL(k_local_map_project, pgrid, dim3(256), 0, s, P);
+  }
   if (search) {
-    const orbm_queries_t q = scratch_view(Q, map0->n, map0->mpdesc, cur0->u_right != nullptr);
-    SearchOpts o;
-    o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
-    const int rc = search_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, &q, map_stride, d_map_n, map_n_stride, npairs, nnratio,
-                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, d_moq ? d_moq : Q.moq, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-139
+    const orbm_queries_t q = scratch_view(Q, query.n, rig ? S.qdesc : map0->mpdesc, f.u_right != nullptr);
+    const int rc = search_batch(m, &f, frame, &q, query, npairs, nnratio, ORBM_TH_HIGH, 1, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-139; rig :75-141, :153-209
     if (rc < 0) return rc;
+    if (rig) {   // the search left query ids in the slots: back to local-map indices
+      RigSlotParams C;
+      memset(&C, 0, sizeof(C));
+      C.moq = moq; C.map_stride = map.stride; C.map_n = map.live();
+      C.partner = o.partner; C.slot = d_slot; C.frame_stride = frame.stride;
+      hipLaunchKernelGGL(k_rig_slot_convert, dim3(npairs), dim3(256), 0, s, C);
+    }
   }
   MCHECK(m, hipGetLastError());
   return 0;
@@ -1944,9 +2098,9 @@ int orbm_search_local_points_batch_device(orbm_t *m, const orbm_frame_t *cur0, i
                                           float view_cos_limit, float th, int bFarPoints, float th_far, float nnratio, int32_t *d_slot,
                                           uint8_t *d_slot_obs, int32_t *d_moq, const orbm_track_t *track0, int32_t *d_nmatches, void *stream_) {
   if (!m) return ORBX_E_ARG;
-  return search_local_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, map0, map_stride, d_map_n, map_n_stride, npairs, sf, nlevels, log_sf,
-                            cam_type, cam_params, mbf, view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, track0,
-                            d_nmatches, (hipStream_t)stream_, true);
+  return search_local_batch(m, cur0, {frame_stride, d_frame_n, frame_n_stride, cur0 ? cur0->n : 0}, map0,
+                            {map_stride, d_map_n, map_n_stride, map0 ? map0->n : 0}, npairs, sf, nlevels, log_sf, cam_type, cam_params, mbf,
+                            view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, track0, d_nmatches, (hipStream_t)stream_, true);
 }
 
 int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, float log_sf, const orbm_local_map_t *map,
@@ -1963,37 +2117,30 @@ int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   // one staged block up, one block down, one synchronisation; a frame without keypoints still gets its track fields
-  const size_t fp = sizeof(float) * (size_t)nmp;
-  enum { KP, DESC, UR, ELIG, XW, NRM, MAXD, MIND, MD, OBS, TC, SLOT, SOBS, MOQ, INV, PX, PY, PXR, DEP, VC, LVL, NM, NPARTS };
-  void *d[NPARTS];
-  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
-                              {cur->u_right, cur->u_right ? sizeof(float) * (size_t)n : 0}, {map->eligible, (size_t)nmp}, {map->Xw, 3 * fp},
-                              {map->normal, 3 * fp}, {map->max_dist, fp}, {map->min_dist, fp}, {map->mpdesc, 32 * (size_t)nmp},
-                              {map->obs, map->obs ? (size_t)nmp : 0}, {map->Tcw, 16 * sizeof(float)},
-                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t) * (size_t)nmp},
-                              {nullptr, (size_t)nmp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp},
-                              {nullptr, sizeof(int32_t)}}, d, true);
+  const size_t N = (size_t)n, NP = (size_t)nmp;
+  Staging S{m};
+  const StagedFrame hf = stage_frame(S, cur);
+  const StagedMap hm = stage_local_map(S, map);
+  const auto hslot = S.add(slot, N); const auto hsobs = S.add(slot_obs, N);
+  const auto hmoq = S.out<int32_t>(NP);
+  const auto hinv = S.out<uint8_t>(NP);
+  const auto hpx = S.out<float>(NP), hpy = S.out<float>(NP), hpxr = S.out<float>(NP), hdep = S.out<float>(NP), hvc = S.out<float>(NP);
+  const auto hlvl = S.out<int32_t>(NP), hnm = S.out<int32_t>(1);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
-  orbm_frame_t df = *cur;
-  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = (const float *)d[UR];
-  orbm_local_map_t dm = *map;
-  dm.eligible = (const uint8_t *)d[ELIG]; dm.Xw = (const float *)d[XW]; dm.normal = (const float *)d[NRM]; dm.max_dist = (const float *)d[MAXD];
-  dm.min_dist = (const float *)d[MIND]; dm.mpdesc = (const uint8_t *)d[MD]; dm.obs = (const uint8_t *)d[OBS]; dm.Tcw = (const float *)d[TC];
-  orbm_track_t dt;
-  dt.in_view = (uint8_t *)d[INV]; dt.proj_x = (float *)d[PX]; dt.proj_y = (float *)d[PY]; dt.proj_xr = (float *)d[PXR];
-  dt.depth = (float *)d[DEP]; dt.view_cos = (float *)d[VC]; dt.level = (int32_t *)d[LVL];
-  int32_t *dslot = n > 0 ? (int32_t *)d[SLOT] : (int32_t *)d[MOQ], *dnm = (int32_t *)d[NM];   // n == 0: no search, any non-null pointer
-  uint8_t *dsobs = n > 0 ? (uint8_t *)d[SOBS] : (uint8_t *)d[INV];
-  const int rs = search_local_batch(m, &df, n, nullptr, 0, &dm, nmp, nullptr, 0, 1, sf, nlevels, log_sf, cam_type, cam_params, mbf, view_cos_limit,
-                                    th, bFarPoints, th_far, nnratio, dslot, dsobs, (int32_t *)d[MOQ], &dt, dnm, s, n > 0);
+  const orbm_frame_t df = on_device(S, hf);
+  const orbm_local_map_t dm = on_device(S, hm);
+  const orbm_track_t dt = {S.dev(hinv), S.dev(hpx), S.dev(hpy), S.dev(hpxr), S.dev(hdep), S.dev(hvc), S.dev(hlvl)};
+  int32_t *dslot = n > 0 ? S.dev(hslot) : S.dev(hmoq);   // n == 0: no search, any non-null pointer
+  uint8_t *dsobs = n > 0 ? S.dev(hsobs) : S.dev(hinv);
+  const int rs = search_local_batch(m, &df, {n, nullptr, 0, n}, &dm, {nmp, nullptr, 0, nmp}, 1, sf, nlevels, log_sf, cam_type, cam_params, mbf,
+                                    view_cos_limit, th, bFarPoints, th_far, nnratio, dslot, dsobs, S.dev(hmoq), &dt, S.dev(hnm), s, n > 0);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, n > 0 ? d[SLOT] : d[MOQ], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  const int nm = download_slots(m, s, n > 0 ? (void *)S.dev(hslot) : (void *)S.dev(hmoq), S.dev(hslot), S.dev(hsobs), S.dev(hnm), n, slot, slot_obs);
   if (nm < 0) return nm;
-  const int32_t *moq = (const int32_t *)mirror_of(m, d[MOQ]);
-  const uint8_t *inv = (const uint8_t *)mirror_of(m, d[INV]);
-  const float *px = (const float *)mirror_of(m, d[PX]), *py = (const float *)mirror_of(m, d[PY]), *pxr = (const float *)mirror_of(m, d[PXR]);
-  const float *dep = (const float *)mirror_of(m, d[DEP]), *vc = (const float *)mirror_of(m, d[VC]);
-  const int32_t *lvl = (const int32_t *)mirror_of(m, d[LVL]);
+  const int32_t *moq = S.host(hmoq), *lvl = S.host(hlvl);
+  const uint8_t *inv = S.host(hinv);
+  const float *px = S.host(hpx), *py = S.host(hpy), *pxr = S.host(hpxr), *dep = S.host(hdep), *vc = S.host(hvc);
   // only what isInFrustum writes: in_view always, the projection of eligible points, the rest where in view
   for (int i = 0; i < nmp; i++) {
     if (match_of_point) match_of_point[i] = n > 0 ? moq[i] : -1;
@@ -2034,65 +2181,8 @@ int orbm_search_by_projection_fisheye(orbm_t *m, const orbm_frame_t *f, int n_le
     if ((fl & 1) && !(fl & 2)) release = true;
   }
   SearchOpts o;
-  o.nleft = n_left; o.couple = 1; o.serial = (anyp && release) ? 1 : 0;
+  o.nleft.konst = n_left; o.couple = 1; o.serial = (anyp && release) ? 1 : 0;
   return search_host(m, f, q, nnratio, th_dist, 1, slot, slot_obs, match_of_query, best_dist, o, anyp ? partner.data() : nullptr, side.data());
-}
-
-// The device core of the last-frame search of a fisheye-stereo current frame: k_lastframe_project_rig (two queries per last-frame
-// keypoint, their descriptors and side bytes), the search with couple = 2, k_rot_prune<1> (slot conversion, then the pruning).
-// Arguments are checked before anything is launched.
-static int search_last_frame_rig_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
-                                       const int32_t *d_n_left, int n_left_stride, int n_left, const orbm_last_frame_t *last0, int last_stride,
-                                       const int32_t *d_last_n, int last_n_stride, int npairs, const float *sf, int nlevels, const float *Trl,
-                                       int cam_type, const float *cam_params, float mb, float th, int bMono, int checkOri, int32_t *d_slot,
-                                       uint8_t *d_slot_obs, int32_t *d_moq, int32_t *d_nmatches, hipStream_t s, int scan_mode) {
-  if (!m || !cur0 || !last0 || !sf || !cam_params || !Trl || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches) return ORBX_E_ARG;
-  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1)) return ORBX_E_ARG;
-  if (!last0->has_mp || !last0->Xw || !last0->mpdesc || !last0->last_keys || !last0->Tcw || !last0->Tlw) return ORBX_E_ARG;
-  if (!cur0->keys_un || !cur0->descriptors || !(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y)) return ORBX_E_ARG;
-  const int maxq = d_last_n ? last_stride : last0->n;
-  const int maxn = d_frame_n ? frame_stride : cur0->n;
-  if (maxq <= 0 || last_stride < maxq || maxn <= 0 || frame_stride < maxn) return ORBX_E_ARG;
-  if (!d_n_left && (n_left < 0 || n_left > cur0->n)) return ORBX_E_ARG;
-  if ((long long)last_stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
-  if (npairs == 0) return 0;
-  MCHECK(m, hipSetDevice(m->device));
-  LastFrameParams P;
-  memset(&P, 0, sizeof(P));
-  QueryScratch &Q = P.Q;
-  RigScratch G;
-  const int rq = carve_query_scratch(m, m->d_lfq, s, npairs, 2 * last_stride, Q, &G);
-  if (rq < 0) return rq;
-  int32_t *moq = d_moq ? d_moq : Q.moq;
-  P.has_mp = last0->has_mp; P.Xw = last0->Xw; P.last_kp = reinterpret_cast<const float *>(last0->last_keys); P.obs = last0->obs;
-  P.Tcw = last0->Tcw; P.Tlw = last0->Tlw;
-  P.last_stride = last_stride; P.last_n = d_last_n; P.last_n_stride = last_n_stride; P.last_n_const = last0->n;
-  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
-  P.mb = mb; P.mbf = 0.f; P.th = th; P.bMono = bMono ? 1 : 0;
-  RigProjectParams R;
-  memset(&R, 0, sizeof(R));
-  for (int i = 0; i < 12; i++) R.Trl[i] = Trl[i];
-  R.mpdesc = last0->mpdesc; R.qdesc = G.qdesc; R.qside = G.qside; R.query_n = G.query_n;
-  hipLaunchKernelGGL(k_lastframe_project_rig, dim3((last_stride + 255) / 256, npairs), dim3(256), 0, s, P, R);
-  const orbm_queries_t q = scratch_view(Q, 2 * last0->n, G.qdesc, false);
-  orbm_frame_t f = *cur0;
-  f.u_right = nullptr;  // Nleft != -1: no mvuRight test (:2139)
-  SearchOpts o;
-  o.scan_mode = scan_mode;
-  o.nleft = n_left; o.nleft_dev = d_n_left; o.nleft_stride = n_left_stride;
-  o.couple = 2; o.qside = G.qside; o.qany = G.qany;   // :2126: an empty left window drops the right pass
-  const int rc = search_batch(m, &f, frame_stride, d_frame_n, frame_n_stride, &q, 2 * last_stride, d_last_n ? G.query_n : nullptr, 1, npairs, 0.f,
-                              ORBM_TH_HIGH, 0, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // :2128-2162, :2208-2256
-  if (rc < 0) return rc;
-  RotPruneParams H;
-  memset(&H, 0, sizeof(H));
-  H.last_kp = reinterpret_cast<const float *>(last0->last_keys);   // :2169-2171
-  H.last_stride = last_stride; H.last_n = d_last_n; H.last_n_stride = last_n_stride; H.last_n_const = last0->n;
-  H.cur_kp = reinterpret_cast<const float *>(cur0->keys_un); H.frame_stride = frame_stride;
-  H.moq = moq; H.slot = d_slot; H.slot_obs = d_slot_obs; H.nmatches = d_nmatches; H.prune = checkOri ? 1 : 0;
-  hipLaunchKernelGGL(k_rot_prune<1>, dim3(npairs), dim3(256), 0, s, H);
-  MCHECK(m, hipGetLastError());
-  return 0;
 }
 
 int orbm_search_by_projection_last_frame_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
@@ -2104,9 +2194,10 @@ int orbm_search_by_projection_last_frame_fisheye_batch_device(orbm_t *m, const o
                                                               void *stream_) {
   if (!m) return ORBX_E_ARG;
   if (frame_stride > ORBM_FISHEYE_MAX_KEYPOINTS) { m->err = "more than 12960 keypoints (left + right) per fisheye-stereo frame not supported by the resident search"; return ORBX_E_ARG; }
-  return search_last_frame_rig_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride, n_left, last0, last_stride, d_last_n,
-                                     last_n_stride, npairs, sf, nlevels, Trl, cam_type, cam_params, mb, th, bMono, checkOri, d_slot, d_slot_obs, d_moq,
-                                     d_nmatches, (hipStream_t)stream_, m->scan_mode);
+  const RigLastExtras rig = {Trl, {d_n_left, n_left_stride, n_left}};
+  return search_last_frame_batch(m, cur0, {frame_stride, d_frame_n, frame_n_stride, cur0 ? cur0->n : 0}, last0,
+                                 {last_stride, d_last_n, last_n_stride, last0 ? last0->n : 0}, npairs, sf, nlevels, cam_type, cam_params, mb, 0.f, th,
+                                 bMono, checkOri, d_slot, d_slot_obs, d_moq, d_nmatches, (hipStream_t)stream_, m->scan_mode, &rig);
 }
 
 int orbm_rig_concat_batch_device(int nframes, const orbx_keypoint_t *d_keysL, const uint8_t *d_descL, const int32_t *d_countsL,
@@ -2212,32 +2303,35 @@ int orbm_stereo_fisheye_matches(orbm_t *m, const orbx_keypoint_t *keysL, const u
   hipStream_t s = m->stream;
   // one staged block up (p3d is in/out: unmatched entries keep the caller's values), one block down, one synchronisation
   const int32_t counts[4] = {nL, monoL, nR, monoR};
-  enum { KL, DL, KR, DR, CNT, P3D, L2R, R2L, DEP, NM, NPARTS };
-  void *d[NPARTS];
-  const int rc = stage(m, s, {{keysL, sizeof(orbx_keypoint_t) * (size_t)nL}, {descL, 32 * (size_t)nL}, {keysR, sizeof(orbx_keypoint_t) * (size_t)nR},
-                              {descR, 32 * (size_t)nR}, {counts, sizeof(counts)}, {p3d, 3 * sizeof(float) * (size_t)nL},
-                              {nullptr, sizeof(int32_t) * (size_t)cap}, {nullptr, sizeof(int32_t) * (size_t)cap}, {nullptr, sizeof(float) * (size_t)cap},
-                              {nullptr, 2 * sizeof(int32_t)}}, d, true);
+  const size_t NL = (size_t)nL, NR = (size_t)nR, CAP = (size_t)cap;
+  Staging S{m};
+  const auto hkl = S.add(keysL, NL); const auto hdl = S.add(descL, 32 * NL);
+  const auto hkr = S.add(keysR, NR); const auto hdr = S.add(descR, 32 * NR);
+  const auto hcnt = S.add(counts, 4);
+  const auto hp3 = S.add((const float *)p3d, 3 * NL);
+  const auto hl2r = S.out<int32_t>(CAP), hr2l = S.out<int32_t>(CAP);
+  const auto hdep = S.out<float>(CAP); const auto hnm = S.out<int32_t>(2);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
-  const int32_t *cnt = (const int32_t *)d[CNT];
+  const int32_t *cnt = S.dev(hcnt);
   // an empty side has no device part: any non-null address stands in, its count keeps every access away
-  const void *kl = d[KL] ? d[KL] : d[CNT], *dl = d[DL] ? d[DL] : d[CNT], *kr = d[KR] ? d[KR] : d[CNT], *dr = d[DR] ? d[DR] : d[CNT];
-  float *dp3 = d[P3D] ? (float *)d[P3D] : (float *)d[DEP];
-  const int rs = orbm_stereo_fisheye_matches_batch_device(m, 1, (const orbx_keypoint_t *)kl, (const uint8_t *)dl, cnt, (const orbx_keypoint_t *)kr,
-                                                          (const uint8_t *)dr, cnt + 2, cap, level_sigma2, nlevels, Tlr, cam_params, cam_params2, cap,
-                                                          (int32_t *)d[L2R], (int32_t *)d[R2L], (float *)d[DEP], dp3, (int32_t *)d[NM], s);
+  const orbx_keypoint_t *kl = nL ? S.dev(hkl) : (const orbx_keypoint_t *)cnt, *kr = nR ? S.dev(hkr) : (const orbx_keypoint_t *)cnt;
+  const uint8_t *dl = nL ? S.dev(hdl) : (const uint8_t *)cnt, *dr = nR ? S.dev(hdr) : (const uint8_t *)cnt;
+  float *dp3 = nL ? S.dev(hp3) : S.dev(hdep);
+  const int rs = orbm_stereo_fisheye_matches_batch_device(m, 1, kl, dl, cnt, kr, dr, cnt + 2, cap, level_sigma2, nlevels, Tlr, cam_params, cam_params2, cap,
+                                                          S.dev(hl2r), S.dev(hr2l), S.dev(hdep), dp3, S.dev(hnm), s);
   if (rs < 0) return rs;
-  const uint8_t *lo = (const uint8_t *)d[P3D] ? (const uint8_t *)d[P3D] : (const uint8_t *)d[L2R];
-  const size_t down = ((const uint8_t *)d[NM] + 2 * sizeof(int32_t)) - lo;
+  const uint8_t *lo = nL ? (const uint8_t *)S.dev(hp3) : (const uint8_t *)S.dev(hl2r);
+  const size_t down = ((const uint8_t *)S.dev(hnm) + 2 * sizeof(int32_t)) - lo;
   MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, down, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   if (nL > 0) {
-    memcpy(p3d, mirror_of(m, d[P3D]), 3 * sizeof(float) * (size_t)nL);
-    memcpy(left_to_right, mirror_of(m, d[L2R]), sizeof(int32_t) * (size_t)nL);
-    memcpy(depth, mirror_of(m, d[DEP]), sizeof(float) * (size_t)nL);
+    memcpy(p3d, S.host(hp3), 3 * sizeof(float) * NL);
+    memcpy(left_to_right, S.host(hl2r), sizeof(int32_t) * NL);
+    memcpy(depth, S.host(hdep), sizeof(float) * NL);
   }
-  if (nR > 0) memcpy(right_to_left, mirror_of(m, d[R2L]), sizeof(int32_t) * (size_t)nR);
-  if (nmatches) memcpy(nmatches, mirror_of(m, d[NM]), 2 * sizeof(int32_t));
+  if (nR > 0) memcpy(right_to_left, S.host(hr2l), sizeof(int32_t) * NR);
+  if (nmatches) memcpy(nmatches, S.host(hnm), 2 * sizeof(int32_t));
   return 0;
 }
 
@@ -2246,126 +2340,13 @@ int orbm_search_by_projection_last_frame_fisheye(orbm_t *m, const orbm_frame_t *
                                                  const orbx_keypoint_t *last_keys, const uint8_t *obs, const float *Tcw,
                                                  const float *Tlw, const float *Trl, int cam_type, const float *cam_params,
                                                  float mb, float th, int bMono, int checkOri, int32_t *slot, uint8_t *slot_obs) {
-  if (!m || !cur || !sf || nLast < 0 || !Tcw || !Tlw || !Trl || !cam_params || !slot || !slot_obs) return ORBX_E_ARG;
-  if (n_left < 0 || n_left > cur->n) return ORBX_E_ARG;
-  if (nLast > 0 && (!has_mp || !Xw || !mpdesc || !last_keys)) return ORBX_E_ARG;
-  if (nlevels < 1 || nlevels > 16) return ORBX_E_ARG;
-  const int n = cur->n;
-  if (n == 0 || nLast == 0) return 0;
-  if (!cur->keys_un || !cur->descriptors) return ORBX_E_ARG;
-  for (int i = 0; i < nLast; i++)
-    if (has_mp[i] && (last_keys[i].octave < 0 || last_keys[i].octave >= nlevels)) return ORBX_E_ARG;
-  MCHECK(m, hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  // one staged block up, one block down, one synchronisation (as orbm_search_by_projection_last_frame); the batch form's kernels, npairs = 1
-  enum { KP, DESC, HAS, XW, MD, LK, OBS, TC, TL, SLOT, SOBS, NM, NPARTS };
-  void *d[NPARTS];
-  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n}, {has_mp, (size_t)nLast},
-                              {Xw, 3 * sizeof(float) * (size_t)nLast}, {mpdesc, 32 * (size_t)nLast}, {last_keys, sizeof(orbx_keypoint_t) * (size_t)nLast},
-                              {obs, obs ? (size_t)nLast : 0}, {Tcw, 16 * sizeof(float)}, {Tlw, 16 * sizeof(float)},
-                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {nullptr, sizeof(int32_t)}}, d, true);
-  if (rc < 0) return rc;
-  orbm_frame_t df = *cur;
-  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = nullptr;
-  orbm_last_frame_t dl;
-  memset(&dl, 0, sizeof(dl));
-  dl.n = nLast;
-  dl.has_mp = (const uint8_t *)d[HAS]; dl.Xw = (const float *)d[XW]; dl.mpdesc = (const uint8_t *)d[MD];
-  dl.last_keys = (const orbx_keypoint_t *)d[LK]; dl.obs = (const uint8_t *)d[OBS]; dl.Tcw = (const float *)d[TC]; dl.Tlw = (const float *)d[TL];
-  const int scan_mode = host_scan_mode(m, cur, sf, nLast, has_mp, last_keys, th);
-  const int rs = search_last_frame_rig_batch(m, &df, n, nullptr, 0, nullptr, 0, n_left, &dl, nLast, nullptr, 0, 1, sf, nlevels, Trl, cam_type, cam_params,
-                                             mb, th, bMono, checkOri, (int32_t *)d[SLOT], (uint8_t *)d[SOBS], nullptr, (int32_t *)d[NM], s, scan_mode);
-  if (rs < 0) return rs;
-  return download_slots(m, s, d[SLOT], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  if (!cur || !Trl || n_left < 0 || n_left > cur->n) return ORBX_E_ARG;
+  const RigLastExtras rig = {Trl, {nullptr, 0, n_left}};
+  return search_last_frame_host(m, cur, sf, nlevels, nLast, has_mp, Xw, mpdesc, last_keys, obs, Tcw, Tlw, cam_type, cam_params, mb, 0.f, th, bMono,
+                                checkOri, slot, slot_obs, &rig);
 }
 
 // ---- Tracking::SearchLocalPoints for a fisheye-stereo frame (Frame.cc:650-660, :1270-1343; ORBmatcher.cc:44-214) ------------------
-static bool valid_track_rig(const orbm_track_rig_t *t) {
-  return t->in_view && t->in_view_r && t->proj_x && t->proj_y && t->depth && t->view_cos && t->proj_xr && t->proj_yr && t->depth_r &&
-         t->view_cos_r && t->level && t->level_r;
-}
-
-// The device core: k_local_map_project_rig (both frustum tests, two queries per local map point, the partner table), the search with
-// couple = 1 (ORBmatcher.cc:127), k_rig_slot_convert.  d_l2r / d_r2l: device arrays [npairs][frame_stride] or NULL.  serial: see
-// orbm_search_local_points_fisheye_batch_device.  Arguments are checked before anything is launched.
-static int search_local_rig_batch(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n, int frame_n_stride,
-                                  const int32_t *d_n_left, int n_left_stride, int n_left, const int32_t *d_l2r, const int32_t *d_r2l,
-                                  const orbm_local_map_t *map0, int map_stride, const int32_t *d_map_n, int map_n_stride, int npairs,
-                                  const float *sf, int nlevels, float log_sf, const float *Trl, const float *tlr, int cam_type,
-                                  const float *cam_params, int cam_type2, const float *cam_params2, float view_cos_limit, float th, int bFarPoints,
-                                  float th_far, float nnratio, int32_t *d_slot, uint8_t *d_slot_obs, int32_t *d_moq, const orbm_track_rig_t *track0,
-                                  int32_t *d_nmatches, hipStream_t s, bool search, int serial) {
-  if (!m || !cur0 || !map0 || !track0 || !sf || !cam_params || !cam_params2 || !Trl || !tlr || npairs < 0 || !d_slot || !d_slot_obs || !d_nmatches)
-    return ORBX_E_ARG;
-  if (nlevels < 1 || nlevels > 16 || (cam_type != 0 && cam_type != 1) || (cam_type2 != 0 && cam_type2 != 1)) return ORBX_E_ARG;
-  if (!valid_local_map(map0) || !valid_track_rig(track0)) return ORBX_E_ARG;
-  if (search && (!cur0->keys_un || !cur0->descriptors)) return ORBX_E_ARG;
-  const int maxq = d_map_n ? map_stride : map0->n;
-  const int maxn = d_frame_n ? frame_stride : cur0->n;
-  if (maxq <= 0 || map_stride < maxq || map0->n < 0 || (!d_map_n && map_stride < map0->n)) return ORBX_E_ARG;
-  if (search && (maxn <= 0 || frame_stride < maxn || (!d_frame_n && frame_stride < cur0->n))) return ORBX_E_ARG;
-  if (search && (!(cur0->max_x > cur0->min_x) || !(cur0->max_y > cur0->min_y))) return ORBX_E_ARG;
-  if (search && !d_n_left && (n_left < 0 || n_left > cur0->n)) return ORBX_E_ARG;
-  if ((long long)map_stride * 2 > 0x7fffffff / 2) return ORBX_E_ARG;
-  if (npairs == 0) return 0;
-  MCHECK(m, hipSetDevice(m->device));
-  LocalMapParams P;
-  memset(&P, 0, sizeof(P));
-  QueryScratch &Q = P.Q;
-  RigScratch S;
-  const int rq = carve_query_scratch(m, m->d_lmq, s, npairs, 2 * map_stride, Q, &S);
-  if (rq < 0) return rq;
-  const bool partners = search && (d_l2r || d_r2l);
-  const size_t pbytes = sizeof(int32_t) * (size_t)npairs * (size_t)frame_stride;
-  if (partners && pbytes > m->d_partner.bytes) {
-    MCHECK(m, hipStreamSynchronize(s));
-    MCHECK(m, m->d_partner.reserve(pbytes + (pbytes >> 2)));
-  }
-  int32_t *moq = d_moq ? d_moq : Q.moq;
-  P.eligible = map0->eligible; P.Xw = map0->Xw; P.normal = map0->normal; P.max_dist = map0->max_dist; P.min_dist = map0->min_dist;
-  P.obs = map0->obs; P.Tcw = map0->Tcw;
-  P.map_stride = map_stride; P.map_n = d_map_n; P.map_n_stride = map_n_stride; P.map_n_const = map0->n;
-  fill_view(P.V, cur0, sf, nlevels, cam_type, cam_params);
-  P.log_sf = log_sf;
-  P.mbf = 0.f; P.view_cos_limit = view_cos_limit; P.th = th; P.bFarPoints = bFarPoints ? 1 : 0; P.th_far = th_far;
-  P.in_view = track0->in_view; P.proj_x = track0->proj_x; P.proj_y = track0->proj_y; P.proj_xr = track0->proj_xr;
-  P.depth = track0->depth; P.view_cos = track0->view_cos; P.level = track0->level;
-  RigLocalParams G;
-  memset(&G, 0, sizeof(G));
-  for (int i = 0; i < 12; i++) G.Trl[i] = Trl[i];
-  for (int i = 0; i < 3; i++) G.tlr[i] = tlr[i];
-  G.cam_type2 = cam_type2;
-  for (int k = 0; k < (cam_type2 == 0 ? 4 : 8); k++) G.cam2[k] = cam_params2[k];
-  G.mpdesc = map0->mpdesc;
-  G.in_view_r = track0->in_view_r; G.proj_yr = track0->proj_yr; G.depth_r = track0->depth_r; G.view_cos_r = track0->view_cos_r;
-  G.level_r = track0->level_r;
-  G.qdesc = S.qdesc; G.qside = S.qside; G.query_n = S.query_n;
-  G.l2r = d_l2r; G.r2l = d_r2l; G.partner = partners ? (int32_t *)m->d_partner.p : nullptr;
-  G.frame_stride = frame_stride; G.frame_n = d_frame_n; G.frame_n_stride = frame_n_stride; G.frame_n_const = cur0->n;
-  G.nleft_dev = d_n_left; G.nleft_stride = n_left_stride; G.nleft_const = n_left;
-  hipLaunchKernelGGL(k_local_map_project_rig, dim3((map_stride + 255) / 256, npairs), dim3(256), 0, s, P, G);
-  if (search) {
-    const orbm_queries_t q = scratch_view(Q, 2 * map0->n, S.qdesc, false);
-    orbm_frame_t f = *cur0;
-    f.u_right = nullptr;  // Nleft != -1: no mvuRight test (ORBmatcher.cc:93)
-    SearchOpts o;
-    o.scan_mode = m->scan_mode;   // SCAN_AUTO: the windows exist only on the device, so the vote is taken there
-    o.nleft = n_left; o.nleft_dev = d_n_left; o.nleft_stride = n_left_stride;
-    o.couple = 1; o.qside = S.qside;   // ORBmatcher.cc:127
-    o.partner = G.partner; o.serial = partners ? serial : 0;
-    const int rc = search_batch(m, &f, frame_stride, d_frame_n, frame_n_stride, &q, 2 * map_stride, d_map_n ? S.query_n : nullptr, 1, npairs, nnratio,
-                                ORBM_TH_HIGH, 1, d_slot, d_slot_obs, moq, nullptr, d_nmatches, s, o);   // ORBmatcher.cc:75-141, :153-209
-    if (rc < 0) return rc;
-    RigSlotParams C;
-    memset(&C, 0, sizeof(C));
-    C.moq = moq; C.map_stride = map_stride; C.map_n = d_map_n; C.map_n_stride = map_n_stride; C.map_n_const = map0->n;
-    C.partner = G.partner; C.slot = d_slot; C.frame_stride = frame_stride;
-    hipLaunchKernelGGL(k_rig_slot_convert, dim3(npairs), dim3(256), 0, s, C);
-  }
-  MCHECK(m, hipGetLastError());
-  return 0;
-}
-
 int orbm_search_local_points_fisheye_batch_device(orbm_t *m, const orbm_frame_t *cur0, int frame_stride, const int32_t *d_frame_n,
                                                   int frame_n_stride, const int32_t *d_n_left, int n_left_stride, int n_left,
                                                   const int32_t *d_left_to_right, const int32_t *d_right_to_left, const orbm_local_map_t *map0,
@@ -2379,10 +2360,11 @@ int orbm_search_local_points_fisheye_batch_device(orbm_t *m, const orbm_frame_t 
   // obs lives on the device: whether a taking query without observations exists is not known here, so the search is serial whenever
   // one can exist and a partner table is passed (exact in either mode)
   const int serial = map0 && map0->obs ? 1 : 0;
-  return search_local_rig_batch(m, cur0, frame_stride, d_frame_n, frame_n_stride, d_n_left, n_left_stride, n_left, d_left_to_right, d_right_to_left,
-                                map0, map_stride, d_map_n, map_n_stride, npairs, sf, nlevels, log_sf, Trl, tlr, cam_type, cam_params, cam_type2,
-                                cam_params2, view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, track0, d_nmatches,
-                                (hipStream_t)stream_, true, serial);
+  const RigLocalExtras rig = {Trl, tlr, cam_type2, cam_params2, d_left_to_right, d_right_to_left, {d_n_left, n_left_stride, n_left}, serial, track0};
+  return search_local_batch(m, cur0, {frame_stride, d_frame_n, frame_n_stride, cur0 ? cur0->n : 0}, map0,
+                            {map_stride, d_map_n, map_n_stride, map0 ? map0->n : 0}, npairs, sf, nlevels, log_sf, cam_type, cam_params, 0.f,
+                            view_cos_limit, th, bFarPoints, th_far, nnratio, d_slot, d_slot_obs, d_moq, nullptr, d_nmatches, (hipStream_t)stream_, true,
+                            &rig);
 }
 
 int orbm_search_local_points_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_left, const int32_t *left_to_right, const int32_t *right_to_left,
@@ -2410,40 +2392,40 @@ int orbm_search_local_points_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_l
   hipStream_t s = m->stream;
   // one staged block up (depth is in/out: it goes up with the slots), one block down, one synchronisation; a frame without keypoints
   // still gets its track fields
-  const size_t fp = sizeof(float) * (size_t)nmp, ip = sizeof(int32_t) * (size_t)nmp;
-  enum { KP, DESC, L2R, R2L, ELIG, XW, NRM, MAXD, MIND, MD, OBS, TC, SLOT, SOBS, DEP, MOQ, INV, INVR, PX, PY, VC, PXR, PYR, DEPR, VCR, LVL, LVLR, NM, NPARTS };
-  void *d[NPARTS];
+  const size_t N = (size_t)n, NP = (size_t)nmp;
   const int32_t *l2r = anyp ? left_to_right : nullptr, *r2l = anyp ? right_to_left : nullptr;
-  const int rc = stage(m, s, {{cur->keys_un, sizeof(orbx_keypoint_t) * (size_t)n}, {cur->descriptors, 32 * (size_t)n},
-                              {l2r, l2r ? sizeof(int32_t) * (size_t)n_left : 0}, {r2l, r2l ? sizeof(int32_t) * (size_t)(n - n_left) : 0},
-                              {map->eligible, (size_t)nmp}, {map->Xw, 3 * fp}, {map->normal, 3 * fp}, {map->max_dist, fp}, {map->min_dist, fp},
-                              {map->mpdesc, 32 * (size_t)nmp}, {map->obs, map->obs ? (size_t)nmp : 0}, {map->Tcw, 16 * sizeof(float)},
-                              {slot, sizeof(int32_t) * (size_t)n}, {slot_obs, (size_t)n}, {track->depth, fp}, {nullptr, 2 * ip},
-                              {nullptr, (size_t)nmp}, {nullptr, (size_t)nmp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp}, {nullptr, fp},
-                              {nullptr, fp}, {nullptr, fp}, {nullptr, ip}, {nullptr, ip}, {nullptr, sizeof(int32_t)}}, d, true);
+  Staging S{m};
+  const StagedFrame hf = stage_frame(S, cur, false);
+  const auto hl2r = S.add(l2r, l2r ? (size_t)n_left : 0), hr2l = S.add(r2l, r2l ? (size_t)(n - n_left) : 0);
+  const StagedMap hm = stage_local_map(S, map);
+  const auto hslot = S.add(slot, N); const auto hsobs = S.add(slot_obs, N);
+  const auto hdep = S.add((const float *)track->depth, NP);
+  const auto hmoq = S.out<int32_t>(2 * NP);
+  const auto hinv = S.out<uint8_t>(NP), hinvr = S.out<uint8_t>(NP);
+  const auto hpx = S.out<float>(NP), hpy = S.out<float>(NP), hvc = S.out<float>(NP), hpxr = S.out<float>(NP), hpyr = S.out<float>(NP);
+  const auto hdepr = S.out<float>(NP), hvcr = S.out<float>(NP);
+  const auto hlvl = S.out<int32_t>(NP), hlvlr = S.out<int32_t>(NP), hnm = S.out<int32_t>(1);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
-  orbm_frame_t df = *cur;
-  df.keys_un = (const orbx_keypoint_t *)d[KP]; df.descriptors = (const uint8_t *)d[DESC]; df.u_right = nullptr;
-  orbm_local_map_t dm = *map;
-  dm.eligible = (const uint8_t *)d[ELIG]; dm.Xw = (const float *)d[XW]; dm.normal = (const float *)d[NRM]; dm.max_dist = (const float *)d[MAXD];
-  dm.min_dist = (const float *)d[MIND]; dm.mpdesc = (const uint8_t *)d[MD]; dm.obs = (const uint8_t *)d[OBS]; dm.Tcw = (const float *)d[TC];
+  const orbm_frame_t df = on_device(S, hf);
+  const orbm_local_map_t dm = on_device(S, hm);
   orbm_track_rig_t dt;
-  dt.in_view = (uint8_t *)d[INV]; dt.in_view_r = (uint8_t *)d[INVR]; dt.proj_x = (float *)d[PX]; dt.proj_y = (float *)d[PY];
-  dt.depth = (float *)d[DEP]; dt.view_cos = (float *)d[VC]; dt.proj_xr = (float *)d[PXR]; dt.proj_yr = (float *)d[PYR];
-  dt.depth_r = (float *)d[DEPR]; dt.view_cos_r = (float *)d[VCR]; dt.level = (int32_t *)d[LVL]; dt.level_r = (int32_t *)d[LVLR];
-  int32_t *dslot = n > 0 ? (int32_t *)d[SLOT] : (int32_t *)d[MOQ];   // n == 0: no search, any non-null pointer
-  uint8_t *dsobs = n > 0 ? (uint8_t *)d[SOBS] : (uint8_t *)d[INV];
-  const int rs = search_local_rig_batch(m, &df, std::max(n, 1), nullptr, 0, nullptr, 0, n_left, (const int32_t *)d[L2R], (const int32_t *)d[R2L], &dm, nmp,
-                                        nullptr, 0, 1, sf, nlevels, log_sf, Trl, tlr, cam_type, cam_params, cam_type2, cam_params2, view_cos_limit, th,
-                                        bFarPoints, th_far, nnratio, dslot, dsobs, (int32_t *)d[MOQ], &dt, (int32_t *)d[NM], s, n > 0, release ? 1 : 0);
+  dt.in_view = S.dev(hinv); dt.in_view_r = S.dev(hinvr); dt.proj_x = S.dev(hpx); dt.proj_y = S.dev(hpy);
+  dt.depth = S.dev(hdep); dt.view_cos = S.dev(hvc); dt.proj_xr = S.dev(hpxr); dt.proj_yr = S.dev(hpyr);
+  dt.depth_r = S.dev(hdepr); dt.view_cos_r = S.dev(hvcr); dt.level = S.dev(hlvl); dt.level_r = S.dev(hlvlr);
+  int32_t *dslot = n > 0 ? S.dev(hslot) : S.dev(hmoq);   // n == 0: no search, any non-null pointer
+  uint8_t *dsobs = n > 0 ? S.dev(hsobs) : S.dev(hinv);
+  // kept difference: serial only when a taking query without observations exists (the scan above); the batch form cannot know
+  const RigLocalExtras rig = {Trl, tlr, cam_type2, cam_params2, S.dev(hl2r), S.dev(hr2l), {nullptr, 0, n_left}, release ? 1 : 0, &dt};
+  const int rs = search_local_batch(m, &df, {std::max(n, 1), nullptr, 0, n}, &dm, {nmp, nullptr, 0, nmp}, 1, sf, nlevels, log_sf, cam_type, cam_params,
+                                    0.f, view_cos_limit, th, bFarPoints, th_far, nnratio, dslot, dsobs, S.dev(hmoq), nullptr, S.dev(hnm), s, n > 0, &rig);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, n > 0 ? d[SLOT] : d[DEP], d[SLOT], d[SOBS], d[NM], n, slot, slot_obs);
+  const int nm = download_slots(m, s, n > 0 ? (void *)S.dev(hslot) : (void *)S.dev(hdep), S.dev(hslot), S.dev(hsobs), S.dev(hnm), n, slot, slot_obs);
   if (nm < 0) return nm;
-  const int32_t *moq = (const int32_t *)mirror_of(m, d[MOQ]), *lvl = (const int32_t *)mirror_of(m, d[LVL]), *lvlr = (const int32_t *)mirror_of(m, d[LVLR]);
-  const uint8_t *inv = (const uint8_t *)mirror_of(m, d[INV]), *invr = (const uint8_t *)mirror_of(m, d[INVR]);
-  const float *px = (const float *)mirror_of(m, d[PX]), *py = (const float *)mirror_of(m, d[PY]), *dep = (const float *)mirror_of(m, d[DEP]);
-  const float *vc = (const float *)mirror_of(m, d[VC]), *pxr = (const float *)mirror_of(m, d[PXR]), *pyr = (const float *)mirror_of(m, d[PYR]);
-  const float *depr = (const float *)mirror_of(m, d[DEPR]), *vcr = (const float *)mirror_of(m, d[VCR]);
+  const int32_t *moq = S.host(hmoq), *lvl = S.host(hlvl), *lvlr = S.host(hlvlr);
+  const uint8_t *inv = S.host(hinv), *invr = S.host(hinvr);
+  const float *px = S.host(hpx), *py = S.host(hpy), *dep = S.host(hdep), *vc = S.host(hvc), *pxr = S.host(hpxr), *pyr = S.host(hpyr);
+  const float *depr = S.host(hdepr), *vcr = S.host(hvcr);
   // only what isInFrustum writes (Frame.cc:651-657): the flags always, the levels of eligible points, a side's fields where it is in view
   for (int i = 0; i < nmp; i++) {
     if (match_of_point) { match_of_point[2 * i] = n > 0 ? moq[2 * i] : -1; match_of_point[2 * i + 1] = n > 0 ? moq[2 * i + 1] : -1; }
@@ -2587,7 +2569,7 @@ static int fuse_core(orbm_t *m, const orbm_frame_t *kf, const float *sf, const f
   std::vector<int32_t> slot((size_t)std::max(kf->n, 1), -1);
   std::vector<uint8_t> sobs((size_t)std::max(kf->n, 1), 0);
   SearchOpts o;
-  o.nleft = kf->n;
+  o.nleft.konst = kf->n;
   o.fuse = chi2;
   if (chi2) for (int l = 0; l < nlevels && l < 16; l++) o.inv_sigma2[l] = inv_sigma2[l];
   const int rc = search_host(m, &f, &q, 0.f, ORBM_TH_LOW, 0, slot.data(), sobs.data(), best_idx, best_dist, o);
@@ -3052,7 +3034,7 @@ int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm
   std::vector<int32_t> slot((size_t)f2->n, -1);
   std::vector<uint8_t> sobs((size_t)f2->n, 0);
   SearchOpts o;
-  o.nleft = f2->n; o.init_th_low = ORBM_TH_LOW;
+  o.nleft.konst = f2->n; o.init_th_low = ORBM_TH_LOW;
   const int rc = search_host(m, &f, &q, nnratio, ORBM_TH_LOW, 1, slot.data(), sobs.data(), acc.data(), nullptr, o);
   if (rc < 0) return rc;
   // replay of the bookkeeping the device leaves to the host: steals (:781-785) and the rotation histogram (:791-801)

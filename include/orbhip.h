@@ -337,6 +337,7 @@ int orbm_search_by_projection(orbm_t *m, const orbm_frame_t *frame, const orbm_q
  * and slot/slot_obs/match_of_query/best_dist, is a device pointer to the data of problem 0; problem p is at
  * element offset p*frame_stride (keypoint-indexed arrays) resp. p*query_stride (query-indexed arrays).
  * d_frame_n[p] / d_query_n[p] give the live counts (device int32, e.g. orbx d_counts with stride 2).
+ * A device count outside [0, stride] is taken into that range, here and in every batched form below.
  * d_nmatches[p] receives the match count.  Asynchronous on stream. */
 int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *frame0, int frame_stride,
                                            const int32_t *d_frame_n, int frame_n_stride, const orbm_queries_t *q0,
