@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -198,6 +198,8 @@ def load(build_if_needed=True):
     L.orbm_triangulation_candidates.argtypes = [vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, i32]
     L.orbm_search_for_triangulation_pred.argtypes = [vp, vp, vp, f32, f32, i32, i32, i32, i32, PAIR_PRED, vp, vp]
     L.orbm_search_for_triangulation_kb8.argtypes = [vp, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, i32, i32, vp]
+    L.orbm_search_for_triangulation_neighbours.argtypes = [vp, vp, i32] + [vp] * 9 + [i32, i32, vp, vp]
+    L.orbm_search_for_triangulation_kb8_neighbours.argtypes = [vp, vp, i32, i32] + [vp] * 7 + [i32, i32, vp, vp]
     L.orbm_search_by_projection_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp]
     L.orbm_search_by_projection_keyframe.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32, i32, vp, vp]
     L.orbm_search_by_projection_last_frame.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32,
@@ -1034,6 +1036,77 @@ class ORBmatcher:
         m12 = m12[:KF1.N]
         i1 = np.nonzero(m12 >= 0)[0]
         return rc, np.stack([i1, m12[i1]], axis=1).astype(np.int64)
+
+    @staticmethod
+    def _keyframe_table(KFs):
+        """orbm_keyframe_t[K] of the views (kept alive by the caller) - (ctypes array or None, its address or None)."""
+        if not KFs:
+            return None, None
+        tab = (KeyFrameStruct * len(KFs))(*[k.struct() for k in KFs])
+        return tab, C.cast(tab, C.c_void_p)
+
+    def _neighbour_rows(self, rc, what, m12, nm, K, n1):
+        self._check(rc, what)
+        if rc < 0:
+            raise OrbError("%s rc=%d" % (what, rc))
+        assert rc == int(nm[:K].sum())
+        return m12[:K * n1].reshape(K, n1), nm[:K].copy()
+
+    def SearchForTriangulationNeighbours(self, KF1, KF2s, R1w, t1w, Cw1, cam1, R2w, t2w, cam2, skip=None, bOnlyStereo=False, bCoarse=False):
+        """SearchForTriangulation of KF1 against all K neighbours KF2s in one call (orbm_search_for_triangulation_neighbours; the loop of
+        LocalMapping::CreateNewMapPoints, LocalMapping.cc:475-583), Pinhole keyframes.  R2w [K, 3, 3], t2w [K, 3], cam2 [K, 4]; skip [K]
+        marks the neighbours the baseline tests drop.  Returns (matches12 [K, KF1.N], nmatches [K]): row j = vMatches12 of the per-pair
+        member from the state at loop entry, without the rotation check; the caller masks idx1 that received a map point since."""
+        K = len(KF2s)
+        a = lambda x, n: np.ascontiguousarray(x, dtype=np.float32).reshape(-1) if x is not None else None
+        R1w, t1w, Cw1, cam1, R2w, t2w, cam2 = a(R1w, 9), a(t1w, 3), a(Cw1, 3), a(cam1, 4), a(R2w, 9 * K), a(t2w, 3 * K), a(cam2, 4 * K)
+        for v, n in ((R1w, 9), (t1w, 3), (Cw1, 3), (cam1, 4), (R2w, 9 * K), (t2w, 3 * K), (cam2, 4 * K)):
+            if v is not None and len(v) != n:
+                raise ValueError("SearchForTriangulationNeighbours: %d floats where %d are expected" % (len(v), n))
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        if sk is not None and len(sk) != K:
+            raise ValueError("SearchForTriangulationNeighbours: skip needs one entry per neighbour")
+        s1 = KF1.struct()
+        tab, ptab = self._keyframe_table(KF2s)
+        m12, nm = np.full(max(K * KF1.N, 1), -1, dtype=np.int32), np.zeros(max(K, 1), np.int32)
+        q = lambda v: _p(v) if v is not None and len(v) else None
+        rc = self.L.orbm_search_for_triangulation_neighbours(self.m, C.byref(s1), K, ptab, q(R1w), q(t1w), q(Cw1), q(cam1), q(R2w), q(t2w), q(cam2),
+                                                             q(sk), int(bool(bOnlyStereo)), int(bool(bCoarse)), _p(m12), _p(nm))
+        return self._neighbour_rows(rc, "orbm_search_for_triangulation_neighbours", m12, nm, K, KF1.N)
+
+    def SearchForTriangulationKB8Neighbours(self, KF1, KF2s, ep, cams1, cams2, T12, n_left1=-1, n_left2=None, skip=None, bOnlyStereo=False,
+                                            bCoarse=False):
+        """The same for KannalaBrandt8 keyframes (n_left1 == -1) or two-camera KannalaBrandt8 rigs (orbm_search_for_triangulation_kb8_neighbours).
+        Per neighbour: ep [K, 2], cams2 [K, 8] or [K, 2, 8], T12 [K, 12] or [K, 4, 12], n_left2 [K] (default: all -1); cams1 [8] or [2, 8].
+        Returns (matches12 [K, KF1.N], nmatches [K])."""
+        K = len(KF2s)
+        rig = n_left1 != -1
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32) if x is not None else None
+        ep, cams1, cams2, T12 = f(ep), f(cams1), f(cams2), f(T12)
+        c1 = None
+        if cams1 is not None:
+            c1 = np.zeros(16, np.float32)
+            c1[:cams1.size] = cams1.reshape(-1)[:16]
+        c2 = t12 = None
+        if cams2 is not None and K:      # the ABI's strides are a rig's
+            c2 = np.zeros((K, 16), np.float32)
+            c2[:, :(16 if rig else 8)] = cams2.reshape(K, -1)
+        if T12 is not None and K:
+            t12 = np.zeros((K, 48), np.float32)
+            t12[:, :(48 if rig else 12)] = T12.reshape(K, -1)
+        if ep is not None:
+            ep = np.ascontiguousarray(ep.reshape(K, 2))
+        nl2 = np.full(K, -1, np.int32) if n_left2 is None else np.ascontiguousarray(n_left2, dtype=np.int32)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        if len(nl2) != K or (sk is not None and len(sk) != K):
+            raise ValueError("SearchForTriangulationKB8Neighbours: n_left2 and skip need one entry per neighbour")
+        s1 = KF1.struct()
+        tab, ptab = self._keyframe_table(KF2s)
+        m12, nm = np.full(max(K * KF1.N, 1), -1, dtype=np.int32), np.zeros(max(K, 1), np.int32)
+        q = lambda v: _p(v) if v is not None and v.size else None
+        rc = self.L.orbm_search_for_triangulation_kb8_neighbours(self.m, C.byref(s1), int(n_left1), K, ptab, q(nl2), q(ep), q(c1), q(c2), q(t12), q(sk),
+                                                                 int(bool(bOnlyStereo)), int(bool(bCoarse)), _p(m12), _p(nm))
+        return self._neighbour_rows(rc, "orbm_search_for_triangulation_kb8_neighbours", m12, nm, K, KF1.N)
 
     def hamming_matrix(self, q, c):
         q = np.ascontiguousarray(q, dtype=np.uint8)

@@ -1673,7 +1673,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(MatchProblemSet M, const ty
 // the keypoints of KF2 in the same vocabulary node.  The reference keeps a running best with `dist>bestDist -> skip`
 // and updates it only when the geometric gates pass, i.e. the result is the LAST minimum among the gated candidates
 // with dist <= TH_LOW: key = dist<<16 | (0xffff - position), wave minimum.
-struct TriItem { int32_t idx1, start2, len2; };
+struct TriItem { int32_t idx1, start2, len2, nb; };   // nb: the neighbour of a one-call search over K neighbours, 0 per pair
 struct TriParams {
   const float *kp1, *kp2;                 // keypoint AoS (7 floats each)
   const uint32_t *desc1, *desc2;
@@ -1688,11 +1688,9 @@ struct TriParams {
   int32_t *matches12;
 };
 
-__global__ __launch_bounds__(256) void k_triangulation_match(TriParams T) {
-  const int lane = threadIdx.x & 63;
-  const int it = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (it >= T.nitems) return;
-  const TriItem item = T.items[it];
+// The answer for one item: the keypoint of KF2 or -1.  P: TriParams, or the view of one neighbour (TriNbView below).
+template <class P>
+__device__ __forceinline__ int32_t tri_match_item(const P &T, const TriItem &item, int lane) {
   const int idx1 = item.idx1;
   uint32_t d1[8];
 #pragma unroll
@@ -1732,7 +1730,64 @@ __global__ __launch_bounds__(256) void k_triangulation_match(TriParams T) {
     }
   }
   best = wave_min_key(best);
-  if (lane == 0) T.matches12[idx1] = best != 0xffffffffu ? T.node_idx2[item.start2 + (0xffff - (int)(best & 0xffff))] : -1;
+  return best != 0xffffffffu ? T.node_idx2[item.start2 + (0xffff - (int)(best & 0xffff))] : -1;
+}
+
+__global__ __launch_bounds__(256) void k_triangulation_match(TriParams T) {
+  const int lane = threadIdx.x & 63;
+  const int it = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (it >= T.nitems) return;
+  const TriItem item = T.items[it];
+  const int32_t r = tri_match_item(T, item, lane);
+  if (lane == 0) T.matches12[item.idx1] = r;
+}
+
+// One keyframe against K neighbours in one launch (LocalMapping::CreateNewMapPoints' loop, LocalMapping.cc:475-583): an item is
+// (neighbour, idx1, node segment of that neighbour).  What the per-pair kernels take by value - F12, the epipole, the scale tables -
+// and where the neighbour's arrays lie in the staged block stand in a table in device memory, one TriNb per neighbour; the item and
+// with it the neighbour are wave-uniform, so the table row is read with scalar loads.
+struct TriNb {
+  uint64_t kp2, desc2, ur2, hasmp2, node_idx2;   // byte offsets of the neighbour's arrays in the staged block
+  float sf2[ORBX_MAX_LEVELS], sigma2_2[ORBX_MAX_LEVELS];
+  float F12[9];                                  // Pinhole form
+  float epx, epy;
+  int32_t n_left2;                               // KannalaBrandt8 form; -1: no second camera
+  int32_t pad_;
+};
+struct TriNbParams {
+  const uint8_t *block;                   // the staged block
+  const TriNb *nb;
+  const float *kp1; const uint32_t *desc1; const float *ur1;   // ur1 NULL: a two-camera rig
+  const TriItem *items; int nitems;
+  int n1;                                 // row stride of matches12
+  int bOnlyStereo, bCoarse;
+  int32_t *matches12;                     // [K][n1], pre-filled with -1
+};
+struct TriNbView {                        // one neighbour through the member names of TriParams
+  const float *kp1, *kp2;
+  const uint32_t *desc1, *desc2;
+  const float *ur1, *ur2;
+  const uint8_t *hasmp2;
+  const int32_t *node_idx2;
+  const float *sf2, *sigma2_2, *F12;
+  float epx, epy;
+  int bOnlyStereo, bCoarse;
+};
+
+__global__ __launch_bounds__(256) void k_triangulation_match_neighbours(TriNbParams T) {
+  const int lane = threadIdx.x & 63;
+  const int it = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (it >= T.nitems) return;
+  const TriItem item = T.items[it];
+  const TriNb &N = T.nb[item.nb];
+  TriNbView V;
+  V.kp1 = T.kp1; V.desc1 = T.desc1; V.ur1 = T.ur1;
+  V.kp2 = (const float *)(T.block + N.kp2); V.desc2 = (const uint32_t *)(T.block + N.desc2); V.ur2 = (const float *)(T.block + N.ur2);
+  V.hasmp2 = T.block + N.hasmp2; V.node_idx2 = (const int32_t *)(T.block + N.node_idx2);
+  V.sf2 = N.sf2; V.sigma2_2 = N.sigma2_2; V.F12 = N.F12;
+  V.epx = N.epx; V.epy = N.epy; V.bOnlyStereo = T.bOnlyStereo; V.bCoarse = T.bCoarse;
+  const int32_t r = tri_match_item(V, item, lane);
+  if (lane == 0) T.matches12[(size_t)item.nb * (size_t)T.n1 + (size_t)item.idx1] = r;
 }
 
 // SearchForTriangulation for keyframes whose epipolar test is NOT Pinhole's (KannalaBrandt8, two-camera rigs; ORBmatcher.cc:1096-1153
@@ -1760,8 +1815,10 @@ struct TriCandParams {
   int32_t *total;                 // running total (allocation counter)
 };
 
-// The candidate key of member j of the item's node of KF2, 0xffffffff: not a candidate
-__device__ __forceinline__ uint32_t tri_key_of(const TriCandParams &T, const TriItem &item, const uint32_t (&d1)[8], bool bStereo1, int j) {
+// The candidate key of member j of the item's node of KF2, 0xffffffff: not a candidate.  P: TriCandParams, or the view of one
+// neighbour (TriCandNbView below).
+template <class P>
+__device__ __forceinline__ uint32_t tri_key_of(const P &T, const TriItem &item, const uint32_t (&d1)[8], bool bStereo1, int j) {
   const int idx2 = T.node_idx2[item.start2 + j];
   if (T.hasmp2[idx2]) return 0xffffffffu;                               // :1083 (vbMatched2 is never set)
   const bool bStereo2 = T.ur2 && T.ur2[idx2] >= 0.f;
@@ -1779,11 +1836,9 @@ __device__ __forceinline__ uint32_t tri_key_of(const TriCandParams &T, const Tri
   return ((uint32_t)dist << 16) | (uint32_t)(0xffff - j);
 }
 
-__global__ __launch_bounds__(256) void k_triangulation_candidates(TriCandParams T) {
-  const int lane = threadIdx.x & 63;
-  const int it = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (it >= T.nitems) return;
-  const TriItem item = T.items[it];
+// The candidates of item `it`, counted, given a segment of the key list and written there
+template <class P>
+__device__ __forceinline__ void tri_candidates_of_item(const P &T, const TriItem &item, int it, int lane) {
   const int idx1 = item.idx1;
   uint32_t d1[8];
 #pragma unroll
@@ -1815,11 +1870,59 @@ __global__ __launch_bounds__(256) void k_triangulation_candidates(TriCandParams 
   }
 }
 
+__global__ __launch_bounds__(256) void k_triangulation_candidates(TriCandParams T) {
+  const int lane = threadIdx.x & 63;
+  const int it = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (it >= T.nitems) return;
+  tri_candidates_of_item(T, T.items[it], it, lane);
+}
+
+// The candidate lists of one keyframe against K neighbours, one compact key list for the whole call (TriNb / TriNbParams above)
+struct TriCandNbParams {
+  TriNbParams in;                 // matches12 unused here
+  int epipole_gate;
+  uint32_t *keys; int cap;
+  int32_t *key_item;
+  int32_t *total;
+};
+struct TriCandNbView {            // one neighbour through the member names of TriCandParams
+  const float *kp2;
+  const uint32_t *desc1, *desc2;
+  const float *ur1, *ur2;
+  const uint8_t *hasmp2;
+  const int32_t *node_idx2;
+  const float *sf2;
+  float epx, epy;
+  int epipole_gate, bOnlyStereo;
+  int32_t *item_off, *item_cnt;
+  uint32_t *keys; int cap;
+  int32_t *key_item;
+  int32_t *total;
+};
+
+__global__ __launch_bounds__(256) void k_triangulation_candidates_neighbours(TriCandNbParams T) {
+  const int lane = threadIdx.x & 63;
+  const int it = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (it >= T.in.nitems) return;
+  const TriItem item = T.in.items[it];
+  const TriNb &N = T.in.nb[item.nb];
+  const uint8_t *blk = T.in.block;
+  TriCandNbView V;
+  V.desc1 = T.in.desc1; V.ur1 = T.in.ur1;
+  V.kp2 = (const float *)(blk + N.kp2); V.desc2 = (const uint32_t *)(blk + N.desc2);
+  V.ur2 = T.in.ur1 ? (const float *)(blk + N.ur2) : nullptr;   // a rig on both sides or on neither
+  V.hasmp2 = blk + N.hasmp2; V.node_idx2 = (const int32_t *)(blk + N.node_idx2);
+  V.sf2 = N.sf2; V.epx = N.epx; V.epy = N.epy; V.epipole_gate = T.epipole_gate; V.bOnlyStereo = T.in.bOnlyStereo;
+  V.item_off = nullptr; V.item_cnt = nullptr;
+  V.keys = T.keys; V.cap = T.cap; V.key_item = T.key_item; V.total = T.total;
+  tri_candidates_of_item(V, item, it, lane);
+}
+
 // KannalaBrandt8::epipolarConstrain (KannalaBrandt8.cpp:244-247: TriangulateMatches(...) > 0.0001f) on the compact candidate list of
 // k_triangulation_candidates, one candidate per lane; the grid covers the host's bound on the list, lanes beyond the device-side total
 // leave.  The reference's answer for an item is the first entry of the order (distance ascending, node position descending) that the
 // test accepts = the minimum accepted key: atomicMin into best[item].  bCoarse accepts without the test (:1148).
-struct TriKb8Consts {             // constant per call, in device memory
+struct TriKb8Consts {             // constant per call (per neighbour of a one-call search), in device memory
   float T12[4][12], Tcw2[4][12];  // [R12 | t12] and rig_Tcw2 of it, pairs ll, lr, rl, rr (a keyframe pair without second cameras: [0])
   float cams1[2][8], cams2[2][8]; // KannalaBrandt8 parameters of mpCamera, mpCamera2 of the two keyframes
 };
@@ -1836,6 +1939,18 @@ struct TriKb8Params {
   int32_t *matches12;             // pre-filled with -1
 };
 
+// The test on the pair (idx1, idx2): camera pair and pose by (bRight1, bRight2)
+__device__ __forceinline__ bool tri_kb8_accepts(const TriKb8Consts &K, const float *kp1, const float *kp2, int idx1, int idx2, int n_left1, int n_left2,
+                                                const float *sigma2_1, const float *sigma2_2) {
+  const float *k1 = kp1 + (size_t)idx1 * 7, *k2 = kp2 + (size_t)idx2 * 7;
+  const int r1 = n_left1 >= 0 && idx1 >= n_left1, r2 = n_left2 >= 0 && idx2 >= n_left2;           // bRight1, bRight2 (:1068, :1102)
+  const int pair = 2 * r1 + r2;                                                                   // :1115-1145
+  const int oct1 = __float_as_int(k1[5]) & (ORBX_MAX_LEVELS - 1), oct2 = __float_as_int(k2[5]) & (ORBX_MAX_LEVELS - 1);
+  float p3D[3];
+  return kb8_triangulate_matches(K.cams1[r1], K.cams2[r2], k1[0], k1[1], k2[0], k2[1], K.T12[pair], K.Tcw2[pair], sigma2_1[oct1], sigma2_2[oct2], p3D) >
+         0.0001f;
+}
+
 __global__ __launch_bounds__(256) void k_triangulation_kb8_predicate(TriKb8Params T) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= min(*T.total, T.cap)) return;
@@ -1844,14 +1959,8 @@ __global__ __launch_bounds__(256) void k_triangulation_kb8_predicate(TriKb8Param
   bool ok = T.bCoarse != 0;
   if (!ok) {
     const TriItem item = T.items[it];
-    const int idx1 = item.idx1, idx2 = T.node_idx2[item.start2 + (0xffff - (int)(key & 0xffffu))];
-    const float *k1 = T.kp1 + (size_t)idx1 * 7, *k2 = T.kp2 + (size_t)idx2 * 7;
-    const int r1 = T.n_left1 >= 0 && idx1 >= T.n_left1, r2 = T.n_left2 >= 0 && idx2 >= T.n_left2;   // bRight1, bRight2 (:1068, :1102)
-    const int pair = 2 * r1 + r2;                                                                   // :1115-1145
-    const int oct1 = __float_as_int(k1[5]) & (ORBX_MAX_LEVELS - 1), oct2 = __float_as_int(k2[5]) & (ORBX_MAX_LEVELS - 1);
-    float p3D[3];
-    ok = kb8_triangulate_matches(T.consts->cams1[r1], T.consts->cams2[r2], k1[0], k1[1], k2[0], k2[1], T.consts->T12[pair], T.consts->Tcw2[pair],
-                                 T.sigma2_1[oct1], T.sigma2_2[oct2], p3D) > 0.0001f;
+    const int idx2 = T.node_idx2[item.start2 + (0xffff - (int)(key & 0xffffu))];
+    ok = tri_kb8_accepts(*T.consts, T.kp1, T.kp2, item.idx1, idx2, T.n_left1, T.n_left2, T.sigma2_1, T.sigma2_2);
   }
   if (ok) atomicMin(&T.best[it], key);
 }
@@ -1864,6 +1973,43 @@ __global__ __launch_bounds__(256) void k_triangulation_kb8_result(TriKb8Params T
   if (best == 0xffffffffu) return;
   const TriItem item = T.items[it];
   T.matches12[item.idx1] = T.node_idx2[item.start2 + (0xffff - (int)(best & 0xffffu))];
+}
+
+// The same two kernels over the one key list of all neighbours: a candidate's item names its neighbour, whose TriKb8Consts, scale
+// table and arrays the lane reads (neighbours mix inside a wavefront here, so these are vector loads).
+struct TriKb8NbParams {
+  TriNbParams in;
+  const uint32_t *keys; const int32_t *key_item; const int32_t *total; int cap;
+  const TriKb8Consts *consts;     // [K]
+  float sigma2_1[ORBX_MAX_LEVELS];
+  int n_left1;
+  uint32_t *best;                 // [nitems], pre-filled with 0xffffffff
+};
+
+__global__ __launch_bounds__(256) void k_triangulation_kb8_predicate_neighbours(TriKb8NbParams T) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= min(*T.total, T.cap)) return;
+  const uint32_t key = T.keys[c];
+  const int it = T.key_item[c];
+  bool ok = T.in.bCoarse != 0;
+  if (!ok) {
+    const TriItem item = T.in.items[it];
+    const TriNb &N = T.in.nb[item.nb];
+    const int idx2 = ((const int32_t *)(T.in.block + N.node_idx2))[item.start2 + (0xffff - (int)(key & 0xffffu))];
+    ok = tri_kb8_accepts(T.consts[item.nb], T.in.kp1, (const float *)(T.in.block + N.kp2), item.idx1, idx2, T.n_left1, N.n_left2, T.sigma2_1, N.sigma2_2);
+  }
+  if (ok) atomicMin(&T.best[it], key);
+}
+
+__global__ __launch_bounds__(256) void k_triangulation_kb8_result_neighbours(TriKb8NbParams T) {
+  const int it = blockIdx.x * 256 + threadIdx.x;
+  if (it >= T.in.nitems) return;
+  const uint32_t best = T.best[it];
+  if (best == 0xffffffffu) return;
+  const TriItem item = T.in.items[it];
+  const TriNb &N = T.in.nb[item.nb];
+  T.in.matches12[(size_t)item.nb * (size_t)T.in.n1 + (size_t)item.idx1] =
+      ((const int32_t *)(T.in.block + N.node_idx2))[item.start2 + (0xffff - (int)(best & 0xffffu))];
 }
 
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) inner loops (ORBmatcher.cc:303-438, Nleft == -1): the

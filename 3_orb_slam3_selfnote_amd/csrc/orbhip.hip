@@ -1211,6 +1211,7 @@ struct orbm_handle {
   DevBuf d_knn;       // the two nearest right rows of every left lapping row (orbm_stereo_fisheye_matches*)
   DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
+  int tri_layout = 0;       // item order of the one-call triangulation searches: 0 neighbour-major (the merge walks' order), 1 KF1-keypoint-major (ORBM_TRI_LAYOUT, measurements only)
   bool profiling = false;
   hipEvent_t ev[PROF_DEPTH][3] = {};
   int prof_head = 0;
@@ -1237,13 +1238,14 @@ static void *getenv_ptr(const char *name) { const char *e = getenv(name); return
 // downloads them through it (mirror_outputs); a large output copied straight to the caller takes no pinned memory.
 // dev[i]: device address of part i, nullptr for an empty part.
 struct Part { const void *src; size_t bytes; };
+static constexpr size_t stage_span(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // what a part takes of the block
 
 struct Parts { const Part *b, *e; const Part *begin() const { return b; } const Part *end() const { return e; } };
 static int stage(orbm_handle *m, hipStream_t s, const Part *first, size_t nparts, void **dev, bool mirror_outputs) {
   size_t total = 0, upload = 0;
   for (const Part &p : Parts{first, first + nparts}) {   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
     if (p.bytes > (SIZE_MAX >> 3) - total) { m->err = "staging: inputs too large"; return ORBX_E_HIP; }
-    total += (p.bytes + 255) & ~(size_t)255;
+    total += stage_span(p.bytes);
     if (p.src) upload = total;
   }
   const size_t mirror = mirror_outputs ? total : upload;
@@ -1258,7 +1260,7 @@ static int stage(orbm_handle *m, hipStream_t s, const Part *first, size_t nparts
   for (const Part &p : Parts{first, first + nparts}) {
     if (p.src && p.bytes) memcpy((uint8_t *)m->pin + off, p.src, p.bytes);
     *dev++ = p.bytes ? (uint8_t *)m->d_block.p + off : nullptr;
-    off += (p.bytes + 255) & ~(size_t)255;
+    off += stage_span(p.bytes);
   }
   if (upload) MCHECK(m, hipMemcpyAsync(m->d_block.p, m->pin, upload, hipMemcpyHostToDevice, s));
   return 0;
@@ -1387,6 +1389,7 @@ orbm_t *orbm_create(int device) {
   m->device = device;
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return nullptr; }
   if (const char *e = getenv("ORBM_SCAN_MODE")) { const int v = atoi(e); if (v >= SCAN_AUTO && v <= SCAN_WALK) m->scan_mode = v; }   // measurements only; see orbm_set_scan_mode
+  if (const char *e = getenv("ORBM_TRI_LAYOUT")) m->tri_layout = atoi(e) == 1;                                                                                           // measurements only; DESIGN.md 6
   if (const char *e = getenv("ORBM_HAMMING_ENGINE")) { const int v = atoi(e); if (v >= 0 && v <= 2) m->hamming_engine = v; }                                               // measurements only; see orbm_set_hamming_engine
   return m;
 }
@@ -2705,12 +2708,46 @@ void inv33(const float *S, float *D) {
   D[3] = (float)((s12 * s20 - s10 * s22) * det); D[4] = (float)((s00 * s22 - s02 * s20) * det); D[5] = (float)((s02 * s10 - s00 * s12) * det);
   D[6] = (float)((s10 * s21 - s11 * s20) * det); D[7] = (float)((s01 * s20 - s00 * s21) * det); D[8] = (float)((s00 * s11 - s01 * s10) * det);
 }
+// What SearchForTriangulation forms once per Pinhole keyframe pair: the epipole of KF1 in image 2 and F12
+void pinhole_pair_geometry(const float *R1w, const float *t1w, const float *R2w, const float *t2w, const float *Cw1, const float *cam1,
+                           const float *cam2, float *F12, float &epx, float &epy) {
+  // epipole in image 2: C2 = R2w*Cw+t2w, ep = pCamera2->project(C2), :988-994
+  float C2[3];
+  for (int i = 0; i < 3; i++) {
+    const float t0 = R2w[3 * i] * Cw1[0] + R2w[3 * i + 1] * Cw1[1] + R2w[3 * i + 2] * Cw1[2];
+    C2[i] = (float)((double)t0 + (double)t2w[i]);
+  }
+  project(0, cam2, C2[0], C2[1], C2[2], epx, epy);
+  // R12 = R1w*R2w.t(); t12 = -R1w*R2w.t()*t2w+t1w, :1008-1010
+  float R12[9], nR[9], t12[3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double acc = 0;
+      for (int k = 0; k < 3; k++) acc += (double)R1w[3 * i + k] * (double)R2w[3 * j + k];
+      R12[3 * i + j] = (float)acc;
+      nR[3 * i + j] = (float)(-acc);
+    }
+  for (int i = 0; i < 3; i++) {
+    const float t0 = nR[3 * i] * t2w[0] + nR[3 * i + 1] * t2w[1] + nR[3 * i + 2] * t2w[2];
+    t12[i] = (float)((double)t0 + (double)t1w[i]);
+  }
+  // F12 = K1.t().inv()*t12x*R12*K2.inv(), Pinhole.cpp:145-148
+  const float tx[9] = {0, -t12[2], t12[1], t12[2], 0, -t12[0], -t12[1], t12[0], 0};
+  const float K1t[9] = {cam1[0], 0.f, 0.f, 0.f, cam1[1], 0.f, cam1[2], cam1[3], 1.f};
+  const float K2[9] = {cam2[0], 0.f, cam2[2], 0.f, cam2[1], cam2[3], 0.f, 0.f, 1.f};
+  float K1ti[9], K2i[9], A[9], B[9];
+  inv33(K1t, K1ti);
+  inv33(K2, K2i);
+  mul33(K1ti, tx, A);
+  mul33(A, R12, B);
+  mul33(B, K2i, F12);
+}
 }  // namespace
 
 // merge-walk of the two feature vectors (ORBmatcher.cc:1036-1188): one work item per unmatched keypoint of KF1 in a shared node
-// ur1 = KF1's mvuRight, NULL for a two-camera rig (bStereo1 is false there, :1057)
+// ur1 = KF1's mvuRight, NULL for a two-camera rig (bStereo1 is false there, :1057).  Appends to items; nb = the neighbour they name.
 static int triangulation_items(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, const float *ur1, int bOnlyStereo,
-                               std::vector<TriItem> &items) {
+                               std::vector<TriItem> &items, int nb = 0) {
   int f1 = 0, f2 = 0;
   while (f1 < k1->n_nodes && f2 < k2->n_nodes) {
     if (k1->node_id[f1] == k2->node_id[f2]) {
@@ -2721,7 +2758,7 @@ static int triangulation_items(orbm_t *m, const orbm_keyframe_t *k1, const orbm_
         if (idx1 < 0 || idx1 >= k1->n) return ORBX_E_ARG;
         if (k1->has_mappoint[idx1]) continue;                          // :1050-1055
         if (bOnlyStereo && !(ur1 && ur1[idx1] >= 0)) continue;         // :1057-1061
-        if (l2 > 0) items.push_back(TriItem{idx1, s2, l2});
+        if (l2 > 0) items.push_back(TriItem{idx1, s2, l2, nb});
       }
       f1++; f2++;
     } else if (k1->node_id[f1] < k2->node_id[f2]) {
@@ -2856,37 +2893,7 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
   if (!k1->u_right || !k2->u_right || !k1->has_mappoint || !k2->has_mappoint) return ORBX_E_ARG;
   TriParams T;
   memset(&T, 0, sizeof(T));
-  // epipole in image 2: C2 = R2w*Cw+t2w, ep = pCamera2->project(C2), :988-994
-  float C2[3];
-  for (int i = 0; i < 3; i++) {
-    const float t0 = R2w[3 * i] * Cw1[0] + R2w[3 * i + 1] * Cw1[1] + R2w[3 * i + 2] * Cw1[2];
-    C2[i] = (float)((double)t0 + (double)t2w[i]);
-  }
-  project(0, cam2, C2[0], C2[1], C2[2], T.epx, T.epy);
-  // R12 = R1w*R2w.t(); t12 = -R1w*R2w.t()*t2w+t1w, :1008-1010
-  float R12[9], nR[9], t12[3];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double acc = 0;
-      for (int k = 0; k < 3; k++) acc += (double)R1w[3 * i + k] * (double)R2w[3 * j + k];
-      R12[3 * i + j] = (float)acc;
-      nR[3 * i + j] = (float)(-acc);
-    }
-  for (int i = 0; i < 3; i++) {
-    const float t0 = nR[3 * i] * t2w[0] + nR[3 * i + 1] * t2w[1] + nR[3 * i + 2] * t2w[2];
-    t12[i] = (float)((double)t0 + (double)t1w[i]);
-  }
-  {  // F12 = K1.t().inv()*t12x*R12*K2.inv(), Pinhole.cpp:145-148
-    const float tx[9] = {0, -t12[2], t12[1], t12[2], 0, -t12[0], -t12[1], t12[0], 0};
-    const float K1t[9] = {cam1[0], 0.f, 0.f, 0.f, cam1[1], 0.f, cam1[2], cam1[3], 1.f};
-    const float K2[9] = {cam2[0], 0.f, cam2[2], 0.f, cam2[1], cam2[3], 0.f, 0.f, 1.f};
-    float K1ti[9], K2i[9], A[9], B[9];
-    inv33(K1t, K1ti);
-    inv33(K2, K2i);
-    mul33(K1ti, tx, A);
-    mul33(A, R12, B);
-    mul33(B, K2i, T.F12);
-  }
+  pinhole_pair_geometry(R1w, t1w, R2w, t2w, Cw1, cam1, cam2, T.F12, T.epx, T.epy);
   std::vector<TriItem> items;
   { const int rc = triangulation_items(m, k1, k2, k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
   int nmatches = 0;
@@ -2920,6 +2927,26 @@ int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const or
   return nmatches;
 }
 
+// Why a keyframe (nlevels in range) cannot be read by the kernels, or NULL.  rig: u_right is not read; scales = false: neither are
+// its scale tables (KF1 under Pinhole's test).
+static const char *tri_keyframe_refusal(const orbm_keyframe_t *k, bool rig, bool scales = true) {
+  if ((scales && (!k->level_sigma2 || !k->scale_factors)) || k->n_nodes < 0) return "keyframe: NULL scale table";
+  if (k->n > 0 && (!k->keys_un || !k->descriptors || !k->has_mappoint || (!rig && !k->u_right))) return "keyframe: NULL array";
+  if (k->n_nodes > 0 && (!k->node_id || !k->node_start || !k->node_idx || k->node_start[0] < 0)) return "keyframe: NULL feature vector";
+  for (int i = 0; scales && i < k->n; i++)   // mvLevelSigma2[kp.octave], :1148
+    if (k->keys_un[i].octave < 0 || k->keys_un[i].octave >= k->nlevels) return "keypoint octave outside [0, nlevels)";
+  for (int f = 0; f < k->n_nodes; f++)
+    if (k->node_start[f + 1] < k->node_start[f]) return "feature vector: node_start decreases";
+  return nullptr;
+}
+// The members of KF2's nodes are keypoints of KF2 (n_nodes > 0)
+static const char *tri_members_refusal(const orbm_keyframe_t *k2) {
+  const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
+  for (size_t i = 0; i < nidx2; i++)
+    if (k2->node_idx[i] < 0 || k2->node_idx[i] >= k2->n) return "feature vector: keypoint index out of range";
+  return nullptr;
+}
+
 // SearchForTriangulation with KannalaBrandt8's epipolarConstrain on the device (ORBmatcher.cc:981-1222, KannalaBrandt8.cpp:244-247):
 // candidates -> predicate on every candidate -> minimum accepted key per item -> vMatches12, one upload and one download.
 int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, const orbm_keyframe_t *k2, int n_left2, float ep_x, float ep_y,
@@ -2931,20 +2958,12 @@ int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int 
   if ((n_left1 == -1) != (n_left2 == -1)) return refuse("n_left: one keyframe with and one without a second camera");
   if (k1->n < 0 || k2->n < 0 || n_left1 < -1 || n_left1 > k1->n || n_left2 < -1 || n_left2 > k2->n) return refuse("n or n_left out of range");
   if (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return refuse("nlevels out of range");
-  for (const orbm_keyframe_t *k : {k1, k2}) {
-    if (!k->level_sigma2 || !k->scale_factors || k->n_nodes < 0) return refuse("keyframe: NULL scale table");
-    if (k->n > 0 && (!k->keys_un || !k->descriptors || !k->has_mappoint || (!rig && !k->u_right))) return refuse("keyframe: NULL array");
-    if (k->n_nodes > 0 && (!k->node_id || !k->node_start || !k->node_idx || k->node_start[0] < 0)) return refuse("keyframe: NULL feature vector");
-    for (int i = 0; i < k->n; i++)   // mvLevelSigma2[kp.octave], :1148
-      if (k->keys_un[i].octave < 0 || k->keys_un[i].octave >= k->nlevels) return refuse("keypoint octave outside [0, nlevels)");
-    for (int f = 0; f < k->n_nodes; f++)
-      if (k->node_start[f + 1] < k->node_start[f]) return refuse("feature vector: node_start decreases");
-  }
+  for (const orbm_keyframe_t *k : {k1, k2})
+    if (const char *why = tri_keyframe_refusal(k, rig)) return refuse(why);
   for (int i = 0; i < k1->n; i++) matches12[i] = -1;
   if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
   const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
-  for (size_t i = 0; i < nidx2; i++)
-    if (k2->node_idx[i] < 0 || k2->node_idx[i] >= k2->n) return refuse("feature vector: keypoint index out of range");
+  if (const char *why = tri_members_refusal(k2)) return refuse(why);
   std::vector<TriItem> items;
   { const int rc = triangulation_items(m, k1, k2, rig ? nullptr : k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
   int nmatches = 0;
@@ -3004,6 +3023,184 @@ int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int 
   }
   if (checkOri && nmatches > 0) nmatches = prune_pairs_by_rotation(k1, k2, matches12, nmatches);
   return nmatches;
+}
+
+// ---- SearchForTriangulation of one keyframe against K neighbours in one call (LocalMapping.cc:475-583) ----------------------------
+// What the two entries share once every neighbour that is not skipped has been validated: the merge walks, ONE staged block (KF1 once,
+// the arrays of every neighbour that has work, the items, the neighbour table), one fill, the kernels over all neighbours, one
+// download of [K][n1], one synchronisation.  nb[j] arrives with F12 / epipole / n_left2; kb8 == NULL selects Pinhole's test.
+static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const uint8_t *skip,
+                                    std::vector<TriNb> &nb, const std::vector<TriKb8Consts> *kb8, int bOnlyStereo, int bCoarse,
+                                    int32_t *matches12, int32_t *nmatches) {
+  const bool rig = n_left1 != -1;
+  const size_t n1 = (size_t)k1->n;
+  for (size_t i = 0; i < (size_t)K * n1; i++) matches12[i] = -1;
+  for (int j = 0; j < K; j++) nmatches[j] = 0;
+  std::vector<TriItem> items;
+  std::vector<uint8_t> live((size_t)K, 0);
+  for (int j = 0; j < K; j++) {
+    if ((skip && skip[j]) || n1 == 0 || k2[j].n == 0 || k1->n_nodes == 0 || k2[j].n_nodes == 0) continue;
+    const size_t before = items.size();
+    m->err.clear();
+    const int rc = triangulation_items(m, k1, &k2[j], rig ? nullptr : k1->u_right, bOnlyStereo, items, j);
+    if (rc < 0) { m->err = "neighbour " + std::to_string(j) + ": " + (m->err.empty() ? std::string("kf1: keypoint index out of range") : m->err); return rc; }
+    live[(size_t)j] = items.size() > before;
+  }
+  if (items.empty()) return 0;
+  const size_t ni = items.size();
+  size_t cap = 0;   // every member of an item's node can be a candidate: the key list never outgrows this
+  for (const TriItem &it : items) cap += (size_t)it.len2;
+  if (cap > 0x7fffffffu || ni > 0x7fffffffu) { m->err = "more than 2^31 - 1 keypoint pairs in shared vocabulary nodes over all neighbours"; return ORBX_E_ARG; }
+  if (m->tri_layout == 1 && K > 1) {   // KF1-keypoint-major: one idx1 against consecutive neighbours (a stable counting sort on idx1); measured slower, DESIGN.md 6
+    std::vector<size_t> at(n1 + 1, 0);
+    for (const TriItem &it : items) at[(size_t)it.idx1 + 1]++;
+    for (size_t i = 0; i < n1; i++) at[i + 1] += at[i];
+    std::vector<TriItem> byKey(ni);
+    for (const TriItem &it : items) byKey[at[(size_t)it.idx1]++] = it;
+    items.swap(byKey);
+  }
+  static const int32_t zero = 0;
+  std::vector<Part> parts;
+  std::vector<size_t> offs;
+  parts.reserve(16 + 5 * (size_t)K);
+  size_t off = 0;
+  auto add = [&](const void *src, size_t bytes) { parts.push_back(Part{src, bytes}); offs.push_back(off); off += stage_span(bytes); return parts.size() - 1; };
+  const size_t KP1 = add(k1->keys_un, sizeof(orbx_keypoint_t) * n1), DESC1 = add(k1->descriptors, 32 * n1);
+  const size_t UR1 = add(rig ? nullptr : k1->u_right, rig ? 0 : sizeof(float) * n1);
+  for (int j = 0; j < K; j++) {
+    if (!live[(size_t)j]) continue;
+    const orbm_keyframe_t &k = k2[j];
+    const size_t n2 = (size_t)k.n;
+    TriNb &N = nb[(size_t)j];
+    N.desc2 = offs[add(k.descriptors, 32 * n2)];
+    N.kp2 = offs[add(k.keys_un, sizeof(orbx_keypoint_t) * n2)];
+    N.ur2 = offs[add(rig ? nullptr : k.u_right, rig ? 0 : sizeof(float) * n2)];
+    N.hasmp2 = offs[add(k.has_mappoint, n2)];
+    N.node_idx2 = offs[add(k.node_idx, sizeof(int32_t) * (size_t)k.node_start[k.n_nodes])];
+    for (int l = 0; l < k.nlevels; l++) { N.sf2[l] = k.scale_factors[l]; N.sigma2_2[l] = k.level_sigma2[l]; }
+  }
+  const size_t ITEMS = add(items.data(), sizeof(TriItem) * ni), NB = add(nb.data(), sizeof(TriNb) * (size_t)K);
+  const size_t CONSTS = add(kb8 ? kb8->data() : nullptr, kb8 ? sizeof(TriKb8Consts) * (size_t)K : 0);
+  const size_t TOTAL = add(kb8 ? &zero : nullptr, kb8 ? sizeof(int32_t) : 0);   // the candidate total starts at the uploaded 0
+  const size_t out_bytes = sizeof(int32_t) * (size_t)K * n1;
+  const size_t MATCHES12 = add(nullptr, out_bytes), BEST = add(nullptr, kb8 ? sizeof(uint32_t) * ni : 0);
+  const size_t KEYS = add(nullptr, kb8 ? sizeof(uint32_t) * cap : 0), KEY_ITEM = add(nullptr, kb8 ? sizeof(int32_t) * cap : 0);
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  std::vector<void *> d(parts.size());
+  { const int rs = stage(m, s, parts.data(), parts.size(), d.data(), false); if (rs < 0) return rs; }
+  const uint8_t *block = (const uint8_t *)m->d_block.p;
+  for (size_t i = 0; i < parts.size(); i++)   // the table's offsets were formed here, stage() formed the addresses: they must agree
+    if (d[i] && d[i] != block + offs[i]) { m->err = "triangulation neighbours: staging layout"; return ORBX_E_HIP; }
+  // matches12 = -1 and best = 0xffffffff in one fill (adjacent parts of the block)
+  MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, kb8 ? offs[BEST] + sizeof(uint32_t) * ni - offs[MATCHES12] : out_bytes, s));
+  TriNbParams T;
+  memset(&T, 0, sizeof(T));
+  T.block = block; T.nb = (const TriNb *)d[NB];
+  T.kp1 = (const float *)d[KP1]; T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
+  T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)ni; T.n1 = k1->n;
+  T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
+  T.matches12 = (int32_t *)d[MATCHES12];
+  if (!kb8) {
+    hipLaunchKernelGGL(k_triangulation_match_neighbours, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, T);
+    MCHECK(m, hipGetLastError());
+  } else {
+    TriCandNbParams C;
+    memset(&C, 0, sizeof(C));
+    C.in = T; C.epipole_gate = rig ? 0 : 1;   // !pKF1->mpCamera2, :1105
+    C.keys = (uint32_t *)d[KEYS]; C.cap = (int)cap; C.key_item = (int32_t *)d[KEY_ITEM]; C.total = (int32_t *)d[TOTAL];
+    TriKb8NbParams P;
+    memset(&P, 0, sizeof(P));
+    P.in = T; P.keys = C.keys; P.key_item = C.key_item; P.total = C.total; P.cap = C.cap;
+    P.consts = (const TriKb8Consts *)d[CONSTS];
+    for (int l = 0; l < k1->nlevels; l++) P.sigma2_1[l] = k1->level_sigma2[l];
+    P.n_left1 = n_left1; P.best = (uint32_t *)d[BEST];
+    hipLaunchKernelGGL(k_triangulation_candidates_neighbours, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, C);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_triangulation_kb8_predicate_neighbours, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_triangulation_kb8_result_neighbours, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+  }
+  MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  long long sum = 0;
+  for (int j = 0; j < K; j++) {
+    for (size_t i = 0; i < n1; i++) nmatches[j] += matches12[(size_t)j * n1 + i] >= 0;
+    sum += nmatches[j];
+  }
+  return (int)std::min<long long>(sum, 0x7fffffff);
+}
+
+// The refusals of a one-call search that do not depend on the epipolar test: the tables, then every neighbour that is not skipped
+// as the per-pair entry would refuse it, m->err naming the neighbour.  1: nothing to search (K == 0, every neighbour skipped).
+static int triangulation_neighbours_refusal(orbm_t *m, const orbm_keyframe_t *k1, bool rig, bool kb8, int K, const orbm_keyframe_t *k2,
+                                            const uint8_t *skip) {
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (K < 0) return refuse(-1, "K < 0");
+  if (K > 0 && !k2) return refuse(-1, "NULL neighbour table");
+  if (k1->n < 0) return refuse(-1, "kf1: n < 0");
+  if (kb8 && (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS)) return refuse(-1, "kf1: nlevels out of range");
+  int searched = 0;
+  for (int j = 0; j < K; j++) searched += !(skip && skip[j]);
+  if (searched == 0) return 1;
+  if (const char *why = tri_keyframe_refusal(k1, rig, kb8)) return refuse(-1, why);
+  for (int j = 0; j < K; j++) {
+    if (skip && skip[j]) continue;
+    const orbm_keyframe_t &k = k2[j];
+    if (k.n < 0) return refuse(j, "n < 0");
+    if (k.nlevels < 1 || k.nlevels > ORBX_MAX_LEVELS) return refuse(j, "nlevels out of range");
+    if (const char *why = tri_keyframe_refusal(&k, rig)) return refuse(j, why);
+    if (k.n_nodes > 0)
+      if (const char *why = tri_members_refusal(&k)) return refuse(j, why);
+  }
+  return 0;
+}
+
+int orbm_search_for_triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int K, const orbm_keyframe_t *k2, const float *R1w, const float *t1w,
+                                             const float *Cw1, const float *cam1, const float *R2w, const float *t2w, const float *cam2,
+                                             const uint8_t *skip, int bOnlyStereo, int bCoarse, int32_t *matches12, int32_t *nmatches) {
+  if (!m || !k1) return ORBX_E_ARG;
+  const int rr = triangulation_neighbours_refusal(m, k1, false, false, K, k2, skip);
+  if (rr < 0) return rr;
+  if (K > 0 && (!matches12 || !nmatches)) { m->err = "NULL result table"; return ORBX_E_ARG; }
+  if (rr == 0 && (!R1w || !t1w || !Cw1 || !cam1 || !R2w || !t2w || !cam2)) { m->err = "NULL pose or camera table"; return ORBX_E_ARG; }
+  std::vector<TriNb> nb((size_t)K);
+  if (K > 0) memset(nb.data(), 0, sizeof(TriNb) * (size_t)K);
+  for (int j = 0; j < K && rr == 0; j++)
+    if (!(skip && skip[j])) pinhole_pair_geometry(R1w, t1w, R2w + 9 * j, t2w + 3 * j, Cw1, cam1, cam2 + 4 * j, nb[(size_t)j].F12, nb[(size_t)j].epx, nb[(size_t)j].epy);
+  return triangulation_neighbours(m, k1, -1, K, k2, skip, nb, nullptr, bOnlyStereo, bCoarse, matches12, nmatches);
+}
+
+int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const int32_t *n_left2,
+                                                 const float *ep, const float *cams1, const float *cams2, const float *T12, const uint8_t *skip,
+                                                 int bOnlyStereo, int bCoarse, int32_t *matches12, int32_t *nmatches) {
+  if (!m || !k1) return ORBX_E_ARG;
+  const bool rig = n_left1 != -1;
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
+  const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
+  if (rr < 0) return rr;
+  if (K > 0 && (!matches12 || !nmatches)) return refuse(-1, "NULL result table");
+  if (rr == 0 && (!n_left2 || !ep || !cams1 || !cams2 || !T12)) return refuse(-1, "NULL n_left2, epipole, camera or pose table");
+  std::vector<TriNb> nb((size_t)K);
+  std::vector<TriKb8Consts> consts((size_t)K);
+  if (K > 0) { memset(nb.data(), 0, sizeof(TriNb) * (size_t)K); memset(consts.data(), 0, sizeof(TriKb8Consts) * (size_t)K); }
+  for (int j = 0; j < K && rr == 0; j++) {
+    if (skip && skip[j]) continue;
+    if ((n_left2[j] == -1) != !rig) return refuse(j, "n_left: one keyframe with and one without a second camera");
+    if (n_left2[j] < -1 || n_left2[j] > k2[j].n) return refuse(j, "n_left out of range");
+    TriNb &N = nb[(size_t)j];
+    N.epx = ep[2 * j]; N.epy = ep[2 * j + 1]; N.n_left2 = n_left2[j];
+    TriKb8Consts &C = consts[(size_t)j];
+    for (int p = 0; p < (rig ? 4 : 1); p++) {
+      memcpy(C.T12[p], T12 + 48 * (size_t)j + 12 * p, sizeof(C.T12[p]));
+      rig_Tcw2(C.T12[p], C.Tcw2[p]);
+    }
+    memcpy(C.cams1, cams1, sizeof(float) * (rig ? 16 : 8));
+    memcpy(C.cams2, cams2 + 16 * (size_t)j, sizeof(float) * (rig ? 16 : 8));
+  }
+  return triangulation_neighbours(m, k1, n_left1, K, k2, skip, nb, &consts, bOnlyStereo, bCoarse, matches12, nmatches);
 }
 
 int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm_frame_t *f2, float *prev_matched, int window_size,

@@ -788,6 +788,49 @@ int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *kf1, int
                                       float ep_x, float ep_y, const float *cams1, const float *cams2, const float *T12,
                                       int bOnlyStereo, int bCoarse, int checkOri, int32_t *matches12);
 
+/* SearchForTriangulation of ONE keyframe against ALL its neighbours in one call: the loop of LocalMapping::CreateNewMapPoints
+ * (LocalMapping.cc:475-583; Tracking::CreateNewMapPoints, Tracking.cc:4288, in localisation mode), which calls the member once per
+ * neighbour of the new keyframe.  kf1 is staged once, the neighbours' arrays go up in the same block, the kernels' grid covers every
+ * (neighbour, keypoint of kf1, shared node) at once: one upload, one fill, one download of [K][kf1->n], one synchronisation per call.
+ *
+ * Row j of matches12 [K][kf1->n] is bit for bit what the per-pair entry above returns for (kf1, kf2[j]) with checkOri = 0, and
+ * nmatches[j] its return value.  skip[j] != 0 (skip may be NULL) stands for the `continue`s of the baseline tests in front of the
+ * search (LocalMapping.cc:544-560): row j is all -1, nmatches[j] = 0, and neighbour j is neither validated nor uploaded.
+ * Returns the sum of nmatches (K == 0 or every neighbour skipped: 0, without touching the device), ORBX_E_HIP or ORBX_E_ARG.
+ *
+ * Why the searches may leave the reference's loop although its body changes kf1 between them - the MASKING RULE:
+ *   - the loop body gives keypoints of kf1 a map point, mpCurrentKeyFrame->AddMapPoint(pMP, idx1) (LocalMapping.cc:892), and the
+ *     member reads exactly that, pKF1->GetMapPoint(idx1), once per idx1 (ORBmatcher.cc:1049-1055);
+ *   - vbMatched2 is declared and never set (ORBmatcher.cc:1027, :1083), so the searches of different idx1 do not see one another;
+ *   - neighbour j's own map points change only in iteration j (LocalMapping.cc:893), after its search;
+ *   - both call sites construct the matcher with checkOri = false (LocalMapping.cc:500, Tracking.cc:4236): no rotation histogram
+ *     couples the keypoints.  That is why there is no checkOri argument here: with it the rule below would not hold.
+ * Hence the sequential result for neighbour j = row j computed from the state at loop entry, with matches12[j][idx1] set to -1 for
+ * every idx1 that received a map point in the iterations before j.  The caller applies the mask while it walks the rows:
+ * `if (mpCurrentKeyFrame->GetMapPoint(idx1)) continue;` in front of each pair (tests/test_gpu_triangulation_neighbours.py replays
+ * the sequential loop against this rule).
+ *
+ * Pinhole form: R1w / t1w / Cw1 / cam1 of kf1 as in orbm_search_for_triangulation; R2w [K][9], t2w [K][3], cam2 [K][4] per neighbour.
+ * KannalaBrandt8 form: n_left1 and cams1 ([1][8] or [2][8]) of kf1; per neighbour n_left2 [K], ep [K][2], cams2 [K][2][8] and
+ * T12 [K][4][12] - the strides are those of a rig also for keyframes without a second camera, which use [j][0] only.
+ * ORBX_E_ARG, with orbm_last_error naming the neighbour ("neighbour <j>: ..."), for:
+ *   - whatever the per-pair entry refuses, per neighbour that is not skipped (KannalaBrandt8 form: a rig paired with a single-camera
+ *     keyframe included); both forms check every neighbour as orbm_search_for_triangulation_kb8 does - NULL arrays, nlevels, octaves
+ *     outside [0, nlevels), node_start decreasing, node members outside [0, n), a node of more than 65535 members - because the
+ *     kernels read the scale tables from device memory;
+ *   - K < 0, a NULL table with K > 0 (a table only the searched neighbours need may be NULL when all are skipped);
+ *   - more than 2^31 - 1 keypoint pairs in shared nodes, summed over the neighbours. */
+int orbm_search_for_triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *kf1, int K, const orbm_keyframe_t *kf2 /*[K]*/,
+                                             const float *R1w, const float *t1w, const float *Cw1, const float *cam1,
+                                             const float *R2w /*[K][9]*/, const float *t2w /*[K][3]*/, const float *cam2 /*[K][4]*/,
+                                             const uint8_t *skip /*[K] or NULL*/, int bOnlyStereo, int bCoarse,
+                                             int32_t *matches12 /*[K][kf1->n]*/, int32_t *nmatches /*[K]*/);
+int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_t *kf1, int n_left1, int K,
+                                                 const orbm_keyframe_t *kf2 /*[K]*/, const int32_t *n_left2 /*[K]*/,
+                                                 const float *ep /*[K][2]*/, const float *cams1, const float *cams2 /*[K][2][8]*/,
+                                                 const float *T12 /*[K][4][12]*/, const uint8_t *skip, int bOnlyStereo, int bCoarse,
+                                                 int32_t *matches12, int32_t *nmatches);
+
 /* int ORBmatcher::SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched,
  *                                         vector<int> &vnMatches12, int windowSize)              (ORBmatcher.cc:722-837)
  * f1 / f2: mvKeysUn + mDescriptors of the two frames (f2 with its image bounds; u_right unused); prev_matched[2*n1]
