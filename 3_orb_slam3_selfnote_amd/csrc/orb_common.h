@@ -17,6 +17,18 @@
 #define FAST_TILE_ROWS 76      // tallest group window: two cells of up to 35 rows + 6 (a single cell: up to 59 + 6)
 #define FAST_S_PITCH 64  // score plane incl. 1-px zero ring: <= 61 columns
 
+// k_fast's group records (orbx_configure): one per group of up to 2 x 2 neighbouring cells, everything the workgroup needs about
+// the group and its cells, so that a group costs one round trip of scalar loads.  128 bytes, aligned to 128.
+//   group part, words 0-7:  tileX | tileY << 16;  tile width | height << 8 | level << 16 | (any valid cell) << 24;  cells in the group;
+//                           level pitch;  level plane offset, low and high word (level 0: the caller's image, kernel arguments);
+//                           slots per cell;  0
+//   cell w, words 8+4w ..:  iniX | iniY << 16;  window width | height << 8 | (inside the detection rectangle) << 24;
+//                           first slot of the cell in a frame's slot array;  cell index in a frame's cell table
+// (cj * wCell, ci * hCell of the packed output coordinates are iniX, iniY - ORB_MIN_BORDER.)  Cells the group does not have: zeros.
+#define FAST_REC_WORDS 32
+#define FAST_REC_GROUP_WORDS 8
+#define FAST_REC_CELL_WORDS 4
+
 // k_describe: keypoint slots per wavefront in batch calls (few-frame calls: 1), and the workgroups (four wavefronts) a frame's totalKp
 // slots then take; at least one, which writes the frame's totals.  4, 8 or 16: 8 measured best (open item 6).
 #ifndef ORB_DESCRIBE_K
@@ -99,14 +111,13 @@ struct FrameParams {
   int32_t *candCnt;                 // [frame][nlevels] dense candidate count
   const int2 *xtab, *ytab;          // resize tables {src index, a0 | a1<<16}
   const int8_t *disc;               // ORB_DISC_PIXELS x (u, v)
-  const uint32_t *cells;            // FAST cell records, 8 words each (orbx_configure), same for every frame
   const uint32_t *tiles;            // blur tile records, 8 words each: x0|y0<<16, level, w|h<<16, pitch|bpitch<<16, off, boff
   uint32_t magicCells, magicTiles, magicKpBlk;  // floor(2^32 / items per frame) of k_fast, k_blur, k_describe (xcd_map)
   int totalTiles;                   // blur tiles per frame
   int totalCells;                   // FAST cells per frame
   int totalGroups;                  // k_fast workgroups per frame: groups of up to 2 x 2 neighbouring cells
   uint32_t magicGroups;             // floor(2^32 / totalGroups), xcd_map
-  const uint32_t *groups;           // 4 words per group: first cell | gx, gy, cell-row stride | tile origin | tile size, level, valid
+  const uint32_t *fastRecs;         // k_fast's group records, FAST_REC_WORDS each (above), same for every frame; written by the host only
   int totalKp;                      // sum of kpCap
   int octCap;                       // node capacity of the octree kernel
   const ChainTile *chain;           // k_pyramid_chain's tile records

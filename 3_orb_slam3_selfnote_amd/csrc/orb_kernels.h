@@ -493,21 +493,29 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   // the right-hand neighbour's columns, so one staged tile - one HBM round trip, one set of address arithmetic - serves four
   // cells.  Wavefront w then detects cell w of the group on its own, with no workgroup barrier after the tile has landed: the
   // reference decides iniThFAST / minThFAST per cell (ORBextractor.cc:820-828), and a cell that needs the second detection
-  // holds up no other.  Group records come from orbx_configure.
+  // holds up no other.
   int groupId, frame;
   xcd_map(P.totalGroups, P.magicGroups, P.nframes, frame, groupId);
-  const uint4 gr = reinterpret_cast<const uint4 *>(P.groups)[groupId];
-  const int firstCell = (int)gr.x, gx = (int)(gr.y & 0xffu), gy = (int)((gr.y >> 8) & 0xffu), gStride = (int)(gr.y >> 16);
-  const int tileX = (int)(gr.z & 0xffffu), tileY = (int)(gr.z >> 16);
-  const int gtw = (int)(gr.w & 0xffu), gth = (int)((gr.w >> 8) & 0xffu), level = (int)((gr.w >> 16) & 0xffu);
-  const bool gvalid = (gr.w >> 24) != 0u;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; tells the compiler so (scalar control flow)
+  // The group's record (orbx_configure, layout in orb_common.h): the group part and this wavefront's cell part, two scalar loads
+  // that depend on the kernel arguments alone and are in flight together, in front of the tile's DMA.  The table is written by
+  // the host only, never by a kernel: read through the constant address space the loads stay scalar loads wherever their
+  // values are used, and nothing is fetched behind the barrier, where no other memory traffic would hide the round trip.
+  typedef uint32_t rec8_t __attribute__((ext_vector_type(8)));
+  typedef uint32_t rec4_t __attribute__((ext_vector_type(4)));
+  const __attribute__((address_space(4))) uint32_t *rec =
+      (const __attribute__((address_space(4))) uint32_t *)P.fastRecs + (size_t)groupId * FAST_REC_WORDS;
+  const rec8_t gr = *reinterpret_cast<const __attribute__((address_space(4))) rec8_t *>(rec);
+  const rec4_t cr = *reinterpret_cast<const __attribute__((address_space(4))) rec4_t *>(rec + FAST_REC_GROUP_WORDS + FAST_REC_CELL_WORDS * wave);
+  const int tileX = (int)(gr[0] & 0xffffu), tileY = (int)(gr[0] >> 16);
+  const int gtw = (int)(gr[1] & 0xffu), gth = (int)((gr[1] >> 8) & 0xffu), level = (int)((gr[1] >> 16) & 0xffu);
+  const bool gvalid = (gr[1] >> 24) != 0u;
   const int ax = tileX & ~3;                          // tile column 0 = image column ax, tile row 0 = image row tileY
   if (gvalid) {
-    const uint4 r1f = reinterpret_cast<const uint4 *>(P.cells)[2 * firstCell + 1];
     int pitch;
     const uint8_t *img;
-    if (level == 0) { pitch = (int)P.img0_stride; img = P.img0 + (size_t)frame * P.img0_frame_stride; }
-    else { pitch = (int)r1f.y; img = P.pyr + (size_t)frame * P.pyr_fs + (((size_t)r1f.w << 32) | r1f.z); }
+    if (level == 0) { pitch = (int)P.img0_stride; img = P.img0 + (size_t)frame * P.img0_frame_stride; }   // the caller's image: not in the record
+    else { pitch = (int)gr[3]; img = P.pyr + (size_t)frame * P.pyr_fs + (((size_t)gr[5] << 32) | gr[4]); }
     // ---- tile -> LDS.  Aligned path: the columns [tileX & ~3, ...) of the group's rows.
     const bool aligned = ((((uintptr_t)img) | (uintptr_t)pitch) & 3u) == 0;
     if (aligned) {
@@ -532,23 +540,20 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
       }
     }
   }
+  FSTAMP(3);
   // Score 0 everywhere, while the LDS-DMA is in flight: a pixel the pre-test never passes keeps it.  S does not depend on the
   // threshold and the minThFAST survivors include the iniThFAST ones, so a second detection rewrites the same values.
   for (int i = tid; i < FAST_TILE_ROWS * FAST_TILE_PITCH / 16; i += FAST_NT) reinterpret_cast<uint4 *>(sS)[i] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();   // the only workgroup barrier: the tile has landed (its fence waits for the LDS-DMA), the plane is clear
   FSTAMP(0);
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; tells the compiler so (scalar control flow)
-  if (wave >= gx * gy) return;                                  // groups at the right / bottom edge of a level: fewer cells
-  const int cellId = firstCell + (gx == 2 ? (wave >> 1) * gStride + (wave & 1) : wave * gStride);
-  // cell record (orbx_configure, ORBextractor.cc:787-803): one 32-byte scalar load instead of a level search plus
-  // a dozen dependent geometry loads
-  const uint4 r0 = reinterpret_cast<const uint4 *>(P.cells)[2 * cellId], r1 = reinterpret_cast<const uint4 *>(P.cells)[2 * cellId + 1];
-  const int iniX = (int)(r0.x & 0xffffu), iniY = (int)(r0.x >> 16);
-  const int tw = (int)(r0.y & 0xffu), th = (int)((r0.y >> 8) & 0xffu), cw = tw - 6, ch = th - 6;
-  const uint32_t baseX = r0.z & 0xffffu, baseY = r0.z >> 16;  // cj * wCell, ci * hCell
-  const uint32_t cellCap = r1.x;
-  uint32_t *cellCnt = P.cellCnt + (size_t)frame * P.cell_fs + cellId;
-  if (!(r0.y >> 24)) {  // cell outside the detection rectangle
+  if (wave >= (int)gr[2]) return;                               // groups at the right / bottom edge of a level: fewer cells
+  // this wavefront's cell (ORBextractor.cc:787-803), from the record: registers, no load
+  const int iniX = (int)(cr[0] & 0xffffu), iniY = (int)(cr[0] >> 16);
+  const int tw = (int)(cr[1] & 0xffu), th = (int)((cr[1] >> 8) & 0xffu), cw = tw - 6, ch = th - 6;
+  const uint32_t baseX = (uint32_t)(iniX - ORB_MIN_BORDER), baseY = (uint32_t)(iniY - ORB_MIN_BORDER);  // cj * wCell, ci * hCell
+  const uint32_t cellCap = gr[6];
+  uint32_t *cellCnt = P.cellCnt + (size_t)frame * P.cell_fs + cr[3];
+  if (!(cr[1] >> 24)) {  // cell outside the detection rectangle
     if (lane == 0) *cellCnt = 0;
     return;
   }
@@ -572,9 +577,13 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
   uint16_t *q = sQ + wave * FAST_QUEUE;
   uint16_t *list = sL + wave * FAST_LIST;
   const int base00 = (iniY - tileY + 3) * FAST_TILE_PITCH + (iniX - ax) + 3;   // tile offset of the interior's first pixel
-  uint32_t *slots = P.slots + (size_t)frame * P.slot_fs + r0.w;
+  uint32_t *slots = P.slots + (size_t)frame * P.slot_fs + cr[2];
   int nkept = 0;
   int t = P.iniTh;
+#ifdef FAST_STAMPS
+  asm volatile("" ::"v"(off0), "v"(yr0), "v"(yx0), "s"(cellCap), "v"(slots), "v"(cellCnt));   // section 4 ends once all the cell's values are there
+#endif
+  FSTAMP(4);
   for (int detection = 0;; detection++) {
     // ---- passes 1 + 2: compass pre-test at t; survivors join the wavefront's queue as tile offsets, and every time the queue
     // holds a full wavefront's worth, 64 of them get the 16-pixel score (a second detection recomputes the first one's

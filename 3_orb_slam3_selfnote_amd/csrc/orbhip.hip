@@ -90,7 +90,7 @@ struct orbx_handle {
   int cell_fs = 0, cand_fs = 0, lkp_fs = 0, totalTiles = 0, totalCells = 0, totalGroups = 0, totalKp = 0, octCap = 0;
   int maxKeypoints = 0;
   // device memory
-  DevBuf d_pyr, d_blur, d_cellCnt, d_cellOff, d_slots, d_cand, d_knode, d_lkp, d_lrank, d_lcnt, d_candCnt, d_cells, d_groups, d_tiles, d_xtab,
+  DevBuf d_pyr, d_blur, d_cellCnt, d_cellOff, d_slots, d_cand, d_knode, d_lkp, d_lrank, d_lcnt, d_candCnt, d_fastRecs, d_tiles, d_xtab,
       d_ytab, d_disc, d_chain;
   DevBuf d_img, d_okps;  // staging for the host entry point (d_okps: counts + keypoints + descriptors, one block)
   hipStream_t stream = nullptr;
@@ -281,7 +281,7 @@ void orbx_destroy(orbx_t *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   DevBuf *bufs[] = {&h->d_pyr, &h->d_blur, &h->d_cellCnt, &h->d_cellOff, &h->d_slots, &h->d_cand, &h->d_knode, &h->d_lkp,
-                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_cells, &h->d_groups, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
+                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_fastRecs, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
   for (DevBuf *b : bufs) b->release();
   for (DevBuf &b : h->stereo) b.release();
   for (DevBuf &b : h->stereo_batch) b.release();
@@ -447,28 +447,24 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
     } else { G.resizeRows = RESIZE_ROWS_MAX; G.resizeSrcRows = 0; }
   }
   if (slots > (1 << 30)) { h->err = "workspace too large"; return ORBX_E_ARG; }
-  // FAST cell records (k_fast): window of every cell as the reference's double loop derives it, ORBextractor.cc:787-803
-  std::vector<uint32_t> cellrec((size_t)std::max(cells, 1) * 8, 0u);
+  // FAST cells: window of every cell as the reference's double loop derives it, ORBextractor.cc:787-803 (the cell words of k_fast's
+  // group records, below)
+  std::vector<uint32_t> cellrec((size_t)std::max(cells, 1) * 4, 0u);
   for (int l = 0; l < nl; l++) {
     LevelGeom &G = g[l];
     G.rowTileMagic = magic_div((uint32_t)((G.h + G.resizeRows - 1) / G.resizeRows));
     for (int ci = 0; ci < G.nRows; ci++)
       for (int cj = 0; cj < G.nCols; cj++) {
         const int c = ci * G.nCols + cj;
-        uint32_t *R = &cellrec[(size_t)(G.cellBase + c) * 8];
+        uint32_t *R = &cellrec[(size_t)(G.cellBase + c) * 4];
         const int iniX = ORB_MIN_BORDER + cj * G.wCell, iniY = ORB_MIN_BORDER + ci * G.hCell;
         const int maxX = std::min(iniX + G.wCell + 6, G.maxBorderX), maxY = std::min(iniY + G.hCell + 6, G.maxBorderY);
         const int tw = maxX - iniX, th = maxY - iniY;
         const bool valid = !(iniX >= G.maxBorderX - 6 || iniY >= G.maxBorderY - 3 || tw - 6 <= 0 || th - 6 <= 0);
         if (valid && (tw > FAST_TILE_COLS || th > FAST_TILE_ROWS)) { h->err = "FAST cell larger than the LDS tile"; return ORBX_E_ARG; }
         R[0] = (uint32_t)iniX | ((uint32_t)iniY << 16);
-        R[1] = valid ? ((uint32_t)tw | ((uint32_t)th << 8) | ((uint32_t)l << 16) | (1u << 24)) : ((uint32_t)l << 16);
-        R[2] = (uint32_t)(cj * G.wCell) | ((uint32_t)(ci * G.hCell) << 16);
-        R[3] = (uint32_t)(G.slotBase + c * G.cellCap);
-        R[4] = (uint32_t)G.cellCap;
-        R[5] = (uint32_t)G.pitch;
-        R[6] = (uint32_t)(G.off & 0xffffffffu);
-        R[7] = (uint32_t)((uint64_t)G.off >> 32);
+        R[1] = valid ? ((uint32_t)tw | ((uint32_t)th << 8) | (1u << 24)) : 0u;
+        R[2] = (uint32_t)(G.slotBase + c * G.cellCap);
       }
   }
   // k_fast's workgroups: groups of up to 2 x 2 neighbouring cells of a level that fit one LDS tile (80-byte rows from the first cell's
@@ -481,12 +477,12 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
       for (int cj = 0; cj < G.nCols; cj += sx) {
         const int gx = std::min(sx, G.nCols - cj), gy = std::min(sy, G.nRows - ci);
         const int first = G.cellBase + ci * G.nCols + cj;
-        const uint32_t *F = &cellrec[(size_t)first * 8];
+        const uint32_t *F = &cellrec[(size_t)first * 4];
         const int tileX = (int)(F[0] & 0xffffu), tileY = (int)(F[0] >> 16);
         int maxX = 0, maxY = 0, nvalid = 0;
         for (int a = 0; a < gy; a++)
           for (int b = 0; b < gx; b++) {
-            const uint32_t *R = &cellrec[(size_t)(first + a * G.nCols + b) * 8];
+            const uint32_t *R = &cellrec[(size_t)(first + a * G.nCols + b) * 4];
             if (!(R[1] >> 24)) continue;
             nvalid++;
             maxX = std::max(maxX, (int)(R[0] & 0xffffu) + (int)(R[1] & 0xffu));
@@ -494,13 +490,29 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
           }
         const int gtw = nvalid ? maxX - tileX : 0, gth = nvalid ? maxY - tileY : 0;
         if (nvalid && ((tileX & 3) + gtw > FAST_TILE_PITCH || gth > FAST_TILE_ROWS)) { h->err = "FAST cell group larger than the LDS tile"; return ORBX_E_ARG; }
-        grouprec.push_back((uint32_t)first);
-        grouprec.push_back((uint32_t)gx | ((uint32_t)gy << 8) | ((uint32_t)G.nCols << 16));
-        grouprec.push_back((uint32_t)tileX | ((uint32_t)tileY << 16));
-        grouprec.push_back((uint32_t)gtw | ((uint32_t)gth << 8) | ((uint32_t)l << 16) | (nvalid ? 1u << 24 : 0u));
+        // the record k_fast reads (layout: orb_common.h): the group, then cell w = wavefront w's, row-major inside the group
+        grouprec.resize(grouprec.size() + FAST_REC_WORDS, 0u);
+        uint32_t *Q = &grouprec[grouprec.size() - FAST_REC_WORDS];
+        Q[0] = (uint32_t)tileX | ((uint32_t)tileY << 16);
+        Q[1] = (uint32_t)gtw | ((uint32_t)gth << 8) | ((uint32_t)l << 16) | (nvalid ? 1u << 24 : 0u);
+        Q[2] = (uint32_t)(gx * gy);
+        Q[3] = (uint32_t)G.pitch;
+        Q[4] = (uint32_t)(G.off & 0xffffffffu);
+        Q[5] = (uint32_t)((uint64_t)G.off >> 32);
+        Q[6] = (uint32_t)G.cellCap;
+        for (int a = 0; a < gy; a++)
+          for (int b = 0; b < gx; b++) {
+            const int cell = first + a * G.nCols + b;
+            const uint32_t *R = &cellrec[(size_t)cell * 4];
+            uint32_t *C = Q + FAST_REC_GROUP_WORDS + FAST_REC_CELL_WORDS * (a * gx + b);
+            C[0] = R[0];
+            C[1] = R[1];
+            C[2] = R[2];
+            C[3] = (uint32_t)cell;
+          }
       }
   }
-  h->totalGroups = (int)(grouprec.size() / 4);
+  h->totalGroups = (int)(grouprec.size() / FAST_REC_WORDS);
   // blur tile records (k_blur)
   std::vector<uint32_t> tilerec((size_t)std::max(tiles, 1) * 8, 0u);
   for (int l = 0; l < nl; l++) {
@@ -542,10 +554,8 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   XCHECK(h, h->d_lrank.reserve(sizeof(uint16_t) * (size_t)h->lkp_fs * B));
   XCHECK(h, h->d_lcnt.reserve(sizeof(int32_t) * 2 * nl * B));
   XCHECK(h, h->d_candCnt.reserve(sizeof(int32_t) * nl * B));
-  XCHECK(h, h->d_cells.reserve(sizeof(uint32_t) * cellrec.size()));
-  XCHECK(h, copy_on(h->stream, h->d_cells.p, cellrec.data(), sizeof(uint32_t) * cellrec.size(), hipMemcpyHostToDevice));
-  XCHECK(h, h->d_groups.reserve(sizeof(uint32_t) * std::max<size_t>(grouprec.size(), 4)));
-  if (!grouprec.empty()) XCHECK(h, copy_on(h->stream, h->d_groups.p, grouprec.data(), sizeof(uint32_t) * grouprec.size(), hipMemcpyHostToDevice));
+  XCHECK(h, h->d_fastRecs.reserve(sizeof(uint32_t) * std::max<size_t>(grouprec.size(), FAST_REC_WORDS)));   // hipMalloc: aligned beyond a record's 128 bytes
+  if (!grouprec.empty()) XCHECK(h, copy_on(h->stream, h->d_fastRecs.p, grouprec.data(), sizeof(uint32_t) * grouprec.size(), hipMemcpyHostToDevice));
   XCHECK(h, h->d_tiles.reserve(sizeof(uint32_t) * tilerec.size()));
   XCHECK(h, copy_on(h->stream, h->d_tiles.p, tilerec.data(), sizeof(uint32_t) * tilerec.size(), hipMemcpyHostToDevice));
   XCHECK(h, h->d_xtab.reserve(sizeof(int2) * std::max<size_t>(xtab.size(), 1)));
@@ -687,8 +697,7 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   P.disc = (const int8_t *)h->d_disc.p;
   P.totalTiles = h->totalTiles;
   P.totalCells = h->totalCells;
-  P.cells = (const uint32_t *)h->d_cells.p;
-  P.groups = (const uint32_t *)h->d_groups.p;
+  P.fastRecs = (const uint32_t *)h->d_fastRecs.p;
   P.totalGroups = h->totalGroups;
   P.magicGroups = magic_div((uint32_t)std::max(h->totalGroups, 1));
   P.tiles = (const uint32_t *)h->d_tiles.p;

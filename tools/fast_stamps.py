@@ -47,9 +47,14 @@ for it in range(3):
     torch.cuda.synchronize()
 v = buf.cpu().numpy().astype(np.float64)
 live = v[:, 0] > 0
-# wavefront 0's cell (thread 0 stamps); a cell's second detection overwrites sections 1 and 2 with its own
-names = ["prologue+tile load", "pass1+2 compass+queue+score+list", "pass3 NMS + emit", "(unused)", "(unused)", "(unused)", "(unused)", "cell count"]
+# wavefront 0's cell (thread 0 stamps); a cell's second detection overwrites sections 1 and 2 with its own.  Slots in the order the
+# kernel passes them; a cell outside the detection rectangle leaves after the barrier and stamps only the first two.
+order = [3, 0, 4, 1, 2, 7]
+names = {3: "arguments, group record, tile DMA issue", 0: "score plane clear + barrier (DMA wait)", 4: "barrier -> detection loop (cell record)",
+         1: "pass1+2 compass+queue+score+list", 2: "pass3 NMS + emit", 7: "cell count"}
+live = live & (v[:, 7] > 0)
 m = v[live].mean(axis=0)
-for n, x in zip(names, m):
-    print("%-22s %6.1f %%   %.0f cycles/workgroup" % (n, 100 * x / m.sum(), x))
+for i in order:
+    print("%-40s %6.1f %%   %.0f cycles/workgroup" % (names[i], 100 * m[i] / m.sum(), m[i]))
+print("prologue (first two sections) %.0f cycles/workgroup" % (m[3] + m[0]))
 print("workgroups with work: %d of %d; total %.0f cycles/workgroup" % (live.sum(), nwg, m.sum()))
