@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -54,6 +54,22 @@ class KeyFrameStruct(C.Structure):  # orbm_keyframe_t
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("descriptors", C.c_void_p), ("u_right", C.c_void_p),
                 ("has_mappoint", C.c_void_p), ("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("node_start", C.c_void_p),
                 ("node_idx", C.c_void_p), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+class KeyFrameGeometryStruct(C.Structure):  # orbm_keyframe_geometry_t
+    _fields_ = [("Tcw", C.c_void_p), ("Ow", C.c_void_p), ("Tcw_right", C.c_void_p), ("Ow_right", C.c_void_p), ("Twc", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")] + [("depth", C.c_void_p), ("keys", C.c_void_p)]
+
+
+# ORBM_NP_* of include/orbhip.h: the outcome of the body of LocalMapping::CreateNewMapPoints' loop for one pair
+(NP_NO_MATCH, NP_ACCEPTED, NP_LOW_PARALLAX, NP_ZERO_W, NP_EMPTY_STEREO, NP_BEHIND1, NP_BEHIND2, NP_REPROJ1, NP_REPROJ1_STEREO, NP_REPROJ2,
+ NP_REPROJ2_STEREO, NP_ZERO_DIST, NP_FAR, NP_SCALE, NP_NSTATUS) = range(15)
+NEW_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("x3D", "<f4", (3,))])          # orbm_new_point_t
+NP_CAMERA_DTYPE = np.dtype([("Tcw", "<f4", (2, 12)), ("Ow", "<f4", (2, 3)), ("Twc", "<f4", (12,)), ("cam", "<f4", (2, 8))] +
+                           [(k, "<f4") for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")] +
+                           [("sf", "<f4", (16,)), ("sigma2", "<f4", (16,)), ("cam_type", "<i4"), ("n_left", "<i4")])     # orbm_new_point_camera_t
+NP_OBS_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("u_right", "<f4"), ("depth", "<f4"), ("key_x", "<f4"), ("key_y", "<f4"),
+                         ("right", "<i4")])                                                                           # orbm_new_point_obs_t
 
 
 class LastFrameStruct(C.Structure):  # orbm_last_frame_t
@@ -200,6 +216,10 @@ def load(build_if_needed=True):
     L.orbm_search_for_triangulation_kb8.argtypes = [vp, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, i32, i32, vp]
     L.orbm_search_for_triangulation_neighbours.argtypes = [vp, vp, i32] + [vp] * 9 + [i32, i32, vp, vp]
     L.orbm_search_for_triangulation_kb8_neighbours.argtypes = [vp, vp, i32, i32] + [vp] * 7 + [i32, i32, vp, vp]
+    L.orbm_new_point_geometry.argtypes = [i32, vp, vp, vp, vp, f32, i32, f32, vp, vp]
+    L.orbm_new_point_geometry_device.argtypes = [i32, vp, vp, vp, vp, f32, i32, f32, vp, vp, vp]
+    L.orbm_create_new_map_points.argtypes = [vp, vp, vp, f32, i32, vp, vp] + [vp] * 8 + [i32, i32, f32, vp, i32, vp, vp, vp]
+    L.orbm_create_new_map_points_kb8.argtypes = [vp, vp, vp, f32, i32, i32, vp, vp] + [vp] * 6 + [i32, i32, f32, vp, i32, vp, vp, vp]
     L.orbm_search_by_projection_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp]
     L.orbm_search_by_projection_keyframe.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32, i32, vp, vp]
     L.orbm_search_by_projection_last_frame.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32,
@@ -517,6 +537,75 @@ class KeyFrameView:
     def struct(self):
         return KeyFrameStruct(self.N, _p(self.keys_un), _p(self.descriptors), _p(self.u_right), _p(self.has_mappoint), len(self.node_id),
                               _p(self.node_id), _p(self.node_start), _p(self.node_idx), _p(self.sf), _p(self.sigma2), len(self.sf))
+
+
+class KeyFrameGeometry:
+    """What the body of LocalMapping::CreateNewMapPoints' loop reads of a keyframe beyond KeyFrameView (orbm_keyframe_geometry_t):
+    Tcw = [Rcw | tcw] (3x4), Ow, for rigs the right camera's Tcw_right / Ow_right, Twc (3x4), the intrinsics fx .. invfy, mb, mbf,
+    mvDepth and mvKeys (both only where a keypoint has u_right >= 0)."""
+
+    def __init__(self, Tcw, Ow, fx=0.0, fy=0.0, cx=0.0, cy=0.0, invfx=None, invfy=None, mb=0.0, mbf=0.0, Twc=None, depth=None, keys=None,
+                 Tcw_right=None, Ow_right=None):
+        f = lambda x, n: None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(-1)[:n].copy()
+        self.Tcw, self.Ow, self.Tcw_right, self.Ow_right, self.Twc = f(Tcw, 12), f(Ow, 3), f(Tcw_right, 12), f(Ow_right, 3), f(Twc, 12)
+        inv = lambda given, f_: given if given is not None else (np.float32(1.0) / np.float32(f_) if f_ else 0.0)   # invfx = 1.0f / fx (Frame.cc:169)
+        self.scalars = [np.float32(v) for v in (fx, fy, cx, cy, inv(invfx, fx), inv(invfy, fy), mb, mbf)]
+        self.depth = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+        self.keys = None if keys is None else np.ascontiguousarray(keys, dtype=KP_DTYPE)
+
+    def struct(self):
+        return KeyFrameGeometryStruct(_p(self.Tcw), _p(self.Ow), _p(self.Tcw_right), _p(self.Ow_right), _p(self.Twc), *[float(v) for v in self.scalars],
+                                      _p(self.depth), _p(self.keys))
+
+
+def new_point_camera(KF, G, cam_type, cams, n_left=-1):
+    """orbm_new_point_camera_t of keyframe (KF, G): cams = mvParameters of mpCamera [, mpCamera2]."""
+    c = np.zeros((), NP_CAMERA_DTYPE)
+    cams = np.ascontiguousarray(cams, dtype=np.float32).reshape(-1)
+    npar = 4 if cam_type == 0 else 8
+    c["Tcw"][0], c["Ow"][0], c["cam"][0][:npar] = G.Tcw, G.Ow, cams[:npar]
+    if n_left != -1:
+        c["Tcw"][1], c["Ow"][1], c["cam"][1][:npar] = G.Tcw_right, G.Ow_right, cams[8:8 + npar]
+    if G.Twc is not None:
+        c["Twc"] = G.Twc
+    for k, v in zip(("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf"), G.scalars):
+        c[k] = v
+    c["sf"][:len(KF.sf)], c["sigma2"][:len(KF.sigma2)] = KF.sf, KF.sigma2
+    c["cam_type"], c["n_left"] = cam_type, n_left
+    return c
+
+
+def new_point_obs(KF, G, idx, n_left=-1):
+    """orbm_new_point_obs_t [len(idx)] of the keypoints idx of keyframe (KF, G) as LocalMapping.cc:613-632 reads them."""
+    idx = np.asarray(idx, dtype=np.int64)
+    o = np.zeros(len(idx), NP_OBS_DTYPE)
+    o["x"], o["y"], o["octave"] = KF.keys_un["x"][idx], KF.keys_un["y"][idx], KF.keys_un["octave"][idx]
+    o["u_right"] = -1.0 if n_left != -1 else KF.u_right[idx]
+    st = o["u_right"] >= 0
+    if st.any():
+        o["depth"][st], o["key_x"][st], o["key_y"][st] = G.depth[idx[st]], G.keys["x"][idx[st]], G.keys["y"][idx[st]]
+    o["right"] = (idx >= n_left) if n_left != -1 else 0
+    return o
+
+
+def new_point_geometry(c1, c2, obs1, obs2, scale_factor1, far_points=False, th_far_points=0.0):
+    """The body of LocalMapping::CreateNewMapPoints' loop (LocalMapping.cc:605-880) for the pairs (obs1[i], obs2[i]) on the host
+    (orbm_new_point_geometry): (status [n] of NP_*, x3D [n, 3], zero where the pair is not accepted)."""
+    obs1, obs2 = np.ascontiguousarray(obs1, dtype=NP_OBS_DTYPE), np.ascontiguousarray(obs2, dtype=NP_OBS_DTYPE)
+    n = len(obs1)
+    c1, c2 = np.ascontiguousarray(c1, dtype=NP_CAMERA_DTYPE), np.ascontiguousarray(c2, dtype=NP_CAMERA_DTYPE)
+    status, x3 = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.float32)
+    _check_free(load().orbm_new_point_geometry(n, _p(c1), _p(c2), _p(obs1), _p(obs2), float(scale_factor1), int(bool(far_points)), float(th_far_points),
+                                               _p(status), _p(x3)), "orbm_new_point_geometry")
+    return status[:n], x3[:n]
+
+
+def new_point_geometry_device(n, c1, c2, d_obs1, d_obs2, scale_factor1, far_points, th_far_points, d_status, d_x3d, stream=None):
+    """The same over device arrays (addresses as ints), asynchronous on `stream` (orbm_new_point_geometry_device)."""
+    c1, c2 = np.ascontiguousarray(c1, dtype=NP_CAMERA_DTYPE), np.ascontiguousarray(c2, dtype=NP_CAMERA_DTYPE)
+    rc = load().orbm_new_point_geometry_device(int(n), _p(c1), _p(c2), _dp(d_obs1), _dp(d_obs2), float(scale_factor1), int(bool(far_points)),
+                                               float(th_far_points), _dp(d_status), _dp(d_x3d), _dp(stream))
+    return _check_free(rc, "orbm_new_point_geometry_device")
 
 
 class ORBmatcher:
@@ -1107,6 +1196,87 @@ class ORBmatcher:
         rc = self.L.orbm_search_for_triangulation_kb8_neighbours(self.m, C.byref(s1), int(n_left1), K, ptab, q(nl2), q(ep), q(c1), q(c2), q(t12), q(sk),
                                                                  int(bool(bOnlyStereo)), int(bool(bCoarse)), _p(m12), _p(nm))
         return self._neighbour_rows(rc, "orbm_search_for_triangulation_kb8_neighbours", m12, nm, K, KF1.N)
+
+    @staticmethod
+    def _geometry_table(Gs):
+        if not Gs:
+            return None, None
+        tab = (KeyFrameGeometryStruct * len(Gs))(*[g.struct() for g in Gs])
+        return tab, C.cast(tab, C.c_void_p)
+
+    def _new_points(self, call, what, K, n1, cap, status, matches):
+        """Runs call(points, cap, status, matches12, nmatches) and shapes (points, status, matches12, nmatches)."""
+        cap = n1 if cap is None else int(cap)
+        pts = np.zeros(max(cap, 1), NEW_POINT_DTYPE)
+        st = np.zeros(max(K * n1, 1), np.uint8) if status else None
+        m12 = np.full(max(K * n1, 1), -1, np.int32) if matches else None
+        nm = np.zeros(max(K, 1), np.int32) if matches else None
+        rc = call(_p(pts) if cap > 0 else None, cap, _p(st), _p(m12), _p(nm))
+        self._check(rc, what)
+        if rc < 0:
+            raise OrbError("%s rc=%d" % (what, rc))
+        shape = lambda a: None if a is None else a[:K * n1].reshape(K, n1)
+        return (pts[:rc] if rc <= cap else rc), shape(st), shape(m12), (None if nm is None else nm[:K].copy())
+
+    def CreateNewMapPoints(self, KF1, G1, scale_factor1, KF2s, G2s, R1w, t1w, Cw1, cam1, R2w, t2w, cam2, skip=None, bCoarse=False, far_points=False,
+                           th_far_points=0.0, cap=None, status=True, matches=True):
+        """LocalMapping::CreateNewMapPoints (LocalMapping.cc:470-905) for Pinhole keyframes, mono and rectified stereo mixed per keypoint
+        (orbm_create_new_map_points): SearchForTriangulationNeighbours, then the body of the loop on every matched pair on the device.
+        G1 / G2s: KeyFrameGeometry; scale_factor1 = mfScaleFactor of KF1.  Returns (points, status [K, N1] or None, matches12 [K, N1] or None,
+        nmatches [K] or None): points is a NEW_POINT_DTYPE array in the reference's creation order - or, when it holds more than cap entries
+        (default KF1.N, which always suffices), the needed count as an int.  The caller keeps the entries with neighbour < i when
+        CheckNewKeyFrames() ends the loop in front of neighbour i."""
+        K = len(KF2s)
+        a = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1) if x is not None else None
+        R1w, t1w, Cw1, cam1, R2w, t2w, cam2 = a(R1w), a(t1w), a(Cw1), a(cam1), a(R2w), a(t2w), a(cam2)
+        for v, n in ((R1w, 9), (t1w, 3), (Cw1, 3), (cam1, 4), (R2w, 9 * K), (t2w, 3 * K), (cam2, 4 * K)):
+            if v is not None and len(v) != n:
+                raise ValueError("CreateNewMapPoints: %d floats where %d are expected" % (len(v), n))
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        if (sk is not None and len(sk) != K) or (G2s is not None and len(G2s) != K):
+            raise ValueError("CreateNewMapPoints: skip and G2s need one entry per neighbour")
+        s1, g1 = KF1.struct(), (G1.struct() if G1 is not None else None)
+        tab, ptab = self._keyframe_table(KF2s)
+        gtab, pgtab = self._geometry_table(G2s)
+        q = lambda v: _p(v) if v is not None and len(v) else None
+        call = lambda pts, cap_, st, m12, nm: self.L.orbm_create_new_map_points(
+            self.m, C.byref(s1), C.byref(g1) if g1 is not None else None, float(scale_factor1), K, ptab, pgtab, q(R1w), q(t1w), q(Cw1), q(cam1), q(R2w),
+            q(t2w), q(cam2), q(sk), int(bool(bCoarse)), int(bool(far_points)), float(th_far_points), pts, cap_, st, m12, nm)
+        return self._new_points(call, "orbm_create_new_map_points", K, KF1.N, cap, status, matches)
+
+    def CreateNewMapPointsKB8(self, KF1, G1, scale_factor1, KF2s, G2s, ep, cams1, cams2, T12, n_left1=-1, n_left2=None, skip=None, bCoarse=False,
+                              far_points=False, th_far_points=0.0, cap=None, status=True, matches=True):
+        """The same for KannalaBrandt8 keyframes (n_left1 == -1) or two-camera KannalaBrandt8 rigs (orbm_create_new_map_points_kb8); the
+        search's arguments are SearchForTriangulationKB8Neighbours', for rigs G?.Tcw_right / Ow_right are read."""
+        K = len(KF2s)
+        rig = n_left1 != -1
+        f = lambda x: np.ascontiguousarray(x, dtype=np.float32) if x is not None else None
+        ep, cams1, cams2, T12 = f(ep), f(cams1), f(cams2), f(T12)
+        c1 = None
+        if cams1 is not None:
+            c1 = np.zeros(16, np.float32)
+            c1[:cams1.size] = cams1.reshape(-1)[:16]
+        c2 = t12 = None
+        if cams2 is not None and K:      # the ABI's strides are a rig's
+            c2 = np.zeros((K, 16), np.float32)
+            c2[:, :(16 if rig else 8)] = cams2.reshape(K, -1)
+        if T12 is not None and K:
+            t12 = np.zeros((K, 48), np.float32)
+            t12[:, :(48 if rig else 12)] = T12.reshape(K, -1)
+        if ep is not None:
+            ep = np.ascontiguousarray(ep.reshape(K, 2))
+        nl2 = np.full(K, -1, np.int32) if n_left2 is None else np.ascontiguousarray(n_left2, dtype=np.int32)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        if len(nl2) != K or (sk is not None and len(sk) != K) or (G2s is not None and len(G2s) != K):
+            raise ValueError("CreateNewMapPointsKB8: n_left2, skip and G2s need one entry per neighbour")
+        s1, g1 = KF1.struct(), (G1.struct() if G1 is not None else None)
+        tab, ptab = self._keyframe_table(KF2s)
+        gtab, pgtab = self._geometry_table(G2s)
+        q = lambda v: _p(v) if v is not None and v.size else None
+        call = lambda pts, cap_, st, m12, nm: self.L.orbm_create_new_map_points_kb8(
+            self.m, C.byref(s1), C.byref(g1) if g1 is not None else None, float(scale_factor1), int(n_left1), K, ptab, pgtab, q(nl2), q(ep), q(c1), q(c2),
+            q(t12), q(sk), int(bool(bCoarse)), int(bool(far_points)), float(th_far_points), pts, cap_, st, m12, nm)
+        return self._new_points(call, "orbm_create_new_map_points_kb8", K, KF1.N, cap, status, matches)
 
     def hamming_matrix(self, q, c):
         q = np.ascontiguousarray(q, dtype=np.uint8)

@@ -1,7 +1,8 @@
 // LocalMapping_CreateNewMapPoints_hip.cc -- the neighbour loop of void LocalMapping::CreateNewMapPoints() (src/LocalMapping.cc:525-583)
-// with ONE search for all neighbours in front of it instead of one ORBmatcher::SearchForTriangulation call per neighbour.
+// with ONE search for all neighbours in front of it instead of one ORBmatcher::SearchForTriangulation call per neighbour - and, on
+// request, the geometric body of the loop (:585-880) in the same call.
 //
-// The geometric body of the loop - parallax, linear triangulation, the reprojection and scale tests, the new MapPoint
+// Search-only form: the geometric body of the loop - parallax, linear triangulation, the reprojection and scale tests, the new MapPoint
 // (src/LocalMapping.cc:585-900) - stays where it is, unchanged.  Add this file to the library's sources and make three edits in
 // src/LocalMapping.cc:
 //   1. in front of the loop (:525), once bCoarse's expression of :577-581 has been moved up there:
@@ -17,6 +18,17 @@
 // with checkOri = false (:500).  So the sequential result for neighbour i is row i from the state at loop entry without the idx1 that
 // received a map point since: matched_indices() drops those.  bCoarse is read once at loop entry, where the reference reads the
 // tracker's state again per neighbour.
+//
+// With `geometry` set the constructor goes one step further (orbm_create_new_map_points / orbm_create_new_map_points_kb8): the body of
+// the loop runs on the device too, and the loop body from :585 to :880 becomes
+//        for (const orbm_new_point_t *p = search.new_points_begin(i); p != search.new_points_end(i); ++p) {
+//          cv::Mat x3D = search.x3D(*p); const int idx1 = p->idx1, idx2 = p->idx2;
+//          MapPoint *pMP = new MapPoint(x3D, mpCurrentKeyFrame, mpAtlas->GetCurrentMap());     // :883
+//          ... :889-902 unchanged ...
+//        }
+// The list holds what the sequential loop creates (the SEQUENTIAL RULE of include/orbhip.h: an accepted pair whose idx1 no earlier
+// neighbour had accepted), in its order; a `return` at :528 in front of neighbour i simply leaves the entries of neighbours >= i unused.
+// Where the camera models are mixed (has_new_points() false) the search-only form and the reference's own body remain.
 //
 // The entry is chosen by camera model as in ORBmatcher_hip.cc: Pinhole throughout -> orbm_search_for_triangulation_neighbours,
 // KannalaBrandt8 throughout (single cameras or rigs) -> orbm_search_for_triangulation_kb8_neighbours; anything else keeps the per-pair
@@ -84,6 +96,34 @@ struct FlatKeyFrame {
   }
 };
 
+// What the body of the loop reads of a KeyFrame beyond FlatKeyFrame (orbm_keyframe_geometry_t)
+struct FlatGeometry {
+  float Tcw[12], Ow[3], TcwRight[12], OwRight[3], Twc[12];
+  orbm_keyframe_geometry_t g;
+  static void rows_of(const cv::Mat &T, float *o) { for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) o[4 * r + c] = T.at<float>(r, c); }
+  explicit FlatGeometry(KeyFrame *pKF) {
+    std::memset(&g, 0, sizeof(g));
+    rows_of(pKF->GetPose(), Tcw);
+    rows_of(pKF->GetPoseInverse(), Twc);
+    cv::Mat O = pKF->GetCameraCenter();
+    for (int r = 0; r < 3; r++) Ow[r] = O.at<float>(r);
+    if (pKF->mpCamera2) {
+      rows_of(pKF->GetRightPose(), TcwRight);
+      cv::Mat Or = pKF->GetRightCameraCenter();
+      for (int r = 0; r < 3; r++) OwRight[r] = Or.at<float>(r);
+    }
+    g.fx = pKF->fx; g.fy = pKF->fy; g.cx = pKF->cx; g.cy = pKF->cy; g.invfx = pKF->invfx; g.invfy = pKF->invfy; g.mb = pKF->mb; g.mbf = pKF->mbf;
+  }
+  void bind(KeyFrame *pKF) {   // after the object has reached its final address
+    g.Tcw = Tcw; g.Ow = Ow; g.Twc = Twc;
+    g.Tcw_right = pKF->mpCamera2 ? TcwRight : NULL;
+    g.Ow_right = pKF->mpCamera2 ? OwRight : NULL;
+    const bool arrays = !pKF->mpCamera2 && (int)pKF->mvDepth.size() >= pKF->N && (int)pKF->mvKeys.size() >= pKF->N;
+    g.depth = arrays ? pKF->mvDepth.data() : NULL;
+    g.keys = arrays ? reinterpret_cast<const orbx_keypoint_t *>(pKF->mvKeys.data()) : NULL;
+  }
+};
+
 void mat33_of(const cv::Mat &M, float *o) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) o[3 * r + c] = M.at<float>(r, c); }
 void vec3_of(const cv::Mat &M, float *o) { for (int r = 0; r < 3; r++) o[r] = M.at<float>(r); }
 void pose_of(const cv::Mat &R, const cv::Mat &t, float *o) {   // [R | t], row stride 4
@@ -97,13 +137,18 @@ void pose_of(const cv::Mat &R, const cv::Mat &t, float *o) {   // [R | t], row s
 struct NeighbourTriangulation {
   KeyFrame *mpCurrentKeyFrame;
   std::vector<KeyFrame *> vpNeighKFs;
-  bool bCoarse, batched;
+  bool bCoarse, batched, listed;
   std::vector<uint8_t> skip;
   std::vector<int32_t> matches12;   // [K][N1], batched only
+  std::vector<orbm_new_point_t> points;   // geometry only: the new map points in creation order
+  std::vector<size_t> first_of;           // [K + 1]: the entries of neighbour i are points[first_of[i] .. first_of[i + 1])
   int N1;
 
-  NeighbourTriangulation(KeyFrame *pKF1, const std::vector<KeyFrame *> &neighbours, bool bMonocular, bool coarse)
-      : mpCurrentKeyFrame(pKF1), vpNeighKFs(neighbours), bCoarse(coarse), batched(false), skip(neighbours.size(), 0), N1(pKF1->N) {
+  // geometry: also run the body of the loop (:605-880) on the device; bFarPoints / thFarPoints = mbFarPoints / mThFarPoints
+  NeighbourTriangulation(KeyFrame *pKF1, const std::vector<KeyFrame *> &neighbours, bool bMonocular, bool coarse, bool geometry = false,
+                         bool bFarPoints = false, float thFarPoints = 0.f)
+      : mpCurrentKeyFrame(pKF1), vpNeighKFs(neighbours), bCoarse(coarse), batched(false), listed(false), skip(neighbours.size(), 0),
+        first_of(neighbours.size() + 1, 0), N1(pKF1->N) {
     const int K = (int)vpNeighKFs.size();
     // the baseline tests, src/LocalMapping.cc:535-560
     cv::Mat Ow1 = pKF1->GetCameraCenter();
@@ -147,6 +192,25 @@ struct NeighbourTriangulation {
       B.back().bind(vpNeighKFs[i]);
       tab[i] = B.back().k;
     }
+    // ... and, for the body of the loop, their poses, intrinsics, mvDepth and mvKeys
+    std::vector<FlatGeometry> GB;
+    std::vector<orbm_keyframe_geometry_t> gtab(K);
+    std::memset(gtab.data(), 0, sizeof(orbm_keyframe_geometry_t) * (size_t)K);
+    FlatGeometry GA(pKF1);
+    GA.bind(pKF1);
+    if (geometry) {
+      GB.reserve(K);
+      for (int i = 0; i < K; i++) {
+        if (skip[i]) continue;
+        GB.push_back(FlatGeometry(vpNeighKFs[i]));
+      }
+      for (int i = 0, b = 0; i < K; i++) {
+        if (skip[i]) continue;
+        GB[b].bind(vpNeighKFs[i]);
+        gtab[i] = GB[b++].g;
+      }
+      points.resize(N1 > 0 ? N1 : 1);   // an idx1 appears at most once
+    }
     matches12.assign((size_t)K * (size_t)(N1 > 0 ? N1 : 1), -1);
     std::vector<int32_t> nmatches(K, 0);
     cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), Cw = pKF1->GetCameraCenter();
@@ -162,8 +226,13 @@ struct NeighbourTriangulation {
         vec3_of(vpNeighKFs[i]->GetTranslation(), &t2w[(size_t)i * 3]);
         for (int k = 0; k < 4; k++) cam2[(size_t)i * 4 + k] = vpNeighKFs[i]->mpCamera->getParameter(k);
       }
-      rc = orbm_search_for_triangulation_neighbours(neighbours_matcher(), &A.k, K, tab.data(), fR1w, ft1w, fCw, cam1, R2w.data(), t2w.data(), cam2.data(),
-                                                    skip.data(), 0, bCoarse ? 1 : 0, matches12.data(), nmatches.data());
+      if (geometry)
+        rc = orbm_create_new_map_points(neighbours_matcher(), &A.k, &GA.g, pKF1->mfScaleFactor, K, tab.data(), gtab.data(), fR1w, ft1w, fCw, cam1, R2w.data(),
+                                        t2w.data(), cam2.data(), skip.data(), bCoarse ? 1 : 0, bFarPoints ? 1 : 0, thFarPoints, points.data(), N1, NULL,
+                                        matches12.data(), nmatches.data());
+      else
+        rc = orbm_search_for_triangulation_neighbours(neighbours_matcher(), &A.k, K, tab.data(), fR1w, ft1w, fCw, cam1, R2w.data(), t2w.data(), cam2.data(),
+                                                      skip.data(), 0, bCoarse ? 1 : 0, matches12.data(), nmatches.data());
     } else {
       float cams1[2][8] = {};
       for (int k = 0; k < 8; k++) {
@@ -198,12 +267,34 @@ struct NeighbourTriangulation {
           pose_of(Rll, tll, T); pose_of(Rlr, tlr, T + 12); pose_of(Rrl, trl, T + 24); pose_of(Rrr, trr, T + 36);
         }
       }
-      rc = orbm_search_for_triangulation_kb8_neighbours(neighbours_matcher(), &A.k, rig ? pKF1->NLeft : -1, K, tab.data(), n_left2.data(), ep.data(),
-                                                        &cams1[0][0], cams2.data(), T12.data(), skip.data(), 0, bCoarse ? 1 : 0, matches12.data(),
-                                                        nmatches.data());
+      if (geometry)
+        rc = orbm_create_new_map_points_kb8(neighbours_matcher(), &A.k, &GA.g, pKF1->mfScaleFactor, rig ? pKF1->NLeft : -1, K, tab.data(), gtab.data(),
+                                            n_left2.data(), ep.data(), &cams1[0][0], cams2.data(), T12.data(), skip.data(), bCoarse ? 1 : 0,
+                                            bFarPoints ? 1 : 0, thFarPoints, points.data(), N1, NULL, matches12.data(), nmatches.data());
+      else
+        rc = orbm_search_for_triangulation_kb8_neighbours(neighbours_matcher(), &A.k, rig ? pKF1->NLeft : -1, K, tab.data(), n_left2.data(), ep.data(),
+                                                          &cams1[0][0], cams2.data(), T12.data(), skip.data(), 0, bCoarse ? 1 : 0, matches12.data(),
+                                                          nmatches.data());
     }
     if (rc < 0) throw std::runtime_error(std::string("LocalMapping::CreateNewMapPoints (liborbhip): ") + orbm_last_error(neighbours_matcher()));
     batched = true;
+    if (geometry) {   // rc = the number of new points; the list is ordered by neighbour
+      points.resize((size_t)rc);
+      for (size_t p = 0; p < points.size(); p++) first_of[(size_t)points[p].neighbour + 1]++;
+      for (int i = 0; i < K; i++) first_of[(size_t)i + 1] += first_of[(size_t)i];
+      listed = true;
+    }
+  }
+
+  // geometry form: true when the list exists (one camera model throughout); otherwise use matched_indices() and the reference's own body
+  bool has_new_points() const { return listed; }
+  // the new map points of neighbour i, in ascending idx1: what the body of the loop (:605-880) accepts in iteration i
+  const orbm_new_point_t *new_points_begin(size_t i) const { return points.data() + first_of[i]; }
+  const orbm_new_point_t *new_points_end(size_t i) const { return points.data() + first_of[i + 1]; }
+  static cv::Mat x3D(const orbm_new_point_t &p) {
+    cv::Mat x(3, 1, CV_32F);
+    for (int r = 0; r < 3; r++) x.at<float>(r) = p.x3D[r];
+    return x;
   }
 
   // src/LocalMapping.cc:535-560

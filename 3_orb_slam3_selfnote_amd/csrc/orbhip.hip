@@ -27,6 +27,7 @@
 #include "orb_stereo_kernels.h"
 #include "orb_depth_kernels.h"
 #include "orb_rig_stereo_kernels.h"
+#include "orb_newpoints_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -3038,13 +3039,29 @@ int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int 
 // What the two entries share once every neighbour that is not skipped has been validated: the merge walks, ONE staged block (KF1 once,
 // the arrays of every neighbour that has work, the items, the neighbour table), one fill, the kernels over all neighbours, one
 // download of [K][n1], one synchronisation.  nb[j] arrives with F12 / epipole / n_left2; kb8 == NULL selects Pinhole's test.
+// np != NULL (orbm_create_new_map_points*): the body of the loop runs on the rows in device memory behind the search, its inputs ride in
+// the same block, matches12 / nmatches may be NULL (then the rows are not downloaded).
+struct NewPointsCall {
+  const orbm_keyframe_geometry_t *g1, *g2;
+  int cam_type;                         // 0 Pinhole, 1 KannalaBrandt8
+  const float *cams1, *cams2;           // mvParameters of kf1's cameras; of neighbour j's at cams2 + j * cams2_stride
+  int cams2_stride;
+  const int32_t *n_left2;               // NULL: -1 for every neighbour
+  float scale_factor1, th_far_points;
+  int far_points;
+  uint8_t *status;                      // [K][n1] or NULL
+  std::vector<orbm_new_point_t> list;   // out: the new points in creation order
+};
+static void new_point_camera(orbm_new_point_camera_t &c, const orbm_keyframe_t &k, const orbm_keyframe_geometry_t &g, int cam_type, const float *cams,
+                             int n_left);
+
 static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const uint8_t *skip,
                                     std::vector<TriNb> &nb, const std::vector<TriKb8Consts> *kb8, int bOnlyStereo, int bCoarse,
-                                    int32_t *matches12, int32_t *nmatches) {
+                                    int32_t *matches12, int32_t *nmatches, NewPointsCall *np = nullptr) {
   const bool rig = n_left1 != -1;
   const size_t n1 = (size_t)k1->n;
-  for (size_t i = 0; i < (size_t)K * n1; i++) matches12[i] = -1;
-  for (int j = 0; j < K; j++) nmatches[j] = 0;
+  if (matches12) for (size_t i = 0; i < (size_t)K * n1; i++) matches12[i] = -1;
+  if (nmatches) for (int j = 0; j < K; j++) nmatches[j] = 0;
   std::vector<TriItem> items;
   std::vector<uint8_t> live((size_t)K, 0);
   for (int j = 0; j < K; j++) {
@@ -3071,7 +3088,7 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
   static const int32_t zero = 0;
   std::vector<Part> parts;
   std::vector<size_t> offs;
-  parts.reserve(16 + 5 * (size_t)K);
+  parts.reserve(24 + 6 * (size_t)K);
   size_t off = 0;
   auto add = [&](const void *src, size_t bytes) { parts.push_back(Part{src, bytes}); offs.push_back(off); off += stage_span(bytes); return parts.size() - 1; };
   const size_t KP1 = add(k1->keys_un, sizeof(orbx_keypoint_t) * n1), DESC1 = add(k1->descriptors, 32 * n1);
@@ -3094,6 +3111,42 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
   const size_t out_bytes = sizeof(int32_t) * (size_t)K * n1;
   const size_t MATCHES12 = add(nullptr, out_bytes), BEST = add(nullptr, kb8 ? sizeof(uint32_t) * ni : 0);
   const size_t KEYS = add(nullptr, kb8 ? sizeof(uint32_t) * cap : 0), KEY_ITEM = add(nullptr, kb8 ? sizeof(int32_t) * cap : 0);
+  // the body's inputs and outputs behind the search's: per keyframe with stereo keypoints {mvDepth, mvKeys.pt}, the constants of the new
+  // keyframe and of every neighbour, then status / x3D / first / total + list
+  std::vector<orbm_new_point_camera_t> np_cams;
+  std::vector<std::vector<float>> np_stereo;
+  std::vector<uint64_t> np_stereo2;
+  size_t NP_STEREO1 = 0, NP_CAMS = 0, NP_STEREO2 = 0, NP_STATUS = 0, NP_X3D = 0, NP_FIRST = 0, NP_TOTAL = 0, NP_LIST = 0;
+  if (np) {
+    np_cams.resize((size_t)K + 1);
+    memset(np_cams.data(), 0, sizeof(orbm_new_point_camera_t) * np_cams.size());
+    np_stereo.resize((size_t)K + 1);
+    np_stereo2.assign((size_t)K, ~(uint64_t)0);
+    auto pack_stereo = [&](const orbm_keyframe_t &k, const orbm_keyframe_geometry_t &g, std::vector<float> &out) {
+      bool any = false;
+      for (int i = 0; !rig && i < k.n && !any; i++) any = k.u_right[i] >= 0;
+      if (!any) return;
+      out.resize(3 * (size_t)k.n);
+      for (int i = 0; i < k.n; i++) { out[3 * (size_t)i] = g.depth[i]; out[3 * (size_t)i + 1] = g.keys[i].x; out[3 * (size_t)i + 2] = g.keys[i].y; }
+    };
+    new_point_camera(np_cams[0], *k1, *np->g1, np->cam_type, np->cams1, n_left1);
+    pack_stereo(*k1, *np->g1, np_stereo[0]);
+    NP_STEREO1 = add(np_stereo[0].empty() ? nullptr : np_stereo[0].data(), sizeof(float) * np_stereo[0].size());
+    for (int j = 0; j < K; j++) {
+      if (!live[(size_t)j]) continue;
+      new_point_camera(np_cams[(size_t)j + 1], k2[j], np->g2[j], np->cam_type, np->cams2 + (size_t)j * (size_t)np->cams2_stride, np->n_left2 ? np->n_left2[j] : -1);
+      pack_stereo(k2[j], np->g2[j], np_stereo[(size_t)j + 1]);
+      const std::vector<float> &st = np_stereo[(size_t)j + 1];
+      if (!st.empty()) np_stereo2[(size_t)j] = offs[add(st.data(), sizeof(float) * st.size())];
+    }
+    NP_CAMS = add(np_cams.data(), sizeof(orbm_new_point_camera_t) * np_cams.size());
+    NP_STEREO2 = add(np_stereo2.data(), sizeof(uint64_t) * (size_t)K);
+    NP_STATUS = add(nullptr, (size_t)K * n1);
+    NP_X3D = add(nullptr, sizeof(float) * 3 * (size_t)K * n1);
+    NP_FIRST = add(nullptr, sizeof(int32_t) * n1);
+    NP_TOTAL = add(nullptr, sizeof(int32_t));
+    NP_LIST = add(nullptr, sizeof(orbm_new_point_t) * n1);
+  }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   std::vector<void *> d(parts.size());
@@ -3131,12 +3184,39 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     hipLaunchKernelGGL(k_triangulation_kb8_result_neighbours, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
   }
-  MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> np_out;   // total (one 256-byte part) and the list behind it, adjacent parts of the block: one copy
+  if (np) {
+    NewPointsParams P;
+    memset(&P, 0, sizeof(P));
+    P.in = T;
+    P.cams = (const orbm_new_point_camera_t *)d[NP_CAMS]; P.stereo1 = (const float *)d[NP_STEREO1]; P.stereo2 = (const uint64_t *)d[NP_STEREO2];
+    P.K = K; P.scale_factor1 = np->scale_factor1; P.th_far_points = np->th_far_points; P.far_points = np->far_points;
+    P.status = (uint8_t *)d[NP_STATUS]; P.x3d = (float *)d[NP_X3D]; P.first = (int32_t *)d[NP_FIRST];
+    P.list = (orbm_new_point_t *)d[NP_LIST]; P.total = (int32_t *)d[NP_TOTAL];
+    MCHECK(m, hipMemsetAsync(d[NP_FIRST], 0x7f, sizeof(int32_t) * n1, s));
+    hipLaunchKernelGGL(k_new_points_geometry, dim3((unsigned)(((size_t)K * n1 + 255) / 256)), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_new_points_emit, dim3((unsigned)K), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    np_out.resize(stage_span(sizeof(int32_t)) + sizeof(orbm_new_point_t) * n1);
+    MCHECK(m, hipMemcpyAsync(np_out.data(), d[NP_TOTAL], np_out.size(), hipMemcpyDeviceToHost, s));
+    if (np->status) MCHECK(m, hipMemcpyAsync(np->status, d[NP_STATUS], (size_t)K * n1, hipMemcpyDeviceToHost, s));
+  }
+  if (matches12) MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
+  if (np) {
+    int32_t total = 0;
+    memcpy(&total, np_out.data(), sizeof(total));
+    if (total < 0 || (size_t)total > n1) { m->err = "new points: list count out of range"; return ORBX_E_HIP; }
+    np->list.resize((size_t)total);
+    if (total) memcpy(np->list.data(), np_out.data() + stage_span(sizeof(int32_t)), sizeof(orbm_new_point_t) * (size_t)total);
+  }
   long long sum = 0;
-  for (int j = 0; j < K; j++) {
-    for (size_t i = 0; i < n1; i++) nmatches[j] += matches12[(size_t)j * n1 + i] >= 0;
-    sum += nmatches[j];
+  for (int j = 0; matches12 && j < K; j++) {
+    int nj = 0;
+    for (size_t i = 0; i < n1; i++) nj += matches12[(size_t)j * n1 + i] >= 0;
+    if (nmatches) nmatches[j] = nj;
+    sum += nj;
   }
   return (int)std::min<long long>(sum, 0x7fffffff);
 }
@@ -3181,19 +3261,13 @@ int orbm_search_for_triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k
   return triangulation_neighbours(m, k1, -1, K, k2, skip, nb, nullptr, bOnlyStereo, bCoarse, matches12, nmatches);
 }
 
-int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const int32_t *n_left2,
-                                                 const float *ep, const float *cams1, const float *cams2, const float *T12, const uint8_t *skip,
-                                                 int bOnlyStereo, int bCoarse, int32_t *matches12, int32_t *nmatches) {
-  if (!m || !k1) return ORBX_E_ARG;
-  const bool rig = n_left1 != -1;
+// The KannalaBrandt8 form's neighbour table and constants from the caller's tables (rr: triangulation_neighbours_refusal's answer)
+static int kb8_neighbour_tables(orbm_t *m, int rr, bool rig, int K, const orbm_keyframe_t *k2, const int32_t *n_left2, const float *ep, const float *cams1,
+                                const float *cams2, const float *T12, const uint8_t *skip, std::vector<TriNb> &nb, std::vector<TriKb8Consts> &consts) {
   auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
-  if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
-  const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
-  if (rr < 0) return rr;
-  if (K > 0 && (!matches12 || !nmatches)) return refuse(-1, "NULL result table");
   if (rr == 0 && (!n_left2 || !ep || !cams1 || !cams2 || !T12)) return refuse(-1, "NULL n_left2, epipole, camera or pose table");
-  std::vector<TriNb> nb((size_t)K);
-  std::vector<TriKb8Consts> consts((size_t)K);
+  nb.resize((size_t)K);
+  consts.resize((size_t)K);
   if (K > 0) { memset(nb.data(), 0, sizeof(TriNb) * (size_t)K); memset(consts.data(), 0, sizeof(TriKb8Consts) * (size_t)K); }
   for (int j = 0; j < K && rr == 0; j++) {
     if (skip && skip[j]) continue;
@@ -3209,7 +3283,147 @@ int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_
     memcpy(C.cams1, cams1, sizeof(float) * (rig ? 16 : 8));
     memcpy(C.cams2, cams2 + 16 * (size_t)j, sizeof(float) * (rig ? 16 : 8));
   }
+  return 0;
+}
+
+int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const int32_t *n_left2,
+                                                 const float *ep, const float *cams1, const float *cams2, const float *T12, const uint8_t *skip,
+                                                 int bOnlyStereo, int bCoarse, int32_t *matches12, int32_t *nmatches) {
+  if (!m || !k1) return ORBX_E_ARG;
+  const bool rig = n_left1 != -1;
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
+  const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
+  if (rr < 0) return rr;
+  if (K > 0 && (!matches12 || !nmatches)) return refuse(-1, "NULL result table");
+  std::vector<TriNb> nb;
+  std::vector<TriKb8Consts> consts;
+  { const int rt = kb8_neighbour_tables(m, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
   return triangulation_neighbours(m, k1, n_left1, K, k2, skip, nb, &consts, bOnlyStereo, bCoarse, matches12, nmatches);
+}
+
+// ---- LocalMapping::CreateNewMapPoints: the searches and the body of the loop (LocalMapping.cc:470-905) -----------------------------
+// A keyframe's constants as the body reads them (csrc/orb_ref_newpoints.h); cams: mvParameters of mpCamera, behind them mpCamera2's
+static void new_point_camera(orbm_new_point_camera_t &c, const orbm_keyframe_t &k, const orbm_keyframe_geometry_t &g, int cam_type, const float *cams,
+                             int n_left) {
+  memset(&c, 0, sizeof(c));
+  const bool rig = n_left != -1;
+  const int np = cam_type == 0 ? 4 : 8;
+  memcpy(c.Tcw[0], g.Tcw, sizeof(c.Tcw[0]));
+  memcpy(c.Ow[0], g.Ow, sizeof(c.Ow[0]));
+  memcpy(c.cam[0], cams, sizeof(float) * (size_t)np);
+  if (rig) {
+    memcpy(c.Tcw[1], g.Tcw_right, sizeof(c.Tcw[1]));
+    memcpy(c.Ow[1], g.Ow_right, sizeof(c.Ow[1]));
+    memcpy(c.cam[1], cams + 8, sizeof(float) * (size_t)np);
+  }
+  if (g.Twc) memcpy(c.Twc, g.Twc, sizeof(c.Twc));
+  c.fx = g.fx; c.fy = g.fy; c.cx = g.cx; c.cy = g.cy; c.invfx = g.invfx; c.invfy = g.invfy; c.mb = g.mb; c.mbf = g.mbf;
+  for (int l = 0; l < k.nlevels && l < ORBX_MAX_LEVELS; l++) { c.sf[l] = k.scale_factors[l]; c.sigma2[l] = k.level_sigma2[l]; }
+  c.cam_type = cam_type; c.n_left = n_left;
+}
+
+static bool fill_new_point_pairs(NewPointPairsParams &P, int n, const orbm_new_point_camera_t *c1, const orbm_new_point_camera_t *c2,
+                                 const orbm_new_point_obs_t *obs1, const orbm_new_point_obs_t *obs2, float scale_factor1, int far_points,
+                                 float th_far_points, uint8_t *status, float *x3D) {
+  if (n < 0 || !c1 || !c2 || (n > 0 && (!obs1 || !obs2 || !status || !x3D))) return false;
+  if (c1->cam_type < 0 || c1->cam_type > 1 || c2->cam_type < 0 || c2->cam_type > 1) return false;
+  P.c1 = *c1; P.c2 = *c2; P.obs1 = obs1; P.obs2 = obs2; P.scale_factor1 = scale_factor1; P.th_far_points = th_far_points;
+  P.far_points = far_points; P.n = n; P.status = status; P.x3d = x3D;
+  return true;
+}
+
+int orbm_new_point_geometry(int n, const orbm_new_point_camera_t *c1, const orbm_new_point_camera_t *c2, const orbm_new_point_obs_t *obs1,
+                            const orbm_new_point_obs_t *obs2, float scale_factor1, int far_points, float th_far_points, uint8_t *status, float *x3D) {
+  NewPointPairsParams P;
+  if (!fill_new_point_pairs(P, n, c1, c2, obs1, obs2, scale_factor1, far_points, th_far_points, status, x3D)) return ORBX_E_ARG;
+  for (int i = 0; i < n; i++)
+    status[i] = (uint8_t)new_point_geometry(P.c1, P.c2, obs1[i], obs2[i], scale_factor1, far_points, th_far_points, x3D + 3 * (size_t)i);
+  return 0;
+}
+
+int orbm_new_point_geometry_device(int n, const orbm_new_point_camera_t *c1, const orbm_new_point_camera_t *c2, const orbm_new_point_obs_t *d_obs1,
+                                   const orbm_new_point_obs_t *d_obs2, float scale_factor1, int far_points, float th_far_points, uint8_t *d_status,
+                                   float *d_x3D, void *stream) {
+  NewPointPairsParams P;
+  if (!fill_new_point_pairs(P, n, c1, c2, d_obs1, d_obs2, scale_factor1, far_points, th_far_points, d_status, d_x3D)) return ORBX_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_new_point_pairs, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
+// What the body needs of keyframe (k, g) beyond the search's arrays, or NULL
+static const char *new_points_keyframe_refusal(const orbm_keyframe_t &k, const orbm_keyframe_geometry_t &g, bool rig) {
+  if (!g.Tcw || !g.Ow || (rig && (!g.Tcw_right || !g.Ow_right))) return "NULL pose";
+  if (!rig && (!g.depth || !g.keys || !g.Twc))
+    for (int i = 0; i < k.n; i++)
+      if (k.u_right[i] >= 0) return "NULL mvDepth, mvKeys or Twc";
+  return nullptr;
+}
+
+// The refusals the two forms share behind those of the search (rr = triangulation_neighbours_refusal's answer) and the empty outputs
+static int new_points_refusal(orbm_t *m, int rr, const orbm_keyframe_t *k1, const orbm_keyframe_geometry_t *g1, bool rig, int K,
+                              const orbm_keyframe_t *k2, const orbm_keyframe_geometry_t *g2, const uint8_t *skip, orbm_new_point_t *points, int cap,
+                              uint8_t *status, int32_t *matches12, int32_t *nmatches) {
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (cap < 0 || (cap > 0 && !points)) return refuse(-1, "NULL point list or cap < 0");
+  if (nmatches && !matches12) return refuse(-1, "nmatches without matches12");
+  if (rr == 0) {
+    if (!g1 || !g2) return refuse(-1, "NULL keyframe geometry table");
+    if (const char *why = new_points_keyframe_refusal(*k1, *g1, rig)) return refuse(-1, (std::string("kf1: ") + why).c_str());
+    for (int j = 0; j < K; j++)
+      if (!(skip && skip[j]))
+        if (const char *why = new_points_keyframe_refusal(k2[j], g2[j], rig)) return refuse(j, why);
+  }
+  if (status && K > 0) memset(status, ORBM_NP_NO_MATCH, (size_t)K * (size_t)k1->n);
+  return 0;
+}
+
+static int new_points_result(const NewPointsCall &np, orbm_new_point_t *points, int cap) {
+  const size_t count = np.list.size();
+  if (count <= (size_t)cap && count) memcpy(points, np.list.data(), sizeof(orbm_new_point_t) * count);
+  return (int)count;
+}
+
+int orbm_create_new_map_points(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_geometry_t *g1, float scale_factor1, int K,
+                               const orbm_keyframe_t *k2, const orbm_keyframe_geometry_t *g2, const float *R1w, const float *t1w, const float *Cw1,
+                               const float *cam1, const float *R2w, const float *t2w, const float *cam2, const uint8_t *skip, int bCoarse,
+                               int far_points, float th_far_points, orbm_new_point_t *points, int cap, uint8_t *status, int32_t *matches12,
+                               int32_t *nmatches) {
+  if (!m || !k1) return ORBX_E_ARG;
+  const int rr = triangulation_neighbours_refusal(m, k1, false, false, K, k2, skip);
+  if (rr < 0) return rr;
+  if (rr == 0 && (!R1w || !t1w || !Cw1 || !cam1 || !R2w || !t2w || !cam2)) { m->err = "NULL pose or camera table"; return ORBX_E_ARG; }
+  if (rr == 0 && (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS)) { m->err = "kf1: nlevels out of range"; return ORBX_E_ARG; }
+  if (rr == 0)   // the body reads kf1's scale tables, which Pinhole's search does not
+    if (const char *why = tri_keyframe_refusal(k1, false, true)) { m->err = std::string("kf1: ") + why; return ORBX_E_ARG; }
+  { const int rn = new_points_refusal(m, rr, k1, g1, false, K, k2, g2, skip, points, cap, status, matches12, nmatches); if (rn < 0) return rn; }
+  std::vector<TriNb> nb((size_t)K);
+  if (K > 0) memset(nb.data(), 0, sizeof(TriNb) * (size_t)K);
+  for (int j = 0; j < K && rr == 0; j++)
+    if (!(skip && skip[j])) pinhole_pair_geometry(R1w, t1w, R2w + 9 * j, t2w + 3 * j, Cw1, cam1, cam2 + 4 * j, nb[(size_t)j].F12, nb[(size_t)j].epx, nb[(size_t)j].epy);
+  NewPointsCall np{g1, g2, 0, cam1, cam2, 4, nullptr, scale_factor1, th_far_points, far_points, status, {}};
+  const int rc = triangulation_neighbours(m, k1, -1, K, k2, skip, nb, nullptr, 0, bCoarse, matches12, nmatches, &np);
+  return rc < 0 ? rc : new_points_result(np, points, cap);
+}
+
+int orbm_create_new_map_points_kb8(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_geometry_t *g1, float scale_factor1, int n_left1, int K,
+                                   const orbm_keyframe_t *k2, const orbm_keyframe_geometry_t *g2, const int32_t *n_left2, const float *ep,
+                                   const float *cams1, const float *cams2, const float *T12, const uint8_t *skip, int bCoarse, int far_points,
+                                   float th_far_points, orbm_new_point_t *points, int cap, uint8_t *status, int32_t *matches12, int32_t *nmatches) {
+  if (!m || !k1) return ORBX_E_ARG;
+  const bool rig = n_left1 != -1;
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
+  const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
+  if (rr < 0) return rr;
+  std::vector<TriNb> nb;
+  std::vector<TriKb8Consts> consts;
+  { const int rt = kb8_neighbour_tables(m, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
+  { const int rn = new_points_refusal(m, rr, k1, g1, rig, K, k2, g2, skip, points, cap, status, matches12, nmatches); if (rn < 0) return rn; }
+  NewPointsCall np{g1, g2, 1, cams1, cams2, 16, n_left2, scale_factor1, th_far_points, far_points, status, {}};
+  const int rc = triangulation_neighbours(m, k1, n_left1, K, k2, skip, nb, &consts, 0, bCoarse, matches12, nmatches, &np);
+  return rc < 0 ? rc : new_points_result(np, points, cap);
 }
 
 int orbm_search_for_initialization(orbm_t *m, const orbm_frame_t *f1, const orbm_frame_t *f2, float *prev_matched, int window_size,

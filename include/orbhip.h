@@ -831,6 +831,112 @@ int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_
                                                  const float *T12 /*[K][4][12]*/, const uint8_t *skip, int bOnlyStereo, int bCoarse,
                                                  int32_t *matches12, int32_t *nmatches);
 
+/* ---- LocalMapping::CreateNewMapPoints (LocalMapping.cc:470-905): the searches above AND the geometric body of the loop ----
+ * The body of the loop over the matched pairs (:605-880: rays and parallax, cv::SVD triangulation or KeyFrame::UnprojectStereo, two
+ * depth tests, two chi-square reprojection tests, the far-point and scale-consistency tests) is stated once for host and device
+ * (csrc/orb_ref_newpoints.h) and returns one of the codes below; every `continue` of :605-880 has its own value. */
+enum {
+  ORBM_NP_NO_MATCH = 0,        /* matches12[j][idx1] < 0: the pair does not exist */
+  ORBM_NP_ACCEPTED = 1,        /* :883 reached */
+  ORBM_NP_LOW_PARALLAX = 2,    /* :782  no stereo and very low parallax */
+  ORBM_NP_ZERO_W = 3,          /* :763  the homogeneous coordinate of vt.row(3) is 0 */
+  ORBM_NP_EMPTY_STEREO = 4,    /* :788  UnprojectStereo returned the empty matrix (mvDepth <= 0) */
+  ORBM_NP_BEHIND1 = 5,         /* :793  z1 <= 0 */
+  ORBM_NP_BEHIND2 = 6,         /* :797  z2 <= 0 */
+  ORBM_NP_REPROJ1 = 7,         /* :814  monocular reprojection error in the new keyframe */
+  ORBM_NP_REPROJ1_STEREO = 8,  /* :827  stereo reprojection error in the new keyframe */
+  ORBM_NP_REPROJ2 = 9,         /* :842  monocular reprojection error in the neighbour */
+  ORBM_NP_REPROJ2_STEREO = 10, /* :853  stereo reprojection error in the neighbour */
+  ORBM_NP_ZERO_DIST = 11,      /* :866  dist1 == 0 || dist2 == 0 */
+  ORBM_NP_FAR = 12,            /* :869  mbFarPoints and a distance >= mThFarPoints */
+  ORBM_NP_SCALE = 13,          /* :879  ratioDist against ratioOctave */
+  ORBM_NP_NSTATUS = 14
+};
+
+/* One new map point: MapPoint(x3D, mpCurrentKeyFrame, map) observed by keypoint idx1 of the new keyframe and idx2 of kf2[neighbour] */
+typedef struct { int32_t neighbour, idx1, idx2; float x3D[3]; } orbm_new_point_t;
+
+/* What the body reads of a keyframe beyond orbm_keyframe_t (host pointers).  Poses are 12 floats with row stride 4. */
+typedef struct {
+  const float *Tcw;        /* [Rcw | tcw] = GetRotation() | GetTranslation() = rows 0..2 of GetPose() */
+  const float *Ow;         /* GetCameraCenter() [3] */
+  const float *Tcw_right;  /* rigs: rows 0..2 of GetRightPose(); NULL otherwise */
+  const float *Ow_right;   /* rigs: GetRightCameraCenter() [3]; NULL otherwise */
+  const float *Twc;        /* rows 0..2 of Twc (UnprojectStereo); may be NULL when no keypoint has u_right >= 0 */
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  const float *depth;      /* mvDepth [n]; may be NULL when no keypoint has u_right >= 0 */
+  const orbx_keypoint_t *keys;   /* mvKeys [n] (UnprojectStereo reads mvKeys, not mvKeysUn); NULL as for depth */
+} orbm_keyframe_geometry_t;
+
+/* The body alone, over arrays of pairs, for inspection and tests.  The keyframe's constants by value and one record per keypoint:
+ *   cam[0] / cam[1] = mvParameters of mpCamera / mpCamera2 ({fx, fy, cx, cy} Pinhole, {fx, fy, cx, cy, k0..k3} KannalaBrandt8);
+ *   Tcw[1] / Ow[1] the right camera's of a rig; n_left = NLeft (-1: no second camera, then bStereo = u_right >= 0);
+ *   sf / sigma2 = mvScaleFactors / mvLevelSigma2; an octave is taken modulo ORBX_MAX_LEVELS.
+ *   obs: x, y, octave of the keypoint the reference picks (:613-626: mvKeysUn, or mvKeys / mvKeysRight of a rig), u_right = mvuRight,
+ *   depth = mvDepth, key_x / key_y = mvKeys[idx].pt, right = idx >= NLeft of a rig. */
+typedef struct {
+  float Tcw[2][12], Ow[2][3], Twc[12], cam[2][8];
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  float sf[ORBX_MAX_LEVELS], sigma2[ORBX_MAX_LEVELS];
+  int32_t cam_type;   /* 0 Pinhole, 1 KannalaBrandt8 */
+  int32_t n_left;
+} orbm_new_point_camera_t;
+typedef struct { float x, y; int32_t octave; float u_right, depth, key_x, key_y; int32_t right; } orbm_new_point_obs_t;
+
+/* status[i] = ORBM_NP_* of pair i of (c1, c2): obs1[i] of the new keyframe, obs2[i] of the neighbour; x3D [n][3] is written where the
+ * status is ORBM_NP_ACCEPTED.  scale_factor1 = mpCurrentKeyFrame->mfScaleFactor (ratioFactor = 1.5f * it, :521), far_points /
+ * th_far_points = mbFarPoints / mThFarPoints.  No GPU call; the device form takes device arrays for obs / status / x3D (c1, c2 stay
+ * host structs) and is asynchronous on `stream`.  0, ORBX_E_ARG (a NULL pointer, n < 0, cam_type outside {0, 1}) or ORBX_E_HIP. */
+int orbm_new_point_geometry(int n, const orbm_new_point_camera_t *c1, const orbm_new_point_camera_t *c2, const orbm_new_point_obs_t *obs1,
+                            const orbm_new_point_obs_t *obs2, float scale_factor1, int far_points, float th_far_points, uint8_t *status,
+                            float *x3D);
+int orbm_new_point_geometry_device(int n, const orbm_new_point_camera_t *c1, const orbm_new_point_camera_t *c2,
+                                   const orbm_new_point_obs_t *d_obs1, const orbm_new_point_obs_t *d_obs2, float scale_factor1,
+                                   int far_points, float th_far_points, uint8_t *d_status, float *d_x3D, void *stream);
+
+/* New keyframe plus neighbours in, the list of new map points out: the one-call searches above (bOnlyStereo = 0 as at the call site,
+ * LocalMapping.cc:583), then the body on every matched pair ON THE DEVICE, reading the rows the search just wrote there; one upload,
+ * one synchronisation, and a download of the list (plus what the caller asks for).
+ *
+ * The SEQUENTIAL RULE, next to the MASKING RULE above.  The reference's loop creates a point for (j, idx1) exactly when
+ *   (a) the body accepts the pair (idx1, matches12[j][idx1]) of the row computed from the state at loop entry, and
+ *   (b) no neighbour j' < j that is not skipped has an accepted pair for the same idx1.
+ * Argument:
+ *   - a keypoint idx1 of the new keyframe is masked only by mpCurrentKeyFrame->AddMapPoint(pMP, idx1) (LocalMapping.cc:892);
+ *   - that line is reached only when the body accepted the pair (every test in front of it ends in `continue`);
+ *   - row j (MASKING RULE) and the geometry of a pair depend on nothing else the loop changes: the poses, cameras, keypoints, depths
+ *     and scale tables of both keyframes are read-only in the loop, and pKF2->AddMapPoint (:893) touches neighbour j after its search;
+ *   - so idx1 is free in iteration j exactly when no earlier iteration accepted it, and then the loop sees the loop-entry pair.
+ * Hence the list = { (j, idx1) : status[j][idx1] == ORBM_NP_ACCEPTED and j is the smallest such neighbour of idx1 }, in the loop's
+ * creation order: j ascending, idx1 ascending (vMatchedIndices is ascending in idx1).  An idx1 appears at most once.
+ * Consequence: when CheckNewKeyFrames() ends the loop in front of neighbour i (LocalMapping.cc:528), the caller keeps the entries
+ * with neighbour < i - a prefix of the list, and exactly what the shortened loop would have created, because (b) looks at smaller j only.
+ *
+ * Arguments: those of the search entry of the same form (bOnlyStereo fixed to 0), then g1 / g2 [K] and scale_factor1 =
+ * mpCurrentKeyFrame->mfScaleFactor, far_points / th_far_points.  Pinhole form: mono and rectified-stereo keypoints mix per keypoint;
+ * cam1 / cam2[j] are also the parameters of pCamera1 / pCamera2.  KannalaBrandt8 form: cams1 / cams2[j] likewise; for rigs g->Tcw_right
+ * and g->Ow_right are read and u_right / depth / keys are not.
+ * Out: points [cap] in creation order, the count is returned; a list longer than cap returns the needed count and writes no point
+ * (an idx1 appears once, so cap = kf1->n always suffices).  Optional (NULL: not downloaded): status [K][kf1->n] = ORBM_NP_* of the
+ * loop-entry pair, NOT masked by (b); matches12 [K][kf1->n] and nmatches [K] as in the search entry (nmatches needs matches12).
+ * skip, K == 0, kf1->n == 0: as in the search entries - an empty list (status 0, rows -1), the device untouched.
+ * ORBX_E_ARG, orbm_last_error naming the neighbour where there is one, for whatever the search entry refuses, and for
+ *   - a NULL g1, g2 (K > 0 and a neighbour searched), points with cap > 0, cap < 0, nmatches without matches12;
+ *   - a NULL Tcw or Ow, for rigs a NULL Tcw_right or Ow_right ("neighbour <j>: NULL pose");
+ *   - a NULL depth, keys or Twc of a keyframe that has a keypoint with u_right >= 0 ("neighbour <j>: NULL mvDepth, mvKeys or Twc"). */
+int orbm_create_new_map_points(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_geometry_t *g1, float scale_factor1, int K,
+                               const orbm_keyframe_t *kf2 /*[K]*/, const orbm_keyframe_geometry_t *g2 /*[K]*/, const float *R1w,
+                               const float *t1w, const float *Cw1, const float *cam1, const float *R2w /*[K][9]*/,
+                               const float *t2w /*[K][3]*/, const float *cam2 /*[K][4]*/, const uint8_t *skip /*[K] or NULL*/, int bCoarse,
+                               int far_points, float th_far_points, orbm_new_point_t *points, int cap, uint8_t *status /*[K][kf1->n] or NULL*/,
+                               int32_t *matches12 /*[K][kf1->n] or NULL*/, int32_t *nmatches /*[K] or NULL*/);
+int orbm_create_new_map_points_kb8(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_geometry_t *g1, float scale_factor1,
+                                   int n_left1, int K, const orbm_keyframe_t *kf2 /*[K]*/, const orbm_keyframe_geometry_t *g2 /*[K]*/,
+                                   const int32_t *n_left2 /*[K]*/, const float *ep /*[K][2]*/, const float *cams1,
+                                   const float *cams2 /*[K][2][8]*/, const float *T12 /*[K][4][12]*/, const uint8_t *skip, int bCoarse,
+                                   int far_points, float th_far_points, orbm_new_point_t *points, int cap, uint8_t *status,
+                                   int32_t *matches12, int32_t *nmatches);
+
 /* int ORBmatcher::SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched,
  *                                         vector<int> &vnMatches12, int windowSize)              (ORBmatcher.cc:722-837)
  * f1 / f2: mvKeysUn + mDescriptors of the two frames (f2 with its image bounds; u_right unused); prev_matched[2*n1]
