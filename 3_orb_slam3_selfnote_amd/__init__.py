@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -48,6 +48,12 @@ ABI_SYMBOLS = [
 class FrameStruct(C.Structure):  # orbm_frame_t
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("descriptors", C.c_void_p), ("u_right", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
+    _fields_ = [("kf", FrameStruct), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
+                ("log_scale_factor", C.c_float), ("Tcw", C.c_void_p), ("Ow", C.c_void_p), ("cam_type", C.c_int32), ("cam_params", C.c_void_p),
+                ("bf", C.c_float)]
 
 
 class KeyFrameStruct(C.Structure):  # orbm_keyframe_t
@@ -200,6 +206,7 @@ def load(build_if_needed=True):
     L.orbm_stereo_fisheye_matches.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_search_for_initialization.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp]
     L.orbm_fuse.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, vp, vp]
+    L.orbm_fuse_keyframes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
     L.orbm_fuse_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
     L.orbm_fuse_sim3_cam.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp]
     L.orbm_search_by_projection_sim3_cam.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, vp, vp]
@@ -537,6 +544,23 @@ class KeyFrameView:
     def struct(self):
         return KeyFrameStruct(self.N, _p(self.keys_un), _p(self.descriptors), _p(self.u_right), _p(self.has_mappoint), len(self.node_id),
                               _p(self.node_id), _p(self.node_start), _p(self.node_idx), _p(self.sf), _p(self.sigma2), len(self.sf))
+
+
+class FuseTarget:
+    """One target keyframe of ORBmatcher.FuseKeyFrames (orbm_fuse_target_t): what ORBmatcher.Fuse takes of a keyframe.  KF: FrameView of
+    the keyframe (for a rig the raw keypoints and descriptor rows of one image); Tcw row-major 4x4, the right camera's for bRight."""
+
+    def __init__(self, KF, scale_factors, inv_level_sigma2, log_scale_factor, Tcw, Ow, cam_type, cam_params, bf):
+        a = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+        self.KF = KF
+        self.sf, self.inv_sigma2 = a(scale_factors), a(inv_level_sigma2)
+        self.log_sf = float(log_scale_factor)
+        self.Tcw, self.Ow, self.cam = a(Tcw), a(Ow), a(cam_params)
+        self.cam_type, self.bf = int(cam_type), float(bf)
+
+    def struct(self):
+        return FuseTargetStruct(self.KF.struct(), _p(self.sf), _p(self.inv_sigma2), len(self.sf), C.c_float(self.log_sf), _p(self.Tcw), _p(self.Ow),
+                                self.cam_type, _p(self.cam), C.c_float(self.bf))
 
 
 class KeyFrameGeometry:
@@ -901,6 +925,25 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_fuse rc=%d" % rc)
         return rc, bi[:n], bd[:n]
+
+    def FuseKeyFrames(self, targets, valid, Xw, normal, mpdesc, max_dist, min_dist, th=3.0):
+        """The search part of every Fuse call of LocalMapping::SearchInNeighbors' loop (LocalMapping.cc:989-1000) in one call: one list of
+        map points against all targets (FuseTarget).  valid: [T, nP], row t as Fuse's valid for target t.
+        Returns (total, best_idx [T, nP], best_dist [T, nP], nfused [T]); row t is what Fuse returns for target t (FUSE RULE, orbhip.h)."""
+        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
+        T = len(targets)
+        Xw, normal, mpdesc = a(Xw, np.float32), a(normal, np.float32), a(mpdesc, np.uint8)
+        max_dist, min_dist = a(max_dist, np.float32), a(min_dist, np.float32)
+        n = len(max_dist)
+        valid = a(valid, np.uint8).reshape(T, n)
+        bi, bd, nf = np.full((T, n), -1, np.int32), np.full((T, n), 256, np.int32), np.zeros(T, np.int32)
+        tab = (FuseTargetStruct * max(T, 1))(*[t.struct() for t in targets])
+        rc = self.L.orbm_fuse_keyframes(self.m, T, C.cast(tab, C.c_void_p), n, _p(valid), _p(Xw), _p(normal), _p(mpdesc), _p(max_dist), _p(min_dist),
+                                        C.c_float(th), _p(bi), _p(bd), _p(nf))
+        self._check(rc, "orbm_fuse_keyframes")
+        if rc < 0:
+            raise OrbError("orbm_fuse_keyframes rc=%d" % rc)
+        return rc, bi, bd, nf
 
     def FuseSim3(self, KF, scale_factors, log_scale_factor, valid, Xw, normal, mp_desc, max_dist, min_dist, Scw, cam, th=4.0, cam_type=0):
         """Search part of Fuse(KeyFrame *pKF, cv::Mat Scw, vpPoints, th, vpReplacePoint) -- ORBmatcher.cc:1660-1786."""

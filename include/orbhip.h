@@ -689,6 +689,68 @@ int orbm_fuse_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const float *scale_fac
                        const float *min_dist, const float *Scw, int cam_type, const float *cam_params, float th, int32_t *best_idx,
                        int32_t *best_dist);
 
+/* ---- LocalMapping::SearchInNeighbors (LocalMapping.cc:909-1058): ONE list of map points fused into ALL target keyframes per call ----
+ * The reference calls ORBmatcher::Fuse(pKFi, vpMapPointMatches) once per target keyframe (:989-1000; a rig keyframe twice, the second
+ * time with bRight = true), always with the same points, and then once in the other direction (:1033-1035).  orbm_fuse_keyframes is
+ * the search part of all those calls: the point arrays are uploaded once, the T keyframes and the valid table in the same block, one
+ * kernel (k_fuse_keyframes: gates, window, chi-square gate and Hamming search on the device), one download of the two tables, one
+ * synchronisation.
+ *
+ * One target = what orbm_fuse takes of a keyframe. */
+typedef struct {
+  orbm_frame_t kf;                 /* what the search reads of the keyframe: mvKeysUn / mDescriptors / mvuRight / bounds; for a rig the raw
+                                      keypoints and descriptor rows of ONE image (mvKeys, or mvKeysRight with the rows behind NLeft) */
+  const float *scale_factors;      /* mvScaleFactors [nlevels] */
+  const float *inv_level_sigma2;   /* mvInvLevelSigma2 [nlevels] */
+  int32_t nlevels;                 /* [1, ORBX_MAX_LEVELS] */
+  float log_scale_factor;
+  const float *Tcw;                /* row-major 4x4; the right camera's pose for bRight */
+  const float *Ow;                 /* [3] */
+  int32_t cam_type; const float *cam_params;   /* as in orbm_project; mpCamera2's for bRight */
+  float bf;
+} orbm_fuse_target_t;
+
+/* valid [T][nP]: row t = valid of orbm_fuse for target t (pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF_t)); Xw, normal, mpdesc,
+ * max_dist, min_dist [nP] and th as in orbm_fuse.  Out: best_idx / best_dist [T][nP], nfused [T].
+ * Row t is bit for bit what orbm_fuse returns for target t with valid + t * nP, nfused[t] is the return value of that call, and the
+ * function returns the sum of nfused.  A right camera of a rig is just another target: the caller adds NLeft to its indices.  Targets
+ * may differ in keypoint count, image bounds, camera model, nlevels and scale tables.  A target with kf.n == 0, or a valid row of
+ * zeros, gives a row of -1 / 256.  T == 0 or nP == 0 returns 0 and does not touch the device.
+ * ORBX_E_ARG, with orbm_last_error naming the target ("target <t>: ...") where there is one, for:
+ *   - whatever orbm_fuse refuses (a NULL handle, table, array or result pointer, nP < 0, kf.n < 0, NULL keypoints or descriptors);
+ *   - T < 0, or a NULL target table with T > 0;
+ *   - kf.n above ORBM_MAX_KEYPOINTS; empty bounds (also where kf.n == 0: the record's grid constants divide by their extent);
+ *   - nlevels outside [1, 16]; a keypoint octave outside [0, nlevels), because the kernel indexes device tables with it;
+ *   - a cam_type other than 0 or 1.
+ *
+ * Why the T searches may leave the reference's loop although its body (ORBmatcher.cc:1622-1645) changes map points between them - the
+ * FUSE RULE, next to the MASKING RULE and the SEQUENTIAL RULE below:
+ *   - Read-only keyframe inputs.  The search reads of a keyframe only keypoints, descriptors, mvuRight, pose, camera and scale tables;
+ *     all of these are read-only in the loop.  The search is claimless: a keypoint that has received a map point stays a candidate
+ *     (:1622-1640 look at pKF->GetMapPoint(bestIdx) only after the search), so different points never see one another inside a target.
+ *   - What the search reads of a point: isBad(), IsInKeyFrame(pKF), world position, normal, the two distances and the descriptor.
+ *   - What the loop body changes: it calls MapPoint::Replace (MapPoint.cc:249-301) or AddObservation (+ KeyFrame::AddMapPoint).
+ *     Neither changes position, normal or distances.  AddObservation changes only the observations.  Replace makes the loser bad for
+ *     good and only ADDS observations to the survivor; it calls the survivor's ComputeDistinctiveDescriptors(), which can change its
+ *     descriptor.  The survivor can be the searched point or the keyframe's own point; in the second case it can sit elsewhere in
+ *     the list, so the caller tests by content (GetDescriptor() against the uploaded bytes), not by index.
+ *   - Validity only shrinks: a bad point stays bad, a point in pKF stays in pKF, so live validity is always a subset of validity at
+ *     loop entry.
+ *   - The rule.  The sequential result for (t, i) is entry (t, i) of the tables computed from the state at loop entry, used under the
+ *     reference's own live test (!isBad() && !IsInKeyFrame(pKF_t)).  The exception is a point whose GetDescriptor() now differs from
+ *     the 32 bytes that were uploaded: for those points alone the caller repeats the search of target t, with orbm_fuse on the subset,
+ *     at the start of iteration t.  That is early enough, because iteration t itself cannot dirty a point that is still valid for t:
+ *     a survivor is in pKF_t afterwards.
+ *   - Rigs.  The two targets of one rig keyframe are consecutive; between them the same test applies (the right call's IsInKeyFrame
+ *     sees what the left call added).
+ *   - How large the dirty fraction is on real sequences is NOT KNOWN here: no sequence was run.  Every dirty point costs one entry of a
+ *     per-target orbm_fuse call on the subset; a loop in which most points turn dirty gains nothing over the per-target calls.
+ * tests/test_fuse_keyframes_abi.py and tests/test_gpu_fuse_keyframes.py replay the sequential loop against this rule. */
+int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets /*[T]*/, int nP,
+                        const uint8_t *valid /*[T][nP]*/, const float *Xw, const float *normal, const uint8_t *mpdesc,
+                        const float *max_dist, const float *min_dist, float th,
+                        int32_t *best_idx /*[T][nP]*/, int32_t *best_dist /*[T][nP]*/, int32_t *nfused /*[T]*/);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12,
  *                              const cv::Mat &R12, const cv::Mat &t12, const float th)           (ORBmatcher.cc:1788-2012)
  * Per keyframe k: kf_k = mvKeysUn / mDescriptors / image bounds, sf_k = mvScaleFactors, log_sf_k = mfLogScaleFactor,
