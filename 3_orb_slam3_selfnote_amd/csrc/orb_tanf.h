@@ -9,11 +9,12 @@
 // in float, and libm has no FMA variant of tanf), so host and gfx950 give the same bits under -ffp-contract=off with the correctly
 // rounded fp32 divide.
 //
-// DOMAIN: |x| < 120, reduce_fast's.  The unprojection's theta starts in [0, pi/2] and moves by Newton steps; tests/test_tanf_replica.py
-// covers [-2, 2].  A finite argument outside the domain gives NaN here (reduce_large is not restated); inf and NaN give NaN as in
-// libm.  glibc 2.41 replaced tanf by a correctly rounded one, and glibc before 2.28 reduced in float: against such a host the
-// replica differs in the last bits for some arguments and the test fails there.  The reference's libm is not pinned (DESIGN.md
-// section 2).
+// DOMAIN: every float.  |x| < 120 is reduce_fast's; beyond it the argument goes through sincosf.h's reduce_large (x times 2/pi in
+// 64-bit integer arithmetic).  The unprojection's theta starts in [0, pi/2] and moves by Newton steps: with a distortion polynomial
+// that turns back below pi/2 the steps diverge, the reference takes tanf of whatever the tenth one left, and so must this
+// (tests/test_ref_cameras.py::test_unproject[distorted]).  inf and NaN give NaN as in libm.  glibc 2.41 replaced tanf by a correctly
+// rounded one, and glibc before 2.28 reduced in float: against such a host the replica differs in the last bits for some arguments
+// and the test fails there.  The reference's libm is not pinned.
 #pragma once
 #include <stdint.h>
 #include "orb_logf.h"   // orblg::fbits / bitsf
@@ -70,6 +71,36 @@ ORBTN_HD float kernel_tanf(float x, float y, int iy) {
   return t + a * (s + t * v);
 }
 
+// sincosf.h:reduce_large for |x| >= 120: the 24 significand bits of x, shifted by the exponent's low three bits, times three
+// consecutive 32-bit words of 2/pi picked by the exponent's next four bits (sincosf_data.c:__inv_pio4 holds the windows of
+// 0xA2F9836E4E441529FC2757D1F534DDC0DB6295993C439041 a byte apart; entry k ends at byte k + 1), keeping the 64 bits below the
+// quadrant count.  Returns the remainder in [-pi/4, pi/4] for |x|, *np = the quadrant.
+ORBTN_HD uint32_t inv_pio4_word(int k) {
+  // bits [s, s + 32) from the left of 0 : H0 : H1 : H2 (64 bits each), s = 8 * (k + 1) + 32
+  const uint64_t H0 = 0xA2F9836E4E441529ull, H1 = 0xFC2757D1F534DDC0ull, H2 = 0xDB6295993C439041ull;
+  const int s = 8 * (k + 1) + 32, i = s >> 6, off = s & 63;
+  const uint64_t hi = i == 0 ? 0ull : i == 1 ? H0 : i == 2 ? H1 : H2;
+  const uint64_t lo = i == 0 ? H0 : i == 1 ? H1 : i == 2 ? H2 : 0ull;
+  const uint64_t v = off ? (hi << off) | (lo >> (64 - off)) : hi;
+  return (uint32_t)(v >> 32);
+}
+ORBTN_HD double reduce_large(uint32_t xi, int32_t *np) {
+  const double pi63 = 0x1.921FB54442D18p-62;   // 2 pi * 2^-64
+  const int k = (int)((xi >> 26) & 15u);
+  const int shift = (int)((xi >> 23) & 7u);
+  xi = (xi & 0xffffffu) | 0x800000u;
+  xi <<= shift;
+  uint64_t res0 = (uint64_t)(uint32_t)(xi * inv_pio4_word(k));
+  const uint64_t res1 = (uint64_t)xi * inv_pio4_word(k + 4);
+  const uint64_t res2 = (uint64_t)xi * inv_pio4_word(k + 8);
+  res0 = (res2 >> 32) | (res0 << 32);
+  res0 += res1;
+  const uint64_t n = (res0 + (1ull << 61)) >> 62;
+  res0 -= n << 62;
+  *np = (int32_t)n;
+  return (double)(int64_t)res0 * pi63;
+}
+
 // s_tanf.c:__tanf; its rem_pio2f is sincosf.h's reduce_fast in double (|x| < 120): n = round(x * 2/pi), dx = x - n * pi/2 by a
 // separate multiply and subtract (tanf has no FMA variant), y0 = (float)dx, y1 = (float)(dx - y0)
 ORBTN_HD float ref_tanf(float x) {
@@ -78,7 +109,14 @@ ORBTN_HD float ref_tanf(float x) {
   const uint32_t ix = orblg::fbits(x) & 0x7fffffffu;
   if (ix <= 0x3f490fdau) return kernel_tanf(x, 0.0f, 1);   // |x| ~< pi/4
   if (ix >= 0x7f800000u) return x - x;                     // inf, nan
-  if (((ix >> 20) & 0x7ffu) >= 0x42fu) return orblg::bitsf(0x7fc00000u);   // |x| >= 120: outside the replica's domain
+  if (((ix >> 20) & 0x7ffu) >= 0x42fu) {   // |x| >= 120: rem_pio2f's other branch, the sign applied to the remainder
+    int32_t n;
+    double dl = reduce_large(orblg::fbits(x), &n);
+    if (orblg::fbits(x) >> 31) dl = -dl;
+    const float l0 = (float)dl;
+    const float l1 = (float)(dl - (double)l0);
+    return kernel_tanf(l0, l1, 1 - ((n & 1) << 1));
+  }
   double dx = (double)x;
   const double r = dx * HPI_INV;
   const int32_t n = ((int32_t)r + 0x800000) >> 24;

@@ -136,7 +136,7 @@ float orbx_ref_logf(float x);
  * (tests/test_gpu_local_points.py compares it with orbx_ref_logf).  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
 int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream);
 /* ... and of glibc's tanf (fdlibm's single-precision kernel behind the double reduction of sinf / cosf, glibc 2.28 - 2.40) that
- * KannalaBrandt8::unproject calls (KannalaBrandt8.cpp:135), csrc/orb_tanf.h, for |x| < 120 (NaN beyond); orbx_tanf_device is the
+ * KannalaBrandt8::unproject calls (KannalaBrandt8.cpp:135), csrc/orb_tanf.h, for every float (the integer reduction from |x| = 120 on); orbx_tanf_device is the
  * device's evaluation, as orbx_logf_device. */
 float orbx_ref_tanf(float x);
 int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream);

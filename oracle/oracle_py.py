@@ -428,6 +428,17 @@ def pinhole_pair_geometry(R1w, t1w, R2w, t2w, Cw1, cam1, cam2):
     return ep, F12
 
 
+def pinhole_F12(R12, t12, cam1, cam2):
+    """F12 = K1.t().inv() * t12x * R12 * K2.inv() (Pinhole.cpp:145-148) as the oracle restates it."""
+    a = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+    R12, t12, cam1, cam2 = a(R12), a(t12), a(cam1), a(cam2)
+    F12 = np.zeros(9, np.float32)
+    L = lib()
+    L.orc_pinhole_F12.argtypes = [C.c_void_p] * 5
+    L.orc_pinhole_F12(_p(R12), _p(t12), _p(cam1), _p(cam2), _p(F12))
+    return F12
+
+
 def pinhole_epipolar_constrain(F12, x1, y1, x2, y2, unc):
     """Pinhole::epipolarConstrain (Pinhole.cpp:150-164) for one pair."""
     L = lib()
@@ -650,6 +661,8 @@ def bench_stream(ex, frames, offs, count, threads=1, warmup=50, lap=(0, 1000), c
 _REF_DIR = os.path.join(_HERE, "_ref")
 _REF_LIB = os.path.join(_REF_DIR, "libref_extractor.so")
 _REF_SOURCES = ("ref_driver.cc", "ref_extractor.map", os.path.join("ref_shim", "opencv", "cv.h"), "orb_oracle.h", "Makefile")
+_REF_CAM_LIB = os.path.join(_REF_DIR, "libref_cameras.so")
+_REF_CAM_LIB_CMATH = os.path.join(_REF_DIR, "libref_cameras_cmath.so")
 _ref_lib = None
 
 
@@ -660,8 +673,8 @@ def reference_tree():
 
 
 def build_ref(force=False):
-    """Build oracle/_ref/libref_extractor.so where the reference tree exists; elsewhere an already built library is used as it is.
-    Returns the library's path, or None when there is neither."""
+    """Build oracle/_ref/libref_extractor.so (and the camera libraries beside it, ref_cam_lib) where the reference tree exists; elsewhere
+    what is already built is used as it is.  Returns the extractor library's path, or None when there is neither."""
     tree = reference_tree()
     if tree is not None:
         build()
@@ -669,6 +682,9 @@ def build_ref(force=False):
             os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_REF_LIB) for f in _REF_SOURCES + ("liborb_oracle.so",))
         if stale and os.path.exists(_REF_LIB):
             os.remove(_REF_LIB)   # not `make -B`: that would also rebuild liborb_oracle.so, which may be loaded
+        for f in (_REF_CAM_LIB, _REF_CAM_LIB_CMATH):   # the camera libraries: make knows what they depend on
+            if force and os.path.exists(f):
+                os.remove(f)
         subprocess.check_call(["make", "-C", _HERE, "-s", "ref", "ORB_REFERENCE=" + tree])
     return _REF_LIB if os.path.exists(_REF_LIB) else None
 
@@ -770,3 +786,87 @@ def ref_distribute_octtree(xyr, minX, maxX, minY, maxY, N):
     if m == -3:
         raise RuntimeError("ref_distribute_octtree: the reference threw a C++ exception")
     return out[:m].copy()
+
+
+# --- the reference's own CameraModels/Pinhole.cpp and KannalaBrandt8.cpp, compiled (oracle/Makefile `ref`, oracle/ref_cam_driver.cc) -
+_ref_cam_libs = {}
+TRIANGULATE_EXITS = ("parallax", "z1", "z2", "reproj1", "reproj2", "accept")   # exit_code of ref_triangulate_matches, in this order
+
+
+def ref_cam_lib(build_if_possible=True, cmath=False):
+    """libref_cameras.so, loaded.  build_if_possible=False never looks at the reference tree: what is under oracle/_ref/ is loaded as
+    it is.  cmath=True: the second build of the same text with <cmath> in place of <math.h> (one CPU test tells the two apart)."""
+    if cmath not in _ref_cam_libs:
+        path = _REF_CAM_LIB_CMATH if cmath else _REF_CAM_LIB
+        if build_if_possible:
+            build_ref()
+        if not os.path.exists(path):
+            raise RuntimeError("oracle/_ref/%s is missing and there is no reference tree to build it from: "
+                               "run __graft_entry__.build() where the reference exists" % os.path.basename(path))
+        L = C.CDLL(path)
+        L.refcam_project.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.refcam_unproject.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.refcam_kb8_triangulate_matches.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
+        L.refcam_epipolar_constrain.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
+        L.refcam_svd.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
+        assert L.refcam_cmath_build() == int(bool(cmath))
+        _ref_cam_libs[cmath] = L
+    return _ref_cam_libs[cmath]
+
+
+def _f(x, shape=(-1,)):
+    return np.ascontiguousarray(x, dtype=np.float32).reshape(shape)
+
+
+def _cam_ok(rc, what):
+    if rc != 0:
+        raise RuntimeError("%s rc=%d" % (what, rc))
+
+
+def ref_project(cam_type, params, xyz, L=None):
+    """The compiled Pinhole::project / KannalaBrandt8::project(cv::Point3f) of xyz [n, 3]: uv [n, 2]."""
+    xyz = _f(xyz, (-1, 3))
+    uv = np.zeros((len(xyz), 2), np.float32)
+    _cam_ok((L or ref_cam_lib()).refcam_project(int(cam_type), _p(_f(params)), len(xyz), _p(xyz), _p(uv)), "refcam_project")
+    return uv
+
+
+def ref_unproject(cam_type, params, xy, L=None):
+    """The compiled unproject of the pixels xy [n, 2]: rays [n, 3]."""
+    xy = _f(xy, (-1, 2))
+    rays = np.zeros((len(xy), 3), np.float32)
+    _cam_ok((L or ref_cam_lib()).refcam_unproject(int(cam_type), _p(_f(params)), len(xy), _p(xy), _p(rays)), "refcam_unproject")
+    return rays
+
+
+def ref_triangulate_matches(cam1, cam2, Tlr, kp1, kp2, sigma1, sigma2, p3d_fill=0.0, L=None):
+    """The compiled KannalaBrandt8::TriangulateMatches with R12 | t12 = Tlr: (depth [n], p3D [n, 3] with p3d_fill where the member
+    returns early, exit [n] as indices into TRIANGULATE_EXITS)."""
+    kp1, kp2 = _f(kp1, (-1, 2)), _f(kp2, (-1, 2))
+    n = len(kp1)
+    depth, p3d, code = np.zeros(n, np.float32), np.full((n, 3), p3d_fill, np.float32), np.zeros(n, np.uint8)
+    s1, s2 = _f(sigma1), _f(sigma2)
+    assert len(kp2) == n and len(s1) == n and len(s2) == n
+    _cam_ok((L or ref_cam_lib()).refcam_kb8_triangulate_matches(_p(_f(cam1)), _p(_f(cam2)), _p(_f(Tlr)), n, _p(kp1), _p(kp2), _p(s1), _p(s2), _p(depth),
+                                                                 _p(p3d), _p(code)), "refcam_kb8_triangulate_matches")
+    return depth, p3d, code
+
+
+def ref_epipolar_constrain(cam_type, cam1, cam2, R12, t12, kp1, kp2, sigma, unc, L=None):
+    """The compiled epipolarConstrain of the pairs kp1 / kp2 [n, 2] with one R12 / t12: verdicts [n] bool."""
+    kp1, kp2 = _f(kp1, (-1, 2)), _f(kp2, (-1, 2))
+    n = len(kp1)
+    sigma, unc = np.broadcast_to(_f(sigma), (n,)).copy(), np.broadcast_to(_f(unc), (n,)).copy()
+    out = np.zeros(n, np.uint8)
+    _cam_ok((L or ref_cam_lib()).refcam_epipolar_constrain(int(cam_type), _p(_f(cam1)), _p(_f(cam2)), _p(_f(R12)), _p(_f(t12)), n, _p(kp1), _p(kp2),
+                                                            _p(sigma), _p(unc), _p(out)), "refcam_epipolar_constrain")
+    return out.astype(bool)
+
+
+def ref_svd(A, L=None):
+    """The stand-in's cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV): (w, u, vt)."""
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    m, n = A.shape
+    w, u, vt = np.zeros(min(m, n), np.float32), np.zeros((m, m), np.float32), np.zeros((n, n), np.float32)
+    _cam_ok((L or ref_cam_lib()).refcam_svd(m, n, _p(A), _p(w), _p(u), _p(vt)), "refcam_svd")
+    return w, u, vt

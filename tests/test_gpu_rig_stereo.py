@@ -32,8 +32,9 @@ def test_tanf_device_equals_host(pkg):
     import torch
     bits = lambda x: int(np.array([x], f32).view(np.uint32)[0])
     hpi = np.pi / 2
-    pats = [np.arange(0, bits(2.0) + 1, 19997, dtype=np.uint32)]
-    for p in (np.pi / 4, 3 * np.pi / 4, hpi, 0.6744, hpi - 0.6744, hpi + 0.6744, 2.0 ** -13, hpi - 2.0 ** -13, 2.0, 119.0):
+    pats = [np.arange(0, bits(2.0) + 1, 19997, dtype=np.uint32), np.arange(bits(120.0), 0x7f800000, 39989, dtype=np.uint32)]
+    for p in (np.pi / 4, 3 * np.pi / 4, hpi, 0.6744, hpi - 0.6744, hpi + 0.6744, 2.0 ** -13, hpi - 2.0 ** -13, 2.0, 119.0, 120.0, 811.62, 1e6, 1e20,
+              3.0e38):                                      # from 120 on the reduction is the integer one
         pats.append(np.arange(bits(p) - 4096, bits(p) + 4097, dtype=np.uint32))
     pats = np.concatenate(pats)
     pats = np.concatenate([pats, pats | np.uint32(0x80000000), np.array([0, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 1, 0x42f00000], np.uint32)])
