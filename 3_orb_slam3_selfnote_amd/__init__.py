@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "orbx_get_scale_tables", "orbx_get_features_per_level", "orbx_configure", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_get_host_us", "orbx_level_info", "orbx_download_level", "orbx_download_pyramid", "orbx_download_blurred_level",
     "orbx_download_candidates", "orbx_download_level_keypoints", "orbx_set_profiling", "orbx_get_stage_ms",
-    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_ref_tanf", "orbx_tanf_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
+    "orbx_ref_cosf", "orbx_ref_sinf", "orbx_ref_atanf", "orbx_ref_atan2f", "orbx_ref_logf", "orbx_logf_device", "orbx_ref_tanf", "orbx_tanf_device", "orbx_cosf_device", "orbx_sinf_device", "orbx_atanf_device", "orbx_atan2f_device", "orbx_fast_atan2_device", "orbx_compute_stereo_matches", "orbx_compute_stereo_matches_batch_device", "orbx_stereo_from_rgbd_batch_device", "orbx_close_points_batch_device", "orbx_cvt_color_gray", "orbx_cvt_color_gray_device",
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
@@ -183,6 +183,8 @@ def load(build_if_needed=True):
     L.orbx_ref_tanf.restype = f32
     L.orbx_ref_tanf.argtypes = [f32]
     L.orbx_tanf_device.argtypes = [vp, i32, vp, vp]
+    L.orbx_cosf_device.argtypes = L.orbx_sinf_device.argtypes = L.orbx_atanf_device.argtypes = [vp, i32, vp, vp]
+    L.orbx_atan2f_device.argtypes = L.orbx_fast_atan2_device.argtypes = [vp, vp, i32, vp, vp]
     L.orbm_create.restype = vp
     L.orbm_create.argtypes = [i32]
     L.orbm_destroy.argtypes = [vp]

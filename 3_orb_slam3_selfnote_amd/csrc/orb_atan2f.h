@@ -9,6 +9,10 @@
 // contracted (-ffp-contract=off, correctly rounded fp32 division).
 // tests/test_libm_replicas.py checks the replica against the host libm: atanf over every float (ORB_EXHAUSTIVE=1) or a
 // strided sample, atan2f on the quadrant / zero / infinity cases and on random pairs.
+// tests/test_gpu_libm_device.py runs the DEVICE build (orbx_atanf_device / orbx_atan2f_device) over the input sets of
+// tests/libm_device_cases.py -- for atan2f also the exponent gaps around the |k| > 60 branches, denormal and vanishing quotients y / x,
+// denormal pairs and the camera's own arguments -- against this host build and the host libm, bit for bit;
+// tests/test_libm_device_cases.py checks the host build against the host libm on the same sets.
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -1320,6 +1320,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
 // (:1159-1180).  One wavefront per keypoint: 749-pixel disc split over 64 lanes and reduced with shuffles;
 // 256 binary tests = 4 rounds of 64 lanes, each round packed with one 64-bit ballot (= 8 descriptor bytes).
 // ------------------------------------------------------------------------------------------------------------
+// Device only: orbx_fast_atan2_device evaluates it for tests/test_gpu_libm_device.py, against the oracle's restatement.
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {  // cv::fastAtan2, SURVEY.md A.6
   const float scale = (float)(180.0 / 3.1415926535897932384626433832795);
   const float p1 = 0.9997878412794807f * scale, p3 = -0.3258083974640975f * scale;

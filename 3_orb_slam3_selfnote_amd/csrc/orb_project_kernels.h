@@ -358,13 +358,6 @@ __global__ __launch_bounds__(256) void k_rig_slot_convert(RigSlotParams S) {
   }
 }
 
-// The device build of the logf replica on n floats (orbx_logf_device): lets the tests compare it with the host build, which
-// tests/test_logf_replica.py compares with the host libm.
-__global__ __launch_bounds__(256) void k_ref_logf(const float *x, int n, float *y) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) y[i] = orblg::ref_logf(x[i]);
-}
-
 struct RotPruneParams {
   const float *last_kp;  // query side: angle of LastFrame.mvKeysUn[i] (word 3 of 7)
   int last_stride; LiveCount last_n;

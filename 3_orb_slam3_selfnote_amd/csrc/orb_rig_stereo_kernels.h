@@ -88,13 +88,8 @@ __global__ __launch_bounds__(256) void k_rig_stereo_triangulate(RigStereoParams 
   }
 }
 
-// The device builds of the restated arithmetic on n items (orbx_tanf_device, orbm_fisheye_triangulate_device): the tests compare
-// them with the host builds, which the CPU tests compare with the host libm and with the numpy model.
-__global__ __launch_bounds__(256) void k_ref_tanf(const float *x, int n, float *y) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) y[i] = orbtn::ref_tanf(x[i]);
-}
-
+// The device build of the restated arithmetic on n items (orbm_fisheye_triangulate_device): the tests compare it with the host build,
+// which the CPU tests compare with the numpy model.
 struct TriangulateParams {
   const float *kp1, *kp2, *sigma1, *sigma2;   // [n][2], [n][2], [n], [n]
   float Tlr[12], Tcw2[12], cam1[8], cam2[8];

@@ -10,6 +10,10 @@
 // tests/test_sincos.py checks the replica against the host libm (exhaustively over all 1 086 953 884 floats in
 // [0, 6.3] when run with ORB_EXHAUSTIVE=1; a strided sample otherwise).  Only |x| < 120 is supported -- the
 // extractor only ever passes angles in [0, 2*pi].
+// tests/test_gpu_libm_device.py runs the DEVICE build (orbx_cosf_device / orbx_sinf_device) over the input set of
+// tests/libm_device_cases.py -- [-3.2, 6.3] strided, +-4096 ulps around k*pi/4 and both top12 thresholds, +-0, denormals,
+// the extractor's own angles -- against this host build and the host libm, bit for bit; tests/test_libm_device_cases.py
+// checks the host build against the host libm on the same set.
 #pragma once
 #include <stdint.h>
 #include <string.h>

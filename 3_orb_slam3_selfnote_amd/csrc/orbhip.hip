@@ -181,6 +181,30 @@ static hipError_t raise_lds_limits(int device) {
   return hipSuccess;
 }
 
+// The device builds of the scalar replicas on n items (orbx_logf_device, orbx_tanf_device, orbx_cosf_device .. orbx_fast_atan2_device):
+// out[i] = F()(in[i]...), where each functor calls the inline function the production kernels call.  tests/test_gpu_libm_device.py
+// (logf: tests/test_gpu_local_points.py, tanf: tests/test_gpu_rig_stereo.py) compares the results with the host builds, with the host
+// libm and with the oracle's fastAtan2.
+struct EvalCosf { __device__ float operator()(float x) const { return orbsc::ref_cosf(x); } };
+struct EvalSinf { __device__ float operator()(float x) const { return orbsc::ref_sinf(x); } };
+struct EvalAtanf { __device__ float operator()(float x) const { return orbat::ref_atanf(x); } };
+struct EvalLogf { __device__ float operator()(float x) const { return orblg::ref_logf(x); } };
+struct EvalTanf { __device__ float operator()(float x) const { return orbtn::ref_tanf(x); } };
+struct EvalAtan2f { __device__ float operator()(float y, float x) const { return orbat::ref_atan2f(y, x); } };
+struct EvalFastAtan2 { __device__ float operator()(float y, float x) const { return fast_atan2_deg(y, x); } };
+template <class F, class... In>
+__global__ __launch_bounds__(256) void k_eval(uint32_t n, float *out, In... in) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) out[i] = F()(in[i]...);
+}
+template <class F, class... In>
+static int eval_device(int n, float *d_out, void *stream, In... d_in) {
+  if (n < 0 || (n > 0 && (!d_out || (!d_in || ...)))) return ORBX_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL((k_eval<F, In...>), dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, d_out, d_in...);
+  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+}
+
 extern "C" {
 
 float orbx_ref_cosf(float x) { return orbsc::ref_cosf(x); }
@@ -189,17 +213,16 @@ float orbx_ref_atanf(float x) { return orbat::ref_atanf(x); }
 float orbx_ref_atan2f(float y, float x) { return orbat::ref_atan2f(y, x); }
 float orbx_ref_logf(float x) { return orblg::ref_logf(x); }
 float orbx_ref_tanf(float x) { return orbtn::ref_tanf(x); }
-int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream) {
-  if (n < 0 || (n > 0 && (!d_x || !d_y))) return ORBX_E_ARG;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_ref_tanf, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, n, d_y);
-  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream) { return eval_device<EvalTanf>(n, d_y, stream, d_x); }
+int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream) { return eval_device<EvalLogf>(n, d_y, stream, d_x); }
+int orbx_cosf_device(const float *d_x, int n, float *d_y, void *stream) { return eval_device<EvalCosf>(n, d_y, stream, d_x); }
+int orbx_sinf_device(const float *d_x, int n, float *d_y, void *stream) { return eval_device<EvalSinf>(n, d_y, stream, d_x); }
+int orbx_atanf_device(const float *d_x, int n, float *d_y, void *stream) { return eval_device<EvalAtanf>(n, d_y, stream, d_x); }
+int orbx_atan2f_device(const float *d_yin, const float *d_xin, int n, float *d_out, void *stream) {
+  return eval_device<EvalAtan2f>(n, d_out, stream, d_yin, d_xin);
 }
-int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream) {
-  if (n < 0 || (n > 0 && (!d_x || !d_y))) return ORBX_E_ARG;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_ref_logf, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, n, d_y);
-  return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
+int orbx_fast_atan2_device(const float *d_yin, const float *d_xin, int n, float *d_out, void *stream) {
+  return eval_device<EvalFastAtan2>(n, d_out, stream, d_yin, d_xin);
 }
 
 orbx_t *orbx_create(int nfeatures, float scaleFactor_, int nlevels, int iniThFAST, int minThFAST, int device) {

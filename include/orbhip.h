@@ -140,6 +140,16 @@ int orbx_logf_device(const float *d_x, int n, float *d_y, void *stream);
  * device's evaluation, as orbx_logf_device. */
 float orbx_ref_tanf(float x);
 int orbx_tanf_device(const float *d_x, int n, float *d_y, void *stream);
+/* The other scalar functions the kernels restate, evaluated by the DEVICE with the contract of orbx_logf_device: cosf / sinf
+ * (csrc/orb_sincos.h, |x| < 120), atanf / atan2f (csrc/orb_atan2f.h; d_out[i] = atan2f(d_yin[i], d_xin[i])) and the kernels' cv::fastAtan2
+ * (fast_atan2_deg of csrc/orb_kernels.h, degrees in [0, 360]; it has no host build).  Each launches one elementwise kernel that calls the
+ * inline function the production kernels call; tests/test_gpu_libm_device.py compares the results with orbx_ref_*, with the host
+ * glibc and with the oracle's fastAtan2 on the input sets of tests/libm_device_cases.py. */
+int orbx_cosf_device(const float *d_x, int n, float *d_y, void *stream);
+int orbx_sinf_device(const float *d_x, int n, float *d_y, void *stream);
+int orbx_atanf_device(const float *d_x, int n, float *d_y, void *stream);
+int orbx_atan2f_device(const float *d_yin, const float *d_xin, int n, float *d_out, void *stream);
+int orbx_fast_atan2_device(const float *d_yin, const float *d_xin, int n, float *d_out, void *stream);
 
 /* cv::cvtColor(im, gray, CV_RGB2GRAY | CV_BGR2GRAY | CV_RGBA2GRAY | CV_BGRA2GRAY) of Tracking::GrabImageMonocular / Stereo / RGBD
  * (Tracking.cc:1122-1135) for 8-bit input: channels = 3 or 4, rgb_order != 0 for RGB(A), 0 for BGR(A).

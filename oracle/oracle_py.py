@@ -570,6 +570,30 @@ def project(cam_type, params, X, Y, Z):
     return u.value, v.value
 
 
+def apply_unary(fn, x):
+    """fn(x[i]) for every element of a float32 array, natively (orc_apply_unary).  fn is a float (*)(float) of any loaded library:
+    lib().orc_libm_cosf, the product's orbx_ref_cosf, ..."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    L = lib()
+    L.orc_apply_unary.restype = None
+    L.orc_apply_unary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.orc_apply_unary(C.cast(fn, C.c_void_p), _p(x), _p(y), x.size)
+    return y
+
+
+def apply_binary(fn, a, b):
+    """fn(a[i], b[i]) for two float32 arrays of one length (orc_apply_binary): orc_libm_atan2f, orbx_ref_atan2f, orc_fast_atan2."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    assert a.shape == b.shape
+    out = np.empty_like(a)
+    L = lib()
+    L.orc_apply_binary.restype = None
+    L.orc_apply_binary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.orc_apply_binary(C.cast(fn, C.c_void_p), _p(a), _p(b), _p(out), a.size)
+    return out
+
+
 def three_maxima(sizes):
     sizes = np.ascontiguousarray(sizes, dtype=np.int32)
     i1, i2, i3 = C.c_int(), C.c_int(), C.c_int()

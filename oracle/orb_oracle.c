@@ -68,6 +68,15 @@ long orc_sweep_atan2f(float (*replica)(float, float), uint64_t seed, long n, flo
   return bad;
 }
 
+/* A function pointer applied to whole arrays, for tests/test_libm_device_cases.py and tests/test_gpu_libm_device.py: the same two
+ * helpers run this host's libm (orc_libm_*), the product's host evaluations (orbx_ref_*) and orc_fast_atan2 over millions of inputs. */
+void orc_apply_unary(float (*f)(float), const float *x, float *y, long n) {
+  for (long i = 0; i < n; i++) y[i] = f(x[i]);
+}
+void orc_apply_binary(float (*f)(float, float), const float *a, const float *b, float *out, long n) {
+  for (long i = 0; i < n; i++) out[i] = f(a[i], b[i]);
+}
+
 static const int8_t kPattern[1024] = {
 #include "../include/orb_pattern_data.inc"
 };

@@ -100,6 +100,9 @@ float orc_libm_atan2f(float y, float x);
 /* Sweeps of a replica (function pointer) against this host's libm; see orb_oracle.c.  Return the mismatch count. */
 long orc_sweep_unary(float (*replica)(float), int which, uint32_t lo, uint32_t hi, uint32_t step, int both_signs);
 long orc_sweep_atan2f(float (*replica)(float, float), uint64_t seed, long n, float scale);
+/* y[i] = f(x[i]) and out[i] = f(a[i], b[i]) for i < n: any of orc_libm_*, the product's orbx_ref_* or orc_fast_atan2 over an array. */
+void orc_apply_unary(float (*f)(float), const float *x, float *y, long n);
+void orc_apply_binary(float (*f)(float, float), const float *a, const float *b, float *out, long n);
 
 /* --- matcher ---------------------------------------------------------------------- */
 /* ORBmatcher::DescriptorDistance, ORBmatcher.cc:2463-2483. */
