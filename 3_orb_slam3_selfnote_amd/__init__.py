@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -218,6 +218,8 @@ def load(build_if_needed=True):
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, f32, i32, vp]
     L.orbm_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, f32, i32, vp]
     L.orbm_search_by_bow_keyframes.argtypes = [vp, vp, vp, f32, i32, vp]
+    L.orbm_search_by_bow_candidates.argtypes = [vp, i32, vp, vp, i32, vp, f32, i32, vp, vp]
+    L.orbm_search_by_bow_keyframes_candidates.argtypes = [vp, vp, i32, vp, vp, f32, i32, vp, vp]
     L.orbm_hamming_matrix.argtypes = [vp, vp, i32, vp, i32, vp]
     L.orbm_search_for_triangulation.argtypes = [vp] * 10 + [i32, i32, i32, vp]
     L.orbm_triangulation_candidates.argtypes = [vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, i32]
@@ -909,6 +911,42 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_search_by_bow_keyframes rc=%d" % rc)
         return rc, m[:KF1.N]
+
+    def _bow_candidates(self, what, call, K, n, skip):
+        """The outputs of a one-call SearchByBoW: call(skip, rows, nmatches) -> rc.  Returns (nmatches [K], rows [K, n])."""
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        if sk is not None and len(sk) != K:
+            raise ValueError("%s: skip needs one entry per candidate" % what)
+        rows, nm = np.full(max(K * n, 1), -1, dtype=np.int32), np.zeros(max(K, 1), np.int32)
+        rc = call(_p(sk) if sk is not None and len(sk) else None, _p(rows), _p(nm))
+        self._check(rc, what)
+        if rc < 0:
+            raise OrbError("%s rc=%d" % (what, rc))
+        assert rc == int(nm[:K].sum())
+        return nm[:K].copy(), rows[:K * n].reshape(K, n)
+
+    def SearchByBoWCandidates(self, KFs, F, n_left=None, skip=None):
+        """SearchByBoW(pKF, F, vpMapPointMatches) of all K candidate keyframes KFs against ONE frame F in one call
+        (orbm_search_by_bow_candidates; the loop of Tracking::Relocalization, Tracking.cc:3796-3816).  n_left: Frame::Nleft of a
+        fisheye-stereo frame (F = mvKeys ++ mvKeysRight); skip [K] marks the candidates that are isBad().
+        Returns (nmatches [K], matchF [K, F.N]): row j = what SearchByBoW(KFs[j], F, n_left) returns."""
+        K = len(KFs)
+        fs = F.struct()
+        tab, ptab = self._keyframe_table(KFs)
+        call = lambda sk, rows, nm: self.L.orbm_search_by_bow_candidates(self.m, K, ptab, C.byref(fs), -1 if n_left is None else int(n_left), sk,
+                                                                         C.c_float(self.mfNNratio), int(self.mbCheckOrientation), rows, nm)
+        return self._bow_candidates("orbm_search_by_bow_candidates", call, K, F.N, skip)
+
+    def SearchByBoWKeyFramesCandidates(self, KF1, KF2s, skip=None):
+        """SearchByBoW(pKF1, pKF2, vpMatches12) of ONE keyframe KF1 against all K keyframes KF2s in one call
+        (orbm_search_by_bow_keyframes_candidates; the loop of LoopClosing::DetectCommonRegionsFromBoW, LoopClosing.cc:724-739).
+        Returns (nmatches [K], matches12 [K, KF1.N]): row j = what SearchByBoWKeyFrames(KF1, KF2s[j]) returns."""
+        K = len(KF2s)
+        s1 = KF1.struct()
+        tab, ptab = self._keyframe_table(KF2s)
+        call = lambda sk, rows, nm: self.L.orbm_search_by_bow_keyframes_candidates(self.m, C.byref(s1), K, ptab, sk, C.c_float(self.mfNNratio),
+                                                                                   int(self.mbCheckOrientation), rows, nm)
+        return self._bow_candidates("orbm_search_by_bow_keyframes_candidates", call, K, KF1.N, skip)
 
     def Fuse(self, KF, scale_factors, inv_level_sigma2, log_scale_factor, valid, Xw, normal, mp_desc, max_dist, min_dist, Tcw, Ow,
              cam_type, cam_params, bf, th=3.0):

@@ -29,6 +29,7 @@
 #include "orb_rig_stereo_kernels.h"
 #include "orb_newpoints_kernels.h"
 #include "orb_fuse_kernels.h"
+#include "orb_bow_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -1245,6 +1246,9 @@ struct orbm_handle {
   DevBuf d_knn;       // the two nearest right rows of every left lapping row (orbm_stereo_fisheye_matches*)
   DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
+  std::vector<BowCandItem> bow_items;   // host side of the one-call SearchByBoW, kept between calls (capacity only grows)
+  std::vector<BowCand> bow_cands;
+  std::vector<float> bow_ang;
   int tri_layout = 0;       // item order of the one-call triangulation searches: 0 neighbour-major (the merge walks' order), 1 KF1-keypoint-major (ORBM_TRI_LAYOUT, measurements only)
   bool profiling = false;
   hipEvent_t ev[PROF_DEPTH][3] = {};
@@ -3836,6 +3840,146 @@ int orbm_search_by_bow_fisheye(orbm_t *m, const orbm_keyframe_t *kf, const orbm_
 int orbm_search_by_bow_keyframes(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_t *kf2, float nnratio, int checkOri,
                                  int32_t *matches12) {
   return bow_core(m, kf1, kf2, nnratio, checkOri, true, -1, matches12);
+}
+
+// ---- SearchByBoW of one frame or keyframe against K candidates in one call (Tracking.cc:3796-3816, LoopClosing.cc:724-739) ----------
+// Shared by the two entries.  `fixed` is the operand every pair has: the frame (the SECOND operand of each pair, kf_kf false) or pKF1
+// (the FIRST, kf_kf true); W / S below are a pair's walked and second operand as in bow_core.  Everything is validated before the
+// outputs or the device are touched; then ONE staged block (the fixed operand once, the arrays of every candidate that shares a node,
+// the records, the items), one fill of the rows, k_bow_match_candidates, k_bow_prune_candidates, one download of rows + counts.
+static int bow_candidates(orbm_t *m, const orbm_keyframe_t *fixed, int K, const orbm_keyframe_t *cands, const uint8_t *skip, bool kf_kf,
+                          int nleftF, float nnratio, int checkOri, int32_t *rows, int32_t *nmatches) {
+  if (!m || !fixed) return ORBX_E_ARG;
+  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "candidate " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  if (K < 0) return refuse(-1, "K < 0");
+  if (K > 0 && (!cands || !rows || !nmatches)) return refuse(-1, "NULL candidate or result table");
+  if (fixed->n < 0) return refuse(-1, "fixed operand: n < 0");
+  if (nleftF < -1 || nleftF > fixed->n) return refuse(-1, "n_left_f outside [-1, f->n]");
+  const size_t nout = (size_t)fixed->n;
+  std::vector<BowCandItem> &items = m->bow_items;
+  std::vector<uint8_t> live((size_t)K, 0);
+  items.clear();
+  size_t nang = (size_t)fixed->n;
+  for (int j = 0; j < K; j++) {
+    if (skip && skip[j]) continue;                                 // isBad(): Tracking.cc:3799-3800, LoopClosing.cc:726-727
+    const orbm_keyframe_t *c = &cands[j], *W = kf_kf ? fixed : c, *S = kf_kf ? c : fixed;
+    if (c->n < 0) return refuse(j, "n < 0");
+    if (W->n == 0 || S->n == 0 || W->n_nodes <= 0 || S->n_nodes <= 0) continue;
+    if (!W->descriptors || !S->descriptors || !W->has_mappoint || !W->node_id || !S->node_id || !W->node_start || !S->node_start ||
+        !W->node_idx || !S->node_idx || !W->keys_un || !S->keys_un || (kf_kf && !S->has_mappoint)) return refuse(j, "NULL array");
+    for (const orbm_keyframe_t *k : {W, S}) {                      // the kernels index device memory with these
+      if (k->node_start[0] < 0) return refuse(j, "feature vector: node_start negative");
+      for (int f = 0; f < k->n_nodes; f++)
+        if (k->node_start[f + 1] < k->node_start[f]) return refuse(j, "feature vector: node_start decreases");
+    }
+    const size_t before = items.size();
+    int a = 0, b = 0;                                              // the merge walk of bow_core (:292-296, :440-447)
+    while (a < W->n_nodes && b < S->n_nodes) {
+      if (W->node_id[a] == S->node_id[b]) {
+        const int sw = W->node_start[a], ss = S->node_start[b], lw = W->node_start[a + 1] - sw, ls = S->node_start[b + 1] - ss;
+        if (ls > 2048) return refuse(j, "SearchByBoW: more than 2048 keypoints of the second operand in one vocabulary node");
+        if (lw > 0 && ls > 0) {
+          for (int i = 0; i < lw; i++)
+            if (W->node_idx[sw + i] < 0 || W->node_idx[sw + i] >= W->n) return refuse(j, "feature vector: keypoint index out of range");
+          for (int i = 0; i < ls; i++)
+            if (S->node_idx[ss + i] < 0 || S->node_idx[ss + i] >= S->n) return refuse(j, "feature vector: keypoint index out of range");
+          items.push_back(BowCandItem{j, sw, lw, ss, ls, {0, 0, 0}});
+        }
+        a++; b++;
+      } else if (W->node_id[a] < S->node_id[b]) {
+        while (a < W->n_nodes && W->node_id[a] < S->node_id[b]) a++;   // lower_bound
+      } else {
+        while (b < S->n_nodes && S->node_id[b] < W->node_id[a]) b++;
+      }
+    }
+    if (items.size() > 0x7fffffffu) return refuse(-1, "more than 2^31 - 1 shared vocabulary nodes over all candidates");
+    live[(size_t)j] = items.size() > before;
+    if (live[(size_t)j]) nang += (size_t)c->n;
+  }
+  for (size_t i = 0; i < (size_t)K * nout; i++) rows[i] = -1;      // :277 / :852
+  for (int j = 0; j < K; j++) nmatches[j] = 0;
+  if (items.empty()) return 0;
+  const size_t ni = items.size();
+  // keypoint angles for the rotation histogram, packed out of mvKeysUn
+  std::vector<float> &ang = m->bow_ang;
+  ang.resize(checkOri ? nang : 0);
+  size_t ang_at = 0;
+  auto pack_angles = [&](const orbm_keyframe_t &k) -> const float * {
+    if (!checkOri) return nullptr;
+    float *p = ang.data() + ang_at;
+    for (int i = 0; i < k.n; i++) p[i] = k.keys_un[i].angle;
+    ang_at += (size_t)k.n;
+    return p;
+  };
+  std::vector<BowCand> &rec = m->bow_cands;
+  rec.resize((size_t)K);
+  memset(rec.data(), 0, sizeof(BowCand) * (size_t)K);
+  std::vector<Part> parts;
+  std::vector<size_t> offs;
+  parts.reserve(8 + 4 * (size_t)K);
+  size_t off = 0;
+  auto add = [&](const void *src, size_t bytes) { parts.push_back(Part{src, bytes}); offs.push_back(off); off += stage_span(bytes); return parts.size() - 1; };
+  const size_t nf = (size_t)fixed->n;
+  const bool fixed_hasmp = kf_kf;                                  // the frame's map points are not read (:273-469)
+  const size_t F_DESC = add(fixed->descriptors, 32 * nf), F_HASMP = add(fixed_hasmp ? fixed->has_mappoint : nullptr, fixed_hasmp ? nf : 0);
+  const size_t F_IDX = add(fixed->node_idx, sizeof(int32_t) * (size_t)fixed->node_start[fixed->n_nodes]);
+  const size_t F_ANG = add(pack_angles(*fixed), checkOri ? sizeof(float) * nf : 0);
+  for (int j = 0; j < K; j++) {
+    if (!live[(size_t)j]) continue;
+    const orbm_keyframe_t &c = cands[j];
+    const size_t nc = (size_t)c.n;
+    const size_t desc = offs[add(c.descriptors, 32 * nc)], hasmp = offs[add(c.has_mappoint, nc)];
+    const size_t idx = offs[add(c.node_idx, sizeof(int32_t) * (size_t)c.node_start[c.n_nodes])];
+    const size_t an = offs[add(pack_angles(c), checkOri ? sizeof(float) * nc : 0)];
+    BowCand &R = rec[(size_t)j];
+    if (kf_kf) {
+      R.descW = offs[F_DESC]; R.hasmpW = offs[F_HASMP]; R.node_idxW = offs[F_IDX]; R.angW = offs[F_ANG];
+      R.descS = desc; R.hasmpS = hasmp; R.node_idxS = idx; R.angS = an;
+    } else {
+      R.descW = desc; R.hasmpW = hasmp; R.node_idxW = idx; R.angW = an;
+      R.descS = offs[F_DESC]; R.hasmpS = BOW_NO_HASMP; R.node_idxS = offs[F_IDX]; R.angS = offs[F_ANG];
+    }
+    R.n_left = nleftF >= 0 ? nleftF : 0x7fffffff;
+  }
+  const size_t RECS = add(rec.data(), sizeof(BowCand) * (size_t)K), ITEMS = add(items.data(), sizeof(BowCandItem) * ni);
+  const size_t rows_bytes = sizeof(int32_t) * (size_t)K * nout;
+  const size_t ROWS = add(nullptr, rows_bytes), COUNTS = add(nullptr, sizeof(int32_t) * (size_t)K);
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  std::vector<void *> d(parts.size());
+  { const int rs = stage(m, s, parts.data(), parts.size(), d.data(), true); if (rs < 0) return rs; }
+  const uint8_t *block = (const uint8_t *)m->d_block.p;
+  for (size_t i = 0; i < parts.size(); i++)   // the records' offsets were formed here, stage() formed the addresses: they must agree
+    if (d[i] && d[i] != block + offs[i]) { m->err = "SearchByBoW candidates: staging layout"; return ORBX_E_HIP; }
+  MCHECK(m, hipMemsetAsync(d[ROWS], 0xff, rows_bytes, s));
+  BowCandParams B;
+  memset(&B, 0, sizeof(B));
+  B.block = block; B.cands = (const BowCand *)d[RECS]; B.items = (const BowCandItem *)d[ITEMS]; B.nitems = (int)ni;
+  B.nout = fixed->n; B.nnratio = nnratio; B.kf_kf = kf_kf ? 1 : 0; B.checkOri = checkOri ? 1 : 0;
+  B.rows = (int32_t *)d[ROWS]; B.nmatches = (int32_t *)d[COUNTS];
+  hipLaunchKernelGGL(k_bow_match_candidates, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, B);
+  MCHECK(m, hipGetLastError());
+  hipLaunchKernelGGL(k_bow_prune_candidates, dim3((unsigned)K), dim3(256), 0, s, B);
+  MCHECK(m, hipGetLastError());
+  // rows and counts are adjacent parts of the block: one copy into the pinned mirror
+  const size_t out_bytes = offs[COUNTS] + sizeof(int32_t) * (size_t)K - offs[ROWS];
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[ROWS]), d[ROWS], out_bytes, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  memcpy(rows, mirror_of(m, d[ROWS]), rows_bytes);
+  memcpy(nmatches, mirror_of(m, d[COUNTS]), sizeof(int32_t) * (size_t)K);
+  long long sum = 0;
+  for (int j = 0; j < K; j++) sum += nmatches[j];
+  return (int)std::min<long long>(sum, 0x7fffffff);
+}
+
+int orbm_search_by_bow_candidates(orbm_t *m, int K, const orbm_keyframe_t *kf, const orbm_keyframe_t *f, int n_left_f, const uint8_t *skip,
+                                  float nnratio, int checkOri, int32_t *matchF, int32_t *nmatches) {
+  return bow_candidates(m, f, K, kf, skip, false, n_left_f, nnratio, checkOri, matchF, nmatches);
+}
+
+int orbm_search_by_bow_keyframes_candidates(orbm_t *m, const orbm_keyframe_t *kf1, int K, const orbm_keyframe_t *kf2, const uint8_t *skip,
+                                            float nnratio, int checkOri, int32_t *matches12, int32_t *nmatches) {
+  return bow_candidates(m, kf1, K, kf2, skip, true, -1, nnratio, checkOri, matches12, nmatches);
 }
 
 int orbm_distinctive_descriptors(orbm_t *m, int nmp, const int32_t *start, const uint8_t *desc, int32_t *best) {

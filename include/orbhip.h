@@ -1041,6 +1041,54 @@ int orbm_search_by_bow_fisheye(orbm_t *m, const orbm_keyframe_t *kf, const orbm_
 int orbm_search_by_bow_keyframes(orbm_t *m, const orbm_keyframe_t *kf1, const orbm_keyframe_t *kf2, float nnratio, int checkOri,
                                  int32_t *matches12);
 
+/* SearchByBoW of ONE frame or keyframe against ALL candidates in one call: the two loops of the reference that call the members
+ * above once per candidate -
+ *   Tracking::Relocalization (Tracking.cc:3796-3816): matcher.SearchByBoW(pKF, mCurrentFrame, vvpMapPointMatches[i]) per
+ *     relocalisation candidate, for every frame while tracking is lost;
+ *   LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:724-739): matcherBoW.SearchByBoW(mpCurrentKF, vpCovKFi[j],
+ *     vvpMatchedMPs[j]) for a candidate and its best covisibles, per loop and merge candidate.
+ * The fixed operand is staged once, every searched candidate's descriptors, flags and feature-vector members go up in the same block
+ * with a record table and the flat list of (candidate, shared node) items: one upload, one fill of the rows with -1 on the device, one
+ * launch over every item (one wavefront each; the node's first 64 second-operand keypoints are held in registers across the walk, the
+ * walked keypoint comes through the scalar path), one launch that does the rotation histogram per candidate on the device, one download
+ * of the rows and the K counts, one synchronisation.
+ *
+ * Row j of matchF [K][f->n] is bit for bit what orbm_search_by_bow returns for (kf[j], f) with the same nnratio and checkOri - with
+ * n_left_f >= 0 what orbm_search_by_bow_fisheye returns - and nmatches[j] that call's return value.  Row j of matches12 [K][kf1->n] is
+ * bit for bit what orbm_search_by_bow_keyframes returns for (kf1, kf2[j]), rotation-histogram pruning included.
+ * skip[j] != 0 (skip may be NULL) stands for the reference's isBad() `continue` (Tracking.cc:3799-3800, LoopClosing.cc:726-727):
+ * row j is all -1, nmatches[j] = 0, and candidate j is neither validated nor uploaded.
+ * Returns the sum of nmatches.  K == 0, every candidate skipped, an empty fixed operand, no pair that shares a node: 0 without touching
+ * the device, the rows still written as all -1.
+ *
+ * Why the searches may leave the two loops - the INDEPENDENCE RULE:
+ *   - each call writes only its own vpMapPointMatches / vpMatches12, which the member itself starts as all-NULL (ORBmatcher.cc:277,
+ *     ORBmatcher.cc:852) and which is the only result it reads back;
+ *   - beyond that the member reads the operands' map-point tables, descriptors and feature vectors, and no statement of
+ *     Tracking.cc:3796-3816 or LoopClosing.cc:724-739 changes any of them: the bodies only test nmatches, set up a solver, or collect
+ *     the matched points;
+ *   - the isBad() tests inside the member (ORBmatcher.cc:310, :865-870, :896-903) are a snapshot at the call, exactly as the
+ *     has_mappoint arrays of the per-pair entries are;
+ *   - hence row j is the per-pair result from the state at loop entry, with no mask and no replay (unlike the MASKING RULE above,
+ *     nothing between the iterations feeds the next search).
+ *
+ * ORBX_E_HIP, or ORBX_E_ARG with orbm_last_error naming the candidate ("candidate <j>: ...") where there is one, for:
+ *   - whatever the per-pair entry refuses, per searched candidate: n < 0, a NULL array of a pair in which both sides have keypoints and
+ *     nodes, a shared node of the second operand with more than 2048 members;
+ *   - a node_start that is negative or decreases, a node_idx outside [0, n) in a shared node (the kernels index device memory with them);
+ *   - K < 0, a NULL table with K > 0, n_left_f outside [-1, f->n], more than 2^31 - 1 items.
+ * Every candidate is validated before the first device call: nothing is launched and no output is written when an argument is refused. */
+
+/* Tracking::Relocalization, Tracking.cc:3796-3816: K candidate keyframes against ONE frame */
+int orbm_search_by_bow_candidates(orbm_t *m, int K, const orbm_keyframe_t *kf /*[K]*/, const orbm_keyframe_t *f,
+                                  int n_left_f /* -1: Frame::Nleft == -1 */, const uint8_t *skip /*[K] or NULL*/,
+                                  float nnratio, int checkOri, int32_t *matchF /*[K][f->n]*/, int32_t *nmatches /*[K]*/);
+
+/* LoopClosing::DetectCommonRegionsFromBoW, LoopClosing.cc:724-739: ONE keyframe against K keyframes */
+int orbm_search_by_bow_keyframes_candidates(orbm_t *m, const orbm_keyframe_t *kf1, int K, const orbm_keyframe_t *kf2 /*[K]*/,
+                                            const uint8_t *skip /*[K] or NULL*/, float nnratio, int checkOri,
+                                            int32_t *matches12 /*[K][kf1->n]*/, int32_t *nmatches /*[K]*/);
+
 /* void MapPoint::ComputeDistinctiveDescriptors()  (MapPoint.cc:350-436), batched over map points: the descriptors that
  * observe map point p are desc[32*start[p] .. 32*start[p+1]) in the order the reference collects them (observations map
  * order, left index before right index); best[p] (out) = BestIdx within that group (-1 for an empty group), i.e.
