@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -54,6 +54,11 @@ class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
     _fields_ = [("kf", FrameStruct), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
                 ("log_scale_factor", C.c_float), ("Tcw", C.c_void_p), ("Ow", C.c_void_p), ("cam_type", C.c_int32), ("cam_params", C.c_void_p),
                 ("bf", C.c_float)]
+
+
+class FuseSim3TargetStruct(C.Structure):  # orbm_fuse_sim3_target_t
+    _fields_ = [("kf", FrameStruct), ("scale_factors", C.c_void_p), ("nlevels", C.c_int32), ("log_scale_factor", C.c_float),
+                ("Scw", C.c_void_p), ("cam_type", C.c_int32), ("cam_params", C.c_void_p)]
 
 
 class KeyFrameStruct(C.Structure):  # orbm_keyframe_t
@@ -209,6 +214,7 @@ def load(build_if_needed=True):
     L.orbm_search_for_initialization.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp]
     L.orbm_fuse.argtypes = [vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, vp, vp]
     L.orbm_fuse_keyframes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
+    L.orbm_fuse_sim3_keyframes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
     L.orbm_fuse_sim3.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
     L.orbm_fuse_sim3_cam.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, vp]
     L.orbm_search_by_projection_sim3_cam.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, vp, vp]
@@ -565,6 +571,22 @@ class FuseTarget:
     def struct(self):
         return FuseTargetStruct(self.KF.struct(), _p(self.sf), _p(self.inv_sigma2), len(self.sf), C.c_float(self.log_sf), _p(self.Tcw), _p(self.Ow),
                                 self.cam_type, _p(self.cam), C.c_float(self.bf))
+
+
+class FuseSim3Target:
+    """One corrected keyframe of ORBmatcher.FuseSim3KeyFrames (orbm_fuse_sim3_target_t): what ORBmatcher.FuseSim3 takes of a keyframe.
+    Scw row-major 4x4 Sim3, or the pose for the SearchAndFuse overload that passes GetPose()."""
+
+    def __init__(self, KF, scale_factors, log_scale_factor, Scw, cam_type, cam_params):
+        a = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+        self.KF = KF
+        self.sf = a(scale_factors)
+        self.log_sf = float(log_scale_factor)
+        self.Scw, self.cam = a(Scw), a(cam_params)
+        self.cam_type = int(cam_type)
+
+    def struct(self):
+        return FuseSim3TargetStruct(self.KF.struct(), _p(self.sf), len(self.sf), C.c_float(self.log_sf), _p(self.Scw), self.cam_type, _p(self.cam))
 
 
 class KeyFrameGeometry:
@@ -1000,6 +1022,25 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_fuse_sim3 rc=%d" % rc)
         return rc, bi[:n], bd[:n]
+
+    def FuseSim3KeyFrames(self, targets, valid, Xw, normal, mpdesc, max_dist, min_dist, th=4.0):
+        """The search part of every Fuse call of LoopClosing::SearchAndFuse's loop (LoopClosing.cc:2631-2707) in one call: one list of map
+        points against all corrected keyframes (FuseSim3Target).  valid: [T, nP], row t as FuseSim3's valid for target t.  Returns
+        (total, best_idx [T, nP], best_dist [T, nP], nfused [T]); row t is what FuseSim3 returns for target t (SEARCH-AND-FUSE RULE, orbhip.h)."""
+        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
+        T = len(targets)
+        Xw, normal, mpdesc = a(Xw, np.float32), a(normal, np.float32), a(mpdesc, np.uint8)
+        max_dist, min_dist = a(max_dist, np.float32), a(min_dist, np.float32)
+        n = len(max_dist)
+        valid = a(valid, np.uint8).reshape(T, n)
+        bi, bd, nf = np.full((T, n), -1, np.int32), np.full((T, n), 256, np.int32), np.zeros(T, np.int32)
+        tab = (FuseSim3TargetStruct * max(T, 1))(*[t.struct() for t in targets])
+        rc = self.L.orbm_fuse_sim3_keyframes(self.m, T, C.cast(tab, C.c_void_p), n, _p(valid), _p(Xw), _p(normal), _p(mpdesc), _p(max_dist),
+                                             _p(min_dist), C.c_float(th), _p(bi), _p(bd), _p(nf))
+        self._check(rc, "orbm_fuse_sim3_keyframes")
+        if rc < 0:
+            raise OrbError("orbm_fuse_sim3_keyframes rc=%d" % rc)
+        return rc, bi, bd, nf
 
     def SearchBySim3(self, KF1, side1, KF2, side2, s12, R12, t12, cam1, th):
         """SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, s12, R12, t12, th) -- ORBmatcher.cc:1788-2012.

@@ -29,6 +29,7 @@
 #include "orb_rig_stereo_kernels.h"
 #include "orb_newpoints_kernels.h"
 #include "orb_fuse_kernels.h"
+#include "orb_fuse_sim3_kernels.h"
 #include "orb_bow_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
@@ -2653,18 +2654,24 @@ int orbm_fuse_sim3_cam(orbm_t *m, const orbm_frame_t *kf, const float *scale_fac
 // ---- SearchInNeighbors (LocalMapping.cc:909-1058): Fuse of one point list into every target keyframe, one call ---------------
 // What orbm_fuse_keyframes refuses about target t, or NULL.  It is what orbm_fuse refuses plus what k_fuse_keyframes relies on: the
 // kernel divides by the bounds' extent and indexes the target's scale tables with PredictScale's level and every keypoint's octave.
-static const char *fuse_target_refusal(const orbm_fuse_target_t &g) {
-  const orbm_frame_t &kf = g.kf;
+// (orbm_fuse_sim3_keyframes: the same set with its own table pointers - no inv_level_sigma2, Scw for Tcw and Ow.)
+static const char *fuse_keyframe_refusal(const orbm_frame_t &kf, int nlevels, int cam_type, bool null_table) {
   if (kf.n < 0) return "n < 0";
   if (kf.n > ORBM_MAX_KEYPOINTS) return "more than 15360 keypoints per frame not supported by the search kernels";
   if (kf.n > 0 && (!kf.keys_un || !kf.descriptors)) return "NULL keypoints or descriptors";
   if (!(kf.max_x > kf.min_x) || !(kf.max_y > kf.min_y)) return "empty image bounds";
-  if (g.nlevels < 1 || g.nlevels > ORBX_MAX_LEVELS) return "nlevels out of range";
-  if (!g.scale_factors || !g.inv_level_sigma2 || !g.Tcw || !g.Ow || !g.cam_params) return "NULL scale table, pose or camera";
-  if (g.cam_type != 0 && g.cam_type != 1) return "cam_type is neither 0 (Pinhole) nor 1 (KannalaBrandt8)";
+  if (nlevels < 1 || nlevels > ORBX_MAX_LEVELS) return "nlevels out of range";
+  if (null_table) return "NULL scale table, pose or camera";
+  if (cam_type != 0 && cam_type != 1) return "cam_type is neither 0 (Pinhole) nor 1 (KannalaBrandt8)";
   for (int i = 0; i < kf.n; i++)
-    if (kf.keys_un[i].octave < 0 || kf.keys_un[i].octave >= g.nlevels) return "keypoint octave outside [0, nlevels)";
+    if (kf.keys_un[i].octave < 0 || kf.keys_un[i].octave >= nlevels) return "keypoint octave outside [0, nlevels)";
   return nullptr;
+}
+static const char *fuse_target_refusal(const orbm_fuse_target_t &g) {
+  return fuse_keyframe_refusal(g.kf, g.nlevels, g.cam_type, !g.scale_factors || !g.inv_level_sigma2 || !g.Tcw || !g.Ow || !g.cam_params);
+}
+static const char *fuse_sim3_target_refusal(const orbm_fuse_sim3_target_t &g) {
+  return fuse_keyframe_refusal(g.kf, g.nlevels, g.cam_type, !g.scale_factors || !g.Scw || !g.cam_params);
 }
 
 int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets, int nP, const uint8_t *valid, const float *Xw, const float *normal,
@@ -2738,6 +2745,89 @@ int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets, int
   for (int t = 0; t < T; t++) {
     int nf = 0;
     for (size_t i = 0; i < NP; i++) nf += best_idx[(size_t)t * NP + i] >= 0 ? 1 : 0;   // bestDist <= TH_LOW, :1622
+    nfused[t] = nf;
+    total += nf;
+  }
+  return total;
+}
+
+// ---- LoopClosing::SearchAndFuse (LoopClosing.cc:2631-2707): the Sim3 Fuse of one point list into every corrected keyframe, one call --
+// orbm_fuse_keyframes' staging with the Sim3 record, the per-target list lengths (zeros, uploaded with the block) and the lists; every
+// Scw is decomposed here as orbm_fuse_sim3_cam decomposes it (double division, camera_centre), so that the kernels' gates start from the
+// same T and Ow.  Two launches (orb_fuse_sim3_kernels.h), one download of both tables, one synchronisation.
+int orbm_fuse_sim3_keyframes(orbm_t *m, int T, const orbm_fuse_sim3_target_t *targets, int nP, const uint8_t *valid, const float *Xw,
+                             const float *normal, const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th,
+                             int32_t *best_idx, int32_t *best_dist, int32_t *nfused) {
+  if (!m) return ORBX_E_ARG;
+  auto refuse = [&](int t, const char *why) { m->err = t < 0 ? std::string(why) : "target " + std::to_string(t) + ": " + why; return ORBX_E_ARG; };
+  if (T < 0 || nP < 0) return refuse(-1, "T < 0 or nP < 0");
+  if (T > 0 && !targets) return refuse(-1, "NULL target table");
+  if (T > 0 && nP > 0 && (!valid || !Xw || !normal || !mpdesc || !max_dist || !min_dist || !best_idx || !best_dist || !nfused))
+    return refuse(-1, "NULL point array or result table");
+  for (int t = 0; t < T; t++)
+    if (const char *why = fuse_sim3_target_refusal(targets[t])) return refuse(t, why);
+  if ((unsigned long long)T * (unsigned long long)nP > 0x7fffffffull) return refuse(-1, "more than 2^31 - 1 (target, point) pairs");
+  if (T == 0 || nP == 0) {   // nothing to search: the device is not touched
+    for (int t = 0; t < T && nfused; t++) nfused[t] = 0;
+    return 0;
+  }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  const size_t NP = (size_t)nP, TP = (size_t)T * NP;
+  // One block, laid out as orbm_fuse_keyframes lays out its own (no mvuRight), with counts and lists in front of the result tables
+  std::vector<FuseSim3Target> rec((size_t)T);
+  std::vector<Part> parts;
+  parts.reserve(12 + 2 * (size_t)T);
+  size_t off = 0;
+  auto add = [&](const void *src, size_t bytes) { const size_t at = off; parts.push_back({src, bytes}); off += stage_span(bytes); return at; };
+  add(valid, TP); add(Xw, sizeof(float) * 3 * NP); add(normal, sizeof(float) * 3 * NP); add(mpdesc, 32 * NP);
+  add(max_dist, sizeof(float) * NP); add(min_dist, sizeof(float) * NP);
+  add(rec.data(), sizeof(FuseSim3Target) * (size_t)T);
+  for (int t = 0; t < T; t++) {
+    const orbm_fuse_sim3_target_t &g = targets[t];
+    const size_t n = (size_t)g.kf.n;
+    FuseSim3Target &R = rec[t];
+    memset(&R, 0, sizeof(R));
+    R.kp_off = add(g.kf.keys_un, sizeof(orbx_keypoint_t) * n);
+    R.desc_off = add(g.kf.descriptors, 32 * n);
+    R.n = g.kf.n;
+    R.min_x = g.kf.min_x; R.max_x = g.kf.max_x; R.min_y = g.kf.min_y; R.max_y = g.kf.max_y;
+    R.inv_w = (float)ORBM_GRID_COLS / (g.kf.max_x - g.kf.min_x);   // Frame.cc:379
+    R.inv_h = (float)ORBM_GRID_ROWS / (g.kf.max_y - g.kf.min_y);   // Frame.cc:380
+    for (int l = 0; l < g.nlevels; l++) R.sf[l] = g.scale_factors[l];
+    R.nlevels = g.nlevels; R.log_sf = g.log_scale_factor;
+    decompose_sim3(g.Scw, R.Tcw, R.Ow);                            // ORBmatcher.cc:1672-1677
+    R.cam_type = g.cam_type;
+    for (int k = 0; k < (g.cam_type == 0 ? 4 : 8); k++) R.cam[k] = g.cam_params[k];
+  }
+  const std::vector<int32_t> zero_counts((size_t)T, 0);   // the lists' lengths start at 0 with the upload
+  add(zero_counts.data(), sizeof(int32_t) * (size_t)T);
+  add(nullptr, sizeof(int32_t) * TP);                     // the lists
+  add(nullptr, sizeof(int32_t) * TP); add(nullptr, sizeof(int32_t) * TP);
+  std::vector<void *> dev(parts.size());
+  const int rc = stage(m, s, parts.data(), parts.size(), dev.data(), true);
+  if (rc < 0) return rc;
+  FusePoints P;
+  P.nP = nP;
+  P.valid = (const uint8_t *)dev[0]; P.Xw = (const float *)dev[1]; P.normal = (const float *)dev[2]; P.mpdesc = (const uint8_t *)dev[3];
+  P.max_dist = (const float *)dev[4]; P.min_dist = (const float *)dev[5];
+  P.th = th;
+  P.best_idx = (int32_t *)dev[parts.size() - 2]; P.best_dist = (int32_t *)dev[parts.size() - 1];
+  const dim3 fgrid((unsigned)((nP + FUSE_NT - 1) / FUSE_NT), (unsigned)T);
+  FuseLists Lst;
+  Lst.count = (int32_t *)dev[parts.size() - 4]; Lst.list = (int32_t *)dev[parts.size() - 3];
+  hipLaunchKernelGGL(k_fuse_sim3_gate, fgrid, dim3(FUSE_NT), 0, s, (const FuseSim3Target *)dev[6], P, Lst);
+  hipLaunchKernelGGL(k_fuse_sim3_search, fgrid, dim3(FUSE_NT), 0, s, (const uint8_t *)m->d_block.p, (const FuseSim3Target *)dev[6], P, Lst);
+  MCHECK(m, hipGetLastError());
+  // both tables down in one copy, one synchronisation
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, P.best_idx), P.best_idx, (uint8_t *)(P.best_dist + TP) - (uint8_t *)P.best_idx, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  memcpy(best_idx, mirror_of(m, P.best_idx), sizeof(int32_t) * TP);
+  memcpy(best_dist, mirror_of(m, P.best_dist), sizeof(int32_t) * TP);
+  int total = 0;
+  for (int t = 0; t < T; t++) {
+    int nf = 0;
+    for (size_t i = 0; i < NP; i++) nf += best_idx[(size_t)t * NP + i] >= 0 ? 1 : 0;   // bestDist <= TH_LOW, :1767
     nfused[t] = nf;
     total += nf;
   }

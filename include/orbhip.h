@@ -761,6 +761,69 @@ int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets /*[T
                         const float *max_dist, const float *min_dist, float th,
                         int32_t *best_idx /*[T][nP]*/, int32_t *best_dist /*[T][nP]*/, int32_t *nfused /*[T]*/);
 
+/* ---- LoopClosing::SearchAndFuse (LoopClosing.cc:2631-2670, :2673-2707): ONE list of loop / merge map points fused into ALL corrected
+ * keyframes per call ----
+ * Both overloads call the Sim3 overload of ORBmatcher::Fuse (ORBmatcher.cc:1664-1786) once per corrected keyframe (CorrectLoop :1376,
+ * the two map merges :1995, :2506), always with the same point list and each time with another Scw.  orbm_fuse_sim3_keyframes is the
+ * search part of all those calls, staged and launched as orbm_fuse_keyframes is: the point arrays once, the valid table, the per-target
+ * records and every target's keypoints and descriptors in one block, two kernels (k_fuse_sim3_gate lists the pairs that pass the
+ * gates, k_fuse_sim3_search searches the lists), one download of the two tables, one synchronisation.
+ *
+ * One target = what orbm_fuse_sim3_cam takes of a keyframe. */
+typedef struct {
+  orbm_frame_t kf;                 /* mvKeysUn / mDescriptors / bounds (u_right is not read: this overload has no stereo term) */
+  const float *scale_factors;      /* mvScaleFactors [nlevels] */
+  int32_t nlevels;                 /* [1, ORBX_MAX_LEVELS] */
+  float log_scale_factor;
+  const float *Scw;                /* row-major 4x4 Sim3; a pose (scale 1) for the overload that passes GetPose() (:2686) */
+  int32_t cam_type; const float *cam_params;   /* as in orbm_project */
+} orbm_fuse_sim3_target_t;
+
+/* valid [T][nP]: row t = valid of orbm_fuse_sim3_cam for target t (!pMP->isBad() && !pKF_t->GetMapPoints().count(pMP)); Xw, normal,
+ * mpdesc, max_dist, min_dist [nP] and th as there.  Out: best_idx / best_dist [T][nP], nfused [T].
+ * Row t is bit for bit what orbm_fuse_sim3_cam returns for target t with valid + t * nP, nfused[t] is the return value of that call,
+ * and the function returns the sum of nfused.  Targets may differ in keypoint count, image bounds, camera model, nlevels and scale
+ * tables.  A target with kf.n == 0, or a valid row of zeros, gives a row of -1 / 256.  T == 0 or nP == 0 returns 0 and does not touch
+ * the device.  Every Scw is decomposed once on the host exactly as orbm_fuse_sim3_cam decomposes it (ORBmatcher.cc:1672-1677).  A Scw whose scale is
+ * zero or not finite is NOT refused, because the per-target entry does not refuse it: its T is then NaN or infinite, no projection
+ * passes IsInImage, and the row is -1 / 256 on both sides (the kernel clamps every table index: PredictScale's level to
+ * [0, nlevels), the cell window to the grid).
+ * ORBX_E_ARG, with orbm_last_error naming the target ("target <t>: ...") where there is one, for what orbm_fuse_keyframes refuses
+ * (above) without inv_level_sigma2, Tcw and Ow, and for a NULL Scw.  Everything is validated before anything is staged or launched.
+ *
+ * Why the T searches may leave the reference's loop although its body changes map points between them - the SEARCH-AND-FUSE RULE,
+ * next to the FUSE RULE above.  The loop body differs from SearchInNeighbors': inside call t, ORBmatcher::Fuse does AddObservation /
+ * AddMapPoint at once for an empty keypoint (:1776-1780) but only RECORDS an occupied one in vpReplacePoint (:1771-1775);
+ * SearchAndFuse then replaces, under mMutexMapUpdate, pRep->Replace(vpMapPoints[i]) for every recorded i (:2654-2665, :2693-2704).
+ *   - Read-only keyframe inputs, claimless search: as in the FUSE RULE.  The search reads of a keyframe only keypoints, descriptors,
+ *     bounds, camera and scale tables; Scw is a local of the loop.  Two points that pick one keypoint do not see each other.
+ *   - Nothing iteration t does reaches its own searches.  AddObservation / AddMapPoint change no searched quantity of any point, and
+ *     every Replace of iteration t runs after call t has returned.
+ *   - Replace always makes the SEARCHED point vpMapPoints[i] the survivor and the keyframe's own point pRep the loser.  The survivor only
+ *     gains observations and keyframe memberships; EraseMapPointMatch / ReplaceMapPointMatch touch only the loser's slots, and the loser
+ *     is bad from then on.  Validity here is !isBad() && !spAlreadyFound.count(pMP) with spAlreadyFound = pKF_t->GetMapPoints() taken
+ *     at entry of iteration t: a listed point can turn bad (it was the pRep of an earlier keypoint) and can enter a keyframe, never the
+ *     reverse, so validity at entry of iteration t is a subset of validity at loop entry.  Position, normal and the two distances
+ *     never change.
+ *   - The only searched quantity that changes is the survivor's descriptor: Replace ends in ComputeDistinctiveDescriptors()
+ *     (MapPoint.cc:300), and the survivor is a searched point.
+ *   - The rule.  The sequential result for (t, i) is entry (t, i) of the tables computed from the state at loop entry, used under the
+ *     live validity test of iteration t.  The exception is a point whose GetDescriptor() now differs from the 32 bytes that were
+ *     uploaded: for those points alone the caller repeats the search of target t at the start of iteration t, with orbm_fuse_sim3_cam
+ *     on the subset.  The start of iteration t is early enough by the second item.
+ *   - A pointer listed twice needs no special case, nor do two points that pick the same keypoint: the body (:1768-1782) and the
+ *     deferred Replace loop run on the live objects exactly as the adapter's ORBmatcher::Fuse and the reference's loop run them; only
+ *     the (best_idx, best_dist) they start from come from the tables.
+ *   - How large the dirty fraction is on real sequences is NOT KNOWN here: no sequence was run.  In this loop EVERY successful Replace
+ *     can dirty a searched point (in SearchInNeighbors only those whose survivor is listed), so it is expected to be larger than
+ *     there.  Every dirty point costs one entry of a per-target orbm_fuse_sim3_cam call on the subset; a loop in which most points
+ *     turn dirty gains nothing over the per-target calls.
+ * tests/test_fuse_sim3_keyframes_abi.py and tests/test_gpu_fuse_sim3_keyframes.py replay the sequential loop against this rule. */
+int orbm_fuse_sim3_keyframes(orbm_t *m, int T, const orbm_fuse_sim3_target_t *targets /*[T]*/, int nP,
+                             const uint8_t *valid /*[T][nP]*/, const float *Xw, const float *normal, const uint8_t *mpdesc,
+                             const float *max_dist, const float *min_dist, float th,
+                             int32_t *best_idx /*[T][nP]*/, int32_t *best_dist /*[T][nP]*/, int32_t *nfused /*[T]*/);
+
 /* int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12,
  *                              const cv::Mat &R12, const cv::Mat &t12, const float th)           (ORBmatcher.cc:1788-2012)
  * Per keyframe k: kf_k = mvKeysUn / mDescriptors / image bounds, sf_k = mvScaleFactors, log_sf_k = mfLogScaleFactor,
