@@ -687,6 +687,7 @@ _REF_LIB = os.path.join(_REF_DIR, "libref_extractor.so")
 _REF_SOURCES = ("ref_driver.cc", "ref_extractor.map", os.path.join("ref_shim", "opencv", "cv.h"), "orb_oracle.h", "Makefile")
 _REF_CAM_LIB = os.path.join(_REF_DIR, "libref_cameras.so")
 _REF_CAM_LIB_CMATH = os.path.join(_REF_DIR, "libref_cameras_cmath.so")
+_REF_MATCH_LIB = os.path.join(_REF_DIR, "libref_matcher.so")
 _ref_lib = None
 
 
@@ -697,8 +698,8 @@ def reference_tree():
 
 
 def build_ref(force=False):
-    """Build oracle/_ref/libref_extractor.so (and the camera libraries beside it, ref_cam_lib) where the reference tree exists; elsewhere
-    what is already built is used as it is.  Returns the extractor library's path, or None when there is neither."""
+    """Build oracle/_ref/libref_extractor.so (and beside it the camera libraries, ref_cam_lib, and the matcher library, ref_match_lib)
+    where the reference tree exists; elsewhere what is already built is used as it is.  Returns the extractor library's path, or None when there is neither."""
     tree = reference_tree()
     if tree is not None:
         build()
@@ -894,3 +895,158 @@ def ref_svd(A, L=None):
     w, u, vt = np.zeros(min(m, n), np.float32), np.zeros((m, m), np.float32), np.zeros((n, n), np.float32)
     _cam_ok((L or ref_cam_lib()).refcam_svd(m, n, _p(A), _p(w), _p(u), _p(vt)), "refcam_svd")
     return w, u, vt
+
+
+# --- the reference's own ORBmatcher.cc, compiled (oracle/Makefile `ref`, oracle/ref_match_driver.cc) ----------------------------------
+_ref_match_lib = None
+
+
+class RefFrameRec(C.Structure):
+    """refm_frame of ref_match_driver.cc: what orc_frame_init takes."""
+    _fields_ = [("N", C.c_int32), ("kx", C.c_void_p), ("ky", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p), ("desc", C.c_void_p),
+                ("uRight", C.c_void_p), ("minX", C.c_float), ("maxX", C.c_float), ("minY", C.c_float), ("maxY", C.c_float),
+                ("scaleFactors", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+def ref_match_lib(build_if_possible=True):
+    """libref_matcher.so, loaded.  build_if_possible=False never looks at the reference tree: what is under oracle/_ref/ is loaded as
+    it is."""
+    global _ref_match_lib
+    if _ref_match_lib is None:
+        if build_if_possible:
+            build_ref()
+        if not os.path.exists(_REF_MATCH_LIB):
+            raise RuntimeError("oracle/_ref/libref_matcher.so is missing and there is no reference tree to build it from: "
+                               "run __graft_entry__.build() where the reference exists")
+        L = C.CDLL(_REF_MATCH_LIB)
+        P, I, F = C.c_void_p, C.c_int, C.c_float
+        L.refm_descriptor_distance.argtypes = [P, P]
+        L.refm_three_maxima.argtypes = [P, I, P, P, P]
+        L.refm_three_maxima.restype = None
+        L.refm_radius_by_viewing_cos.argtypes = [F]
+        L.refm_radius_by_viewing_cos.restype = F
+        L.refm_get_features_in_area.argtypes = [P, F, F, F, I, I, P]
+        L.refm_search_by_projection_mp.argtypes = [P, P, P, P, I] + [P] * 14 + [F, I, F, F, P, P]
+        L.refm_search_by_projection_ff.argtypes = [P, P, I] + [P] * 9 + [I, P, F, F, F, I, I, P, P]
+        L.refm_search_by_projection_kf.argtypes = [P, I] + [P] * 7 + [I, P, F, I, I, P, P]
+        L.refm_search_by_bow.argtypes = [P, P, I, I, F, I, P]
+        L.refm_search_for_initialization.argtypes = [I, P, P, P, P, P, I, F, I, P]
+        _ref_match_lib = L
+    return _ref_match_lib
+
+
+def _u8(x):
+    return None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
+
+
+def _i32(x):
+    return None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+
+
+def _f32(x):
+    return None if x is None else np.ascontiguousarray(x, dtype=np.float32)
+
+
+class RefFrame:
+    """The compiled matcher's view of the arrays an OracleFrame was made of (the very same numpy arrays), with its own slot /
+    slot_obs (mvpMapPoints as indices, see ref_match_driver.cc)."""
+
+    def __init__(self, of, L=None):
+        self.L = L or ref_match_lib()
+        self.of = of
+        self.N = of.N
+        self.rec = RefFrameRec(of.N, of.kx.ctypes.data, of.ky.ctypes.data, of.octave.ctypes.data, of.angle.ctypes.data, of.desc.ctypes.data,
+                               None if of.u_right is None else of.u_right.ctypes.data, of.f.mnMinX, of.f.mnMaxX, of.f.mnMinY, of.f.mnMaxY,
+                               of.sf.ctypes.data, len(of.sf))
+        self.slot = of.slot.copy()
+        self.slot_obs = of.slot_obs.copy()
+
+    def features_in_area(self, x, y, r, min_level=-1, max_level=-1):
+        out = np.zeros(max(self.N, 1), np.int32)
+        n = self.L.refm_get_features_in_area(C.byref(self.rec), x, y, r, int(min_level), int(max_level), _p(out))
+        return out[:n].copy()
+
+    def search_by_projection_mp(self, in_view, qdesc, projX, projY, viewCos, level, th, nnratio, qobs=None, projXR=None, bad=None,
+                                track_depth=None, far_points=False, th_far=0.0):
+        """SearchByProjection(Frame, MapPoints) (ORBmatcher.cc:44) on a mono / rectified frame: nmatches; slot / slot_obs updated."""
+        nq = len(projX)
+        return self.L.refm_search_by_projection_mp(
+            C.byref(self.rec), None, None, None, nq, _p(_u8(in_view)), None, _p(_u8(bad)), _p(_f32(track_depth)), _p(_u8(qdesc)), _p(_f32(projX)),
+            _p(_f32(projY)), _p(_f32(viewCos)), _p(_i32(level)), _p(_f32(projXR)), None, None, None, _p(_u8(qobs)), th, int(far_points), th_far,
+            nnratio, _p(self.slot), _p(self.slot_obs))
+
+    def search_by_projection_ff(self, has_mp, Xw, mpdesc, last_octave, last_angle, Tcw, Tlw, cam_type, cam_params, th, mono=True, check_ori=True,
+                                mb=0.0, mbf=0.0, qobs=None):
+        """SearchByProjection(Frame, Frame) (ORBmatcher.cc:2027): nmatches; slot / slot_obs updated.  has_mp == 2: an outlier."""
+        return self.L.refm_search_by_projection_ff(
+            C.byref(self.rec), None, len(has_mp), _p(_u8(has_mp)), _p(_f32(Xw)), _p(_u8(mpdesc)), _p(_i32(last_octave)), _p(_f32(last_angle)),
+            _p(_u8(qobs)), _p(_f32(Tcw)), _p(_f32(Tlw)), None, int(cam_type), _p(_f32(cam_params)), mb, mbf, th, int(mono), int(check_ori),
+            _p(self.slot), _p(self.slot_obs))
+
+    def search_by_projection_kf(self, state, Xw, mpdesc, kf_angle, max_dist, min_dist, Tcw, cam_type, cam_params, th, orb_dist, check_ori=True):
+        """SearchByProjection(Frame, KeyFrame, sAlreadyFound) (ORBmatcher.cc:2291).  state: 0 none, 1 point, 2 bad, 3 already found."""
+        return self.L.refm_search_by_projection_kf(
+            C.byref(self.rec), len(state), _p(_u8(state)), _p(_f32(Xw)), _p(_u8(mpdesc)), _p(_f32(kf_angle)), _p(_f32(max_dist)), _p(_f32(min_dist)),
+            _p(_f32(Tcw)), int(cam_type), _p(_f32(cam_params)), th, int(orb_dist), int(check_ori), _p(self.slot), _p(self.slot_obs))
+
+
+class RefFisheyeFrame:
+    """The compiled matcher's view of an OracleFisheyeFrame (Nleft != -1)."""
+
+    def __init__(self, off, L=None):
+        self.L = L or ref_match_lib()
+        self.left, self.right = RefFrame(off.left, self.L), RefFrame(off.right, self.L)
+        self.slot, self.slot_obs = off.slot.copy(), off.slot_obs.copy()
+
+    def search_by_projection_mp(self, l2r, r2l, in_view, in_view_r, qdesc, projX, projY, viewCos, level, projXR, projYR, viewCosR, levelR, th,
+                                nnratio, qobs=None):
+        return self.L.refm_search_by_projection_mp(
+            C.byref(self.left.rec), C.byref(self.right.rec), _p(_i32(l2r)), _p(_i32(r2l)), len(level), _p(_u8(in_view)), _p(_u8(in_view_r)), None,
+            None, _p(_u8(qdesc)), _p(_f32(projX)), _p(_f32(projY)), _p(_f32(viewCos)), _p(_i32(level)), _p(_f32(projXR)), _p(_f32(projYR)),
+            _p(_f32(viewCosR)), _p(_i32(levelR)), _p(_u8(qobs)), th, 0, 0.0, nnratio, _p(self.slot), _p(self.slot_obs))
+
+    def search_by_projection_ff(self, has_mp, Xw, mpdesc, last_octave, last_angle, Tcw, Tlw, Trl, cam_type, cam_params, th, mono=False,
+                                check_ori=True, mb=0.0, qobs=None):
+        return self.L.refm_search_by_projection_ff(
+            C.byref(self.left.rec), C.byref(self.right.rec), len(has_mp), _p(_u8(has_mp)), _p(_f32(Xw)), _p(_u8(mpdesc)), _p(_i32(last_octave)),
+            _p(_f32(last_angle)), _p(_u8(qobs)), _p(_f32(Tcw)), _p(_f32(Tlw)), _p(_f32(Trl)), int(cam_type), _p(_f32(cam_params)), mb, 0.0, th,
+            int(mono), int(check_ori), _p(self.slot), _p(self.slot_obs))
+
+
+def ref_descriptor_distance(a, b, L=None):
+    return (L or ref_match_lib()).refm_descriptor_distance(_p(_u8(a)), _p(_u8(b)))
+
+
+def ref_three_maxima(sizes, L=None):
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    i1, i2, i3 = C.c_int(-9), C.c_int(-9), C.c_int(-9)
+    (L or ref_match_lib()).refm_three_maxima(_p(sizes), len(sizes), C.byref(i1), C.byref(i2), C.byref(i3))
+    return i1.value, i2.value, i3.value
+
+
+def radius_by_viewing_cos(view_cos):
+    """The oracle's RadiusByViewingCos (ORBmatcher.cc:216)."""
+    L = lib()
+    L.orc_radius_by_viewing_cos.restype = C.c_float
+    L.orc_radius_by_viewing_cos.argtypes = [C.c_float]
+    return float(L.orc_radius_by_viewing_cos(float(view_cos)))
+
+
+def ref_radius_by_viewing_cos(view_cos, L=None):
+    return float((L or ref_match_lib()).refm_radius_by_viewing_cos(float(view_cos)))
+
+
+def ref_search_by_bow(KF, F, nnratio=0.7, check_ori=True, n_left=-1, kf_n_left=-1, L=None):
+    """The compiled SearchByBoW(KeyFrame*, Frame&, ...) (ORBmatcher.cc:273) on the records of two OracleKeyFrame views."""
+    m = np.full(max(F.N, 1), -1, np.int32)
+    n = (L or ref_match_lib()).refm_search_by_bow(C.byref(KF.k), C.byref(F.k), int(n_left), int(kf_n_left), nnratio, int(check_ori), _p(m))
+    return n, m[:F.N]
+
+
+def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window_size, nnratio=0.9, check_ori=True):
+    """The compiled SearchForInitialization (ORBmatcher.cc:722); F2 = RefFrame; prev_matched (n1, 2) float32 in / out."""
+    n1 = len(keys1)
+    m12 = np.full(n1, -1, np.int32)
+    n = F2.L.refm_search_for_initialization(n1, _p(_i32(keys1["octave"])), _p(_f32(keys1["angle"])), _p(_u8(desc1)), C.byref(F2.rec),
+                                            _p(prev_matched), int(window_size), nnratio, int(check_ori), _p(m12))
+    return n, m12

@@ -15,9 +15,12 @@
  * record (see DESIGN.md "Oracle").  PINNED: the extractor part (control flow, geometry,
  * octree, orientation, descriptor, ordering) equals the reference's own ORBextractor.cc
  * compiled against stand-in containers (`make ref`, ref_driver.cc), under the
- * creation-order definition of the pointer tie.  STILL UNPINNED: the OpenCV primitives
- * below (the compiled text calls these very functions), the libm overloads, and all of
- * the ORBmatcher, Frame and camera-model restatements.
+ * creation-order definition of the pointer tie; the camera models equal the reference's
+ * own Pinhole.cpp / KannalaBrandt8.cpp compiled (ref_cam_driver.cc); the matcher members
+ * tracking calls (M1-M4, M7, the first N3 member, N2) equal the reference's own
+ * ORBmatcher.cc compiled (ref_match_driver.cc).  STILL UNPINNED: the OpenCV primitives
+ * below (the compiled text calls these very functions), the Frame restatements, and the
+ * matcher members local mapping and loop closing call.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this.
  * The shipped library (liborbhip.so) never links, loads or calls anything in oracle/.

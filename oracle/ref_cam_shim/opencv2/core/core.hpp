@@ -1,13 +1,16 @@
 /*
- * Stand-in for <opencv2/core/core.hpp> (TEST INFRASTRUCTURE): what the reference's CameraModels/Pinhole.cpp and KannalaBrandt8.cpp,
- * and the headers they include, use of OpenCV 3.4.x - and nothing else.  Written from scratch from OpenCV's published algorithms;
+ * Stand-in for <opencv2/core/core.hpp> (TEST INFRASTRUCTURE): what the reference's CameraModels/Pinhole.cpp, KannalaBrandt8.cpp and
+ * ORBmatcher.cc, and the headers they include, use of OpenCV 3.4.x - and nothing else.  Written from scratch from OpenCV's published algorithms;
  * an independent, general (any small m x n) restatement that shares no code with the product, the oracle or the test models.
  *
- *   Mat            CV_32F only, two dimensions, shared storage; row / col / rowRange / colRange are views into it.
+ *   Mat            CV_32F for the algebra, CV_8U for descriptor rows (row, ptr<int32_t>, clone - no algebra); two dimensions, shared
+ *                  storage; row / col / rowRange / colRange are views into it.
  *   MatExpr        the lazy expressions of the two files, folded as OpenCV's MatExpr folds them (DESIGN.md section 2 has the table):
  *                    A*B, -A*B, s*A*B, A*B + C      one gemm: D = alpha*A*B + beta*C
  *                    s*A - B                        one scaled addition in float: product rounded, then the difference
  *                    A / s                          (float)((double)v * (1.0 / (double)s))
+ *                    -A.t()*B                       the transposition materialised, then one gemm with alpha = -1 (the matcher)
+ *                    A - B                          one float difference per entry (the matcher)
  *                    A.t(), A.inv(), A.t().inv()    materialised when assigned or used as a gemm operand
  *                  Every other expression shape asserts.
  *   gemm           inner length 2..4 (equal to one side of the result), no transposed operand: OpenCV's small-matrix path, the sum
@@ -17,6 +20,7 @@
  *   SVD::compute   OpenCV's own one-sided Jacobi for float (JacobiSVDImpl_<float>), in full: u, w, all of vt, rows sorted.  An OpenCV
  *                  built with LAPACK gives other low bits.
  *   fisheye::undistortPoints  declared because KannalaBrandt8::ReconstructWithTwoViews names it; aborts.
+ *   FileStorage, BFMatcher, InputArray ...  declared, without bodies, at the end: named by the SLAM headers ORBmatcher.cc includes.
  *
  * This header does not include <math.h>: whether an unqualified cos(float) inside a namespace is the float or the double function is
  * decided by opencv2/opencv.hpp (see there).  Compile without -DNDEBUG: what is not provided asserts.
@@ -32,12 +36,18 @@
 
 #include <algorithm>
 #include <cmath>
+#include <fstream>
 #include <iostream>
 #include <memory>
+#include <sstream>
+#include <string>
 #include <vector>
 
 #define CV_PI 3.1415926535897932384626433832795
+#define CV_8U 0
+#define CV_8UC1 0
 #define CV_32F 5
+#define CV_64F 6
 
 namespace cv {
 
@@ -48,6 +58,9 @@ struct Point_ {
   Point_(T _x, T _y) : x(_x), y(_y) {}
 };
 typedef Point_<float> Point2f;
+typedef Point_<int> Point2i;
+typedef Point_<int> Point;
+typedef Point_<double> Point2d;
 
 template <typename T>
 struct Point3_ {
@@ -56,6 +69,15 @@ struct Point3_ {
   Point3_(T _x, T _y, T _z) : x(_x), y(_y), z(_z) {}
 };
 typedef Point3_<float> Point3f;
+typedef Point3_<double> Point3d;
+typedef unsigned char uchar;
+template <typename T>
+struct Size_ {
+  T width, height;
+  Size_() : width(0), height(0) {}
+  Size_(T w, T h) : width(w), height(h) {}
+};
+typedef Size_<int> Size;
 
 struct KeyPoint {
   Point2f pt;
@@ -77,7 +99,7 @@ template <typename T> class MatCommaInitializer_;
 
 /* A lazy expression.  a, b, c hold the operands (sharing their storage), alpha / beta the scalars. */
 struct MatExpr {
-  enum Op { T, INV, SCALE, GEMM, AXMB, DIV };
+  enum Op { T, INV, SCALE, GEMM, AXMB, DIV, SUB };
   Op op;
   std::shared_ptr<Mat> a, b, c;
   double alpha, beta;
@@ -90,22 +112,33 @@ class Mat {
  public:
   int rows, cols;
 
-  Mat() : rows(0), cols(0), step_(0), off_(0) {}
-  Mat(int r, int c, int type) : rows(0), cols(0), step_(0), off_(0) { create(r, c, type); }
+  Mat() : rows(0), cols(0), type_(CV_32F), step_(0), off_(0) {}
+  Mat(int r, int c, int type) : rows(0), cols(0), type_(CV_32F), step_(0), off_(0) { create(r, c, type); }
   template <typename T> Mat(const MatCommaInitializer_<T> &ci);
 
   void create(int r, int c, int type) {
-    assert(type == CV_32F && r >= 0 && c >= 0);
-    if (rows == r && cols == c && buf_) return;
-    rows = r; cols = c; step_ = (size_t)c; off_ = 0;
-    buf_ = std::shared_ptr<float>(new float[(size_t)r * (size_t)c + 1](), std::default_delete<float[]>());
+    assert((type == CV_32F || type == CV_8U) && r >= 0 && c >= 0);
+    if (rows == r && cols == c && type_ == type && (buf_ || bytes_)) return;
+    rows = r; cols = c; step_ = (size_t)c; off_ = 0; type_ = type;
+    buf_.reset(); bytes_.reset();
+    if (type == CV_32F) buf_ = std::shared_ptr<float>(new float[(size_t)r * (size_t)c + 1](), std::default_delete<float[]>());
+    /* descriptor rows are read as 32-bit words (ptr<int32_t>): new[] storage is aligned for them when every row is a multiple of 4 */
+    else bytes_ = std::shared_ptr<uchar>(new uchar[(size_t)r * (size_t)c + 4](), std::default_delete<uchar[]>());
   }
-  bool empty() const { return rows == 0 || cols == 0 || !buf_; }
+  int type() const { return type_; }
+  bool empty() const { return rows == 0 || cols == 0 || (!buf_ && !bytes_); }
   bool isContinuous() const { return rows <= 1 || step_ == (size_t)cols; }
+  size_t elemSize() const { return type_ == CV_32F ? sizeof(float) : 1; }
+  size_t total() const { return (size_t)rows * (size_t)cols; }
+  int channels() const { return 1; }
+  Size size() const { return Size(cols, rows); }
 
-  template <typename T> T *ptr(int y = 0) { only_float((T *)0); shim::trace().ptr++; assert(y >= 0 && y < rows); return buf_.get() + off_ + (size_t)y * step_; }
-  template <typename T> const T *ptr(int y = 0) const { only_float((T *)0); shim::trace().ptr++; assert(y >= 0 && y < rows); return buf_.get() + off_ + (size_t)y * step_; }
-  template <typename T> T &at(int y, int x) { only_float((T *)0); assert(y >= 0 && y < rows && x >= 0 && x < cols); return buf_.get()[off_ + (size_t)y * step_ + (size_t)x]; }
+  /* ptr<float> of a CV_32F matrix; ptr<uchar> / ptr<int32_t> (a row of descriptor words) of a CV_8U one */
+  template <typename T> T *ptr(int y = 0) { shim::trace().ptr++; assert(y >= 0 && y < rows); return row_((T *)0, y); }
+  template <typename T> const T *ptr(int y = 0) const { shim::trace().ptr++; assert(y >= 0 && y < rows); return const_cast<Mat *>(this)->row_((T *)0, y); }
+  uchar *ptr(int y = 0) { return ptr<uchar>(y); }
+  const uchar *ptr(int y = 0) const { return ptr<uchar>(y); }
+  template <typename T> T &at(int y, int x) { assert(y >= 0 && y < rows && x >= 0 && x < cols); return row_((T *)0, y)[x]; }
   template <typename T> const T &at(int y, int x) const { return const_cast<Mat *>(this)->at<T>(y, x); }
   /* the one-index form: a continuous matrix or a single row is indexed in storage order, a single column by rows */
   template <typename T> T &at(int i) {
@@ -132,11 +165,17 @@ class Mat {
     return m;
   }
   Mat clone() const {
-    Mat m(rows, cols, CV_32F);
+    if (empty()) return Mat();
+    Mat m(rows, cols, type_);
     for (int y = 0; y < rows; y++)
-      for (int x = 0; x < cols; x++) m.at<float>(y, x) = at<float>(y, x);
+      for (int x = 0; x < cols; x++) {
+        if (type_ == CV_32F) m.at<float>(y, x) = at<float>(y, x);
+        else m.at<uchar>(y, x) = at<uchar>(y, x);
+      }
     return m;
   }
+  static Mat zeros(int r, int c, int type) { return Mat(r, c, type); }
+  static Mat zeros(Size s, int type) { return Mat(s.height, s.width, type); }
   /* written into the existing storage where the shape already fits (A.row(i) = ...), into new storage otherwise */
   Mat &operator=(const MatExpr &e);
 
@@ -158,8 +197,12 @@ class Mat {
   }
 
  private:
-  static void only_float(float *) {}
+  float *row_(float *, int y) { assert(type_ == CV_32F && buf_); return buf_.get() + off_ + (size_t)y * step_; }
+  uchar *row_(uchar *, int y) { assert(type_ == CV_8U && bytes_); return bytes_.get() + off_ + (size_t)y * step_; }
+  int *row_(int *, int y) { assert(cols % 4 == 0 && (off_ + (size_t)y * step_) % 4 == 0); return (int *)row_((uchar *)0, y); }
+  int type_;
   std::shared_ptr<float> buf_;
+  std::shared_ptr<uchar> bytes_;
   size_t step_, off_; /* in elements */
 };
 
@@ -192,7 +235,7 @@ inline MatCommaInitializer_<T> operator<<(const Mat_<T> &m, T2 v) {
   MatCommaInitializer_<T> ci(m);
   return (ci, v);
 }
-template <typename T> inline Mat::Mat(const MatCommaInitializer_<T> &ci) : rows(0), cols(0), step_(0), off_(0) { *this = ci.get(); }
+template <typename T> inline Mat::Mat(const MatCommaInitializer_<T> &ci) : rows(0), cols(0), type_(CV_32F), step_(0), off_(0) { *this = ci.get(); }
 
 /* ---- evaluation ---------------------------------------------------------------------------------------------------------------- */
 namespace shim {
@@ -263,6 +306,14 @@ inline Mat eval(const MatExpr &e) {
         }
       return d;
     }
+    case MatExpr::SUB: { /* subtract() of two CV_32F matrices: one float difference per entry */
+      const Mat &a = *e.a, &b = *e.b;
+      assert(a.rows == b.rows && a.cols == b.cols);
+      Mat d(a.rows, a.cols, CV_32F);
+      for (int y = 0; y < a.rows; y++)
+        for (int x = 0; x < a.cols; x++) d.at<float>(y, x) = a.at<float>(y, x) - b.at<float>(y, x);
+      return d;
+    }
     case MatExpr::DIV: { /* convertTo with the scale 1/s */
       const Mat &a = *e.a;
       const double inv = 1.0 / e.alpha;
@@ -293,7 +344,7 @@ inline MatExpr MatExpr::inv() const {
 }
 inline Mat &Mat::operator=(const MatExpr &e) {
   Mat v = shim::eval(e);
-  if (buf_ && rows == v.rows && cols == v.cols) {
+  if (buf_ && type_ == CV_32F && rows == v.rows && cols == v.cols) {
     for (int y = 0; y < rows; y++)
       for (int x = 0; x < cols; x++) at<float>(y, x) = v.at<float>(y, x);
   } else {
@@ -308,6 +359,17 @@ inline MatExpr make_gemm(const Mat &a, const Mat &b, double alpha) {
   return e;
 }
 inline MatExpr operator-(const Mat &a) { return MatExpr(MatExpr::SCALE, a, -1.0); }
+/* -A.t(): MatOp::negate materialises the transposition and scales it by -1, still lazily, so -A.t()*B is one gemm with alpha = -1
+   and no transposition flag */
+inline MatExpr operator-(const MatExpr &e) {
+  assert(e.op == MatExpr::T);
+  return MatExpr(MatExpr::SCALE, shim::transposed(*e.a), -1.0);
+}
+inline MatExpr operator-(const Mat &a, const Mat &b) {
+  MatExpr r(MatExpr::SUB, a);
+  r.b.reset(new Mat(b));
+  return r;
+}
 inline MatExpr operator*(double s, const Mat &a) { return MatExpr(MatExpr::SCALE, a, s); }
 inline MatExpr operator*(const Mat &a, const Mat &b) { return make_gemm(a, b, 1.0); }
 inline MatExpr operator*(const MatExpr &e, const Mat &b) {
@@ -329,6 +391,16 @@ inline MatExpr operator-(const MatExpr &e, const Mat &b) {
   return r;
 }
 inline MatExpr operator/(const Mat &a, double s) { return MatExpr(MatExpr::DIV, a, s); }
+/* Shapes no pinned text forms.  Without these two a lazy right operand would convert to a Mat silently and take the small-matrix path,
+   which is not what OpenCV does with a transposition flag (A*B.t()) or a nested product: they assert instead. */
+inline MatExpr operator*(const Mat &, const MatExpr &) {
+  assert(!"ref_cam_shim: matrix * lazy expression is not provided");
+  abort();
+}
+inline MatExpr operator*(double, const MatExpr &) {
+  assert(!"ref_cam_shim: scalar * lazy expression is not provided");
+  abort();
+}
 
 /* NORM_L2 of CV_32F: the sum of squares in double */
 inline double norm(const Mat &a) {
@@ -499,6 +571,38 @@ inline void undistortPoints(const std::vector<Point2f> &, std::vector<Point2f> &
   abort();
 }
 }  // namespace fisheye
+
+/* ---- named by the SLAM headers the matcher includes (Frame.h, KeyFrame.h, Map.h, the in-tree DBoW2 headers), never called ------ */
+typedef std::string String;
+struct Rect { int x, y, width, height; Rect(int a, int b, int c, int d) : x(a), y(b), width(c), height(d) {} };
+template <typename T, int M, int N> struct Matx { T val[M * N]; };
+struct _InputArray { _InputArray(const Mat &m); };
+struct _OutputArray { _OutputArray(Mat &m); };
+typedef const _InputArray &InputArray;
+typedef const _OutputArray &OutputArray;
+struct DMatch { int queryIdx, trainIdx, imgIdx; float distance; };
+enum { NORM_HAMMING = 6 };
+struct BFMatcher {
+  BFMatcher(int normType = 4, bool crossCheck = false);
+  void knnMatch(const Mat &, const Mat &, std::vector<std::vector<DMatch> > &, int) const;
+};
+struct FileNode;
+struct FileNodeIterator { FileNodeIterator &operator++(); FileNode operator*() const; bool operator!=(const FileNodeIterator &) const; };
+struct FileNode {
+  enum { SEQ = 5, MAP = 6 };
+  FileNode operator[](const char *) const; FileNode operator[](const std::string &) const; FileNode operator[](int) const;
+  operator int() const; operator float() const; operator double() const; operator std::string() const;
+  bool empty() const; size_t size() const; int type() const; bool isSeq() const;
+  FileNodeIterator begin() const; FileNodeIterator end() const;
+};
+struct FileStorage {
+  enum { READ = 0, WRITE = 1 };
+  FileStorage(); FileStorage(const std::string &, int);
+  bool isOpened() const; void release();
+  FileNode operator[](const char *) const; FileNode operator[](const std::string &) const;
+};
+template <typename T> FileStorage &operator<<(FileStorage &, const T &);
+template <typename T> void operator>>(const FileNode &, T &);
 
 }  // namespace cv
 
