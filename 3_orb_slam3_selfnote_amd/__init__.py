@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 
@@ -48,6 +48,11 @@ ABI_SYMBOLS = [
 class FrameStruct(C.Structure):  # orbm_frame_t
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("descriptors", C.c_void_p), ("u_right", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class MapPointUpdateStruct(C.Structure):  # orbm_map_point_update_t
+    _fields_ = [("nmp", C.c_int32), ("start", C.c_void_p), ("desc", C.c_void_p), ("centre", C.c_void_p), ("in_desc", C.c_void_p),
+                ("pos", C.c_void_p), ("ref_centre", C.c_void_p), ("ref_scale", C.c_void_p), ("ref_max_scale", C.c_void_p)]
 
 
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
@@ -220,6 +225,8 @@ def load(build_if_needed=True):
     L.orbm_search_by_projection_sim3_cam.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, vp, vp]
     L.orbm_search_by_sim3.argtypes = [vp] + [vp, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp] * 2 + [f32, vp, vp, vp, f32, vp]
     L.orbm_distinctive_descriptors.argtypes = [vp, i32, vp, vp, vp]
+    L.orbm_update_map_points.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.orbm_map_point_normal_depth.argtypes = [i32, vp, vp, vp, f32, f32, vp, vp, vp]
     L.orbm_knn_match2.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, f32, i32, vp]
     L.orbm_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, f32, i32, vp]
@@ -636,6 +643,30 @@ def new_point_obs(KF, G, idx, n_left=-1):
         o["depth"][st], o["key_x"][st], o["key_y"][st] = G.depth[idx[st]], G.keys["x"][idx[st]], G.keys["y"][idx[st]]
     o["right"] = (idx >= n_left) if n_left != -1 else 0
     return o
+
+
+def map_point_normal_depth(centre, pos, ref_centre, ref_scale, ref_max_scale):
+    """MapPoint::UpdateNormalAndDepth (MapPoint.cc:486-545) for one map point on the host (orbm_map_point_normal_depth): centre [n, 3] the
+    camera centres of its entries in the reference's walk order.  Returns (normal [3], min_dist, max_dist); n == 0 writes nothing (NaN)."""
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    centre, pos, ref_centre = f(centre), f(pos), f(ref_centre)
+    normal, mn, mx = np.full(3, np.nan, np.float32), np.full(1, np.nan, np.float32), np.full(1, np.nan, np.float32)
+    _check_free(load().orbm_map_point_normal_depth(len(centre) // 3, _p(centre), _p(pos), _p(ref_centre), float(ref_scale), float(ref_max_scale),
+                                                   _p(normal), _p(mn), _p(mx)), "orbm_map_point_normal_depth")
+    return normal, mn[0], mx[0]
+
+
+def pack_map_points(points):
+    """The flat arrays of orbm_map_point_update_t from a list of points, each a mapping with `desc` [n, 32], `centre` [n, 3], `in_desc` [n]
+    (one row per entry, in the reference's walk order), `pos` [3], `ref_centre` [3], `ref_scale`, `ref_max_scale`."""
+    n = len(points)
+    start = np.zeros(n + 1, np.int32)
+    for i, pt in enumerate(points):
+        start[i + 1] = start[i] + len(pt["desc"])
+    cat = lambda k, t, w: np.ascontiguousarray(np.concatenate([np.asarray(pt[k], t).reshape((-1,) + w) for pt in points]) if n else np.zeros((0,) + w, t))
+    col = lambda k, w: np.ascontiguousarray(np.array([np.asarray(pt[k], np.float32).reshape(w) for pt in points], np.float32).reshape((n,) + w))
+    return dict(start=start, desc=cat("desc", np.uint8, (32,)), centre=cat("centre", np.float32, (3,)), in_desc=cat("in_desc", np.uint8, ()),
+                pos=col("pos", (3,)), ref_centre=col("ref_centre", (3,)), ref_scale=col("ref_scale", ()), ref_max_scale=col("ref_max_scale", ()))
 
 
 def new_point_geometry(c1, c2, obs1, obs2, scale_factor1, far_points=False, th_far_points=0.0):
@@ -1078,6 +1109,22 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_distinctive_descriptors rc=%d" % rc)
         return best[:len(groups)]
+
+    def UpdateMapPoints(self, points, fill=np.nan):
+        """MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:350-436) and MapPoint::UpdateNormalAndDepth (MapPoint.cc:467-547) for all
+        map points of one call (orbm_update_map_points; LocalMapping.cc:1040-1053).  points: see pack_map_points, or its result.
+        Returns (best [n], normal [n, 3], min_dist [n], max_dist [n]): best relative to the point's first entry, -1 where no entry has
+        in_desc set; a point without entries has best -1 and keeps `fill` in its floats."""
+        A = points if isinstance(points, dict) else pack_map_points(points)
+        n = len(A["start"]) - 1
+        u = MapPointUpdateStruct(n, *[_p(A[k]) for k in ("start", "desc", "centre", "in_desc", "pos", "ref_centre", "ref_scale", "ref_max_scale")])
+        best = np.full(max(n, 1), -1, np.int32)
+        normal, mn, mx = np.full((max(n, 1), 3), fill, np.float32), np.full(max(n, 1), fill, np.float32), np.full(max(n, 1), fill, np.float32)
+        rc = self.L.orbm_update_map_points(self.m, C.byref(u), _p(best), _p(normal), _p(mn), _p(mx))
+        self._check(rc, "orbm_update_map_points")
+        if rc < 0:
+            raise OrbError("orbm_update_map_points rc=%d" % rc)
+        return best[:n], normal[:n], mn[:n], mx[:n]
 
     def ComputeStereoFishEyeMatches(self, keysL, descL, monoL, keysR, descR, monoR, level_sigma2, Tlr, cam_params, cam_params2, p3d=None):
         """Frame::ComputeStereoFishEyeMatches (Frame.cc:1228-1268) of one rig frame from host arrays (orbm_stereo_fisheye_matches).

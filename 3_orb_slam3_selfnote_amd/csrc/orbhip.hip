@@ -31,6 +31,7 @@
 #include "orb_fuse_kernels.h"
 #include "orb_fuse_sim3_kernels.h"
 #include "orb_bow_kernels.h"
+#include "orb_mappoint_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -4090,6 +4091,59 @@ int orbm_distinctive_descriptors(orbm_t *m, int nmp, const int32_t *start, const
   MCHECK(m, hipGetLastError());
   MCHECK(m, hipMemcpyAsync(best, d[2], sizeof(int32_t) * (size_t)nmp, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
+  return 0;
+}
+
+int orbm_update_map_points(orbm_t *m, const orbm_map_point_update_t *u, int32_t *best, float *normal, float *min_dist, float *max_dist) {
+  if (!m || !u || u->nmp < 0) return ORBX_E_ARG;
+  const int nmp = u->nmp;
+  if (nmp == 0) return 0;
+  // everything is validated before anything is uploaded or launched; a refusal writes nothing
+  if (!u->start || !u->pos || !u->ref_centre || !u->ref_scale || !u->ref_max_scale || !best || !normal || !min_dist || !max_dist) {
+    m->err = "UpdateMapPoints: NULL argument"; return ORBX_E_ARG;
+  }
+  if (u->start[0] != 0) { m->err = "UpdateMapPoints: start[0] != 0"; return ORBX_E_ARG; }
+  for (int p = 0; p < nmp; p++) {
+    const int64_t n = (int64_t)u->start[p + 1] - (int64_t)u->start[p];
+    if (n < 0) { m->err = "UpdateMapPoints: start decreases"; return ORBX_E_ARG; }
+    if (n > 64 * DISTINCT_MAXT) { m->err = "UpdateMapPoints: more than 1024 observations of one map point"; return ORBX_E_ARG; }
+  }
+  const size_t total = (size_t)u->start[nmp], NP = (size_t)nmp;
+  if (total > 0 && (!u->desc || !u->centre || !u->in_desc)) { m->err = "UpdateMapPoints: NULL entry array"; return ORBX_E_ARG; }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  Staging S{m};   // one block up, one launch, the four outputs down as one span of the block, one synchronisation
+  const auto hdesc = S.add(u->desc, 32 * total); const auto hstart = S.add(u->start, NP + 1);
+  const auto hcen = S.add(u->centre, 3 * total); const auto hin = S.add(u->in_desc, total);
+  const auto hpos = S.add(u->pos, 3 * NP), hrc = S.add(u->ref_centre, 3 * NP), hrs = S.add(u->ref_scale, NP), hrm = S.add(u->ref_max_scale, NP);
+  const auto hbest = S.out<int32_t>(NP);
+  const auto hnor = S.out<float>(3 * NP), hmin = S.out<float>(NP), hmax = S.out<float>(NP);
+  const int rc = S.upload(s);
+  if (rc < 0) return rc;
+  MapPointUpdateParams P;
+  P.desc = (const uint32_t *)S.dev(hdesc); P.start = S.dev(hstart); P.centre = S.dev(hcen); P.in_desc = S.dev(hin);
+  P.pos = S.dev(hpos); P.ref_centre = S.dev(hrc); P.ref_scale = S.dev(hrs); P.ref_max_scale = S.dev(hrm);
+  P.nmp = nmp; P.best = S.dev(hbest); P.normal = S.dev(hnor); P.min_dist = S.dev(hmin); P.max_dist = S.dev(hmax);
+  hipLaunchKernelGGL(k_update_map_points, dim3((unsigned)((nmp + 3) / 4)), dim3(256), 0, s, P);
+  MCHECK(m, hipGetLastError());
+  const uint8_t *lo = (const uint8_t *)S.dev(hbest);
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hmax) + NP) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  memcpy(best, S.host(hbest), sizeof(int32_t) * NP);
+  const float *nor = S.host(hnor), *mind = S.host(hmin), *maxd = S.host(hmax);
+  for (size_t p = 0; p < NP; p++) {
+    if (u->start[p + 1] == u->start[p]) continue;   // observations.empty() (MapPoint.cc:483): the member returns without writing
+    memcpy(normal + 3 * p, nor + 3 * p, 3 * sizeof(float));
+    min_dist[p] = mind[p]; max_dist[p] = maxd[p];
+  }
+  return 0;
+}
+
+int orbm_map_point_normal_depth(int n, const float *centre, const float *pos, const float *ref_centre, float ref_scale, float ref_max_scale,
+                                float *normal, float *min_dist, float *max_dist) {
+  if (n < 0 || (n > 0 && !centre) || !pos || !ref_centre || !normal || !min_dist || !max_dist) return ORBX_E_ARG;
+  if (n == 0) return 0;   // observations.empty() (MapPoint.cc:483)
+  map_point_normal_depth(n, centre, pos, ref_centre, ref_scale, ref_max_scale, normal, min_dist, max_dist);
   return 0;
 }
 

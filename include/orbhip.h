@@ -1158,6 +1158,53 @@ int orbm_search_by_bow_keyframes_candidates(orbm_t *m, const orbm_keyframe_t *kf
  * mDescriptor = vDescriptors[best[p]].  At most 1024 observations per map point.  Returns 0. */
 int orbm_distinctive_descriptors(orbm_t *m, int nmp, const int32_t *start, const uint8_t *desc, int32_t *best);
 
+/* void MapPoint::ComputeDistinctiveDescriptors()  (MapPoint.cc:350-436) AND void MapPoint::UpdateNormalAndDepth()  (MapPoint.cc:467-547)
+ * for ALL map points of one call: the loop of LocalMapping.cc:1040-1053 (every map point of the current keyframe), the same pair after
+ * LocalMapping::CreateNewMapPoints (LocalMapping.cc:890-897) and at initialisation and map creation (Tracking.cc:2353, :2374, :2552,
+ * :3400, :4460).  One upload block, one launch (k_update_map_points: one wavefront per map point; for up to 64 entries every descriptor
+ * is loaded once into its lane's registers and row i reaches the lanes by a lane read), one download, one synchronisation.
+ *
+ * best[p] (out) = the entry index RELATIVE to start[p] of the descriptor MapPoint.cc:389-435 keeps (mDescriptor = that entry's row): the
+ * first least median (vDists[0.5*(N'-1)], strict `<`) over the N' entries with in_desc set, or -1 where no entry has in_desc set (the
+ * reference returns without writing, :389).  normal[p], min_dist[p], max_dist[p] (out) = mNormalVector, mfMinDistance, mfMaxDistance of
+ * :543-545, from EVERY entry (the walk of :489-511 has no isBad() test); the arithmetic is csrc/orb_ref_mappoint.h, host and device.
+ * A point without entries (observations.empty(), :365 / :483) gets best[p] = -1 and its three float outputs are LEFT UNTOUCHED, as both
+ * members return without writing.  A point lying in one of its camera centres gives NaN, as the reference's arithmetic does.
+ *
+ * Why the points may leave the loop - INDEPENDENCE:
+ *   - a call of either member reads the keyframes' descriptors and camera centres, the point's own mWorldPos, its own mObservations and
+ *     its own mpRefKF (with that keyframe's scale table), and writes only the point's own mDescriptor, mNormalVector, mfMinDistance and
+ *     mfMaxDistance;
+ *   - none of what is read is written by either member, so no call changes an input of the call for another point, and the order of the
+ *     points does not matter;
+ *   - a point listed twice is recomputed from the same inputs to the same values;
+ *   - isBad() of a keyframe or of the point, and a concurrent change of the observations or the position by another thread, are a
+ *     snapshot at the member's own lock in the reference; a caller that batches takes the snapshot earlier and must compare it again
+ *     when it writes (csrc/adapter/snippets/MapPoint_UpdateBatch_hip.cc does).
+ *
+ * ORBX_E_ARG before anything is uploaded or launched, with no output written, for: a NULL handle, struct or output; nmp < 0; a NULL array
+ * that is indexed; start[0] != 0 or a start that decreases; more than 1024 entries of one point.  nmp == 0 returns 0. */
+typedef struct {
+  int32_t nmp;
+  const int32_t *start;       /* [nmp+1], entries of point p are start[p] .. start[p+1]-1: one entry per (keyframe, camera) that
+                                 observes it, in the order of the reference's walk (:371-386, :489-511) */
+  const uint8_t *desc;        /* [nobs][32] pKF->mDescriptors.row(index) */
+  const float   *centre;      /* [nobs][3]  GetCameraCenter() or GetRightCameraCenter() of that entry */
+  const uint8_t *in_desc;     /* [nobs]     1 = !pKF->isBad() (:375): the entry takes part in the descriptor choice; the normal
+                                 takes every entry (:489-511 has no such test) */
+  const float   *pos;         /* [nmp][3]   mWorldPos */
+  const float   *ref_centre;  /* [nmp][3]   pRefKF->GetCameraCenter() */
+  const float   *ref_scale;   /* [nmp]      pRefKF->mvScaleFactors[level], level by :522-531 */
+  const float   *ref_max_scale; /* [nmp]    pRefKF->mvScaleFactors[nLevels-1] */
+} orbm_map_point_update_t;
+
+int orbm_update_map_points(orbm_t *m, const orbm_map_point_update_t *u,
+                           int32_t *best /*[nmp]*/, float *normal /*[nmp][3]*/, float *min_dist /*[nmp]*/, float *max_dist /*[nmp]*/);
+/* MapPoint.cc:486-545 for ONE map point on the host, no handle: the same functions of csrc/orb_ref_mappoint.h, hence the same bits.
+ * n == 0 returns 0 and writes nothing; ORBX_E_ARG for n < 0 or a NULL pointer. */
+int orbm_map_point_normal_depth(int n, const float *centre /*[n][3]*/, const float *pos, const float *ref_centre,
+                                float ref_scale, float ref_max_scale, float *normal, float *min_dist, float *max_dist);
+
 /* cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, matches, 2) as called by Frame::ComputeStereoFishEyeMatches
  * (Frame.cc:1246): idx2[2i..], dist2[2i..] = train index and distance of the nearest and second nearest train descriptor
  * of query i (-1 where nc < 2).  Equal distances are ordered by train index; the only consumer (the ratio test of
