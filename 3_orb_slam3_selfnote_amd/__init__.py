@@ -43,6 +43,12 @@ ABI_SYMBOLS = [
     "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
+# the vocabulary's symbols (orbv_*), a list of their own: tests/test_abi.py holds ABI_SYMBOLS equal to the header's orbx_ / orbm_ names;
+# tests/test_voc_abi.py holds this one equal to its orbv_ names, and build() asks the library for both
+VOC_ABI_SYMBOLS = [
+    "orbv_create", "orbv_destroy", "orbv_last_error", "orbv_n_nodes", "orbv_n_words", "orbv_max_children", "orbv_min_leaf_level",
+    "orbv_transform_host", "orbv_transform", "orbv_batch_scratch_bytes", "orbv_transform_batch_device", "orbv_transform_batch_device_form",
+]
 
 
 class FrameStruct(C.Structure):  # orbm_frame_t
@@ -53,6 +59,11 @@ class FrameStruct(C.Structure):  # orbm_frame_t
 class MapPointUpdateStruct(C.Structure):  # orbm_map_point_update_t
     _fields_ = [("nmp", C.c_int32), ("start", C.c_void_p), ("desc", C.c_void_p), ("centre", C.c_void_p), ("in_desc", C.c_void_p),
                 ("pos", C.c_void_p), ("ref_centre", C.c_void_p), ("ref_scale", C.c_void_p), ("ref_max_scale", C.c_void_p)]
+
+
+class VocNodesStruct(C.Structure):  # orbv_nodes_t
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("n_nodes", C.c_int32),
+                ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("descriptor", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
@@ -274,6 +285,20 @@ def load(build_if_needed=True):
     L.orbm_get_last_ms.restype = f32
     L.orbm_get_last_ms.argtypes = [vp]
     L.orbm_get_stage_ms.argtypes = [vp, vp, i32]
+    L.orbv_create.restype = vp
+    L.orbv_create.argtypes = [vp, i32]
+    L.orbv_destroy.restype = None
+    L.orbv_destroy.argtypes = [vp]
+    L.orbv_last_error.restype = C.c_char_p
+    L.orbv_last_error.argtypes = [vp]
+    for name in ("orbv_n_nodes", "orbv_n_words", "orbv_max_children", "orbv_min_leaf_level"):
+        getattr(L, name).argtypes = [vp]
+    L.orbv_transform_host.argtypes = [vp, vp, i32, i32] + [vp] * 9
+    L.orbv_transform.argtypes = [vp, vp, i32, i32] + [vp] * 9
+    L.orbv_batch_scratch_bytes.restype = sz
+    L.orbv_batch_scratch_bytes.argtypes = [i32, i32]
+    L.orbv_transform_batch_device.argtypes = [vp, vp, i32, i32, vp, i32, i32] + [vp] * 11
+    L.orbv_transform_batch_device_form.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32] + [vp] * 11
     _lib = L
     return L
 
@@ -1714,3 +1739,135 @@ def fisheye_triangulate_device(n, d_kp1, d_kp2, d_sigma1, d_sigma2, Tlr, cam_par
     rc = load().orbm_fisheye_triangulate_device(int(n), _dp(d_kp1), _dp(d_kp2), _dp(d_sigma1), _dp(d_sigma2), _p(f(Tlr)), _p(f(cam_params)),
                                                 _p(f(cam_params2)), _dp(d_depth), _dp(d_p3d), _dp(stream))
     return _check_free(rc, "orbm_fisheye_triangulate_device")
+
+
+def _voc_error(what, rc):
+    msg = (load().orbv_last_error(None) or b"").decode()
+    if rc == E_ARG:
+        raise ValueError("%s: %s" % (what, msg or "bad argument"))
+    raise OrbError("%s rc=%d: %s" % (what, rc, msg))
+
+
+class ORBVocabulary:
+    """ORB_SLAM3::ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>, ORBVocabulary.h:29-30): the transform of
+    Frame::ComputeBoW (Frame.cc:828-835) and KeyFrame::ComputeBoW (KeyFrame.cc:100-110) over orbv_* of include/orbhip.h.
+
+    device >= 0 uploads the tables; device = -1 gives a handle on which only transform_host works (so that the statement of
+    csrc/orb_ref_voc.h can be tested without a GPU; it is not a fallback: transform raises on it)."""
+
+    WEIGHTING = ("TF_IDF", "TF", "IDF", "BINARY")                                              # BowVector.h:39-45
+    SCORING = ("L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA", "DOT_PRODUCT")       # BowVector.h:48-56
+
+    def __init__(self, k, L, weighting, scoring, parent, is_leaf, descriptor, weight, device=0):
+        self.L_lib = load()
+        self.k, self.L, self.weighting, self.scoring, self.device = int(k), int(L), int(weighting), int(scoring), int(device)
+        self.parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        self.is_leaf = np.ascontiguousarray(is_leaf, dtype=np.uint8)
+        self.descriptor = np.ascontiguousarray(descriptor, dtype=np.uint8).reshape(-1, 32)
+        self.weight = np.ascontiguousarray(weight, dtype=np.float64)
+        n = len(self.parent)
+        if not (len(self.is_leaf) == len(self.descriptor) == len(self.weight) == n):
+            raise ValueError("ORBVocabulary: the node tables differ in length")
+        s = VocNodesStruct(self.k, self.L, self.weighting, self.scoring, n, _p(self.parent), _p(self.is_leaf), _p(self.descriptor),
+                           _p(self.weight))
+        self.v = self.L_lib.orbv_create(C.byref(s), self.device)
+        if not self.v:
+            msg = (self.L_lib.orbv_last_error(None) or b"").decode()
+            if "HIP: " in msg:
+                raise OrbError("orbv_create: " + msg)
+            raise ValueError("orbv_create: " + msg)
+        self.n_nodes = self.L_lib.orbv_n_nodes(self.v)
+        self.n_words = self.L_lib.orbv_n_words(self.v)
+        self.max_children = self.L_lib.orbv_max_children(self.v)
+        self.min_leaf_level = self.L_lib.orbv_min_leaf_level(self.v)
+
+    def __del__(self):
+        try:
+            if getattr(self, "v", None):
+                self.L_lib.orbv_destroy(self.v)
+                self.v = None
+        except Exception:
+            pass
+
+    @classmethod
+    def from_nodes(cls, k, L, weighting, scoring, parent, is_leaf, descriptor, weight, device=0):
+        """m_nodes flattened in id order (orbv_nodes_t): node 0 is the root, parent[i] < i, descriptor [n, 32] uint8, weight float64."""
+        return cls(k, L, weighting, scoring, parent, is_leaf, descriptor, weight, device=device)
+
+    @staticmethod
+    def parse_text(path):
+        """The tables of an ORBvoc-format text file: (k, L, scoring, weighting, parent, is_leaf, descriptor, weight).  First line
+        `k L scoring weighting`, then one line per node `parent is_leaf d0 .. d31 weight` (TemplatedVocabulary.h:1338-1424)."""
+        with open(path) as f:
+            head = f.readline().split()
+            k, L, scoring, weighting = (int(x) for x in head[:4])
+            parent, leaf, desc, weight = [0], [0], [np.zeros(32, np.uint8)], [0.0]
+            for line in f:
+                t = line.split()
+                if not t:
+                    continue
+                parent.append(int(t[0]))
+                leaf.append(1 if int(t[1]) > 0 else 0)
+                desc.append(np.array([int(x) for x in t[2:34]], dtype=np.uint8))
+                weight.append(float(t[34]))
+        return k, L, scoring, weighting, np.array(parent, np.uint32), np.array(leaf, np.uint8), np.stack(desc), np.array(weight, np.float64)
+
+    @classmethod
+    def load_text(cls, path, device=0):
+        """loadFromTextFile (TemplatedVocabulary.h:1338-1424).  ONE DIFFERENCE from the loader: blank lines are skipped.  The loader
+        makes a node of every line it reads, so a trailing empty line gives it one more node under the root (parent 0 from the
+        failed `>> pid`, an indeterminate leaf flag and descriptor); a drop-in build passes m_nodes as the loader left them through
+        from_nodes / orbv_create instead (csrc/adapter/snippets/ComputeBoW_hip.cc), extra node included."""
+        k, L, scoring, weighting, parent, leaf, desc, weight = cls.parse_text(path)
+        return cls(k, L, weighting, scoring, parent, leaf, desc, weight, device=device)
+
+    def _transform(self, fn, what, desc, levelsup):
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        n = len(desc)
+        m = max(n, 1)
+        word, node = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        bow_id, bow_val = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        fv_node, fv_start, fv_idx = np.zeros(m, np.uint32), np.zeros(m + 1, np.int32), np.zeros(m, np.int32)
+        n_bow, n_fv = C.c_int32(-1), C.c_int32(-1)
+        rc = fn(self.v, _p(desc), n, int(levelsup), _p(word), _p(node), _p(bow_id), _p(bow_val), C.byref(n_bow), _p(fv_node), _p(fv_start),
+                _p(fv_idx), C.byref(n_fv))
+        if rc < 0:
+            _voc_error(what, rc)
+        nb, nf = n_bow.value, n_fv.value
+        return dict(word=word[:n], node=node[:n], bow_id=bow_id[:nb].copy(), bow_val=bow_val[:nb].copy(), fv_node_id=fv_node[:nf].copy(),
+                    fv_start=fv_start[:nf + 1].copy(), fv_idx=fv_idx[:int(fv_start[nf])].copy())
+
+    def transform(self, desc, levelsup=4):
+        """transform(features, mBowVec, mFeatVec, levelsup) on the device (orbv_transform).  Returns a dict of the flat layouts: word,
+        node [n]; bow_id (ascending), bow_val = the BowVector; fv_node_id (ascending), fv_start, fv_idx = the FeatureVector as
+        orbm_keyframe_t reads it.  Raises on a device = -1 handle: there is no host fallback."""
+        return self._transform(self.L_lib.orbv_transform, "orbv_transform", desc, levelsup)
+
+    def transform_host(self, desc, levelsup=4):
+        """The same through orbv_transform_host: csrc/orb_ref_voc.h in plain C++ (what tests compare the kernels and the model with)."""
+        return self._transform(self.L_lib.orbv_transform_host, "orbv_transform_host", desc, levelsup)
+
+    @staticmethod
+    def feat_vec(t):
+        """{node id: [feature indices]} of a transform result: what KeyFrameView takes as mFeatVec."""
+        return {int(nid): [int(i) for i in t["fv_idx"][t["fv_start"][g]:t["fv_start"][g + 1]]] for g, nid in enumerate(t["fv_node_id"])}
+
+    @staticmethod
+    def batch_scratch_bytes(nframes, cap):
+        return int(load().orbv_batch_scratch_bytes(int(nframes), int(cap)))
+
+    def transform_batch_device(self, d_descriptors, nframes, cap, d_n, n_stride, levelsup, d_bow_id, d_bow_val, d_n_bow, d_fv_node_id,
+                               d_fv_start, d_fv_idx, d_n_fv, d_scratch, d_word=None, d_node=None, stream=None, descend_form=None):
+        """The transform for `nframes` resident frames (orbv_transform_batch_device): all pointers are device addresses (ints),
+        asynchronous on `stream`.  d_descriptors [nframes][cap][32]; live count of frame p = d_n[p * n_stride]; outputs of frame p at
+        p * cap (d_fv_start at p * (cap + 1)); d_scratch: batch_scratch_bytes(nframes, cap) bytes.  descend_form (0 / 1) selects the
+        descent kernel through orbv_transform_batch_device_form, for tests and measurements."""
+        tail = (_dp(d_descriptors), int(nframes), int(cap), _dp(d_n), int(n_stride), int(levelsup), _dp(d_word), _dp(d_node), _dp(d_bow_id),
+                _dp(d_bow_val), _dp(d_n_bow), _dp(d_fv_node_id), _dp(d_fv_start), _dp(d_fv_idx), _dp(d_n_fv), _dp(d_scratch), _dp(stream))
+        if descend_form is None:
+            rc = self.L_lib.orbv_transform_batch_device(self.v, *tail)
+        else:
+            rc = self.L_lib.orbv_transform_batch_device_form(self.v, int(descend_form), *tail)
+        if rc < 0:
+            _voc_error("orbv_transform_batch_device", rc)
+        return rc

@@ -8,6 +8,7 @@
 //                       Tracking::CreateNewKeyFrame (:3345-3416), the close counts of Tracking::NeedNewKeyFrame (:3183-3204) and
 //                       Frame::UnprojectStereo (Frame.cc:1105-1116).
 #pragma once
+#include "orb_sort.h"
 
 // ---- Frame::ComputeStereoFromRGBD ------------------------------------------------------------------------------------------------
 
@@ -83,7 +84,7 @@ struct CloseParams {
 
 // sort(vDepthIdx) orders pair<float, int> by z, then by i.  z > 0 here, and positive floats (+inf included) order as their bit
 // patterns, so the pair orders as this integer; keypoints without depth get the largest key and sort behind every pair.
-// The keys are unique, so any correct sort gives the reference's order: a bitonic sort in LDS, padded to a power of two.  Measured
+// The keys are unique, so any correct sort gives the reference's order: a bitonic sort in LDS (orb_sort.h), padded to a power of two.  Measured
 // against rank-by-counting (each keypoint counts the keys below its own) on 256 frames of 1205 keypoints: 0.033 ms against
 // 0.060 ms for this kernel (profiles/rgbd_batch_sort_choice.txt), and the count grows with N * N.
 __device__ __forceinline__ uint64_t close_key(float z, int i) {
@@ -140,15 +141,7 @@ __global__ __launch_bounds__(CLOSE_THREADS) void k_close_points(CloseParams P) {
   const int last = max(c, P.max_point);
   const int nvisit = last >= m ? m : last + 1;
   int32_t *order = P.order + (size_t)f * P.cap;
-  for (int k = 2; k <= p2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (p2 >> 1); t += CLOSE_THREADS) {
-        const int lo = 2 * t - (t & (j - 1)), hi = lo + j;
-        const uint64_t a = s_key[lo], b = s_key[hi];
-        if ((a > b) == ((lo & k) == 0)) { s_key[lo] = b; s_key[hi] = a; }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_lds<CLOSE_THREADS>(s_key, p2, tid);
   for (int t = tid; t < nvisit; t += CLOSE_THREADS) order[t] = (int32_t)(uint32_t)s_key[t];
   if (tid == 0) {
     P.nvisit[f] = nvisit;

@@ -1,0 +1,20 @@
+// orb_sort.h -- the sort that k_close_points (orb_depth_kernels.h) and k_voc_collect (orb_voc_kernels.h) share: a bitonic sort of
+// 64-bit keys in LDS by one workgroup of THREADS lanes.  p2 is a power of two >= 2 and s_key[0 .. p2) is filled (padding = ~0ull,
+// which sorts last) and made visible by a barrier before the call; the sorted keys are visible to every lane on return.  The network
+// is oblivious of the data, so with UNIQUE keys any two correct sorts give the same array: callers put the element's index into the
+// low bits and get a stable order by construction.
+#pragma once
+#include <stdint.h>
+
+template <int THREADS>
+__device__ __forceinline__ void bitonic_sort_lds(uint64_t *s_key, int p2, int tid) {
+  for (int k = 2; k <= p2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (p2 >> 1); t += THREADS) {
+        const int lo = 2 * t - (t & (j - 1)), hi = lo + j;
+        const uint64_t a = s_key[lo], b = s_key[hi];
+        if ((a > b) == ((lo & k) == 0)) { s_key[lo] = b; s_key[hi] = a; }
+      }
+      __syncthreads();
+    }
+}

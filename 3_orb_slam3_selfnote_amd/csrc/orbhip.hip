@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <mutex>
+#include <map>
 #include <chrono>
 
 #include "../../include/orbhip.h"
@@ -32,6 +33,7 @@
 #include "orb_fuse_sim3_kernels.h"
 #include "orb_bow_kernels.h"
 #include "orb_mappoint_kernels.h"
+#include "orb_voc_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -4188,6 +4190,363 @@ int orbm_hamming_matrix(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, i
   MCHECK(m, hipMemcpyAsync(dist, d_dist, sizeof(uint16_t) * (size_t)nq * nc, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   return 0;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================================
+// ORBVocabulary::transform (Frame::ComputeBoW, KeyFrame::ComputeBoW): csrc/orb_ref_voc.h on the host, csrc/orb_voc_kernels.h on the device
+// =====================================================================================================================================
+
+// What one call of orbv_transform owns while it runs: a stream, a device block and its pinned mirror.  Tracking and LocalMapping call
+// into one vocabulary at the same time, so a call takes one from the handle's pool and gives it back; the tables are read-only.
+struct VocWork {
+  hipStream_t s = nullptr;
+  uint8_t *dev = nullptr, *pin = nullptr;
+  size_t bytes = 0;
+};
+
+struct orbv_handle {
+  int device = -1;
+  int k = 0, L = 0, weighting = 0, scoring = 0;
+  int n_nodes = 0, n_words = 0, max_children = 0;
+  int min_leaf_level = 0; uint32_t min_leaf_node = 0;   // the shallowest childless node of weight > 0 (the lowest id among those)
+  std::vector<uint32_t> desc; std::vector<VocRec> rec; std::vector<double> weight;   // by entry
+  uint32_t *d_desc = nullptr; VocRec *d_rec = nullptr; double *d_weight = nullptr;
+  std::mutex mu;
+  std::vector<VocWork *> pool;
+};
+
+static thread_local std::string g_voc_err;   // orbv_last_error: of the calling thread, so that concurrent calls do not share a string
+static int voc_fail(const std::string &what) { g_voc_err = what; return ORBX_E_ARG; }
+#define VCHECK(call)                                                        \
+  do {                                                                      \
+    hipError_t e_ = (call);                                                 \
+    if (e_ != hipSuccess) {                                                 \
+      g_voc_err = std::string(#call) + ": " + hipGetErrorString(e_);        \
+      return ORBX_E_HIP;                                                    \
+    }                                                                       \
+  } while (0)
+
+static int voc_p2(int n) { int p2 = 2; while (p2 < n) p2 <<= 1; return p2; }
+
+// k_voc_collect sorts up to 16384 8-byte keys: 128 KiB of dynamic LDS, above the 64 KiB a kernel gets unasked.  Raised once per device.
+static hipError_t voc_raise_lds(int device) {
+  static std::mutex mu;
+  static bool done[64] = {};
+  std::lock_guard<std::mutex> lock(mu);
+  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
+  if (done[device]) return hipSuccess;
+  const void *fn = reinterpret_cast<const void *>(&k_voc_collect);
+  hipFuncAttributes a;
+  hipError_t e = hipFuncGetAttributes(&a, fn);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ORB_LDS_LIMIT - (int)a.sharedSizeBytes);
+  if (e != hipSuccess) return e;
+  done[device] = true;
+  return hipSuccess;
+}
+
+static void voc_free_work(VocWork *w) {
+  if (!w) return;
+  if (w->dev) (void)hipFree(w->dev);
+  if (w->pin) (void)hipHostFree(w->pin);
+  if (w->s) (void)hipStreamDestroy(w->s);
+  delete w;
+}
+
+// the arguments every transform entry shares; nid_level out
+static int voc_check(const orbv_handle *v, int levelsup, int *nid_level) {
+  if (!v) return voc_fail("orbv: NULL handle");
+  const long long lvl = (long long)v->L - (long long)levelsup;
+  *nid_level = lvl > 0x7fffffff ? 0x7fffffff : lvl < 0 ? 0 : (int)lvl;
+  if (v->n_words > 0 && *nid_level > 0 && v->min_leaf_level < *nid_level) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "orbv_transform: node %u has no children and a weight > 0 at level %d, above level m_L - levelsup = %d - %d: the "
+             "reference leaves the NodeId of a feature that ends there unset", v->min_leaf_node, v->min_leaf_level, v->L, levelsup);
+    return voc_fail(buf);
+  }
+  return 0;
+}
+
+static void voc_launch(const orbv_handle *v, hipStream_t s, const uint8_t *d_q, LiveCount live, int cap, int nframes, int nid_level,
+                       int32_t *d_entry, uint32_t *d_word, uint32_t *d_node, uint32_t *d_bow_id, double *d_bow_val, int32_t *d_n_bow,
+                       uint32_t *d_fv_node_id, int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv, int descend_form) {
+  VocDescendParams D;
+  D.desc = v->d_desc; D.rec = v->d_rec; D.q = d_q; D.n = live; D.cap = cap; D.nid_level = nid_level;
+  D.entry = d_entry; D.word = d_word; D.node = d_node;
+  if (descend_form == 1) hipLaunchKernelGGL(k_voc_descend_lane, dim3((unsigned)((cap + 255) / 256), (unsigned)nframes), dim3(256), 0, s, D);
+  else hipLaunchKernelGGL(k_voc_descend, dim3((unsigned)((cap + 15) / 16), (unsigned)nframes), dim3(256), 0, s, D);
+  VocCollectParams C;
+  C.rec = v->d_rec; C.weight = v->d_weight; C.n = live; C.cap = cap; C.weighting = v->weighting; C.scoring = v->scoring;
+  C.entry = d_entry; C.node = d_node; C.bow_id = d_bow_id; C.bow_val = d_bow_val; C.n_bow = d_n_bow;
+  C.fv_node_id = d_fv_node_id; C.fv_start = d_fv_start; C.fv_idx = d_fv_idx; C.n_fv = d_n_fv;
+  hipLaunchKernelGGL(k_voc_collect, dim3((unsigned)nframes), dim3(VOC_THREADS), sizeof(uint64_t) * (size_t)voc_p2(cap), s, C);
+}
+
+extern "C" {
+
+const char *orbv_last_error(const orbv_t *) { return g_voc_err.c_str(); }
+
+void orbv_destroy(orbv_t *v) {
+  if (!v) return;
+  if (v->device >= 0) {
+    (void)hipSetDevice(v->device);
+    for (VocWork *w : v->pool) voc_free_work(w);
+    if (v->d_desc) (void)hipFree(v->d_desc);
+    if (v->d_rec) (void)hipFree(v->d_rec);
+    if (v->d_weight) (void)hipFree(v->d_weight);
+  }
+  delete v;
+}
+
+orbv_t *orbv_create(const orbv_nodes_t *nodes, int device) {
+  g_voc_err.clear();
+  if (!nodes || nodes->n_nodes < 1 || !nodes->parent || !nodes->is_leaf || !nodes->descriptor || !nodes->weight || device < -1) {
+    voc_fail("orbv_create: NULL table, n_nodes < 1 or device < -1");
+    return nullptr;
+  }
+  if (nodes->scoring == VOC_L2_NORM) { voc_fail("orbv_create: L2_NORM scoring is not supported (csrc/orb_ref_voc.h)"); return nullptr; }
+  if (nodes->scoring < 0 || nodes->scoring > VOC_DOT_PRODUCT || nodes->weighting < 0 || nodes->weighting > VOC_BINARY) {
+    voc_fail("orbv_create: weighting outside [0, 3] or scoring outside [0, 5]");
+    return nullptr;
+  }
+  const int N = nodes->n_nodes;
+  for (int i = 1; i < N; i++)
+    if (nodes->parent[i] >= (uint32_t)i) {   // the loader appends: a node's parent is loaded before it
+      char buf[96];
+      snprintf(buf, sizeof buf, "orbv_create: node %d has parent %u, not below its own id", i, nodes->parent[i]);
+      voc_fail(buf);
+      return nullptr;
+    }
+  orbv_handle *v = new orbv_handle;
+  v->device = device; v->k = nodes->k; v->L = nodes->L; v->weighting = nodes->weighting; v->scoring = nodes->scoring; v->n_nodes = N;
+  // children in ascending node id = the loader's push_back order (TemplatedVocabulary.h:1385-1392)
+  std::vector<int32_t> nchild(N, 0), first(N + 1, 0), fill(N, 0), child(N > 1 ? N - 1 : 0);
+  for (int i = 1; i < N; i++) nchild[nodes->parent[i]]++;
+  for (int i = 0; i < N; i++) first[i + 1] = first[i] + nchild[i];
+  for (int i = 1; i < N; i++) { const uint32_t p = nodes->parent[i]; child[first[p] + fill[p]++] = i; }
+  // word ids over the flagged nodes in id order (:1408-1415); node 0 is not in the file and is never flagged by the loader
+  std::vector<uint32_t> word(N, 0);
+  for (int i = 1; i < N; i++) if (nodes->is_leaf[i]) word[i] = (uint32_t)v->n_words++;
+  // entries: breadth first, so that the children of a node are contiguous and the upper levels share cache lines
+  std::vector<int32_t> node_of(N), level(N, 0);
+  v->rec.resize(N); v->desc.resize(8 * (size_t)N); v->weight.resize(N);
+  node_of[0] = 0;
+  int next = 1;
+  v->min_leaf_level = 0x7fffffff;
+  for (int e = 0; e < N; e++) {
+    const int id = node_of[e];
+    VocRec &r = v->rec[e];
+    r.first = nchild[id] ? next : 0; r.count = nchild[id]; r.node = (uint32_t)id; r.word = word[id];
+    for (int c = 0; c < nchild[id]; c++) { const int ch = child[first[id] + c]; level[next] = level[e] + 1; node_of[next++] = ch; }
+    memcpy(&v->desc[8 * (size_t)e], nodes->descriptor + 32 * (size_t)id, 32);
+    v->weight[e] = nodes->weight[id];
+    v->max_children = std::max(v->max_children, nchild[id]);
+    if (nchild[id] == 0 && nodes->weight[id] > 0 && (level[e] < v->min_leaf_level || (level[e] == v->min_leaf_level && (uint32_t)id < v->min_leaf_node))) {
+      v->min_leaf_level = level[e]; v->min_leaf_node = (uint32_t)id;
+    }
+  }
+  if (device < 0) return v;
+  const hipError_t e0 = hipSetDevice(device);
+  hipError_t e = e0;
+  if (e == hipSuccess) e = voc_raise_lds(device);
+  if (e == hipSuccess) e = hipMalloc(&v->d_desc, 32 * (size_t)N);
+  if (e == hipSuccess) e = hipMalloc(&v->d_rec, sizeof(VocRec) * (size_t)N);
+  if (e == hipSuccess) e = hipMalloc(&v->d_weight, sizeof(double) * (size_t)N);
+  if (e == hipSuccess) e = hipMemcpy(v->d_desc, v->desc.data(), 32 * (size_t)N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(v->d_rec, v->rec.data(), sizeof(VocRec) * (size_t)N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(v->d_weight, v->weight.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    const std::string what = std::string("orbv_create: HIP: ") + hipGetErrorString(e);
+    if (e0 != hipSuccess) v->device = -1;   // nothing of the device to free
+    orbv_destroy(v);
+    g_voc_err = what;
+    return nullptr;
+  }
+  return v;
+}
+
+int orbv_n_nodes(const orbv_t *v) { return v ? v->n_nodes : ORBX_E_ARG; }
+int orbv_n_words(const orbv_t *v) { return v ? v->n_words : ORBX_E_ARG; }
+int orbv_max_children(const orbv_t *v) { return v ? v->max_children : ORBX_E_ARG; }
+int orbv_min_leaf_level(const orbv_t *v) { return v ? v->min_leaf_level : ORBX_E_ARG; }
+
+int orbv_transform_host(const orbv_t *v, const uint8_t *descriptors, int n, int levelsup, uint32_t *word_of_feature, uint32_t *node_of_feature,
+                        uint32_t *bow_id, double *bow_val, int32_t *n_bow, uint32_t *fv_node_id, int32_t *fv_start, int32_t *fv_idx,
+                        int32_t *n_fv) {
+  int nid_level;
+  const int rc = voc_check(v, levelsup, &nid_level);
+  if (rc < 0) return rc;
+  if (n < 0 || n > ORBM_MAX_KEYPOINTS) return voc_fail("orbv_transform_host: n outside [0, ORBM_MAX_KEYPOINTS]");
+  if (!n_bow || !n_fv || !fv_start || (n > 0 && (!descriptors || !bow_id || !bow_val || !fv_node_id || !fv_idx)))
+    return voc_fail("orbv_transform_host: NULL argument");
+  std::map<uint32_t, double> bow;                      // DBoW2::BowVector
+  std::map<uint32_t, std::vector<uint32_t>> fv;        // DBoW2::FeatureVector
+  const bool adds = voc_adds_weight(v->weighting), must = voc_must_normalize(v->scoring);
+  if (v->n_words > 0) {                                // empty() (:1134)
+    for (int i = 0; i < n; i++) {
+      uint32_t q[8];
+      memcpy(q, descriptors + 32 * (size_t)i, 32);
+      int32_t entry; uint32_t nid;
+      voc_descend(v->desc.data(), v->rec.data(), q, nid_level, &entry, &nid);
+      const uint32_t id = v->rec[entry].word;
+      const double w = v->weight[entry];
+      if (word_of_feature) word_of_feature[i] = id;
+      if (node_of_feature) node_of_feature[i] = nid;
+      if (w > 0) {                                     // :1157, :1185
+        auto it = bow.lower_bound(id);
+        const bool first = it == bow.end() || bow.key_comp()(id, it->first);
+        if (first) it = bow.insert(it, std::make_pair(id, 0.0));
+        voc_add(&it->second, w, first, adds);
+        fv[nid].push_back((uint32_t)i);
+      }
+    }
+    if (adds && !must && !bow.empty()) {               // :1164-1170
+      const double nd = (double)bow.size();
+      for (auto &kv : bow) kv.second = voc_div(kv.second, nd);
+    }
+    if (must) {                                        // BowVector::normalize(L1)
+      double norm = 0.0;
+      for (auto &kv : bow) voc_l1_step(&norm, kv.second);
+      if (norm > 0.0) for (auto &kv : bow) kv.second = voc_div(kv.second, norm);
+    }
+  } else {
+    for (int i = 0; i < n; i++) { if (word_of_feature) word_of_feature[i] = 0; if (node_of_feature) node_of_feature[i] = 0; }
+  }
+  int t = 0;
+  for (const auto &kv : bow) { bow_id[t] = kv.first; bow_val[t] = kv.second; t++; }
+  *n_bow = t;
+  int g = 0, at = 0;
+  for (const auto &kv : fv) {
+    fv_node_id[g] = kv.first; fv_start[g] = at; g++;
+    for (uint32_t i : kv.second) fv_idx[at++] = (int32_t)i;
+  }
+  fv_start[g] = at;
+  *n_fv = g;
+  return 0;
+}
+
+int orbv_transform(orbv_t *v, const uint8_t *descriptors, int n, int levelsup, uint32_t *word_of_feature, uint32_t *node_of_feature,
+                   uint32_t *bow_id, double *bow_val, int32_t *n_bow, uint32_t *fv_node_id, int32_t *fv_start, int32_t *fv_idx,
+                   int32_t *n_fv) {
+  // everything is validated before anything is written or launched
+  int nid_level;
+  const int rc = voc_check(v, levelsup, &nid_level);
+  if (rc < 0) return rc;
+  if (v->device < 0) return voc_fail("orbv_transform: the handle was created with device = -1 and has no device tables");
+  if (n < 0 || n > ORBM_MAX_KEYPOINTS) return voc_fail("orbv_transform: n outside [0, ORBM_MAX_KEYPOINTS]");
+  if (!n_bow || !n_fv || !fv_start || (n > 0 && (!descriptors || !bow_id || !bow_val || !fv_node_id || !fv_idx)))
+    return voc_fail("orbv_transform: NULL argument");
+  if (n == 0 || v->n_words == 0) {
+    for (int i = 0; i < n; i++) { if (word_of_feature) word_of_feature[i] = 0; if (node_of_feature) node_of_feature[i] = 0; }
+    *n_bow = 0; *n_fv = 0; fv_start[0] = 0;
+    return 0;
+  }
+  VCHECK(hipSetDevice(v->device));
+  // one block: descriptors | entry | word | node | bow_id | fv_node_id | fv_idx | fv_start[n + 1] | n_bow, n_fv | bow_val (8-byte aligned)
+  const size_t N = (size_t)n;
+  const size_t o_entry = 32 * N, o_word = o_entry + 4 * N, o_node = o_word + 4 * N, o_bid = o_node + 4 * N, o_fnode = o_bid + 4 * N,
+               o_fidx = o_fnode + 4 * N, o_fstart = o_fidx + 4 * N, o_cnt = o_fstart + 4 * (N + 1), o_bval = (o_cnt + 8 + 7) & ~(size_t)7,
+               bytes = o_bval + 8 * N;
+  // a workspace from the pool (or a new one) for the length of this call; it goes back on every way out
+  struct Lease {
+    orbv_handle *v; VocWork *w = nullptr;
+    explicit Lease(orbv_handle *h) : v(h) {
+      std::lock_guard<std::mutex> lock(v->mu);
+      if (!v->pool.empty()) { w = v->pool.back(); v->pool.pop_back(); }
+    }
+    ~Lease() { if (w) { std::lock_guard<std::mutex> lock(v->mu); v->pool.push_back(w); } }
+  } lease(v);
+  if (!lease.w) lease.w = new VocWork;
+  VocWork *w = lease.w;
+  if (!w->s) VCHECK(hipStreamCreateWithFlags(&w->s, hipStreamNonBlocking));
+  if (w->bytes < bytes) {
+    if (w->dev) VCHECK(hipFree(w->dev));
+    w->dev = nullptr;
+    if (w->pin) VCHECK(hipHostFree(w->pin));
+    w->pin = nullptr; w->bytes = 0;
+    const size_t room = bytes + bytes / 2;
+    VCHECK(hipMalloc(&w->dev, room));
+    VCHECK(hipHostMalloc(&w->pin, room, hipHostMallocDefault));
+    w->bytes = room;
+  }
+  memcpy(w->pin, descriptors, 32 * N);
+  VCHECK(hipMemcpyAsync(w->dev, w->pin, 32 * N, hipMemcpyHostToDevice, w->s));
+  uint8_t *d = w->dev;
+  int32_t *d_cnt = (int32_t *)(d + o_cnt);
+  voc_launch(v, w->s, d, LiveCount{nullptr, 0, n}, n, 1, nid_level, (int32_t *)(d + o_entry), (uint32_t *)(d + o_word), (uint32_t *)(d + o_node),
+             (uint32_t *)(d + o_bid), (double *)(d + o_bval), d_cnt, (uint32_t *)(d + o_fnode), (int32_t *)(d + o_fstart), (int32_t *)(d + o_fidx),
+             d_cnt + 1, 0);
+  VCHECK(hipGetLastError());
+  VCHECK(hipMemcpyAsync(w->pin + o_word, d + o_word, bytes - o_word, hipMemcpyDeviceToHost, w->s));
+  VCHECK(hipStreamSynchronize(w->s));
+  const uint8_t *h = w->pin;
+  const int32_t nb = ((const int32_t *)(h + o_cnt))[0], nf = ((const int32_t *)(h + o_cnt))[1];
+  const int32_t live = nf >= 0 && nf <= n ? ((const int32_t *)(h + o_fstart))[nf] : -1;
+  if (nb < 0 || nb > n || nf < 0 || nf > n || live < 0 || live > n) { g_voc_err = "orbv_transform: the device returned counts outside [0, n]"; return ORBX_E_HIP; }
+  if (word_of_feature) memcpy(word_of_feature, h + o_word, 4 * N);
+  if (node_of_feature) memcpy(node_of_feature, h + o_node, 4 * N);
+  memcpy(bow_id, h + o_bid, 4 * (size_t)nb);
+  memcpy(bow_val, h + o_bval, 8 * (size_t)nb);
+  memcpy(fv_node_id, h + o_fnode, 4 * (size_t)nf);
+  memcpy(fv_start, h + o_fstart, 4 * ((size_t)nf + 1));
+  memcpy(fv_idx, h + o_fidx, 4 * (size_t)live);
+  *n_bow = nb; *n_fv = nf;
+  return 0;
+}
+
+size_t orbv_batch_scratch_bytes(int nframes, int cap) {
+  if (nframes < 0 || cap < 0) return 0;
+  return 3 * sizeof(int32_t) * (size_t)nframes * (size_t)cap;
+}
+
+static int voc_batch(orbv_t *v, const uint8_t *d_descriptors, int nframes, int cap, const int32_t *d_n, int n_stride, int levelsup,
+                     uint32_t *d_word, uint32_t *d_node, uint32_t *d_bow_id, double *d_bow_val, int32_t *d_n_bow, uint32_t *d_fv_node_id,
+                     int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv, void *d_scratch, void *stream, int descend_form) {
+  int nid_level;
+  const int rc = voc_check(v, levelsup, &nid_level);
+  if (rc < 0) return rc;
+  if (v->device < 0) return voc_fail("orbv_transform_batch_device: the handle was created with device = -1 and has no device tables");
+  if (nframes < 0 || nframes > 65535 || cap <= 0 || cap > ORBM_MAX_KEYPOINTS || n_stride <= 0)
+    return voc_fail("orbv_transform_batch_device: nframes outside [0, 65535], cap outside [1, ORBM_MAX_KEYPOINTS] or n_stride <= 0");
+  if (nframes == 0) return 0;
+  if (!d_descriptors || !d_n || !d_bow_id || !d_bow_val || !d_n_bow || !d_fv_node_id || !d_fv_start || !d_fv_idx || !d_n_fv || !d_scratch)
+    return voc_fail("orbv_transform_batch_device: NULL argument");
+  if (((uintptr_t)d_descriptors & 15) || ((uintptr_t)d_bow_val & 7) || ((uintptr_t)d_scratch & 3))
+    return voc_fail("orbv_transform_batch_device: descriptors not 16-byte aligned, bow_val not 8-byte aligned or scratch not 4-byte aligned");
+  VCHECK(hipSetDevice(v->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t FC = (size_t)nframes * (size_t)cap;
+  if (v->n_words == 0) {   // empty() (:1134): empty containers for every frame
+    VCHECK(hipMemsetAsync(d_n_bow, 0, sizeof(int32_t) * (size_t)nframes, s));
+    VCHECK(hipMemsetAsync(d_n_fv, 0, sizeof(int32_t) * (size_t)nframes, s));
+    VCHECK(hipMemsetAsync(d_fv_start, 0, sizeof(int32_t) * (size_t)nframes * ((size_t)cap + 1), s));
+    if (d_word) VCHECK(hipMemsetAsync(d_word, 0, 4 * FC, s));
+    if (d_node) VCHECK(hipMemsetAsync(d_node, 0, 4 * FC, s));
+    return 0;
+  }
+  int32_t *sc = (int32_t *)d_scratch;
+  voc_launch(v, s, d_descriptors, LiveCount{d_n, n_stride, 0}, cap, nframes, nid_level, sc, d_word ? d_word : (uint32_t *)(sc + FC),
+             d_node ? d_node : (uint32_t *)(sc + 2 * FC), d_bow_id, d_bow_val, d_n_bow, d_fv_node_id, d_fv_start, d_fv_idx, d_n_fv, descend_form);
+  VCHECK(hipGetLastError());
+  return 0;
+}
+
+int orbv_transform_batch_device(orbv_t *v, const uint8_t *d_descriptors, int nframes, int cap, const int32_t *d_n, int n_stride, int levelsup,
+                                uint32_t *d_word, uint32_t *d_node, uint32_t *d_bow_id, double *d_bow_val, int32_t *d_n_bow,
+                                uint32_t *d_fv_node_id, int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv, void *d_scratch, void *stream) {
+  return voc_batch(v, d_descriptors, nframes, cap, d_n, n_stride, levelsup, d_word, d_node, d_bow_id, d_bow_val, d_n_bow, d_fv_node_id,
+                   d_fv_start, d_fv_idx, d_n_fv, d_scratch, stream, 0);
+}
+
+int orbv_transform_batch_device_form(orbv_t *v, int descend_form, const uint8_t *d_descriptors, int nframes, int cap, const int32_t *d_n,
+                                     int n_stride, int levelsup, uint32_t *d_word, uint32_t *d_node, uint32_t *d_bow_id, double *d_bow_val,
+                                     int32_t *d_n_bow, uint32_t *d_fv_node_id, int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv,
+                                     void *d_scratch, void *stream) {
+  if (descend_form != 0 && descend_form != 1) return voc_fail("orbv_transform_batch_device_form: descend_form outside {0, 1}");
+  return voc_batch(v, d_descriptors, nframes, cap, d_n, n_stride, levelsup, d_word, d_node, d_bow_id, d_bow_val, d_n_bow, d_fv_node_id,
+                   d_fv_start, d_fv_idx, d_n_fv, d_scratch, stream, descend_form);
 }
 
 }  // extern "C"

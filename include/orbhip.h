@@ -1270,6 +1270,99 @@ float orbm_get_last_ms(orbm_t *m);
  * orbx_get_stage_ms): ms[0] = k_match_walk + k_match_scan (+ k_topk_merge), ms[1] = k_match_resolve.  Returns 2, or 0 if unavailable. */
 int orbm_get_stage_ms(orbm_t *m, float *ms, int cap);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>): the transform behind Frame::ComputeBoW
+ * (Frame.cc:828-835) and KeyFrame::ComputeBoW (KeyFrame.cc:100-110), both
+ *     mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)
+ * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1126-1194 over the descent of :1217-1259, BowVector.cpp:34-84,
+ * FeatureVector.cpp:31-45).  It produces the DBoW2::FeatureVector that orbm_keyframe_t carries into SearchByBoW,
+ * SearchForTriangulation and CreateNewMapPoints.  The arithmetic is stated once, in csrc/orb_ref_voc.h, for the host form and
+ * the kernels (csrc/orb_voc_kernels.h).  L2_NORM scoring (type 1) is refused; so is a levelsup for which the vocabulary has a
+ * childless node of weight > 0 above level L - levelsup (the reference leaves the NodeId of a feature that ends there unset, :1251,
+ * and files the feature under it, :1160).  A childless node of weight <= 0 up there only stops features and is accepted.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* m_nodes flattened in id order; node 0 is the root (it is not in the text file, TemplatedVocabulary.h:1376-1377).
+ * The children of a node are rebuilt in ascending node id, which is the loader's push_back order (:1385-1392); word ids are
+ * counted over the nodes with is_leaf set, in id order (:1408-1415; is_leaf[0] is not read).  The child count of a node is
+ * whatever parent[] says and is NOT bounded by k: a trailing empty line of the text file makes one more node under the
+ * root (its failed `>> pid` leaves 0, :1389-1392), so the root of a loaded k-ary vocabulary can own k + 1 children.  The
+ * descent ends at a node without children (Node::isLeaf() is children.empty(), :328), flagged or not; an unflagged one
+ * answers word 0 (Node(), :316) with its own weight. */
+typedef struct {
+  int32_t k, L;                /* m_k, m_L (L gives the level of the FeatureVector's nodes, :1226) */
+  int32_t weighting;           /* m_weighting: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY (BowVector.h:39-45) */
+  int32_t scoring;             /* m_scoring: 0 L1_NORM, 1 L2_NORM (refused), 2 CHI_SQUARE, 3 KL, 4 BHATTACHARYYA,
+                                  5 DOT_PRODUCT (BowVector.h:48-56); decides the normalisation, ScoringObject.h:74-89 */
+  int32_t n_nodes;             /* m_nodes.size() >= 1 */
+  const uint32_t *parent;      /* [n_nodes] Node::parent; parent[i] < i for i >= 1 (parent[0] is not read) */
+  const uint8_t *is_leaf;      /* [n_nodes] the node owns a word: m_words[node.word_id] == &node */
+  const uint8_t *descriptor;   /* [n_nodes][32] Node::descriptor */
+  const double *weight;        /* [n_nodes] Node::weight */
+} orbv_nodes_t;
+
+typedef struct orbv_handle orbv_t;
+
+/* Copies the tables, re-laid so that the children of a node are contiguous.  device >= 0 also uploads them; device = -1 gives
+ * a handle WITHOUT device tables, on which only orbv_transform_host works and the device entries return ORBX_E_ARG: it
+ * exists so that the statement can be tested where there is no GPU, and is not a fallback.  NULL on failure (a NULL table,
+ * n_nodes < 1, parent[i] >= i, weighting / scoring out of range, L2_NORM scoring, a HIP error), with the reason in
+ * orbv_last_error(NULL). */
+orbv_t *orbv_create(const orbv_nodes_t *nodes, int device);
+void orbv_destroy(orbv_t *v);
+/* The reason of the CALLING THREAD's last failed orbv_* call (Tracking and LocalMapping share one vocabulary, so the text is
+ * kept per thread, not per handle); v may be NULL. */
+const char *orbv_last_error(const orbv_t *v);
+/* m_nodes.size(), m_words.size(), the largest child count, the level (root = 0) of the shallowest childless node of weight > 0
+ * (INT32_MAX without one). */
+int orbv_n_nodes(const orbv_t *v);
+int orbv_n_words(const orbv_t *v);
+int orbv_max_children(const orbv_t *v);
+int orbv_min_leaf_level(const orbv_t *v);
+
+/* transform(features, v, fv, levelsup) (TemplatedVocabulary.h:1126-1194) for descriptors[n][32], host pointers.
+ *   word_of_feature[n], node_of_feature[n]  (optional) WordId and NodeId of every feature, stopped ones included (:1217-1259); 0 as
+ *                                           the NodeId of a stopped feature that ended above level L - levelsup
+ *   bow_id[n], bow_val[n], *n_bow           DBoW2::BowVector in key order: the first *n_bow entries are written
+ *   fv_node_id[n], fv_start[n + 1], fv_idx[n], *n_fv
+ *                                           DBoW2::FeatureVector exactly as orbm_keyframe_t reads it (node_id, node_start,
+ *                                           node_idx, n_nodes): the first *n_fv, *n_fv + 1 and fv_start[*n_fv] entries
+ * A feature whose word has weight > 0 enters both containers, a feature on a stop word neither (:1157, :1185).  n == 0 and a
+ * vocabulary without words (:1134) give empty containers (*n_bow = *n_fv = 0, fv_start[0] = 0).
+ * orbv_transform_host is csrc/orb_ref_voc.h in plain C++ over the handle's host tables with two std::maps.  orbv_transform is
+ * one upload, k_voc_descend and k_voc_collect, one download, one synchronisation; it may be called on one handle from several
+ * host threads at once (each call takes a stream and a workspace from the handle's pool).
+ * Both validate everything before anything is written or launched.  ORBX_E_ARG: a NULL handle or required pointer, n < 0 or
+ * above ORBM_MAX_KEYPOINTS, a levelsup the vocabulary's shape refuses (orbv_last_error names the node), orbv_transform on a
+ * device = -1 handle.  Returns 0, ORBX_E_ARG or ORBX_E_HIP. */
+int orbv_transform_host(const orbv_t *v, const uint8_t *descriptors, int n, int levelsup, uint32_t *word_of_feature,
+                        uint32_t *node_of_feature, uint32_t *bow_id, double *bow_val, int32_t *n_bow, uint32_t *fv_node_id,
+                        int32_t *fv_start, int32_t *fv_idx, int32_t *n_fv);
+int orbv_transform(orbv_t *v, const uint8_t *descriptors, int n, int levelsup, uint32_t *word_of_feature,
+                   uint32_t *node_of_feature, uint32_t *bow_id, double *bow_val, int32_t *n_bow, uint32_t *fv_node_id,
+                   int32_t *fv_start, int32_t *fv_idx, int32_t *n_fv);
+
+/* The same transform (TemplatedVocabulary.h:1126-1194) for `nframes` frames resident in HBM, asynchronous on `stream`: the same
+ * two kernels with a grid over all frames.  d_descriptors[nframes][cap][32] (16-byte aligned); frame p has
+ * min(max(d_n[p * n_stride], 0), cap) live descriptors, so the extractor's d_counts plugs in with n_stride = 2.  Frame p's
+ * outputs start at p * cap (d_fv_start at p * (cap + 1)) in the per-frame layout above; d_n_bow[nframes], d_n_fv[nframes];
+ * d_word / d_node [nframes][cap] are optional.  d_scratch: orbv_batch_scratch_bytes(nframes, cap) bytes of device memory that
+ * belong to the call until the stream has passed it (no state of the handle is written, so calls may overlap).
+ * ORBX_E_ARG: as orbv_transform, nframes outside [0, 65535], cap outside [1, ORBM_MAX_KEYPOINTS], n_stride <= 0, a
+ * misaligned d_descriptors / d_bow_val.  nframes == 0 launches nothing.
+ * orbv_transform_batch_device_form is the same call with the descent kernel chosen: 0 = k_voc_descend (a 16-lane row per
+ * descriptor, what every other entry runs), 1 = k_voc_descend_lane (a lane per descriptor); results do not depend on it, it
+ * exists for tests and for tools/bow_transform_bench.py. */
+size_t orbv_batch_scratch_bytes(int nframes, int cap);
+int orbv_transform_batch_device(orbv_t *v, const uint8_t *d_descriptors, int nframes, int cap, const int32_t *d_n, int n_stride,
+                                int levelsup, uint32_t *d_word, uint32_t *d_node, uint32_t *d_bow_id, double *d_bow_val,
+                                int32_t *d_n_bow, uint32_t *d_fv_node_id, int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv,
+                                void *d_scratch, void *stream);
+int orbv_transform_batch_device_form(orbv_t *v, int descend_form, const uint8_t *d_descriptors, int nframes, int cap,
+                                     const int32_t *d_n, int n_stride, int levelsup, uint32_t *d_word, uint32_t *d_node,
+                                     uint32_t *d_bow_id, double *d_bow_val, int32_t *d_n_bow, uint32_t *d_fv_node_id,
+                                     int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv, void *d_scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,283 @@
+"""CPU: the vocabulary transform behind Frame::ComputeBoW / KeyFrame::ComputeBoW (orbv_* of include/orbhip.h).
+
+The host form orbv_transform_host - csrc/orb_ref_voc.h in plain C++, the same functions the kernels call - against the literal model of
+tests/voc_model.py on the scenes of tests/voc_scene.py, doubles by bit pattern; what the scenes must contain for that comparison to mean
+something; the refusals; the text loader; symbols, struct layout and citations; the drop-in snippet against the reference's headers.
+Everything here runs on a handle made with device = -1 (no device tables)."""
+import ctypes as C
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import voc_model as VM
+import voc_scene as VS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF = "/root/reference"
+REF_INC = os.path.join(REF, "include")
+
+
+@pytest.fixture(scope="module")
+def vocs(pkg):
+    made = {}
+
+    def get(name, weighting, scoring):
+        key = (name, weighting, scoring)
+        if key not in made:
+            made[key] = VS.vocabulary(pkg, name, weighting, scoring, device=-1)
+        return made[key]
+    return get
+
+
+@pytest.mark.parametrize("name", VS.NAMES)
+def test_host_form_equals_model(vocs, name):
+    S = VS.scene(name)
+    refused = 0
+    for weighting in VS.WEIGHTINGS:
+        for scoring in VS.SCORINGS:
+            voc, model = vocs(name, weighting, scoring), VS.model(name, weighting, scoring)
+            assert voc.n_nodes == len(S["parent"]) and voc.n_words == model.n_words
+            assert voc.max_children == max(len(c) for c in model.children) and voc.min_leaf_level == model.min_leaf_level
+            for levelsup in VS.levelsups(S["L"]):
+                for n in VS.N_VALUES:
+                    what = "%s weighting %d scoring %d levelsup %d n %d" % (name, weighting, scoring, levelsup, n)
+                    refused += VS.check_against_model(voc, model, S["queries"][:n], levelsup, what) is None
+    # the shapes decide which levelsup the library refuses: the irregular tree and the wide one (its 21st root child, of weight 0.7) have
+    # shallow leaves that let features in; the same child with the loader's weight 0 only stops features
+    assert (refused > 0) == (name in ("irregular", "wide"))
+
+
+@pytest.mark.parametrize("scoring", [2, 3, 4])
+def test_other_l1_scorings(vocs, scoring):
+    """CHI_SQUARE, KL and BHATTACHARYYA normalise like L1_NORM (ScoringObject.h:80-86)."""
+    S = VS.scene("regular")
+    got = vocs("regular", 0, scoring).transform_host(S["queries"], 4)
+    VM.same(got, VS.model("regular", 0, 0).transform(S["queries"], 4), "scoring %d" % scoring)
+
+
+def test_largest_frame_on_the_small_tree(vocs):
+    voc, model = vocs("flat", 0, 0), VS.model("flat", 0, 0)
+    desc = VS.flat_big(15361)
+    VS.check_against_model(voc, model, desc[:15360], 1, "n = 15360")
+    with pytest.raises(ValueError):
+        voc.transform_host(desc, 1)
+
+
+def test_scenes_hold_what_the_comparison_relies_on():
+    seq_differs = order_differs = ties = stops = 0
+    max_pos = 0
+    for name in VS.NAMES:
+        S = VS.scene(name)
+        t = VS.model(name, 0, 0).transform(S["queries"], S["L"])
+        st = t["stats"]
+        ties += st["tie"]
+        stops += st["stop"]
+        max_pos = max(max_pos, st["max_pos"])
+        for wid, ws in st["counts"].items():
+            acc = ws[0]
+            for w in ws[1:]:
+                acc += w
+            if len(set(ws)) == 1 and acc != len(ws) * ws[0]:
+                seq_differs += 1                                 # k sequential adds of w are not k * w
+        vals = st["unnormalised"]
+        fwd = bwd = 0.0
+        for v in vals:
+            fwd += abs(v)
+        for v in reversed(vals):
+            bwd += abs(v)
+        order_differs += fwd != bwd and fwd != math.fsum(vals)
+    assert seq_differs >= 1, "no word whose sequential sum differs from count x weight"
+    assert order_differs >= 1, "no frame whose forward L1 sum differs from the reverse one and from math.fsum"
+    assert ties >= 20, "too few ties decided by position"
+    assert stops >= 10, "too few stop-word hits"
+    assert max_pos >= 16, "no chosen child at a position >= 16"
+    # the wide tree: the root owns k + 1 children, the last one unflagged and childless, and it is hit (word 0 with its own weight)
+    W = VS.scene("wide")
+    m = VS.model("wide", 0, 0)
+    extra = len(W["parent"]) - 1
+    assert len(m.children[0]) == W["k"] + 1 and m.children[0][-1] == extra and not W["is_leaf"][extra] and W["weight"][extra] > 0
+    t = m.transform(W["queries"], W["L"])
+    ws = t["stats"]["counts"][0]
+    assert W["weight"][extra] in ws and len(set(ws)) >= 1
+    # the same child as the loader leaves it (weight 0) is hit too, at a levelsup that puts the FeatureVector's level below it: stopped
+    A = VS.scene("wide_as_loaded")
+    ma = VS.model("wide_as_loaded", 0, 0)
+    ta = ma.transform(A["queries"], 0)
+    extra_a = len(A["parent"]) - 1
+    ends = [ma.path(int.from_bytes(q.tobytes(), "little"))[0][-1] for q in A["queries"]]
+    assert ends.count(extra_a) >= 3 and ma.min_leaf_level == 2 and A["weight"][extra_a] == 0
+    assert all(ta["node"][i] == 0 for i, e in enumerate(ends) if e == extra_a)
+    # twins below and above position 16: the first of two equal descriptors wins
+    kids = m.children[0]
+    for a, b in ((3, 7), (17, 19), (5, 18)):
+        q = int.from_bytes(W["descriptor"][kids[b]].tobytes(), "little")
+        assert m.path(q)[0][0] == kids[a]
+
+
+def _raw(pkg, voc, fn, desc, n, levelsup, null=()):
+    """One direct call with sentinel-filled outputs: (rc, outputs)."""
+    L = pkg.load()
+    m = max(n, 1)
+    outs = dict(word=np.full(m, 0xABCD, np.uint32), node=np.full(m, 0xABCD, np.uint32), bow_id=np.full(m, 0xABCD, np.uint32),
+                bow_val=np.full(m, -7.5, np.float64), n_bow=np.full(1, -77, np.int32), fv_node_id=np.full(m, 0xABCD, np.uint32),
+                fv_start=np.full(m + 1, -77, np.int32), fv_idx=np.full(m, -77, np.int32), n_fv=np.full(1, -77, np.int32))
+    before = {k: v.copy() for k, v in outs.items()}
+    p = lambda k: None if k in null else outs[k].ctypes.data_as(C.c_void_p)
+    d = None if "desc" in null else np.ascontiguousarray(desc).ctypes.data_as(C.c_void_p)
+    rc = getattr(L, fn)(None if "handle" in null else voc.v, d, n, levelsup, p("word"), p("node"), p("bow_id"), p("bow_val"), p("n_bow"),
+                        p("fv_node_id"), p("fv_start"), p("fv_idx"), p("n_fv"))
+    untouched = all(np.array_equal(outs[k], before[k]) for k in outs)
+    return rc, untouched
+
+
+def test_refusals_write_nothing(pkg, vocs):
+    S = VS.scene("irregular")
+    q = S["queries"][:65]
+    # L2_NORM scoring
+    with pytest.raises(ValueError) as e:
+        VS.vocabulary(pkg, "regular", 0, 1, device=-1)
+    assert "L2_NORM" in str(e.value)
+    # a table whose parent does not precede its node
+    bad = S["parent"].copy()
+    bad[5] = 5
+    with pytest.raises(ValueError):
+        pkg.ORBVocabulary.from_nodes(S["k"], S["L"], 0, 0, bad, S["is_leaf"], S["descriptor"], S["weight"], device=-1)
+    voc = vocs("irregular", 0, 0)
+    for fn in ("orbv_transform_host", "orbv_transform"):
+        # a shallow leaf: level 2 < L - levelsup = 3
+        rc, untouched = _raw(pkg, voc, fn, q, len(q), 1)
+        assert rc == pkg.E_ARG and untouched, fn
+        assert b"node" in pkg.load().orbv_last_error(None)
+        # n too large, n negative
+        big = np.zeros((15361, 32), np.uint8)
+        for n in (15361, -1):
+            rc, untouched = _raw(pkg, voc, fn, big, n, 4)
+            assert rc == pkg.E_ARG and untouched, fn
+        # NULLs
+        for null in ("handle", "desc", "bow_id", "bow_val", "n_bow", "fv_node_id", "fv_start", "fv_idx", "n_fv"):
+            rc, untouched = _raw(pkg, voc, fn, q, len(q), 4, null=(null,))
+            assert rc == pkg.E_ARG and untouched, (fn, null)
+    # the device entries on a handle without device tables
+    rc, untouched = _raw(pkg, voc, "orbv_transform", q, len(q), 4)
+    assert rc == pkg.E_ARG and untouched and b"device = -1" in pkg.load().orbv_last_error(None)
+    with pytest.raises(ValueError):
+        voc.transform(q)
+    with pytest.raises(ValueError):
+        voc.transform_batch_device(1 << 20, 1, 64, 1 << 20, 1, 4, *([1 << 20] * 8))
+    # the optional outputs may be NULL, and n = 0 gives empty containers
+    rc, _ = _raw(pkg, voc, "orbv_transform_host", q, len(q), 4, null=("word", "node"))
+    assert rc == 0
+    t = voc.transform_host(np.zeros((0, 32), np.uint8))
+    assert len(t["bow_id"]) == 0 and len(t["fv_node_id"]) == 0 and list(t["fv_start"]) == [0]
+
+
+def test_no_cpu_fallback(pkg):
+    """Without a usable HIP device a vocabulary with device tables cannot be made; nothing falls back to the host form."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    with pytest.raises(pkg.OrbError):
+        VS.vocabulary(pkg, "flat", 0, 0, device=0)
+
+
+def test_a_vocabulary_without_words_gives_empty_containers(pkg):
+    """empty() (TemplatedVocabulary.h:1134): v.clear(), fv.clear(), return."""
+    voc = pkg.ORBVocabulary.from_nodes(10, 6, 0, 0, [0], [0], np.zeros((1, 32), np.uint8), [0.0], device=-1)
+    t = voc.transform_host(VS.scene("flat")["queries"][:5])
+    assert voc.n_words == 0 and len(t["bow_id"]) == 0 and len(t["fv_idx"]) == 0 and list(t["fv_start"]) == [0]
+
+
+def test_load_text_equals_from_nodes(pkg, tmp_path):
+    for name, blank in (("irregular", False), ("wide", True)):
+        S = VS.scene(name)
+        path = str(tmp_path / (name + ".txt"))
+        VS.write_text(S, 0, 5, path, trailing_blank=blank)
+        a = pkg.ORBVocabulary.load_text(path, device=-1)
+        b = VS.vocabulary(pkg, name, 0, 5, device=-1)
+        assert (a.k, a.L, a.weighting, a.scoring, a.n_nodes, a.n_words) == (b.k, b.L, 0, 5, b.n_nodes, b.n_words)
+        assert np.array_equal(a.parent, b.parent) and np.array_equal(a.is_leaf, b.is_leaf)
+        assert np.array_equal(a.descriptor[1:], b.descriptor[1:])    # the root is not in the file, and its descriptor is never read
+        assert np.array_equal(a.weight.view(np.uint64), b.weight.view(np.uint64))
+        VM.same(a.transform_host(S["queries"], S["L"]), b.transform_host(S["queries"], S["L"]), name)
+    assert "blank lines are skipped" in pkg.ORBVocabulary.load_text.__doc__
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "orbhip.h")).read()
+
+
+def test_symbols(pkg):
+    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(orbv_[a-z0-9_]+)\s*\(", txt)))
+    assert declared == sorted(pkg.VOC_ABI_SYMBOLS) and len(declared) >= 10
+    L = pkg.load()
+    for s in declared:
+        assert hasattr(L, s), "liborbhip.so does not export %s" % s
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="no C compiler")
+def test_struct_layout(pkg, tmp_path):
+    """orbv_nodes_t as the C compiler lays it out against the ctypes mirror; the header is plain C."""
+    src = tmp_path / "layout.c"
+    fields = [f for f, _ in pkg.VocNodesStruct._fields_]
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "orbhip.h"\nint main(void) { printf("%zu", sizeof(orbv_nodes_t));\n' +
+                   "".join('printf(" %%zu", offsetof(orbv_nodes_t, %s));\n' % f for f in fields) + "return 0; }\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    out = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert out[0] == C.sizeof(pkg.VocNodesStruct)
+    assert out[1:] == [getattr(pkg.VocNodesStruct, f).offset for f in fields]
+
+
+CITED = {   # file -> {line: a token that line must hold}
+    "Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h": {1126: "template", 1134: "empty()", 1145: "m_weighting == TF", 1157: "w > 0", 1167: "v.size()",
+                                                    1185: "w > 0", 1193: "normalize", 1226: "m_L - levelsup", 1227: "*nid = 0", 1244: "d < best_d",
+                                                    1251: "nid_level", 1254: "isLeaf()", 316: "word_id(0)", 328: "children.empty()",
+                                                    1392: "children.push_back", 1410: "m_words.size()"},
+    "Thirdparty/DBoW2/DBoW2/BowVector.cpp": {34: "addWeight", 50: "addIfNotExist", 70: "fabs", 79: "norm > 0.0", 82: "/= norm"},
+    "Thirdparty/DBoW2/DBoW2/FeatureVector.cpp": {31: "addFeature", 37: "push_back"},
+    "Thirdparty/DBoW2/DBoW2/ScoringObject.h": {74: "L1Scoring, true, L1", 77: "L2Scoring, true, L2", 89: "DotProductScoring, false"},
+    "Thirdparty/DBoW2/DBoW2/BowVector.h": {39: "WeightingType", 48: "ScoringType"},
+    "Thirdparty/DBoW2/DBoW2/FORB.cpp": {81: "FORB::distance"},
+    "src/Frame.cc": {828: "Frame::ComputeBoW", 833: "transform(vCurrentDesc,mBowVec,mFeatVec,4)"},
+    "src/KeyFrame.cc": {100: "KeyFrame::ComputeBoW", 107: "transform(vCurrentDesc,mBowVec,mFeatVec,4)"},
+}
+
+
+def test_citations_are_written_down():
+    """Every entry of the orbv_ section cites the reference's lines, and so do the statement and the kernels."""
+    hdr = _header()
+    sec = hdr[hdr.index("ORBVocabulary (DBoW2::TemplatedVocabulary"):]
+    for cite in ("Frame.cc:828-835", "KeyFrame.cc:100-110", "TemplatedVocabulary.h:1126-1194", ":1217-1259", "BowVector.cpp:34-84",
+                 "FeatureVector.cpp:31-45", "ScoringObject.h:74-89", ":1385-1392", ":1408-1415", "csrc/orb_ref_voc.h"):
+        assert cite in sec, cite
+    ref = open(os.path.join(ROOT, "3_orb_slam3_selfnote_amd", "csrc", "orb_ref_voc.h")).read()
+    for cite in ("TemplatedVocabulary.h:1126-1194", ":1217-1259", ":1244", "BowVector.cpp:34-84", "FORB.cpp:81-101", "ScoringObject.h:74-89",
+                 "L2_NORM scoring (type 1) is REFUSED", "REFUSED for that levelsup"):
+        assert cite in ref, cite
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "Thirdparty", "DBoW2", "DBoW2", "TemplatedVocabulary.h")),
+                    reason="reference tree not available")
+def test_cited_lines_say_what_is_claimed():
+    for rel, lines in CITED.items():
+        txt = open(os.path.join(REF, rel), encoding="utf-8", errors="ignore").read().splitlines()
+        for no, token in lines.items():
+            assert token in txt[no - 1], "%s:%d does not hold %r: %r" % (rel, no, token, txt[no - 1])
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(REF_INC, "Frame.h")) or shutil.which("g++") is None,
+                    reason="reference headers or g++ not available")
+def test_snippet_typechecks_against_reference_headers():
+    """Both ComputeBoW bodies and the flattening of m_nodes against the reference's unmodified Frame.h, KeyFrame.h, ORBVocabulary.h and
+    the in-tree DBoW2 headers (declaration-only doubles for OpenCV, Eigen, boost: tests/support/slam_typecheck_stub)."""
+    stub = os.path.join(ROOT, "tests", "support", "slam_typecheck_stub")
+    cmd = ["g++", "-std=c++11", "-fsyntax-only", "-I", stub, "-I", REF_INC, "-I", os.path.join(REF_INC, "CameraModels"), "-I", REF,
+           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "3_orb_slam3_selfnote_amd", "csrc", "adapter", "snippets", "ComputeBoW_hip.cc")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
