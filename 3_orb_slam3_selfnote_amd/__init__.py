@@ -1815,9 +1815,17 @@ class ORBVocabulary:
     @classmethod
     def load_text(cls, path, device=0):
         """loadFromTextFile (TemplatedVocabulary.h:1338-1424).  ONE DIFFERENCE from the loader: blank lines are skipped.  The loader
-        makes a node of every line it reads, so a trailing empty line gives it one more node under the root (parent 0 from the
-        failed `>> pid`, an indeterminate leaf flag and descriptor); a drop-in build passes m_nodes as the loader left them through
-        from_nodes / orbv_create instead (csrc/adapter/snippets/ComputeBoW_hip.cc), extra node included."""
+        makes a node of every line it reads (:1378-1386), and its `while(!f.eof())` reads one empty line for every newline after
+        the last node line - the one that ends the file as saveToTextFile writes it included.  On an empty line `>> pid` and
+        `>> nIsLeaf` fail at the stream's sentry and store nothing, so the parent and the leaf flag of that node are indeterminate
+        reads; its weight is 0 (Node()) and its descriptor whatever cv::Mat::create(1, 32, CV_8U) returns.  Compiled with g++
+        -std=c++11 -O2 against libstdc++ (tests/test_ref_voc.py prints it) the node hangs under the PREVIOUS line's parent, is
+        flagged as a leaf and takes a new word id, so size() grows by one per empty line.  Skipping the line costs exactly that:
+        this vocabulary has one word fewer than size() reports there - a word of weight 0 that no BowVector can hold, with a
+        descriptor that cannot be reproduced.  Every word id, node id and weight of the real nodes is the loader's (the extra nodes
+        come last).  A drop-in build passes m_nodes as the loader left them through from_nodes / orbv_create instead
+        (csrc/adapter/snippets/ComputeBoW_hip.cc), extra nodes included; tests/test_ref_voc.py and tests/test_gpu_ref_voc.py run
+        that path on the compiled loader's own tables."""
         k, L, scoring, weighting, parent, leaf, desc, weight = cls.parse_text(path)
         return cls(k, L, weighting, scoring, parent, leaf, desc, weight, device=device)
 

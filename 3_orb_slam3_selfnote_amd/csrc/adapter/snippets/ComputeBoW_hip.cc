@@ -3,8 +3,8 @@
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1126-1194), here orbv_transform of include/orbhip.h.
 //
 // Delete (or #if 0) the two members in src/Frame.cc and src/KeyFrame.cc and add this file to the library's sources.  The vocabulary is
-// flattened ONCE per ORBVocabulary object, from m_nodes AS THE LOADER LEFT THEM (a trailing empty line of ORBvoc.txt gives the root one
-// more child, TemplatedVocabulary.h:1378-1392; it is carried over, not repaired), and the handle is kept in a mutex-guarded map: Tracking
+// flattened ONCE per ORBVocabulary object, from m_nodes AS THE LOADER LEFT THEM (a trailing empty line of ORBvoc.txt gives some
+// node one more child of weight 0, TemplatedVocabulary.h:1378-1392; it is carried over, not repaired), and the handle is kept in a mutex-guarded map: Tracking
 // and LocalMapping call ComputeBoW on the same vocabulary from their own threads, which orbv_transform allows.  m_nodes is protected;
 // it is reached through a derived class's pointer to member, without touching DBoW2's sources.  The two containers are filled by hinted
 // insert from the sorted output, so they hold exactly the keys, values and per-node index order the reference's loop builds.
@@ -36,13 +36,19 @@ struct VocAccess : public ORBVocabulary {
     std::vector<uint32_t> parent(n);
     std::vector<uint8_t> leaf(n), desc(n * 32, 0);
     std::vector<double> weight(n);
+    size_t flagged = 0;
     for (size_t i = 0; i < n; i++) {
       const Node &nd = nodes[i];
       parent[i] = (uint32_t)nd.parent;
       leaf[i] = nd.word_id < words.size() && words[nd.word_id] == &nd;   // the loader gave it a word (:1408-1415)
+      flagged += leaf[i];
       if (!nd.descriptor.empty()) std::memcpy(&desc[i * 32], nd.descriptor.ptr<uint8_t>(), 32);   // the root has none
       weight[i] = nd.weight;
     }
+    // m_words points into m_nodes, and the loader reserves (k^(L+1) - 1)/(k - 1) nodes once (:1370-1372): a file with more node lines
+    // than that (a COMPLETE tree plus the node of a trailing empty line; ORBvoc.txt is pruned and stays below) makes m_nodes grow and
+    // leaves every pointer of m_words dangling, in the reference too.  Then no node would pass for a word: an error, not an empty BoW.
+    if (flagged != words.size()) throw std::runtime_error("ComputeBoW: m_words does not point into m_nodes (the vocabulary grew after its words were filed)");
     orbv_nodes_t t;
     t.k = voc.*(&VocAccess::m_k);
     t.L = voc.*(&VocAccess::m_L);

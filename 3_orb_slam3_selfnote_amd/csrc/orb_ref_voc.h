@@ -1,7 +1,8 @@
 // orb_ref_voc.h -- DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB>::transform(features, BowVector, FeatureVector, levelsup)
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1126-1194 over :1217-1259) as Frame::ComputeBoW (Frame.cc:828-835) and
 // KeyFrame::ComputeBoW (KeyFrame.cc:100-110) call it, stated once for the host entry orbv_transform_host and the kernels of
-// orb_voc_kernels.h.  Integer arithmetic in the descent, IEEE-754 double `+=`, fabs and `/=` in the reference's order in the assembly,
+// orb_voc_kernels.h.  Held against that text itself, compiled unmodified (oracle/ref_voc_driver.cc; tests/test_ref_voc.py for the host
+// entry, tests/test_gpu_ref_voc.py for the kernels), besides the literal model of tests/voc_model.py.  Integer arithmetic in the descent, IEEE-754 double `+=`, fabs and `/=` in the reference's order in the assembly,
 // no contraction; no libm call and no OpenCV primitive is involved.
 //
 // The vocabulary is held re-laid so that the children of a node are contiguous ("entries"; entry 0 is the root):
@@ -28,9 +29,12 @@
 //   * A vocabulary with a childless node of weight > 0 above level m_L - levelsup is REFUSED for that levelsup: the reference leaves
 //     *nid unset there (:1251 never fires) and FeatureVector::addFeature (:1160, :1188) reads an uninitialised NodeId.  A childless
 //     node of weight <= 0 above that level is harmless - a feature that ends there is stopped (:1157, :1185) and its NodeId is never
-//     read - and is accepted: the node that the loader makes of a trailing empty line (:1378-1392; under the root, weight 0 from the
-//     failed read) is one, so a vocabulary loaded from a file that ends in a newline works as it does in the reference.  node_of_feature
-//     of such a feature is 0 here, indeterminate there.
+//     read - and is accepted.  The node that the loader makes of each trailing empty line (:1378-1420) has weight 0 (Node()) wherever
+//     it hangs, so a vocabulary loaded from a file that ends in a newline works as it does in the reference.  Where it hangs is not
+//     the text's choice: `>> pid` and `>> nIsLeaf` fail at the stream's sentry and store nothing, so both are indeterminate reads.
+//     Compiled with g++ -std=c++11 -O2 (oracle/_ref/libref_voc.so, tests/test_ref_voc.py) it is a child of the previous line's
+//     parent, flagged as a leaf, with a word id of its own; nothing here depends on that.  node_of_feature of a stopped feature that
+//     ends above the level is 0 here, unset there.
 //   * An empty vocabulary (no word, :1134) gives two empty containers.
 #pragma once
 #include <stdint.h>

@@ -1285,8 +1285,9 @@ int orbm_get_stage_ms(orbm_t *m, float *ms, int cap);
 /* m_nodes flattened in id order; node 0 is the root (it is not in the text file, TemplatedVocabulary.h:1376-1377).
  * The children of a node are rebuilt in ascending node id, which is the loader's push_back order (:1385-1392); word ids are
  * counted over the nodes with is_leaf set, in id order (:1408-1415; is_leaf[0] is not read).  The child count of a node is
- * whatever parent[] says and is NOT bounded by k: a trailing empty line of the text file makes one more node under the
- * root (its failed `>> pid` leaves 0, :1389-1392), so the root of a loaded k-ary vocabulary can own k + 1 children.  The
+ * whatever parent[] says and is NOT bounded by k: every trailing empty line of the text file makes one more node (:1378-1386)
+ * whose parent is an indeterminate read (`>> pid` fails and stores nothing, :1389-1392; seen with g++ -O2: the previous
+ * line's parent, flagged as a leaf, weight 0), so a node of a loaded k-ary vocabulary can own more than k children.  The
  * descent ends at a node without children (Node::isLeaf() is children.empty(), :328), flagged or not; an unflagged one
  * answers word 0 (Node(), :316) with its own weight. */
 typedef struct {

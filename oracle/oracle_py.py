@@ -688,6 +688,7 @@ _REF_SOURCES = ("ref_driver.cc", "ref_extractor.map", os.path.join("ref_shim", "
 _REF_CAM_LIB = os.path.join(_REF_DIR, "libref_cameras.so")
 _REF_CAM_LIB_CMATH = os.path.join(_REF_DIR, "libref_cameras_cmath.so")
 _REF_MATCH_LIB = os.path.join(_REF_DIR, "libref_matcher.so")
+_REF_VOC_LIB = os.path.join(_REF_DIR, "libref_voc.so")
 _ref_lib = None
 
 
@@ -698,8 +699,8 @@ def reference_tree():
 
 
 def build_ref(force=False):
-    """Build oracle/_ref/libref_extractor.so (and beside it the camera libraries, ref_cam_lib, and the matcher library, ref_match_lib)
-    where the reference tree exists; elsewhere what is already built is used as it is.  Returns the extractor library's path, or None when there is neither."""
+    """Build oracle/_ref/libref_extractor.so (and beside it the camera libraries, ref_cam_lib, the matcher library, ref_match_lib, and the
+    vocabulary library, ref_voc_lib) where the reference tree exists; elsewhere what is already built is used as it is.  Returns the extractor library's path, or None when there is neither."""
     tree = reference_tree()
     if tree is not None:
         build()
@@ -1050,3 +1051,106 @@ def ref_search_for_initialization(keys1, desc1, F2, prev_matched, window_size, n
     n = F2.L.refm_search_for_initialization(n1, _p(_i32(keys1["octave"])), _p(_f32(keys1["angle"])), _p(_u8(desc1)), C.byref(F2.rec),
                                             _p(prev_matched), int(window_size), nnratio, int(check_ori), _p(m12))
     return n, m12
+
+
+# --- the reference's own DBoW2 (TemplatedVocabulary.h for FORB), compiled (oracle/Makefile `ref`, oracle/ref_voc_driver.cc) -----------
+_ref_voc_lib = None
+REF_VOC_UNSET = 0xFFFFFFFF   # what *nid holds where the single-feature transform never wrote it
+
+
+def ref_voc_lib(build_if_possible=True):
+    """libref_voc.so, loaded.  build_if_possible=False never looks at the reference tree: what is under oracle/_ref/ is loaded as it
+    is."""
+    global _ref_voc_lib
+    if _ref_voc_lib is None:
+        if build_if_possible:
+            build_ref()
+        if not os.path.exists(_REF_VOC_LIB):
+            raise RuntimeError("oracle/_ref/libref_voc.so is missing and there is no reference tree to build it from: "
+                               "run __graft_entry__.build() where the reference exists")
+        L = C.CDLL(_REF_VOC_LIB)
+        P, I = C.c_void_p, C.c_int
+        L.refv_load.argtypes = [C.c_char_p]
+        L.refv_load.restype = P
+        L.refv_destroy.argtypes = [P]
+        L.refv_destroy.restype = None
+        L.refv_params.argtypes = [P, P]
+        L.refv_params.restype = None
+        L.refv_nodes.argtypes = [P] * 7
+        L.refv_desc_stored.argtypes = [C.c_char_p, I, P]
+        L.refv_transform.argtypes = [P, P, I, I] + [P] * 7
+        L.refv_transform_each.argtypes = [P, P, I, I, P, P, P]
+        _ref_voc_lib = L
+    return _ref_voc_lib
+
+
+class RefVocabulary:
+    """The reference's TemplatedVocabulary<FORB::TDescriptor, FORB>, compiled from its own text, after its own loadFromTextFile(path).
+    k, L, weighting, scoring, n_nodes, n_words (size()); nodes() = m_nodes as the loader left them; transform / transform_each."""
+
+    def __init__(self, path, L=None):
+        self.lib = L or ref_voc_lib()
+        self.path = os.fsencode(str(path))
+        self.h = self.lib.refv_load(self.path)
+        if not self.h:
+            raise ValueError("loadFromTextFile(%s) returned false" % path)
+        p = np.zeros(6, np.int32)
+        self.lib.refv_params(self.h, _p(p))
+        self.k, self.L, self.weighting, self.scoring, self.n_nodes, self.n_words = (int(x) for x in p)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.refv_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def nodes(self):
+        """m_nodes in id order: dict of parent, n_children, word_id, weight, descriptor [n, 32], flagged (1: the loader took its
+        `nIsLeaf > 0` branch; told from the word ids, see refv_nodes) and stored [n, 32] (1 where FORB::fromString stored the byte: the
+        stand-in cv::Mat::create zero-fills, a real one does not, so an unstored byte's value means nothing)."""
+        n = self.n_nodes
+        out = dict(parent=np.zeros(n, np.uint32), n_children=np.zeros(n, np.int32), word_id=np.zeros(n, np.uint32), weight=np.zeros(n, np.float64),
+                   descriptor=np.zeros((n, 32), np.uint8), flagged=np.zeros(n, np.uint8))
+        rc = self.lib.refv_nodes(self.h, *[_p(out[k]) for k in ("parent", "n_children", "word_id", "weight", "descriptor", "flagged")])
+        if rc != n:
+            raise RuntimeError("refv_nodes rc=%d" % rc)
+        if np.any(out["flagged"] == 2):
+            raise RuntimeError("refv_nodes: which node is word 0 cannot be told from m_nodes")
+        stored = np.zeros((n, 32), np.uint8)
+        lines = self.lib.refv_desc_stored(self.path, n, _p(stored))
+        if lines != n - 1:
+            raise RuntimeError("refv_desc_stored: %d node lines for %d nodes" % (lines, n))
+        out["stored"] = stored
+        return out
+
+    def transform(self, desc, levelsup=4):
+        """transform(features, v, fv, levelsup), flattened in the order the two std::maps iterate in (the product's layout)."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        n = len(desc)
+        m = max(n, 1)
+        bow_id, bow_val = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        fv_node, fv_start, fv_idx = np.zeros(m, np.uint32), np.zeros(m + 1, np.int32), np.zeros(m, np.int32)
+        n_bow, n_fv = C.c_int32(-1), C.c_int32(-1)
+        rc = self.lib.refv_transform(self.h, _p(desc), n, int(levelsup), _p(bow_id), _p(bow_val), C.byref(n_bow), _p(fv_node), _p(fv_start),
+                                     _p(fv_idx), C.byref(n_fv))
+        if rc != 0:
+            raise RuntimeError("refv_transform rc=%d" % rc)
+        nb, nf = n_bow.value, n_fv.value
+        return dict(bow_id=bow_id[:nb].copy(), bow_val=bow_val[:nb].copy(), fv_node_id=fv_node[:nf].copy(), fv_start=fv_start[:nf + 1].copy(),
+                    fv_idx=fv_idx[:int(fv_start[nf])].copy())
+
+    def transform_each(self, desc, levelsup=4):
+        """transform(feature, word_id, weight, &nid, levelsup) per feature: (word [n], weight [n], nid [n]); nid is REF_VOC_UNSET where
+        the reference never wrote it."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        n = len(desc)
+        word, weight, nid = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint32)
+        rc = self.lib.refv_transform_each(self.h, _p(desc), n, int(levelsup), _p(word), _p(weight), _p(nid))
+        if rc != 0:
+            raise RuntimeError("refv_transform_each rc=%d (a vocabulary without words)" % rc)
+        return word[:n], weight[:n], nid[:n]

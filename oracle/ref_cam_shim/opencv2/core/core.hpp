@@ -3,7 +3,7 @@
  * ORBmatcher.cc, and the headers they include, use of OpenCV 3.4.x - and nothing else.  Written from scratch from OpenCV's published algorithms;
  * an independent, general (any small m x n) restatement that shares no code with the product, the oracle or the test models.
  *
- *   Mat            CV_32F for the algebra, CV_8U for descriptor rows (row, ptr<int32_t>, clone - no algebra); two dimensions, shared
+ *   Mat            CV_32F for the algebra, CV_8U for descriptor rows (row, ptr<int32_t>, clone, release - no algebra); two dimensions, shared
  *                  storage; row / col / rowRange / colRange are views into it.
  *   MatExpr        the lazy expressions of the two files, folded as OpenCV's MatExpr folds them (DESIGN.md section 2 has the table):
  *                    A*B, -A*B, s*A*B, A*B + C      one gemm: D = alpha*A*B + beta*C
@@ -21,6 +21,7 @@
  *                  built with LAPACK gives other low bits.
  *   fisheye::undistortPoints  declared because KannalaBrandt8::ReconstructWithTwoViews names it; aborts.
  *   FileStorage, BFMatcher, InputArray ...  declared, without bodies, at the end: named by the SLAM headers ORBmatcher.cc includes.
+ *                  (oracle/ref_voc_driver.cc gives the FileStorage family aborting bodies: DBoW2's template names them in virtual members.)
  *
  * This header does not include <math.h>: whether an unqualified cos(float) inside a namespace is the float or the double function is
  * decided by opencv2/opencv.hpp (see there).  Compile without -DNDEBUG: what is not provided asserts.
@@ -125,6 +126,7 @@ class Mat {
     /* descriptor rows are read as 32-bit words (ptr<int32_t>): new[] storage is aligned for them when every row is a multiple of 4 */
     else bytes_ = std::shared_ptr<uchar>(new uchar[(size_t)r * (size_t)c + 4](), std::default_delete<uchar[]>());
   }
+  void release() { rows = 0; cols = 0; step_ = 0; off_ = 0; buf_.reset(); bytes_.reset(); }
   int type() const { return type_; }
   bool empty() const { return rows == 0 || cols == 0 || (!buf_ && !bytes_); }
   bool isContinuous() const { return rows <= 1 || step_ == (size_t)cols; }

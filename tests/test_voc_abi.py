@@ -48,7 +48,8 @@ def test_host_form_equals_model(vocs, name):
                     what = "%s weighting %d scoring %d levelsup %d n %d" % (name, weighting, scoring, levelsup, n)
                     refused += VS.check_against_model(voc, model, S["queries"][:n], levelsup, what) is None
     # the shapes decide which levelsup the library refuses: the irregular tree and the wide one (its 21st root child, of weight 0.7) have
-    # shallow leaves that let features in; the same child with the loader's weight 0 only stops features
+    # shallow leaves that let features in; the same child with weight 0 only stops features, and so does the node the compiled loader
+    # makes of a trailing empty line (wide_trailing)
     assert (refused > 0) == (name in ("irregular", "wide"))
 
 
@@ -104,7 +105,7 @@ def test_scenes_hold_what_the_comparison_relies_on():
     t = m.transform(W["queries"], W["L"])
     ws = t["stats"]["counts"][0]
     assert W["weight"][extra] in ws and len(set(ws)) >= 1
-    # the same child as the loader leaves it (weight 0) is hit too, at a levelsup that puts the FeatureVector's level below it: stopped
+    # the same child with weight 0 (the loader's Node()) is hit too, at a levelsup that puts the FeatureVector's level below it: stopped
     A = VS.scene("wide_as_loaded")
     ma = VS.model("wide_as_loaded", 0, 0)
     ta = ma.transform(A["queries"], 0)

@@ -2,8 +2,9 @@
 (TemplatedVocabulary.h:1126-1194 over :1217-1259, BowVector.cpp:34-84, FeatureVector.cpp:31-45): a dict plus its sorted keys for each
 std::map, Python floats (IEEE doubles) for the values, Python ints for the descriptors.  It shares no code with csrc/orb_ref_voc.h.
 
-What it does not pin (DBoW2 itself is not compiled here): that std::map iterates in ascending key order, and that `+=`, fabs and `/=` on
-doubles are the IEEE operations - both hold for the reference's build (x86-64, SSE2, no fast-math)."""
+What it does not pin by itself: that std::map iterates in ascending key order, and that `+=`, fabs and `/=` on doubles are the IEEE
+operations.  Both are pinned by the reference's own text, compiled unmodified into oracle/_ref/libref_voc.so (oracle/ref_voc_driver.cc):
+tests/test_ref_voc.py holds this model and orbv_transform_host against it on every scene, tests/test_gpu_ref_voc.py the kernels."""
 import numpy as np
 
 TF_IDF, TF, IDF, BINARY = range(4)
