@@ -51,6 +51,18 @@ VOC_ABI_SYMBOLS = [
 ]
 
 
+# the keyframe database's symbols (orbd_*), held equal to the header's orbd_ names by tests/test_kfdb_abi.py
+KFDB_ABI_SYMBOLS = [
+    "orbd_create", "orbd_create_for_vocabulary", "orbd_destroy", "orbd_last_error", "orbd_n_words", "orbd_capacity", "orbd_size",
+    "orbd_add", "orbd_add_device", "orbd_erase", "orbd_clear", "orbd_clear_map", "orbd_set_map", "orbd_get_members",
+    "orbd_query_reloc", "orbd_query_reloc_host", "orbd_query_place", "orbd_query_place_host", "orbd_batch_scratch_bytes",
+    "orbd_score_batch_device", "orbd_accumulate_reloc", "orbd_accumulate_place",
+]
+MAX_KEYFRAMES = 16384  # ORBD_MAX_KEYFRAMES
+COVISIBLES = 10  # ORBD_COVISIBLES
+NO_TAG = 0xFFFFFFFFFFFFFFFF  # ORBD_NO_TAG
+
+
 class FrameStruct(C.Structure):  # orbm_frame_t
     _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("descriptors", C.c_void_p), ("u_right", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
@@ -64,6 +76,10 @@ class MapPointUpdateStruct(C.Structure):  # orbm_map_point_update_t
 class VocNodesStruct(C.Structure):  # orbv_nodes_t
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("n_nodes", C.c_int32),
                 ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("descriptor", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class KfdbMembersStruct(C.Structure):  # orbd_members_t
+    _fields_ = [("reloc_query", C.c_uint64), ("place_query", C.c_uint64), ("reloc_score", C.c_float), ("place_score", C.c_float)]
 
 
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
@@ -299,6 +315,32 @@ def load(build_if_needed=True):
     L.orbv_batch_scratch_bytes.argtypes = [i32, i32]
     L.orbv_transform_batch_device.argtypes = [vp, vp, i32, i32, vp, i32, i32] + [vp] * 11
     L.orbv_transform_batch_device_form.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32] + [vp] * 11
+    u64 = C.c_uint64
+    L.orbd_create.restype = vp
+    L.orbd_create.argtypes = [i32, i32, i32, i32]
+    L.orbd_create_for_vocabulary.restype = vp
+    L.orbd_create_for_vocabulary.argtypes = [vp, i32, i32]
+    L.orbd_destroy.restype = None
+    L.orbd_destroy.argtypes = [vp]
+    L.orbd_last_error.restype = C.c_char_p
+    L.orbd_last_error.argtypes = [vp]
+    for name in ("orbd_n_words", "orbd_capacity", "orbd_size", "orbd_clear"):
+        getattr(L, name).argtypes = [vp]
+    L.orbd_add.argtypes = [vp, u64, u64, vp, vp, i32, vp]
+    L.orbd_add_device.argtypes = [vp, u64, u64, vp, vp, vp, i32, i32, vp, vp]
+    L.orbd_erase.argtypes = [vp, u64]
+    L.orbd_clear_map.argtypes = [vp, u64]
+    L.orbd_set_map.argtypes = [vp, u64, u64]
+    L.orbd_get_members.argtypes = [vp, u64, vp]
+    for name in ("orbd_query_reloc", "orbd_query_reloc_host"):
+        getattr(L, name).argtypes = [vp, u64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    for name in ("orbd_query_place", "orbd_query_place_host"):
+        getattr(L, name).argtypes = [vp, u64, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.orbd_batch_scratch_bytes.restype = sz
+    L.orbd_batch_scratch_bytes.argtypes = [vp, i32]
+    L.orbd_score_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.orbd_accumulate_reloc.argtypes = [vp, u64, u64, vp, vp, i32, vp, vp, vp]
+    L.orbd_accumulate_place.argtypes = [vp, u64, vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -1879,3 +1921,208 @@ class ORBVocabulary:
         if rc < 0:
             _voc_error("orbv_transform_batch_device", rc)
         return rc
+
+
+def _kfdb_error(what, rc):
+    msg = (load().orbd_last_error(None) or b"").decode()
+    if rc == E_ARG:
+        raise ValueError("%s: %s" % (what, msg or "bad argument"))
+    raise OrbError("%s rc=%d: %s" % (what, rc, msg))
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM3::KeyFrameDatabase (KeyFrameDatabase.cc:39-98) with its two live queries, DetectRelocalizationCandidates
+    (KeyFrameDatabase.cc:814-926) and DetectNBestCandidates (KeyFrameDatabase.cc:620-811), over orbd_* of include/orbhip.h.
+
+    Keyframes are named by tags (any unsigned 64-bit integer but NO_TAG).  A BowVector is a pair (ids, values) or a transform result
+    (a dict with bow_id / bow_val).  device >= 0 allocates the device tables; device = -1 gives a handle on which only the _host forms
+    work (so that csrc/orb_ref_kfdb.h can be tested without a GPU; it is not a fallback: the device forms raise on it)."""
+
+    def __init__(self, n_words, capacity=MAX_KEYFRAMES, scoring=0, device=0, vocabulary=None):
+        self.L_lib = load()
+        self.device = int(device)
+        if vocabulary is not None:
+            self.d = self.L_lib.orbd_create_for_vocabulary(vocabulary.v, int(capacity), self.device)
+        else:
+            self.d = self.L_lib.orbd_create(int(n_words), int(scoring), int(capacity), self.device)
+        if not self.d:
+            msg = (self.L_lib.orbd_last_error(None) or b"").decode()
+            if "HIP: " in msg:
+                raise OrbError("orbd_create: " + msg)
+            raise ValueError("orbd_create: " + msg)
+        self.n_words = self.L_lib.orbd_n_words(self.d)
+        self.capacity = self.L_lib.orbd_capacity(self.d)
+
+    @classmethod
+    def for_vocabulary(cls, voc, capacity=MAX_KEYFRAMES, device=0):
+        return cls(0, capacity, device=device, vocabulary=voc)
+
+    def __del__(self):
+        try:
+            if getattr(self, "d", None):
+                self.L_lib.orbd_destroy(self.d)
+                self.d = None
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.L_lib.orbd_size(self.d)
+
+    @staticmethod
+    def _bow(bow):
+        if isinstance(bow, dict):
+            bow = (bow["bow_id"], bow["bow_val"])
+        ids = np.ascontiguousarray(bow[0], dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(bow[1], dtype=np.float64).reshape(-1)
+        if len(ids) != len(val):
+            raise ValueError("KeyFrameDatabase: ids and values differ in length")
+        return ids, val
+
+    @staticmethod
+    def _members(init):
+        if init is None:
+            return None
+        return C.byref(KfdbMembersStruct(int(init.get("reloc_query", 0)), int(init.get("place_query", 0)), float(init.get("reloc_score", 0.0)),
+                                         float(init.get("place_score", 0.0))))
+
+    def _rc(self, rc, what):
+        if rc < 0:
+            _kfdb_error(what, rc)
+        return rc
+
+    def add(self, tag, map_id, bow, init=None):
+        """KeyFrameDatabase::add (KeyFrameDatabase.cc:39-45).  init: a dict of reloc_query, reloc_score, place_query, place_score."""
+        ids, val = self._bow(bow)
+        self._rc(self.L_lib.orbd_add(self.d, int(tag), int(map_id), _p(ids), _p(val), len(ids), self._members(init)), "orbd_add")
+
+    def add_device(self, tag, map_id, d_bow_id, d_bow_val, d_n_bow, cap, p, init=None, stream=None):
+        """add for frame p of a transform_batch_device output, device to device (orbd_add_device)."""
+        self._rc(self.L_lib.orbd_add_device(self.d, int(tag), int(map_id), _dp(d_bow_id), _dp(d_bow_val), _dp(d_n_bow), int(cap), int(p),
+                                            self._members(init), _dp(stream)), "orbd_add_device")
+
+    def erase(self, tag):
+        """KeyFrameDatabase::erase (KeyFrameDatabase.cc:47-66)."""
+        self._rc(self.L_lib.orbd_erase(self.d, int(tag)), "orbd_erase")
+
+    def clear(self):
+        """KeyFrameDatabase::clear (KeyFrameDatabase.cc:68-72)."""
+        self._rc(self.L_lib.orbd_clear(self.d), "orbd_clear")
+
+    def clear_map(self, map_id):
+        """KeyFrameDatabase::clearMap (KeyFrameDatabase.cc:74-98)."""
+        self._rc(self.L_lib.orbd_clear_map(self.d, int(map_id)), "orbd_clear_map")
+
+    def set_map(self, tag, map_id):
+        self._rc(self.L_lib.orbd_set_map(self.d, int(tag), int(map_id)), "orbd_set_map")
+
+    def members(self, tag):
+        """mnRelocQuery, mRelocScore, mnPlaceRecognitionQuery, mPlaceRecognitionScore as the handle holds them."""
+        m = KfdbMembersStruct()
+        self._rc(self.L_lib.orbd_get_members(self.d, int(tag), C.byref(m)), "orbd_get_members")
+        return dict(reloc_query=m.reloc_query, place_query=m.place_query, reloc_score=np.float32(m.reloc_score),
+                    place_score=np.float32(m.place_score))
+
+    def _query(self, name, query_id, connected, bow):
+        ids, val = self._bow(bow)
+        cap = self.capacity          # not len(self): another thread may add between the two calls
+        tags, scores = np.zeros(cap, np.uint64), np.zeros(cap, np.float32)
+        ns, mx, mn, nl = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        tail = (_p(ids), _p(val), len(ids), _p(tags), _p(scores), cap, C.byref(ns), C.byref(mx), C.byref(mn), C.byref(nl))
+        if connected is None:
+            rc = getattr(self.L_lib, name)(self.d, int(query_id), *tail)
+        else:
+            con = np.ascontiguousarray(connected, dtype=np.uint64).reshape(-1)
+            rc = getattr(self.L_lib, name)(self.d, int(query_id), _p(con), len(con), *tail)
+        self._rc(rc, name)
+        return dict(tags=tags[:ns.value].copy(), scores=scores[:ns.value].copy(), max_common=mx.value, min_common=mn.value,
+                    n_listed=nl.value)
+
+    def query_reloc(self, query_id, bow):
+        """The device part of DetectRelocalizationCandidates (KeyFrameDatabase.cc:816-871): lScoreAndMatch as tags / scores in the
+        reference's order, max_common, min_common, n_listed.  Raises on a device = -1 handle: there is no host fallback."""
+        return self._query("orbd_query_reloc", query_id, None, bow)
+
+    def query_reloc_host(self, query_id, bow):
+        return self._query("orbd_query_reloc_host", query_id, None, bow)
+
+    def query_place(self, query_id, connected, bow):
+        """The device part of DetectNBestCandidates (KeyFrameDatabase.cc:627-711); connected: pKF->GetConnectedKeyFrames() as tags."""
+        return self._query("orbd_query_place", query_id, list(connected), bow)
+
+    def query_place_host(self, query_id, connected, bow):
+        return self._query("orbd_query_place_host", query_id, list(connected), bow)
+
+    @staticmethod
+    def _covisibles(tags, covisibles_of):
+        table = np.full((max(len(tags), 1), COVISIBLES), NO_TAG, np.uint64)
+        for i, t in enumerate(tags):
+            row = list(covisibles_of(int(t)))[:COVISIBLES]
+            table[i, :len(row)] = row
+        return table
+
+    def accumulate_reloc(self, query_id, map_id, scored, covisibles_of):
+        """KeyFrameDatabase.cc:873-923 on a query_reloc result; covisibles_of(tag) = GetBestCovisibilityKeyFrames(10) as tags.
+        Returns vpRelocCandidates as tags."""
+        tags = np.ascontiguousarray(scored["tags"], dtype=np.uint64)
+        scores = np.ascontiguousarray(scored["scores"], dtype=np.float32)
+        table = self._covisibles(tags, covisibles_of)
+        out, n = np.zeros(max(len(tags), 1), np.uint64), C.c_int32(-1)
+        self._rc(self.L_lib.orbd_accumulate_reloc(self.d, int(query_id), int(map_id), _p(tags), _p(scores), len(tags), _p(table), _p(out),
+                                                  C.byref(n)), "orbd_accumulate_reloc")
+        return [int(t) for t in out[:n.value]]
+
+    def accumulate_place(self, query_id, scored, covisibles_of):
+        """KeyFrameDatabase.cc:713-748 on a query_place result: lAccScoreAndMatch after the sort, as (accScore [n] float32, tags [n])."""
+        tags = np.ascontiguousarray(scored["tags"], dtype=np.uint64)
+        scores = np.ascontiguousarray(scored["scores"], dtype=np.float32)
+        table = self._covisibles(tags, covisibles_of)
+        acc, best = np.zeros(max(len(tags), 1), np.float32), np.zeros(max(len(tags), 1), np.uint64)
+        self._rc(self.L_lib.orbd_accumulate_place(self.d, int(query_id), _p(tags), _p(scores), len(tags), _p(table), _p(acc), _p(best)),
+                 "orbd_accumulate_place")
+        return acc[:len(tags)].copy(), [int(t) for t in best[:len(tags)]]
+
+    @staticmethod
+    def take_n_best(sorted_acc, n_candidates, query_map, map_of, is_bad=lambda tag: False, map_is_bad=lambda m: False):
+        """The take loop of KeyFrameDatabase.cc:760-783 over accumulate_place's list: (vpLoopCand, vpMergeCand).  As written, the
+        reference's loop never advances past a bad keyframe (:764-765); this one skips it."""
+        loop, merge, seen = [], [], set()
+        for t in sorted_acc[1]:
+            if not (len(loop) < n_candidates or len(merge) < n_candidates):
+                break
+            if is_bad(t):
+                continue
+            if t not in seen:
+                if map_of(t) == query_map and len(loop) < n_candidates:
+                    loop.append(t)
+                elif map_of(t) != query_map and len(merge) < n_candidates and not map_is_bad(map_of(t)):
+                    merge.append(t)
+                seen.add(t)
+        return loop, merge
+
+    def DetectRelocalizationCandidates(self, query_id, bow, covisibles_of, map_id, host=False):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (KeyFrameDatabase.cc:814-926): vpRelocCandidates as tags."""
+        scored = (self.query_reloc_host if host else self.query_reloc)(query_id, bow)
+        if len(scored["tags"]) == 0:
+            return []
+        return self.accumulate_reloc(query_id, map_id, scored, covisibles_of)
+
+    def DetectNBestCandidates(self, query_id, connected, bow, covisibles_of, n_candidates, query_map, map_of, is_bad=lambda tag: False,
+                              map_is_bad=lambda m: False, host=False):
+        """KeyFrameDatabase::DetectNBestCandidates (KeyFrameDatabase.cc:620-811): (vpLoopCand, vpMergeCand) as tags."""
+        scored = (self.query_place_host if host else self.query_place)(query_id, connected, bow)
+        if len(scored["tags"]) == 0:
+            return [], []
+        return self.take_n_best(self.accumulate_place(query_id, scored, covisibles_of), n_candidates, query_map, map_of, is_bad, map_is_bad)
+
+    def batch_scratch_bytes(self, nq):
+        return int(self.L_lib.orbd_batch_scratch_bytes(self.d, int(nq)))
+
+    def score_batch_device(self, query_ids, d_bow_id, d_bow_val, d_n_bow, cap, d_out_tag, d_out_score, out_cap, d_counts, d_scratch,
+                           stream=None):
+        """The relocalisation query for len(query_ids) resident BowVectors (orbd_score_batch_device): device addresses (ints),
+        asynchronous on `stream`; reads the handle's query ids and does not update them.  d_out_tag / d_out_score [nq][out_cap],
+        d_counts [nq][4] = max_common, min_common, scored, listed; d_scratch: batch_scratch_bytes(nq) bytes."""
+        q = np.ascontiguousarray(query_ids, dtype=np.uint64).reshape(-1)
+        rc = self.L_lib.orbd_score_batch_device(self.d, len(q), _p(q), _dp(d_bow_id), _dp(d_bow_val), _dp(d_n_bow), int(cap), _dp(d_out_tag),
+                                                _dp(d_out_score), int(out_cap), _dp(d_counts), _dp(d_scratch), _dp(stream))
+        return self._rc(rc, "orbd_score_batch_device")

@@ -8,6 +8,7 @@
 // ORBX_E_HIP when no device is usable.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,7 @@
 #include "orb_bow_kernels.h"
 #include "orb_mappoint_kernels.h"
 #include "orb_voc_kernels.h"
+#include "orb_kfdb_kernels.h"
 
 static_assert(sizeof(orbx_keypoint_t) == 28, "cv::KeyPoint layout");
 static_assert(sizeof(KpOut) == 28, "cv::KeyPoint layout");
@@ -4547,6 +4549,608 @@ int orbv_transform_batch_device_form(orbv_t *v, int descend_form, const uint8_t 
   if (descend_form != 0 && descend_form != 1) return voc_fail("orbv_transform_batch_device_form: descend_form outside {0, 1}");
   return voc_batch(v, d_descriptors, nframes, cap, d_n, n_stride, levelsup, d_word, d_node, d_bow_id, d_bow_val, d_n_bow, d_fv_node_id,
                    d_fv_start, d_fv_idx, d_n_fv, d_scratch, stream, descend_form);
+}
+
+}  // extern "C"
+
+// =====================================================================================================================================
+// KeyFrameDatabase (KeyFrameDatabase.cc:39-98, :620-811, :814-926): csrc/orb_ref_kfdb.h on the host, csrc/orb_kfdb_kernels.h on the device
+// =====================================================================================================================================
+
+struct orbd_handle {
+  int device = -1, n_words = 0, capacity = 0;
+  std::mutex mu;                                   // where the reference holds mMutex, and around every other use of the tables
+  // slots in add order; an erased slot is a tombstone (n = -1) until the next compaction
+  std::vector<KfdbSlot> slot;                      // the mirror of d_slot: off, n, tag, rq = mnRelocQuery
+  std::vector<uint64_t> map_id, place_q;           // GetMap(), mnPlaceRecognitionQuery
+  std::vector<float> reloc_s, place_s;             // mRelocScore, mPlaceRecognitionScore
+  std::vector<uint8_t> on_host;                    // the slot's words are in h_ids / h_val (not so after orbd_add_device)
+  std::vector<uint32_t> h_ids; std::vector<double> h_val;   // the pool, same offsets as on the device
+  size_t pool_used = 0, pool_cap = 0;
+  int live = 0;
+  std::map<uint64_t, int> by_tag;                  // live entries only
+  KfdbSlot *d_slot = nullptr; uint32_t *d_ids = nullptr; double *d_val = nullptr; uint32_t *d_bitmap = nullptr;
+  int bm_stride = 0;
+  bool rq_dirty = false;                           // d_slot[].rq is behind slot[].rq (only the batch form reads it there)
+  hipStream_t s = nullptr;
+  uint8_t *d_work = nullptr, *pin = nullptr; size_t work_bytes = 0;
+};
+
+static thread_local std::string g_kfdb_err;
+static int kfdb_fail(const std::string &what) { g_kfdb_err = what; return ORBX_E_ARG; }
+#define DCHECK(call)                                                        \
+  do {                                                                      \
+    hipError_t e_ = (call);                                                 \
+    if (e_ != hipSuccess) {                                                 \
+      g_kfdb_err = std::string(#call) + ": " + hipGetErrorString(e_);       \
+      return ORBX_E_HIP;                                                    \
+    }                                                                       \
+  } while (0)
+
+// k_kfdb_order sorts up to 16384 8-byte keys in dynamic LDS
+static hipError_t kfdb_raise_lds(int device) {
+  static std::mutex mu;
+  static bool done[64] = {};
+  std::lock_guard<std::mutex> lock(mu);
+  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
+  if (done[device]) return hipSuccess;
+  const void *fn = reinterpret_cast<const void *>(&k_kfdb_order);
+  hipFuncAttributes a;
+  hipError_t e = hipFuncGetAttributes(&a, fn);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ORB_LDS_LIMIT - (int)a.sharedSizeBytes);
+  if (e != hipSuccess) return e;
+  done[device] = true;
+  return hipSuccess;
+}
+
+// ids strictly ascending and below n_words, values finite
+static int kfdb_check_bow(const orbd_handle *d, const char *who, const uint32_t *id, const double *val, int n) {
+  if (n < 0 || n > ORBM_MAX_KEYPOINTS) return kfdb_fail(std::string(who) + ": n outside [0, ORBM_MAX_KEYPOINTS]");
+  if (n > 0 && (!id || !val)) return kfdb_fail(std::string(who) + ": NULL BowVector");
+  for (int i = 0; i < n; i++) {
+    if (id[i] >= (uint32_t)d->n_words) return kfdb_fail(std::string(who) + ": a word id is not below n_words");
+    if (i > 0 && id[i] <= id[i - 1]) return kfdb_fail(std::string(who) + ": word ids are not strictly ascending");
+    if (val && !std::isfinite(val[i])) return kfdb_fail(std::string(who) + ": a word value is not finite");
+  }
+  return 0;
+}
+
+// the device pool holds at least `need` words: a larger block, the used prefix copied device to device
+static int kfdb_reserve_pool(orbd_handle *d, size_t need) {
+  if (d->device < 0 || need <= d->pool_cap) return 0;
+  size_t cap = d->pool_cap ? d->pool_cap : 65536;
+  while (cap < need) cap *= 2;
+  uint32_t *ni = nullptr; double *nv = nullptr;
+  DCHECK(hipMalloc(&ni, sizeof(uint32_t) * cap));
+  hipError_t e = hipMalloc(&nv, sizeof(double) * cap);
+  if (e == hipSuccess && d->pool_used) e = hipMemcpy(ni, d->d_ids, sizeof(uint32_t) * d->pool_used, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && d->pool_used) e = hipMemcpy(nv, d->d_val, sizeof(double) * d->pool_used, hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) { (void)hipFree(ni); if (nv) (void)hipFree(nv); g_kfdb_err = std::string("orbd: pool: ") + hipGetErrorString(e); return ORBX_E_HIP; }
+  if (d->d_ids) (void)hipFree(d->d_ids);
+  if (d->d_val) (void)hipFree(d->d_val);
+  d->d_ids = ni; d->d_val = nv; d->pool_cap = cap;
+  return 0;
+}
+
+// Drops the tombstones; the live entries keep their relative order (the ORDER RULE reads the slot index as the add sequence).
+static int kfdb_compact(orbd_handle *d) {
+  const int ns = (int)d->slot.size();
+  if (d->live == ns) return 0;
+  std::vector<KfdbSlot> slot; std::vector<uint64_t> map_id, place_q; std::vector<float> reloc_s, place_s; std::vector<uint8_t> on_host;
+  std::vector<uint32_t> h_ids(d->h_ids.size()); std::vector<double> h_val(d->h_val.size());
+  uint32_t *ni = nullptr; double *nv = nullptr;
+  if (d->device >= 0 && d->pool_cap) {
+    DCHECK(hipMalloc(&ni, sizeof(uint32_t) * d->pool_cap));
+    hipError_t e = hipMalloc(&nv, sizeof(double) * d->pool_cap);
+    if (e != hipSuccess) { (void)hipFree(ni); g_kfdb_err = std::string("orbd: compaction: ") + hipGetErrorString(e); return ORBX_E_HIP; }
+  }
+  size_t used = 0;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < ns; i++) {
+    const KfdbSlot &o = d->slot[i];
+    if (o.n < 0) continue;
+    KfdbSlot t = o;
+    t.off = (uint32_t)used;
+    if (o.n > 0) {
+      if (d->on_host[i]) {
+        memcpy(&h_ids[used], &d->h_ids[o.off], sizeof(uint32_t) * (size_t)o.n);
+        memcpy(&h_val[used], &d->h_val[o.off], sizeof(double) * (size_t)o.n);
+      }
+      if (ni && e == hipSuccess) e = hipMemcpy(ni + used, d->d_ids + o.off, sizeof(uint32_t) * (size_t)o.n, hipMemcpyDeviceToDevice);
+      if (ni && e == hipSuccess) e = hipMemcpy(nv + used, d->d_val + o.off, sizeof(double) * (size_t)o.n, hipMemcpyDeviceToDevice);
+    }
+    used += (size_t)o.n;
+    slot.push_back(t); map_id.push_back(d->map_id[i]); place_q.push_back(d->place_q[i]); reloc_s.push_back(d->reloc_s[i]);
+    place_s.push_back(d->place_s[i]); on_host.push_back(d->on_host[i]);
+  }
+  if (e == hipSuccess && d->device >= 0 && !slot.empty())
+    e = hipMemcpy(d->d_slot, slot.data(), sizeof(KfdbSlot) * slot.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (ni) (void)hipFree(ni);
+    if (nv) (void)hipFree(nv);
+    g_kfdb_err = std::string("orbd: compaction: ") + hipGetErrorString(e);
+    return ORBX_E_HIP;
+  }
+  if (ni) { (void)hipFree(d->d_ids); (void)hipFree(d->d_val); d->d_ids = ni; d->d_val = nv; }
+  d->slot.swap(slot); d->map_id.swap(map_id); d->place_q.swap(place_q); d->reloc_s.swap(reloc_s); d->place_s.swap(place_s);
+  d->on_host.swap(on_host); d->h_ids.swap(h_ids); d->h_val.swap(h_val);
+  d->pool_used = used; d->rq_dirty = false;
+  d->by_tag.clear();
+  for (int i = 0; i < (int)d->slot.size(); i++) d->by_tag[d->slot[i].tag] = i;
+  return 0;
+}
+
+static int kfdb_upload_slot(orbd_handle *d, int i) {
+  if (d->device < 0) return 0;
+  DCHECK(hipMemcpy(d->d_slot + i, &d->slot[i], sizeof(KfdbSlot), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// room for one more keyframe of n words: a free slot (after a compaction if need be) and pool space
+static int kfdb_make_room(orbd_handle *d, const char *who, uint64_t tag, int n) {
+  if (tag == ORBD_NO_TAG) return kfdb_fail(std::string(who) + ": tag is the sentinel ORBD_NO_TAG");
+  if (d->by_tag.count(tag)) return kfdb_fail(std::string(who) + ": duplicate tag (the keyframe is in the database)");
+  if (d->live >= d->capacity) return kfdb_fail(std::string(who) + ": the database holds `capacity` keyframes");
+  if (d->device >= 0) DCHECK(hipSetDevice(d->device));
+  if ((int)d->slot.size() >= d->capacity || d->pool_used + (size_t)n > 0xffffffffull) {
+    const int rc = kfdb_compact(d);
+    if (rc < 0) return rc;
+  }
+  if (d->pool_used + (size_t)n > 0xffffffffull) return kfdb_fail(std::string(who) + ": the word pool is full");
+  return kfdb_reserve_pool(d, d->pool_used + (size_t)n);
+}
+
+static void kfdb_push(orbd_handle *d, uint64_t tag, uint64_t map_id, int n, bool on_host, const orbd_members_t *init) {
+  KfdbSlot t;
+  memset(&t, 0, sizeof t);
+  t.off = (uint32_t)d->pool_used; t.n = n; t.tag = tag; t.rq = init ? init->reloc_query : 0;
+  d->by_tag[tag] = (int)d->slot.size();
+  d->slot.push_back(t); d->map_id.push_back(map_id); d->place_q.push_back(init ? init->place_query : 0);
+  d->reloc_s.push_back(init ? init->reloc_score : 0.0f); d->place_s.push_back(init ? init->place_score : 0.0f);
+  d->on_host.push_back(on_host ? 1 : 0);
+  d->pool_used += (size_t)n; d->live++;
+  if (d->h_ids.size() < d->pool_used) { d->h_ids.resize(d->pool_used + d->pool_used / 2); d->h_val.resize(d->h_ids.size()); }
+}
+
+static int kfdb_erase_slot(orbd_handle *d, int i) {
+  d->by_tag.erase(d->slot[i].tag);
+  d->slot[i].n = -1;
+  d->live--;
+  return kfdb_upload_slot(d, i);
+}
+
+// What both forms of a query hand to the common tail: the common-word count of every slot and the scored list in list order.
+struct KfdbResult {
+  std::vector<int32_t> cnt;         // [n_slots]; meaningful where listable
+  int32_t hdr[KFDB_HDR] = {0, 0, 0, 0};
+  std::vector<int32_t> out_slot; std::vector<float> out_score;
+};
+
+// csrc/orb_ref_kfdb.h in plain C++ over the host copy, by the ORDER RULE
+static void kfdb_query_host(const orbd_handle *d, const std::vector<uint8_t> &listable, const uint32_t *qid, const double *qval, int n, KfdbResult *R) {
+  const int ns = (int)d->slot.size();
+  R->cnt.assign(ns, 0);
+  std::vector<uint64_t> keys;
+  int max_common = 0;
+  for (int s = 0; s < ns; s++) {
+    if (!listable[s]) continue;
+    const KfdbSlot &sl = d->slot[s];
+    const uint32_t *ids = d->h_ids.data() + sl.off;
+    int a = 0, b = 0, words = 0;
+    uint32_t first = 0;
+    while (a < n && b < sl.n) {
+      if (qid[a] == ids[b]) { if (!words) first = ids[b]; words++; a++; b++; }
+      else if (qid[a] < ids[b]) a++;
+      else b++;
+    }
+    R->cnt[s] = words;
+    if (words > 0) { keys.push_back(kfdb_order_key(first, (uint32_t)s)); if (words > max_common) max_common = words; }
+  }
+  std::sort(keys.begin(), keys.end());
+  const int min_common = kfdb_min_common(max_common);
+  for (uint64_t key : keys) {
+    const int s = (int)(uint32_t)key;
+    if (!kfdb_passes(R->cnt[s], min_common)) continue;
+    const KfdbSlot &sl = d->slot[s];
+    const uint32_t *ids = d->h_ids.data() + sl.off;
+    const double *val = d->h_val.data() + sl.off;
+    double score = 0;
+    int a = 0, b = 0;
+    while (a < n && b < sl.n) {
+      if (qid[a] == ids[b]) { kfdb_l1_add(&score, kfdb_l1_term(qval[a], val[b])); a++; b++; }
+      else if (qid[a] < ids[b]) a++;
+      else b++;
+    }
+    R->out_slot.push_back(s);
+    R->out_score.push_back(kfdb_l1_finish(score));
+  }
+  R->hdr[KFDB_H_MAX] = max_common; R->hdr[KFDB_H_MIN] = min_common;
+  R->hdr[KFDB_H_SCORED] = (int32_t)R->out_slot.size(); R->hdr[KFDB_H_LISTED] = (int32_t)keys.size();
+}
+
+static void kfdb_fill_params(const orbd_handle *d, KfdbParams *P) {
+  memset(P, 0, sizeof *P);
+  P->slot = d->d_slot; P->n_slots = (int)d->slot.size(); P->ids = d->d_ids; P->val = d->d_val;
+  P->n_words = d->n_words; P->bm_stride = d->bm_stride;
+}
+
+static void kfdb_launch(const KfdbParams &P, int nq, hipStream_t s, bool unmark) {
+  const unsigned gq = (unsigned)std::max(1, (P.cap + 255) / 256), gs = (unsigned)((P.n_slots + 3) / 4);
+  int p2 = 2;
+  while (p2 < P.n_slots) p2 <<= 1;
+  hipLaunchKernelGGL(k_kfdb_mark, dim3(gq, (unsigned)nq), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(k_kfdb_count, dim3(gs, (unsigned)nq), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(k_kfdb_order, dim3((unsigned)nq), dim3(KFDB_THREADS), sizeof(uint64_t) * (size_t)p2, s, P);
+  hipLaunchKernelGGL(k_kfdb_score, dim3(gs, (unsigned)nq), dim3(256), 0, s, P);
+  if (unmark) hipLaunchKernelGGL(k_kfdb_unmark, dim3(gq, 1u), dim3(256), 0, s, P);
+}
+
+// one upload (count, values, ids, listable flags), five kernels, one download (header, counts, scored list), one synchronisation
+static int kfdb_query_device(orbd_handle *d, const std::vector<uint8_t> &listable, const uint32_t *qid, const double *qval, int n, KfdbResult *R) {
+  const size_t ns = d->slot.size(), N = (size_t)n;
+  const size_t o_val = 8, o_id = o_val + 8 * N, o_flag = o_id + 4 * N, up = o_flag + ns;
+  const size_t o_hdr = (up + 15) & ~(size_t)15, o_cnt = o_hdr + 4 * KFDB_HDR, o_slot = o_cnt + 4 * ns, o_score = o_slot + 4 * ns,
+               o_first = o_score + 4 * ns, bytes = o_first + 4 * ns;
+  DCHECK(hipSetDevice(d->device));
+  if (d->work_bytes < bytes) {
+    if (d->d_work) DCHECK(hipFree(d->d_work));
+    d->d_work = nullptr;
+    if (d->pin) DCHECK(hipHostFree(d->pin));
+    d->pin = nullptr; d->work_bytes = 0;
+    const size_t room = bytes + bytes / 2;
+    DCHECK(hipMalloc(&d->d_work, room));
+    DCHECK(hipHostMalloc(&d->pin, room, hipHostMallocDefault));
+    d->work_bytes = room;
+  }
+  uint8_t *h = d->pin, *w = d->d_work;
+  *(int32_t *)h = n; *(int32_t *)(h + 4) = 0;
+  memcpy(h + o_val, qval, 8 * N);
+  memcpy(h + o_id, qid, 4 * N);
+  memcpy(h + o_flag, listable.data(), ns);
+  DCHECK(hipMemcpyAsync(w, h, up, hipMemcpyHostToDevice, d->s));
+  KfdbParams P;
+  kfdb_fill_params(d, &P);
+  P.bitmap = d->d_bitmap;
+  P.q_n = (const int32_t *)w; P.q_val = (const double *)(w + o_val); P.q_id = (const uint32_t *)(w + o_id); P.cap = n;
+  P.listable = w + o_flag;
+  P.hdr = (int32_t *)(w + o_hdr); P.cnt = (int32_t *)(w + o_cnt); P.out_slot = (int32_t *)(w + o_slot); P.out_score = (float *)(w + o_score);
+  P.first = (uint32_t *)(w + o_first); P.out_tag = nullptr; P.out_stride = (int)ns;
+  kfdb_launch(P, 1, d->s, true);
+  DCHECK(hipGetLastError());
+  DCHECK(hipMemcpyAsync(h + o_hdr, w + o_hdr, o_first - o_hdr, hipMemcpyDeviceToHost, d->s));
+  DCHECK(hipStreamSynchronize(d->s));
+  memcpy(R->hdr, h + o_hdr, 4 * KFDB_HDR);
+  const int scored = R->hdr[KFDB_H_SCORED];
+  if (scored < 0 || (size_t)scored > ns || R->hdr[KFDB_H_LISTED] < scored || (size_t)R->hdr[KFDB_H_LISTED] > ns) {
+    g_kfdb_err = "orbd_query: the device returned counts outside [0, keyframes]";
+    return ORBX_E_HIP;
+  }
+  R->cnt.assign((const int32_t *)(h + o_cnt), (const int32_t *)(h + o_cnt) + ns);
+  R->out_slot.assign((const int32_t *)(h + o_slot), (const int32_t *)(h + o_slot) + scored);
+  R->out_score.assign((const float *)(h + o_score), (const float *)(h + o_score) + scored);
+  for (int s : R->out_slot)
+    if (s < 0 || (size_t)s >= ns) { g_kfdb_err = "orbd_query: the device returned a slot outside the database"; return ORBX_E_HIP; }
+  return 0;
+}
+
+// form 0: DetectRelocalizationCandidates :816-871; form 1: DetectNBestCandidates :627-711
+static int kfdb_query(orbd_handle *d, const char *who, int form, bool on_device, uint64_t query_id, const uint64_t *connected, int n_connected,
+                      const uint32_t *bow_id, const double *bow_val, int n, uint64_t *out_tag, float *out_score, int out_cap,
+                      int32_t *n_scored, int32_t *max_common, int32_t *min_common, int32_t *n_listed) {
+  if (!d) return kfdb_fail(std::string(who) + ": NULL handle");
+  if (on_device && d->device < 0) return kfdb_fail(std::string(who) + ": the handle was created with device = -1 and has no device tables");
+  if (!n_scored || !max_common || !min_common || !n_listed || n_connected < 0 || (n_connected > 0 && !connected))
+    return kfdb_fail(std::string(who) + ": NULL argument or n_connected < 0");
+  std::lock_guard<std::mutex> lock(d->mu);
+  int rc = kfdb_check_bow(d, who, bow_id, bow_val, n);
+  if (rc < 0) return rc;
+  if (out_cap < d->live || (d->live > 0 && (!out_tag || !out_score)))
+    return kfdb_fail(std::string(who) + ": out_cap is below the number of live keyframes, or a NULL output");
+  const int ns = (int)d->slot.size();
+  std::vector<uint8_t> listable(ns, 0);
+  for (int s = 0; s < ns; s++) {
+    if (d->slot[s].n < 0) continue;
+    if (!on_device && !d->on_host[s]) return kfdb_fail(std::string(who) + ": a keyframe added by orbd_add_device has no host copy");
+    listable[s] = (form == 0 ? d->slot[s].rq : d->place_q[s]) != query_id;
+  }
+  for (int c = 0; c < n_connected; c++) {   // spConnectedKF (:637, :656): counted, never listed, never marked
+    const auto it = d->by_tag.find(connected[c]);
+    if (it == d->by_tag.end()) return kfdb_fail(std::string(who) + ": a connected tag is not in the database");
+    listable[it->second] = 0;
+  }
+  KfdbResult R;
+  if (ns > 0 && n > 0) {
+    if (on_device) { rc = kfdb_query_device(d, listable, bow_id, bow_val, n, &R); if (rc < 0) return rc; }
+    else kfdb_query_host(d, listable, bow_id, bow_val, n, &R);
+    for (int s = 0; s < ns; s++)
+      if (listable[s] && R.cnt[s] > 0) {   // :832, :659
+        if (form == 0) { d->slot[s].rq = query_id; d->rq_dirty = true; } else d->place_q[s] = query_id;
+      }
+  }
+  for (size_t r = 0; r < R.out_slot.size(); r++) {
+    const int s = R.out_slot[r];
+    (form == 0 ? d->reloc_s : d->place_s)[s] = R.out_score[r];   // :865, :705
+    out_tag[r] = d->slot[s].tag; out_score[r] = R.out_score[r];
+  }
+  *n_scored = R.hdr[KFDB_H_SCORED]; *max_common = R.hdr[KFDB_H_MAX]; *min_common = R.hdr[KFDB_H_MIN]; *n_listed = R.hdr[KFDB_H_LISTED];
+  return 0;
+}
+
+// the accumulation over covisibles (:877-902, :719-744) shared by both forms
+struct KfdbAcc { float acc; uint64_t best; };
+static int kfdb_accumulate(orbd_handle *d, const char *who, int form, uint64_t query_id, const uint64_t *tags, const float *scores, int n,
+                           const uint64_t *covisibles, std::vector<KfdbAcc> *out, float *best_acc) {
+  if (n < 0 || (n > 0 && (!tags || !scores || !covisibles))) return kfdb_fail(std::string(who) + ": NULL argument or n < 0");
+  for (int i = 0; i < n; i++)
+    if (!d->by_tag.count(tags[i])) return kfdb_fail(std::string(who) + ": a scored tag is not in the database");
+  *best_acc = 0;   // :874, :714
+  for (int i = 0; i < n; i++) {
+    float best = scores[i], acc = best;
+    uint64_t best_kf = tags[i];
+    for (int k = 0; k < ORBD_COVISIBLES; k++) {
+      const uint64_t t = covisibles[(size_t)i * ORBD_COVISIBLES + k];
+      if (t == ORBD_NO_TAG) continue;
+      const auto it = d->by_tag.find(t);
+      if (it == d->by_tag.end()) continue;                                                        // unknown or erased: "query id differs"
+      if ((form == 0 ? d->slot[it->second].rq : d->place_q[it->second]) != query_id) continue;    // :888, :730
+      const float s2 = (form == 0 ? d->reloc_s : d->place_s)[it->second];
+      kfdb_acc_add(&acc, s2);
+      if (kfdb_beats(s2, best)) { best_kf = t; best = s2; }
+    }
+    out->push_back(KfdbAcc{acc, best_kf});
+    if (acc > *best_acc) *best_acc = acc;
+  }
+  return 0;
+}
+
+extern "C" {
+
+const char *orbd_last_error(const orbd_t *) { return g_kfdb_err.c_str(); }
+
+void orbd_destroy(orbd_t *d) {
+  if (!d) return;
+  if (d->device >= 0) {
+    (void)hipSetDevice(d->device);
+    if (d->s) { (void)hipStreamSynchronize(d->s); (void)hipStreamDestroy(d->s); }
+    if (d->d_slot) (void)hipFree(d->d_slot);
+    if (d->d_ids) (void)hipFree(d->d_ids);
+    if (d->d_val) (void)hipFree(d->d_val);
+    if (d->d_bitmap) (void)hipFree(d->d_bitmap);
+    if (d->d_work) (void)hipFree(d->d_work);
+    if (d->pin) (void)hipHostFree(d->pin);
+  }
+  delete d;
+}
+
+orbd_t *orbd_create(int n_words, int scoring, int capacity, int device) {
+  g_kfdb_err.clear();
+  if (n_words < 0 || device < -1) { kfdb_fail("orbd_create: n_words < 0 or device < -1"); return nullptr; }
+  if (scoring != VOC_L1_NORM) { kfdb_fail("orbd_create: only L1_NORM scoring (type 0, what ORBvoc uses) is supported (csrc/orb_ref_kfdb.h)"); return nullptr; }
+  if (capacity < 1 || capacity > ORBD_MAX_KEYFRAMES) { kfdb_fail("orbd_create: capacity outside [1, ORBD_MAX_KEYFRAMES]"); return nullptr; }
+  orbd_handle *d = new orbd_handle;
+  d->device = device; d->n_words = n_words; d->capacity = capacity; d->bm_stride = (n_words + 31) / 32 + 1;
+  if (device < 0) return d;
+  const hipError_t e0 = hipSetDevice(device);
+  hipError_t e = e0;
+  if (e == hipSuccess) e = kfdb_raise_lds(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc(&d->d_slot, sizeof(KfdbSlot) * (size_t)capacity);
+  if (e == hipSuccess) e = hipMalloc(&d->d_bitmap, sizeof(uint32_t) * (size_t)d->bm_stride);
+  if (e == hipSuccess) e = hipMemset(d->d_bitmap, 0, sizeof(uint32_t) * (size_t)d->bm_stride);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    const std::string what = std::string("orbd_create: HIP: ") + hipGetErrorString(e);
+    if (e0 != hipSuccess) d->device = -1;
+    orbd_destroy(d);
+    g_kfdb_err = what;
+    return nullptr;
+  }
+  return d;
+}
+
+orbd_t *orbd_create_for_vocabulary(const orbv_t *v, int capacity, int device) {
+  if (!v) { kfdb_fail("orbd_create_for_vocabulary: NULL vocabulary"); return nullptr; }
+  return orbd_create(v->n_words, v->scoring, capacity, device);
+}
+
+int orbd_n_words(const orbd_t *d) { return d ? d->n_words : ORBX_E_ARG; }
+int orbd_capacity(const orbd_t *d) { return d ? d->capacity : ORBX_E_ARG; }
+int orbd_size(orbd_t *d) {
+  if (!d) return ORBX_E_ARG;
+  std::lock_guard<std::mutex> lock(d->mu);
+  return d->live;
+}
+
+int orbd_add(orbd_t *d, uint64_t tag, uint64_t map_id, const uint32_t *bow_id, const double *bow_val, int n, const orbd_members_t *init) {
+  if (!d) return kfdb_fail("orbd_add: NULL handle");
+  std::lock_guard<std::mutex> lock(d->mu);
+  int rc = kfdb_check_bow(d, "orbd_add", bow_id, bow_val, n);
+  if (rc < 0) return rc;
+  rc = kfdb_make_room(d, "orbd_add", tag, n);
+  if (rc < 0) return rc;
+  if (d->device >= 0 && n > 0) {
+    DCHECK(hipMemcpy(d->d_ids + d->pool_used, bow_id, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
+    DCHECK(hipMemcpy(d->d_val + d->pool_used, bow_val, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  }
+  const size_t at = d->pool_used;
+  kfdb_push(d, tag, map_id, n, true, init);
+  if (n > 0) { memcpy(&d->h_ids[at], bow_id, sizeof(uint32_t) * (size_t)n); memcpy(&d->h_val[at], bow_val, sizeof(double) * (size_t)n); }
+  return kfdb_upload_slot(d, (int)d->slot.size() - 1);
+}
+
+int orbd_add_device(orbd_t *d, uint64_t tag, uint64_t map_id, const uint32_t *d_bow_id, const double *d_bow_val, const int32_t *d_n_bow,
+                    int cap, int p, const orbd_members_t *init, void *stream) {
+  if (!d) return kfdb_fail("orbd_add_device: NULL handle");
+  if (d->device < 0) return kfdb_fail("orbd_add_device: the handle was created with device = -1 and has no device tables");
+  if (!d_bow_id || !d_bow_val || !d_n_bow || cap < 1 || cap > ORBM_MAX_KEYPOINTS || p < 0 || p > 65534)
+    return kfdb_fail("orbd_add_device: NULL argument, cap outside [1, ORBM_MAX_KEYPOINTS] or p outside [0, 65534]");
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (tag == ORBD_NO_TAG || d->by_tag.count(tag)) return kfdb_fail("orbd_add_device: duplicate tag, or the sentinel ORBD_NO_TAG");
+  DCHECK(hipSetDevice(d->device));
+  hipStream_t s = (hipStream_t)stream;
+  int32_t n = 0;
+  DCHECK(hipMemcpyAsync(&n, d_n_bow + p, sizeof n, hipMemcpyDeviceToHost, s));   // the 4-byte count, nothing else comes back
+  DCHECK(hipStreamSynchronize(s));
+  n = std::min(std::max(n, 0), cap);
+  const int rc = kfdb_make_room(d, "orbd_add_device", tag, n);
+  if (rc < 0) return rc;
+  if (n > 0) {
+    DCHECK(hipMemcpyAsync(d->d_ids + d->pool_used, d_bow_id + (size_t)p * cap, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    DCHECK(hipMemcpyAsync(d->d_val + d->pool_used, d_bow_val + (size_t)p * cap, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    DCHECK(hipStreamSynchronize(s));
+  }
+  kfdb_push(d, tag, map_id, n, false, init);
+  return kfdb_upload_slot(d, (int)d->slot.size() - 1);
+}
+
+int orbd_erase(orbd_t *d, uint64_t tag) {
+  if (!d) return kfdb_fail("orbd_erase: NULL handle");
+  std::lock_guard<std::mutex> lock(d->mu);
+  const auto it = d->by_tag.find(tag);
+  if (it == d->by_tag.end()) return kfdb_fail("orbd_erase: the tag is not in the database");
+  if (d->device >= 0) DCHECK(hipSetDevice(d->device));
+  return kfdb_erase_slot(d, it->second);
+}
+
+int orbd_clear(orbd_t *d) {
+  if (!d) return kfdb_fail("orbd_clear: NULL handle");
+  std::lock_guard<std::mutex> lock(d->mu);
+  d->slot.clear(); d->map_id.clear(); d->place_q.clear(); d->reloc_s.clear(); d->place_s.clear(); d->on_host.clear(); d->by_tag.clear();
+  d->pool_used = 0; d->live = 0; d->rq_dirty = false;
+  return 0;
+}
+
+int orbd_clear_map(orbd_t *d, uint64_t map_id) {
+  if (!d) return kfdb_fail("orbd_clear_map: NULL handle");
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (d->device >= 0) DCHECK(hipSetDevice(d->device));
+  for (int i = 0; i < (int)d->slot.size(); i++)
+    if (d->slot[i].n >= 0 && d->map_id[i] == map_id) {
+      const int rc = kfdb_erase_slot(d, i);
+      if (rc < 0) return rc;
+    }
+  return 0;
+}
+
+int orbd_set_map(orbd_t *d, uint64_t tag, uint64_t map_id) {
+  if (!d) return kfdb_fail("orbd_set_map: NULL handle");
+  std::lock_guard<std::mutex> lock(d->mu);
+  const auto it = d->by_tag.find(tag);
+  if (it == d->by_tag.end()) return kfdb_fail("orbd_set_map: the tag is not in the database");
+  d->map_id[it->second] = map_id;
+  return 0;
+}
+
+int orbd_get_members(orbd_t *d, uint64_t tag, orbd_members_t *out) {
+  if (!d || !out) return kfdb_fail("orbd_get_members: NULL argument");
+  std::lock_guard<std::mutex> lock(d->mu);
+  const auto it = d->by_tag.find(tag);
+  if (it == d->by_tag.end()) return kfdb_fail("orbd_get_members: the tag is not in the database");
+  const int s = it->second;
+  out->reloc_query = d->slot[s].rq; out->place_query = d->place_q[s]; out->reloc_score = d->reloc_s[s]; out->place_score = d->place_s[s];
+  return 0;
+}
+
+int orbd_query_reloc(orbd_t *d, uint64_t query_id, const uint32_t *bow_id, const double *bow_val, int n, uint64_t *out_tag, float *out_score,
+                     int out_cap, int32_t *n_scored, int32_t *max_common, int32_t *min_common, int32_t *n_listed) {
+  return kfdb_query(d, "orbd_query_reloc", 0, true, query_id, nullptr, 0, bow_id, bow_val, n, out_tag, out_score, out_cap, n_scored, max_common,
+                    min_common, n_listed);
+}
+int orbd_query_reloc_host(orbd_t *d, uint64_t query_id, const uint32_t *bow_id, const double *bow_val, int n, uint64_t *out_tag,
+                          float *out_score, int out_cap, int32_t *n_scored, int32_t *max_common, int32_t *min_common, int32_t *n_listed) {
+  return kfdb_query(d, "orbd_query_reloc_host", 0, false, query_id, nullptr, 0, bow_id, bow_val, n, out_tag, out_score, out_cap, n_scored,
+                    max_common, min_common, n_listed);
+}
+int orbd_query_place(orbd_t *d, uint64_t query_id, const uint64_t *connected_tags, int n_connected, const uint32_t *bow_id,
+                     const double *bow_val, int n, uint64_t *out_tag, float *out_score, int out_cap, int32_t *n_scored, int32_t *max_common,
+                     int32_t *min_common, int32_t *n_listed) {
+  return kfdb_query(d, "orbd_query_place", 1, true, query_id, connected_tags, n_connected, bow_id, bow_val, n, out_tag, out_score, out_cap,
+                    n_scored, max_common, min_common, n_listed);
+}
+int orbd_query_place_host(orbd_t *d, uint64_t query_id, const uint64_t *connected_tags, int n_connected, const uint32_t *bow_id,
+                          const double *bow_val, int n, uint64_t *out_tag, float *out_score, int out_cap, int32_t *n_scored,
+                          int32_t *max_common, int32_t *min_common, int32_t *n_listed) {
+  return kfdb_query(d, "orbd_query_place_host", 1, false, query_id, connected_tags, n_connected, bow_id, bow_val, n, out_tag, out_score, out_cap,
+                    n_scored, max_common, min_common, n_listed);
+}
+
+size_t orbd_batch_scratch_bytes(const orbd_t *d, int nq) {
+  if (!d || nq < 0) return 0;
+  return (size_t)nq * (8 + 4 * (size_t)d->bm_stride + 12 * (size_t)d->capacity) + 16;
+}
+
+int orbd_score_batch_device(orbd_t *d, int nq, const uint64_t *query_id, const uint32_t *d_bow_id, const double *d_bow_val,
+                            const int32_t *d_n_bow, int cap, uint64_t *d_out_tag, float *d_out_score, int out_cap, int32_t *d_counts,
+                            void *d_scratch, void *stream) {
+  if (!d) return kfdb_fail("orbd_score_batch_device: NULL handle");
+  if (d->device < 0) return kfdb_fail("orbd_score_batch_device: the handle was created with device = -1 and has no device tables");
+  if (nq < 0 || nq > 65535 || cap < 1 || cap > ORBM_MAX_KEYPOINTS)
+    return kfdb_fail("orbd_score_batch_device: nq outside [0, 65535] or cap outside [1, ORBM_MAX_KEYPOINTS]");
+  if (nq == 0) return 0;
+  if (!query_id || !d_bow_id || !d_bow_val || !d_n_bow || !d_out_tag || !d_out_score || !d_counts || !d_scratch)
+    return kfdb_fail("orbd_score_batch_device: NULL argument");
+  if (((uintptr_t)d_bow_val & 7) || ((uintptr_t)d_out_tag & 7) || ((uintptr_t)d_scratch & 7))
+    return kfdb_fail("orbd_score_batch_device: bow_val, out_tag or scratch not 8-byte aligned");
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (out_cap < std::max(d->live, 1) || out_cap > d->capacity)
+    return kfdb_fail("orbd_score_batch_device: out_cap outside [max(live keyframes, 1), capacity]");
+  DCHECK(hipSetDevice(d->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ns = d->slot.size(), Q = (size_t)nq;
+  if (ns == 0) { DCHECK(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * KFDB_HDR * Q, s)); return 0; }
+  if (d->rq_dirty) {   // mnRelocQuery as the single queries left it
+    DCHECK(hipMemcpy(d->d_slot, d->slot.data(), sizeof(KfdbSlot) * ns, hipMemcpyHostToDevice));
+    d->rq_dirty = false;
+  }
+  uint8_t *w = (uint8_t *)d_scratch;
+  const size_t o_bm = 8 * Q, o_cnt = o_bm + 4 * Q * (size_t)d->bm_stride, o_first = o_cnt + 4 * Q * ns, o_slot = o_first + 4 * Q * ns;
+  DCHECK(hipMemcpyAsync(w, query_id, 8 * Q, hipMemcpyHostToDevice, s));
+  DCHECK(hipMemsetAsync(w + o_bm, 0, 4 * Q * (size_t)d->bm_stride, s));
+  KfdbParams P;
+  kfdb_fill_params(d, &P);
+  P.bitmap = (uint32_t *)(w + o_bm);
+  P.q_n = d_n_bow; P.q_val = d_bow_val; P.q_id = d_bow_id; P.cap = cap;
+  P.listable = nullptr; P.query_id = (const uint64_t *)w;
+  P.hdr = d_counts; P.cnt = (int32_t *)(w + o_cnt); P.first = (uint32_t *)(w + o_first); P.out_slot = (int32_t *)(w + o_slot);
+  P.out_score = d_out_score; P.out_tag = d_out_tag; P.out_stride = out_cap;
+  kfdb_launch(P, nq, s, false);
+  DCHECK(hipGetLastError());
+  return 0;
+}
+
+int orbd_accumulate_reloc(orbd_t *d, uint64_t query_id, uint64_t map_id, const uint64_t *tags, const float *scores, int n,
+                          const uint64_t *covisibles, uint64_t *out_tags, int32_t *n_out) {
+  if (!d || !n_out || (n > 0 && !out_tags)) return kfdb_fail("orbd_accumulate_reloc: NULL argument");
+  std::lock_guard<std::mutex> lock(d->mu);
+  std::vector<KfdbAcc> acc;
+  float best_acc;
+  const int rc = kfdb_accumulate(d, "orbd_accumulate_reloc", 0, query_id, tags, scores, n, covisibles, &acc, &best_acc);
+  if (rc < 0) return rc;
+  const float min_retain = kfdb_min_retain(best_acc);
+  int m = 0;
+  for (const KfdbAcc &a : acc) {
+    if (!kfdb_retained(a.acc, min_retain)) continue;
+    if (d->map_id[d->by_tag.find(a.best)->second] != map_id) continue;   // :915, after the threshold over all maps
+    bool seen = false;                                                   // spAlreadyAddedKF
+    for (int k = 0; k < m && !seen; k++) seen = out_tags[k] == a.best;
+    if (!seen) out_tags[m++] = a.best;
+  }
+  *n_out = m;
+  return 0;
+}
+
+int orbd_accumulate_place(orbd_t *d, uint64_t query_id, const uint64_t *tags, const float *scores, int n, const uint64_t *covisibles,
+                          float *out_acc, uint64_t *out_best) {
+  if (!d || (n > 0 && (!out_acc || !out_best))) return kfdb_fail("orbd_accumulate_place: NULL argument");
+  std::lock_guard<std::mutex> lock(d->mu);
+  std::vector<KfdbAcc> acc;
+  float best_acc;
+  const int rc = kfdb_accumulate(d, "orbd_accumulate_place", 1, query_id, tags, scores, n, covisibles, &acc, &best_acc);
+  if (rc < 0) return rc;
+  std::stable_sort(acc.begin(), acc.end(), [](const KfdbAcc &a, const KfdbAcc &b) { return a.acc > b.acc; });   // list::sort(compFirst), :748
+  for (int i = 0; i < n; i++) { out_acc[i] = acc[i].acc; out_best[i] = acc[i].best; }
+  return 0;
 }
 
 }  // extern "C"

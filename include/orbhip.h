@@ -1364,6 +1364,145 @@ int orbv_transform_batch_device_form(orbv_t *v, int descend_form, const uint8_t 
                                      uint32_t *d_bow_id, double *d_bow_val, int32_t *d_n_bow, uint32_t *d_fv_node_id,
                                      int32_t *d_fv_start, int32_t *d_fv_idx, int32_t *d_n_fv, void *d_scratch, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * KeyFrameDatabase: the inverted file (KeyFrameDatabase.cc:39-98) and its two live queries,
+ * DetectRelocalizationCandidates (KeyFrameDatabase.cc:814-926, called at Tracking.cc:3772) and DetectNBestCandidates
+ * (KeyFrameDatabase.cc:620-811, called at LoopClosing.cc:519), over mpVoc->score = L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  It consumes the BowVector that orbv_transform leaves and names the
+ * candidates that orbm_search_by_bow_candidates / orbm_search_by_bow_keyframes_candidates take.  DetectLoopCandidates,
+ * DetectCandidates and DetectBestCandidates have no call site in the reference and are not covered.  The arithmetic is stated
+ * once, in csrc/orb_ref_kfdb.h, for the host forms and the kernels (csrc/orb_kfdb_kernels.h); everything is bit-exact against the
+ * literal model of tests/kfdb_model.py (reference text unpinned: nothing of KeyFrameDatabase.cc is compiled against it yet).
+ *
+ * A query has two parts.  The heavy part (orbd_query_*: :816-871, :627-711) counts common words per keyframe, gates at
+ * maxCommonWords * 0.8f and scores what passes; it grows with the map and runs on the device.  The small part
+ * (orbd_accumulate_*: :873-923, :713-748) accumulates over at most ORBD_COVISIBLES covisibles of each scored keyframe; it reads the
+ * caller's live objects (GetBestCovisibilityKeyFrames, and in the take loop isBad / GetMap) and runs on the host.
+ *
+ * Keyframes are named by `tag`, the caller's opaque 64-bit name (a KeyFrame*, an mnId), unique among live entries; ORBD_NO_TAG is
+ * reserved as padding.  Results are always reported as tags, so the handle renumbers its slots when it compacts.
+ *
+ * The ORDER RULE, next to the MASKING, SEQUENTIAL, INDEPENDENCE, FUSE and SEARCH-AND-FUSE RULES above.  The reference's result
+ * order is the order of lKFsSharingWords: the order of first encounter in a walk over the query's words in ascending id and over
+ * each word's list in insertion order (:822-837, :639-671).  add (:39-45) appends the keyframe to the list of every one of its
+ * words in one call, and erase (:47-66) and clearMap (:74-98) remove without reordering, so EVERY list is a subsequence of the
+ * global add order.  A keyframe is first met under the smallest word id it shares with the query, and among the keyframes first
+ * met under the same word the list's order - the add order - decides.  Hence the first-encounter key of keyframe i is
+ *     (smallest word id it shares with the query, add sequence number of i),
+ * and sorting those unique keys gives the list.  Two consequences: a keyframe that is erased and added again moves to the END of
+ * its lists (as in the reference: push_back); and the reference's add would list a keyframe twice if it were called twice for it -
+ * every path of LoopClosing.cc:314-547 adds once and returns - so a second orbd_add of a live tag is refused.
+ *
+ * Query state.  The four KeyFrame members that only KeyFrameDatabase.cc reads or writes (serialisation apart) - mnRelocQuery,
+ * mRelocScore, mnPlaceRecognitionQuery, mPlaceRecognitionScore - live in host arrays of the handle, 0 for a new entry unless
+ * orbd_add is given values (PostLoad); orbd_get_members reads them back for a saved map.  The accumulation adds scores left by
+ * EARLIER queries for a neighbour that was listed but did not pass the gate this time (:888-891, :730-733); holding the members
+ * here keeps that exact.  DEVIATION: the reference leaves mRelocScore uninitialised (KeyFrame.cc:34, :52), so reading it before
+ * the first write is an uninitialised read there; here it is 0.  mnRelocWords / mnPlaceRecognitionWords are not kept: a count
+ * is only ever read of a keyframe the same query listed, and listing resets it (:831, :655).
+ * A keyframe whose stored query id already EQUALS query_id is not listed again (:829, :653) - which is why query id 0 finds
+ * nothing in fresh entries until another query has run.  In the place form a connected keyframe is counted but never listed and
+ * never marked (:653-663): it is absent from maxCommonWords, from the list and from the later neighbour test.
+ *
+ * Every entry validates everything before anything is written or launched, takes the handle's mutex where the reference holds
+ * mMutex (so Tracking, LocalMapping and LoopClosing threads may share a handle), and returns 0, ORBX_E_ARG or ORBX_E_HIP with the
+ * reason in orbd_last_error (per calling thread).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define ORBD_MAX_KEYFRAMES 16384            /* live keyframes: what one workgroup sorts in LDS (csrc/orb_sort.h) */
+#define ORBD_COVISIBLES 10                  /* GetBestCovisibilityKeyFrames(10), :880, :722 */
+#define ORBD_NO_TAG 0xffffffffffffffffull   /* pads a covisibles row */
+
+typedef struct orbd_handle orbd_t;
+
+typedef struct {
+  uint64_t reloc_query;   /* mnRelocQuery */
+  uint64_t place_query;   /* mnPlaceRecognitionQuery */
+  float reloc_score;      /* mRelocScore */
+  float place_score;      /* mPlaceRecognitionScore */
+} orbd_members_t;
+
+/* KeyFrameDatabase::KeyFrameDatabase (KeyFrameDatabase.cc:32-36) for a vocabulary of n_words words.  scoring: only 0 (L1_NORM, what
+ * ORBvoc uses; BowVector.h:48-56) is accepted.  capacity: live keyframes, in [1, ORBD_MAX_KEYFRAMES].  device >= 0 allocates the
+ * device tables; device = -1 gives a handle on which only the host forms work (for tests without a GPU; it is no fallback:
+ * the device entries return ORBX_E_ARG on it).  NULL on failure, the reason in orbd_last_error(NULL).
+ * orbd_create_for_vocabulary takes n_words and the scoring from a vocabulary. */
+orbd_t *orbd_create(int n_words, int scoring, int capacity, int device);
+orbd_t *orbd_create_for_vocabulary(const orbv_t *v, int capacity, int device);
+void orbd_destroy(orbd_t *d);
+const char *orbd_last_error(const orbd_t *d);
+int orbd_n_words(const orbd_t *d);
+int orbd_capacity(const orbd_t *d);
+int orbd_size(orbd_t *d);   /* live keyframes */
+
+/* KeyFrameDatabase::add (KeyFrameDatabase.cc:39-45): appends the keyframe's BowVector bow_id[n] (strictly ascending, below n_words),
+ * bow_val[n] (finite).  init: the four members (PostLoad) or NULL for zeros.  ORBX_E_ARG: an invalid vector, a duplicate tag,
+ * ORBD_NO_TAG, `capacity` live keyframes.  On the device the vectors are a CSR in add order (word ids, double values); erased
+ * entries are tombstones until a compaction, which keeps the relative order of the live entries and is invisible to the caller.
+ * orbd_add_device takes the vector of frame p of an orbv_transform_batch_device output (d_bow_id / d_bow_val [..][cap], d_n_bow[..])
+ * by device-to-device copies on `stream` and reads back only the 4-byte count; it returns after the copies.  Such an entry has no
+ * host copy, so the host forms refuse a handle that holds one. */
+int orbd_add(orbd_t *d, uint64_t tag, uint64_t map_id, const uint32_t *bow_id, const double *bow_val, int n, const orbd_members_t *init);
+int orbd_add_device(orbd_t *d, uint64_t tag, uint64_t map_id, const uint32_t *d_bow_id, const double *d_bow_val, const int32_t *d_n_bow,
+                    int cap, int p, const orbd_members_t *init, void *stream);
+/* KeyFrameDatabase::erase (:47-66), clear (:68-72), clearMap (:74-98).  orbd_set_map: a merge moves keyframes between maps
+ * (the reference reads pKF->GetMap() when it needs it, :87, :915). */
+int orbd_erase(orbd_t *d, uint64_t tag);
+int orbd_clear(orbd_t *d);
+int orbd_clear_map(orbd_t *d, uint64_t map_id);
+int orbd_set_map(orbd_t *d, uint64_t tag, uint64_t map_id);
+int orbd_get_members(orbd_t *d, uint64_t tag, orbd_members_t *out);
+
+/* The heavy part of DetectRelocalizationCandidates (KeyFrameDatabase.cc:816-871) and of DetectNBestCandidates
+ * (KeyFrameDatabase.cc:627-711) for the query BowVector bow_id[n], bow_val[n] (as orbd_add; n in [0, ORBM_MAX_KEYPOINTS]).
+ *   query_id                     F->mnId / pKF->mnId
+ *   connected_tags[n_connected]  pKF->GetConnectedKeyFrames() (:637), place form; every tag must be in the database
+ *   out_tag, out_score [out_cap] lScoreAndMatch in the reference's order (ORDER RULE): the first *n_scored entries;
+ *                                out_cap >= orbd_size(d)
+ *   *max_common, *min_common     maxCommonWords, minCommonWords = (int)(maxCommonWords * 0.8f); a keyframe is scored when its count
+ *                                is strictly greater
+ *   *n_listed                    lKFsSharingWords.size()
+ * score: over the word ids in both vectors, ascending, `score += fabs(vi - wi) - fabs(vi) - fabs(wi)` in double with vi the
+ * query's value and wi the keyframe's, then -score / 2.0 rounded to float (ScoringObject.cpp:32-65).  The stored query ids and
+ * scores are updated as the reference updates the members (:832, :865, :659, :705).
+ * The device forms cost one upload of the query, one download of the compact result and one synchronisation.  The _host forms
+ * run csrc/orb_ref_kfdb.h in plain C++ over the handle's host copy; they exist for tests, like orbv_transform_host. */
+int orbd_query_reloc(orbd_t *d, uint64_t query_id, const uint32_t *bow_id, const double *bow_val, int n, uint64_t *out_tag, float *out_score,
+                     int out_cap, int32_t *n_scored, int32_t *max_common, int32_t *min_common, int32_t *n_listed);
+int orbd_query_reloc_host(orbd_t *d, uint64_t query_id, const uint32_t *bow_id, const double *bow_val, int n, uint64_t *out_tag,
+                          float *out_score, int out_cap, int32_t *n_scored, int32_t *max_common, int32_t *min_common, int32_t *n_listed);
+int orbd_query_place(orbd_t *d, uint64_t query_id, const uint64_t *connected_tags, int n_connected, const uint32_t *bow_id,
+                     const double *bow_val, int n, uint64_t *out_tag, float *out_score, int out_cap, int32_t *n_scored, int32_t *max_common,
+                     int32_t *min_common, int32_t *n_listed);
+int orbd_query_place_host(orbd_t *d, uint64_t query_id, const uint64_t *connected_tags, int n_connected, const uint32_t *bow_id,
+                          const double *bow_val, int n, uint64_t *out_tag, float *out_score, int out_cap, int32_t *n_scored,
+                          int32_t *max_common, int32_t *min_common, int32_t *n_listed);
+
+/* The relocalisation query (KeyFrameDatabase.cc:816-871) for `nq` resident BowVectors in the layout orbv_transform_batch_device writes
+ * (d_bow_id / d_bow_val [nq][cap], d_n_bow[nq]; query q has min(max(d_n_bow[q], 0), cap) words), asynchronous on `stream`: the same
+ * kernels with a grid over all queries.  query_id[nq] is a HOST array, one id per query: a keyframe whose stored mnRelocQuery
+ * equals it is not listed.  It READS the handle's arrays and does NOT update them: no keyframe is marked and no score is stored.
+ * Per query it writes d_out_tag / d_out_score [nq][out_cap] (the scored list in list order; out_cap in [max(orbd_size, 1), capacity])
+ * and d_counts[nq][4] = maxCommonWords, minCommonWords, keyframes scored, keyframes listed.  d_scratch:
+ * orbd_batch_scratch_bytes(d, nq) bytes, 8-byte aligned, that belong to the call until the stream has passed it; the handle must not
+ * be changed (add, erase, clear, queries) until then. */
+size_t orbd_batch_scratch_bytes(const orbd_t *d, int nq);
+int orbd_score_batch_device(orbd_t *d, int nq, const uint64_t *query_id, const uint32_t *d_bow_id, const double *d_bow_val,
+                            const int32_t *d_n_bow, int cap, uint64_t *d_out_tag, float *d_out_score, int out_cap, int32_t *d_counts,
+                            void *d_scratch, void *stream);
+
+/* The small part.  tags / scores [n]: a query's scored list; covisibles[n][ORBD_COVISIBLES]: GetBestCovisibilityKeyFrames(10) of
+ * each, as tags, padded with ORBD_NO_TAG.  A neighbour that is unknown to the handle or erased counts as "query id differs" and is
+ * skipped; a scored tag must be in the database.
+ * orbd_accumulate_reloc (KeyFrameDatabase.cc:873-923): the float accumulation in the reference's order, pBestKF, bestAccScore,
+ * 0.75f * bestAccScore and the strict `>`; the map filter (:915) is applied AFTER the threshold was computed over all maps; no
+ * duplicates, list order.  out_tags[n], *n_out.
+ * orbd_accumulate_place (KeyFrameDatabase.cc:713-748): the same accumulation, then list::sort(compFirst): stable, descending by
+ * accumulated score.  out_acc[n], out_best[n]: the whole sorted list; the take loop of :760-783 stays with the caller. */
+int orbd_accumulate_reloc(orbd_t *d, uint64_t query_id, uint64_t map_id, const uint64_t *tags, const float *scores, int n,
+                          const uint64_t *covisibles, uint64_t *out_tags, int32_t *n_out);
+int orbd_accumulate_place(orbd_t *d, uint64_t query_id, const uint64_t *tags, const float *scores, int n, const uint64_t *covisibles,
+                          float *out_acc, uint64_t *out_best);
+
 #ifdef __cplusplus
 }
 #endif
