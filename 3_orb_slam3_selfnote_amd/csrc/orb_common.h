@@ -29,6 +29,22 @@
 #define FAST_REC_GROUP_WORDS 8
 #define FAST_REC_CELL_WORDS 4
 
+// k_resize's row-tile records (orbx_configure): one per (level >= 1, tile of resizeRows output rows), everything the two-pass form
+// needs of the y table, so that a tile costs one scalar load in front of its staging.  272 bytes, aligned to 16.
+//   group part, words 0-3:  first source row of the tile (clamped);  source rows it stages;  output rows it has;  its first output row
+//   row r, words 4+4r ..:   byte offset of the row's upper and of its lower source row in the T plane, (sy - first source row) * tPitch;
+//                           b0 | b1 << 16;  byte offset of output row dy0 + r in the level plane
+// Rows the tile does not have: zeros.
+#define RESIZE_ROWS_MAX 16
+#define RESIZE_REC_GROUP_WORDS 4
+#define RESIZE_REC_WORDS (RESIZE_REC_GROUP_WORDS + 4 * RESIZE_ROWS_MAX)
+
+// k_blur's tile records (orbx_configure), 8 words: x0 | y0 << 16;  level | flags;  w | h << 16;  pitch | bpitch << 16;  level plane
+// offset, low and high word;  blurred plane offset, low and high word.  Flags, from the level's geometry alone:
+#define BLUR_TILE_INTERIOR 0x100u       // input rows y0 - 3 .. y0 + 66 and the eleven 16-byte chunks from column x0 - 16 all lie inside the
+                                        // level (inside its pitch; level 0: inside its width), and no stored output needs a column outside it
+#define BLUR_TILE_WHOLE_STORES 0x200u   // every 16-byte segment of the tile's outputs that starts inside the level ends inside bpitch
+
 // k_describe: keypoint slots per wavefront in batch calls (few-frame calls: 1), and the workgroups (four wavefronts) a frame's totalKp
 // slots then take; at least one, which writes the frame's totals.  4, 8 or 16: 8 measured best (open item 6).
 #ifndef ORB_DESCRIBE_K
@@ -75,6 +91,8 @@ struct LevelGeom {
   int xtabBase, ytabBase;
   int resizeRows;    // output rows per k_resize workgroup of this level: 16, or 8 when the 16-row LDS stage would not fit (host)
   int resizeSrcRows; // most source rows any resizeRows-row tile of this level reads (host: sizes k_resize's LDS stage)
+  int resizeTPitch;  // bytes per row of k_resize's LDS plane of horizontally interpolated rows; 0: the level takes the one-pass form (host)
+  int resizeRecBase; // index of this level's first row-tile record in resizeRecs
   // blur tiles
   int tilesX, tilesY, tileBase;
   uint32_t rowTileMagic;  // floor(2^32 / row tiles of k_resize), see xcd_map
@@ -111,13 +129,14 @@ struct FrameParams {
   int32_t *candCnt;                 // [frame][nlevels] dense candidate count
   const int2 *xtab, *ytab;          // resize tables {src index, a0 | a1<<16}
   const int8_t *disc;               // ORB_DISC_PIXELS x (u, v)
-  const uint32_t *tiles;            // blur tile records, 8 words each: x0|y0<<16, level, w|h<<16, pitch|bpitch<<16, off, boff
+  const uint32_t *tiles;            // blur tile records, 8 words each (above)
   uint32_t magicCells, magicTiles, magicKpBlk;  // floor(2^32 / items per frame) of k_fast, k_blur, k_describe (xcd_map)
   int totalTiles;                   // blur tiles per frame
   int totalCells;                   // FAST cells per frame
   int totalGroups;                  // k_fast workgroups per frame: groups of up to 2 x 2 neighbouring cells
   uint32_t magicGroups;             // floor(2^32 / totalGroups), xcd_map
   const uint32_t *fastRecs;         // k_fast's group records, FAST_REC_WORDS each (above), same for every frame; written by the host only
+  const uint32_t *resizeRecs;       // k_resize's row-tile records, RESIZE_REC_WORDS each (above), same for every frame; written by the host only
   int totalKp;                      // sum of kpCap
   int octCap;                       // node capacity of the octree kernel
   const ChainTile *chain;           // k_pyramid_chain's tile records

@@ -171,30 +171,50 @@ __device__ uint32_t lds_excl_scan(uint32_t *a, int n, uint32_t *sw) {
 // behind it is twice the work per wait (the same reasoning as k_blur's 64-row tiles); alone on the chip the kernel is as fast as before,
 // beside the other pipelines the step gains 2 % (16: 208-211 k frames/s, 8: 204-207 k, 24: 206 k, 32: 201 k).  Levels whose 16-row stage
 // would not fit the LDS (images wider than ~2600 columns) take 8-row tiles (G.resizeRows, decided in orbx_configure).
-#define RESIZE_ROWS_MAX 16
 #define RESIZE_MAXSRC 32   // most source rows per tile the two-pass form stages (16 rows at scale 2: 32)
+// Diagnostic builds (-DFAST_STAMPS, -DOCT_STAMPS, -DTILE_STAMPS; tools/fast_stamps.py, octree_stamps.py, tile_stamps.py): cycle stamps of
+// thread 0 of every workgroup, eight words per workgroup.
+#if defined(FAST_STAMPS) || defined(OCT_STAMPS) || defined(TILE_STAMPS)
+__device__ unsigned int *g_fast_stamps;  // [workgroup][8], set by orbx_debug_fast_stamps
+#endif
+// -DTILE_STAMPS: k_blur's workgroups take rows 0 .. totalTiles * nframes - 1 of the buffer, k_resize's follow level by level.  Words:
+// cycles from kernel entry to 0 "tile fetch issued", 1 "tile landed" (behind the barrier), 2 the end;  3: level + 1.
+#ifdef TILE_STAMPS
+#define TSTAMP_BEGIN() const long long ts0_ = __builtin_readcyclecounter()
+#define TSTAMP(i, rowExpr, lvl) do { const long long t_ = __builtin_readcyclecounter(); if (threadIdx.x == 0 && g_fast_stamps) { const size_t r_ = (rowExpr); g_fast_stamps[r_ * 8 + (i)] = (unsigned int)(t_ - ts0_); g_fast_stamps[r_ * 8 + 3] = (unsigned int)((lvl) + 1); } } while (0)
+__device__ __forceinline__ size_t resize_stamp_row(const FrameParams &P, int level) {
+  size_t row = (size_t)P.totalTiles * P.nframes + blockIdx.x;
+  for (int l = 1; l < level; l++) row += (size_t)((P.geom[l].h + P.geom[l].resizeRows - 1) / P.geom[l].resizeRows) * P.nframes;
+  return row;
+}
+#else
+#define TSTAMP_BEGIN() do {} while (0)
+#define TSTAMP(i, rowExpr, lvl) do {} while (0)
+#endif
+#define RSTAMP(i) TSTAMP(i, resize_stamp_row(P, level), level)
 __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int smemRowBytes, int tPitch, int maxSrc) {
+  TSTAMP_BEGIN();
   extern __shared__ __align__(16) uint8_t smem_rs[];
   const LevelGeom G = P.geom[level];
   const LevelGeom Gs = P.geom[level - 1];
   const int tid = threadIdx.x;
   int frame, rowTile;
   xcd_map((G.h + G.resizeRows - 1) / G.resizeRows, G.rowTileMagic, P.nframes, frame, rowTile);
-  const int dy0 = rowTile * G.resizeRows;
-  const int nrows = min(G.resizeRows, G.h - dy0);
   int spitch;
   const uint8_t *src = level_plane(P, frame, level - 1, spitch);
   uint8_t *dstplane = P.pyr + (size_t)frame * P.pyr_fs + G.off;
   const int wq = (G.w + 3) & ~3, qw = wq >> 2;   // the x table is padded to whole output quads with copies of its last entry (host)
-  // the tile's y-coefficients go through LDS: the row code below then has no global load in front of it
-  __shared__ int2 sY[RESIZE_ROWS_MAX];
-  if (tid < nrows) sY[tid] = P.ytab[G.ytabBase + dy0 + tid];
+  // (taken here, in front of the branch, so that the table's address arrives with the other kernel arguments)
+  const uint32_t *tileRec = P.resizeRecs + (size_t)(G.resizeRecBase + rowTile) * RESIZE_REC_WORDS;
 
   if (tPitch > 0) {
-    // source row span of this tile (at most maxSrc rows: the host derived maxSrc from the same table)
-    const int syFirst = min(max(P.ytab[G.ytabBase + dy0].x, 0), Gs.h - 1);
-    const int syLast = min(max(P.ytab[G.ytabBase + dy0 + nrows - 1].x + 1, 0), Gs.h - 1);
-    const int nsrc = min(syLast - syFirst + 1, maxSrc);
+    // The row tile's record (orbx_configure, layout in orb_common.h), built from the y table on the host: the group part is one
+    // scalar load that depends on the kernel arguments alone - read through the constant address space, as k_fast reads its
+    // records (the host alone writes the table) -, so no vector-memory round trip stands in front of the staging below.
+    typedef uint32_t rec4_t __attribute__((ext_vector_type(4)));
+    const __attribute__((address_space(4))) uint32_t *rec = (const __attribute__((address_space(4))) uint32_t *)tileRec;
+    const rec4_t gr = *reinterpret_cast<const __attribute__((address_space(4))) rec4_t *>(rec);
+    const int syFirst = (int)gr[0], nsrc = (int)gr[1], nrows = (int)gr[2];   // source row span of this tile (at most maxSrc rows), its output rows
     uint8_t *sRows = smem_rs;                                  // [maxSrc][smemRowBytes]
     uint8_t *sT = sRows + (size_t)maxSrc * smemRowBytes;       // [maxSrc][tPitch] bytes, u16 entries
     // [RESIZE_ROWS_MAX], 16-byte aligned for its ds_read_b128 / ds_write_b128 (tPitch is a multiple of 8 only; the host's LDS size
@@ -205,6 +225,11 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
     int4 xtPre[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) { const int p = tid + 256 * k; xtPre[k] = 2 * p < wq ? xtab4[p] : make_int4(0, 0, 0, 0); }
+    // per output row of the tile: where its two T rows start, its coefficient pair, where it goes - the record's row part, 16 bytes
+    // per lane by LDS-DMA (lane-linear: row r lands in sRowRec[r]); pass 2 reads it behind the barriers that are there anyway
+    if (tid < nrows)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(tileRec + RESIZE_REC_GROUP_WORDS + 4 * tid),
+                                       (__attribute__((address_space(3))) void *)sRowRec, 16, 0, 0);
     const bool aligned = ((((uintptr_t)src) | (uintptr_t)spitch) & 3u) == 0;
     // Index arithmetic: 32-bit integer multiplies issue at a quarter of the full rate, so idx / ndw is taken in float --
     // (idx + 0.5) / ndw stays at least 0.5 / ndw >= 2^-11 away from an integer while the rounding error of the product is
@@ -244,13 +269,9 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
         sRows[mul24((uint32_t)r, (uint32_t)smemRowBytes) + c] = src0[mul24((uint32_t)r, (uint32_t)spitch) + c];
       }
     }
-    // per output row of the tile: where its two T rows start, its coefficient pair, where it goes
-    if (tid < nrows) {
-      const int2 yt = P.ytab[G.ytabBase + dy0 + tid];
-      const int sy0 = min(max(yt.x, 0), Gs.h - 1), sy1 = min(max(yt.x + 1, 0), Gs.h - 1);
-      sRowRec[tid] = make_uint4((uint32_t)((sy0 - syFirst) * tPitch), (uint32_t)((sy1 - syFirst) * tPitch), (uint32_t)yt.y, (uint32_t)((dy0 + tid) * G.pitch));
-    }
-    __syncthreads();
+    RSTAMP(0);
+    __syncthreads();   // the source rows and the row records have landed
+    RSTAMP(1);
     // Pass 1: T[r][c] = (S[r][sx] * a0 + S[r][sx + 1] * a1) >> 4, at most 255 * 2048 / 16 = 32640: 16 bits.  Thread = two neighbouring
     // output columns, loop over the staged source rows.  Per row ONE aligned 8-byte window [base, base + 8), base = sx_A & ~3, holds all
     // four source bytes (sx_B - sx_A <= 3: the host takes this form for horizontal scale factors below 3 only): v_perm_b32 picks each
@@ -317,10 +338,16 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
         else for (int j = 0; j < 4 && dx0 + j < G.w; j++) dst[dx0 + j] = (uint8_t)(packed >> (8 * j));
       }
     }
+    RSTAMP(2);
     return;
   }
 
   // One-pass form: the x table in LDS, the four source bytes of every output pixel straight from global memory.
+  const int dy0 = rowTile * G.resizeRows;
+  const int nrows = min(G.resizeRows, G.h - dy0);
+  // the tile's y-coefficients go through LDS: the row code below then has no global load in front of it
+  __shared__ int2 sY[RESIZE_ROWS_MAX];
+  if (tid < nrows) sY[tid] = P.ytab[G.ytabBase + dy0 + tid];
   int2 *sX = reinterpret_cast<int2 *>(smem_rs);                       // [wq]
   for (int i = tid; i < wq; i += 256) sX[i] = P.xtab[G.xtabBase + i];
   __syncthreads();
@@ -348,6 +375,7 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
     if (dx0 + 3 < G.w) *reinterpret_cast<uint32_t *>(dst + dx0) = packed;
     else for (int j = 0; j < 4 && dx0 + j < G.w; j++) dst[dx0 + j] = (uint8_t)(packed >> (8 * j));
   }
+  RSTAMP(2);   // (the one-pass form stages no tile: the end only)
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -465,10 +493,8 @@ static_assert(FAST_NT == 4 * WAVE, "k_fast gives each cell of a 2 x 2 group a wa
 static_assert(FAST_LIST % WAVE == 0, "pass 3 reads the corner list 64 entries at a time, all inside the list");
 static_assert((FAST_TILE_ROWS * FAST_TILE_PITCH) % 16 == 0, "the score plane is cleared in 16-byte stores");
 static_assert(FAST_TILE_ROWS * FAST_TILE_PITCH <= 65536, "queue entries are 16-bit tile offsets");
-// Diagnostic builds (-DFAST_STAMPS, tools/fast_stamps.py): cycles per section, thread 0 of every workgroup (wavefront 0's cell).
-#if defined(FAST_STAMPS) || defined(OCT_STAMPS)
-__device__ unsigned int *g_fast_stamps;  // [workgroup][8] cycle deltas, set by orbx_debug_fast_stamps
-#endif
+// Diagnostic builds (-DFAST_STAMPS, tools/fast_stamps.py): cycles per section, thread 0 of every workgroup (wavefront 0's cell), as
+// [workgroup][8] cycle deltas in g_fast_stamps (above)
 #ifdef FAST_STAMPS
 #define FSTAMP(i) do { const long long t_ = __builtin_readcyclecounter(); if (threadIdx.x == 0 && g_fast_stamps) g_fast_stamps[(size_t)blockIdx.x * 8 + (i)] = (unsigned int)(t_ - ft0); ft0 = t_; } while (0)
 #else
@@ -1153,6 +1179,8 @@ __device__ const BlurTab g_blurTab = make_blur_tab();
 // products per 64 rows instead of 8 + 8, one block of row sums and byte splits less, and - what the kernel's time is made of - one HBM
 // round trip in front of twice the work.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_blur(FrameParams P) {   // seven workgroups per CU by LDS (21.5 KB each): no more than 72 registers
+#define BSTAMP(i) TSTAMP(i, (size_t)blockIdx.x, level)
+  TSTAMP_BEGIN();
   typedef int v4i __attribute__((ext_vector_type(4)));
   typedef int v16i __attribute__((ext_vector_type(16)));
   // input rows 0 .. 69, then the output staging rows: the A fragments of the third block read "rows" 70 .. 95, i.e. into the staging
@@ -1164,7 +1192,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
   int tile, frame;
   xcd_map(P.totalTiles, P.magicTiles, P.nframes, frame, tile);
   const uint4 t0 = reinterpret_cast<const uint4 *>(P.tiles)[2 * tile], t1 = reinterpret_cast<const uint4 *>(P.tiles)[2 * tile + 1];
-  const int x0 = (int)(t0.x & 0xffffu), y0 = (int)(t0.x >> 16), level = (int)t0.y;
+  const int x0 = (int)(t0.x & 0xffffu), y0 = (int)(t0.x >> 16), level = (int)(t0.y & 0xffu);
+  // the host's view of the tile (orbx_configure): nothing of its 70 x 176-byte window is reflected, clamped or synthesised; every
+  // 16-byte store of its outputs lies inside the blurred plane's rows
+  const bool interior = (t0.y & BLUR_TILE_INTERIOR) != 0u, wholeStores = (t0.y & BLUR_TILE_WHOLE_STORES) != 0u;
   struct { int w, h, bpitch; size_t boff; } G;
   G.w = (int)(t0.z & 0xffffu); G.h = (int)(t0.z >> 16); G.bpitch = (int)(t0.w >> 16);
   G.boff = ((size_t)t1.w << 32) | t1.z;
@@ -1182,7 +1213,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
   const int wlim = level == 0 ? G.w : pitch;                 // bytes of a row that may be read (level 0 is the caller's image: not past its rows)
   const bool dma = aligned && G.w >= 160 && G.h >= 40 && (wlim & 15) == 0;
   const bool edgeL = x0 == 0, edgeR = x0 + 131 >= G.w;       // some stored output of this tile needs a column left of 0 / right of w - 1
-  if (dma) {
+  // ---- constant operands of this lane: H (B of the first product), V (A of the second), in the operands' element order (g_blurTab).
+  // Requested in front of the tile, so that no path fetches them behind a barrier, where nothing else would hide the round trip.
+  const int n = lane & 31, hh = lane >> 5;
+  v4i Hb[2], Va[2];
+  {
+    const uint4 *tab = reinterpret_cast<const uint4 *>(g_blurTab.v[lane]);
+    const uint4 q0 = tab[0], q1 = tab[1], q2 = tab[2], q3 = tab[3];
+    Hb[0] = v4i{(int)q0.x, (int)q0.y, (int)q0.z, (int)q0.w}; Hb[1] = v4i{(int)q1.x, (int)q1.y, (int)q1.z, (int)q1.w};
+    Va[0] = v4i{(int)q2.x, (int)q2.y, (int)q2.z, (int)q2.w}; Va[1] = v4i{(int)q3.x, (int)q3.y, (int)q3.z, (int)q3.w};
+  }
+  if (dma && interior) {
+    // Interior tiles: chunk idx = 11 r + c comes from img + (y0 - 3 + r) * pitch + x0 - 16 + 16 c as it is.  A lane's chunk of the next
+    // trip is idx + 256 = idx + 23 * 11 + 3, i.e. (r + 23, c + 3) or, past the row's end, (r + 24, c - 8): one add per trip for the
+    // address, no divide, no reflection, no clamp.
+    const uint8_t *tile0 = img + ((uint32_t)(y0 - 3) * (uint32_t)pitch + (uint32_t)(x0 - 16));   // uniform: scalar arithmetic
+    const uint32_t r0 = mul24((uint32_t)tid, 5958u) >> 16;     // tid / 11
+    uint32_t c = (uint32_t)tid - 11u * r0, off = mul24(r0, (uint32_t)pitch) + 16u * c;
+    const uint32_t step = 23u * (uint32_t)pitch + 48u, stepWrap = 24u * (uint32_t)pitch - 128u;
+#pragma unroll
+    for (int k = 0; k < (BLUR_ROWS_IN * 11 + 255) / 256; k++) {
+      if (256 * (k + 1) <= BLUR_ROWS_IN * 11 || tid + 256 * k < BLUR_ROWS_IN * 11)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(tile0 + off),
+                                         (__attribute__((address_space(3))) void *)(sIn + (tid + 256 * k) * 16), 16, 0, 0);
+      const bool wrap = c >= 8u;
+      c = wrap ? c - 8u : c + 3u;
+      off += wrap ? stepWrap : step;
+    }
+    BSTAMP(0);
+  } else if (dma) {
     for (int idx = tid; idx < BLUR_ROWS_IN * 11; idx += 256) {
       const uint32_t r = mul24((uint32_t)idx, 5958u) >> 16, c = (uint32_t)idx - 11u * r;      // idx / 11, exact below 770
       int yy = y0 - 3 + (int)r;
@@ -1194,6 +1253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(img + (mul24((uint32_t)yy, (uint32_t)pitch) + (uint32_t)xb)),
                                        (__attribute__((address_space(3))) void *)(sIn + idx * 16), 16, 0, 0);
     }
+    BSTAMP(0);
     if (edgeL || edgeR) {
       __syncthreads();                                        // the tile has landed (the compiler drains the DMA in front of the barrier)
       for (int i = tid; i < BLUR_ROWS_IN * 6; i += 256) {
@@ -1231,17 +1291,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
       }
       *reinterpret_cast<uint32_t *>(sIn + r * BLURM_PITCH + 4u * c) = v;
     }
-  }
-  // ---- constant operands of this lane: H (B of the first product), V (A of the second), in the operands' element order (g_blurTab)
-  const int n = lane & 31, hh = lane >> 5;
-  v4i Hb[2], Va[2];
-  {
-    const uint4 *tab = reinterpret_cast<const uint4 *>(g_blurTab.v[lane]);
-    const uint4 q0 = tab[0], q1 = tab[1], q2 = tab[2], q3 = tab[3];
-    Hb[0] = v4i{(int)q0.x, (int)q0.y, (int)q0.z, (int)q0.w}; Hb[1] = v4i{(int)q1.x, (int)q1.y, (int)q1.z, (int)q1.w};
-    Va[0] = v4i{(int)q2.x, (int)q2.y, (int)q2.z, (int)q2.w}; Va[1] = v4i{(int)q3.x, (int)q3.y, (int)q3.z, (int)q3.w};
+    BSTAMP(0);
   }
   __syncthreads();
+  BSTAMP(1);
   // ---- T = I H for a 32-row block of the tile's rows, seeded with 128 * 257 so that the accumulators are the row sums 0 .. 65535,
   // split into (high byte - 128, low byte - 128): the second product's B fragments (element j = register j)
   auto row_sums = [&](int mt, v4i &Bhi, v4i &Blo) {
@@ -1299,20 +1352,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     Hp = Hc; Lp = Lc;
   }
   __syncthreads();
+  // ---- stores: thread = 16-byte segment seg of staging rows tid / 8 and tid / 8 + 32.  One base per workgroup (the tile's first
+  // output, scalar) and a 32-bit offset per thread that advances by 32 rows; the byte tail exists only where the record allows it.
+  {
+    uint8_t *out0 = P.blur + (size_t)frame * P.blur_fs + G.boff + (size_t)y0 * G.bpitch + x0;
+    const int row = tid >> 3, seg = tid & 7, x = x0 + 16 * seg;
+    const uint8_t *b = sOut + row * BLURM_OPITCH + 16 * seg;
+    uint32_t off = mul24((uint32_t)row, (uint32_t)G.bpitch) + 16u * (uint32_t)seg;
 #pragma unroll
-  for (int t = 0; t < BLUR_TY / 32; t++) {
-    const int row = (tid >> 3) + 32 * t, seg = tid & 7;
-    const int y = y0 + row, x = x0 + 16 * seg;
-    if (y < G.h && x < G.w) {
-      uint8_t *out = P.blur + (size_t)frame * P.blur_fs + G.boff + (size_t)y * G.bpitch + x;
-      const uint4 v = *reinterpret_cast<const uint4 *>(sOut + row * BLURM_OPITCH + 16 * seg);
-      if (x + 16 <= G.bpitch) *reinterpret_cast<uint4 *>(out) = v;
-      else {
-        const uint8_t *b = sOut + row * BLURM_OPITCH + 16 * seg;
-        for (int cc = 0; cc < 16 && x + cc < G.w; cc++) out[cc] = b[cc];
+    for (int t = 0; t < BLUR_TY / 32; t++) {
+      if (y0 + row + 32 * t < G.h && x < G.w) {
+        if (wholeStores || x + 16 <= G.bpitch) *reinterpret_cast<uint4 *>(out0 + off) = *reinterpret_cast<const uint4 *>(b);
+        else {
+#pragma clang loop vectorize(disable) unroll(disable)
+          for (int cc = 0; cc < 16 && x + cc < G.w; cc++) out0[off + cc] = b[cc];
+        }
       }
+      b += 32 * BLURM_OPITCH;
+      off += 32u * (uint32_t)G.bpitch;
     }
   }
+  BSTAMP(2);
+#undef BSTAMP
 }
 
 // ------------------------------------------------------------------------------------------------------------

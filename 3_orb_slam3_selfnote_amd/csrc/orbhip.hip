@@ -99,7 +99,7 @@ struct orbx_handle {
   int cell_fs = 0, cand_fs = 0, lkp_fs = 0, totalTiles = 0, totalCells = 0, totalGroups = 0, totalKp = 0, octCap = 0;
   int maxKeypoints = 0;
   // device memory
-  DevBuf d_pyr, d_blur, d_cellCnt, d_cellOff, d_slots, d_cand, d_knode, d_lkp, d_lrank, d_lcnt, d_candCnt, d_fastRecs, d_tiles, d_xtab,
+  DevBuf d_pyr, d_blur, d_cellCnt, d_cellOff, d_slots, d_cand, d_knode, d_lkp, d_lrank, d_lcnt, d_candCnt, d_fastRecs, d_resizeRecs, d_tiles, d_xtab,
       d_ytab, d_disc, d_chain;
   DevBuf d_img, d_okps;  // staging for the host entry point (d_okps: counts + keypoints + descriptors, one block)
   hipStream_t stream = nullptr;
@@ -313,7 +313,7 @@ void orbx_destroy(orbx_t *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   DevBuf *bufs[] = {&h->d_pyr, &h->d_blur, &h->d_cellCnt, &h->d_cellOff, &h->d_slots, &h->d_cand, &h->d_knode, &h->d_lkp,
-                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_fastRecs, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
+                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_fastRecs, &h->d_resizeRecs, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
   for (DevBuf *b : bufs) b->release();
   for (DevBuf &b : h->stereo) b.release();
   for (DevBuf &b : h->stereo_batch) b.release();
@@ -355,8 +355,8 @@ int orbx_get_features_per_level(const orbx_t *h, int *n) {
 // floor(2^32 / n) for xcd_map's division by multiplication (n == 1: the estimate q-1 is corrected on the device)
 static uint32_t magic_div(uint32_t n) { return n <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / n); }
 
-#if defined(FAST_STAMPS) || defined(OCT_STAMPS)
-// diagnostic builds only (tools/fast_stamps.py, tools/octree_stamps.py): device buffer [workgroups][8] of u32 cycle deltas per k_fast section
+#if defined(FAST_STAMPS) || defined(OCT_STAMPS) || defined(TILE_STAMPS)
+// diagnostic builds only (tools/fast_stamps.py, tools/octree_stamps.py, tools/tile_stamps.py): device buffer [workgroups][8] of u32 cycle stamps
 int orbx_debug_fast_stamps(void *d_buf) {
   unsigned int *p = (unsigned int *)d_buf;
   return hipMemcpyToSymbol(HIP_SYMBOL(g_fast_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -1;
@@ -364,6 +364,20 @@ int orbx_debug_fast_stamps(void *d_buf) {
 #endif
 
 int orbx_max_keypoints(const orbx_t *h) { return h ? h->maxKeypoints : ORBX_E_ARG; }
+
+// k_resize's form for level G from level Gs, and the dynamic LDS it takes.  Two-pass form (rows and their horizontal interpolation
+// staged in LDS) whenever a tile's source rows fit the stage and pass 1's precondition holds (two neighbouring columns' source bytes
+// inside one aligned 8-byte window: horizontal scale factor below 3): returns the pitch of the interpolated rows.  Otherwise the
+// one-pass form straight from global memory, which stages the x table only: returns 0.
+static int resize_form(const LevelGeom &G, const LevelGeom &Gs, size_t *lds) {
+  const int rowBytes = (int)align_up((size_t)Gs.w + 4, 16);
+  const int wq = (G.w + 3) & ~3;
+  const int tPitch2 = (int)align_up((size_t)wq * 2, 8);                  // horizontally interpolated rows, 16 bits per column
+  const size_t lds2 = (size_t)G.resizeSrcRows * rowBytes + align_up((size_t)G.resizeSrcRows * tPitch2, 16) + 16 * RESIZE_ROWS_MAX;   // + the row records, 16-byte aligned
+  const bool twoPass = G.resizeSrcRows <= RESIZE_MAXSRC && (double)Gs.w / G.w < 3.0 && lds2 <= ORB_LDS_LIMIT - 1024;   // (very wide images: one-pass)
+  *lds = twoPass ? lds2 : (size_t)wq * 8;
+  return twoPass ? tPitch2 : 0;
+}
 
 int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   if (!h || rows <= 0 || cols <= 0 || max_batch <= 0) return ORBX_E_ARG;
@@ -375,6 +389,7 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   const int nl = h->nlevels;
   std::vector<LevelGeom> g(nl);
   std::vector<int2> xtab, ytab;
+  std::vector<uint32_t> resizerec;   // k_resize's row-tile records
   size_t pyr = 0, blur = 0;
   int cells = 0, slots = 0, kps = 0, tiles = 0, octCap = 8;
   for (int l = 0; l < nl; l++) {
@@ -476,6 +491,29 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
       G.resizeRows = RESIZE_ROWS_MAX;
       G.resizeSrcRows = src_rows(G.resizeRows);
       if ((size_t)G.resizeSrcRows * rowStage > 64 * 1024 || G.resizeSrcRows > RESIZE_MAXSRC) { G.resizeRows = 8; G.resizeSrcRows = src_rows(8); }
+      // the level's form, and the record of every row tile (layout: orb_common.h), from the table entries above
+      size_t ldsUnused;
+      G.resizeTPitch = resize_form(G, g[l - 1], &ldsUnused);
+      G.resizeRecBase = (int)(resizerec.size() / RESIZE_REC_WORDS);
+      for (int dy0 = 0; dy0 < G.h; dy0 += G.resizeRows) {
+        const int nrows = std::min(G.resizeRows, G.h - dy0);
+        const int2 *yt = &ytab[G.ytabBase + dy0];
+        const int syFirst = std::min(std::max(yt[0].x, 0), sh - 1), syLast = std::min(std::max(yt[nrows - 1].x + 1, 0), sh - 1);
+        resizerec.resize(resizerec.size() + RESIZE_REC_WORDS, 0u);
+        uint32_t *Q = &resizerec[resizerec.size() - RESIZE_REC_WORDS];
+        Q[0] = (uint32_t)syFirst;
+        Q[1] = (uint32_t)std::min(syLast - syFirst + 1, G.resizeSrcRows);
+        Q[2] = (uint32_t)nrows;
+        Q[3] = (uint32_t)dy0;
+        for (int r = 0; r < nrows; r++) {
+          const int sy0 = std::min(std::max(yt[r].x, 0), sh - 1), sy1 = std::min(std::max(yt[r].x + 1, 0), sh - 1);
+          uint32_t *R = Q + RESIZE_REC_GROUP_WORDS + 4 * r;
+          R[0] = (uint32_t)((sy0 - syFirst) * G.resizeTPitch);
+          R[1] = (uint32_t)((sy1 - syFirst) * G.resizeTPitch);
+          R[2] = (uint32_t)yt[r].y;
+          R[3] = (uint32_t)((dy0 + r) * G.pitch);
+        }
+      }
     } else { G.resizeRows = RESIZE_ROWS_MAX; G.resizeSrcRows = 0; }
   }
   if (slots > (1 << 30)) { h->err = "workspace too large"; return ORBX_E_ARG; }
@@ -554,8 +592,13 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
     for (int ty = 0; ty < G.tilesY; ty++)
       for (int tx = 0; tx < G.tilesX; tx++) {
         uint32_t *R = &tilerec[(size_t)(G.tileBase + ty * G.tilesX + tx) * 8];
-        R[0] = (uint32_t)(tx * BLUR_TX) | ((uint32_t)(ty * BLUR_TY) << 16);
-        R[1] = (uint32_t)l;
+        const int x0 = tx * BLUR_TX, y0 = ty * BLUR_TY;
+        const int wlim = l == 0 ? G.w : G.pitch;   // bytes of a row that k_blur may read (level 0: the caller's image)
+        const bool interior = y0 - 3 >= 0 && y0 + BLUR_TY + 2 < G.h && x0 - 16 >= 0 && x0 + 160 <= wlim && x0 + 131 < G.w;
+        bool whole = true;
+        for (int x = x0; x < std::min(x0 + BLUR_TX, G.w); x += 16) whole = whole && x + 16 <= G.bpitch;
+        R[0] = (uint32_t)x0 | ((uint32_t)y0 << 16);
+        R[1] = (uint32_t)l | (interior ? BLUR_TILE_INTERIOR : 0u) | (whole ? BLUR_TILE_WHOLE_STORES : 0u);
         R[2] = (uint32_t)G.w | ((uint32_t)G.h << 16);
         R[3] = (uint32_t)G.pitch | ((uint32_t)G.bpitch << 16);
         R[4] = (uint32_t)(G.off & 0xffffffffu); R[5] = (uint32_t)((uint64_t)G.off >> 32);
@@ -588,6 +631,8 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   XCHECK(h, h->d_candCnt.reserve(sizeof(int32_t) * nl * B));
   XCHECK(h, h->d_fastRecs.reserve(sizeof(uint32_t) * std::max<size_t>(grouprec.size(), FAST_REC_WORDS)));   // hipMalloc: aligned beyond a record's 128 bytes
   if (!grouprec.empty()) XCHECK(h, copy_on(h->stream, h->d_fastRecs.p, grouprec.data(), sizeof(uint32_t) * grouprec.size(), hipMemcpyHostToDevice));
+  XCHECK(h, h->d_resizeRecs.reserve(sizeof(uint32_t) * std::max<size_t>(resizerec.size(), RESIZE_REC_WORDS)));
+  if (!resizerec.empty()) XCHECK(h, copy_on(h->stream, h->d_resizeRecs.p, resizerec.data(), sizeof(uint32_t) * resizerec.size(), hipMemcpyHostToDevice));
   XCHECK(h, h->d_tiles.reserve(sizeof(uint32_t) * tilerec.size()));
   XCHECK(h, copy_on(h->stream, h->d_tiles.p, tilerec.data(), sizeof(uint32_t) * tilerec.size(), hipMemcpyHostToDevice));
   XCHECK(h, h->d_xtab.reserve(sizeof(int2) * std::max<size_t>(xtab.size(), 1)));
@@ -730,6 +775,7 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   P.totalTiles = h->totalTiles;
   P.totalCells = h->totalCells;
   P.fastRecs = (const uint32_t *)h->d_fastRecs.p;
+  P.resizeRecs = (const uint32_t *)h->d_resizeRecs.p;
   P.totalGroups = h->totalGroups;
   P.magicGroups = magic_div((uint32_t)std::max(h->totalGroups, 1));
   P.tiles = (const uint32_t *)h->d_tiles.p;
@@ -759,15 +805,10 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   for (int l = 1; l < h->nlevels; l++) {
     const LevelGeom &G = h->geom[l], &Gs = h->geom[l - 1];
     const int rowBytes = (int)align_up((size_t)Gs.w + 4, 16);
-    // Two-pass form (rows and their horizontal interpolation staged in LDS) whenever a tile's source rows fit the stage and pass 1's
-    // precondition holds (two neighbouring columns' source bytes inside one aligned 8-byte window: horizontal scale factor below 3);
-    // otherwise the one-pass form straight from global memory (tPitch 0), which stages the x table only.
-    const int wq = (G.w + 3) & ~3;
-    const int tPitch2 = (int)align_up((size_t)wq * 2, 8);                  // horizontally interpolated rows, 16 bits per column
-    const size_t lds2 = (size_t)G.resizeSrcRows * rowBytes + align_up((size_t)G.resizeSrcRows * tPitch2, 16) + 16 * RESIZE_ROWS_MAX;   // + the row records, 16-byte aligned
-    const bool twoPass = G.resizeSrcRows <= RESIZE_MAXSRC && (double)Gs.w / G.w < 3.0 && lds2 <= ORB_LDS_LIMIT - 1024;   // (very wide images: one-pass)
-    const int tPitch = twoPass ? tPitch2 : 0;
-    const size_t lds = twoPass ? lds2 : (size_t)wq * 8;
+    size_t lds;
+    (void)resize_form(G, Gs, &lds);
+    const int tPitch = G.resizeTPitch;   // orbx_configure built the row-tile records with it
+    const bool twoPass = tPitch > 0;
     hipLaunchKernelGGL(k_resize, dim3(((G.h + G.resizeRows - 1) / G.resizeRows) * nframes), dim3(256), lds, s, P, l, rowBytes, tPitch, G.resizeSrcRows);
     if (printForms) pyrForm += std::string(l > 1 ? "," : "") + (!twoPass ? "1p" : G.resizeRows == 16 ? "2p16" : "2p8");
   }
