@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 # the vocabulary's symbols (orbv_*), a list of their own: tests/test_abi.py holds ABI_SYMBOLS equal to the header's orbx_ / orbm_ names;
@@ -80,6 +80,49 @@ class VocNodesStruct(C.Structure):  # orbv_nodes_t
 
 class KfdbMembersStruct(C.Structure):  # orbd_members_t
     _fields_ = [("reloc_query", C.c_uint64), ("place_query", C.c_uint64), ("reloc_score", C.c_float), ("place_score", C.c_float)]
+
+
+class CullingStruct(C.Structure):  # orbm_culling_t
+    _fields_ = [("K", C.c_int32), ("skip", C.c_void_p), ("th_depth", C.c_void_p), ("row_start", C.c_void_p), ("row_point", C.c_void_p),
+                ("row_level", C.c_void_p), ("row_depth", C.c_void_p), ("P", C.c_int32), ("bad", C.c_void_p), ("n_obs", C.c_void_p),
+                ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_level", C.c_void_p), ("obs_w", C.c_void_p), ("mono", C.c_int32),
+                ("redundant_th", C.c_float)]
+
+
+CULL_MAX_KEYFRAMES = 1024  # ORBM_CULL_MAX_KEYFRAMES
+_CULL_TYPES = dict(skip=np.uint8, th_depth=np.float32, row_start=np.int32, row_point=np.int32, row_level=np.int32, row_depth=np.float32,
+                   bad=np.uint8, n_obs=np.int32, obs_start=np.int32, obs_kf=np.int32, obs_level=np.int32, obs_w=np.uint8)
+
+
+def culling_struct(scene):
+    """(CullingStruct, the arrays it points to) from a scene dict: the arrays of orbm_culling_t by name (K and P come from row_start and
+    obs_start; row_depth may be None when mono), `mono` and `redundant_th`."""
+    A = {k: (None if scene.get(k) is None else np.ascontiguousarray(scene[k], dtype=t)) for k, t in _CULL_TYPES.items()}
+    c = CullingStruct()
+    c.K, c.P = len(A["row_start"]) - 1, len(A["obs_start"]) - 1
+    for k in _CULL_TYPES:
+        setattr(c, k, _p(A[k]))
+    c.mono, c.redundant_th = int(scene["mono"]), float(scene["redundant_th"])
+    return c, A
+
+
+def _culling_outputs(c):
+    K, P = max(c.K, 1), max(c.P, 1)
+    return np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.uint8), np.zeros(P, np.int32), np.zeros(P, np.uint8)
+
+
+def keyframe_culling_host(scene, erasable=None):
+    """LocalMapping::KeyFrameCulling (LocalMapping.cc:1158-1310) on the CPU with the kernels' own statement (orbm_keyframe_culling_host,
+    csrc/orb_ref_culling.h).  Same arguments and results as ORBmatcher.KeyFrameCulling; not a fallback of it."""
+    L = load()
+    c, keep = culling_struct(scene)
+    era = None if erasable is None else np.ascontiguousarray(erasable, dtype=np.uint8)
+    out = _culling_outputs(c)
+    rc = L.orbm_keyframe_culling_host(C.byref(c), _p(era), *[_p(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError("orbm_keyframe_culling_host: bad argument (%s)" % L.orbm_keyframe_culling_host_error().decode())
+    _check_free(rc, "orbm_keyframe_culling_host")
+    return out[0][:c.K], out[1][:c.K], out[2][:c.K], out[3][:c.P], out[4][:c.P]
 
 
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
@@ -254,6 +297,12 @@ def load(build_if_needed=True):
     L.orbm_distinctive_descriptors.argtypes = [vp, i32, vp, vp, vp]
     L.orbm_update_map_points.argtypes = [vp, vp, vp, vp, vp, vp]
     L.orbm_map_point_normal_depth.argtypes = [i32, vp, vp, vp, f32, f32, vp, vp, vp]
+    L.orbm_keyframe_culling.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_keyframe_culling_open.argtypes = [vp, vp]
+    L.orbm_keyframe_culling_step.argtypes = [vp, i32, vp, vp, vp]
+    L.orbm_keyframe_culling_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_keyframe_culling_host_error.argtypes = []
+    L.orbm_keyframe_culling_host_error.restype = C.c_char_p
     L.orbm_knn_match2.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, f32, i32, vp]
     L.orbm_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, f32, i32, vp]
@@ -1192,6 +1241,42 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_update_map_points rc=%d" % rc)
         return best[:n], normal[:n], mn[:n], mx[:n]
+
+    def KeyFrameCulling(self, scene, erasable=None):
+        """LocalMapping::KeyFrameCulling (LocalMapping.cc:1158-1310) under the non-inertial rule, the whole loop on the device
+        (orbm_keyframe_culling).  scene: see culling_struct; erasable [K] = !mbNotErase per keyframe, None = all.  Returns (n_mps [K],
+        n_red [K], culled [K], n_obs_out [P], bad_out [P]): nMPs and nRedundantObservations at each keyframe's turn, which keyframes were
+        erased, and Observations() / isBad() of every map point after the loop."""
+        c, keep = culling_struct(scene)
+        era = None if erasable is None else np.ascontiguousarray(erasable, dtype=np.uint8)
+        out = _culling_outputs(c)
+        rc = self.L.orbm_keyframe_culling(self.m, C.byref(c), _p(era), *[_p(o) for o in out])
+        self._check(rc, "orbm_keyframe_culling")
+        if rc < 0:
+            raise OrbError("orbm_keyframe_culling rc=%d" % rc)
+        return out[0][:c.K], out[1][:c.K], out[2][:c.K], out[3][:c.P], out[4][:c.P]
+
+    def KeyFrameCullingOpen(self, scene):
+        """Opens the stepwise walk (orbm_keyframe_culling_open): uploads the scene and computes the loop-entry status of every row.  An
+        unfinished walk is discarded."""
+        c, keep = culling_struct(scene)
+        rc = self.L.orbm_keyframe_culling_open(self.m, C.byref(c))
+        self._check(rc, "orbm_keyframe_culling_open")
+        if rc < 0:
+            raise OrbError("orbm_keyframe_culling_open rc=%d" % rc)
+        self._cull_counts = (np.full(max(c.K, 1), -1, np.int32), np.full(max(c.K, 1), -1, np.int32), c.K)
+
+    def KeyFrameCullingStep(self, applied):
+        """One step of the walk (orbm_keyframe_culling_step): erases the keyframe the previous step returned if `applied`, then walks on to
+        the next unskipped keyframe that passes the test.  Returns (k, n_mps [K], n_red [K]): k = that keyframe or K at the end; the
+        counts of every keyframe walked so far, -1 where the walk has not been yet."""
+        n_mps, n_red, K = getattr(self, "_cull_counts", (np.zeros(1, np.int32), np.zeros(1, np.int32), 0))
+        k = np.full(1, -1, np.int32)
+        rc = self.L.orbm_keyframe_culling_step(self.m, int(bool(applied)), _p(k), _p(n_mps), _p(n_red))
+        self._check(rc, "orbm_keyframe_culling_step")
+        if rc < 0:
+            raise OrbError("orbm_keyframe_culling_step rc=%d" % rc)
+        return int(k[0]), n_mps[:K].copy(), n_red[:K].copy()
 
     def ComputeStereoFishEyeMatches(self, keysL, descL, monoL, keysR, descR, monoR, level_sigma2, Tlr, cam_params, cam_params2, p3d=None):
         """Frame::ComputeStereoFishEyeMatches (Frame.cc:1228-1268) of one rig frame from host arrays (orbm_stereo_fisheye_matches).

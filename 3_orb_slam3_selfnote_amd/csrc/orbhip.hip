@@ -34,6 +34,7 @@
 #include "orb_fuse_sim3_kernels.h"
 #include "orb_bow_kernels.h"
 #include "orb_mappoint_kernels.h"
+#include "orb_culling_kernels.h"
 #include "orb_voc_kernels.h"
 #include "orb_kfdb_kernels.h"
 
@@ -1293,6 +1294,10 @@ struct orbm_handle {
   DevBuf d_knn;       // the two nearest right rows of every left lapping row (orbm_stereo_fisheye_matches*)
   DevBuf d_partner;   // stereo-partner table built by k_local_map_project_rig (orbm_search_local_points_fisheye*)
   DevBuf d_tri_count, d_tri_keys;   // k_triangulation_candidates: per-item offsets and counts + total, candidate keys
+  DevBuf d_cull;      // tables and state of an open stepwise KeyFrameCulling walk (orbm_keyframe_culling_open / _step): no other entry uses it
+  CullParams cull{};  // its device addresses inside d_cull
+  bool cull_open = false, cull_any = false;   // a walk is open; one of its erases has been applied
+  int cull_next = 0, cull_pending = -1;       // the next keyframe to walk; the passing keyframe the last step returned, or -1
   std::vector<BowCandItem> bow_items;   // host side of the one-call SearchByBoW, kept between calls (capacity only grows)
   std::vector<BowCand> bow_cands;
   std::vector<float> bow_ang;
@@ -1483,7 +1488,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_knn, &m->d_partner, &m->d_tri_count, &m->d_tri_keys};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_knn, &m->d_partner, &m->d_tri_count, &m->d_tri_keys, &m->d_cull};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -4189,6 +4194,203 @@ int orbm_map_point_normal_depth(int n, const float *centre, const float *pos, co
   if (n < 0 || (n > 0 && !centre) || !pos || !ref_centre || !normal || !min_dist || !max_dist) return ORBX_E_ARG;
   if (n == 0) return 0;   // observations.empty() (MapPoint.cc:483)
   map_point_normal_depth(n, centre, pos, ref_centre, ref_scale, ref_max_scale, normal, min_dist, max_dist);
+  return 0;
+}
+
+// ---- LocalMapping::KeyFrameCulling (LocalMapping.cc:1158-1310): orb_ref_culling.h, orb_culling_kernels.h ----
+// What is refused before anything is uploaded, launched or written (include/orbhip.h); nullptr = accepted
+static const char *culling_refusal(const orbm_culling_t *c) {
+  if (!c) return "KeyFrameCulling: NULL struct";
+  if (c->K < 0 || c->P < 0) return "KeyFrameCulling: negative count";
+  if (c->K > ORBM_CULL_MAX_KEYFRAMES) return "KeyFrameCulling: K above ORBM_CULL_MAX_KEYFRAMES (1024)";
+  if (c->redundant_th != c->redundant_th) return "KeyFrameCulling: redundant_th is NaN";
+  if (c->K == 0) return nullptr;
+  if (!c->skip || !c->th_depth || !c->row_start || !c->obs_start) return "KeyFrameCulling: NULL argument";
+  if (c->P > 0 && (!c->bad || !c->n_obs)) return "KeyFrameCulling: NULL point array";
+  if (c->row_start[0] != 0 || c->obs_start[0] != 0) return "KeyFrameCulling: row_start[0] / obs_start[0] != 0";
+  for (int k = 0; k < c->K; k++) {
+    const int64_t n = (int64_t)c->row_start[k + 1] - (int64_t)c->row_start[k];
+    if (n < 0) return "KeyFrameCulling: row_start decreases";
+    if (n > ORBM_MAX_KEYPOINTS) return "KeyFrameCulling: more than ORBM_MAX_KEYPOINTS (15360) rows in one keyframe";
+  }
+  for (int p = 0; p < c->P; p++)
+    if (c->obs_start[p + 1] < c->obs_start[p]) return "KeyFrameCulling: obs_start decreases";
+  const int R = c->row_start[c->K], E = c->obs_start[c->P];
+  if (R > 0 && (!c->row_point || !c->row_level || (!c->mono && !c->row_depth))) return "KeyFrameCulling: NULL row array";
+  if (E > 0 && (!c->obs_kf || !c->obs_level || !c->obs_w)) return "KeyFrameCulling: NULL entry array";
+  for (int i = 0; i < R; i++)
+    if (c->row_point[i] < -1 || c->row_point[i] >= c->P) return "KeyFrameCulling: row_point outside [-1, P)";
+  std::vector<int32_t> seen((size_t)c->K, -1);   // seen[kf] = the last point that had an entry of keyframe kf
+  for (int p = 0; p < c->P; p++)
+    for (int e = c->obs_start[p]; e < c->obs_start[p + 1]; e++) {
+      const int kf = c->obs_kf[e];
+      if (kf < -1 || kf >= c->K) return "KeyFrameCulling: obs_kf outside [-1, K)";
+      if (c->obs_w[e] != 1 && c->obs_w[e] != 2) return "KeyFrameCulling: obs_w outside {1, 2}";
+      if (kf >= 0) {
+        if (seen[kf] == p) return "KeyFrameCulling: two entries of one point with the same obs_kf";
+        seen[kf] = p;
+      }
+    }
+  return nullptr;
+}
+
+// The tables and the loop's state as parts of one staged block.  n_obs and bad come last, so that the one-call form's outputs follow
+// them and everything that goes back is one span.
+struct CullParts {
+  PartOf<uint8_t> skip, erasable, obs_w, bad, zero, row_stat;
+  PartOf<float> th_depth, row_depth;
+  PartOf<int32_t> row_start, row_point, row_level, obs_start, obs_level, obs_kf, n_obs;
+  size_t K, NP, zero_bytes;
+};
+static CullParts culling_add(Staging &S, const orbm_culling_t *c, const uint8_t *erasable) {
+  CullParts H;
+  const size_t K = H.K = (size_t)c->K, NP = H.NP = (size_t)c->P, R = (size_t)c->row_start[K], E = (size_t)c->obs_start[NP];
+  H.skip = S.add(c->skip, K); H.erasable = S.add(erasable, K); H.th_depth = S.add(c->th_depth, K);
+  H.row_start = S.add(c->row_start, K + 1); H.row_point = S.add(c->row_point, R); H.row_level = S.add(c->row_level, R);
+  H.row_depth = S.add(c->row_depth, c->mono ? 0 : R);
+  H.obs_start = S.add(c->obs_start, NP + 1); H.obs_level = S.add(c->obs_level, E); H.obs_w = S.add(c->obs_w, E); H.obs_kf = S.add(c->obs_kf, E);
+  H.zero_bytes = stage_span(NP) + 2 * sizeof(int32_t) * K;       // touched [P], sum_mps [K], sum_red [K]: cleared on the device
+  H.zero = S.out<uint8_t>(H.zero_bytes); H.row_stat = S.out<uint8_t>(R);
+  H.n_obs = S.add(c->n_obs, NP); H.bad = S.add(c->bad, NP);
+  return H;
+}
+static CullParams culling_bind(const Staging &S, const CullParts &H, const orbm_culling_t *c) {
+  CullParams P;
+  P.K = c->K; P.mono = c->mono; P.redundant_th = c->redundant_th;
+  P.skip = S.dev(H.skip); P.erasable = S.dev(H.erasable); P.th_depth = S.dev(H.th_depth);
+  P.row_start = S.dev(H.row_start); P.row_point = S.dev(H.row_point); P.row_level = S.dev(H.row_level); P.row_depth = S.dev(H.row_depth);
+  P.obs_start = S.dev(H.obs_start); P.obs_level = S.dev(H.obs_level); P.obs_w = S.dev(H.obs_w); P.obs_kf = S.dev(H.obs_kf);
+  P.bad = S.dev(H.bad); P.n_obs = S.dev(H.n_obs);
+  P.touched = S.dev(H.zero);
+  P.sum_mps = (int32_t *)(S.dev(H.zero) + stage_span(H.NP)); P.sum_red = P.sum_mps + H.K;
+  P.row_stat = S.dev(H.row_stat);
+  return P;
+}
+// The loop-entry status of every row (k_cull_count) behind the upload
+static int culling_count(orbm_t *m, hipStream_t s, const CullParams &P, const CullParts &H, const orbm_culling_t *c) {
+  MCHECK(m, hipMemsetAsync(P.touched, 0, H.zero_bytes, s));
+  int most = 0;
+  for (int k = 0; k < c->K; k++) most = std::max(most, c->row_start[k + 1] - c->row_start[k]);
+  if (most > 0) {
+    hipLaunchKernelGGL(k_cull_count, dim3((unsigned)((most + 255) / 256), (unsigned)c->K), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+  }
+  return 0;
+}
+
+int orbm_keyframe_culling(orbm_t *m, const orbm_culling_t *c, const uint8_t *erasable, int32_t *n_mps, int32_t *n_red, uint8_t *culled,
+                          int32_t *n_obs_out, uint8_t *bad_out) {
+  if (!m) return ORBX_E_ARG;
+  if (const char *why = culling_refusal(c)) { m->err = why; return ORBX_E_ARG; }
+  if (c->K == 0) return 0;
+  if (!n_mps || !n_red || !culled) { m->err = "KeyFrameCulling: NULL output"; return ORBX_E_ARG; }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  const size_t K = (size_t)c->K, NP = (size_t)c->P;
+  const std::vector<uint8_t> all(erasable ? 0 : K, (uint8_t)1);
+  Staging S{m};   // one block up, two launches, the state and the outputs down as one span of the block, one synchronisation
+  const CullParts H = culling_add(S, c, erasable ? erasable : all.data());
+  const auto hmps = S.out<int32_t>(K), hred = S.out<int32_t>(K), hres = S.out<int32_t>(1);
+  const auto hcul = S.out<uint8_t>(K);
+  int rc = S.upload(s);
+  if (rc < 0) return rc;
+  const CullParams P = culling_bind(S, H, c);
+  if ((rc = culling_count(m, s, P, H, c)) < 0) return rc;
+  CullWalkParams W{0, -1, 0, 0, S.dev(hmps), S.dev(hred), S.dev(hcul), S.dev(hres)};
+  hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(CULL_WALK_THREADS), 0, s, P, W);
+  MCHECK(m, hipGetLastError());
+  const uint8_t *lo = NP ? (const uint8_t *)S.dev(H.n_obs) : (const uint8_t *)S.dev(hmps);
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hcul) + K) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  memcpy(n_mps, S.host(hmps), sizeof(int32_t) * K); memcpy(n_red, S.host(hred), sizeof(int32_t) * K); memcpy(culled, S.host(hcul), K);
+  if (n_obs_out && NP) memcpy(n_obs_out, S.host(H.n_obs), sizeof(int32_t) * NP);
+  if (bad_out && NP) memcpy(bad_out, S.host(H.bad), NP);
+  return 0;
+}
+
+int orbm_keyframe_culling_open(orbm_t *m, const orbm_culling_t *c) {
+  if (!m) return ORBX_E_ARG;
+  if (const char *why = culling_refusal(c)) { m->err = why; return ORBX_E_ARG; }
+  m->cull_open = false;   // an unfinished walk is discarded
+  m->cull = CullParams{};
+  m->cull.K = c->K; m->cull_next = 0; m->cull_pending = -1; m->cull_any = false;
+  if (c->K == 0) { m->cull_open = true; return 0; }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  const std::vector<uint8_t> all((size_t)c->K, (uint8_t)1);   // the stepwise form never reads erasable
+  Staging S{m};
+  const CullParts H = culling_add(S, c, all.data());
+  int rc = S.upload(s);
+  if (rc < 0) return rc;
+  CullParams P = culling_bind(S, H, c);
+  if ((rc = culling_count(m, s, P, H, c)) < 0) return rc;
+  // the block moves into the walk's own buffer: other entries reuse d_block between the steps
+  size_t bytes = 0;
+  for (int i = 0; i < S.n; i++) bytes += stage_span(S.parts[i].bytes);
+  MCHECK(m, m->d_cull.reserve(m->d_cull.bytes >= bytes ? bytes : 2 * bytes));
+  MCHECK(m, hipMemcpyAsync(m->d_cull.p, m->d_block.p, bytes, hipMemcpyDeviceToDevice, s));
+  MCHECK(m, hipStreamSynchronize(s));   // the pinned mirror is free for the next entry
+  const ptrdiff_t delta = (const uint8_t *)m->d_cull.p - (const uint8_t *)m->d_block.p;
+  auto moved = [delta](auto *&p) { if (p) p = (std::remove_reference_t<decltype(p)>)((uintptr_t)p + delta); };
+  moved(P.skip); moved(P.erasable); moved(P.th_depth); moved(P.row_start); moved(P.row_point); moved(P.row_level); moved(P.row_depth);
+  moved(P.obs_start); moved(P.obs_level); moved(P.obs_w); moved(P.obs_kf); moved(P.bad); moved(P.n_obs); moved(P.touched);
+  moved(P.sum_mps); moved(P.sum_red); moved(P.row_stat);
+  m->cull = P;
+  m->cull_open = true;
+  return 0;
+}
+
+int orbm_keyframe_culling_step(orbm_t *m, int applied, int32_t *k, int32_t *n_mps, int32_t *n_red) {
+  if (!m) return ORBX_E_ARG;
+  if (!m->cull_open) { m->err = "KeyFrameCulling: step without open"; return ORBX_E_ARG; }
+  if (!k || !n_mps || !n_red) { m->err = "KeyFrameCulling: NULL output"; return ORBX_E_ARG; }
+  const int K = m->cull.K, first = m->cull_next;
+  if (first >= K) { *k = K; return 0; }   // the walk has ended: nothing is left that an erase could change
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  Staging S{m};   // the outputs alone; the tables and the state stay in d_cull
+  const auto hmps = S.out<int32_t>((size_t)K), hred = S.out<int32_t>((size_t)K), hres = S.out<int32_t>(1);
+  const int rc = S.upload(s);
+  if (rc < 0) return rc;
+  const bool erase = applied != 0 && m->cull_pending >= 0;
+  CullWalkParams W{first, erase ? m->cull_pending : -1, m->cull_any, 1, S.dev(hmps), S.dev(hred), nullptr, S.dev(hres)};
+  m->cull_any = m->cull_any || erase;
+  hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(CULL_WALK_THREADS), 0, s, m->cull, W);
+  MCHECK(m, hipGetLastError());
+  const uint8_t *lo = (const uint8_t *)S.dev(hmps);
+  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hres) + 1) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  const int at = *S.host(hres);
+  for (int j = first; j <= std::min(at, K - 1); j++) { n_mps[j] = S.host(hmps)[j]; n_red[j] = S.host(hred)[j]; }
+  m->cull_pending = at < K ? at : -1;
+  m->cull_next = at < K ? at + 1 : K;
+  *k = at;
+  return 0;
+}
+
+static thread_local const char *g_cull_host_err = "";
+const char *orbm_keyframe_culling_host_error(void) { return g_cull_host_err; }
+
+int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable, int32_t *n_mps, int32_t *n_red, uint8_t *culled,
+                               int32_t *n_obs_out, uint8_t *bad_out) {
+  if (const char *why = culling_refusal(c)) { g_cull_host_err = why; return ORBX_E_ARG; }
+  if (c->K == 0) return 0;
+  if (!n_mps || !n_red || !culled) { g_cull_host_err = "KeyFrameCulling: NULL output"; return ORBX_E_ARG; }
+  const CullTables T{c->K, c->skip, c->th_depth, c->row_start, c->row_point, c->row_level, c->row_depth, c->obs_start, c->obs_level, c->obs_w,
+                     c->mono != 0, c->redundant_th};
+  const size_t NP = (size_t)c->P, E = (size_t)c->obs_start[NP];
+  std::vector<uint8_t> bad(c->bad, c->bad + NP);
+  std::vector<int32_t> n_obs(c->n_obs, c->n_obs + NP), obs_kf(c->obs_kf, c->obs_kf + E);
+  for (int k = 0; k < c->K; k++) {
+    n_mps[k] = n_red[k] = 0; culled[k] = 0;
+    if (c->skip[k]) continue;                                                        // :1200
+    cull_counts_host(T, k, bad.data(), n_obs.data(), obs_kf.data(), &n_mps[k], &n_red[k]);
+    if (!cull_test(n_red[k], c->redundant_th, n_mps[k]) || (erasable && !erasable[k])) continue;
+    culled[k] = 1;
+    cull_erase_host(T, k, bad.data(), n_obs.data(), obs_kf.data());                  // pKF->SetBadFlag() (:1302)
+  }
+  if (n_obs_out && NP) memcpy(n_obs_out, n_obs.data(), sizeof(int32_t) * NP);
+  if (bad_out && NP) memcpy(bad_out, bad.data(), NP);
   return 0;
 }
 

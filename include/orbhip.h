@@ -1205,6 +1205,87 @@ int orbm_update_map_points(orbm_t *m, const orbm_map_point_update_t *u,
 int orbm_map_point_normal_depth(int n, const float *centre /*[n][3]*/, const float *pos, const float *ref_centre,
                                 float ref_scale, float ref_max_scale, float *normal, float *min_dist, float *max_dist);
 
+/* void LocalMapping::KeyFrameCulling()  (LocalMapping.cc:1158-1310): the redundancy counts of every local keyframe and the cull loop,
+ * on the device.  The loop body is LocalMapping.cc:1204-1266; what a culled keyframe changes is KeyFrame::SetBadFlag's walk over its
+ * map points (KeyFrame.cc:670-677) through MapPoint::EraseObservation (MapPoint.cc:168-202) and MapPoint::SetBadFlag
+ * (MapPoint.cc:217-226).  Every compare is a function of csrc/orb_ref_culling.h, host and device; parity with the literal model of
+ * tests/keyframe_culling_model.py is exact.
+ *
+ * A ROW is one keypoint i of one local keyframe k; an ENTRY is one element of a map point's mObservations.
+ *   - Row i of keyframe k is dead when row_point[i] < 0 (no map point, :1211) or bad[p] (:1213) and, when mono == 0, when
+ *     row_depth[i] > th_depth[k] || row_depth[i] < 0 in float (:1217).  Otherwise it counts in nMPs (:1221).
+ *   - When n_obs[p] > 3 (:1222) the row is redundant when more than 3 live entries of p have obs_kf != k (:1232) and
+ *     obs_level <= row_level[i] + 1 (:1250).  The break at the fourth hit (:1253) changes no result.
+ *   - Keyframe k passes when nRedundantObservations > redundant_th * nMPs as C evaluates it (:1266): a float product with nMPs
+ *     converted to float, compared in float with the left side converted.  It is not a double product.
+ *   - Erasing keyframe c visits every row of c with row_point >= 0 in row order (KeyFrame.cc:670-677).  Where point p has a live entry
+ *     with obs_kf == c, n_obs[p] -= obs_w[entry] (MapPoint.cc:179-187) and the entry dies (:189); n_obs[p] <= 2 (:195) turns the point
+ *     bad and all its entries die (MapPoint.cc:223-225).  A second row of c with the same point (a rig's left and right index) finds no
+ *     entry and does nothing.  The entries of a point that is bad on entry are dead: a bad point's mObservations is empty.
+ *
+ * SEQUENTIAL CULLING RULE - why the loop may run on the device, and why the stepwise walk equals the sequential loop:
+ *   - the loop body for keyframe k reads, of mutable state, only isBad(), Observations() and GetObservations() of k's map points, and
+ *     k's own isBad(); it writes, through SetBadFlag of k, exactly these three of k's map points (and k's isBad()).  No other state that
+ *     the body reads is written by the loop: levels, depths, mThDepth and the keyframe list are fixed at loop entry;
+ *   - validity only shrinks: an entry never comes back to life, n_obs never rises, a bad point never recovers.  So a row's status at
+ *     keyframe k's turn is its loop-entry status unless an erase touched the row's point before k's turn, and re-evaluating the rows of
+ *     touched points from the current state gives what the reference computes at that turn;
+ *   - an erase is applied once per point although the rows are handled in parallel: the keyframe's entry of a point is claimed by one
+ *     atomic compare-and-swap, and the order of the points within one erase does not matter because an erase of c changes only
+ *     per-point state and reads no other point;
+ *   - the stepwise form stops at each passing keyframe and applies its erase, or not, at the start of the next step, before any later
+ *     keyframe is evaluated: exactly the reference's order of SetBadFlag and the next iteration.  Keyframes that do not pass change
+ *     nothing, so walking over them inside one step equals visiting them one at a time.
+ *
+ * ORBX_E_ARG with a message, nothing launched and no output written, for: a NULL handle (device forms), struct or output; a NULL array
+ * that is indexed (row_depth only when mono == 0; erasable, n_obs_out and bad_out may be NULL); K, P or a count < 0; K above
+ * ORBM_CULL_MAX_KEYFRAMES; row_start[0] / obs_start[0] not 0 or a start table that decreases; more rows in one keyframe than
+ * ORBM_MAX_KEYPOINTS; a row_point outside [-1, P); an obs_kf outside [-1, K); an obs_w outside {1, 2}; two entries of one point with
+ * the same obs_kf >= 0 (mObservations is a map); a NaN redundant_th; step without open.  K == 0 returns 0 without touching the device.
+ * There is no cap on the entries of one point: lists above 64 entries are walked by a wavefront in 64-entry tiles. */
+#define ORBM_CULL_MAX_KEYFRAMES 1024   /* the reference's loop stops after 101 (:1305) */
+typedef struct {
+  int32_t K;                  /* local keyframes in the loop's order (GetVectorCovisibleKeyFrames, :1166) */
+  const uint8_t *skip;        /* [K] mnId == GetInitKFid() || isBad()  (:1200): no counts, never culled */
+  const float   *th_depth;    /* [K] pKF->mThDepth (:1217) */
+  const int32_t *row_start;   /* [K+1] rows of keyframe k = its keypoints i (:1208), row_start[k] .. row_start[k+1]-1 */
+  const int32_t *row_point;   /* [R] index into the point table, -1 = no map point (:1211) */
+  const int32_t *row_level;   /* [R] scaleLevel of :1224-1226 */
+  const float   *row_depth;   /* [R] pKF->mvDepth[i] (:1217); may be NULL when mono != 0 */
+  int32_t P;                  /* distinct map points */
+  const uint8_t *bad;         /* [P] pMP->isBad() (:1213) */
+  const int32_t *n_obs;       /* [P] pMP->Observations() (:1222) */
+  const int32_t *obs_start;   /* [P+1] entries of point p = obs_start[p] .. obs_start[p+1]-1 (GetObservations, :1227) */
+  const int32_t *obs_kf;      /* [E] index into the K keyframes, -1 = an observer that is not in the list */
+  const int32_t *obs_level;   /* [E] scaleLeveli of :1236-1248 */
+  const uint8_t *obs_w;       /* [E] what EraseObservation subtracts for this keyframe: 1 or 2 (MapPoint.cc:179-187) */
+  int32_t mono;               /* mbMonocular (:1215) */
+  float redundant_th;         /* :1168-1174 */
+} orbm_culling_t;
+
+/* The whole loop under the non-inertial rule (:1300-1303): keyframe k is culled when it passes, !skip[k] and erasable[k] (NULL = all 1);
+ * erasable[k] stands for !mbNotErase, and where it is 0 SetBadFlag returns without erasing (KeyFrame.cc:650-655).  n_mps[k], n_red[k] =
+ * nMPs and nRedundantObservations at keyframe k's turn, culled[k] = 1 where it was erased; skipped keyframes get 0, 0, 0.
+ * n_obs_out[p], bad_out[p] (either may be NULL) = Observations() and isBad() after the loop.  One upload, k_cull_count, k_cull_walk,
+ * one download, one synchronisation.  The `count > 100` and mbAbortBA breaks (:1305) are the caller's: pass the keyframes that the
+ * loop would reach.  Returns 0. */
+int orbm_keyframe_culling(orbm_t *m, const orbm_culling_t *c, const uint8_t *erasable /*[K] or NULL*/, int32_t *n_mps /*[K]*/,
+                          int32_t *n_red /*[K]*/, uint8_t *culled /*[K]*/, int32_t *n_obs_out /*[P] or NULL*/, uint8_t *bad_out /*[P] or NULL*/);
+/* The stepwise form, for the inertial branch (:1268-1299), where the live objects decide, and for callers that cannot read mbNotErase.
+ * open uploads the tables into buffers of the handle that no other entry uses and computes the loop-entry status of every row; it
+ * discards an unfinished walk.  Every step first erases the keyframe that the previous step returned if applied != 0, then walks on
+ * to the next unskipped keyframe that passes, writes n_mps[j] / n_red[j] of every keyframe j it walked (0, 0 for a skipped one; other
+ * elements are left alone) and returns that keyframe's index in *k, or K at the end (further steps return K again).  Other orbm_*
+ * calls between steps are allowed.  One launch, one download and one synchronisation per step. */
+int orbm_keyframe_culling_open(orbm_t *m, const orbm_culling_t *c);
+int orbm_keyframe_culling_step(orbm_t *m, int applied, int32_t *k, int32_t *n_mps /*[K]*/, int32_t *n_red /*[K]*/);
+/* The one-call form on the CPU with the functions of csrc/orb_ref_culling.h, one object at a time in the loop's order: no handle, same
+ * outputs, same refusals (the message: orbm_keyframe_culling_host_error).  It exists so that the statement can be tested without a
+ * device; it is not a fallback of the device forms. */
+int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable, int32_t *n_mps, int32_t *n_red, uint8_t *culled,
+                               int32_t *n_obs_out, uint8_t *bad_out);
+const char *orbm_keyframe_culling_host_error(void);
+
 /* cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, matches, 2) as called by Frame::ComputeStereoFishEyeMatches
  * (Frame.cc:1246): idx2[2i..], dist2[2i..] = train index and distance of the nearest and second nearest train descriptor
  * of query i (-1 where nc < 2).  Equal distances are ordered by train index; the only consumer (the ratio test of
