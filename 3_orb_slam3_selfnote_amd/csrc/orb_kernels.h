@@ -297,45 +297,66 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
       const uint8_t *sp = sRows + base;
       uint8_t *tp = sT + 4 * p;
       // four rows per trip, all loads first: the compiler may not move an LDS load over an LDS store (T and the staged rows could alias
-      // for all it knows), and one load -> store chain per row is one LDS latency per row
-      for (int r = 0; r < nsrc; r += 4) {
+      // for all it knows), and one load -> store chain per row is one LDS latency per row.  The row addresses run (sp, tp advance by
+      // four rows per trip, the rows of a trip lie at loop-invariant offsets from them), and the trips are nsrc / 4 full ones with no
+      // test on the row count, then one tail trip of nsrc % 4 rows: the scalar unit is left with the trip counter.
+      // The two running addresses are LDS byte addresses in one register each, opaque to the compiler: left to itself it keeps them
+      // without the stage's constant offset in the LDS and adds that offset again for every row of every trip.
+      typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
+      typedef __attribute__((address_space(3))) uint32_t lds_u32;
+      uint32_t sa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)sp;
+      uint32_t ta = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tp;
+      asm("" : "+v"(sa), "+v"(ta));
+      auto rows4 = [&](uint32_t s, uint32_t t, int n) {   // n = 4 in the full trips (a constant there), 1 .. 3 in the tail
         uint32_t lo[4], hi[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          const uint32_t *q = reinterpret_cast<const uint32_t *>(sp + min(r + k, nsrc - 1) * smemRowBytes);       // uniform: scalar arithmetic
+          lds_cu32 *q = (lds_cu32 *)(uintptr_t)(s + (uint32_t)(min(k, n - 1) * smemRowBytes));
           lo[k] = q[0]; hi[k] = q[1];
         }
 #pragma unroll
         for (int k = 0; k < 4; k++)
-          if (r + k < nsrc) {
+          if (k < n) {
             const uint32_t vA = dot2(__builtin_amdgcn_perm(hi[k], lo[k], selA), kA), vB = dot2(__builtin_amdgcn_perm(hi[k], lo[k], selB), kB);
-            *reinterpret_cast<uint32_t *>(tp + (r + k) * tPitch) = __builtin_amdgcn_perm(vB, vA, 0x06050201u);
+            *(lds_u32 *)(uintptr_t)(t + (uint32_t)(k * tPitch)) = __builtin_amdgcn_perm(vB, vA, 0x06050201u);
           }
-      }
+      };
+      for (int i = nsrc >> 2; i > 0; i--, sa += 4 * smemRowBytes, ta += 4 * tPitch) rows4(sa, ta, 4);
+      if (nsrc & 3) rows4(sa, ta, nsrc & 3);
     }
     __syncthreads();
     // Pass 2: 32 threads per output row, eight rows at a time, each 4 consecutive output pixels per trip: everything that
     // depends on the row alone is read once, a trip is two 8-byte LDS loads, the arithmetic and one 32-bit store.  No saturate_cast
     // needed: the coefficients are non-negative and each pair sums to 2048, so v is a convex combination of four bytes, rounded
     // down-ish: always inside [0, 255].
+    // A row is G.w / 4 whole quads and, for a width that is no multiple of 4, one more of G.w % 4 bytes.  The 32 lanes of a row take
+    // 32 whole quads per trip for (G.w / 4) / 32 trips - a count that is the same for every lane, so the loop is a scalar counter
+    // and three running addresses, with no lane mask and no test on the column - and then one last trip, in which the lanes below
+    // (G.w / 4) % 32 store a whole quad and the next lane the row's tail bytes.
+    auto quad = [](const uint8_t *T0q, const uint8_t *T1q, uint32_t b0, uint32_t b1) -> uint32_t {
+      const uint2 t0 = *reinterpret_cast<const uint2 *>(T0q), t1 = *reinterpret_cast<const uint2 *>(T1q);
+      const uint32_t u0[4] = {t0.x & 0xffffu, t0.x >> 16, t0.y & 0xffffu, t0.y >> 16};
+      const uint32_t u1[4] = {t1.x & 0xffffu, t1.x >> 16, t1.y & 0xffffu, t1.y >> 16};
+      uint32_t packed = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t v = ((mul24_vv(b0, u0[j]) >> 16) + (mul24_vv(b1, u1[j]) >> 16) + 2) >> 2;
+        packed |= v << (8 * j);
+      }
+      return packed;
+    };
+    const int nfq = G.w >> 2, lx = tid & 31, remq = nfq & 31, tailBytes = G.w & 3;
     for (int ry = tid >> 5; ry < nrows; ry += 8) {
       const uint4 rec = sRowRec[ry];
       const uint32_t b0 = rec.z & 0xffffu, b1 = rec.z >> 16;
-      const uint8_t *T0 = sT + rec.x, *T1 = sT + rec.y;
-      uint8_t *dst = dstplane + rec.w;
-      for (int qx = tid & 31; qx < qw; qx += 32) {
-        const uint2 t0 = *reinterpret_cast<const uint2 *>(T0 + 8 * qx), t1 = *reinterpret_cast<const uint2 *>(T1 + 8 * qx);
-        const uint32_t u0[4] = {t0.x & 0xffffu, t0.x >> 16, t0.y & 0xffffu, t0.y >> 16};
-        const uint32_t u1[4] = {t1.x & 0xffffu, t1.x >> 16, t1.y & 0xffffu, t1.y >> 16};
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const uint32_t v = ((mul24_vv(b0, u0[j]) >> 16) + (mul24_vv(b1, u1[j]) >> 16) + 2) >> 2;
-          packed |= v << (8 * j);
-        }
-        const int dx0 = 4 * qx;
-        if (dx0 + 3 < G.w) *reinterpret_cast<uint32_t *>(dst + dx0) = packed;
-        else for (int j = 0; j < 4 && dx0 + j < G.w; j++) dst[dx0 + j] = (uint8_t)(packed >> (8 * j));
+      const uint8_t *T0 = sT + rec.x + 8 * lx, *T1 = sT + rec.y + 8 * lx;
+      uint8_t *dst = dstplane + rec.w + 4 * lx;
+      for (int n = nfq >> 5; n > 0; n--, T0 += 8 * 32, T1 += 8 * 32, dst += 4 * 32) *reinterpret_cast<uint32_t *>(dst) = quad(T0, T1, b0, b1);
+      const bool whole = lx < remq;
+      if (whole || (lx == remq && tailBytes)) {   // the arithmetic once for both kinds of lane
+        const uint32_t packed = quad(T0, T1, b0, b1);
+        if (whole) *reinterpret_cast<uint32_t *>(dst) = packed;
+        else for (int j = 0; j < tailBytes; j++) dst[j] = (uint8_t)(packed >> (8 * j));
       }
     }
     RSTAMP(2);
@@ -485,11 +506,12 @@ __device__ __forceinline__ int fast_compass_sign(const uint8_t *c, int t) {  // 
 #ifndef FAST_NT
 #define FAST_NT 256
 #endif
-#define FAST_QUEUE 128   // per-wavefront ring of pre-test survivors waiting for the 16-pixel score; a row step adds at most 64
+#define FAST_QUEUE 128   // per-wavefront ring of pre-test survivors waiting for the 16-pixel score; a row step adds at most 64 to at most 63
 #ifndef FAST_LIST
 #define FAST_LIST 384    // per-wavefront list of a detection's corners (S > t) for the NMS; a cell with more takes the full-cell walk
 #endif
 static_assert(FAST_NT == 4 * WAVE, "k_fast gives each cell of a 2 x 2 group a wavefront of its own");
+static_assert(FAST_QUEUE >= 2 * WAVE - 1 && (FAST_QUEUE & (FAST_QUEUE - 1)) == 0, "the queue is looked at after every row step; its indices wrap by a mask");
 static_assert(FAST_LIST % WAVE == 0, "pass 3 reads the corner list 64 entries at a time, all inside the list");
 static_assert((FAST_TILE_ROWS * FAST_TILE_PITCH) % 16 == 0, "the score plane is cleared in 16-byte stores");
 static_assert(FAST_TILE_ROWS * FAST_TILE_PITCH <= 65536, "queue entries are 16-bit tile offsets");
@@ -616,9 +638,11 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
     // entries: same values).  Lanes whose score is above t append their offset to the corner list: the queue is filled and
     // drained in raster order, so the list is in raster order too.  A second detection starts a new list.
     const int tt = max(t, 1);   // S > t, and S >= 2: the response S - 1 must be positive
-    int qh = 0, qn = 0, nl = 0;   // queue head and length, list length: wave-uniform
+    // queue head and tail (running counts, reduced mod FAST_QUEUE where they index) and the list's length: wave-uniform.  The head is
+    // kept as qfull = head + WAVE, the tail at which a full wavefront's worth is waiting: the look at the queue is one compare.
+    int qfull = WAVE, qt = 0, nl = 0;
     auto score = [&](bool act) {
-      const int o = act ? (int)q[(qh + lane) & (FAST_QUEUE - 1)] : base00;   // idle lanes of the tail: a pixel of the cell
+      const int o = act ? (int)q[(qfull - WAVE + lane) & (FAST_QUEUE - 1)] : base00;   // idle lanes of the tail: a pixel of the cell
       const int S = fast_score_S(&sTile[o]);
       if (act) sS[o] = (uint8_t)S;
       const bool c = act && S > tt;
@@ -627,9 +651,22 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
       if (c && li < FAST_LIST) list[li] = (uint16_t)o;
       nl += __popcll(bc);
     };
-    {
+    // Two row steps per trip, specialised on the rows per step: the second step's pixels lie at a constant distance from the
+    // first one's, so its five byte reads are the first step's addresses with another immediate and all ten are in flight
+    // before the first wait; one loop counter and one advance of off / yr serve both steps.  A step past the cell's last row (an
+    // odd number of steps) is masked like any row outside the cell: yr + RPI is not negative there.  The queue is still looked at
+    // after each step (one compare and a branch that is rarely taken): looked at once per pair it has to hold 63 + 128 entries, and
+    // the 1 KB of LDS that costs per workgroup lost more beside the other pipelines than the two instructions cost.
+    auto drain = [&]() {
+      wave_lds_order();
+      score(true);
+      qfull += WAVE;
+      wave_lds_order();   // these queue entries are free again
+    };
+    auto pretest = [&](auto rpiC) {
+      constexpr int RPI = decltype(rpiC)::value, STEP = RPI * FAST_TILE_PITCH;
       int off = off0, yr = yr0;
-      for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi) {
+      for (int y0 = 0; y0 < ch; y0 += 2 * RPI, off += 2 * STEP, yr += 2 * RPI) {
         // lanes outside the cell read LDS bytes that mean nothing (or zero past the allocation) and are masked out by yr
 #ifdef FAST_PAD   // diagnostic builds only (tools/fast_sensitivity.sh): 16 extra instructions of one class per pass-1 trip, results unused
         {
@@ -647,21 +684,21 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
           asm volatile("" ::"v"(pad0), "v"(pad1));
         }
 #endif
-        const bool pass = (fast_compass_sign(&sTile[off], t) & yr) < 0;
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(pass);
-        if (pass) q[(qh + qn + lane_rank(b)) & (FAST_QUEUE - 1)] = (uint16_t)off;
-        qn += __popcll(b);
-        if (qn >= WAVE) {
-          wave_lds_order();
-          score(true);
-          qh = (qh + WAVE) & (FAST_QUEUE - 1);
-          qn -= WAVE;
-          wave_lds_order();   // these queue entries are free again
-        }
+        const uint8_t *c = &sTile[off];
+        const bool passA = (fast_compass_sign(c, t) & yr) < 0, passB = (fast_compass_sign(c + STEP, t) & (yr + RPI)) < 0;
+        const unsigned long long bA = __builtin_amdgcn_ballot_w64(passA), bB = __builtin_amdgcn_ballot_w64(passB);
+        if (passA) q[(qt + lane_rank(bA)) & (FAST_QUEUE - 1)] = (uint16_t)off;
+        qt += __popcll(bA);
+        if (__builtin_expect(qt >= qfull, 0)) drain();
+        if (passB) q[(qt + lane_rank(bB)) & (FAST_QUEUE - 1)] = (uint16_t)(off + STEP);
+        qt += __popcll(bB);
+        if (__builtin_expect(qt >= qfull, 0)) drain();
       }
-      wave_lds_order();
-      if (qn > 0) score(lane < qn);
-    }
+    };
+    if (xsh == 5) pretest(std::integral_constant<int, 2>());
+    else pretest(std::integral_constant<int, 1>());
+    wave_lds_order();
+    if (qt > qfull - WAVE) score(lane < qt - (qfull - WAVE));
     wave_lds_order();   // the plane and the list are complete
     FSTAMP(1);
     // ---- pass 3: NMS + emit.  cv::FAST emits rows ascending, x ascending = the order of the corner list, so a kept corner's
@@ -690,17 +727,15 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
       }
     } else {
       // more corners than the list holds (dense texture or noise): the cell's plane rows in raster order; only lanes with
-      // S > t look at their neighbours
+      // S > t look at their neighbours.  Two row steps per trip, as in the pre-test: both plane reads first, one counter and one
+      // advance for the pair; a step past the last row is masked by yr.
       int off = off0, yr = yr0;
       uint32_t yx = yx0;
-      for (int y0 = 0; y0 < ch; y0 += rpi, off += rpi * FAST_TILE_PITCH, yr += rpi, yx += (uint32_t)rpi << 12) {
-        const int S = sS[off];
-        const bool cand = ((tt - S) & yr) < 0;
-        if (__builtin_amdgcn_ballot_w64(cand) == 0ull) continue;
+      const int stepB = rpi * FAST_TILE_PITCH;
+      auto walk = [&](bool cand, int S, int o, int y, uint32_t yxv) {
         bool keep = false;
         if (cand) {
-          const int y = y0 + sub;
-          const uint8_t *s = &sS[off];
+          const uint8_t *s = &sS[o];
           const bool l = px > 0, r = px < cw - 1, u = y > 0, d = y < ch - 1;   // neighbours outside the cell count as 0
           const int mu = u ? max(max(l ? (int)s[-FAST_TILE_PITCH - 1] : 0, (int)s[-FAST_TILE_PITCH]), r ? (int)s[-FAST_TILE_PITCH + 1] : 0) : 0;
           const int md = d ? max(max(l ? (int)s[FAST_TILE_PITCH - 1] : 0, (int)s[FAST_TILE_PITCH]), r ? (int)s[FAST_TILE_PITCH + 1] : 0) : 0;
@@ -709,8 +744,15 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
         }
         const unsigned long long bK = __builtin_amdgcn_ballot_w64(keep);
         const uint32_t rank = (uint32_t)nkept + (uint32_t)lane_rank(bK);
-        if (keep && rank < cellCap) slots[rank] = ((uint32_t)(S - 1) << 24) | yx;
+        if (keep && rank < cellCap) slots[rank] = ((uint32_t)(S - 1) << 24) | yxv;
         nkept += __popcll(bK);
+      };
+      for (int y0 = 0; y0 < ch; y0 += 2 * rpi, off += 2 * stepB, yr += 2 * rpi, yx += (uint32_t)rpi << 13) {
+        const int SA = sS[off], SB = sS[off + stepB];
+        const bool candA = ((tt - SA) & yr) < 0, candB = ((tt - SB) & (yr + rpi)) < 0;
+        const unsigned long long bA = __builtin_amdgcn_ballot_w64(candA), bB = __builtin_amdgcn_ballot_w64(candB);
+        if (bA != 0ull) walk(candA, SA, off, y0 + sub, yx);
+        if (bB != 0ull) walk(candB, SB, off + stepB, y0 + rpi + sub, yx + ((uint32_t)rpi << 12));
       }
     }
     FSTAMP(2);
