@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_two_view_reconstruct", "orbm_two_view_reconstruct_host", "orbm_two_view_host_error", "orbm_two_view_models", "orbm_two_view_models_host", "orbm_two_view_check_rt", "orbm_two_view_check_rt_host", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 # the vocabulary's symbols (orbv_*), a list of their own: tests/test_abi.py holds ABI_SYMBOLS equal to the header's orbx_ / orbm_ names;
@@ -123,6 +123,125 @@ def keyframe_culling_host(scene, erasable=None):
         raise ValueError("orbm_keyframe_culling_host: bad argument (%s)" % L.orbm_keyframe_culling_host_error().decode())
     _check_free(rc, "orbm_keyframe_culling_host")
     return out[0][:c.K], out[1][:c.K], out[2][:c.K], out[3][:c.P], out[4][:c.P]
+
+
+class TwoViewDetailsStruct(C.Structure):  # orbm_two_view_details_t
+    _fields_ = [(k, C.c_void_p) for k in ("SH", "SF", "best_it", "H21", "F21", "inliersH", "inliersF", "score", "used_H", "nhyp", "R", "t",
+                                          "nGood", "parallax", "chosen", "status")]
+
+
+TV_STATUS = dict(NOT_INLIER=0, GOOD=1, LOW_PARALLAX=2, NONFINITE=3, BEHIND1=4, BEHIND2=5, REPROJ1=6, REPROJ2=7)  # ORBM_TV_*
+
+
+class TwoViewResult:
+    """What TwoViewReconstruction::Reconstruct returns and leaves behind: ok (the bool), R21 [3,3], t21 [3], vP3D [n1,3], vbTriangulated
+    [n1] (the four are None unless ok), and `details`: every array of orbm_two_view_details_t by name (SH, SF, best_it, H21, F21,
+    inliersH, inliersF, score, used_H, nhyp, R, t, nGood, parallax, chosen, status)."""
+
+    def __init__(self, ok, R21, t21, vP3D, vbTriangulated, details):
+        self.ok, self.R21, self.t21, self.vP3D, self.vbTriangulated, self.details = ok, R21, t21, vP3D, vbTriangulated, details
+
+    def __bool__(self):
+        return self.ok
+
+
+def _two_view_inputs(keys1, keys2, matches12):
+    keys1, keys2 = np.ascontiguousarray(keys1, dtype=KP_DTYPE), np.ascontiguousarray(keys2, dtype=KP_DTYPE)
+    matches12 = np.ascontiguousarray(matches12, dtype=np.int32)
+    if len(matches12) != len(keys1):
+        raise ValueError("matches12 has one entry per keypoint of the first frame")
+    return keys1, keys2, matches12, int((matches12 >= 0).sum())
+
+
+def _two_view_reconstruct(call, what, error, keys1, keys2, matches12, K, sigma, iterations, sets):
+    keys1, keys2, matches12, N = _two_view_inputs(keys1, keys2, matches12)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    iterations = int(iterations)
+    sets = np.ascontiguousarray(sets, dtype=np.int32)
+    if sets.size != 8 * max(iterations, 0):
+        raise ValueError("sets is [iterations][8]")
+    n1, I = len(keys1), max(iterations, 1)
+    R21, t21, p3d, tri = np.zeros((3, 3), np.float32), np.zeros(3, np.float32), np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8)
+    d = dict(SH=np.zeros(1, np.float32), SF=np.zeros(1, np.float32), best_it=np.full(2, -1, np.int32), H21=np.zeros((3, 3), np.float32),
+             F21=np.zeros((3, 3), np.float32), inliersH=np.zeros(max(N, 1), np.uint8), inliersF=np.zeros(max(N, 1), np.uint8),
+             score=np.zeros((2, I), np.float32), used_H=np.full(1, -1, np.int32), nhyp=np.zeros(1, np.int32), R=np.zeros((8, 3, 3), np.float32),
+             t=np.zeros((8, 3), np.float32), nGood=np.zeros(8, np.int32), parallax=np.zeros(8, np.float32), chosen=np.full(1, -1, np.int32),
+             status=np.zeros((8, max(N, 1)), np.uint8))
+    ds = TwoViewDetailsStruct()
+    for k, a in d.items():
+        setattr(ds, k, _p(a))
+    rc = call(_p(keys1), n1, _p(keys2), len(keys2), _p(matches12), _p(K), C.c_float(sigma), iterations, _p(sets), _p(R21), _p(t21), _p(p3d),
+              _p(tri), C.byref(ds))
+    if rc == E_ARG:
+        raise ValueError("%s: bad argument (%s)" % (what, error()))
+    if rc < 0:
+        raise OrbError("%s rc=%d (%s)" % (what, rc, error()))
+    d["inliersH"], d["inliersF"], d["status"] = d["inliersH"][:N], d["inliersF"][:N], d["status"][:, :N]
+    ok = rc == 1
+    return TwoViewResult(ok, R21 if ok else None, t21 if ok else None, p3d[:n1] if ok else None, tri[:n1].astype(bool) if ok else None, d)
+
+
+def _two_view_models(call, what, error, keys1, keys2, matches12, sigma, iterations, sets):
+    keys1, keys2, matches12, N = _two_view_inputs(keys1, keys2, matches12)
+    iterations = int(iterations)
+    sets = np.ascontiguousarray(sets, dtype=np.int32)
+    if sets.size != 8 * max(iterations, 0):
+        raise ValueError("sets is [iterations][8]")
+    I = max(iterations, 1)
+    H21, H12, F21 = (np.zeros((I, 3, 3), np.float32) for _ in range(3))
+    score, best, masks = np.zeros((2, I), np.float32), np.full(2, -1, np.int32), np.zeros((2, max(N, 1)), np.uint8)
+    rc = call(_p(keys1), len(keys1), _p(keys2), len(keys2), _p(matches12), C.c_float(sigma), iterations, _p(sets), _p(H21), _p(H12), _p(F21),
+              _p(score), _p(best), _p(masks))
+    if rc == E_ARG:
+        raise ValueError("%s: bad argument (%s)" % (what, error()))
+    if rc < 0:
+        raise OrbError("%s rc=%d (%s)" % (what, rc, error()))
+    return dict(H21=H21, H12=H12, F21=F21, score=score, best_it=best, masks=masks.reshape(-1)[:2 * N].reshape(2, N))
+
+
+def _two_view_check_rt(call, what, error, keys1, keys2, matches12, inliers, K, sigma, R, t):
+    keys1, keys2, matches12, N = _two_view_inputs(keys1, keys2, matches12)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    R, t = np.ascontiguousarray(R, dtype=np.float32).reshape(-1, 9), np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 3)
+    inliers = np.ascontiguousarray(inliers, dtype=np.uint8)
+    if len(R) != len(t) or len(inliers) != N:
+        raise ValueError("R [nhyp][9], t [nhyp][3], inliers [N]")
+    nhyp, n1 = len(R), len(keys1)
+    H = max(nhyp, 1)
+    p3d, good, status = np.zeros((H, max(n1, 1), 3), np.float32), np.zeros((H, max(n1, 1)), np.uint8), np.zeros((H, max(N, 1)), np.uint8)
+    nGood, cos_rank, parallax = np.zeros(H, np.int32), np.zeros(H, np.float32), np.zeros(H, np.float32)
+    rc = call(_p(keys1), n1, _p(keys2), len(keys2), _p(matches12), _p(inliers), _p(K), C.c_float(sigma), nhyp, _p(R), _p(t), _p(p3d), _p(good),
+              _p(status), _p(nGood), _p(cos_rank), _p(parallax))
+    if rc == E_ARG:
+        raise ValueError("%s: bad argument (%s)" % (what, error()))
+    if rc < 0:
+        raise OrbError("%s rc=%d (%s)" % (what, rc, error()))
+    return dict(vP3D=p3d[:nhyp, :n1], vbGood=good[:nhyp, :n1], status=status[:nhyp, :N], nGood=nGood[:nhyp], cos_rank=cos_rank[:nhyp],
+                parallax=parallax[:nhyp])
+
+
+def _two_view_host_error():
+    return load().orbm_two_view_host_error().decode()
+
+
+def two_view_reconstruct_host(keys1, keys2, matches12, K, sigma, iterations, sets):
+    """TwoViewReconstruction::Reconstruct (TwoViewReconstruction.cc:39-127) on the CPU with the kernels' own statement
+    (orbm_two_view_reconstruct_host, csrc/orb_ref_twoview.h).  Same arguments and result as ORBmatcher.TwoViewReconstruct; for tests
+    without a GPU, not a fallback of it."""
+    return _two_view_reconstruct(load().orbm_two_view_reconstruct_host, "orbm_two_view_reconstruct_host", _two_view_host_error, keys1, keys2,
+                                 matches12, K, sigma, iterations, sets)
+
+
+def two_view_models_host(keys1, keys2, matches12, sigma, iterations, sets):
+    """orbm_two_view_models_host: every iteration's H21, H12, F21 and scores, the winners and their inlier vectors, on the CPU."""
+    return _two_view_models(load().orbm_two_view_models_host, "orbm_two_view_models_host", _two_view_host_error, keys1, keys2, matches12, sigma,
+                            iterations, sets)
+
+
+def two_view_check_rt_host(keys1, keys2, matches12, inliers, K, sigma, R, t):
+    """orbm_two_view_check_rt_host: CheckRT (TwoViewReconstruction.cc:802-911) for the caller's hypotheses, on the CPU."""
+    return _two_view_check_rt(load().orbm_two_view_check_rt_host, "orbm_two_view_check_rt_host", _two_view_host_error, keys1, keys2, matches12,
+                              inliers, K, sigma, R, t)
 
 
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
@@ -303,6 +422,15 @@ def load(build_if_needed=True):
     L.orbm_keyframe_culling_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.orbm_keyframe_culling_host_error.argtypes = []
     L.orbm_keyframe_culling_host_error.restype = C.c_char_p
+    tv = [vp, i32, vp, i32, vp]   # keys1, n1, keys2, n2, matches12
+    L.orbm_two_view_reconstruct.argtypes = [vp] + tv + [vp, f32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbm_two_view_reconstruct_host.argtypes = tv + [vp, f32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbm_two_view_host_error.argtypes = []
+    L.orbm_two_view_host_error.restype = C.c_char_p
+    L.orbm_two_view_models.argtypes = [vp] + tv + [f32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_two_view_models_host.argtypes = tv + [f32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_two_view_check_rt.argtypes = [vp] + tv + [vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_two_view_check_rt_host.argtypes = tv + [vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_knn_match2.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, f32, i32, vp]
     L.orbm_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, f32, i32, vp]
@@ -1255,6 +1383,32 @@ class ORBmatcher:
         if rc < 0:
             raise OrbError("orbm_keyframe_culling rc=%d" % rc)
         return out[0][:c.K], out[1][:c.K], out[2][:c.K], out[3][:c.P], out[4][:c.P]
+
+    def _tv_call(self, fn):
+        return lambda *a: fn(self.m, *a)
+
+    def _tv_error(self):
+        return self.L.orbm_last_error(self.m).decode()
+
+    def TwoViewReconstruct(self, keys1, keys2, matches12, K, sigma=1.0, iterations=200, sets=None):
+        """bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated)
+        (TwoViewReconstruction.cc:39-127) on the device (orbm_two_view_reconstruct).  keys1 / keys2: KP_DTYPE arrays (mvKeysUn of the two
+        frames), matches12 [n1] as SearchForInitialization returns it, K the 3x3 calibration, sets [iterations][8] = mvSets, drawn by the
+        caller as the reference draws them (DUtils::Random over rand()).  Returns a TwoViewResult."""
+        if sets is None:
+            raise ValueError("sets [iterations][8] come from the caller (the reference draws them from libc rand())")
+        return _two_view_reconstruct(self._tv_call(self.L.orbm_two_view_reconstruct), "orbm_two_view_reconstruct", self._tv_error, keys1, keys2,
+                                     matches12, K, sigma, iterations, sets)
+
+    def TwoViewModels(self, keys1, keys2, matches12, sigma, iterations, sets):
+        """The first device stage alone (orbm_two_view_models): H21, H12, F21 and scores of every iteration, best_it, masks."""
+        return _two_view_models(self._tv_call(self.L.orbm_two_view_models), "orbm_two_view_models", self._tv_error, keys1, keys2, matches12,
+                                sigma, iterations, sets)
+
+    def TwoViewCheckRT(self, keys1, keys2, matches12, inliers, K, sigma, R, t):
+        """The second device stage alone (orbm_two_view_check_rt): CheckRT for the caller's hypotheses R [nhyp,3,3], t [nhyp,3]."""
+        return _two_view_check_rt(self._tv_call(self.L.orbm_two_view_check_rt), "orbm_two_view_check_rt", self._tv_error, keys1, keys2,
+                                  matches12, inliers, K, sigma, R, t)
 
     def KeyFrameCullingOpen(self, scene):
         """Opens the stepwise walk (orbm_keyframe_culling_open): uploads the scene and computes the loop-entry status of every row.  An

@@ -35,6 +35,7 @@
 #include "orb_bow_kernels.h"
 #include "orb_mappoint_kernels.h"
 #include "orb_culling_kernels.h"
+#include "orb_twoview_kernels.h"
 #include "orb_voc_kernels.h"
 #include "orb_kfdb_kernels.h"
 
@@ -4391,6 +4392,425 @@ int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable,
   }
   if (n_obs_out && NP) memcpy(n_obs_out, n_obs.data(), sizeof(int32_t) * NP);
   if (bad_out && NP) memcpy(bad_out, bad.data(), NP);
+  return 0;
+}
+
+// ---- TwoViewReconstruction::Reconstruct (TwoViewReconstruction.cc:39-127): orb_ref_twoview.h, orb_twoview_kernels.h ----
+// mvMatches12 as the reference fills it (:53-62), the four coordinates of every match, and both frames normalised (:137-139, :188-190)
+struct TvProblem {
+  const orbx_keypoint_t *keys1, *keys2;
+  int n1, n2, N;
+  std::vector<int32_t> first, second;
+  std::vector<float> mx;   // [N][4]: kp1.pt, kp2.pt
+  std::vector<float> pn1, pn2;
+  float T1[9], T2[9], T2inv[9], T2t[9];
+};
+// What is refused before anything is uploaded, launched or written (include/orbhip.h); nullptr = accepted
+static const char *two_view_problem(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                    int min_matches, TvProblem &Q) {
+  if (!keys1 || !keys2 || !matches12) return "TwoViewReconstruction: NULL argument";
+  if (n1 < 0 || n2 < 0) return "TwoViewReconstruction: negative count";
+  Q.keys1 = keys1; Q.keys2 = keys2; Q.n1 = n1; Q.n2 = n2;
+  for (int i = 0; i < n1; i++) {
+    if (matches12[i] < 0) continue;
+    if (matches12[i] >= n2) return "TwoViewReconstruction: match index outside [0, n2)";
+    Q.first.push_back(i); Q.second.push_back(matches12[i]);
+    const orbx_keypoint_t &a = keys1[i], &b = keys2[matches12[i]];
+    Q.mx.insert(Q.mx.end(), {a.x, a.y, b.x, b.y});
+  }
+  Q.N = (int)Q.first.size();
+  if (Q.N < min_matches) return min_matches == 8 ? "TwoViewReconstruction: fewer than 8 matches" : "TwoViewReconstruction: no match";
+  return nullptr;
+}
+static const char *two_view_sets(const TvProblem &Q, int iterations, const int32_t *sets) {
+  if (iterations < 1) return "TwoViewReconstruction: iterations < 1";
+  if (!sets) return "TwoViewReconstruction: NULL argument";
+  for (size_t k = 0; k < 8 * (size_t)iterations; k++)
+    if (sets[k] < 0 || sets[k] >= Q.N) return "TwoViewReconstruction: set index outside [0, N)";
+  return nullptr;
+}
+static void two_view_normalize(TvProblem &Q) {
+  Q.pn1.resize(2 * (size_t)Q.n1); Q.pn2.resize(2 * (size_t)Q.n2);
+  tv_normalize(Q.keys1, Q.n1, Q.pn1.data(), Q.T1);
+  tv_normalize(Q.keys2, Q.n2, Q.pn2.data(), Q.T2);
+  tv_inv33(Q.T2, Q.T2inv);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) Q.T2t[3 * i + j] = Q.T2[3 * j + i];
+}
+
+// The outputs of the two stages, on the host
+struct TvModels {
+  std::vector<float> H21, H12, F21, score;   // [iterations][9] x 3, [2][iterations]
+  int32_t best[2];
+  float top[2], M[18];                       // SH, SF; H21, F21 of the winners
+  std::vector<uint8_t> mask;                 // [2][N]
+};
+struct TvChecked {
+  std::vector<float> p3d;                    // [nhyp][n1][3]
+  std::vector<uint8_t> good, status;         // [nhyp][n1], [nhyp][N]
+  int32_t nGood[8];
+  float cos_rank[8], parallax[8];
+};
+static void two_view_parallax(int nhyp, TvChecked &C) {
+  for (int h = 0; h < nhyp; h++) C.parallax[h] = C.nGood[h] > 0 ? tv_parallax_degrees(acosf(C.cos_rank[h])) : 0.f;   // :900-908
+}
+
+static void two_view_models_cpu(const TvProblem &Q, float sigma, int iterations, const int32_t *sets, TvModels &M) {
+  const size_t I = (size_t)iterations, N = (size_t)Q.N;
+  M.H21.assign(9 * I, 0.f); M.H12.assign(9 * I, 0.f); M.F21.assign(9 * I, 0.f); M.score.assign(2 * I, 0.f);
+  M.mask.assign(2 * N, 0);
+  float ws[TV_WS_FLOATS];
+  double W[TV_WS_DOUBLES];
+  const float inv = tv_inv_sigma_square(sigma);
+  for (int model = 0; model < 2; model++) {
+    M.best[model] = -1; M.top[model] = 0.f;
+    for (int k = 0; k < 9; k++) M.M[9 * model + k] = 0.f;
+    std::vector<uint8_t> cur(N);
+    for (size_t it = 0; it < I; it++) {
+      float q[32];
+      for (int j = 0; j < 8; j++) {
+        const int idx = sets[8 * it + j], i1 = Q.first[idx], i2 = Q.second[idx];
+        q[4 * j] = Q.pn1[2 * i1]; q[4 * j + 1] = Q.pn1[2 * i1 + 1]; q[4 * j + 2] = Q.pn2[2 * i2]; q[4 * j + 3] = Q.pn2[2 * i2 + 1];
+      }
+      float *M21 = (model ? M.F21.data() : M.H21.data()) + 9 * it, *M12 = M.H12.data() + 9 * it;
+      if (model == 0) tv_homography(q, Q.T1, Q.T2inv, ws, W, M21, M12, TvSolo());
+      else tv_fundamental(q, Q.T1, Q.T2t, ws, W, M21, TvSolo());
+      float score = 0;
+      for (size_t i = 0; i < N; i++) {
+        const float *m = &Q.mx[4 * i];
+        const TvTerms r = tv_check_model(model, M21, M12, m[0], m[1], m[2], m[3], inv);
+        if (r.in1) score += r.t1;
+        if (r.in2) score += r.t2;
+        cur[i] = r.in1 && r.in2;
+      }
+      M.score[model * I + it] = score;
+      if (score > M.top[model]) {
+        M.top[model] = score; M.best[model] = (int32_t)it;
+        memcpy(&M.M[9 * model], M21, 9 * sizeof(float));
+        memcpy(&M.mask[model * N], cur.data(), N);
+      }
+    }
+  }
+}
+
+static void two_view_cameras(const float *K, float sigma, int nhyp, const float *T, TvCamera *cams) {
+  for (int h = 0; h < nhyp; h++) tv_camera(K, T + 12 * h, sigma, cams[h]);
+}
+static void two_view_check_cpu(const TvProblem &Q, const uint8_t *mask, const float *K, float sigma, int nhyp, const float *T, TvChecked &C) {
+  const size_t N = (size_t)Q.N, n1 = (size_t)Q.n1;
+  C.p3d.assign(3 * n1 * nhyp, 0.f); C.good.assign(n1 * nhyp, 0); C.status.assign(N * nhyp, 0);
+  TvCamera cams[8];
+  two_view_cameras(K, sigma, nhyp, T, cams);
+  for (int h = 0; h < nhyp; h++) {
+    std::vector<float> cosv;
+    for (size_t i = 0; i < N; i++) {
+      if (!mask[i]) { C.status[h * N + i] = TV_NOT_INLIER; continue; }
+      const float *m = &Q.mx[4 * i];
+      float p[3], cp = 0.f;
+      const int st = tv_check_rt(cams[h], m[0], m[1], m[2], m[3], p, &cp);
+      C.status[h * N + i] = (uint8_t)st;
+      if (st != TV_GOOD && st != TV_LOW_PARALLAX) continue;
+      const size_t k = h * n1 + (size_t)Q.first[i];
+      C.p3d[3 * k] = p[0]; C.p3d[3 * k + 1] = p[1]; C.p3d[3 * k + 2] = p[2];
+      if (st == TV_GOOD) C.good[k] = 1;
+      cosv.push_back(cp);
+    }
+    C.nGood[h] = (int32_t)cosv.size();
+    C.cos_rank[h] = 0.f;
+    if (!cosv.empty()) {
+      std::sort(cosv.begin(), cosv.end());
+      C.cos_rank[h] = cosv[std::min<size_t>(50, cosv.size() - 1)];
+    }
+  }
+  two_view_parallax(nhyp, C);
+}
+
+// The device side: one staged block for both stages.  Inputs first, then the models' outputs (one span down), then CheckRT's.
+struct TvDevice {
+  orbm_t *m;
+  Staging S;
+  PartOf<float> pn1, pn2, mx, H21, H12, F21, score, top, M, cos_list, p3d, cos_rank;
+  PartOf<int32_t> first, second, sets, best, nGood;
+  PartOf<uint8_t> mask_in, mask, good, status;
+  PartOf<TvCamera> cams;
+  size_t I, N, n1;
+  int max_hyp;
+  // iterations == 0: no model stage; max_hyp == 0: no CheckRT stage; inliers: the caller's mask for CheckRT alone
+  int upload(const TvProblem &Q, int iterations, const int32_t *set_idx, int hyp, const uint8_t *inliers) {
+    I = (size_t)iterations; N = (size_t)Q.N; n1 = (size_t)Q.n1; max_hyp = hyp;
+    const size_t H = (size_t)hyp;
+    mx = S.add(Q.mx.data(), 4 * N); first = S.add(Q.first.data(), N);
+    pn1 = S.add(Q.pn1.data(), I ? 2 * n1 : 0); pn2 = S.add(Q.pn2.data(), I ? 2 * (size_t)Q.n2 : 0);
+    second = S.add(Q.second.data(), I ? N : 0); sets = S.add(set_idx, 8 * I);
+    mask_in = S.add(inliers, inliers ? N : 0);
+    H21 = S.out<float>(9 * I); H12 = S.out<float>(9 * I); F21 = S.out<float>(9 * I); score = S.out<float>(2 * I);
+    best = S.out<int32_t>(I ? 2 : 0); top = S.out<float>(I ? 2 : 0); M = S.out<float>(I ? 18 : 0); mask = S.out<uint8_t>(I ? 2 * N : 0);
+    cams = S.out<TvCamera>(H); cos_list = S.out<float>(H * N);
+    p3d = S.out<float>(3 * H * n1); good = S.out<uint8_t>(H * n1); nGood = S.out<int32_t>(H);
+    status = S.out<uint8_t>(H * N); cos_rank = S.out<float>(H);
+    return S.upload(m->stream);
+  }
+  // k_tv_hypotheses, k_tv_score, k_tv_winner, everything down, one synchronisation
+  int models(const TvProblem &Q, float sigma, TvModels &R) {
+    hipStream_t s = m->stream;
+    TvModelParams P;
+    memcpy(P.T1, Q.T1, sizeof(P.T1)); memcpy(P.T2inv, Q.T2inv, sizeof(P.T2inv)); memcpy(P.T2t, Q.T2t, sizeof(P.T2t));
+    P.pn1 = S.dev(pn1); P.pn2 = S.dev(pn2); P.first = S.dev(first); P.second = S.dev(second); P.sets = S.dev(sets);
+    P.mx = (const float4 *)S.dev(mx);
+    P.iterations = (int)I; P.N = (int)N; P.invSigmaSquare = tv_inv_sigma_square(sigma);
+    P.H21 = S.dev(H21); P.H12 = S.dev(H12); P.F21 = S.dev(F21); P.score = S.dev(score);
+    P.best = S.dev(best); P.best_score = S.dev(top); P.best_M = S.dev(M); P.mask = S.dev(mask);
+    hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)((2 * I + 3) / 4)), dim3(64), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_tv_score, dim3((unsigned)I, 2), dim3(64), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_tv_winner, dim3(2), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    const uint8_t *lo = (const uint8_t *)S.dev(H21);
+    MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)(S.dev(mask) + 2 * N - lo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    R.H21.assign(S.host(H21), S.host(H21) + 9 * I); R.H12.assign(S.host(H12), S.host(H12) + 9 * I);
+    R.F21.assign(S.host(F21), S.host(F21) + 9 * I); R.score.assign(S.host(score), S.host(score) + 2 * I);
+    memcpy(R.best, S.host(best), sizeof(R.best)); memcpy(R.top, S.host(top), sizeof(R.top)); memcpy(R.M, S.host(M), sizeof(R.M));
+    R.mask.assign(S.host(mask), S.host(mask) + 2 * N);
+    return 0;
+  }
+  // The hypotheses' cameras up, k_tv_check_rt, k_tv_cos_rank, the results down, one synchronisation.  d_mask: the inlier vector on the device
+  int check(const float *K, float sigma, int nhyp, const float *T, const uint8_t *d_mask, TvChecked &C) {
+    hipStream_t s = m->stream;
+    const size_t H = (size_t)nhyp;
+    two_view_cameras(K, sigma, nhyp, T, S.host(cams));
+    MCHECK(m, hipMemcpyAsync(S.dev(cams), S.host(cams), sizeof(TvCamera) * H, hipMemcpyHostToDevice, s));
+    uint8_t *zlo = (uint8_t *)S.dev(p3d);
+    MCHECK(m, hipMemsetAsync(zlo, 0, (size_t)((uint8_t *)(S.dev(nGood) + max_hyp) - zlo), s));   // vP3D, vbGood, nGood
+    TvCheckParams P;
+    P.cams = S.dev(cams); P.mx = (const float4 *)S.dev(mx); P.first = S.dev(first); P.mask = d_mask;
+    P.nhyp = nhyp; P.N = (int)N; P.n1 = (int)n1;
+    P.p3d = S.dev(p3d); P.good = S.dev(good); P.status = S.dev(status); P.nGood = S.dev(nGood);
+    P.cos_list = S.dev(cos_list); P.cos_rank = S.dev(cos_rank);
+    hipLaunchKernelGGL(k_tv_check_rt, dim3((unsigned)((N + 255) / 256), (unsigned)nhyp), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    hipLaunchKernelGGL(k_tv_cos_rank, dim3((unsigned)((N + 255) / 256), (unsigned)nhyp), dim3(256), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    MCHECK(m, hipMemcpyAsync(mirror_of(m, zlo), zlo, (size_t)((uint8_t *)(S.dev(cos_rank) + max_hyp) - zlo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    C.p3d.assign(S.host(p3d), S.host(p3d) + 3 * H * n1); C.good.assign(S.host(good), S.host(good) + H * n1);
+    C.status.assign(S.host(status), S.host(status) + H * N);
+    memcpy(C.nGood, S.host(nGood), sizeof(int32_t) * H); memcpy(C.cos_rank, S.host(cos_rank), sizeof(float) * H);
+    two_view_parallax(nhyp, C);
+    return 0;
+  }
+};
+
+// Reconstruct behind the argument checks, for either side: models(M) and check(mask_index, nhyp, T, C) are the two stages
+extern "C++" {
+template <class Models, class Check>
+static int two_view_reconstruct(const TvProblem &Q, const float *K, float sigma, int iterations, float *R21, float *t21, float *vP3D,
+                                uint8_t *vbTriangulated, const orbm_two_view_details_t *d, Models models, Check check) {
+  const size_t N = (size_t)Q.N, n1 = (size_t)Q.n1, I = (size_t)iterations;
+  static const orbm_two_view_details_t none = {};
+  const orbm_two_view_details_t &D = d ? *d : none;
+  if (D.used_H) *D.used_H = -1;
+  if (D.nhyp) *D.nhyp = 0;
+  if (D.chosen) *D.chosen = -1;
+  if (D.R) memset(D.R, 0, sizeof(float) * 72);
+  if (D.t) memset(D.t, 0, sizeof(float) * 24);
+  if (D.nGood) memset(D.nGood, 0, sizeof(int32_t) * 8);
+  if (D.parallax) memset(D.parallax, 0, sizeof(float) * 8);
+  if (D.status) memset(D.status, 0, 8 * N);
+  TvModels M;
+  int rc = models(M);
+  if (rc < 0) return rc;
+  const float SH = M.top[0], SF = M.top[1];
+  if (D.SH) *D.SH = SH;
+  if (D.SF) *D.SF = SF;
+  if (D.best_it) memcpy(D.best_it, M.best, sizeof(M.best));
+  if (D.H21) memcpy(D.H21, M.M, 9 * sizeof(float));
+  if (D.F21) memcpy(D.F21, M.M + 9, 9 * sizeof(float));
+  if (D.inliersH) memcpy(D.inliersH, M.mask.data(), N);
+  if (D.inliersF) memcpy(D.inliersF, M.mask.data() + N, N);
+  if (D.score) memcpy(D.score, M.score.data(), 2 * I * sizeof(float));
+  if (SH + SF == 0.f) return 0;                          // :111
+  const float RH = SH / (SH + SF);
+  const int model = (double)RH > 0.50 ? 0 : 1;           // :117
+  if (D.used_H) *D.used_H = model == 0;
+  int inliers = 0;
+  for (size_t i = 0; i < N; i++) inliers += M.mask[model * N + i];
+  float ws[TV_WS_FLOATS], T[8 * 12];
+  double W[TV_WS_DOUBLES];
+  const int nhyp = model == 0 ? tv_hypotheses_H(M.M, K, ws, W, T) : tv_hypotheses_F(M.M + 9, K, ws, W, T);
+  if (D.nhyp) *D.nhyp = nhyp;
+  if (nhyp == 0) return 0;                               // :601
+  for (int h = 0; h < nhyp; h++)
+    for (int i = 0; i < 3; i++) {
+      if (D.R) memcpy(D.R + 9 * h + 3 * i, T + 12 * h + 4 * i, 3 * sizeof(float));
+      if (D.t) D.t[3 * h + i] = T[12 * h + 4 * i + 3];
+    }
+  TvChecked C;
+  if ((rc = check(model, nhyp, T, C)) < 0) return rc;
+  if (D.nGood) memcpy(D.nGood, C.nGood, sizeof(int32_t) * nhyp);
+  if (D.parallax) memcpy(D.parallax, C.parallax, sizeof(float) * nhyp);
+  if (D.status) memcpy(D.status, C.status.data(), (size_t)nhyp * N);
+  const int chosen = model == 0 ? tv_select_H(C.nGood, C.parallax, inliers) : tv_select_F(C.nGood, C.parallax, inliers);
+  if (D.chosen) *D.chosen = chosen;
+  if (chosen < 0) return 0;
+  for (int i = 0; i < 3; i++) {
+    memcpy(R21 + 3 * i, T + 12 * chosen + 4 * i, 3 * sizeof(float));
+    t21[i] = T[12 * chosen + 4 * i + 3];
+  }
+  memcpy(vP3D, C.p3d.data() + 3 * n1 * chosen, 3 * n1 * sizeof(float));
+  memcpy(vbTriangulated, C.good.data() + n1 * chosen, n1);
+  return 1;
+}
+}  // extern "C++"
+
+static thread_local const char *g_two_view_host_err = "";
+const char *orbm_two_view_host_error(void) { return g_two_view_host_err; }
+
+static const char *two_view_refusal(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                    const float *K, int iterations, const int32_t *sets, const float *R21, const float *t21, const float *vP3D,
+                                    const uint8_t *vbTriangulated, TvProblem &Q) {
+  if (!K || !R21 || !t21 || !vP3D || !vbTriangulated) return "TwoViewReconstruction: NULL argument";
+  if (const char *why = two_view_problem(keys1, n1, keys2, n2, matches12, 8, Q)) return why;
+  return two_view_sets(Q, iterations, sets);
+}
+
+int orbm_two_view_reconstruct_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                   const float *K, float sigma, int iterations, const int32_t *sets, float *R21, float *t21, float *vP3D,
+                                   uint8_t *vbTriangulated, const orbm_two_view_details_t *details) {
+  TvProblem Q;
+  if (const char *why = two_view_refusal(keys1, n1, keys2, n2, matches12, K, iterations, sets, R21, t21, vP3D, vbTriangulated, Q)) {
+    g_two_view_host_err = why;
+    return ORBX_E_ARG;
+  }
+  two_view_normalize(Q);
+  const uint8_t *masks = nullptr;
+  return two_view_reconstruct(
+      Q, K, sigma, iterations, R21, t21, vP3D, vbTriangulated, details,
+      [&](TvModels &M) { two_view_models_cpu(Q, sigma, iterations, sets, M); masks = M.mask.data(); return 0; },
+      [&](int model, int nhyp, const float *T, TvChecked &C) {
+        two_view_check_cpu(Q, masks + (size_t)model * Q.N, K, sigma, nhyp, T, C);
+        return 0;
+      });
+}
+
+int orbm_two_view_reconstruct(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                              const float *K, float sigma, int iterations, const int32_t *sets, float *R21, float *t21, float *vP3D,
+                              uint8_t *vbTriangulated, const orbm_two_view_details_t *details) {
+  if (!m) return ORBX_E_ARG;
+  TvProblem Q;
+  if (const char *why = two_view_refusal(keys1, n1, keys2, n2, matches12, K, iterations, sets, R21, t21, vP3D, vbTriangulated, Q)) {
+    m->err = why;
+    return ORBX_E_ARG;
+  }
+  two_view_normalize(Q);
+  MCHECK(m, hipSetDevice(m->device));
+  TvDevice D{m, Staging{m}};
+  const int rc = D.upload(Q, iterations, sets, 8, nullptr);
+  if (rc < 0) return rc;
+  return two_view_reconstruct(
+      Q, K, sigma, iterations, R21, t21, vP3D, vbTriangulated, details, [&](TvModels &M) { return D.models(Q, sigma, M); },
+      [&](int model, int nhyp, const float *T, TvChecked &C) { return D.check(K, sigma, nhyp, T, D.S.dev(D.mask) + (size_t)model * Q.N, C); });
+}
+
+static const char *two_view_models_refusal(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                           int iterations, const int32_t *sets, const float *H21, const float *H12, const float *F21,
+                                           const float *score, const int32_t *best_it, const uint8_t *masks, TvProblem &Q) {
+  if (!H21 || !H12 || !F21 || !score || !best_it || !masks) return "TwoViewReconstruction: NULL argument";
+  if (const char *why = two_view_problem(keys1, n1, keys2, n2, matches12, 8, Q)) return why;
+  return two_view_sets(Q, iterations, sets);
+}
+static void two_view_models_out(const TvModels &M, int iterations, int N, float *H21, float *H12, float *F21, float *score, int32_t *best_it,
+                                uint8_t *masks) {
+  const size_t I = (size_t)iterations;
+  memcpy(H21, M.H21.data(), 9 * I * sizeof(float)); memcpy(H12, M.H12.data(), 9 * I * sizeof(float));
+  memcpy(F21, M.F21.data(), 9 * I * sizeof(float)); memcpy(score, M.score.data(), 2 * I * sizeof(float));
+  memcpy(best_it, M.best, sizeof(M.best)); memcpy(masks, M.mask.data(), 2 * (size_t)N);
+}
+int orbm_two_view_models_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12, float sigma,
+                              int iterations, const int32_t *sets, float *H21, float *H12, float *F21, float *score, int32_t *best_it,
+                              uint8_t *masks) {
+  TvProblem Q;
+  if (const char *why = two_view_models_refusal(keys1, n1, keys2, n2, matches12, iterations, sets, H21, H12, F21, score, best_it, masks, Q)) {
+    g_two_view_host_err = why;
+    return ORBX_E_ARG;
+  }
+  two_view_normalize(Q);
+  TvModels M;
+  two_view_models_cpu(Q, sigma, iterations, sets, M);
+  two_view_models_out(M, iterations, Q.N, H21, H12, F21, score, best_it, masks);
+  return 0;
+}
+int orbm_two_view_models(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                         float sigma, int iterations, const int32_t *sets, float *H21, float *H12, float *F21, float *score, int32_t *best_it,
+                         uint8_t *masks) {
+  if (!m) return ORBX_E_ARG;
+  TvProblem Q;
+  if (const char *why = two_view_models_refusal(keys1, n1, keys2, n2, matches12, iterations, sets, H21, H12, F21, score, best_it, masks, Q)) {
+    m->err = why;
+    return ORBX_E_ARG;
+  }
+  two_view_normalize(Q);
+  MCHECK(m, hipSetDevice(m->device));
+  TvDevice D{m, Staging{m}};
+  int rc = D.upload(Q, iterations, sets, 0, nullptr);
+  if (rc < 0) return rc;
+  TvModels M;
+  if ((rc = D.models(Q, sigma, M)) < 0) return rc;
+  two_view_models_out(M, iterations, Q.N, H21, H12, F21, score, best_it, masks);
+  return 0;
+}
+
+static const char *two_view_check_refusal(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                          const uint8_t *inliers, const float *K, int nhyp, const float *R, const float *t, const float *vP3D,
+                                          const uint8_t *vbGood, const uint8_t *status, const int32_t *nGood, const float *cos_rank,
+                                          const float *parallax, TvProblem &Q, float *T) {
+  if (!inliers || !K || !R || !t || !vP3D || !vbGood || !status || !nGood || !cos_rank || !parallax) return "TwoViewReconstruction: NULL argument";
+  if (nhyp < 1 || nhyp > 8) return "TwoViewReconstruction: nhyp outside [1, 8]";
+  if (const char *why = two_view_problem(keys1, n1, keys2, n2, matches12, 1, Q)) return why;
+  for (int h = 0; h < nhyp; h++) tv_store_hypothesis(R + 9 * h, t + 3 * h, 1.f, T + 12 * h);
+  return nullptr;
+}
+static void two_view_check_out(const TvChecked &C, int nhyp, float *vP3D, uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank,
+                               float *parallax) {
+  memcpy(vP3D, C.p3d.data(), C.p3d.size() * sizeof(float)); memcpy(vbGood, C.good.data(), C.good.size());
+  memcpy(status, C.status.data(), C.status.size());
+  memcpy(nGood, C.nGood, sizeof(int32_t) * nhyp); memcpy(cos_rank, C.cos_rank, sizeof(float) * nhyp);
+  memcpy(parallax, C.parallax, sizeof(float) * nhyp);
+}
+int orbm_two_view_check_rt_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                const uint8_t *inliers, const float *K, float sigma, int nhyp, const float *R, const float *t, float *vP3D,
+                                uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank, float *parallax) {
+  TvProblem Q;
+  float T[8 * 12];
+  if (const char *why = two_view_check_refusal(keys1, n1, keys2, n2, matches12, inliers, K, nhyp, R, t, vP3D, vbGood, status, nGood, cos_rank,
+                                               parallax, Q, T)) {
+    g_two_view_host_err = why;
+    return ORBX_E_ARG;
+  }
+  TvChecked C;
+  two_view_check_cpu(Q, inliers, K, sigma, nhyp, T, C);
+  two_view_check_out(C, nhyp, vP3D, vbGood, status, nGood, cos_rank, parallax);
+  return 0;
+}
+int orbm_two_view_check_rt(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                           const uint8_t *inliers, const float *K, float sigma, int nhyp, const float *R, const float *t, float *vP3D,
+                           uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank, float *parallax) {
+  if (!m) return ORBX_E_ARG;
+  TvProblem Q;
+  float T[8 * 12];
+  if (const char *why = two_view_check_refusal(keys1, n1, keys2, n2, matches12, inliers, K, nhyp, R, t, vP3D, vbGood, status, nGood, cos_rank,
+                                               parallax, Q, T)) {
+    m->err = why;
+    return ORBX_E_ARG;
+  }
+  MCHECK(m, hipSetDevice(m->device));
+  TvDevice D{m, Staging{m}};
+  int rc = D.upload(Q, 0, nullptr, nhyp, inliers);
+  if (rc < 0) return rc;
+  TvChecked C;
+  if ((rc = D.check(K, sigma, nhyp, T, D.S.dev(D.mask_in), C)) < 0) return rc;
+  two_view_check_out(C, nhyp, vP3D, vbGood, status, nGood, cos_rank, parallax);
   return 0;
 }
 

@@ -1286,6 +1286,98 @@ int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable,
                                int32_t *n_obs_out, uint8_t *bad_out);
 const char *orbm_keyframe_culling_host_error(void);
 
+/* ---- bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated) ----
+ * (TwoViewReconstruction.cc:39-127; what GeometricCamera::ReconstructWithTwoViews calls for both camera models, Pinhole.cpp:126-133,
+ * KannalaBrandt8.cpp:211-234, from Tracking::MonocularInitialization, Tracking.cc:2492).  Every expression of the member and of what it
+ * calls (Normalize, ComputeH21 / ComputeF21 with cv::SVD, CheckHomography / CheckFundamental, ReconstructH / ReconstructF, DecomposeE,
+ * CheckRT, Triangulate) is stated once for host and device in csrc/orb_ref_twoview.h.
+ *
+ * The TWO-VIEW RULE: why the iterations may leave the two loops of FindHomography / FindFundamental (:153-176, :204-227).
+ *   - The minimal sets are drawn before either loop starts (:77-96) and neither loop changes them.
+ *   - An iteration reads nothing an earlier iteration wrote except the running best (score, and with it H21 / F21 and the inlier vector):
+ *     vPn1i / vPn2i, H21i / H12i / F21i, vbCurrentInliers and currentScore are all overwritten from the set alone (:156-168, :207-219);
+ *     the keypoints, the matches and the normalisation are read-only.
+ *   - The running best is a strict maximum taken in order (`currentScore > score` from score = 0, :170, :221): the loop keeps the FIRST
+ *     iteration whose score is the greatest one above 0, and none when no score is above 0 (a NaN score compares false and never wins).
+ * Hence the 2 x iterations hypotheses and scores are computed independently, and the winner per model is the smallest iteration that
+ * attains the maximum of the scores above 0.  Within one score the additions keep the reference's order (match ascending, the first
+ * image's term before the second's, into one float), and CheckRT's loop writes disjoint entries per match except the sorted list of
+ * cosParallax values, of which only the value at one rank is read (:902-905): equal values are interchangeable.
+ *
+ * Device form: Normalize on the host in front of the upload (it walks every keypoint of both frames, which arrive from the host), then
+ * k_tv_hypotheses, k_tv_score, k_tv_winner, one synchronisation, the 3 x 3 algebra of ReconstructH / ReconstructF and the decisions on the
+ * host (compares and one acos per hypothesis), k_tv_check_rt and k_tv_cos_rank, a second synchronisation.
+ *
+ * keys1 [n1] / keys2 [n2]: vKeys1 / vKeys2 (mvKeysUn of the two frames, the form orbm_search_for_initialization's frames use);
+ * matches12 [n1]: vMatches12, exactly what orbm_search_for_initialization returns (< 0: no match); N = the number of entries >= 0.
+ * K [9]: mK, row-major; sigma, iterations: the constructor's (1.0, 200 at Tracking.cc:2431 / the camera models).
+ * sets [iterations][8]: mvSets, indices into the N matches in ascending first-keypoint order.  They come from the CALLER: the reference
+ * draws them with DUtils::Random::RandomInt over libc rand(), seeded once per process (Random.cpp:38-50), later calls continue the
+ * stream; only the caller can reproduce that, and the library never calls rand().
+ * Out: returns 1 / 0 = the member's bool; on 1 R21 [9], t21 [3], vP3D [n1][3] (zeros where not triangulated) and vbTriangulated [n1];
+ * on 0 they are left alone (the reference leaves its arguments alone or empties R21 / t21).
+ * details (NULL, or a struct whose non-NULL members are filled as far as the call got; the rest of an array is zeros):
+ *   SH, SF [1]; best_it [2] the winning iteration of H, F or -1; H21, F21 [9] (zeros when the model is absent); inliersH, inliersF [N];
+ *   score [2][iterations]; used_H [1]: 1 ReconstructH ran, 0 ReconstructF, -1 neither (SH + SF == 0); nhyp [1]: 0, 4 or 8 hypotheses checked
+ *   (0: ReconstructH returned at :601); R [8][9], t [8][3], nGood [8], parallax [8] per hypothesis in the reference's order;
+ *   chosen [1] or -1; status [8][N] = ORBM_TV_* of every (hypothesis, match).
+ * ORBX_E_ARG, named by orbm_last_error, nothing launched, for: a NULL handle or required pointer; n1 or n2 < 0; fewer than 8 matches (the
+ * reference's draw runs off its vector there); iterations < 1; a set index outside [0, N); a match index >= n2.
+ * Undefined in the reference and unspecified here: a NaN cosParallax among the accepted ones (std::sort on it). */
+enum {
+  ORBM_TV_NOT_INLIER = 0,    /* :836  !vbMatchesInliers[i] */
+  ORBM_TV_GOOD = 1,          /* :897  accepted, cosParallax < 0.99998: vbGood */
+  ORBM_TV_LOW_PARALLAX = 2,  /* :894  accepted and counted, not vbGood */
+  ORBM_TV_NONFINITE = 3,     /* :848  a non-finite coordinate of p3dC1 */
+  ORBM_TV_BEHIND1 = 4,       /* :862  depth in the first camera */
+  ORBM_TV_BEHIND2 = 5,       /* :868  depth in the second camera */
+  ORBM_TV_REPROJ1 = 6,       /* :879  reprojection error in the first image */
+  ORBM_TV_REPROJ2 = 7,       /* :890  reprojection error in the second image */
+  ORBM_TV_NSTATUS = 8
+};
+typedef struct {
+  float *SH, *SF;
+  int32_t *best_it;
+  float *H21, *F21;
+  uint8_t *inliersH, *inliersF;
+  float *score;
+  int32_t *used_H, *nhyp;
+  float *R, *t;
+  int32_t *nGood;
+  float *parallax;
+  int32_t *chosen;
+  uint8_t *status;
+} orbm_two_view_details_t;
+int orbm_two_view_reconstruct(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2,
+                              const int32_t *matches12 /*[n1]*/, const float *K /*[9]*/, float sigma, int iterations,
+                              const int32_t *sets /*[iterations][8]*/, float *R21, float *t21, float *vP3D, uint8_t *vbTriangulated,
+                              const orbm_two_view_details_t *details);
+/* The same result on the CPU from csrc/orb_ref_twoview.h, without a device or a handle (the message of a refusal:
+ * orbm_two_view_host_error).  For tests without a GPU; it is not a fallback of the device form. */
+int orbm_two_view_reconstruct_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                   const float *K, float sigma, int iterations, const int32_t *sets, float *R21, float *t21, float *vP3D,
+                                   uint8_t *vbTriangulated, const orbm_two_view_details_t *details);
+const char *orbm_two_view_host_error(void);
+/* The two device stages alone, each with its CPU form (same refusals as above where the arguments exist).
+ * Models: H21, H12, F21 [iterations][9] of every iteration (H12 = H21i.inv()), score [2][iterations], best_it [2], masks [2][N] (the
+ * winners' inlier vectors, zeros for an absent model).  Every output is required. */
+int orbm_two_view_models(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                         float sigma, int iterations, const int32_t *sets, float *H21, float *H12, float *F21, float *score,
+                         int32_t *best_it, uint8_t *masks);
+int orbm_two_view_models_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                              float sigma, int iterations, const int32_t *sets, float *H21, float *H12, float *F21, float *score,
+                              int32_t *best_it, uint8_t *masks);
+/* CheckRT (:802-911) for nhyp in [1, 8] caller-supplied hypotheses R [nhyp][9], t [nhyp][3] and an inlier vector inliers [N]:
+ * vP3D [nhyp][n1][3] and vbGood [nhyp][n1] (zeros elsewhere), status [nhyp][N], nGood [nhyp], cos_rank [nhyp] =
+ * vCosParallax[min(50, nGood - 1)] of the sorted vector (0 when nGood == 0), parallax [nhyp] (degrees; acos on the host).  Every output
+ * is required; at least one match (not eight) is. */
+int orbm_two_view_check_rt(orbm_t *m, const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                           const uint8_t *inliers, const float *K, float sigma, int nhyp, const float *R, const float *t, float *vP3D,
+                           uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank, float *parallax);
+int orbm_two_view_check_rt_host(const orbx_keypoint_t *keys1, int n1, const orbx_keypoint_t *keys2, int n2, const int32_t *matches12,
+                                const uint8_t *inliers, const float *K, float sigma, int nhyp, const float *R, const float *t, float *vP3D,
+                                uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank, float *parallax);
+
 /* cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, matches, 2) as called by Frame::ComputeStereoFishEyeMatches
  * (Frame.cc:1246): idx2[2i..], dist2[2i..] = train index and distance of the nearest and second nearest train descriptor
  * of query i (-1 where nc < 2).  Equal distances are ordered by train index; the only consumer (the ratio test of
