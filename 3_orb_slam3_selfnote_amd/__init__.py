@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_two_view_reconstruct", "orbm_two_view_reconstruct_host", "orbm_two_view_host_error", "orbm_two_view_models", "orbm_two_view_models_host", "orbm_two_view_check_rt", "orbm_two_view_check_rt_host", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_two_view_reconstruct", "orbm_two_view_reconstruct_host", "orbm_two_view_host_error", "orbm_two_view_models", "orbm_two_view_models_host", "orbm_two_view_check_rt", "orbm_two_view_check_rt_host", "orbm_sim3_solve", "orbm_sim3_solve_host", "orbm_sim3_host_error", "orbm_sim3_hypotheses", "orbm_sim3_hypotheses_host", "orbm_sim3_check", "orbm_sim3_check_host", "orbm_sim3_ransac_iterations", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 # the vocabulary's symbols (orbv_*), a list of their own: tests/test_abi.py holds ABI_SYMBOLS equal to the header's orbx_ / orbm_ names;
@@ -244,6 +244,172 @@ def two_view_check_rt_host(keys1, keys2, matches12, inliers, K, sigma, R, t):
                               inliers, K, sigma, R, t)
 
 
+class Sim3ProblemStruct(C.Structure):  # orbm_sim3_problem_t
+    _fields_ = [("n1", C.c_int32), ("N", C.c_int32), ("idx1", C.c_void_p), ("Xw1", C.c_void_p), ("Xw2", C.c_void_p), ("sigma2_1", C.c_void_p),
+                ("sigma2_2", C.c_void_p), ("Tcw1", C.c_void_p), ("Tcw2", C.c_void_p), ("cam_type1", C.c_int32), ("cam_type2", C.c_int32),
+                ("cam_params1", C.c_void_p), ("cam_params2", C.c_void_p), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32),
+                ("iterations_done", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class Sim3ResultStruct(C.Structure):  # orbm_sim3_result_t
+    _fields_ = [(k, C.c_int32) for k in ("converged", "it_stop", "best_it", "best_inliers", "improved", "no_more")] + [
+        ("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float), ("best_mask", C.c_void_p),
+        ("vbInliers", C.c_void_p)]
+
+
+class Sim3DetailsStruct(C.Structure):  # orbm_sim3_details_t
+    _fields_ = [(k, C.c_void_p) for k in ("counts", "T12", "T21", "quat", "masks", "wall_ms")]
+
+
+class Sim3Result:
+    """What one call of Sim3Solver::iterate returns and leaves behind: converged, it_stop, best_it, best_inliers, improved, no_more (ints);
+    T12 [4,4], R12 [3,3], t12 [3], s12 of the best of this call (zeros when best_it < 0); best_mask [N]; vbInliers [n1]; and `details`:
+    counts [iterations], T12 / T21 [iterations,4,4], quat [iterations,4], masks [iterations,N]; wall_ms [4]: the device form's host clock
+    per phase (orbm_sim3_details_t::wall_ms), zeros from the CPU form."""
+
+    def __init__(self, r, best_mask, vbInliers, details, wall_ms):
+        self.wall_ms = wall_ms
+        for k in ("converged", "it_stop", "best_it", "best_inliers", "improved", "no_more"):
+            setattr(self, k, int(getattr(r, k)))
+        self.T12 = np.array(r.T12, np.float32).reshape(4, 4)
+        self.R12 = np.array(r.R12, np.float32).reshape(3, 3)
+        self.t12 = np.array(r.t12, np.float32)
+        self.s12 = np.float32(r.s12)
+        self.best_mask, self.vbInliers, self.details = best_mask, vbInliers, details
+
+    def __bool__(self):
+        return bool(self.converged)
+
+
+def _sim3_problem(prob):
+    """orbm_sim3_problem_t from a dict (n1, idx1, Xw1, Xw2, sigma2_1, sigma2_2, Tcw1, Tcw2, cam_type1, cam_type2, cam_params1, cam_params2,
+    fix_scale, min_inliers and optionally iterations_done = 0, max_iterations = 300).  Returns (struct, N, n1, the arrays it points into)."""
+    keep = dict(idx1=np.ascontiguousarray(prob["idx1"], dtype=np.int32).reshape(-1))
+    N = len(keep["idx1"])
+    for k, w in (("Xw1", 3), ("Xw2", 3), ("sigma2_1", 1), ("sigma2_2", 1)):
+        keep[k] = np.ascontiguousarray(prob[k], dtype=np.float32).reshape(-1)
+        if keep[k].size != w * N:
+            raise ValueError("%s has %d entries per pair" % (k, w))
+    for k in ("Tcw1", "Tcw2"):
+        keep[k] = np.ascontiguousarray(prob[k], dtype=np.float32).reshape(-1)
+        if keep[k].size != 16:
+            raise ValueError("%s is a 4 x 4 pose" % k)
+    for k, t in (("cam_params1", "cam_type1"), ("cam_params2", "cam_type2")):
+        keep[k] = np.zeros(8, np.float32)
+        v = np.asarray(prob[k], dtype=np.float32).reshape(-1)
+        keep[k][:min(len(v), 8)] = v[:8]
+    P = Sim3ProblemStruct()
+    P.n1, P.N = int(prob["n1"]), N
+    for k, a in keep.items():
+        setattr(P, k, a.ctypes.data if a.size else None)
+    P.cam_type1, P.cam_type2 = int(prob["cam_type1"]), int(prob["cam_type2"])
+    P.fix_scale, P.min_inliers = int(bool(prob["fix_scale"])), int(prob["min_inliers"])
+    P.iterations_done, P.max_iterations = int(prob.get("iterations_done", 0)), int(prob.get("max_iterations", 300))
+    return P, N, max(int(prob["n1"]), 0), keep
+
+
+def _sim3_sets(sets, iterations):
+    sets = np.ascontiguousarray(sets, dtype=np.int32)
+    if sets.size != 3 * max(int(iterations), 0):
+        raise ValueError("sets is [iterations][3]")
+    return sets
+
+
+def _sim3_rc(rc, what, error):
+    if rc == E_ARG:
+        raise ValueError("%s: bad argument (%s)" % (what, error()))
+    if rc < 0:
+        raise OrbError("%s rc=%d (%s)" % (what, rc, error()))
+
+
+def _sim3_solve(call, what, error, prob, sets, best_inliers_in):
+    P, N, n1, keep = _sim3_problem(prob)
+    sets = np.asarray(sets, dtype=np.int32)
+    iterations = sets.size // 3
+    sets = _sim3_sets(sets, iterations)
+    I = max(iterations, 1)
+    best_mask, vb = np.zeros(max(N, 1), np.uint8), np.zeros(max(n1, 1), np.uint8)
+    d = dict(counts=np.zeros(I, np.int32), T12=np.zeros((I, 4, 4), np.float32), T21=np.zeros((I, 4, 4), np.float32),
+             quat=np.zeros((I, 4), np.float32), masks=np.zeros((I, max(N, 1)), np.uint8))
+    wall_ms = np.zeros(4, np.float64)
+    ds = Sim3DetailsStruct()
+    for k, a in d.items():
+        setattr(ds, k, a.ctypes.data)
+    ds.wall_ms = wall_ms.ctypes.data
+    r = Sim3ResultStruct()
+    r.best_mask, r.vbInliers = best_mask.ctypes.data, vb.ctypes.data
+    _sim3_rc(call(C.byref(P), iterations, _p(sets), int(best_inliers_in), C.byref(r), C.byref(ds)), what, error)
+    d["masks"] = d["masks"].reshape(-1)[:I * N].reshape(I, N)
+    return Sim3Result(r, best_mask[:N], vb[:n1], d, wall_ms)
+
+
+def _sim3_hypotheses(call, what, error, prob, sets):
+    P, N, n1, keep = _sim3_problem(prob)
+    sets = np.asarray(sets, dtype=np.int32)
+    iterations = sets.size // 3
+    sets = _sim3_sets(sets, iterations)
+    I = max(iterations, 1)
+    T12, T21, quat = np.zeros((I, 4, 4), np.float32), np.zeros((I, 4, 4), np.float32), np.zeros((I, 4), np.float32)
+    _sim3_rc(call(C.byref(P), iterations, _p(sets), _p(T12), _p(T21), _p(quat)), what, error)
+    return dict(T12=T12, T21=T21, quat=quat)
+
+
+def _sim3_check(call, what, error, prob, T12, T21):
+    P, N, n1, keep = _sim3_problem(prob)
+    T12, T21 = np.ascontiguousarray(T12, dtype=np.float32).reshape(-1, 16), np.ascontiguousarray(T21, dtype=np.float32).reshape(-1, 16)
+    if len(T12) != len(T21):
+        raise ValueError("T12, T21 [nhyp][16]")
+    nhyp = len(T12)
+    H = max(nhyp, 1)
+    counts, masks = np.zeros(H, np.int32), np.zeros((H, max(N, 1)), np.uint8)
+    _sim3_rc(call(C.byref(P), nhyp, _p(T12), _p(T21), _p(counts), _p(masks)), what, error)
+    return dict(counts=counts[:nhyp], masks=masks.reshape(-1)[:nhyp * N].reshape(nhyp, N))
+
+
+def _sim3_host_error():
+    return load().orbm_sim3_host_error().decode()
+
+
+def sim3_solve_host(prob, sets, best_inliers_in=0):
+    """One call of Sim3Solver::iterate (Sim3Solver.cc:176-321) behind the constructor, on the CPU with the kernels' own statement
+    (orbm_sim3_solve_host, csrc/orb_ref_sim3.h).  Same arguments and result as ORBmatcher.Sim3Solve; for tests without a GPU, not a
+    fallback of it."""
+    return _sim3_solve(load().orbm_sim3_solve_host, "orbm_sim3_solve_host", _sim3_host_error, prob, sets, best_inliers_in)
+
+
+def sim3_hypotheses_host(prob, sets):
+    """orbm_sim3_hypotheses_host: ComputeSim3 for every set, on the CPU: T12, T21 [iterations,4,4], quat [iterations,4]."""
+    return _sim3_hypotheses(load().orbm_sim3_hypotheses_host, "orbm_sim3_hypotheses_host", _sim3_host_error, prob, sets)
+
+
+def sim3_check_host(prob, T12, T21):
+    """orbm_sim3_check_host: CheckInliers for the caller's transforms, on the CPU: counts [nhyp], masks [nhyp,N]."""
+    return _sim3_check(load().orbm_sim3_check_host, "orbm_sim3_check_host", _sim3_host_error, prob, T12, T21)
+
+
+def sim3_ransac_iterations(probability, min_inliers, max_its, N):
+    """Sim3Solver::SetRansacParameters (Sim3Solver.cc:150-174): the value left in mRansacMaxIts (orbm_sim3_ransac_iterations)."""
+    return int(load().orbm_sim3_ransac_iterations(float(probability), int(min_inliers), int(max_its), int(N)))
+
+
+def sim3_draw_sets(N, iterations, rand):
+    """The minimal sets of `iterations` iterations of Sim3Solver::iterate (Sim3Solver.cc:199-213) as [iterations][3] int32: per iteration
+    three times DUtils::Random::RandomInt(0, size - 1) of the shrinking index vector, the drawn entry replaced by the last.  rand: a
+    callable returning the next value of libc rand(); RandomInt(min, max) is int(((double)rand() / ((double)RAND_MAX + 1.0)) * (max - min + 1)) + min
+    (Random.cpp:47-50)."""
+    if N < 3:
+        raise ValueError("the draw needs three pairs")
+    sets = np.zeros((iterations, 3), np.int32)
+    for it in range(iterations):
+        avail = list(range(N))
+        for j in range(3):
+            randi = int((float(rand()) / 2147483648.0) * len(avail))
+            sets[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return sets
+
+
 class FuseTargetStruct(C.Structure):  # orbm_fuse_target_t
     _fields_ = [("kf", FrameStruct), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
                 ("log_scale_factor", C.c_float), ("Tcw", C.c_void_p), ("Ow", C.c_void_p), ("cam_type", C.c_int32), ("cam_params", C.c_void_p),
@@ -431,6 +597,15 @@ def load(build_if_needed=True):
     L.orbm_two_view_models_host.argtypes = tv + [f32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_two_view_check_rt.argtypes = [vp] + tv + [vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_two_view_check_rt_host.argtypes = tv + [vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_sim3_solve.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+    L.orbm_sim3_solve_host.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.orbm_sim3_host_error.argtypes = []
+    L.orbm_sim3_host_error.restype = C.c_char_p
+    L.orbm_sim3_hypotheses.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.orbm_sim3_hypotheses_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.orbm_sim3_check.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.orbm_sim3_check_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.orbm_sim3_ransac_iterations.argtypes = [C.c_double, i32, i32, i32]
     L.orbm_knn_match2.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, f32, i32, vp]
     L.orbm_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, f32, i32, vp]
@@ -1409,6 +1584,20 @@ class ORBmatcher:
         """The second device stage alone (orbm_two_view_check_rt): CheckRT for the caller's hypotheses R [nhyp,3,3], t [nhyp,3]."""
         return _two_view_check_rt(self._tv_call(self.L.orbm_two_view_check_rt), "orbm_two_view_check_rt", self._tv_error, keys1, keys2,
                                   matches12, inliers, K, sigma, R, t)
+
+    def Sim3Solve(self, prob, sets, best_inliers_in=0):
+        """Sim3Solver's constructor and one call of iterate(nIterations, bNoMore, vbInliers, nInliers[, bConverge]) (Sim3Solver.cc:35-321) on
+        the device (orbm_sim3_solve).  prob: the dict of _sim3_problem (the kept pairs and both keyframes); sets [iterations][3] drawn by the
+        caller as the reference draws them (sim3_draw_sets over rand()); best_inliers_in = mnBestInliers.  Returns a Sim3Result."""
+        return _sim3_solve(self._tv_call(self.L.orbm_sim3_solve), "orbm_sim3_solve", self._tv_error, prob, sets, best_inliers_in)
+
+    def Sim3Hypotheses(self, prob, sets):
+        """The first device stage and the host tail alone (orbm_sim3_hypotheses): T12, T21 and the quaternion row of every set."""
+        return _sim3_hypotheses(self._tv_call(self.L.orbm_sim3_hypotheses), "orbm_sim3_hypotheses", self._tv_error, prob, sets)
+
+    def Sim3Check(self, prob, T12, T21):
+        """The second device stage alone (orbm_sim3_check): CheckInliers for the caller's transforms T12, T21 [nhyp,4,4]."""
+        return _sim3_check(self._tv_call(self.L.orbm_sim3_check), "orbm_sim3_check", self._tv_error, prob, T12, T21)
 
     def KeyFrameCullingOpen(self, scene):
         """Opens the stepwise walk (orbm_keyframe_culling_open): uploads the scene and computes the loop-entry status of every row.  An

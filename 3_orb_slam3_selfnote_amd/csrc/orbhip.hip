@@ -36,6 +36,7 @@
 #include "orb_mappoint_kernels.h"
 #include "orb_culling_kernels.h"
 #include "orb_twoview_kernels.h"
+#include "orb_sim3_kernels.h"
 #include "orb_voc_kernels.h"
 #include "orb_kfdb_kernels.h"
 
@@ -4812,6 +4813,349 @@ int orbm_two_view_check_rt(orbm_t *m, const orbx_keypoint_t *keys1, int n1, cons
   if ((rc = D.check(K, sigma, nhyp, T, D.S.dev(D.mask_in), C)) < 0) return rc;
   two_view_check_out(C, nhyp, vP3D, vbGood, status, nGood, cos_rank, parallax);
   return 0;
+}
+
+// ---- Sim3Solver (Sim3Solver.cc:35-530): orb_ref_sim3.h, orb_sim3_kernels.h ----
+// What the constructor leaves behind (:85-147): camera coordinates, their projections and the thresholds of the N kept pairs
+struct Sim3Problem {
+  const orbm_sim3_problem_t *p;
+  size_t N, n1;
+  std::vector<float> X1, X2, im1, im2, th1, th2;
+};
+// What is refused before anything is uploaded, launched or written (include/orbhip.h); nullptr = accepted
+static const char *sim3_problem(const orbm_sim3_problem_t *p, Sim3Problem &Q) {
+  if (!p) return "Sim3Solver: NULL argument";
+  if (p->n1 < 0 || p->N < 0) return "Sim3Solver: negative count";
+  if (p->N > p->n1) return "Sim3Solver: N > n1";
+  if (!p->Tcw1 || !p->Tcw2 || !p->cam_params1 || !p->cam_params2) return "Sim3Solver: NULL argument";
+  if (p->N > 0 && (!p->idx1 || !p->Xw1 || !p->Xw2 || !p->sigma2_1 || !p->sigma2_2)) return "Sim3Solver: NULL argument";
+  if (p->cam_type1 < 0 || p->cam_type1 > 1 || p->cam_type2 < 0 || p->cam_type2 > 1) return "Sim3Solver: unknown camera type";
+  if (p->min_inliers < 0) return "Sim3Solver: min_inliers < 0";
+  if (p->iterations_done < 0) return "Sim3Solver: iterations_done < 0";
+  for (int i = 0; i < p->N; i++) {
+    if (p->idx1[i] < 0 || p->idx1[i] >= p->n1) return "Sim3Solver: idx1 outside [0, n1)";
+    if (i > 0 && p->idx1[i] <= p->idx1[i - 1]) return "Sim3Solver: idx1 not ascending";
+    if (!sim3_sigma2_ok(p->sigma2_1[i]) || !sim3_sigma2_ok(p->sigma2_2[i])) return "Sim3Solver: sigma2 negative, not finite or too large";
+  }
+  Q.p = p; Q.N = (size_t)p->N; Q.n1 = (size_t)p->n1;
+  return nullptr;
+}
+static const char *sim3_sets(const Sim3Problem &Q, int iterations, const int32_t *sets) {
+  if (iterations < 1) return "Sim3Solver: iterations < 1";
+  if (!sets) return "Sim3Solver: NULL argument";
+  if (Q.N < 3) return "Sim3Solver: fewer than 3 pairs";
+  for (size_t k = 0; k < (size_t)iterations; k++) {
+    const int32_t *s = sets + 3 * k;
+    for (int j = 0; j < 3; j++)
+      if (s[j] < 0 || (size_t)s[j] >= Q.N) return "Sim3Solver: set index outside [0, N)";
+    if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) return "Sim3Solver: set index repeated within a set";
+  }
+  return nullptr;
+}
+static void sim3_construct(Sim3Problem &Q) {   // :128-132, :143-144, :119-120
+  const orbm_sim3_problem_t &p = *Q.p;
+  Q.X1.resize(3 * Q.N); Q.X2.resize(3 * Q.N); Q.im1.resize(2 * Q.N); Q.im2.resize(2 * Q.N); Q.th1.resize(Q.N); Q.th2.resize(Q.N);
+  for (size_t i = 0; i < Q.N; i++) {
+    sim3_transform(p.Tcw1, p.Xw1 + 3 * i, &Q.X1[3 * i]);
+    sim3_transform(p.Tcw2, p.Xw2 + 3 * i, &Q.X2[3 * i]);
+    sim3_project(p.cam_type1, p.cam_params1, &Q.X1[3 * i], &Q.im1[2 * i]);
+    sim3_project(p.cam_type2, p.cam_params2, &Q.X2[3 * i], &Q.im2[2 * i]);
+    Q.th1[i] = sim3_max_error(p.sigma2_1[i]);
+    Q.th2[i] = sim3_max_error(p.sigma2_2[i]);
+  }
+}
+static int sim3_cam_floats(int cam_type) { return cam_type == 0 ? 4 : 8; }
+
+static void sim3_gather(const Sim3Problem &Q, const int32_t *set, float *P1, float *P2) {   // copyTo(P3Dc1i.col(i)) :208-209
+  for (int c = 0; c < 3; c++)
+    for (int r = 0; r < 3; r++) { P1[3 * r + c] = Q.X1[3 * (size_t)set[c] + r]; P2[3 * r + c] = Q.X2[3 * (size_t)set[c] + r]; }
+}
+// The outputs of the hypothesis stage on the host: per iteration the tail's result and the quaternion row
+struct Sim3Hyps { std::vector<Sim3Hyp> H; std::vector<float> quat; };
+static void sim3_hypotheses_cpu(const Sim3Problem &Q, int iterations, const int32_t *sets, Sim3Hyps &R) {
+  R.H.resize((size_t)iterations); R.quat.resize(4 * (size_t)iterations);
+  for (size_t it = 0; it < (size_t)iterations; it++) {
+    float P1[9], P2[9];
+    sim3_gather(Q, sets + 3 * it, P1, P2);
+    Sim3Set S;
+    float ws[SIM3_WS_FLOATS];
+    int iw[SIM3_WS_INTS];
+    sim3_quaternion(P1, P2, S, &R.quat[4 * it], ws, iw);
+    sim3_tail(S, &R.quat[4 * it], Q.p->fix_scale != 0, R.H[it]);
+  }
+}
+static void sim3_check_cpu(const Sim3Problem &Q, size_t nhyp, const float *T /*[nhyp][32]*/, int32_t *counts, uint8_t *masks) {
+  const orbm_sim3_problem_t &p = *Q.p;
+  for (size_t h = 0; h < nhyp; h++) {
+    int count = 0;
+    for (size_t i = 0; i < Q.N; i++) {
+      const bool in = sim3_inlier(T + 32 * h, T + 32 * h + 16, p.cam_type1, p.cam_params1, p.cam_type2, p.cam_params2, &Q.X1[3 * i],
+                                  &Q.X2[3 * i], &Q.im1[2 * i], &Q.im2[2 * i], Q.th1[i], Q.th2[i]);
+      masks[h * Q.N + i] = in;
+      count += in;
+    }
+    counts[h] = count;
+  }
+}
+static void sim3_pack(const Sim3Hyps &R, std::vector<float> &T) {
+  T.resize(32 * R.H.size());
+  for (size_t h = 0; h < R.H.size(); h++) { memcpy(&T[32 * h], R.H[h].T12, 64); memcpy(&T[32 * h + 16], R.H[h].T21, 64); }
+}
+
+// The device side: one staged block.  Inputs first, then T (uploaded behind the host tail), then the outputs, one span down.
+struct Sim3Device {
+  orbm_t *m;
+  Staging S;
+  PartOf<float> X1, X2, im1, im2, th1, th2, T, set_out;
+  PartOf<int32_t> idx1, sets, counts, pass;
+  PartOf<uint64_t> words;
+  PartOf<uint8_t> best_mask, vb;
+  size_t I, N, n1, W;
+  double wall_ms[4] = {0, 0, 0, 0};   // orbm_sim3_details_t::wall_ms; [0] is the caller's
+  using Clock = std::chrono::steady_clock;
+  static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+  int upload(const Sim3Problem &Q, size_t iterations, const int32_t *set_idx) {
+    I = iterations; N = Q.N; n1 = Q.n1; W = (N + 63) / 64;
+    X1 = S.add(Q.X1.data(), 3 * N); X2 = S.add(Q.X2.data(), 3 * N); im1 = S.add(Q.im1.data(), 2 * N); im2 = S.add(Q.im2.data(), 2 * N);
+    th1 = S.add(Q.th1.data(), N); th2 = S.add(Q.th2.data(), N); idx1 = S.add(Q.p->idx1, N); sets = S.add(set_idx, set_idx ? 3 * I : 0);
+    T = S.out<float>(32 * I); set_out = S.out<float>(set_idx ? SIM3_SET_FLOATS * I : 0);
+    counts = S.out<int32_t>(I); words = S.out<uint64_t>(I * W); pass = S.out<int32_t>(8); best_mask = S.out<uint8_t>(N); vb = S.out<uint8_t>(n1 + 1);
+    return S.upload(m->stream);
+  }
+  Sim3Params params(const Sim3Problem &Q) const {
+    const orbm_sim3_problem_t &p = *Q.p;
+    Sim3Params P = {};
+    P.X1 = S.dev(X1); P.X2 = S.dev(X2); P.im1 = S.dev(im1); P.im2 = S.dev(im2); P.th1 = S.dev(th1); P.th2 = S.dev(th2);
+    P.idx1 = S.dev(idx1); P.sets = S.dev(sets);
+    P.iterations = (int)I; P.N = (int)N; P.n1 = (int)n1; P.words = (int)W;
+    P.cam1 = p.cam_type1; P.cam2 = p.cam_type2;
+    memcpy(P.p1, p.cam_params1, sizeof(float) * sim3_cam_floats(p.cam_type1));
+    memcpy(P.p2, p.cam_params2, sizeof(float) * sim3_cam_floats(p.cam_type2));
+    P.set_out = S.dev(set_out); P.T = S.dev(T); P.counts = S.dev(counts); P.mask_words = S.dev(words);
+    P.pass = S.dev(pass); P.best_mask = S.dev(best_mask); P.vb = S.dev(vb);
+    return P;
+  }
+  // k_sim3_hypotheses, the sets' centred points and quaternions down, the first synchronisation, the tail on the host
+  int hypotheses(const Sim3Problem &Q, Sim3Hyps &R) {
+    hipStream_t s = m->stream;
+    const Sim3Params P = params(Q);
+    hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    MCHECK(m, hipMemcpyAsync(S.host(set_out), S.dev(set_out), sizeof(float) * SIM3_SET_FLOATS * I, hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    const Clock::time_point t_tail = Clock::now();
+    R.H.resize(I); R.quat.resize(4 * I);
+    const float *o = S.host(set_out);
+    for (size_t it = 0; it < I; it++, o += SIM3_SET_FLOATS) {
+      Sim3Set set;
+      memcpy(&set, o, sizeof(set));
+      memcpy(&R.quat[4 * it], o + 24, 4 * sizeof(float));
+      sim3_tail(set, o + 24, Q.p->fix_scale != 0, R.H[it]);
+    }
+    wall_ms[2] = ms_since(t_tail);
+    return 0;
+  }
+  // T up, k_sim3_check, with `winner` k_sim3_winner, everything down, one synchronisation.  masks: [I][N] bytes or NULL
+  int check(const Sim3Problem &Q, const float *Tpacked, bool winner, int best_in, int32_t *counts_out, uint8_t *masks, Sim3Pass *pass_out,
+            uint8_t *best_mask_out, uint8_t *vb_out) {
+    hipStream_t s = m->stream;
+    const Clock::time_point t_check = Clock::now();
+    memcpy(S.host(T), Tpacked, sizeof(float) * 32 * I);
+    MCHECK(m, hipMemcpyAsync(S.dev(T), S.host(T), sizeof(float) * 32 * I, hipMemcpyHostToDevice, s));
+    Sim3Params P = params(Q);
+    P.best_in = best_in; P.min_inliers = Q.p->min_inliers; P.done = Q.p->iterations_done; P.max_its = Q.p->max_iterations;
+    hipLaunchKernelGGL(k_sim3_check, dim3((unsigned)I), dim3(64), 0, s, P);
+    MCHECK(m, hipGetLastError());
+    if (winner) {
+      hipLaunchKernelGGL(k_sim3_winner, dim3(1), dim3(256), 0, s, P);
+      MCHECK(m, hipGetLastError());
+    }
+    const uint8_t *lo = (const uint8_t *)S.dev(counts);
+    MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)(S.dev(vb) + n1 + 1 - lo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    wall_ms[3] = ms_since(t_check);
+    if (counts_out) memcpy(counts_out, S.host(counts), sizeof(int32_t) * I);
+    if (masks) {
+      const uint64_t *w = S.host(words);
+      for (size_t it = 0; it < I; it++)
+        for (size_t i = 0; i < N; i++) masks[it * N + i] = (uint8_t)((w[it * W + (i >> 6)] >> (i & 63)) & 1);
+    }
+    if (winner) {
+      const int32_t *ps = S.host(pass);
+      *pass_out = Sim3Pass{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5]};
+      memcpy(best_mask_out, S.host(best_mask), N);
+      memcpy(vb_out, S.host(vb), n1);
+    }
+    return 0;
+  }
+};
+
+static thread_local const char *g_sim3_host_err = "";
+const char *orbm_sim3_host_error(void) { return g_sim3_host_err; }
+
+static void sim3_no_more(const Sim3Problem &Q, int best_in, orbm_sim3_result_t *r) {   // :182-186, :252-256
+  uint8_t *bm = r->best_mask, *vb = r->vbInliers;
+  memset(r, 0, sizeof(*r));
+  r->best_mask = bm; r->vbInliers = vb;
+  r->best_it = -1; r->best_inliers = best_in; r->no_more = 1;
+  memset(bm, 0, Q.N); memset(vb, 0, Q.n1);
+}
+// The result and the details from the pass and every iteration's hypothesis
+static void sim3_result(const Sim3Problem &Q, size_t I, const Sim3Pass &pass, const Sim3Hyps &R, const int32_t *counts, const uint8_t *masks,
+                        orbm_sim3_result_t *r, const orbm_sim3_details_t *d) {
+  r->converged = pass.converged; r->it_stop = pass.it_stop; r->best_it = pass.best_it; r->best_inliers = pass.best_inliers;
+  r->improved = pass.improved; r->no_more = pass.no_more;
+  memset(r->T12, 0, sizeof(r->T12)); memset(r->R12, 0, sizeof(r->R12)); memset(r->t12, 0, sizeof(r->t12)); r->s12 = 0.f;
+  if (pass.best_it >= 0) {
+    const Sim3Hyp &H = R.H[(size_t)pass.best_it];
+    memcpy(r->T12, H.T12, sizeof(r->T12)); memcpy(r->R12, H.R, sizeof(r->R12)); memcpy(r->t12, H.t, sizeof(r->t12)); r->s12 = H.s;
+  }
+  if (!d) return;
+  if (d->counts) memcpy(d->counts, counts, sizeof(int32_t) * I);
+  if (d->masks) memcpy(d->masks, masks, I * Q.N);
+  for (size_t it = 0; it < I; it++) {
+    if (d->T12) memcpy(d->T12 + 16 * it, R.H[it].T12, 64);
+    if (d->T21) memcpy(d->T21 + 16 * it, R.H[it].T21, 64);
+  }
+  if (d->quat) memcpy(d->quat, R.quat.data(), sizeof(float) * 4 * I);
+  if (d->wall_ms) memset(d->wall_ms, 0, 4 * sizeof(double));
+}
+// 0: go on; 1: answered without a launch (N < min_inliers); the refusal's text otherwise
+static const char *sim3_solve_refusal(const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, orbm_sim3_result_t *r, Sim3Problem &Q,
+                                      bool &no_more) {
+  no_more = false;
+  if (!r || !r->best_mask || !r->vbInliers) return "Sim3Solver: NULL argument";
+  if (const char *why = sim3_problem(p, Q)) return why;
+  if (iterations < 1) return "Sim3Solver: iterations < 1";
+  if (!sets) return "Sim3Solver: NULL argument";
+  if (p->N < p->min_inliers) { no_more = true; return nullptr; }
+  return sim3_sets(Q, iterations, sets);
+}
+
+int orbm_sim3_solve_host(const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, int best_inliers_in, orbm_sim3_result_t *r,
+                         const orbm_sim3_details_t *d) {
+  Sim3Problem Q;
+  bool no_more;
+  if (const char *why = sim3_solve_refusal(p, iterations, sets, r, Q, no_more)) { g_sim3_host_err = why; return ORBX_E_ARG; }
+  if (no_more) { sim3_no_more(Q, best_inliers_in, r); return 0; }
+  sim3_construct(Q);
+  const size_t I = (size_t)iterations;
+  Sim3Hyps R;
+  sim3_hypotheses_cpu(Q, iterations, sets, R);
+  std::vector<float> T;
+  sim3_pack(R, T);
+  std::vector<int32_t> counts(I);
+  std::vector<uint8_t> masks(I * Q.N);
+  sim3_check_cpu(Q, I, T.data(), counts.data(), masks.data());
+  const Sim3Pass pass = sim3_ordered_pass(counts.data(), iterations, best_inliers_in, p->min_inliers, p->iterations_done, p->max_iterations);
+  memset(r->best_mask, 0, Q.N); memset(r->vbInliers, 0, Q.n1);
+  if (pass.best_it >= 0) memcpy(r->best_mask, &masks[(size_t)pass.best_it * Q.N], Q.N);
+  if (pass.converged)
+    for (size_t i = 0; i < Q.N; i++)
+      if (r->best_mask[i]) r->vbInliers[p->idx1[i]] = 1;   // :231-233
+  sim3_result(Q, I, pass, R, counts.data(), masks.data(), r, d);
+  return 0;
+}
+
+int orbm_sim3_solve(orbm_t *m, const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, int best_inliers_in, orbm_sim3_result_t *r,
+                    const orbm_sim3_details_t *d) {
+  if (!m) return ORBX_E_ARG;
+  Sim3Problem Q;
+  bool no_more;
+  if (const char *why = sim3_solve_refusal(p, iterations, sets, r, Q, no_more)) { m->err = why; return ORBX_E_ARG; }
+  if (no_more) { sim3_no_more(Q, best_inliers_in, r); return 0; }
+  const Sim3Device::Clock::time_point t0 = Sim3Device::Clock::now();
+  sim3_construct(Q);
+  MCHECK(m, hipSetDevice(m->device));
+  const size_t I = (size_t)iterations;
+  Sim3Device D{m, Staging{m}};
+  D.wall_ms[0] = Sim3Device::ms_since(t0);
+  const Sim3Device::Clock::time_point t1 = Sim3Device::Clock::now();
+  int rc = D.upload(Q, I, sets);
+  if (rc < 0) return rc;
+  Sim3Hyps R;
+  if ((rc = D.hypotheses(Q, R)) < 0) return rc;
+  D.wall_ms[1] = Sim3Device::ms_since(t1) - D.wall_ms[2];
+  std::vector<float> T;
+  sim3_pack(R, T);
+  std::vector<int32_t> counts(I);
+  std::vector<uint8_t> masks(d && d->masks ? I * Q.N : 0);
+  Sim3Pass pass;
+  if ((rc = D.check(Q, T.data(), true, best_inliers_in, counts.data(), masks.empty() ? nullptr : masks.data(), &pass, r->best_mask,
+                    r->vbInliers)) < 0)
+    return rc;
+  sim3_result(Q, I, pass, R, counts.data(), masks.data(), r, d);
+  if (d && d->wall_ms) memcpy(d->wall_ms, D.wall_ms, sizeof(D.wall_ms));
+  return 0;
+}
+
+static const char *sim3_hypotheses_refusal(const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, const float *T12, const float *T21,
+                                           const float *quat, Sim3Problem &Q) {
+  if (!T12 || !T21 || !quat) return "Sim3Solver: NULL argument";
+  if (const char *why = sim3_problem(p, Q)) return why;
+  return sim3_sets(Q, iterations, sets);
+}
+static void sim3_hypotheses_out(const Sim3Hyps &R, float *T12, float *T21, float *quat) {
+  for (size_t it = 0; it < R.H.size(); it++) { memcpy(T12 + 16 * it, R.H[it].T12, 64); memcpy(T21 + 16 * it, R.H[it].T21, 64); }
+  memcpy(quat, R.quat.data(), sizeof(float) * R.quat.size());
+}
+int orbm_sim3_hypotheses_host(const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, float *T12, float *T21, float *quat) {
+  Sim3Problem Q;
+  if (const char *why = sim3_hypotheses_refusal(p, iterations, sets, T12, T21, quat, Q)) { g_sim3_host_err = why; return ORBX_E_ARG; }
+  sim3_construct(Q);
+  Sim3Hyps R;
+  sim3_hypotheses_cpu(Q, iterations, sets, R);
+  sim3_hypotheses_out(R, T12, T21, quat);
+  return 0;
+}
+int orbm_sim3_hypotheses(orbm_t *m, const orbm_sim3_problem_t *p, int iterations, const int32_t *sets, float *T12, float *T21, float *quat) {
+  if (!m) return ORBX_E_ARG;
+  Sim3Problem Q;
+  if (const char *why = sim3_hypotheses_refusal(p, iterations, sets, T12, T21, quat, Q)) { m->err = why; return ORBX_E_ARG; }
+  sim3_construct(Q);
+  MCHECK(m, hipSetDevice(m->device));
+  Sim3Device D{m, Staging{m}};
+  int rc = D.upload(Q, (size_t)iterations, sets);
+  if (rc < 0) return rc;
+  Sim3Hyps R;
+  if ((rc = D.hypotheses(Q, R)) < 0) return rc;
+  sim3_hypotheses_out(R, T12, T21, quat);
+  return 0;
+}
+
+static const char *sim3_check_refusal(const orbm_sim3_problem_t *p, int nhyp, const float *T12, const float *T21, const int32_t *counts,
+                                      const uint8_t *masks, Sim3Problem &Q, std::vector<float> &T) {
+  if (!T12 || !T21 || !counts || !masks) return "Sim3Solver: NULL argument";
+  if (const char *why = sim3_problem(p, Q)) return why;
+  if (nhyp < 1) return "Sim3Solver: nhyp < 1";
+  if (Q.N < 1) return "Sim3Solver: no pair";
+  T.resize(32 * (size_t)nhyp);
+  for (size_t h = 0; h < (size_t)nhyp; h++) { memcpy(&T[32 * h], T12 + 16 * h, 64); memcpy(&T[32 * h + 16], T21 + 16 * h, 64); }
+  return nullptr;
+}
+int orbm_sim3_check_host(const orbm_sim3_problem_t *p, int nhyp, const float *T12, const float *T21, int32_t *counts, uint8_t *masks) {
+  Sim3Problem Q;
+  std::vector<float> T;
+  if (const char *why = sim3_check_refusal(p, nhyp, T12, T21, counts, masks, Q, T)) { g_sim3_host_err = why; return ORBX_E_ARG; }
+  sim3_construct(Q);
+  sim3_check_cpu(Q, (size_t)nhyp, T.data(), counts, masks);
+  return 0;
+}
+int orbm_sim3_check(orbm_t *m, const orbm_sim3_problem_t *p, int nhyp, const float *T12, const float *T21, int32_t *counts, uint8_t *masks) {
+  if (!m) return ORBX_E_ARG;
+  Sim3Problem Q;
+  std::vector<float> T;
+  if (const char *why = sim3_check_refusal(p, nhyp, T12, T21, counts, masks, Q, T)) { m->err = why; return ORBX_E_ARG; }
+  sim3_construct(Q);
+  MCHECK(m, hipSetDevice(m->device));
+  Sim3Device D{m, Staging{m}};
+  const int rc = D.upload(Q, (size_t)nhyp, nullptr);
+  if (rc < 0) return rc;
+  return D.check(Q, T.data(), false, 0, counts, masks, nullptr, nullptr, nullptr);
+}
+
+int orbm_sim3_ransac_iterations(double probability, int min_inliers, int max_its, int N) {
+  return sim3_ransac_iterations(probability, min_inliers, max_its, N);
 }
 
 int orbm_knn_match2(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, int nc, int32_t *idx2, int32_t *dist2) {

@@ -1378,6 +1378,96 @@ int orbm_two_view_check_rt_host(const orbx_keypoint_t *keys1, int n1, const orbx
                                 const uint8_t *inliers, const float *K, float sigma, int nhyp, const float *R, const float *t, float *vP3D,
                                 uint8_t *vbGood, uint8_t *status, int32_t *nGood, float *cos_rank, float *parallax);
 
+/* ---- Sim3Solver: the constructor, SetRansacParameters, ComputeSim3, CheckInliers and one call of iterate ----
+ * (Sim3Solver.cc:35-530; built at LoopClosing.cc:810-824 from the matches of SearchByBoW against a candidate and its covisibles, the
+ * step between orbm_search_by_bow_keyframes_candidates and the Sim3 SearchByProjection.)  Every expression is stated once for host and
+ * device in csrc/orb_ref_sim3.h.
+ *
+ * The SIM3 RULE: why the iterations may leave the loop of iterate (:194-237, :267-315).
+ *   - The set of iteration i is drawn from mvAllIndices alone (:199-213); nothing an iteration computes reaches a later draw.
+ *   - ComputeSim3 and CheckInliers overwrite mR12i, mt12i, ms12i, mT12i, mT21i, mvbInliersi and mnInliersi from the set alone; the camera
+ *     coordinates, the projections and the thresholds are read-only behind the constructor.
+ *   - The only state carried across iterations, and across calls of iterate, is the running best, taken with `>=` (:219, :292): of equal
+ *     counts the LATER iteration wins.
+ *   - An iteration ends the loop where its count is >= the best before it AND > mRansacMinInliers, strictly (:228, :301): a count equal
+ *     to mRansacMinInliers does not converge.
+ * Hence all counts are computed independently, and one ordered pass over them gives the stop iteration, the best hypothesis, bNoMore
+ * (mnIterations >= mRansacMaxIts, :239, :317) and, for the five-argument overload, whether this call improved the best (its bestSim3).
+ *
+ * Device form: the constructor's two transforms and projections on the host in front of one staged upload (they walk host data);
+ * k_sim3_hypotheses (centroids, M, N, OpenCV's float Jacobi eigen per iteration); a first synchronisation; per hypothesis on the host
+ * the double-libm tail (atan2, cv::Rodrigues, scale, translation, T12, T21: no device sin / cos / atan2 for double is pinned against
+ * glibc); k_sim3_check for every (iteration, pair); k_sim3_winner, the ordered pass and the winner's mask; one download, the second
+ * synchronisation.
+ *
+ * The problem: n1 = mN1 (the length of vpMatched12) and the N pairs the constructor keeps (:85-137), in its order:
+ *   idx1 [N] mvnIndices1 (ascending, in [0, n1)); Xw1 / Xw2 [N][3] the world positions of pMP1 / pMP2; sigma2_1 / sigma2_2 [N]
+ *   pKF1->mvLevelSigma2[kp1.octave] / pKFm->mvLevelSigma2[kp2.octave] (pKFm: the keyframe the pair was matched in, :101-115);
+ *   Tcw1 / Tcw2 [16] row-major poses of pKF1 / pKF2 - pKF2's even for a pair matched in another keyframe (:132);
+ *   cam_type1/2 (0 Pinhole, 1 KannalaBrandt8) and cam_params1/2 (4 / 8 floats) of pKF1->mpCamera / pKF2->mpCamera;
+ *   fix_scale mbFixScale; min_inliers mRansacMinInliers; iterations_done / max_iterations: mnIterations at entry and mRansacMaxIts
+ *   (orbm_sim3_ransac_iterations).
+ * sets [iterations][3]: the pairs of every iteration of this call, indices into the N pairs after the reference's swap-with-last draw
+ * (:204-212), so distinct within a set.  They come from the CALLER (DUtils::Random over libc rand()); the library never calls rand().
+ * The loop runs min(iterations, max_iterations - iterations_done) iterations at the most; later sets are not part of the answer.
+ * best_inliers_in: mnBestInliers at entry.
+ * The result: converged (bConverge / a non-empty return of the four-argument overload), it_stop (iterations consumed, what mnIterations
+ * grows by), best_it (the iteration of this call that holds the best, -1 when none reached best_inliers_in), best_inliers (mnBestInliers
+ * at exit), improved (1 when best_it >= 0), no_more (bNoMore); T12 [16], R12 [9], t12 [3], s12 of best_it (mBestT12, mBestRotation,
+ * mBestTranslation, mBestScale; zeros when best_it < 0: the members keep their values); best_mask [N] mvbBestInliers of best_it (zeros
+ * when best_it < 0) and vbInliers [n1], spread through idx1 on convergence and zeros otherwise - the caller's two buffers, both required.
+ * details (NULL, or a struct whose non-NULL members are filled): counts [iterations], T12 / T21 [iterations][16], quat [iterations][4]
+ * (evec.row(0)), masks [iterations][N] - of EVERY iteration of the call, also those behind it_stop; wall_ms [4], the host's clock over
+ * the device form's four phases, for measurements (tools/sim3_solver_bench.py; zeros from the CPU form): the constructor's host loop;
+ * staging, upload, k_sim3_hypotheses and its download up to the first synchronisation; the host tail; the transforms' upload,
+ * k_sim3_check, k_sim3_winner and the download up to the second synchronisation.
+ * N < min_inliers is the reference's bNoMore return (:182, :252): converged = 0, it_stop = 0, no_more = 1, nothing launched.
+ * ORBX_E_ARG, named by orbm_last_error, nothing launched, for: NULL where required; N < 3 (the draw runs off its vector); N > n1; an idx1
+ * outside [0, n1) or not ascending; a set index outside [0, N) or repeated within a set; iterations < 1; min_inliers < 0;
+ * iterations_done < 0; an unknown camera type; a sigma2 that is negative, not finite or >= 9e15 (its size_t conversion is undefined). */
+typedef struct {
+  int32_t n1, N;
+  const int32_t *idx1;
+  const float *Xw1, *Xw2;
+  const float *sigma2_1, *sigma2_2;
+  const float *Tcw1, *Tcw2;
+  int32_t cam_type1, cam_type2;
+  const float *cam_params1, *cam_params2;
+  int32_t fix_scale, min_inliers;
+  int32_t iterations_done, max_iterations;
+} orbm_sim3_problem_t;
+typedef struct {
+  int32_t converged, it_stop, best_it, best_inliers, improved, no_more;
+  float T12[16], R12[9], t12[3], s12;
+  uint8_t *best_mask; /* [N], the caller's */
+  uint8_t *vbInliers; /* [n1], the caller's */
+} orbm_sim3_result_t;
+typedef struct {
+  int32_t *counts;
+  float *T12, *T21, *quat;
+  uint8_t *masks;
+  double *wall_ms;
+} orbm_sim3_details_t;
+int orbm_sim3_solve(orbm_t *m, const orbm_sim3_problem_t *problem, int iterations, const int32_t *sets /*[iterations][3]*/,
+                    int best_inliers_in, orbm_sim3_result_t *result, const orbm_sim3_details_t *details);
+/* The same result on the CPU from csrc/orb_ref_sim3.h, without a device or a handle (the message of a refusal: orbm_sim3_host_error).
+ * For tests without a GPU; it is not a fallback of the device form. */
+int orbm_sim3_solve_host(const orbm_sim3_problem_t *problem, int iterations, const int32_t *sets, int best_inliers_in,
+                         orbm_sim3_result_t *result, const orbm_sim3_details_t *details);
+const char *orbm_sim3_host_error(void);
+/* The stages alone, each with its CPU form (the same refusals where the arguments exist; every output is required).
+ * Hypotheses: ComputeSim3 for every set: T12, T21 [iterations][16], quat [iterations][4].  (k_sim3_hypotheses and the host tail.) */
+int orbm_sim3_hypotheses(orbm_t *m, const orbm_sim3_problem_t *problem, int iterations, const int32_t *sets, float *T12, float *T21,
+                         float *quat);
+int orbm_sim3_hypotheses_host(const orbm_sim3_problem_t *problem, int iterations, const int32_t *sets, float *T12, float *T21, float *quat);
+/* Check: CheckInliers for nhyp >= 1 caller-supplied transforms T12, T21 [nhyp][16]: counts [nhyp], masks [nhyp][N].  (k_sim3_check.) */
+int orbm_sim3_check(orbm_t *m, const orbm_sim3_problem_t *problem, int nhyp, const float *T12, const float *T21, int32_t *counts,
+                    uint8_t *masks);
+int orbm_sim3_check_host(const orbm_sim3_problem_t *problem, int nhyp, const float *T12, const float *T21, int32_t *counts, uint8_t *masks);
+/* SetRansacParameters (:150-174): the value it leaves in mRansacMaxIts for N kept pairs.  epsilon as float, pow, log and ceil in double,
+ * min_inliers == N gives 1, then max(1, min(nIterations, max_its)). */
+int orbm_sim3_ransac_iterations(double probability, int min_inliers, int max_its, int N);
+
 /* cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, matches, 2) as called by Frame::ComputeStereoFishEyeMatches
  * (Frame.cc:1246): idx2[2i..], dist2[2i..] = train index and distance of the nearest and second nearest train descriptor
  * of query i (-1 where nc < 2).  Equal distances are ordered by train index; the only consumer (the ratio test of
