@@ -65,6 +65,13 @@ struct LiveCount {
   __device__ __forceinline__ int at(int p, int cap) const { return dev ? clamp_count(dev[(size_t)p * stride], cap) : konst; }
 };
 
+// k_octree's code form: the rounds run on nodes that know their cell (depth, ix, iy) of the split grid, down to depth OCT_D
+// (tools/octree_depth_counts.py: the deepest split seen on the bench's streams plus one).  16-bit key counts of every cell of depths
+// OCT_D .. 0, leaves first: depth d starts at entry OCT_PYR_OFF(nIni, d) and holds nIni << 2d cells, cell (ix, iy) at (ix << d) + iy.
+#define OCT_D 5
+#define OCT_PYR_OFF(nIni, d) ((uint32_t)(nIni) * (((1u << (2 * OCT_D + 2)) - (4u << (2 * (d)))) / 3u))
+#define OCT_TABLE_BYTES(nIni) ((size_t)((2u * OCT_PYR_OFF(nIni, 0) + 2u * (uint32_t)(nIni) + 3u) & ~3u))
+
 // Geometry of one pyramid level; filled on the host (orbx_configure), read by every kernel.
 struct LevelGeom {
   int w, h;          // level image size (ORBextractor.cc:1192-1193)
@@ -85,6 +92,7 @@ struct LevelGeom {
   int candBase;      // first dense candidate of this level in a frame's candidate arrays
   int candCap;
   int kpBase, kpCap; // level keypoint arrays (octree output)
+  int octTabX, octTabY; // first byte of this level's column / row code table in FrameParams::octTab (k_octree's code form)
   float scale;       // mvScaleFactor[level]
   float kpsize;      // (float)(int)(PATCH_SIZE*scale), :862
   // resize tables (level >= 1): index into xtab/ytab
@@ -139,6 +147,8 @@ struct FrameParams {
   const uint32_t *resizeRecs;       // k_resize's row-tile records, RESIZE_REC_WORDS each (above), same for every frame; written by the host only
   int totalKp;                      // sum of kpCap
   int octCap;                       // node capacity of the octree kernel
+  int octHead;                      // bytes of k_octree's first LDS region (chcnt / chpos; the code form's counts and map): >= 32 * octCap
+  const uint8_t *octTab;            // k_octree's code tables (LevelGeom::octTabX / octTabY), written by the host only; NULL: the per-key rounds
   const ChainTile *chain;           // k_pyramid_chain's tile records
   int chainBuf0, chainBuf1;         // bytes of its two LDS level buffers (even / odd levels)
   // outputs

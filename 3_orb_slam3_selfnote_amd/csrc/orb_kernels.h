@@ -780,6 +780,9 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
 //  * the winner of a node is max response, first in vKeys order on ties (:745-757) = smallest dense index,
 //    taken with a 64-bit LDS atomicMax over (response, ~index).
 // Candidates are first compacted from the per-cell slot lists into the reference's vToDistributeKeys order.
+// Where the host built the code tables (P.octTab), the rounds touch no key: a key's cell at every depth down to OCT_D follows from
+// its column and its row alone (DivideNode's lines depend on the node's bounds only), so one pass codes and counts the keys and the
+// rounds read the child counts of a node from a pyramid of sums (model + proof-by-test in tests/octree_codes_model.py).
 // ------------------------------------------------------------------------------------------------------------
 #ifdef OCT_STAMPS   // diagnostic builds only (tools/octree_stamps.py): cycles per phase, thread 0 of every workgroup, summed over the rounds
 #define OSTAMP(i) do { const long long t_ = __builtin_readcyclecounter(); if (threadIdx.x == 0 && g_fast_stamps) g_fast_stamps[(size_t)blockIdx.x * 8 + (i)] += (unsigned int)(t_ - ot0); ot0 = t_; } while (0)
@@ -792,7 +795,8 @@ struct OctNode { short ulx, urx, uly, bry; };
 #define OCT_REGKEYS 4096   // keys of a level held in registers (the rest goes through the global cand / knode arrays)
 #endif
 template <int NT, bool CELLS_LDS>
-__global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffScratch) {
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_octree(   // four workgroups of 256 per CU, as before the code form: no more than 128 registers
+FrameParams P, uint32_t *cellOffScratch) {
   extern __shared__ __align__(16) uint8_t smem[];
 #ifdef OCT_STAMPS
   long long ot0 = __builtin_readcyclecounter();
@@ -802,7 +806,7 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
   unsigned long long *best = reinterpret_cast<unsigned long long *>(smem);          // aliases chcnt/chpos
   uint32_t *chcnt = reinterpret_cast<uint32_t *>(smem);                               // 4*CAP
   int32_t *chpos = reinterpret_cast<int32_t *>(smem + 16 * (size_t)CAP);              // 4*CAP
-  OctNode *nodeA = reinterpret_cast<OctNode *>(smem + 32 * (size_t)CAP);
+  OctNode *nodeA = reinterpret_cast<OctNode *>(smem + (size_t)P.octHead);
   OctNode *nodeB = nodeA + CAP;
   uint32_t *cntA = reinterpret_cast<uint32_t *>(nodeB + CAP);
   uint32_t *cntB = cntA + CAP;
@@ -812,6 +816,13 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
   uint32_t *sflag = incl + CAP;                                  // unprocessed flags -> exclusive sums
   uint32_t *sw = sflag + CAP;                                    // scan scratch (NT/64+2)
   __shared__ int shI[8];
+  // Code form (P.octTab): every key is looked up once - its leaf of the depth-OCT_D split grid - and counted
+  // into a leaf histogram; the counts of the coarser cells are sums, the rounds run on the nodes alone (a node knows its cell and
+  // reads its children's counts), and a leaf -> list position map gives the keys their node at the end.  Bins, sums and map take
+  // the place of chcnt / chpos, the nodes' cells that of npos: none of those is live while no key is re-labelled.
+  uint16_t *pyr = reinterpret_cast<uint16_t *>(smem);            // counts, leaves first (OCT_PYR_OFF); the map lies over the leaf bins
+  uint16_t *codeA = reinterpret_cast<uint16_t *>(npos), *codeB = codeA + CAP;   // depth << 13 | ix << 5 | iy
+  bool codes = P.octTab != nullptr;                              // false from the round that has to split a depth-OCT_D node
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   constexpr int NW = NT / 64;
@@ -917,6 +928,35 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
   const int nIni = G.nIni;
   const float hX = G.hX;
   const int Hrect = G.maxBorderY - ORB_MIN_BORDER;
+  if (n > 65535) codes = false;   // the counts are 16 bits wide
+  if (codes) {
+    // the one pass over the keys: leaf code (root and x bits from the column table, y bits from the row table) and leaf histogram
+    uint32_t *bins = reinterpret_cast<uint32_t *>(smem);   // two 16-bit bins per word; no count passes n <= 65535
+    for (int i = tid; i < (nIni << (2 * OCT_D - 1)); i += NT) bins[i] = 0u;
+    if (tid == 0) shI[5] = 0;
+    __syncthreads();
+    const uint8_t *tabX = P.octTab + G.octTabX, *tabY = P.octTab + G.octTabY;
+    const int Wrect = G.maxBorderX - ORB_MIN_BORDER;
+    for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
+      const int x = min((int)(c & 0xfff), Wrect), y = min((int)((c >> 12) & 0xfff), Hrect);
+      nd = ((uint32_t)tabX[x] << OCT_D) | (uint32_t)tabY[y];
+      atomicAdd(&bins[nd >> 1], 1u << ((nd & 1u) << 4));
+    });
+    __syncthreads();
+    // counts of depths OCT_D - 1 .. 0: a cell's four children are two adjacent pairs of the finer grid
+#pragma unroll
+    for (int d = OCT_D - 1; d >= 0; d--) {
+      const uint16_t *fine = pyr + OCT_PYR_OFF(nIni, d + 1);
+      uint16_t *coarse = pyr + OCT_PYR_OFF(nIni, d);
+      for (int e = tid; e < (nIni << (2 * d)); e += NT) {
+        const int ix = e >> d, iy = e & ((1 << d) - 1);
+        const uint32_t w0 = *reinterpret_cast<const uint32_t *>(fine + ((2 * ix) << (d + 1)) + 2 * iy);
+        const uint32_t w1 = *reinterpret_cast<const uint32_t *>(fine + ((2 * ix + 1) << (d + 1)) + 2 * iy);
+        coarse[e] = (uint16_t)((w0 & 0xffffu) + (w0 >> 16) + (w1 & 0xffffu) + (w1 >> 16));
+      }
+      __syncthreads();
+    }
+  } else {
   for (int i = tid; i < nIni; i += NT) chcnt[i] = 0;
   __syncthreads();
   for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
@@ -926,10 +966,11 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
     atomicAdd(&chcnt[r], 1u);
   });
   __syncthreads();
+  }
   if (tid == 0) {
     int L = 0;
     for (int r = 0; r < nIni; r++) {
-      uint32_t cn = chcnt[r];
+      uint32_t cn = codes ? (uint32_t)pyr[OCT_PYR_OFF(nIni, 0) + r] : chcnt[r];
       if (cn > 0) {
         OctNode nd;
         nd.ulx = (short)(int)(hX * (float)r);
@@ -938,14 +979,14 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
         nd.bry = (short)Hrect;
         nodeA[L] = nd;
         cntA[L] = cn;
-        chpos[r] = L;
+        if (codes) codeA[L] = (uint16_t)(r << 5); else chpos[r] = L;
         L++;
       }
     }
     shI[0] = L;
   }
   __syncthreads();
-  for_keys(n, [&](int, uint32_t &, uint32_t &nd) { nd = (uint32_t)chpos[nd]; });
+  if (!codes) for_keys(n, [&](int, uint32_t &, uint32_t &nd) { nd = (uint32_t)chpos[nd]; });
   int L = shI[0];
   __syncthreads();
   OSTAMP(1);
@@ -955,13 +996,54 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
   bool careful = false;
   OctNode *nodes = nodeA, *nodesN = nodeB;
   uint32_t *cnts = cntA, *cntsN = cntB;
+  uint16_t *ncode = codeA, *ncodeN = codeB;
+  // code form: every node of the list writes its list position over its leaves (each leaf once; leaves without keys belong to no
+  // node and are not read), then the keys exchange their leaf code for the position
+  auto label_keys = [&]() {
+    for (int w = tid; w < 4 * L; w += NT) {
+      const int i = w >> 2, part = w & 3;
+      const uint32_t code = ncode[i];
+      const int up = OCT_D - (int)(code >> 13), side = 1 << up;
+      const int x0 = (int)((code >> 5) & 255u) << up, y0 = (int)(code & 31u) << up;
+      if (up == 0) { if (part == 0) pyr[(x0 << OCT_D) + y0] = (uint16_t)i; }
+      else
+        for (int cx = part; cx < side; cx += 4) {
+          uint32_t *col = reinterpret_cast<uint32_t *>(pyr + ((x0 + cx) << OCT_D) + y0);
+          for (int j = 0; j < side / 2; j++) col[j] = (uint32_t)i * 0x10001u;
+        }
+    }
+    __syncthreads();
+    for_keys(n, [&](int, uint32_t &, uint32_t &nd) { nd = (uint32_t)pyr[nd]; });
+    __syncthreads();
+  };
+  // key counts of node i's four children: the finer grid's cells in the code form, else what this round's key pass counted
+  auto child_counts = [&](int i, uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3) {
+    if (codes) {
+      const uint32_t code = ncode[i];
+      const int d = min((int)(code >> 13), OCT_D - 1), ix = (int)((code >> 5) & 255u), iy = (int)(code & 31u);
+      const uint16_t *fine = pyr + OCT_PYR_OFF(nIni, d + 1);
+      const uint32_t w0 = *reinterpret_cast<const uint32_t *>(fine + ((2 * ix) << (d + 1)) + 2 * iy);
+      const uint32_t w1 = *reinterpret_cast<const uint32_t *>(fine + ((2 * ix + 1) << (d + 1)) + 2 * iy);
+      c0 = w0 & 0xffffu; c1 = w1 & 0xffffu; c2 = w0 >> 16; c3 = w1 >> 16;
+    } else {
+      c0 = chcnt[i * 4]; c1 = chcnt[i * 4 + 1]; c2 = chcnt[i * 4 + 2]; c3 = chcnt[i * 4 + 3];
+    }
+  };
+  auto child_nodes = [&](int i) -> uint32_t {
+    uint32_t c0, c1, c2, c3;
+    child_counts(i, c0, c1, c2, c3);
+    return (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
+  };
   for (int guard = 0; guard < 64; guard++) {
     const int prevSize = L;
-    for (int i = tid; i < 4 * L; i += NT) chcnt[i] = 0;
+    // deeper than OCT_D: some node with more than one key is a leaf of the grid (shI[5], set when the node was made), so this round
+    // and the ones after it count and re-label per key
+    if (codes && shI[5] != 0) { label_keys(); codes = false; }
+    if (!codes) for (int i = tid; i < 4 * L; i += NT) chcnt[i] = 0;
     if (tid == 0) { shI[1] = 0; shI[2] = 0x7fffffff; }
     __syncthreads();
     // child key counts of every expandable node
-    for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
+    if (!codes) for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
       if (cnts[nd] > 1) {
         OctNode o = nodes[nd];
         int x = c & 0xfff, y = (c >> 12) & 0xfff;
@@ -980,7 +1062,7 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
     if (fusedScan) {
       for (int i = tid; i < L; i += NT) {
         const bool e = cnts[i] > 1;
-        const uint32_t c = e ? (chcnt[i * 4] > 0) + (chcnt[i * 4 + 1] > 0) + (chcnt[i * 4 + 2] > 0) + (chcnt[i * 4 + 3] > 0) : 0u;
+        const uint32_t c = e ? child_nodes(i) : 0u;
         sflag[i] = (e ? 1u : 0u) | (c << 10) | ((e ? 0u : 1u) << 22);
       }
       __syncthreads();
@@ -1027,7 +1109,7 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
     for (int i = tid; i < L; i += NT) {
       int r = rankOf[i];
       if (r >= 0) {
-        uint32_t c = (chcnt[i * 4] > 0) + (chcnt[i * 4 + 1] > 0) + (chcnt[i * 4 + 2] > 0) + (chcnt[i * 4 + 3] > 0);
+        uint32_t c = child_nodes(i);
         incl[r] = c;
       }
     }
@@ -1038,7 +1120,7 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
       for (int i = tid; i < L; i += NT) {
         int r = rankOf[i];
         if (r >= 0) {
-          uint32_t c = (chcnt[i * 4] > 0) + (chcnt[i * 4 + 1] > 0) + (chcnt[i * 4 + 2] > 0) + (chcnt[i * 4 + 3] > 0);
+          uint32_t c = child_nodes(i);
           int after = L + (int)(incl[r] + c) - (r + 1);
           if (after >= N) atomicMin(&shI[2], r);
         }
@@ -1053,7 +1135,7 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
       bool proc = r >= 0 && r <= mstar;
       sflag[i] = proc ? 0u : 1u;
       if (r == mstar && r >= 0) {
-        uint32_t c = (chcnt[i * 4] > 0) + (chcnt[i * 4 + 1] > 0) + (chcnt[i * 4 + 2] > 0) + (chcnt[i * 4 + 3] > 0);
+        uint32_t c = child_nodes(i);
         shI[4] = (int)(incl[r] + c);
       }
     }
@@ -1077,8 +1159,11 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
         proc = r >= 0 && r <= mstar; childrenBefore = proc ? incl[r] : 0u; unprocBefore = sflag[i];
       }
       if (proc) {
-        uint32_t c0 = chcnt[i * 4], c1 = chcnt[i * 4 + 1], c2 = chcnt[i * 4 + 2], c3 = chcnt[i * 4 + 3];
+        uint32_t c0, c1, c2, c3;
+        child_counts(i, c0, c1, c2, c3);
         uint32_t c = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
+        const uint32_t code = codes ? (uint32_t)ncode[i] : 0u;
+        const uint32_t dN = (code >> 13) + 1u, ixN = 2u * ((code >> 5) & 255u), iyN = 2u * (code & 31u);   // the children's depth, first cell
         int pos = Eproc - (int)(childrenBefore + c);  // block start; inside the block n4,n3,n2,n1
         int hx = (o.urx - o.ulx + 1) >> 1, hy = (o.bry - o.uly + 1) >> 1;
         int nexp = 0;
@@ -1092,25 +1177,28 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
             ch.uly = (short)((q & 2) ? o.uly + hy : o.uly);
             ch.bry = (short)((q & 2) ? o.bry : o.uly + hy);
             if (pos < CAP) { nodesN[pos] = ch; cntsN[pos] = cc[q]; }
-            chpos[i * 4 + q] = pos;
+            if (codes) { if (pos < CAP) ncodeN[pos] = (uint16_t)((dN << 13) | ((ixN + (q & 1)) << 5) | (iyN + (q >> 1))); }
+            else chpos[i * 4 + q] = pos;
             nexp += cc[q] > 1 ? 1 : 0;
             pos++;
           } else {
-            chpos[i * 4 + q] = -1;
+            if (!codes) chpos[i * 4 + q] = -1;
           }
         }
         if (nexp) atomicAdd(&shI[1], nexp);
-        npos[i] = -1;
+        if (codes) { if (nexp && dN == OCT_D) shI[5] = 1; }
+        else npos[i] = -1;
       } else {
         int pos = Eproc + (int)unprocBefore;
         if (pos < CAP) { nodesN[pos] = o; cntsN[pos] = cnts[i]; }
-        npos[i] = pos;
+        if (codes) { if (pos < CAP) ncodeN[pos] = ncode[i]; }
+        else npos[i] = pos;
       }
     }
     __syncthreads();
     OSTAMP(4);
     // re-label the keys
-    for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
+    if (!codes) for_keys(n, [&](int, uint32_t &c, uint32_t &nd) {
       int np = npos[nd];
       if (np < 0) {
         OctNode o = nodes[nd];
@@ -1126,11 +1214,13 @@ __global__ __launch_bounds__(NT) void k_octree(FrameParams P, uint32_t *cellOffS
     OSTAMP(5);
     { OctNode *t = nodes; nodes = nodesN; nodesN = t; }
     { uint32_t *t = cnts; cnts = cntsN; cntsN = t; }
+    { uint16_t *t = ncode; ncode = ncodeN; ncodeN = t; }
     L = min(Lnew, CAP);
     if (Lnew >= N || Lnew == prevSize) break;                      // :667, :731
     if (!careful && Lnew + nToExpand * 3 > N) careful = true;      // :671
   }
 
+  if (codes) label_keys();
   // ---- D. best key per node, list order out, lapping ranks (ORBextractor.cc:742-758, :1169-1178) ----
   for (int i = tid; i < L; i += NT) best[i] = 0ull;
   __syncthreads();

@@ -96,6 +96,8 @@ struct orbx_handle {
   std::vector<LevelGeom> geom;
   size_t pyr_fs = 0, blur_fs = 0, slot_fs = 0;
   bool octCellsLds = false;
+  bool octCodes = false;   // k_octree runs its rounds on the nodes alone (code tables in d_octTab)
+  size_t octHead = 0;      // bytes of k_octree's first LDS region: chcnt / chpos, or the code form's counts and map
   int chainTiles = 0, chainBuf0 = 0, chainBuf1 = 0;   // k_pyramid_chain (single-frame calls); chainTiles = 0: not available
   size_t chainLds = 0;
   size_t octLds = 0;
@@ -103,7 +105,7 @@ struct orbx_handle {
   int maxKeypoints = 0;
   // device memory
   DevBuf d_pyr, d_blur, d_cellCnt, d_cellOff, d_slots, d_cand, d_knode, d_lkp, d_lrank, d_lcnt, d_candCnt, d_fastRecs, d_resizeRecs, d_tiles, d_xtab,
-      d_ytab, d_disc, d_chain;
+      d_ytab, d_disc, d_chain, d_octTab;
   DevBuf d_img, d_okps;  // staging for the host entry point (d_okps: counts + keypoints + descriptors, one block)
   hipStream_t stream = nullptr;
   float host_us[4] = {0, 0, 0, 0};          // orbx_extract's last call: staging copy, submission, wait, copy-out (orbx_get_host_us)
@@ -316,7 +318,7 @@ void orbx_destroy(orbx_t *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   DevBuf *bufs[] = {&h->d_pyr, &h->d_blur, &h->d_cellCnt, &h->d_cellOff, &h->d_slots, &h->d_cand, &h->d_knode, &h->d_lkp,
-                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_fastRecs, &h->d_resizeRecs, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_img, &h->d_okps};
+                    &h->d_lrank, &h->d_lcnt, &h->d_candCnt, &h->d_fastRecs, &h->d_resizeRecs, &h->d_tiles, &h->d_xtab, &h->d_ytab, &h->d_disc, &h->d_chain, &h->d_octTab, &h->d_img, &h->d_okps};
   for (DevBuf *b : bufs) b->release();
   for (DevBuf &b : h->stereo) b.release();
   for (DevBuf &b : h->stereo_batch) b.release();
@@ -693,7 +695,55 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   // k_octree LDS: node arrays (72 B per node) + scan scratch, plus the level's cell offsets when they fit
   int maxCells = 1;
   for (int l = 0; l < nl; l++) maxCells = std::max(maxCells, g[l].nCols * g[l].nRows);
-  size_t lds = 72 * (size_t)octCap + 128;
+  // k_octree's code form: per level one byte per column and per row of the detection rectangle - the root and
+  // the OCT_D x bits, the OCT_D y bits of the key's path through DivideNode's splits (ORBextractor.cc:479-535), walked with the
+  // kernel's own interval arithmetic.  A split line is ul + ((ur - ul + 1) >> 1) and a key goes right / down when it is not below
+  // it; an interval of width 1 splits into widths 1 and 0, one of width 0 keeps itself as its right child: the walk just goes on,
+  // the bits are what the comparisons give.  The leaf bins, the count pyramid and the leaf map live in the LDS of chcnt / chpos
+  // (32 * octCap bytes): where they fit there - the bench's configurations - octLds is what it is without them; a configuration
+  // with fewer nodes gets that head region enlarged as long as the whole stays small (32 KiB), any other keeps the per-key rounds.
+  {
+    int maxIni = 0;
+    for (int l = 0; l < nl; l++) maxIni = std::max(maxIni, g[l].nIni);   // (a level with more than 65535 keys: the kernel's own check)
+    size_t limit = ORB_LDS_LIMIT;
+    if (const char *e = getenv("ORBHIP_OCTREE_TABLE_LIMIT")) limit = (size_t)strtoul(e, nullptr, 10);   // tests: a bound the tables do not fit
+    const size_t tabBytes = align_up(OCT_TABLE_BYTES(std::max(maxIni, 1)), 16);
+    h->octCodes = maxIni >= 1 && (maxIni << OCT_D) <= 256 && octCap <= 65535 && tabBytes <= limit;
+    h->octHead = 32 * (size_t)octCap;
+    if (h->octCodes && tabBytes > h->octHead) {
+      if (tabBytes + 40 * (size_t)octCap + 128 + 4 * ((size_t)maxCells + 1) <= 32 * 1024) h->octHead = tabBytes;
+      else h->octCodes = false;
+    }
+    if (h->octCodes) {
+      std::vector<uint8_t> tab;
+      auto walk = [](int v, int ul, int ur) {
+        int bits = 0;
+        for (int d = 0; d < OCT_D; d++) {
+          const int half = (ur - ul + 1) >> 1;   // ceil(/2), :481-482
+          const int b = v < ul + half ? 0 : 1;
+          if (b) ul = ul + half; else ur = ul + half;
+          bits = (bits << 1) | b;
+        }
+        return bits;
+      };
+      for (int l = 0; l < nl; l++) {
+        LevelGeom &G = g[l];
+        G.octTabX = G.octTabY = (int)tab.size();
+        if (G.nIni < 1) continue;
+        const int Wrect = G.maxBorderX - ORB_MIN_BORDER, Hrect = G.maxBorderY - ORB_MIN_BORDER;
+        for (int x = 0; x <= Wrect; x++) {   // one entry more than the rectangle has columns: the kernel clamps to it
+          const int r = std::min(std::max((int)((float)x / G.hX), 0), G.nIni - 1);   // vpIniNodes[kp.pt.x/hX], :567
+          tab.push_back((uint8_t)((r << OCT_D) | walk(x, (int)(G.hX * (float)r), (int)(G.hX * (float)(r + 1)))));
+        }
+        G.octTabY = (int)tab.size();
+        for (int y = 0; y <= Hrect; y++) tab.push_back((uint8_t)walk(y, 0, Hrect));
+      }
+      h->geom = g;
+      XCHECK(h, h->d_octTab.reserve(std::max<size_t>(tab.size(), 1)));
+      if (!tab.empty()) XCHECK(h, copy_on(h->stream, h->d_octTab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    }
+  }
+  size_t lds = h->octHead + 40 * (size_t)octCap + 128;
   if (lds > 160 * 1024 - 256) { h->err = "nfeatures too large for the LDS-resident octree"; return ORBX_E_ARG; }
   h->octCellsLds = lds + 4 * ((size_t)maxCells + 1) <= 96 * 1024;
   if (h->octCellsLds) lds += 4 * ((size_t)maxCells + 1);
@@ -792,6 +842,8 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   P.magicKpBlk = magic_div((uint32_t)describeGroups);
   P.totalKp = h->totalKp;
   P.octCap = h->octCap;
+  P.octHead = (int)h->octHead;
+  P.octTab = h->octCodes ? (const uint8_t *)h->d_octTab.p : nullptr;
   P.chain = (const ChainTile *)h->d_chain.p; P.chainBuf0 = h->chainBuf0; P.chainBuf1 = h->chainBuf1;
   P.out_kps = d_kps;
   P.out_desc = d_desc;
@@ -842,8 +894,8 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
     for (int f = 0; f < nframes; f++) aligned0 += (((uintptr_t)(d_images + (size_t)f * frame_stride) | (uintptr_t)stride) & 3u) == 0;
     const LevelGeom &G0 = h->geom[0];
     const int blur0dma = G0.w >= 160 && G0.h >= 40 && (G0.w & 15) == 0 ? aligned0 : 0;
-    fprintf(stderr, "orbhip: extract nframes %d pyramid %s octree %d/%s aligned0 %d blur0dma %d describe %d\n", nframes, pyrForm.c_str(), wide ? 1024 : 256,
-            h->octCellsLds ? "lds" : "global", aligned0, blur0dma, wide ? 1 : ORB_DESCRIBE_K);
+    fprintf(stderr, "orbhip: extract nframes %d pyramid %s octree %d/%s aligned0 %d blur0dma %d describe %d rounds %s octLds %zu octCap %d\n", nframes, pyrForm.c_str(), wide ? 1024 : 256,
+            h->octCellsLds ? "lds" : "global", aligned0, blur0dma, wide ? 1 : ORB_DESCRIBE_K, h->octCodes ? "codes" : "keys", h->octLds, h->octCap);
   }
   h->last = P;
   h->have_last = true;
