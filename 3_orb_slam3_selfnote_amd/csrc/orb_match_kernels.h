@@ -1795,8 +1795,9 @@ __global__ __launch_bounds__(256) void k_triangulation_match_neighbours(TriNbPar
 // the same vocabulary node that passes the gates in front of the predicate - no map point (:1083), stereo filter (:1088-1090),
 // distance <= TH_LOW (:1096), epipole distance (:1105-1113) - as keys dist << 16 | (0xffff - position).  Two consumers:
 //   * orbm_search_for_triangulation_pred: the host orders each item's segment and the caller's predicate picks;
-//   * orbm_search_for_triangulation_kb8: k_triangulation_kb8_predicate evaluates KannalaBrandt8's test on every key of the compact
-//     list (key_item = the item of each key) and keeps the minimum accepted key per item.
+//   * orbm_search_for_triangulation_kb8 and the one-call forms (k_triangulation_candidates_neighbours below):
+//     k_triangulation_kb8_predicate_neighbours evaluates KannalaBrandt8's test on every key of the compact list (key_item = the item
+//     of each key) and keeps the minimum accepted key per item.
 // One wavefront per item; the segment of the output buffer comes from one atomicAdd per wavefront, a segment that would not fit is
 // counted but not written.
 struct TriCandParams {
@@ -1926,18 +1927,6 @@ struct TriKb8Consts {             // constant per call (per neighbour of a one-c
   float T12[4][12], Tcw2[4][12];  // [R12 | t12] and rig_Tcw2 of it, pairs ll, lr, rl, rr (a keyframe pair without second cameras: [0])
   float cams1[2][8], cams2[2][8]; // KannalaBrandt8 parameters of mpCamera, mpCamera2 of the two keyframes
 };
-struct TriKb8Params {
-  const float *kp1, *kp2;         // keypoint AoS (7 floats each); rigs: [mvKeys; mvKeysRight]
-  const int32_t *node_idx2;
-  const TriItem *items; int nitems;
-  const uint32_t *keys; const int32_t *key_item; const int32_t *total; int cap;
-  const TriKb8Consts *consts;
-  float sigma2_1[ORBX_MAX_LEVELS], sigma2_2[ORBX_MAX_LEVELS];
-  int n_left1, n_left2;           // -1: no second camera
-  int bCoarse;
-  uint32_t *best;                 // [nitems], pre-filled with 0xffffffff
-  int32_t *matches12;             // pre-filled with -1
-};
 
 // The test on the pair (idx1, idx2): camera pair and pose by (bRight1, bRight2)
 __device__ __forceinline__ bool tri_kb8_accepts(const TriKb8Consts &K, const float *kp1, const float *kp2, int idx1, int idx2, int n_left1, int n_left2,
@@ -1951,31 +1940,7 @@ __device__ __forceinline__ bool tri_kb8_accepts(const TriKb8Consts &K, const flo
          0.0001f;
 }
 
-__global__ __launch_bounds__(256) void k_triangulation_kb8_predicate(TriKb8Params T) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= min(*T.total, T.cap)) return;
-  const uint32_t key = T.keys[c];
-  const int it = T.key_item[c];
-  bool ok = T.bCoarse != 0;
-  if (!ok) {
-    const TriItem item = T.items[it];
-    const int idx2 = T.node_idx2[item.start2 + (0xffff - (int)(key & 0xffffu))];
-    ok = tri_kb8_accepts(*T.consts, T.kp1, T.kp2, item.idx1, idx2, T.n_left1, T.n_left2, T.sigma2_1, T.sigma2_2);
-  }
-  if (ok) atomicMin(&T.best[it], key);
-}
-
-// best[item] -> vMatches12[idx1] (:1160)
-__global__ __launch_bounds__(256) void k_triangulation_kb8_result(TriKb8Params T) {
-  const int it = blockIdx.x * 256 + threadIdx.x;
-  if (it >= T.nitems) return;
-  const uint32_t best = T.best[it];
-  if (best == 0xffffffffu) return;
-  const TriItem item = T.items[it];
-  T.matches12[item.idx1] = T.node_idx2[item.start2 + (0xffff - (int)(best & 0xffffu))];
-}
-
-// The same two kernels over the one key list of all neighbours: a candidate's item names its neighbour, whose TriKb8Consts, scale
+// The two kernels over the one key list of all neighbours: a candidate's item names its neighbour, whose TriKb8Consts, scale
 // table and arrays the lane reads (neighbours mix inside a wavefront here, so these are vector loads).
 struct TriKb8NbParams {
   TriNbParams in;

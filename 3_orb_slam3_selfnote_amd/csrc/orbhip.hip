@@ -17,6 +17,7 @@
 #include <vector>
 #include <algorithm>
 #include <type_traits>
+#include <initializer_list>
 #include <mutex>
 #include <map>
 #include <chrono>
@@ -165,22 +166,11 @@ static hipError_t join_last(orbx_handle *h) {
 // a per-launch "set to this launch's size" against each other's launches.  It is raised once per device, to the CU's whole
 // 160 KiB, for every kernel that can ask for more than the 64 KiB default; launches only check their own size against it.
 #define ORB_LDS_LIMIT (160 * 1024)
-static hipError_t raise_lds_limits(int device) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  std::lock_guard<std::mutex> lock(mu);
+struct LdsOnce { std::mutex mu; bool done[64] = {}; };   // the once-table of one kernel list
+static hipError_t raise_lds_once(LdsOnce &once, int device, std::initializer_list<const void *> fns) {
+  std::lock_guard<std::mutex> lock(once.mu);
   if (device < 0 || device >= 64) return hipErrorInvalidDevice;
-  if (done[device]) return hipSuccess;
-  const void *fns[] = {reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_PLAIN, 1>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_UR, 1>),
-                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FISHEYE, 1>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FUSE, 1>),
-                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_PLAIN, 4>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_UR, 4>),
-                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FISHEYE, 4>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FUSE, 4>),
-                       reinterpret_cast<const void *>(&k_octree<256, true>), reinterpret_cast<const void *>(&k_octree<256, false>),
-                       reinterpret_cast<const void *>(&k_octree<1024, true>), reinterpret_cast<const void *>(&k_octree<1024, false>),
-                       reinterpret_cast<const void *>(&k_resize),
-                       reinterpret_cast<const void *>(&k_match_resolve<Key32, true>), reinterpret_cast<const void *>(&k_match_resolve<Key32, false>),
-                       reinterpret_cast<const void *>(&k_match_resolve<Key64, true>), reinterpret_cast<const void *>(&k_match_resolve<Key64, false>),
-                       reinterpret_cast<const void *>(&k_match_resolve<Key32, true, true>), reinterpret_cast<const void *>(&k_pyramid_chain)};
+  if (once.done[device]) return hipSuccess;
   for (const void *fn : fns) {
     hipFuncAttributes a;
     hipError_t e = hipFuncGetAttributes(&a, fn);
@@ -189,8 +179,21 @@ static hipError_t raise_lds_limits(int device) {
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, room);
     if (e != hipSuccess) return e;
   }
-  done[device] = true;
+  once.done[device] = true;
   return hipSuccess;
+}
+static hipError_t raise_lds_limits(int device) {
+  static LdsOnce once;
+  return raise_lds_once(once, device, {reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_PLAIN, 1>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_UR, 1>),
+                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FISHEYE, 1>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FUSE, 1>),
+                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_PLAIN, 4>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_UR, 4>),
+                       reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FISHEYE, 4>), reinterpret_cast<const void *>(&k_match_walk<Key32, SCAN_FUSE, 4>),
+                       reinterpret_cast<const void *>(&k_octree<256, true>), reinterpret_cast<const void *>(&k_octree<256, false>),
+                       reinterpret_cast<const void *>(&k_octree<1024, true>), reinterpret_cast<const void *>(&k_octree<1024, false>),
+                       reinterpret_cast<const void *>(&k_resize),
+                       reinterpret_cast<const void *>(&k_match_resolve<Key32, true>), reinterpret_cast<const void *>(&k_match_resolve<Key32, false>),
+                       reinterpret_cast<const void *>(&k_match_resolve<Key64, true>), reinterpret_cast<const void *>(&k_match_resolve<Key64, false>),
+                       reinterpret_cast<const void *>(&k_match_resolve<Key32, true, true>), reinterpret_cast<const void *>(&k_pyramid_chain)});
 }
 
 // The device builds of the scalar replicas on n items (orbx_logf_device, orbx_tanf_device, orbx_cosf_device .. orbx_fast_atan2_device):
@@ -1338,7 +1341,7 @@ struct orbm_handle {
   hipStream_t stream = nullptr;
   int scan_mode = 0;        // SCAN_AUTO / SCAN_DENSE / SCAN_WALK of the projection searches (orbm_set_scan_mode)
   int hamming_engine = 2;   // orbm_set_hamming_engine: 0 vector ALU, 1 k_match_scan_mfma, 2 (default) + lists built inside k_match_resolve for all-open pairs
-  DevBuf d_block;     // inputs + outputs of one host-pointer entry point, one block (see stage)
+  DevBuf d_block;     // inputs + outputs of one host-pointer entry point, one block (see Staging)
   void *pin = nullptr; size_t pin_bytes = 0;   // its pinned host mirror
   DevBuf d_topk;      // per-query candidate lists of the scan / walk, for the resolve (all projection searches)
   DevBuf d_rank;      // k_match_rank's two tables (accumulator seeds, Key32 tie-break bits) for k_match_scan_mfma
@@ -1380,55 +1383,57 @@ static void *getenv_ptr(const char *name) { const char *e = getenv(name); return
 // copied into the pinned mirror m->pin and uploaded with one H2D copy (a dozen pageable copies would each stage and synchronise
 // on their own).  A part without a source reserves an output-only region.  The mirror spans the outputs too only when the caller
 // downloads them through it (mirror_outputs); a large output copied straight to the caller takes no pinned memory.
-// dev[i]: device address of part i, nullptr for an empty part.
-struct Part { const void *src; size_t bytes; };
-static constexpr size_t stage_span(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // what a part takes of the block
-
-struct Parts { const Part *b, *e; const Part *begin() const { return b; } const Part *end() const { return e; } };
-static int stage(orbm_handle *m, hipStream_t s, const Part *first, size_t nparts, void **dev, bool mirror_outputs) {
-  size_t total = 0, upload = 0;
-  for (const Part &p : Parts{first, first + nparts}) {   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
-    if (p.bytes > (SIZE_MAX >> 3) - total) { m->err = "staging: inputs too large"; return ORBX_E_HIP; }
-    total += stage_span(p.bytes);
-    if (p.src) upload = total;
-  }
-  const size_t mirror = mirror_outputs ? total : upload;
-  if (m->pin_bytes < mirror) {
-    if (m->pin) (void)hipHostFree(m->pin);
-    m->pin = nullptr; m->pin_bytes = 0;
-    MCHECK(m, hipHostMalloc(&m->pin, 2 * mirror, hipHostMallocDefault));   // grown rarely: a re-allocation costs tens of milliseconds
-    m->pin_bytes = 2 * mirror;
-  }
-  MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
-  size_t off = 0;
-  for (const Part &p : Parts{first, first + nparts}) {
-    if (p.src && p.bytes) memcpy((uint8_t *)m->pin + off, p.src, p.bytes);
-    *dev++ = p.bytes ? (uint8_t *)m->d_block.p + off : nullptr;
-    off += stage_span(p.bytes);
-  }
-  if (upload) MCHECK(m, hipMemcpyAsync(m->d_block.p, m->pin, upload, hipMemcpyHostToDevice, s));
-  return 0;
-}
-
-static int stage(orbm_handle *m, hipStream_t s, std::initializer_list<Part> parts, void **dev, bool mirror_outputs = false) {
-  return stage(m, s, parts.begin(), parts.size(), dev, mirror_outputs);
-}
-
-// The pinned-mirror address of a device address inside m->d_block (entry points staged with mirror_outputs)
-static void *mirror_of(orbm_handle *m, const void *d) { return (uint8_t *)m->pin + ((const uint8_t *)d - (const uint8_t *)m->d_block.p); }
-
-// A staged block with typed parts: add() returns the part's handle; after upload() dev() / host() are its device / pinned-mirror address.
+// add() / out() return the part's typed handle; its offset in the block is known from then on (offset(): what the records of the
+// one-call entries store), after upload() dev() / host() are its device / pinned-mirror address, dev() nullptr for an empty part.
 template <class T> struct PartOf { int i; };
 struct Staging {
+  struct Slot { const void *src; size_t bytes, off; };
   orbm_handle *m;
   int n = 0;
-  Part parts[32];   // the largest block (the rig local-map form) has 29 parts; no allocation on the way
-  void *d[32];
-  template <class T> PartOf<T> add(const T *src, size_t count) { assert(n < 32); parts[n] = {src, sizeof(T) * count}; return {n++}; }
+  size_t total = 0, up = 0;   // bytes of the block so far; of its front that ends with the last part that has a source
+  bool too_large = false;
+  Slot inl[32];               // the largest per-frame block (the rig local-map form) has 29 parts: no allocation on that way
+  std::vector<Slot> more;     // the one-call entries, a few parts per neighbour, target or candidate
+  const Slot &at(int i) const { return i < 32 ? inl[i] : more[(size_t)i - 32]; }
+  template <class T> PartOf<T> add(const T *src, size_t count) {
+    const size_t bytes = sizeof(T) * count;   // sizes come from the caller's counts: one beyond any allocation fails as that allocation would
+    const bool fits = bytes <= (SIZE_MAX >> 3) - total;
+    if (!fits) too_large = true;              // upload() refuses; until then the handle names an empty part
+    const Slot p{src, fits ? bytes : 0, total};
+    if (n < 32) inl[n] = p;
+    else { if (more.empty()) more.reserve(96); more.push_back(p); }   // one allocation serves K = 20 neighbours of six parts
+    total += (p.bytes + 255) & ~(size_t)255;  // what a part takes of the block
+    if (src) up = total;
+    return {n++};
+  }
   template <class T> PartOf<T> out(size_t count) { return add((const T *)nullptr, count); }
-  int upload(hipStream_t s) { return stage(m, s, parts, (size_t)n, d, true); }
-  template <class T> T *dev(PartOf<T> h) const { return (T *)d[h.i]; }
-  template <class T> T *host(PartOf<T> h) const { return (T *)mirror_of(m, d[h.i]); }
+  int upload(hipStream_t s, bool mirror_outputs = true) {
+    if (too_large) { m->err = "staging: inputs too large"; return ORBX_E_HIP; }
+    const size_t mirror = mirror_outputs ? total : up;
+    if (m->pin_bytes < mirror) {
+      if (m->pin) (void)hipHostFree(m->pin);
+      m->pin = nullptr; m->pin_bytes = 0;
+      MCHECK(m, hipHostMalloc(&m->pin, 2 * mirror, hipHostMallocDefault));   // grown rarely: a re-allocation costs tens of milliseconds
+      m->pin_bytes = 2 * mirror;
+    }
+    MCHECK(m, m->d_block.reserve(m->d_block.bytes >= total ? total : 2 * total));
+    for (int i = 0; i < n; i++)
+      if (at(i).src && at(i).bytes) memcpy((uint8_t *)m->pin + at(i).off, at(i).src, at(i).bytes);
+    if (up) MCHECK(m, hipMemcpyAsync(m->d_block.p, m->pin, up, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  const uint8_t *block() const { return (const uint8_t *)m->d_block.p; }
+  template <class T> size_t offset(PartOf<T> h) const { return at(h.i).off; }
+  template <class T> T *dev(PartOf<T> h) const { return at(h.i).bytes ? (T *)((uint8_t *)m->d_block.p + at(h.i).off) : nullptr; }
+  template <class T> T *host(PartOf<T> h) const { return (T *)((uint8_t *)m->pin + at(h.i).off); }
+  // Adjacent parts as one span, from the start of part a to the end of part b: down into the mirror in one copy, or filled with one byte
+  template <class A, class B> size_t span(PartOf<A> a, PartOf<B> b) const { return at(b.i).off + at(b.i).bytes - at(a.i).off; }
+  template <class A, class B> hipError_t download(hipStream_t s, PartOf<A> a, PartOf<B> b) const {
+    return hipMemcpyAsync((uint8_t *)m->pin + at(a.i).off, block() + at(a.i).off, span(a, b), hipMemcpyDeviceToHost, s);
+  }
+  template <class A, class B> hipError_t fill(hipStream_t s, PartOf<A> a, PartOf<B> b, int byte) const {
+    return hipMemsetAsync((uint8_t *)m->d_block.p + at(a.i).off, byte, span(a, b), s);
+  }
 };
 
 // The structs the host-pointer forms stage: stage_*() appends the parts (absent arrays as empty ones), on_device() is the device-side struct.
@@ -1493,6 +1498,15 @@ struct SearchOpts {
 template <int V> using ScanKind = std::integral_constant<int, V>;
 
 // ---- helpers of the C entry points below that are templates (C++ linkage) ----------------------------------------------------
+// A refusal of a one-call entry: m->err names item j of the entry's kind ("neighbour 3: ..."), j < 0 the call as a whole; a kind of NULL
+// never names an item (the pair forms).
+struct Refuse {
+  orbm_handle *m; const char *kind;
+  int operator()(int j, const char *why) const {
+    m->err = j < 0 || !kind ? std::string(why) : std::string(kind) + " " + std::to_string(j) + ": " + why;
+    return ORBX_E_ARG;
+  }
+};
 // Rotation-consistency check of every matcher with checkOri (e.g. ORBmatcher.cc:2177-2185 + :2263-2286): a match goes into the bin
 // of the angle difference of its two keypoints (rot_bin); matches outside the three fullest bins (three_maxima) are pruned.  What an id
 // is and what pruning does to it stay with the caller.
@@ -1838,16 +1852,17 @@ int orbm_search_by_projection_batch_device(orbm_t *m, const orbm_frame_t *f, int
                       nnratio, th_dist, use_second, d_slot, d_slot_obs, d_moq, d_bd, d_nm, (hipStream_t)stream_, o);   // verbatim: NULL is the device's default stream
 }
 
-// The tail of a host search whose outputs were staged as [first .. d_nm]: that range comes down through the pinned mirror in one copy
+// The tail of a host search whose outputs were staged as [slot .. nm] (the one count): that range comes down through the pinned mirror in one copy
 // and one synchronisation; slot / slot_obs (n entries; nothing when n == 0) are copied out and the match count is returned.
-static int download_slots(orbm_t *m, hipStream_t s, void *first, void *d_slot, void *d_sobs, void *d_nm, int n, int32_t *slot, uint8_t *slot_obs) {
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, first), first, (uint8_t *)d_nm + sizeof(int32_t) - (uint8_t *)first, hipMemcpyDeviceToHost, s));
+static int download_slots(orbm_t *m, hipStream_t s, const Staging &S, PartOf<int32_t> hslot, PartOf<uint8_t> hsobs, PartOf<int32_t> hnm, int n,
+                          int32_t *slot, uint8_t *slot_obs) {
+  MCHECK(m, S.download(s, hslot, hnm));
   MCHECK(m, hipStreamSynchronize(s));
   int32_t nm = 0;
   if (n > 0) {
-    memcpy(slot, mirror_of(m, d_slot), sizeof(int32_t) * (size_t)n);
-    memcpy(slot_obs, mirror_of(m, d_sobs), (size_t)n);
-    memcpy(&nm, mirror_of(m, d_nm), sizeof(nm));
+    memcpy(slot, S.host(hslot), sizeof(int32_t) * (size_t)n);
+    memcpy(slot_obs, S.host(hsobs), (size_t)n);
+    nm = *S.host(hnm);
   }
   return nm;
 }
@@ -1902,7 +1917,7 @@ static int search_host(orbm_t *m, const orbm_frame_t *f, const orbm_queries_t *q
   const int rs = search_batch(m, &df, {n, nullptr, 0, n}, &dq, {nq, nullptr, 0, nq}, 1, nnratio, th_dist, use_second, S.dev(dslot), S.dev(dsobs),
                               S.dev(moq), S.dev(bd), S.dev(nmp), s, o);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, S.dev(dslot), S.dev(dslot), S.dev(dsobs), S.dev(nmp), n, slot, slot_obs);
+  const int nm = download_slots(m, s, S, dslot, dsobs, nmp, n, slot, slot_obs);
   if (nm < 0) return nm;
   if (match_of_query) memcpy(match_of_query, S.host(moq), sizeof(int32_t) * NQ);
   if (best_dist) memcpy(best_dist, S.host(bd), sizeof(int32_t) * NQ);
@@ -2131,7 +2146,7 @@ static int search_last_frame_host(orbm_t *m, const orbm_frame_t *cur, const floa
   const int rs = search_last_frame_batch(m, &df, {n, nullptr, 0, n}, &dl, {last.n, nullptr, 0, last.n}, 1, sf, nlevels, cam_type, cam_params, mb, mbf,
                                          th, bMono, checkOri, S.dev(dslot), S.dev(dsobs), nullptr, S.dev(nm), s, scan_mode, rig);
   if (rs < 0) return rs;
-  return download_slots(m, s, S.dev(dslot), S.dev(dslot), S.dev(dsobs), S.dev(nm), n, slot, slot_obs);
+  return download_slots(m, s, S, dslot, dsobs, nm, n, slot, slot_obs);
 }
 
 int orbm_search_by_projection_last_frame(orbm_t *m, const orbm_frame_t *cur, const float *sf, int nlevels, int nLast,
@@ -2283,7 +2298,7 @@ int orbm_search_local_points(orbm_t *m, const orbm_frame_t *cur, const float *sf
   const int rs = search_local_batch(m, &df, {n, nullptr, 0, n}, &dm, {nmp, nullptr, 0, nmp}, 1, sf, nlevels, log_sf, cam_type, cam_params, mbf,
                                     view_cos_limit, th, bFarPoints, th_far, nnratio, dslot, dsobs, S.dev(hmoq), &dt, S.dev(hnm), s, n > 0);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, n > 0 ? (void *)S.dev(hslot) : (void *)S.dev(hmoq), S.dev(hslot), S.dev(hsobs), S.dev(hnm), n, slot, slot_obs);
+  const int nm = download_slots(m, s, S, hslot, hsobs, hnm, n, slot, slot_obs);
   if (nm < 0) return nm;
   const int32_t *moq = S.host(hmoq), *lvl = S.host(hlvl);
   const uint8_t *inv = S.host(hinv);
@@ -2468,9 +2483,7 @@ int orbm_stereo_fisheye_matches(orbm_t *m, const orbx_keypoint_t *keysL, const u
   const int rs = orbm_stereo_fisheye_matches_batch_device(m, 1, kl, dl, cnt, kr, dr, cnt + 2, cap, level_sigma2, nlevels, Tlr, cam_params, cam_params2, cap,
                                                           S.dev(hl2r), S.dev(hr2l), S.dev(hdep), dp3, S.dev(hnm), s);
   if (rs < 0) return rs;
-  const uint8_t *lo = nL ? (const uint8_t *)S.dev(hp3) : (const uint8_t *)S.dev(hl2r);
-  const size_t down = ((const uint8_t *)S.dev(hnm) + 2 * sizeof(int32_t)) - lo;
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, down, hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, hp3, hnm));
   MCHECK(m, hipStreamSynchronize(s));
   if (nL > 0) {
     memcpy(p3d, S.host(hp3), 3 * sizeof(float) * NL);
@@ -2567,7 +2580,7 @@ int orbm_search_local_points_fisheye(orbm_t *m, const orbm_frame_t *cur, int n_l
   const int rs = search_local_batch(m, &df, {std::max(n, 1), nullptr, 0, n}, &dm, {nmp, nullptr, 0, nmp}, 1, sf, nlevels, log_sf, cam_type, cam_params,
                                     0.f, view_cos_limit, th, bFarPoints, th_far, nnratio, dslot, dsobs, S.dev(hmoq), nullptr, S.dev(hnm), s, n > 0, &rig);
   if (rs < 0) return rs;
-  const int nm = download_slots(m, s, n > 0 ? (void *)S.dev(hslot) : (void *)S.dev(hdep), S.dev(hslot), S.dev(hsobs), S.dev(hnm), n, slot, slot_obs);
+  const int nm = download_slots(m, s, S, hslot, hsobs, hnm, n, slot, slot_obs);
   if (nm < 0) return nm;
   const int32_t *moq = S.host(hmoq), *lvl = S.host(hlvl), *lvlr = S.host(hlvlr);
   const uint8_t *inv = S.host(hinv), *invr = S.host(hinvr);
@@ -2779,17 +2792,23 @@ static const char *fuse_sim3_target_refusal(const orbm_fuse_sim3_target_t &g) {
   return fuse_keyframe_refusal(g.kf, g.nlevels, g.cam_type, !g.scale_factors || !g.Scw || !g.cam_params);
 }
 
-int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets, int nP, const uint8_t *valid, const float *Xw, const float *normal,
-                        const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th, int32_t *best_idx, int32_t *best_dist,
-                        int32_t *nfused) {
+// What the two Fuse-into-targets entries share: the argument checks, ONE block (the point arrays once, the valid table, the per-target
+// records, every target's arrays, the form's own parts, then the two result tables), the launches, both tables down in one copy, one
+// synchronisation, the counts.  The records address the arrays by their offsets in the block.  A form names its target and record
+// types and gives refusal(g), fill(S, g, R) for what its record has beyond the shared fields, extra(S, T, TP) and launch(...).
+extern "C++" {
+template <class Form>
+static int fuse_into_targets(orbm_t *m, Form form, int T, const typename Form::Target *targets, int nP, const uint8_t *valid, const float *Xw,
+                             const float *normal, const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th, int32_t *best_idx,
+                             int32_t *best_dist, int32_t *nfused) {
   if (!m) return ORBX_E_ARG;
-  auto refuse = [&](int t, const char *why) { m->err = t < 0 ? std::string(why) : "target " + std::to_string(t) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "target"};
   if (T < 0 || nP < 0) return refuse(-1, "T < 0 or nP < 0");
   if (T > 0 && !targets) return refuse(-1, "NULL target table");
   if (T > 0 && nP > 0 && (!valid || !Xw || !normal || !mpdesc || !max_dist || !min_dist || !best_idx || !best_dist || !nfused))
     return refuse(-1, "NULL point array or result table");
   for (int t = 0; t < T; t++)
-    if (const char *why = fuse_target_refusal(targets[t])) return refuse(t, why);
+    if (const char *why = Form::refusal(targets[t])) return refuse(t, why);
   if ((unsigned long long)T * (unsigned long long)nP > 0x7fffffffull) return refuse(-1, "more than 2^31 - 1 (target, point) pairs");
   if (T == 0 || nP == 0) {   // nothing to search: the device is not touched
     for (int t = 0; t < T && nfused; t++) nfused[t] = 0;
@@ -2798,145 +2817,109 @@ int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets, int
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   const size_t NP = (size_t)nP, TP = (size_t)T * NP;
-  // One block: the point arrays once, the valid table, the per-target records, every target's arrays, then the two result tables.
-  // The records address the arrays by their offsets in the block, which are known before it is allocated.
-  std::vector<FuseTarget> rec((size_t)T);
-  std::vector<Part> parts;
-  parts.reserve(10 + 3 * (size_t)T);
-  size_t off = 0;
-  auto add = [&](const void *src, size_t bytes) { const size_t at = off; parts.push_back({src, bytes}); off += stage_span(bytes); return at; };
-  add(valid, TP); add(Xw, sizeof(float) * 3 * NP); add(normal, sizeof(float) * 3 * NP); add(mpdesc, 32 * NP);
-  add(max_dist, sizeof(float) * NP); add(min_dist, sizeof(float) * NP);
-  add(rec.data(), sizeof(FuseTarget) * (size_t)T);
+  std::vector<typename Form::Rec> rec((size_t)T);
+  Staging S{m};
+  const auto hvalid = S.add(valid, TP);
+  const auto hxw = S.add(Xw, 3 * NP), hnormal = S.add(normal, 3 * NP);
+  const auto hdesc = S.add(mpdesc, 32 * NP);
+  const auto hmax = S.add(max_dist, NP), hmin = S.add(min_dist, NP);
+  const auto hrec = S.add(rec.data(), (size_t)T);   // copied at the upload, filled until then
   for (int t = 0; t < T; t++) {
-    const orbm_fuse_target_t &g = targets[t];
+    const auto &g = targets[t];
     const size_t n = (size_t)g.kf.n;
-    FuseTarget &R = rec[t];
+    typename Form::Rec &R = rec[(size_t)t];
     memset(&R, 0, sizeof(R));
-    R.kp_off = add(g.kf.keys_un, sizeof(orbx_keypoint_t) * n);
-    R.desc_off = add(g.kf.descriptors, 32 * n);
-    R.ur_off = g.kf.u_right && n ? add(g.kf.u_right, sizeof(float) * n) : FUSE_NO_UR;
-    R.n = g.kf.n;
-    R.min_x = g.kf.min_x; R.max_x = g.kf.max_x; R.min_y = g.kf.min_y; R.max_y = g.kf.max_y;
-    R.inv_w = (float)ORBM_GRID_COLS / (g.kf.max_x - g.kf.min_x);   // Frame.cc:379
-    R.inv_h = (float)ORBM_GRID_ROWS / (g.kf.max_y - g.kf.min_y);   // Frame.cc:380
-    for (int l = 0; l < g.nlevels; l++) { R.sf[l] = g.scale_factors[l]; R.inv_sigma2[l] = g.inv_level_sigma2[l]; }
-    R.nlevels = g.nlevels; R.log_sf = g.log_scale_factor;
-    for (int k = 0; k < 16; k++) R.Tcw[k] = g.Tcw[k];
-    for (int k = 0; k < 3; k++) R.Ow[k] = g.Ow[k];
-    R.cam_type = g.cam_type;
-    for (int k = 0; k < (g.cam_type == 0 ? 4 : 8); k++) R.cam[k] = g.cam_params[k];
-    R.bf = g.bf;
-  }
-  add(nullptr, sizeof(int32_t) * TP); add(nullptr, sizeof(int32_t) * TP);
-  std::vector<void *> dev(parts.size());
-  const int rc = stage(m, s, parts.data(), parts.size(), dev.data(), true);
-  if (rc < 0) return rc;
-  FusePoints P;
-  P.nP = nP;
-  P.valid = (const uint8_t *)dev[0]; P.Xw = (const float *)dev[1]; P.normal = (const float *)dev[2]; P.mpdesc = (const uint8_t *)dev[3];
-  P.max_dist = (const float *)dev[4]; P.min_dist = (const float *)dev[5];
-  P.th = th;
-  P.best_idx = (int32_t *)dev[parts.size() - 2]; P.best_dist = (int32_t *)dev[parts.size() - 1];
-  hipLaunchKernelGGL(k_fuse_keyframes, dim3((unsigned)((nP + FUSE_NT - 1) / FUSE_NT), (unsigned)T), dim3(FUSE_NT), 0, s, (const uint8_t *)m->d_block.p,
-                     (const FuseTarget *)dev[6], P);
-  MCHECK(m, hipGetLastError());
-  // both tables down in one copy, one synchronisation
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, P.best_idx), P.best_idx, (uint8_t *)(P.best_dist + TP) - (uint8_t *)P.best_idx, hipMemcpyDeviceToHost, s));
-  MCHECK(m, hipStreamSynchronize(s));
-  memcpy(best_idx, mirror_of(m, P.best_idx), sizeof(int32_t) * TP);
-  memcpy(best_dist, mirror_of(m, P.best_dist), sizeof(int32_t) * TP);
-  int total = 0;
-  for (int t = 0; t < T; t++) {
-    int nf = 0;
-    for (size_t i = 0; i < NP; i++) nf += best_idx[(size_t)t * NP + i] >= 0 ? 1 : 0;   // bestDist <= TH_LOW, :1622
-    nfused[t] = nf;
-    total += nf;
-  }
-  return total;
-}
-
-// ---- LoopClosing::SearchAndFuse (LoopClosing.cc:2631-2707): the Sim3 Fuse of one point list into every corrected keyframe, one call --
-// orbm_fuse_keyframes' staging with the Sim3 record, the per-target list lengths (zeros, uploaded with the block) and the lists; every
-// Scw is decomposed here as orbm_fuse_sim3_cam decomposes it (double division, camera_centre), so that the kernels' gates start from the
-// same T and Ow.  Two launches (orb_fuse_sim3_kernels.h), one download of both tables, one synchronisation.
-int orbm_fuse_sim3_keyframes(orbm_t *m, int T, const orbm_fuse_sim3_target_t *targets, int nP, const uint8_t *valid, const float *Xw,
-                             const float *normal, const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th,
-                             int32_t *best_idx, int32_t *best_dist, int32_t *nfused) {
-  if (!m) return ORBX_E_ARG;
-  auto refuse = [&](int t, const char *why) { m->err = t < 0 ? std::string(why) : "target " + std::to_string(t) + ": " + why; return ORBX_E_ARG; };
-  if (T < 0 || nP < 0) return refuse(-1, "T < 0 or nP < 0");
-  if (T > 0 && !targets) return refuse(-1, "NULL target table");
-  if (T > 0 && nP > 0 && (!valid || !Xw || !normal || !mpdesc || !max_dist || !min_dist || !best_idx || !best_dist || !nfused))
-    return refuse(-1, "NULL point array or result table");
-  for (int t = 0; t < T; t++)
-    if (const char *why = fuse_sim3_target_refusal(targets[t])) return refuse(t, why);
-  if ((unsigned long long)T * (unsigned long long)nP > 0x7fffffffull) return refuse(-1, "more than 2^31 - 1 (target, point) pairs");
-  if (T == 0 || nP == 0) {   // nothing to search: the device is not touched
-    for (int t = 0; t < T && nfused; t++) nfused[t] = 0;
-    return 0;
-  }
-  MCHECK(m, hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  const size_t NP = (size_t)nP, TP = (size_t)T * NP;
-  // One block, laid out as orbm_fuse_keyframes lays out its own (no mvuRight), with counts and lists in front of the result tables
-  std::vector<FuseSim3Target> rec((size_t)T);
-  std::vector<Part> parts;
-  parts.reserve(12 + 2 * (size_t)T);
-  size_t off = 0;
-  auto add = [&](const void *src, size_t bytes) { const size_t at = off; parts.push_back({src, bytes}); off += stage_span(bytes); return at; };
-  add(valid, TP); add(Xw, sizeof(float) * 3 * NP); add(normal, sizeof(float) * 3 * NP); add(mpdesc, 32 * NP);
-  add(max_dist, sizeof(float) * NP); add(min_dist, sizeof(float) * NP);
-  add(rec.data(), sizeof(FuseSim3Target) * (size_t)T);
-  for (int t = 0; t < T; t++) {
-    const orbm_fuse_sim3_target_t &g = targets[t];
-    const size_t n = (size_t)g.kf.n;
-    FuseSim3Target &R = rec[t];
-    memset(&R, 0, sizeof(R));
-    R.kp_off = add(g.kf.keys_un, sizeof(orbx_keypoint_t) * n);
-    R.desc_off = add(g.kf.descriptors, 32 * n);
+    R.kp_off = S.offset(S.add(g.kf.keys_un, n));
+    R.desc_off = S.offset(S.add(g.kf.descriptors, 32 * n));
     R.n = g.kf.n;
     R.min_x = g.kf.min_x; R.max_x = g.kf.max_x; R.min_y = g.kf.min_y; R.max_y = g.kf.max_y;
     R.inv_w = (float)ORBM_GRID_COLS / (g.kf.max_x - g.kf.min_x);   // Frame.cc:379
     R.inv_h = (float)ORBM_GRID_ROWS / (g.kf.max_y - g.kf.min_y);   // Frame.cc:380
     for (int l = 0; l < g.nlevels; l++) R.sf[l] = g.scale_factors[l];
     R.nlevels = g.nlevels; R.log_sf = g.log_scale_factor;
-    decompose_sim3(g.Scw, R.Tcw, R.Ow);                            // ORBmatcher.cc:1672-1677
     R.cam_type = g.cam_type;
     for (int k = 0; k < (g.cam_type == 0 ? 4 : 8); k++) R.cam[k] = g.cam_params[k];
+    Form::fill(S, g, R);
   }
-  const std::vector<int32_t> zero_counts((size_t)T, 0);   // the lists' lengths start at 0 with the upload
-  add(zero_counts.data(), sizeof(int32_t) * (size_t)T);
-  add(nullptr, sizeof(int32_t) * TP);                     // the lists
-  add(nullptr, sizeof(int32_t) * TP); add(nullptr, sizeof(int32_t) * TP);
-  std::vector<void *> dev(parts.size());
-  const int rc = stage(m, s, parts.data(), parts.size(), dev.data(), true);
+  form.extra(S, (size_t)T, TP);
+  const auto hidx = S.out<int32_t>(TP), hdist = S.out<int32_t>(TP);
+  const int rc = S.upload(s);
   if (rc < 0) return rc;
   FusePoints P;
   P.nP = nP;
-  P.valid = (const uint8_t *)dev[0]; P.Xw = (const float *)dev[1]; P.normal = (const float *)dev[2]; P.mpdesc = (const uint8_t *)dev[3];
-  P.max_dist = (const float *)dev[4]; P.min_dist = (const float *)dev[5];
+  P.valid = S.dev(hvalid); P.Xw = S.dev(hxw); P.normal = S.dev(hnormal); P.mpdesc = S.dev(hdesc);
+  P.max_dist = S.dev(hmax); P.min_dist = S.dev(hmin);
   P.th = th;
-  P.best_idx = (int32_t *)dev[parts.size() - 2]; P.best_dist = (int32_t *)dev[parts.size() - 1];
-  const dim3 fgrid((unsigned)((nP + FUSE_NT - 1) / FUSE_NT), (unsigned)T);
-  FuseLists Lst;
-  Lst.count = (int32_t *)dev[parts.size() - 4]; Lst.list = (int32_t *)dev[parts.size() - 3];
-  hipLaunchKernelGGL(k_fuse_sim3_gate, fgrid, dim3(FUSE_NT), 0, s, (const FuseSim3Target *)dev[6], P, Lst);
-  hipLaunchKernelGGL(k_fuse_sim3_search, fgrid, dim3(FUSE_NT), 0, s, (const uint8_t *)m->d_block.p, (const FuseSim3Target *)dev[6], P, Lst);
+  P.best_idx = S.dev(hidx); P.best_dist = S.dev(hdist);
+  form.launch(s, dim3((unsigned)((nP + FUSE_NT - 1) / FUSE_NT), (unsigned)T), S, S.dev(hrec), P);
   MCHECK(m, hipGetLastError());
-  // both tables down in one copy, one synchronisation
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, P.best_idx), P.best_idx, (uint8_t *)(P.best_dist + TP) - (uint8_t *)P.best_idx, hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, hidx, hdist));
   MCHECK(m, hipStreamSynchronize(s));
-  memcpy(best_idx, mirror_of(m, P.best_idx), sizeof(int32_t) * TP);
-  memcpy(best_dist, mirror_of(m, P.best_dist), sizeof(int32_t) * TP);
+  memcpy(best_idx, S.host(hidx), sizeof(int32_t) * TP);
+  memcpy(best_dist, S.host(hdist), sizeof(int32_t) * TP);
   int total = 0;
   for (int t = 0; t < T; t++) {
     int nf = 0;
-    for (size_t i = 0; i < NP; i++) nf += best_idx[(size_t)t * NP + i] >= 0 ? 1 : 0;   // bestDist <= TH_LOW, :1767
+    for (size_t i = 0; i < NP; i++) nf += best_idx[(size_t)t * NP + i] >= 0 ? 1 : 0;   // bestDist <= TH_LOW, :1622 / :1767
     nfused[t] = nf;
     total += nf;
   }
   return total;
+}
+}  // extern "C++"
+
+struct FuseKeyframesForm {
+  using Target = orbm_fuse_target_t;
+  using Rec = FuseTarget;
+  static const char *refusal(const Target &g) { return fuse_target_refusal(g); }
+  static void fill(Staging &S, const Target &g, Rec &R) {
+    const size_t n = (size_t)g.kf.n;
+    R.ur_off = g.kf.u_right && n ? S.offset(S.add(g.kf.u_right, n)) : FUSE_NO_UR;
+    for (int l = 0; l < g.nlevels; l++) R.inv_sigma2[l] = g.inv_level_sigma2[l];
+    for (int k = 0; k < 16; k++) R.Tcw[k] = g.Tcw[k];
+    for (int k = 0; k < 3; k++) R.Ow[k] = g.Ow[k];
+    R.bf = g.bf;
+  }
+  void extra(Staging &, size_t, size_t) {}
+  void launch(hipStream_t s, dim3 grid, const Staging &S, const Rec *rec, const FusePoints &P) const {
+    hipLaunchKernelGGL(k_fuse_keyframes, grid, dim3(FUSE_NT), 0, s, S.block(), rec, P);
+  }
+};
+
+int orbm_fuse_keyframes(orbm_t *m, int T, const orbm_fuse_target_t *targets, int nP, const uint8_t *valid, const float *Xw, const float *normal,
+                        const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th, int32_t *best_idx, int32_t *best_dist,
+                        int32_t *nfused) {
+  return fuse_into_targets(m, FuseKeyframesForm{}, T, targets, nP, valid, Xw, normal, mpdesc, max_dist, min_dist, th, best_idx, best_dist, nfused);
+}
+
+// ---- LoopClosing::SearchAndFuse (LoopClosing.cc:2631-2707): the Sim3 Fuse of one point list into every corrected keyframe, one call --
+// The Sim3 record (no mvuRight), the per-target list lengths (zeros, uploaded with the block) and the lists in front of the result
+// tables; every Scw is decomposed here as orbm_fuse_sim3_cam decomposes it (double division, camera_centre), so that the kernels' gates
+// start from the same T and Ow.  Two launches (orb_fuse_sim3_kernels.h).
+struct FuseSim3KeyframesForm {
+  using Target = orbm_fuse_sim3_target_t;
+  using Rec = FuseSim3Target;
+  std::vector<int32_t> zero_counts;   // the lists' lengths start at 0 with the upload
+  PartOf<int32_t> count, list;
+  static const char *refusal(const Target &g) { return fuse_sim3_target_refusal(g); }
+  static void fill(Staging &, const Target &g, Rec &R) { decompose_sim3(g.Scw, R.Tcw, R.Ow); }   // ORBmatcher.cc:1672-1677
+  void extra(Staging &S, size_t T, size_t TP) {
+    zero_counts.assign(T, 0);
+    count = S.add(zero_counts.data(), T);
+    list = S.out<int32_t>(TP);
+  }
+  void launch(hipStream_t s, dim3 grid, const Staging &S, const Rec *rec, const FusePoints &P) const {
+    FuseLists Lst;
+    Lst.count = S.dev(count); Lst.list = S.dev(list);
+    hipLaunchKernelGGL(k_fuse_sim3_gate, grid, dim3(FUSE_NT), 0, s, rec, P, Lst);
+    hipLaunchKernelGGL(k_fuse_sim3_search, grid, dim3(FUSE_NT), 0, s, S.block(), rec, P, Lst);
+  }
+};
+
+int orbm_fuse_sim3_keyframes(orbm_t *m, int T, const orbm_fuse_sim3_target_t *targets, int nP, const uint8_t *valid, const float *Xw,
+                             const float *normal, const uint8_t *mpdesc, const float *max_dist, const float *min_dist, float th,
+                             int32_t *best_idx, int32_t *best_dist, int32_t *nfused) {
+  return fuse_into_targets(m, FuseSim3KeyframesForm{}, T, targets, nP, valid, Xw, normal, mpdesc, max_dist, min_dist, th, best_idx, best_dist, nfused);
 }
 
 // ---- SearchBySim3 (ORBmatcher.cc:1788-2012) ------------------------------------------------------------------------------
@@ -3112,18 +3095,23 @@ static int triangulation_candidates(orbm_t *m, const orbm_keyframe_t *k1, const 
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
   const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
-  enum { DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, NPARTS };
-  void *d[NPARTS];
-  const int rs = stage(m, s, {{k1->descriptors, 32 * (size_t)k1->n}, {k1->u_right, sizeof(float) * (size_t)k1->n}, {k2->descriptors, 32 * (size_t)k2->n},
-                              {k2->keys_un, sizeof(orbx_keypoint_t) * (size_t)k2->n}, {k2->u_right, sizeof(float) * (size_t)k2->n},
-                              {k2->has_mappoint, (size_t)k2->n}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * items.size()}}, d);
+  Staging S{m};
+  const auto DESC1 = S.add(k1->descriptors, 32 * (size_t)k1->n);
+  const auto UR1 = S.add(k1->u_right, (size_t)k1->n);
+  const auto DESC2 = S.add(k2->descriptors, 32 * (size_t)k2->n);
+  const auto KP2 = S.add(k2->keys_un, (size_t)k2->n);
+  const auto UR2 = S.add(k2->u_right, (size_t)k2->n);
+  const auto HASMP2 = S.add(k2->has_mappoint, (size_t)k2->n);
+  const auto NODE_IDX2 = S.add(k2->node_idx, nidx2);
+  const auto ITEMS = S.add(items.data(), items.size());
+  const int rs = S.upload(s, false);
   if (rs < 0) return rs;
   TriCandParams T;
   memset(&T, 0, sizeof(T));
-  T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
-  T.desc2 = (const uint32_t *)d[DESC2]; T.kp2 = (const float *)d[KP2]; T.ur2 = (const float *)d[UR2];
-  T.hasmp2 = (const uint8_t *)d[HASMP2]; T.node_idx2 = (const int32_t *)d[NODE_IDX2];
-  T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)items.size();
+  T.desc1 = (const uint32_t *)S.dev(DESC1); T.ur1 = S.dev(UR1);
+  T.desc2 = (const uint32_t *)S.dev(DESC2); T.kp2 = (const float *)S.dev(KP2); T.ur2 = S.dev(UR2);
+  T.hasmp2 = S.dev(HASMP2); T.node_idx2 = S.dev(NODE_IDX2);
+  T.items = S.dev(ITEMS); T.nitems = (int)items.size();
   for (int l = 0; l < ORBX_MAX_LEVELS; l++) T.sf2[l] = l < k2->nlevels ? k2->scale_factors[l] : 0.f;
   T.epx = ep_x; T.epy = ep_y; T.epipole_gate = epipole_gate; T.bOnlyStereo = bOnlyStereo;
   const size_t ni = items.size();
@@ -3210,50 +3198,6 @@ int orbm_search_for_triangulation_pred(orbm_t *m, const orbm_keyframe_t *k1, con
   return nmatches;
 }
 
-int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, const float *R1w, const float *t1w,
-                                  const float *R2w, const float *t2w, const float *Cw1, const float *cam1, const float *cam2,
-                                  int bOnlyStereo, int bCoarse, int checkOri, int32_t *matches12) {
-  if (!m || !k1 || !k2 || !R1w || !t1w || !R2w || !t2w || !Cw1 || !cam1 || !cam2 || !matches12) return ORBX_E_ARG;
-  if (k1->n < 0 || k2->n < 0 || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return ORBX_E_ARG;
-  for (int i = 0; i < k1->n; i++) matches12[i] = -1;
-  if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
-  if (!k1->u_right || !k2->u_right || !k1->has_mappoint || !k2->has_mappoint) return ORBX_E_ARG;
-  TriParams T;
-  memset(&T, 0, sizeof(T));
-  pinhole_pair_geometry(R1w, t1w, R2w, t2w, Cw1, cam1, cam2, T.F12, T.epx, T.epy);
-  std::vector<TriItem> items;
-  { const int rc = triangulation_items(m, k1, k2, k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
-  int nmatches = 0;
-  if (!items.empty()) {
-    MCHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes], out_bytes = sizeof(int32_t) * (size_t)k1->n;
-    enum { KP1, DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, MATCHES12, NPARTS };
-    void *d[NPARTS];
-    const int rs = stage(m, s, {{k1->keys_un, sizeof(orbx_keypoint_t) * (size_t)k1->n}, {k1->descriptors, 32 * (size_t)k1->n},
-                                {k1->u_right, sizeof(float) * (size_t)k1->n}, {k2->descriptors, 32 * (size_t)k2->n},
-                                {k2->keys_un, sizeof(orbx_keypoint_t) * (size_t)k2->n}, {k2->u_right, sizeof(float) * (size_t)k2->n},
-                                {k2->has_mappoint, (size_t)k2->n}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * items.size()},
-                                {nullptr, out_bytes}}, d);
-    if (rs < 0) return rs;
-    MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, out_bytes, s));
-    T.kp1 = (const float *)d[KP1]; T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
-    T.desc2 = (const uint32_t *)d[DESC2]; T.kp2 = (const float *)d[KP2]; T.ur2 = (const float *)d[UR2];
-    T.hasmp2 = (const uint8_t *)d[HASMP2]; T.node_idx2 = (const int32_t *)d[NODE_IDX2];
-    T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)items.size();
-    for (int l = 0; l < k2->nlevels; l++) { T.sf2[l] = k2->scale_factors[l]; T.sigma2_2[l] = k2->level_sigma2[l]; }
-    T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
-    T.matches12 = (int32_t *)d[MATCHES12];
-    hipLaunchKernelGGL(k_triangulation_match, dim3((T.nitems + 3) / 4), dim3(256), 0, s, T);
-    MCHECK(m, hipGetLastError());
-    MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
-    MCHECK(m, hipStreamSynchronize(s));
-    for (int i = 0; i < k1->n; i++) nmatches += matches12[i] >= 0;
-  }
-  if (checkOri && nmatches > 0) nmatches = prune_pairs_by_rotation(k1, k2, matches12, nmatches);
-  return nmatches;
-}
-
 // Why a keyframe (nlevels in range) cannot be read by the kernels, or NULL.  rig: u_right is not read; scales = false: neither are
 // its scale tables (KF1 under Pinhole's test).
 static const char *tri_keyframe_refusal(const orbm_keyframe_t *k, bool rig, bool scales = true) {
@@ -3272,84 +3216,6 @@ static const char *tri_members_refusal(const orbm_keyframe_t *k2) {
   for (size_t i = 0; i < nidx2; i++)
     if (k2->node_idx[i] < 0 || k2->node_idx[i] >= k2->n) return "feature vector: keypoint index out of range";
   return nullptr;
-}
-
-// SearchForTriangulation with KannalaBrandt8's epipolarConstrain on the device (ORBmatcher.cc:981-1222, KannalaBrandt8.cpp:244-247):
-// candidates -> predicate on every candidate -> minimum accepted key per item -> vMatches12, one upload and one download.
-int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, const orbm_keyframe_t *k2, int n_left2, float ep_x, float ep_y,
-                                      const float *cams1, const float *cams2, const float *T12, int bOnlyStereo, int bCoarse, int checkOri,
-                                      int32_t *matches12) {
-  if (!m || !k1 || !k2 || !cams1 || !cams2 || !T12 || !matches12) return ORBX_E_ARG;
-  const bool rig = n_left1 != -1;
-  auto refuse = [&](const char *why) { m->err = why; return ORBX_E_ARG; };
-  if ((n_left1 == -1) != (n_left2 == -1)) return refuse("n_left: one keyframe with and one without a second camera");
-  if (k1->n < 0 || k2->n < 0 || n_left1 < -1 || n_left1 > k1->n || n_left2 < -1 || n_left2 > k2->n) return refuse("n or n_left out of range");
-  if (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return refuse("nlevels out of range");
-  for (const orbm_keyframe_t *k : {k1, k2})
-    if (const char *why = tri_keyframe_refusal(k, rig)) return refuse(why);
-  for (int i = 0; i < k1->n; i++) matches12[i] = -1;
-  if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
-  const size_t nidx2 = (size_t)k2->node_start[k2->n_nodes];
-  if (const char *why = tri_members_refusal(k2)) return refuse(why);
-  std::vector<TriItem> items;
-  { const int rc = triangulation_items(m, k1, k2, rig ? nullptr : k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
-  int nmatches = 0;
-  if (!items.empty()) {
-    size_t cap = 0;   // every member of an item's node can be a candidate: the list never outgrows this
-    for (const TriItem &it : items) cap += (size_t)it.len2;
-    if (cap > 0x7fffffffu) return refuse("more than 2^31 - 1 keypoint pairs in shared vocabulary nodes");
-    TriKb8Consts K;
-    memset(&K, 0, sizeof(K));
-    for (int p = 0; p < (rig ? 4 : 1); p++) {
-      memcpy(K.T12[p], T12 + 12 * p, sizeof(K.T12[p]));
-      rig_Tcw2(K.T12[p], K.Tcw2[p]);
-    }
-    memcpy(K.cams1, cams1, sizeof(float) * (rig ? 16 : 8));
-    memcpy(K.cams2, cams2, sizeof(float) * (rig ? 16 : 8));
-    MCHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    const size_t n1 = (size_t)k1->n, n2 = (size_t)k2->n, ni = items.size(), out_bytes = sizeof(int32_t) * n1;
-    enum { KP1, DESC1, UR1, DESC2, KP2, UR2, HASMP2, NODE_IDX2, ITEMS, CONSTS, MATCHES12, BEST, TOTAL, KEYS, KEY_ITEM, NPARTS };
-    void *d[NPARTS];
-    const int rs = stage(m, s, {{k1->keys_un, sizeof(orbx_keypoint_t) * n1}, {k1->descriptors, 32 * n1}, {rig ? nullptr : k1->u_right, rig ? 0 : sizeof(float) * n1},
-                                {k2->descriptors, 32 * n2}, {k2->keys_un, sizeof(orbx_keypoint_t) * n2}, {rig ? nullptr : k2->u_right, rig ? 0 : sizeof(float) * n2},
-                                {k2->has_mappoint, n2}, {k2->node_idx, sizeof(int32_t) * nidx2}, {items.data(), sizeof(TriItem) * ni}, {&K, sizeof(K)},
-                                {nullptr, out_bytes}, {nullptr, sizeof(uint32_t) * ni}, {nullptr, sizeof(int32_t)}, {nullptr, sizeof(uint32_t) * cap},
-                                {nullptr, sizeof(int32_t) * cap}}, d);
-    if (rs < 0) return rs;
-    // matches12 = -1 and best = 0xffffffff in one fill (adjacent parts of the block), total = 0
-    MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, (size_t)((uint8_t *)d[TOTAL] - (uint8_t *)d[MATCHES12]), s));
-    MCHECK(m, hipMemsetAsync(d[TOTAL], 0, sizeof(int32_t), s));
-    TriCandParams C;
-    memset(&C, 0, sizeof(C));
-    C.desc1 = (const uint32_t *)d[DESC1]; C.ur1 = (const float *)d[UR1];
-    C.desc2 = (const uint32_t *)d[DESC2]; C.kp2 = (const float *)d[KP2]; C.ur2 = (const float *)d[UR2];
-    C.hasmp2 = (const uint8_t *)d[HASMP2]; C.node_idx2 = (const int32_t *)d[NODE_IDX2];
-    C.items = (const TriItem *)d[ITEMS]; C.nitems = (int)ni;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) C.sf2[l] = l < k2->nlevels ? k2->scale_factors[l] : 0.f;
-    C.epx = ep_x; C.epy = ep_y; C.epipole_gate = rig ? 0 : 1; C.bOnlyStereo = bOnlyStereo;   // !pKF1->mpCamera2, :1105
-    C.keys = (uint32_t *)d[KEYS]; C.cap = (int)cap; C.key_item = (int32_t *)d[KEY_ITEM]; C.total = (int32_t *)d[TOTAL];
-    TriKb8Params T;
-    memset(&T, 0, sizeof(T));
-    T.kp1 = (const float *)d[KP1]; T.kp2 = C.kp2; T.node_idx2 = C.node_idx2; T.items = C.items; T.nitems = C.nitems;
-    T.keys = C.keys; T.key_item = C.key_item; T.total = C.total; T.cap = C.cap;
-    T.consts = (const TriKb8Consts *)d[CONSTS];
-    for (int l = 0; l < k1->nlevels; l++) T.sigma2_1[l] = k1->level_sigma2[l];
-    for (int l = 0; l < k2->nlevels; l++) T.sigma2_2[l] = k2->level_sigma2[l];
-    T.n_left1 = n_left1; T.n_left2 = n_left2; T.bCoarse = bCoarse;
-    T.best = (uint32_t *)d[BEST]; T.matches12 = (int32_t *)d[MATCHES12];
-    hipLaunchKernelGGL(k_triangulation_candidates, dim3((C.nitems + 3) / 4), dim3(256), 0, s, C);
-    MCHECK(m, hipGetLastError());
-    hipLaunchKernelGGL(k_triangulation_kb8_predicate, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, T);
-    MCHECK(m, hipGetLastError());
-    hipLaunchKernelGGL(k_triangulation_kb8_result, dim3((T.nitems + 255) / 256), dim3(256), 0, s, T);
-    MCHECK(m, hipGetLastError());
-    MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
-    MCHECK(m, hipStreamSynchronize(s));
-    for (int i = 0; i < k1->n; i++) nmatches += matches12[i] >= 0;
-  }
-  if (checkOri && nmatches > 0) nmatches = prune_pairs_by_rotation(k1, k2, matches12, nmatches);
-  return nmatches;
 }
 
 // ---- SearchForTriangulation of one keyframe against K neighbours in one call (LocalMapping.cc:475-583) ----------------------------
@@ -3372,9 +3238,10 @@ struct NewPointsCall {
 static void new_point_camera(orbm_new_point_camera_t &c, const orbm_keyframe_t &k, const orbm_keyframe_geometry_t &g, int cam_type, const float *cams,
                              int n_left);
 
-static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const uint8_t *skip,
+static int triangulation_neighbours(orbm_t *m, const char *kind, const orbm_keyframe_t *k1, int n_left1, int K, const orbm_keyframe_t *k2, const uint8_t *skip,
                                     std::vector<TriNb> &nb, const std::vector<TriKb8Consts> *kb8, int bOnlyStereo, int bCoarse,
                                     int32_t *matches12, int32_t *nmatches, NewPointsCall *np = nullptr) {
+  const Refuse refuse{m, kind};   // kind NULL: a pair entry, no item named
   const bool rig = n_left1 != -1;
   const size_t n1 = (size_t)k1->n;
   if (matches12) for (size_t i = 0; i < (size_t)K * n1; i++) matches12[i] = -1;
@@ -3386,14 +3253,16 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     const size_t before = items.size();
     m->err.clear();
     const int rc = triangulation_items(m, k1, &k2[j], rig ? nullptr : k1->u_right, bOnlyStereo, items, j);
-    if (rc < 0) { m->err = "neighbour " + std::to_string(j) + ": " + (m->err.empty() ? std::string("kf1: keypoint index out of range") : m->err); return rc; }
+    if (rc < 0) { refuse(j, (m->err.empty() ? std::string("kf1: keypoint index out of range") : std::string(m->err)).c_str()); return rc; }
     live[(size_t)j] = items.size() > before;
   }
   if (items.empty()) return 0;
   const size_t ni = items.size();
   size_t cap = 0;   // every member of an item's node can be a candidate: the key list never outgrows this
   for (const TriItem &it : items) cap += (size_t)it.len2;
-  if (cap > 0x7fffffffu || ni > 0x7fffffffu) { m->err = "more than 2^31 - 1 keypoint pairs in shared vocabulary nodes over all neighbours"; return ORBX_E_ARG; }
+  if (cap > 0x7fffffffu || ni > 0x7fffffffu)
+    return refuse(-1, refuse.kind ? "more than 2^31 - 1 keypoint pairs in shared vocabulary nodes over all neighbours"
+                                  : "more than 2^31 - 1 keypoint pairs in shared vocabulary nodes");
   if (m->tri_layout == 1 && K > 1) {   // KF1-keypoint-major: one idx1 against consecutive neighbours (a stable counting sort on idx1); measured slower, DESIGN.md 6
     std::vector<size_t> at(n1 + 1, 0);
     for (const TriItem &it : items) at[(size_t)it.idx1 + 1]++;
@@ -3403,37 +3272,42 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     items.swap(byKey);
   }
   static const int32_t zero = 0;
-  std::vector<Part> parts;
-  std::vector<size_t> offs;
-  parts.reserve(24 + 6 * (size_t)K);
-  size_t off = 0;
-  auto add = [&](const void *src, size_t bytes) { parts.push_back(Part{src, bytes}); offs.push_back(off); off += stage_span(bytes); return parts.size() - 1; };
-  const size_t KP1 = add(k1->keys_un, sizeof(orbx_keypoint_t) * n1), DESC1 = add(k1->descriptors, 32 * n1);
-  const size_t UR1 = add(rig ? nullptr : k1->u_right, rig ? 0 : sizeof(float) * n1);
+  Staging S{m};
+  const auto KP1 = S.add(k1->keys_un, n1);
+  const auto DESC1 = S.add(k1->descriptors, 32 * n1);
+  const auto UR1 = S.add(rig ? nullptr : k1->u_right, rig ? 0 : n1);
   for (int j = 0; j < K; j++) {
     if (!live[(size_t)j]) continue;
     const orbm_keyframe_t &k = k2[j];
     const size_t n2 = (size_t)k.n;
     TriNb &N = nb[(size_t)j];
-    N.desc2 = offs[add(k.descriptors, 32 * n2)];
-    N.kp2 = offs[add(k.keys_un, sizeof(orbx_keypoint_t) * n2)];
-    N.ur2 = offs[add(rig ? nullptr : k.u_right, rig ? 0 : sizeof(float) * n2)];
-    N.hasmp2 = offs[add(k.has_mappoint, n2)];
-    N.node_idx2 = offs[add(k.node_idx, sizeof(int32_t) * (size_t)k.node_start[k.n_nodes])];
+    N.desc2 = S.offset(S.add(k.descriptors, 32 * n2));
+    N.kp2 = S.offset(S.add(k.keys_un, n2));
+    N.ur2 = S.offset(S.add(rig ? nullptr : k.u_right, rig ? 0 : n2));
+    N.hasmp2 = S.offset(S.add(k.has_mappoint, n2));
+    N.node_idx2 = S.offset(S.add(k.node_idx, (size_t)k.node_start[k.n_nodes]));
     for (int l = 0; l < k.nlevels; l++) { N.sf2[l] = k.scale_factors[l]; N.sigma2_2[l] = k.level_sigma2[l]; }
   }
-  const size_t ITEMS = add(items.data(), sizeof(TriItem) * ni), NB = add(nb.data(), sizeof(TriNb) * (size_t)K);
-  const size_t CONSTS = add(kb8 ? kb8->data() : nullptr, kb8 ? sizeof(TriKb8Consts) * (size_t)K : 0);
-  const size_t TOTAL = add(kb8 ? &zero : nullptr, kb8 ? sizeof(int32_t) : 0);   // the candidate total starts at the uploaded 0
+  const auto ITEMS = S.add(items.data(), ni);
+  const auto NB = S.add(nb.data(), (size_t)K);
+  const auto CONSTS = S.add(kb8 ? kb8->data() : nullptr, kb8 ? (size_t)K : 0);
+  const auto TOTAL = S.add(kb8 ? &zero : nullptr, kb8 ? 1 : 0);   // the candidate total starts at the uploaded 0
   const size_t out_bytes = sizeof(int32_t) * (size_t)K * n1;
-  const size_t MATCHES12 = add(nullptr, out_bytes), BEST = add(nullptr, kb8 ? sizeof(uint32_t) * ni : 0);
-  const size_t KEYS = add(nullptr, kb8 ? sizeof(uint32_t) * cap : 0), KEY_ITEM = add(nullptr, kb8 ? sizeof(int32_t) * cap : 0);
+  const auto MATCHES12 = S.out<int32_t>((size_t)K * n1);
+  const auto BEST = S.out<uint32_t>(kb8 ? ni : 0);
+  const auto KEYS = S.out<uint32_t>(kb8 ? cap : 0);
+  const auto KEY_ITEM = S.out<int32_t>(kb8 ? cap : 0);
   // the body's inputs and outputs behind the search's: per keyframe with stereo keypoints {mvDepth, mvKeys.pt}, the constants of the new
   // keyframe and of every neighbour, then status / x3D / first / total + list
   std::vector<orbm_new_point_camera_t> np_cams;
   std::vector<std::vector<float>> np_stereo;
   std::vector<uint64_t> np_stereo2;
-  size_t NP_STEREO1 = 0, NP_CAMS = 0, NP_STEREO2 = 0, NP_STATUS = 0, NP_X3D = 0, NP_FIRST = 0, NP_TOTAL = 0, NP_LIST = 0;
+  PartOf<float> NP_STEREO1{}, NP_X3D{};
+  PartOf<orbm_new_point_camera_t> NP_CAMS{};
+  PartOf<uint64_t> NP_STEREO2{};
+  PartOf<uint8_t> NP_STATUS{};
+  PartOf<int32_t> NP_FIRST{}, NP_TOTAL{};
+  PartOf<orbm_new_point_t> NP_LIST{};
   if (np) {
     np_cams.resize((size_t)K + 1);
     memset(np_cams.data(), 0, sizeof(orbm_new_point_camera_t) * np_cams.size());
@@ -3448,38 +3322,34 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     };
     new_point_camera(np_cams[0], *k1, *np->g1, np->cam_type, np->cams1, n_left1);
     pack_stereo(*k1, *np->g1, np_stereo[0]);
-    NP_STEREO1 = add(np_stereo[0].empty() ? nullptr : np_stereo[0].data(), sizeof(float) * np_stereo[0].size());
+    NP_STEREO1 = S.add(np_stereo[0].empty() ? (const float *)nullptr : np_stereo[0].data(), np_stereo[0].size());
     for (int j = 0; j < K; j++) {
       if (!live[(size_t)j]) continue;
       new_point_camera(np_cams[(size_t)j + 1], k2[j], np->g2[j], np->cam_type, np->cams2 + (size_t)j * (size_t)np->cams2_stride, np->n_left2 ? np->n_left2[j] : -1);
       pack_stereo(k2[j], np->g2[j], np_stereo[(size_t)j + 1]);
       const std::vector<float> &st = np_stereo[(size_t)j + 1];
-      if (!st.empty()) np_stereo2[(size_t)j] = offs[add(st.data(), sizeof(float) * st.size())];
+      if (!st.empty()) np_stereo2[(size_t)j] = S.offset(S.add(st.data(), st.size()));
     }
-    NP_CAMS = add(np_cams.data(), sizeof(orbm_new_point_camera_t) * np_cams.size());
-    NP_STEREO2 = add(np_stereo2.data(), sizeof(uint64_t) * (size_t)K);
-    NP_STATUS = add(nullptr, (size_t)K * n1);
-    NP_X3D = add(nullptr, sizeof(float) * 3 * (size_t)K * n1);
-    NP_FIRST = add(nullptr, sizeof(int32_t) * n1);
-    NP_TOTAL = add(nullptr, sizeof(int32_t));
-    NP_LIST = add(nullptr, sizeof(orbm_new_point_t) * n1);
+    NP_CAMS = S.add(np_cams.data(), np_cams.size());
+    NP_STEREO2 = S.add(np_stereo2.data(), (size_t)K);
+    NP_STATUS = S.out<uint8_t>((size_t)K * n1);
+    NP_X3D = S.out<float>(3 * (size_t)K * n1);
+    NP_FIRST = S.out<int32_t>(n1);
+    NP_TOTAL = S.out<int32_t>(1);
+    NP_LIST = S.out<orbm_new_point_t>(n1);
   }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  std::vector<void *> d(parts.size());
-  { const int rs = stage(m, s, parts.data(), parts.size(), d.data(), false); if (rs < 0) return rs; }
-  const uint8_t *block = (const uint8_t *)m->d_block.p;
-  for (size_t i = 0; i < parts.size(); i++)   // the table's offsets were formed here, stage() formed the addresses: they must agree
-    if (d[i] && d[i] != block + offs[i]) { m->err = "triangulation neighbours: staging layout"; return ORBX_E_HIP; }
+  { const int rs = S.upload(s, false); if (rs < 0) return rs; }   // no output mirror: the rows go straight to the caller
   // matches12 = -1 and best = 0xffffffff in one fill (adjacent parts of the block)
-  MCHECK(m, hipMemsetAsync(d[MATCHES12], 0xff, kb8 ? offs[BEST] + sizeof(uint32_t) * ni - offs[MATCHES12] : out_bytes, s));
+  MCHECK(m, kb8 ? S.fill(s, MATCHES12, BEST, 0xff) : S.fill(s, MATCHES12, MATCHES12, 0xff));
   TriNbParams T;
   memset(&T, 0, sizeof(T));
-  T.block = block; T.nb = (const TriNb *)d[NB];
-  T.kp1 = (const float *)d[KP1]; T.desc1 = (const uint32_t *)d[DESC1]; T.ur1 = (const float *)d[UR1];
-  T.items = (const TriItem *)d[ITEMS]; T.nitems = (int)ni; T.n1 = k1->n;
+  T.block = S.block(); T.nb = S.dev(NB);
+  T.kp1 = (const float *)S.dev(KP1); T.desc1 = (const uint32_t *)S.dev(DESC1); T.ur1 = S.dev(UR1);
+  T.items = S.dev(ITEMS); T.nitems = (int)ni; T.n1 = k1->n;
   T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
-  T.matches12 = (int32_t *)d[MATCHES12];
+  T.matches12 = S.dev(MATCHES12);
   if (!kb8) {
     hipLaunchKernelGGL(k_triangulation_match_neighbours, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, T);
     MCHECK(m, hipGetLastError());
@@ -3487,13 +3357,13 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     TriCandNbParams C;
     memset(&C, 0, sizeof(C));
     C.in = T; C.epipole_gate = rig ? 0 : 1;   // !pKF1->mpCamera2, :1105
-    C.keys = (uint32_t *)d[KEYS]; C.cap = (int)cap; C.key_item = (int32_t *)d[KEY_ITEM]; C.total = (int32_t *)d[TOTAL];
+    C.keys = S.dev(KEYS); C.cap = (int)cap; C.key_item = S.dev(KEY_ITEM); C.total = S.dev(TOTAL);
     TriKb8NbParams P;
     memset(&P, 0, sizeof(P));
     P.in = T; P.keys = C.keys; P.key_item = C.key_item; P.total = C.total; P.cap = C.cap;
-    P.consts = (const TriKb8Consts *)d[CONSTS];
+    P.consts = S.dev(CONSTS);
     for (int l = 0; l < k1->nlevels; l++) P.sigma2_1[l] = k1->level_sigma2[l];
-    P.n_left1 = n_left1; P.best = (uint32_t *)d[BEST];
+    P.n_left1 = n_left1; P.best = S.dev(BEST);
     hipLaunchKernelGGL(k_triangulation_candidates_neighbours, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, C);
     MCHECK(m, hipGetLastError());
     hipLaunchKernelGGL(k_triangulation_kb8_predicate_neighbours, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, P);
@@ -3501,32 +3371,32 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
     hipLaunchKernelGGL(k_triangulation_kb8_result_neighbours, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
   }
-  std::vector<uint8_t> np_out;   // total (one 256-byte part) and the list behind it, adjacent parts of the block: one copy
+  std::vector<uint8_t> np_out;   // total and the list behind it, adjacent parts of the block: one copy
   if (np) {
     NewPointsParams P;
     memset(&P, 0, sizeof(P));
     P.in = T;
-    P.cams = (const orbm_new_point_camera_t *)d[NP_CAMS]; P.stereo1 = (const float *)d[NP_STEREO1]; P.stereo2 = (const uint64_t *)d[NP_STEREO2];
+    P.cams = S.dev(NP_CAMS); P.stereo1 = S.dev(NP_STEREO1); P.stereo2 = S.dev(NP_STEREO2);
     P.K = K; P.scale_factor1 = np->scale_factor1; P.th_far_points = np->th_far_points; P.far_points = np->far_points;
-    P.status = (uint8_t *)d[NP_STATUS]; P.x3d = (float *)d[NP_X3D]; P.first = (int32_t *)d[NP_FIRST];
-    P.list = (orbm_new_point_t *)d[NP_LIST]; P.total = (int32_t *)d[NP_TOTAL];
-    MCHECK(m, hipMemsetAsync(d[NP_FIRST], 0x7f, sizeof(int32_t) * n1, s));
+    P.status = S.dev(NP_STATUS); P.x3d = S.dev(NP_X3D); P.first = S.dev(NP_FIRST);
+    P.list = S.dev(NP_LIST); P.total = S.dev(NP_TOTAL);
+    MCHECK(m, S.fill(s, NP_FIRST, NP_FIRST, 0x7f));
     hipLaunchKernelGGL(k_new_points_geometry, dim3((unsigned)(((size_t)K * n1 + 255) / 256)), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
     hipLaunchKernelGGL(k_new_points_emit, dim3((unsigned)K), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
-    np_out.resize(stage_span(sizeof(int32_t)) + sizeof(orbm_new_point_t) * n1);
-    MCHECK(m, hipMemcpyAsync(np_out.data(), d[NP_TOTAL], np_out.size(), hipMemcpyDeviceToHost, s));
-    if (np->status) MCHECK(m, hipMemcpyAsync(np->status, d[NP_STATUS], (size_t)K * n1, hipMemcpyDeviceToHost, s));
+    np_out.resize(S.span(NP_TOTAL, NP_LIST));
+    MCHECK(m, hipMemcpyAsync(np_out.data(), S.dev(NP_TOTAL), np_out.size(), hipMemcpyDeviceToHost, s));
+    if (np->status) MCHECK(m, hipMemcpyAsync(np->status, S.dev(NP_STATUS), (size_t)K * n1, hipMemcpyDeviceToHost, s));
   }
-  if (matches12) MCHECK(m, hipMemcpyAsync(matches12, d[MATCHES12], out_bytes, hipMemcpyDeviceToHost, s));
+  if (matches12) MCHECK(m, hipMemcpyAsync(matches12, S.dev(MATCHES12), out_bytes, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   if (np) {
     int32_t total = 0;
     memcpy(&total, np_out.data(), sizeof(total));
     if (total < 0 || (size_t)total > n1) { m->err = "new points: list count out of range"; return ORBX_E_HIP; }
     np->list.resize((size_t)total);
-    if (total) memcpy(np->list.data(), np_out.data() + stage_span(sizeof(int32_t)), sizeof(orbm_new_point_t) * (size_t)total);
+    if (total) memcpy(np->list.data(), np_out.data() + (S.offset(NP_LIST) - S.offset(NP_TOTAL)), sizeof(orbm_new_point_t) * (size_t)total);
   }
   long long sum = 0;
   for (int j = 0; matches12 && j < K; j++) {
@@ -3542,7 +3412,7 @@ static int triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k1, int n_
 // as the per-pair entry would refuse it, m->err naming the neighbour.  1: nothing to search (K == 0, every neighbour skipped).
 static int triangulation_neighbours_refusal(orbm_t *m, const orbm_keyframe_t *k1, bool rig, bool kb8, int K, const orbm_keyframe_t *k2,
                                             const uint8_t *skip) {
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "neighbour"};
   if (K < 0) return refuse(-1, "K < 0");
   if (K > 0 && !k2) return refuse(-1, "NULL neighbour table");
   if (k1->n < 0) return refuse(-1, "kf1: n < 0");
@@ -3575,13 +3445,12 @@ int orbm_search_for_triangulation_neighbours(orbm_t *m, const orbm_keyframe_t *k
   if (K > 0) memset(nb.data(), 0, sizeof(TriNb) * (size_t)K);
   for (int j = 0; j < K && rr == 0; j++)
     if (!(skip && skip[j])) pinhole_pair_geometry(R1w, t1w, R2w + 9 * j, t2w + 3 * j, Cw1, cam1, cam2 + 4 * j, nb[(size_t)j].F12, nb[(size_t)j].epx, nb[(size_t)j].epy);
-  return triangulation_neighbours(m, k1, -1, K, k2, skip, nb, nullptr, bOnlyStereo, bCoarse, matches12, nmatches);
+  return triangulation_neighbours(m, "neighbour", k1, -1, K, k2, skip, nb, nullptr, bOnlyStereo, bCoarse, matches12, nmatches);
 }
 
 // The KannalaBrandt8 form's neighbour table and constants from the caller's tables (rr: triangulation_neighbours_refusal's answer)
-static int kb8_neighbour_tables(orbm_t *m, int rr, bool rig, int K, const orbm_keyframe_t *k2, const int32_t *n_left2, const float *ep, const float *cams1,
+static int kb8_neighbour_tables(const Refuse &refuse, int rr, bool rig, int K, const orbm_keyframe_t *k2, const int32_t *n_left2, const float *ep, const float *cams1,
                                 const float *cams2, const float *T12, const uint8_t *skip, std::vector<TriNb> &nb, std::vector<TriKb8Consts> &consts) {
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
   if (rr == 0 && (!n_left2 || !ep || !cams1 || !cams2 || !T12)) return refuse(-1, "NULL n_left2, epipole, camera or pose table");
   nb.resize((size_t)K);
   consts.resize((size_t)K);
@@ -3608,15 +3477,92 @@ int orbm_search_for_triangulation_kb8_neighbours(orbm_t *m, const orbm_keyframe_
                                                  int bOnlyStereo, int bCoarse, int32_t *matches12, int32_t *nmatches) {
   if (!m || !k1) return ORBX_E_ARG;
   const bool rig = n_left1 != -1;
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "neighbour"};
   if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
   const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
   if (rr < 0) return rr;
   if (K > 0 && (!matches12 || !nmatches)) return refuse(-1, "NULL result table");
   std::vector<TriNb> nb;
   std::vector<TriKb8Consts> consts;
-  { const int rt = kb8_neighbour_tables(m, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
-  return triangulation_neighbours(m, k1, n_left1, K, k2, skip, nb, &consts, bOnlyStereo, bCoarse, matches12, nmatches);
+  { const int rt = kb8_neighbour_tables(refuse, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
+  return triangulation_neighbours(m, "neighbour", k1, n_left1, K, k2, skip, nb, &consts, bOnlyStereo, bCoarse, matches12, nmatches);
+}
+
+// ---- The pair forms (ORBmatcher.cc:981-1222) --------------------------------------------------------------------------------------
+// Pinhole: its own kernel with F12, the epipole and the scale tables by value.  (Served as the K = 1 call of the one-call form it
+// measured 2 to 6 % slower per call, profiles/host_layer_bench.txt; the KannalaBrandt8 form below did not.)
+int orbm_search_for_triangulation(orbm_t *m, const orbm_keyframe_t *k1, const orbm_keyframe_t *k2, const float *R1w, const float *t1w,
+                                  const float *R2w, const float *t2w, const float *Cw1, const float *cam1, const float *cam2,
+                                  int bOnlyStereo, int bCoarse, int checkOri, int32_t *matches12) {
+  if (!m || !k1 || !k2 || !R1w || !t1w || !R2w || !t2w || !Cw1 || !cam1 || !cam2 || !matches12) return ORBX_E_ARG;
+  if (k1->n < 0 || k2->n < 0 || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return ORBX_E_ARG;
+  for (int i = 0; i < k1->n; i++) matches12[i] = -1;
+  if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
+  if (!k1->u_right || !k2->u_right || !k1->has_mappoint || !k2->has_mappoint) return ORBX_E_ARG;
+  TriParams T;
+  memset(&T, 0, sizeof(T));
+  pinhole_pair_geometry(R1w, t1w, R2w, t2w, Cw1, cam1, cam2, T.F12, T.epx, T.epy);
+  std::vector<TriItem> items;
+  { const int rc = triangulation_items(m, k1, k2, k1->u_right, bOnlyStereo, items); if (rc < 0) return rc; }
+  int nmatches = 0;
+  if (!items.empty()) {
+    MCHECK(m, hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t n1 = (size_t)k1->n, n2 = (size_t)k2->n;
+    Staging S{m};
+    const auto KP1 = S.add(k1->keys_un, n1);
+    const auto DESC1 = S.add(k1->descriptors, 32 * n1);
+    const auto UR1 = S.add(k1->u_right, n1);
+    const auto DESC2 = S.add(k2->descriptors, 32 * n2);
+    const auto KP2 = S.add(k2->keys_un, n2);
+    const auto UR2 = S.add(k2->u_right, n2);
+    const auto HASMP2 = S.add(k2->has_mappoint, n2);
+    const auto NODE_IDX2 = S.add(k2->node_idx, (size_t)k2->node_start[k2->n_nodes]);
+    const auto ITEMS = S.add(items.data(), items.size());
+    const auto MATCHES12 = S.out<int32_t>(n1);
+    const int rs = S.upload(s, false);
+    if (rs < 0) return rs;
+    MCHECK(m, S.fill(s, MATCHES12, MATCHES12, 0xff));
+    T.kp1 = (const float *)S.dev(KP1); T.desc1 = (const uint32_t *)S.dev(DESC1); T.ur1 = S.dev(UR1);
+    T.desc2 = (const uint32_t *)S.dev(DESC2); T.kp2 = (const float *)S.dev(KP2); T.ur2 = S.dev(UR2);
+    T.hasmp2 = S.dev(HASMP2); T.node_idx2 = S.dev(NODE_IDX2);
+    T.items = S.dev(ITEMS); T.nitems = (int)items.size();
+    for (int l = 0; l < k2->nlevels; l++) { T.sf2[l] = k2->scale_factors[l]; T.sigma2_2[l] = k2->level_sigma2[l]; }
+    T.bOnlyStereo = bOnlyStereo; T.bCoarse = bCoarse;
+    T.matches12 = S.dev(MATCHES12);
+    hipLaunchKernelGGL(k_triangulation_match, dim3((T.nitems + 3) / 4), dim3(256), 0, s, T);
+    MCHECK(m, hipGetLastError());
+    MCHECK(m, hipMemcpyAsync(matches12, S.dev(MATCHES12), sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
+    MCHECK(m, hipStreamSynchronize(s));
+    for (int i = 0; i < k1->n; i++) nmatches += matches12[i] >= 0;
+  }
+  if (checkOri && nmatches > 0) nmatches = prune_pairs_by_rotation(k1, k2, matches12, nmatches);
+  return nmatches;
+}
+
+// KannalaBrandt8: the one-call search with K = 1 behind the entry's own front checks (no "neighbour 0: " in m->err), then the rotation
+// histogram.
+int orbm_search_for_triangulation_kb8(orbm_t *m, const orbm_keyframe_t *k1, int n_left1, const orbm_keyframe_t *k2, int n_left2, float ep_x, float ep_y,
+                                      const float *cams1, const float *cams2, const float *T12, int bOnlyStereo, int bCoarse, int checkOri,
+                                      int32_t *matches12) {
+  if (!m || !k1 || !k2 || !cams1 || !cams2 || !T12 || !matches12) return ORBX_E_ARG;
+  const bool rig = n_left1 != -1;
+  const Refuse refuse{m, nullptr};
+  if ((n_left1 == -1) != (n_left2 == -1)) return refuse(-1, "n_left: one keyframe with and one without a second camera");
+  if (k1->n < 0 || k2->n < 0 || n_left1 < -1 || n_left1 > k1->n || n_left2 < -1 || n_left2 > k2->n) return refuse(-1, "n or n_left out of range");
+  if (k1->nlevels < 1 || k1->nlevels > ORBX_MAX_LEVELS || k2->nlevels < 1 || k2->nlevels > ORBX_MAX_LEVELS) return refuse(-1, "nlevels out of range");
+  for (const orbm_keyframe_t *k : {k1, k2})
+    if (const char *why = tri_keyframe_refusal(k, rig)) return refuse(-1, why);
+  for (int i = 0; i < k1->n; i++) matches12[i] = -1;
+  if (k1->n == 0 || k2->n == 0 || k1->n_nodes == 0 || k2->n_nodes == 0) return 0;
+  if (const char *why = tri_members_refusal(k2)) return refuse(-1, why);
+  const int32_t nl2 = n_left2;
+  const float ep[2] = {ep_x, ep_y};
+  std::vector<TriNb> nb;
+  std::vector<TriKb8Consts> consts;
+  { const int rt = kb8_neighbour_tables(refuse, 0, rig, 1, k2, &nl2, ep, cams1, cams2, T12, nullptr, nb, consts); if (rt < 0) return rt; }
+  const int nmatches = triangulation_neighbours(m, nullptr, k1, n_left1, 1, k2, nullptr, nb, &consts, bOnlyStereo, bCoarse, matches12, nullptr);
+  return checkOri && nmatches > 0 ? prune_pairs_by_rotation(k1, k2, matches12, nmatches) : nmatches;
 }
 
 // ---- LocalMapping::CreateNewMapPoints: the searches and the body of the loop (LocalMapping.cc:470-905) -----------------------------
@@ -3682,7 +3628,7 @@ static const char *new_points_keyframe_refusal(const orbm_keyframe_t &k, const o
 static int new_points_refusal(orbm_t *m, int rr, const orbm_keyframe_t *k1, const orbm_keyframe_geometry_t *g1, bool rig, int K,
                               const orbm_keyframe_t *k2, const orbm_keyframe_geometry_t *g2, const uint8_t *skip, orbm_new_point_t *points, int cap,
                               uint8_t *status, int32_t *matches12, int32_t *nmatches) {
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "neighbour"};
   if (cap < 0 || (cap > 0 && !points)) return refuse(-1, "NULL point list or cap < 0");
   if (nmatches && !matches12) return refuse(-1, "nmatches without matches12");
   if (rr == 0) {
@@ -3720,7 +3666,7 @@ int orbm_create_new_map_points(orbm_t *m, const orbm_keyframe_t *k1, const orbm_
   for (int j = 0; j < K && rr == 0; j++)
     if (!(skip && skip[j])) pinhole_pair_geometry(R1w, t1w, R2w + 9 * j, t2w + 3 * j, Cw1, cam1, cam2 + 4 * j, nb[(size_t)j].F12, nb[(size_t)j].epx, nb[(size_t)j].epy);
   NewPointsCall np{g1, g2, 0, cam1, cam2, 4, nullptr, scale_factor1, th_far_points, far_points, status, {}};
-  const int rc = triangulation_neighbours(m, k1, -1, K, k2, skip, nb, nullptr, 0, bCoarse, matches12, nmatches, &np);
+  const int rc = triangulation_neighbours(m, "neighbour", k1, -1, K, k2, skip, nb, nullptr, 0, bCoarse, matches12, nmatches, &np);
   return rc < 0 ? rc : new_points_result(np, points, cap);
 }
 
@@ -3730,16 +3676,16 @@ int orbm_create_new_map_points_kb8(orbm_t *m, const orbm_keyframe_t *k1, const o
                                    float th_far_points, orbm_new_point_t *points, int cap, uint8_t *status, int32_t *matches12, int32_t *nmatches) {
   if (!m || !k1) return ORBX_E_ARG;
   const bool rig = n_left1 != -1;
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "neighbour " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "neighbour"};
   if (n_left1 < -1 || (k1->n >= 0 && n_left1 > k1->n)) return refuse(-1, "kf1: n_left out of range");
   const int rr = triangulation_neighbours_refusal(m, k1, rig, true, K, k2, skip);
   if (rr < 0) return rr;
   std::vector<TriNb> nb;
   std::vector<TriKb8Consts> consts;
-  { const int rt = kb8_neighbour_tables(m, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
+  { const int rt = kb8_neighbour_tables(refuse, rr, rig, K, k2, n_left2, ep, cams1, cams2, T12, skip, nb, consts); if (rt < 0) return rt; }
   { const int rn = new_points_refusal(m, rr, k1, g1, rig, K, k2, g2, skip, points, cap, status, matches12, nmatches); if (rn < 0) return rn; }
   NewPointsCall np{g1, g2, 1, cams1, cams2, 16, n_left2, scale_factor1, th_far_points, far_points, status, {}};
-  const int rc = triangulation_neighbours(m, k1, n_left1, K, k2, skip, nb, &consts, 0, bCoarse, matches12, nmatches, &np);
+  const int rc = triangulation_neighbours(m, "neighbour", k1, n_left1, K, k2, skip, nb, &consts, 0, bCoarse, matches12, nmatches, &np);
   return rc < 0 ? rc : new_points_result(np, points, cap);
 }
 
@@ -3989,24 +3935,27 @@ static int bow_core(orbm_t *m, const orbm_keyframe_t *kf, const orbm_keyframe_t 
   hipStream_t s = m->stream;
   const size_t nidxKF = (size_t)kf->node_start[kf->n_nodes], nidxF = (size_t)f->node_start[f->n_nodes];
   const size_t out_bytes = sizeof(int32_t) * (size_t)nout;
-  enum { DESC_KF, DESC_F, HASMP_KF, NODE_IDX_KF, NODE_IDX_F, ITEMS, OUT, HASMP_F, NPARTS };
-  void *d[NPARTS];
-  const int rs = stage(m, s, {{kf->descriptors, 32 * (size_t)kf->n}, {f->descriptors, 32 * (size_t)f->n}, {kf->has_mappoint, (size_t)kf->n},
-                              {kf->node_idx, sizeof(int32_t) * nidxKF}, {f->node_idx, sizeof(int32_t) * nidxF}, {items.data(), sizeof(BowItem) * items.size()},
-                              {out, out_bytes}, {f->has_mappoint, kf_kf ? (size_t)f->n : 0}}, d);
+  Staging S{m};
+  const auto DESC_KF = S.add(kf->descriptors, 32 * (size_t)kf->n), DESC_F = S.add(f->descriptors, 32 * (size_t)f->n);
+  const auto HASMP_KF = S.add(kf->has_mappoint, (size_t)kf->n);
+  const auto NODE_IDX_KF = S.add(kf->node_idx, nidxKF), NODE_IDX_F = S.add(f->node_idx, nidxF);
+  const auto ITEMS = S.add(items.data(), items.size());
+  const auto OUT = S.add((const int32_t *)out, (size_t)nout);   // uploaded: the rows start at the caller's -1
+  const auto HASMP_F = S.add(f->has_mappoint, kf_kf ? (size_t)f->n : 0);
+  const int rs = S.upload(s, false);
   if (rs < 0) return rs;
   BowParams B;
   memset(&B, 0, sizeof(B));
-  B.descKF = (const uint32_t *)d[DESC_KF]; B.descF = (const uint32_t *)d[DESC_F]; B.hasmpKF = (const uint8_t *)d[HASMP_KF];
-  B.node_idxKF = (const int32_t *)d[NODE_IDX_KF]; B.node_idxF = (const int32_t *)d[NODE_IDX_F];
-  B.items = (const BowItem *)d[ITEMS]; B.nitems = (int)items.size();
+  B.descKF = (const uint32_t *)S.dev(DESC_KF); B.descF = (const uint32_t *)S.dev(DESC_F); B.hasmpKF = S.dev(HASMP_KF);
+  B.node_idxKF = S.dev(NODE_IDX_KF); B.node_idxF = S.dev(NODE_IDX_F);
+  B.items = S.dev(ITEMS); B.nitems = (int)items.size();
   B.nnratio = nnratio;
   B.nleftF = nleftF >= 0 ? nleftF : 0x7fffffff;
-  if (kf_kf) { B.match12 = (int32_t *)d[OUT]; B.hasmpF = (const uint8_t *)d[HASMP_F]; B.strict = 1; }
-  else B.matchF = (int32_t *)d[OUT];
+  if (kf_kf) { B.match12 = S.dev(OUT); B.hasmpF = S.dev(HASMP_F); B.strict = 1; }
+  else B.matchF = S.dev(OUT);
   hipLaunchKernelGGL(k_bow_match, dim3((B.nitems + 3) / 4), dim3(256), 0, s, B);
   MCHECK(m, hipGetLastError());
-  MCHECK(m, hipMemcpyAsync(out, d[OUT], out_bytes, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipMemcpyAsync(out, S.dev(OUT), out_bytes, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   int nmatches = 0;
   for (int i = 0; i < nout; i++) nmatches += out[i] >= 0 ? 1 : 0;
@@ -4045,7 +3994,7 @@ int orbm_search_by_bow_keyframes(orbm_t *m, const orbm_keyframe_t *kf1, const or
 static int bow_candidates(orbm_t *m, const orbm_keyframe_t *fixed, int K, const orbm_keyframe_t *cands, const uint8_t *skip, bool kf_kf,
                           int nleftF, float nnratio, int checkOri, int32_t *rows, int32_t *nmatches) {
   if (!m || !fixed) return ORBX_E_ARG;
-  auto refuse = [&](int j, const char *why) { m->err = j < 0 ? std::string(why) : "candidate " + std::to_string(j) + ": " + why; return ORBX_E_ARG; };
+  const Refuse refuse{m, "candidate"};
   if (K < 0) return refuse(-1, "K < 0");
   if (K > 0 && (!cands || !rows || !nmatches)) return refuse(-1, "NULL candidate or result table");
   if (fixed->n < 0) return refuse(-1, "fixed operand: n < 0");
@@ -4109,59 +4058,52 @@ static int bow_candidates(orbm_t *m, const orbm_keyframe_t *fixed, int K, const 
   std::vector<BowCand> &rec = m->bow_cands;
   rec.resize((size_t)K);
   memset(rec.data(), 0, sizeof(BowCand) * (size_t)K);
-  std::vector<Part> parts;
-  std::vector<size_t> offs;
-  parts.reserve(8 + 4 * (size_t)K);
-  size_t off = 0;
-  auto add = [&](const void *src, size_t bytes) { parts.push_back(Part{src, bytes}); offs.push_back(off); off += stage_span(bytes); return parts.size() - 1; };
+  Staging S{m};
   const size_t nf = (size_t)fixed->n;
   const bool fixed_hasmp = kf_kf;                                  // the frame's map points are not read (:273-469)
-  const size_t F_DESC = add(fixed->descriptors, 32 * nf), F_HASMP = add(fixed_hasmp ? fixed->has_mappoint : nullptr, fixed_hasmp ? nf : 0);
-  const size_t F_IDX = add(fixed->node_idx, sizeof(int32_t) * (size_t)fixed->node_start[fixed->n_nodes]);
-  const size_t F_ANG = add(pack_angles(*fixed), checkOri ? sizeof(float) * nf : 0);
+  const size_t F_DESC = S.offset(S.add(fixed->descriptors, 32 * nf));
+  const size_t F_HASMP = S.offset(S.add(fixed_hasmp ? fixed->has_mappoint : nullptr, fixed_hasmp ? nf : 0));
+  const size_t F_IDX = S.offset(S.add(fixed->node_idx, (size_t)fixed->node_start[fixed->n_nodes]));
+  const size_t F_ANG = S.offset(S.add(pack_angles(*fixed), checkOri ? nf : 0));
   for (int j = 0; j < K; j++) {
     if (!live[(size_t)j]) continue;
     const orbm_keyframe_t &c = cands[j];
     const size_t nc = (size_t)c.n;
-    const size_t desc = offs[add(c.descriptors, 32 * nc)], hasmp = offs[add(c.has_mappoint, nc)];
-    const size_t idx = offs[add(c.node_idx, sizeof(int32_t) * (size_t)c.node_start[c.n_nodes])];
-    const size_t an = offs[add(pack_angles(c), checkOri ? sizeof(float) * nc : 0)];
+    const size_t desc = S.offset(S.add(c.descriptors, 32 * nc)), hasmp = S.offset(S.add(c.has_mappoint, nc));
+    const size_t idx = S.offset(S.add(c.node_idx, (size_t)c.node_start[c.n_nodes]));
+    const size_t an = S.offset(S.add(pack_angles(c), checkOri ? nc : 0));
     BowCand &R = rec[(size_t)j];
     if (kf_kf) {
-      R.descW = offs[F_DESC]; R.hasmpW = offs[F_HASMP]; R.node_idxW = offs[F_IDX]; R.angW = offs[F_ANG];
+      R.descW = F_DESC; R.hasmpW = F_HASMP; R.node_idxW = F_IDX; R.angW = F_ANG;
       R.descS = desc; R.hasmpS = hasmp; R.node_idxS = idx; R.angS = an;
     } else {
       R.descW = desc; R.hasmpW = hasmp; R.node_idxW = idx; R.angW = an;
-      R.descS = offs[F_DESC]; R.hasmpS = BOW_NO_HASMP; R.node_idxS = offs[F_IDX]; R.angS = offs[F_ANG];
+      R.descS = F_DESC; R.hasmpS = BOW_NO_HASMP; R.node_idxS = F_IDX; R.angS = F_ANG;
     }
     R.n_left = nleftF >= 0 ? nleftF : 0x7fffffff;
   }
-  const size_t RECS = add(rec.data(), sizeof(BowCand) * (size_t)K), ITEMS = add(items.data(), sizeof(BowCandItem) * ni);
+  const auto RECS = S.add(rec.data(), (size_t)K);
+  const auto ITEMS = S.add(items.data(), ni);
   const size_t rows_bytes = sizeof(int32_t) * (size_t)K * nout;
-  const size_t ROWS = add(nullptr, rows_bytes), COUNTS = add(nullptr, sizeof(int32_t) * (size_t)K);
+  const auto ROWS = S.out<int32_t>((size_t)K * nout), COUNTS = S.out<int32_t>((size_t)K);
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  std::vector<void *> d(parts.size());
-  { const int rs = stage(m, s, parts.data(), parts.size(), d.data(), true); if (rs < 0) return rs; }
-  const uint8_t *block = (const uint8_t *)m->d_block.p;
-  for (size_t i = 0; i < parts.size(); i++)   // the records' offsets were formed here, stage() formed the addresses: they must agree
-    if (d[i] && d[i] != block + offs[i]) { m->err = "SearchByBoW candidates: staging layout"; return ORBX_E_HIP; }
-  MCHECK(m, hipMemsetAsync(d[ROWS], 0xff, rows_bytes, s));
+  { const int rs = S.upload(s); if (rs < 0) return rs; }
+  MCHECK(m, S.fill(s, ROWS, ROWS, 0xff));
   BowCandParams B;
   memset(&B, 0, sizeof(B));
-  B.block = block; B.cands = (const BowCand *)d[RECS]; B.items = (const BowCandItem *)d[ITEMS]; B.nitems = (int)ni;
+  B.block = S.block(); B.cands = S.dev(RECS); B.items = S.dev(ITEMS); B.nitems = (int)ni;
   B.nout = fixed->n; B.nnratio = nnratio; B.kf_kf = kf_kf ? 1 : 0; B.checkOri = checkOri ? 1 : 0;
-  B.rows = (int32_t *)d[ROWS]; B.nmatches = (int32_t *)d[COUNTS];
+  B.rows = S.dev(ROWS); B.nmatches = S.dev(COUNTS);
   hipLaunchKernelGGL(k_bow_match_candidates, dim3((unsigned)((ni + 3) / 4)), dim3(256), 0, s, B);
   MCHECK(m, hipGetLastError());
   hipLaunchKernelGGL(k_bow_prune_candidates, dim3((unsigned)K), dim3(256), 0, s, B);
   MCHECK(m, hipGetLastError());
   // rows and counts are adjacent parts of the block: one copy into the pinned mirror
-  const size_t out_bytes = offs[COUNTS] + sizeof(int32_t) * (size_t)K - offs[ROWS];
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, d[ROWS]), d[ROWS], out_bytes, hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, ROWS, COUNTS));
   MCHECK(m, hipStreamSynchronize(s));
-  memcpy(rows, mirror_of(m, d[ROWS]), rows_bytes);
-  memcpy(nmatches, mirror_of(m, d[COUNTS]), sizeof(int32_t) * (size_t)K);
+  memcpy(rows, S.host(ROWS), rows_bytes);
+  memcpy(nmatches, S.host(COUNTS), sizeof(int32_t) * (size_t)K);
   long long sum = 0;
   for (int j = 0; j < K; j++) sum += nmatches[j];
   return (int)std::min<long long>(sum, 0x7fffffff);
@@ -4188,12 +4130,15 @@ int orbm_distinctive_descriptors(orbm_t *m, int nmp, const int32_t *start, const
   if (start[0] < 0 || (total > 0 && !desc)) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  void *d[3];   // descriptors, start, best
-  const int rs = stage(m, s, {{desc, 32 * (size_t)total}, {start, sizeof(int32_t) * (size_t)(nmp + 1)}, {nullptr, sizeof(int32_t) * (size_t)nmp}}, d);
+  Staging S{m};
+  const auto hdesc = S.add(desc, 32 * (size_t)total);
+  const auto hstart = S.add(start, (size_t)nmp + 1);
+  const auto hbest = S.out<int32_t>((size_t)nmp);
+  const int rs = S.upload(s, false);
   if (rs < 0) return rs;
-  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, s, (const uint32_t *)d[0], (const int32_t *)d[1], nmp, (int32_t *)d[2]);
+  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, s, (const uint32_t *)S.dev(hdesc), (const int32_t *)S.dev(hstart), nmp, S.dev(hbest));
   MCHECK(m, hipGetLastError());
-  MCHECK(m, hipMemcpyAsync(best, d[2], sizeof(int32_t) * (size_t)nmp, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipMemcpyAsync(best, S.dev(hbest), sizeof(int32_t) * (size_t)nmp, hipMemcpyDeviceToHost, s));
   MCHECK(m, hipStreamSynchronize(s));
   return 0;
 }
@@ -4230,8 +4175,7 @@ int orbm_update_map_points(orbm_t *m, const orbm_map_point_update_t *u, int32_t 
   P.nmp = nmp; P.best = S.dev(hbest); P.normal = S.dev(hnor); P.min_dist = S.dev(hmin); P.max_dist = S.dev(hmax);
   hipLaunchKernelGGL(k_update_map_points, dim3((unsigned)((nmp + 3) / 4)), dim3(256), 0, s, P);
   MCHECK(m, hipGetLastError());
-  const uint8_t *lo = (const uint8_t *)S.dev(hbest);
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hmax) + NP) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, hbest, hmax));
   MCHECK(m, hipStreamSynchronize(s));
   memcpy(best, S.host(hbest), sizeof(int32_t) * NP);
   const float *nor = S.host(hnor), *mind = S.host(hmin), *maxd = S.host(hmax);
@@ -4291,20 +4235,22 @@ static const char *culling_refusal(const orbm_culling_t *c) {
 // The tables and the loop's state as parts of one staged block.  n_obs and bad come last, so that the one-call form's outputs follow
 // them and everything that goes back is one span.
 struct CullParts {
-  PartOf<uint8_t> skip, erasable, obs_w, bad, zero, row_stat;
+  PartOf<uint8_t> skip, erasable, obs_w, bad, touched, row_stat;
   PartOf<float> th_depth, row_depth;
-  PartOf<int32_t> row_start, row_point, row_level, obs_start, obs_level, obs_kf, n_obs;
-  size_t K, NP, zero_bytes;
+  PartOf<int32_t> row_start, row_point, row_level, obs_start, obs_level, obs_kf, n_obs, sums;
+  size_t K;
 };
 static CullParts culling_add(Staging &S, const orbm_culling_t *c, const uint8_t *erasable) {
   CullParts H;
-  const size_t K = H.K = (size_t)c->K, NP = H.NP = (size_t)c->P, R = (size_t)c->row_start[K], E = (size_t)c->obs_start[NP];
+  const size_t K = H.K = (size_t)c->K, NP = (size_t)c->P, R = (size_t)c->row_start[K], E = (size_t)c->obs_start[NP];
   H.skip = S.add(c->skip, K); H.erasable = S.add(erasable, K); H.th_depth = S.add(c->th_depth, K);
   H.row_start = S.add(c->row_start, K + 1); H.row_point = S.add(c->row_point, R); H.row_level = S.add(c->row_level, R);
   H.row_depth = S.add(c->row_depth, c->mono ? 0 : R);
   H.obs_start = S.add(c->obs_start, NP + 1); H.obs_level = S.add(c->obs_level, E); H.obs_w = S.add(c->obs_w, E); H.obs_kf = S.add(c->obs_kf, E);
-  H.zero_bytes = stage_span(NP) + 2 * sizeof(int32_t) * K;       // touched [P], sum_mps [K], sum_red [K]: cleared on the device
-  H.zero = S.out<uint8_t>(H.zero_bytes); H.row_stat = S.out<uint8_t>(R);
+  // touched [P], sum_mps [K], sum_red [K]: cleared on the device as one span.  With P == 0 touched is an empty part (NULL on the device):
+  // the kernels index it with a row's point only, and a row's point lies in [0, P)
+  H.touched = S.out<uint8_t>(NP); H.sums = S.out<int32_t>(2 * K);
+  H.row_stat = S.out<uint8_t>(R);
   H.n_obs = S.add(c->n_obs, NP); H.bad = S.add(c->bad, NP);
   return H;
 }
@@ -4315,14 +4261,14 @@ static CullParams culling_bind(const Staging &S, const CullParts &H, const orbm_
   P.row_start = S.dev(H.row_start); P.row_point = S.dev(H.row_point); P.row_level = S.dev(H.row_level); P.row_depth = S.dev(H.row_depth);
   P.obs_start = S.dev(H.obs_start); P.obs_level = S.dev(H.obs_level); P.obs_w = S.dev(H.obs_w); P.obs_kf = S.dev(H.obs_kf);
   P.bad = S.dev(H.bad); P.n_obs = S.dev(H.n_obs);
-  P.touched = S.dev(H.zero);
-  P.sum_mps = (int32_t *)(S.dev(H.zero) + stage_span(H.NP)); P.sum_red = P.sum_mps + H.K;
+  P.touched = S.dev(H.touched);
+  P.sum_mps = S.dev(H.sums); P.sum_red = P.sum_mps + H.K;
   P.row_stat = S.dev(H.row_stat);
   return P;
 }
 // The loop-entry status of every row (k_cull_count) behind the upload
-static int culling_count(orbm_t *m, hipStream_t s, const CullParams &P, const CullParts &H, const orbm_culling_t *c) {
-  MCHECK(m, hipMemsetAsync(P.touched, 0, H.zero_bytes, s));
+static int culling_count(orbm_t *m, hipStream_t s, const Staging &S, const CullParams &P, const CullParts &H, const orbm_culling_t *c) {
+  MCHECK(m, S.fill(s, H.touched, H.sums, 0));
   int most = 0;
   for (int k = 0; k < c->K; k++) most = std::max(most, c->row_start[k + 1] - c->row_start[k]);
   if (most > 0) {
@@ -4349,12 +4295,11 @@ int orbm_keyframe_culling(orbm_t *m, const orbm_culling_t *c, const uint8_t *era
   int rc = S.upload(s);
   if (rc < 0) return rc;
   const CullParams P = culling_bind(S, H, c);
-  if ((rc = culling_count(m, s, P, H, c)) < 0) return rc;
+  if ((rc = culling_count(m, s, S, P, H, c)) < 0) return rc;
   CullWalkParams W{0, -1, 0, 0, S.dev(hmps), S.dev(hred), S.dev(hcul), S.dev(hres)};
   hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(CULL_WALK_THREADS), 0, s, P, W);
   MCHECK(m, hipGetLastError());
-  const uint8_t *lo = NP ? (const uint8_t *)S.dev(H.n_obs) : (const uint8_t *)S.dev(hmps);
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hcul) + K) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, H.n_obs, hcul));
   MCHECK(m, hipStreamSynchronize(s));
   memcpy(n_mps, S.host(hmps), sizeof(int32_t) * K); memcpy(n_red, S.host(hred), sizeof(int32_t) * K); memcpy(culled, S.host(hcul), K);
   if (n_obs_out && NP) memcpy(n_obs_out, S.host(H.n_obs), sizeof(int32_t) * NP);
@@ -4377,10 +4322,9 @@ int orbm_keyframe_culling_open(orbm_t *m, const orbm_culling_t *c) {
   int rc = S.upload(s);
   if (rc < 0) return rc;
   CullParams P = culling_bind(S, H, c);
-  if ((rc = culling_count(m, s, P, H, c)) < 0) return rc;
+  if ((rc = culling_count(m, s, S, P, H, c)) < 0) return rc;
   // the block moves into the walk's own buffer: other entries reuse d_block between the steps
-  size_t bytes = 0;
-  for (int i = 0; i < S.n; i++) bytes += stage_span(S.parts[i].bytes);
+  const size_t bytes = S.total;
   MCHECK(m, m->d_cull.reserve(m->d_cull.bytes >= bytes ? bytes : 2 * bytes));
   MCHECK(m, hipMemcpyAsync(m->d_cull.p, m->d_block.p, bytes, hipMemcpyDeviceToDevice, s));
   MCHECK(m, hipStreamSynchronize(s));   // the pinned mirror is free for the next entry
@@ -4411,8 +4355,7 @@ int orbm_keyframe_culling_step(orbm_t *m, int applied, int32_t *k, int32_t *n_mp
   m->cull_any = m->cull_any || erase;
   hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(CULL_WALK_THREADS), 0, s, m->cull, W);
   MCHECK(m, hipGetLastError());
-  const uint8_t *lo = (const uint8_t *)S.dev(hmps);
-  MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)((const uint8_t *)(S.dev(hres) + 1) - lo), hipMemcpyDeviceToHost, s));
+  MCHECK(m, S.download(s, hmps, hres));
   MCHECK(m, hipStreamSynchronize(s));
   const int at = *S.host(hres);
   for (int j = first; j <= std::min(at, K - 1); j++) { n_mps[j] = S.host(hmps)[j]; n_red[j] = S.host(hred)[j]; }
@@ -4587,10 +4530,9 @@ struct TvDevice {
   PartOf<uint8_t> mask_in, mask, good, status;
   PartOf<TvCamera> cams;
   size_t I, N, n1;
-  int max_hyp;
-  // iterations == 0: no model stage; max_hyp == 0: no CheckRT stage; inliers: the caller's mask for CheckRT alone
+  // iterations == 0: no model stage; hyp == 0: no CheckRT stage; inliers: the caller's mask for CheckRT alone
   int upload(const TvProblem &Q, int iterations, const int32_t *set_idx, int hyp, const uint8_t *inliers) {
-    I = (size_t)iterations; N = (size_t)Q.N; n1 = (size_t)Q.n1; max_hyp = hyp;
+    I = (size_t)iterations; N = (size_t)Q.N; n1 = (size_t)Q.n1;
     const size_t H = (size_t)hyp;
     mx = S.add(Q.mx.data(), 4 * N); first = S.add(Q.first.data(), N);
     pn1 = S.add(Q.pn1.data(), I ? 2 * n1 : 0); pn2 = S.add(Q.pn2.data(), I ? 2 * (size_t)Q.n2 : 0);
@@ -4619,8 +4561,7 @@ struct TvDevice {
     MCHECK(m, hipGetLastError());
     hipLaunchKernelGGL(k_tv_winner, dim3(2), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
-    const uint8_t *lo = (const uint8_t *)S.dev(H21);
-    MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)(S.dev(mask) + 2 * N - lo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, S.download(s, H21, mask));
     MCHECK(m, hipStreamSynchronize(s));
     R.H21.assign(S.host(H21), S.host(H21) + 9 * I); R.H12.assign(S.host(H12), S.host(H12) + 9 * I);
     R.F21.assign(S.host(F21), S.host(F21) + 9 * I); R.score.assign(S.host(score), S.host(score) + 2 * I);
@@ -4634,8 +4575,7 @@ struct TvDevice {
     const size_t H = (size_t)nhyp;
     two_view_cameras(K, sigma, nhyp, T, S.host(cams));
     MCHECK(m, hipMemcpyAsync(S.dev(cams), S.host(cams), sizeof(TvCamera) * H, hipMemcpyHostToDevice, s));
-    uint8_t *zlo = (uint8_t *)S.dev(p3d);
-    MCHECK(m, hipMemsetAsync(zlo, 0, (size_t)((uint8_t *)(S.dev(nGood) + max_hyp) - zlo), s));   // vP3D, vbGood, nGood
+    MCHECK(m, S.fill(s, p3d, nGood, 0));   // vP3D, vbGood, nGood
     TvCheckParams P;
     P.cams = S.dev(cams); P.mx = (const float4 *)S.dev(mx); P.first = S.dev(first); P.mask = d_mask;
     P.nhyp = nhyp; P.N = (int)N; P.n1 = (int)n1;
@@ -4645,7 +4585,7 @@ struct TvDevice {
     MCHECK(m, hipGetLastError());
     hipLaunchKernelGGL(k_tv_cos_rank, dim3((unsigned)((N + 255) / 256), (unsigned)nhyp), dim3(256), 0, s, P);
     MCHECK(m, hipGetLastError());
-    MCHECK(m, hipMemcpyAsync(mirror_of(m, zlo), zlo, (size_t)((uint8_t *)(S.dev(cos_rank) + max_hyp) - zlo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, S.download(s, p3d, cos_rank));
     MCHECK(m, hipStreamSynchronize(s));
     C.p3d.assign(S.host(p3d), S.host(p3d) + 3 * H * n1); C.good.assign(S.host(good), S.host(good) + H * n1);
     C.status.assign(S.host(status), S.host(status) + H * N);
@@ -5022,8 +4962,7 @@ struct Sim3Device {
       hipLaunchKernelGGL(k_sim3_winner, dim3(1), dim3(256), 0, s, P);
       MCHECK(m, hipGetLastError());
     }
-    const uint8_t *lo = (const uint8_t *)S.dev(counts);
-    MCHECK(m, hipMemcpyAsync(mirror_of(m, lo), lo, (size_t)(S.dev(vb) + n1 + 1 - lo), hipMemcpyDeviceToHost, s));
+    MCHECK(m, S.download(s, counts, vb));
     MCHECK(m, hipStreamSynchronize(s));
     wall_ms[3] = ms_since(t_check);
     if (counts_out) memcpy(counts_out, S.host(counts), sizeof(int32_t) * I);
@@ -5216,11 +5155,13 @@ int orbm_knn_match2(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, int n
   if (nc == 0) { for (int i = 0; i < 2 * nq; i++) { idx2[i] = -1; dist2[i] = -1; } return 0; }
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  void *d[3];   // queries, candidates, (idx, dist)
-  const int rs = stage(m, s, {{q, 32 * (size_t)nq}, {c, 32 * (size_t)nc}, {nullptr, sizeof(int32_t) * 4 * (size_t)nq}}, d);
+  Staging S{m};
+  const auto hq = S.add(q, 32 * (size_t)nq), hc = S.add(c, 32 * (size_t)nc);
+  const auto hout = S.out<int32_t>(4 * (size_t)nq);   // idx, dist
+  const int rs = S.upload(s, false);
   if (rs < 0) return rs;
-  const uint32_t *d_q = (const uint32_t *)d[0], *d_c = (const uint32_t *)d[1];
-  int32_t *d_idx = (int32_t *)d[2], *d_dist = d_idx + 2 * (size_t)nq;
+  const uint32_t *d_q = (const uint32_t *)S.dev(hq), *d_c = (const uint32_t *)S.dev(hc);
+  int32_t *d_idx = S.dev(hout), *d_dist = d_idx + 2 * (size_t)nq;
   // matrix-pipe form (orb_match_mfma.h) unless the vector-ALU engine is selected; its keys carry the train index in 20 bits
   if (m->hamming_engine >= 1 && nc < (1 << 20))
     hipLaunchKernelGGL(k_knn2_mfma, dim3((nq + MF_NT - 1) / MF_NT), dim3(MF_NT), 0, s, d_q, nq, d_c, nc, d_idx, d_dist);
@@ -5237,11 +5178,13 @@ int orbm_hamming_matrix(orbm_t *m, const uint8_t *q, int nq, const uint8_t *c, i
   if (!m || !q || !c || !dist || nq <= 0 || nc <= 0) return ORBX_E_ARG;
   MCHECK(m, hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  void *d[3];   // queries, candidates, the nq x nc matrix (downloaded straight to the caller)
-  const int rs = stage(m, s, {{q, 32 * (size_t)nq}, {c, 32 * (size_t)nc}, {nullptr, sizeof(uint16_t) * (size_t)nq * nc}}, d);
+  Staging S{m};
+  const auto hq = S.add(q, 32 * (size_t)nq), hc = S.add(c, 32 * (size_t)nc);
+  const auto hdist = S.out<uint16_t>((size_t)nq * nc);   // the nq x nc matrix, downloaded straight to the caller
+  const int rs = S.upload(s, false);
   if (rs < 0) return rs;
-  const uint32_t *d_q = (const uint32_t *)d[0], *d_c = (const uint32_t *)d[1];
-  uint16_t *d_dist = (uint16_t *)d[2];
+  const uint32_t *d_q = (const uint32_t *)S.dev(hq), *d_c = (const uint32_t *)S.dev(hc);
+  uint16_t *d_dist = S.dev(hdist);
   constexpr int QSLAB = 128;   // query rows per workgroup of the matrix-pipe form: four tiles behind one expansion of its 256 candidates
   if (m->hamming_engine >= 1 && (nq + QSLAB - 1) / QSLAB <= 65535)
     hipLaunchKernelGGL(k_hamming_matrix_mfma, dim3((nc + MF_NT - 1) / MF_NT, (nq + QSLAB - 1) / QSLAB), dim3(MF_NT), 0, s, d_q, nq, d_c, nc, d_dist, QSLAB);
@@ -5292,21 +5235,7 @@ static int voc_fail(const std::string &what) { g_voc_err = what; return ORBX_E_A
 static int voc_p2(int n) { int p2 = 2; while (p2 < n) p2 <<= 1; return p2; }
 
 // k_voc_collect sorts up to 16384 8-byte keys: 128 KiB of dynamic LDS, above the 64 KiB a kernel gets unasked.  Raised once per device.
-static hipError_t voc_raise_lds(int device) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  std::lock_guard<std::mutex> lock(mu);
-  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
-  if (done[device]) return hipSuccess;
-  const void *fn = reinterpret_cast<const void *>(&k_voc_collect);
-  hipFuncAttributes a;
-  hipError_t e = hipFuncGetAttributes(&a, fn);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ORB_LDS_LIMIT - (int)a.sharedSizeBytes);
-  if (e != hipSuccess) return e;
-  done[device] = true;
-  return hipSuccess;
-}
+static LdsOnce g_voc_lds;
 
 static void voc_free_work(VocWork *w) {
   if (!w) return;
@@ -5411,7 +5340,7 @@ orbv_t *orbv_create(const orbv_nodes_t *nodes, int device) {
   if (device < 0) return v;
   const hipError_t e0 = hipSetDevice(device);
   hipError_t e = e0;
-  if (e == hipSuccess) e = voc_raise_lds(device);
+  if (e == hipSuccess) e = raise_lds_once(g_voc_lds, device, {reinterpret_cast<const void *>(&k_voc_collect)});
   if (e == hipSuccess) e = hipMalloc(&v->d_desc, 32 * (size_t)N);
   if (e == hipSuccess) e = hipMalloc(&v->d_rec, sizeof(VocRec) * (size_t)N);
   if (e == hipSuccess) e = hipMalloc(&v->d_weight, sizeof(double) * (size_t)N);
@@ -5647,21 +5576,7 @@ static int kfdb_fail(const std::string &what) { g_kfdb_err = what; return ORBX_E
   } while (0)
 
 // k_kfdb_order sorts up to 16384 8-byte keys in dynamic LDS
-static hipError_t kfdb_raise_lds(int device) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  std::lock_guard<std::mutex> lock(mu);
-  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
-  if (done[device]) return hipSuccess;
-  const void *fn = reinterpret_cast<const void *>(&k_kfdb_order);
-  hipFuncAttributes a;
-  hipError_t e = hipFuncGetAttributes(&a, fn);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ORB_LDS_LIMIT - (int)a.sharedSizeBytes);
-  if (e != hipSuccess) return e;
-  done[device] = true;
-  return hipSuccess;
-}
+static LdsOnce g_kfdb_lds;
 
 // ids strictly ascending and below n_words, values finite
 static int kfdb_check_bow(const orbd_handle *d, const char *who, const uint32_t *id, const double *val, int n) {
@@ -5992,7 +5907,7 @@ orbd_t *orbd_create(int n_words, int scoring, int capacity, int device) {
   if (device < 0) return d;
   const hipError_t e0 = hipSetDevice(device);
   hipError_t e = e0;
-  if (e == hipSuccess) e = kfdb_raise_lds(device);
+  if (e == hipSuccess) e = raise_lds_once(g_kfdb_lds, device, {reinterpret_cast<const void *>(&k_kfdb_order)});
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc(&d->d_slot, sizeof(KfdbSlot) * (size_t)capacity);
   if (e == hipSuccess) e = hipMalloc(&d->d_bitmap, sizeof(uint32_t) * (size_t)d->bm_stride);

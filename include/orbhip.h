@@ -903,7 +903,10 @@ int orbm_search_for_triangulation_pred(orbm_t *m, const orbm_keyframe_t *kf1, co
  * (KannalaBrandt8.cpp:244-247, :343-412; the arithmetic of csrc/orb_ref_triangulate.h, cv::SVD restated as OpenCV's own float Jacobi,
  * [OPENCV-UNVERIFIED]).  One upload, three kernels - candidate lists, the test on EVERY candidate with the minimum accepted key per
  * keypoint of KF1 (= the first accepted entry of the order above), keys to indices - and one download; the rotation-histogram pruning
- * runs on the host afterwards.  bCoarse accepts the first entry of every list without the test.
+ * runs on the host afterwards.  bCoarse accepts the first entry of every list without the test.  It is
+ * orbm_search_for_triangulation_kb8_neighbours with K = 1 behind its own checks (which already were that entry's checks of a keyframe's
+ * arrays, listed below); orbm_last_error carries no "neighbour 0: ".  One text is new: a node_idx of kf1 outside [0, n) in a shared
+ * node, which left orbm_last_error as it was, now sets it to "kf1: keypoint index out of range" (the code, ORBX_E_ARG, is the same).
  * n_left? == -1: a keyframe without a second camera - keys_un = mvKeysUn, bStereo = u_right >= 0, the epipole gate (:1105-1113) is on;
  * cams? [1][8] = mpCamera's {fx, fy, cx, cy, k0..k3}; T12 [1][12] = [R12 | t12] (row stride 4) of :1007-1008.
  * n_left? >= 0: a two-camera rig - keys_un = [mvKeys; mvKeysRight], keypoint idx is the right camera's when idx >= n_left, bStereo is false

@@ -239,6 +239,26 @@ def subset(S, targets, points):
     return out
 
 
+def many_small_targets(S, rows, T=12, nP=5, order=(0, 1, 2, 3, 6), all_ur=False):
+    """T targets of 3 to 8 keypoints and nP points out of S: a call whose staged block has more parts than the 32 it holds inline.
+    The targets are copies of the targets `order` in turn, copy c cut to the keypoints that the reference gives to the chosen points
+    (rows[t] = oracle_row of the full target t) and the first of its other keypoints up to 3 + c % 6; the points are the first nP that
+    the first two targets of `order` both take, so each of their copies still fuses all of them.  all_ur: a target without mvuRight
+    gets one of all -1 (every keypoint monocular), so that every target brings three arrays."""
+    both = np.nonzero((rows[order[0]][1] >= 0) & (rows[order[1]][1] >= 0))[0][:nP]
+    assert len(both) == nP
+    out = subset(S, [order[c % len(order)] for c in range(T)], both)
+    small = []
+    for c, tg in enumerate(out["targets"]):
+        hits = sorted({int(v) for v in rows[order[c % len(order)]][1][both] if v >= 0})
+        rest = [i for i in range(len(tg["k"])) if i not in hits]
+        sel = np.array(sorted(hits + rest[:max(0, 3 + c % 6 - len(hits))]))
+        ur = tg["ur"][sel] if tg["ur"] is not None else (np.full(len(sel), -1, f32) if all_ur else None)
+        small.append(dict(tg, k=np.ascontiguousarray(tg["k"][sel]), d=np.ascontiguousarray(tg["d"][sel]), ur=ur, dupA={}, dupB={}))
+    out["targets"] = small
+    return out
+
+
 def product_target(pkg, tg):
     return pkg.FuseTarget(pkg.FrameView(tg["k"], tg["d"], tg["bounds"], u_right=tg["ur"]), tg["sf"], tg["inv_sigma2"], tg["log_sf"], tg["Tcw"], tg["Ow"],
                           tg["cam_type"], tg["cam"], tg["bf"])

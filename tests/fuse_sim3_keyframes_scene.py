@@ -55,6 +55,7 @@ def scene(undo=None):
 
 
 subset = FS.subset
+many_small_targets = FS.many_small_targets
 
 
 def truncated(S, t, n):

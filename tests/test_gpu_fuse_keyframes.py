@@ -73,6 +73,16 @@ def test_one_point_one_target(pkg, oracle, matcher):
         assert total == (1 if i == hit else 0)
 
 
+def test_more_parts_than_a_block_holds_inline(pkg, oracle, matcher):
+    """T = 12 targets of 3 to 8 keypoints, each with mvuRight, and nP = 5: 7 + 3 T + 2 = 45 parts, where a staged block holds 32 before
+    it grows.  Targets 0 and 1 take all five points in the full scene and their six copies keep those keypoints: 30 fused at least."""
+    S0 = FS.scene()
+    S = FS.many_small_targets(S0, oracle_rows(oracle, S0, 3.0, "full"), all_ur=True)
+    assert len(S["targets"]) == 12 and S["nP"] == 5 and all(3 <= len(tg["k"]) <= 8 and tg["ur"] is not None for tg in S["targets"])
+    total, bi, bd, nf = check(pkg, oracle, matcher, S, 3.0, "many small")
+    assert total >= 30
+
+
 def test_the_staged_block_grows_and_stays(pkg, oracle):
     m = pkg.ORBmatcher(0.6, False)                                # a fresh handle: nothing is allocated yet
     try:

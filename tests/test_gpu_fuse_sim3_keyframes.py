@@ -158,6 +158,16 @@ def test_a_scw_without_a_usable_scale_is_not_refused(pkg, matcher, what):
         assert n == 0 and np.array_equal(pi, bi[t]) and np.array_equal(pd, bd[t])
 
 
+def test_more_parts_than_a_block_holds_inline(pkg, oracle, matcher):
+    """T = 12 targets of 3 to 8 keypoints and nP = 5: 7 + 2 T + 4 = 35 parts, where a staged block holds 32 before it grows.  Targets 0
+    and 1 take all five points in the full scene and their six copies keep those keypoints: 30 fused at least."""
+    S0 = SS.scene()
+    S = SS.many_small_targets(S0, oracle_rows(oracle, S0, TH, "full"))
+    assert len(S["targets"]) == 12 and S["nP"] == 5 and all(3 <= len(tg["k"]) <= 8 for tg in S["targets"])
+    total, bi, bd, nf = check(pkg, oracle, matcher, S, TH, "many small")
+    assert total >= 30
+
+
 def test_the_staged_block_grows_and_stays(pkg, oracle):
     m = pkg.ORBmatcher(0.8, False)                                # a fresh handle: nothing is allocated yet
     try:

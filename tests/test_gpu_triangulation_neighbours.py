@@ -14,6 +14,7 @@ import pytest
 
 import triangulation_kb8_scene as SC
 import triangulation_neighbours_scene as NS
+from test_gpu_triangulation_kb8 import check as kb8_check
 from test_gpu_triangulation_kb8 import pred_of
 from test_triangulation_neighbours_abi import kb8_scenes
 
@@ -212,6 +213,104 @@ def test_refusals_name_the_neighbour(pkg, matcher):
         matcher.SearchForTriangulationKB8Neighbours(Q1, qviews, [T["ep"] for T in Ss], Ss[0]["cams1"], [T["cams2"] for T in Ss], [T["T12"] for T in Ss])
     rows, nm = pinhole(matcher, pkg, S)
     assert np.all(nm >= 10)
+
+
+# ---- the per-pair entries (KannalaBrandt8: the one-call form with K = 1 and the rotation histogram behind it) ----------------------
+def pinhole_pair(m, pkg, oracle, S, nb, check_ori=False, only_stereo=False):
+    """(nmatches, pairs) of orbm_search_for_triangulation for KF1 of S and the neighbour nb, equal to the oracle's member."""
+    m.mbCheckOrientation = check_ori
+    n, pairs = m.SearchForTriangulation(NS.product_kf1(pkg, S), NS.product_nb(pkg, nb), S["R1w"], S["t1w"], nb["R2w"], nb["t2w"], S["Cw1"], S["cam"], S["cam"],
+                                        bOnlyStereo=only_stereo)
+    n_ref, pairs_ref = oracle.search_for_triangulation(NS.oracle_kf1(oracle, S), NS.oracle_nb(oracle, nb), S["R1w"], S["t1w"], nb["R2w"], nb["t2w"], S["Cw1"],
+                                                       S["cam"], S["cam"], only_stereo=only_stereo, coarse=False, check_ori=check_ori)
+    assert n == n_ref == len(pairs) and np.array_equal(pairs, pairs_ref)
+    return n, pairs
+
+
+def node_of_65(fv, shared):
+    """(feature vector, key): a copy of fv in which the largest node that is also in `shared` holds exactly 65 keypoints, a wavefront
+    and one: short of that, members taken from the front of the other nodes stand IN FRONT of its own (random descriptors, far from
+    everything the node is asked for); beyond that, its first members move into a node nobody shares."""
+    fv = {k: list(v) for k, v in fv.items()}
+    key = max((k for k in fv if k in shared), key=lambda k: len(fv[k]))
+    if len(fv[key]) > 65:
+        fv[max(max(fv), max(shared)) + 1], fv[key] = fv[key][:-65], fv[key][-65:]
+    pad = []
+    for k in fv:
+        while k != key and len(fv[key]) + len(pad) < 65 and len(fv[k]) > 1:
+            pad.append(fv[k].pop(0))
+    fv[key] = pad + fv[key]
+    assert len(fv[key]) == 65
+    return fv, key
+
+
+def answer_in_the_last_place(fv, key, answers):
+    """fv with a keypoint that the search answers with moved to position 64 of node `key`, the one lane of the second trip.  It had the
+    smallest distance among the accepted candidates of its keypoint of KF1; a later position only helps it (`dist > bestDist -> skip`,
+    update on <=), so it stays an answer."""
+    last = next(int(v) for v in answers(fv) if v in fv[key])
+    fv = dict(fv)
+    fv[key] = [v for v in fv[key] if v != last] + [last]
+    assert fv[key].index(last) == 64 and last in answers(fv)
+    return fv
+
+
+@pytest.mark.parametrize("only_stereo", [False, True])
+def test_pinhole_pair_entry_prunes_by_rotation(pkg, oracle, matcher, only_stereo):
+    """checkOri exists on the pair entry alone.  The keypoint angles are random on both sides, so the three fullest of the 30 bins keep
+    a fraction of the pairs.  mvuRight is >= 0 for 60 % of the keypoints of both keyframes: bOnlyStereo drops the rest (:1057-1061,
+    :1088-1090)."""
+    S = NS.scene(NS.MAIN)
+    nb = S["nbs"][0]
+    assert all((ur >= 0).any() and (ur < 0).any() for ur in (S["ur1"], nb["ur"]))
+    plain, pairs = pinhole_pair(matcher, pkg, oracle, S, nb, only_stereo=only_stereo)
+    pruned, _ = pinhole_pair(matcher, pkg, oracle, S, nb, check_ori=True, only_stereo=only_stereo)
+    assert 1 <= pruned < plain
+    mono = (S["ur1"][pairs[:, 0]] < 0) | (nb["ur"][pairs[:, 1]] < 0)
+    assert not mono.any() if only_stereo else mono.any()
+
+
+def test_pinhole_pair_entry_node_of_65_members(pkg, oracle, matcher):
+    S = NS.scene(NS.MAIN)
+    nb = S["nbs"][3]
+    fv, key = node_of_65(nb["fv"], S["fv1"])
+    answers = lambda f: pinhole_pair(matcher, pkg, oracle, S, dict(nb, fv=f))[1][:, 1]
+    fv = answer_in_the_last_place(fv, key, answers)
+    assert pinhole_pair(matcher, pkg, oracle, S, dict(nb, fv=fv), check_ori=True)[0] >= 1
+
+
+def test_pinhole_pair_entry_nothing_to_search(pkg, matcher):
+    """n1 = 0, n2 = 0, no shared node: 0 and a row of -1 (written by the entry: the row arrives full of 7)."""
+    S = NS.scene(NS.MAIN)
+    none = pkg.KeyFrameView(np.zeros(0, SC.KP_DTYPE), np.zeros((0, 32), np.uint8), {}, S["sf1"], S["sigma2_1"], u_right=np.zeros(0, np.float32),
+                            has_mappoint=np.zeros(0, np.uint8))
+    K1, real, nonode, empty = NS.product_kf1(pkg, S), NS.product_nb(pkg, S["nbs"][0]), NS.product_nb(pkg, S["nbs"][1]), NS.product_nb(pkg, S["nbs"][2])
+    f = lambda v: np.ascontiguousarray(v, np.float32)
+    nb = S["nbs"][0]
+    poses = [f(v) for v in (S["R1w"], S["t1w"], nb["R2w"], nb["t2w"], S["Cw1"], S["cam"], S["cam"])]
+    for a, b in ((none, real), (K1, empty), (K1, nonode), (none, empty)):
+        s1, s2, row = a.struct(), b.struct(), np.full(max(a.N, 1), 7, np.int32)
+        for check_ori in (0, 1):
+            row[:] = 7
+            rc = matcher.L.orbm_search_for_triangulation(matcher.m, C.byref(s1), C.byref(s2), *[pkg._p(v) for v in poses], 0, 0, check_ori, pkg._p(row))
+            assert rc == 0 and np.all(row[:a.N] == -1) and np.all(row[a.N:] == 7)
+
+
+@pytest.mark.parametrize("rig", [False, True])
+def test_kb8_pair_entry_prunes_by_rotation(pkg, oracle, matcher, rig):
+    S = SC.scene(96, rig)
+    plain, _ = kb8_check(pkg, oracle, matcher, S, 4, route=False)
+    pruned, _ = kb8_check(pkg, oracle, matcher, S, 4, check_ori=True, route=False)
+    assert 1 <= pruned < plain
+
+
+@pytest.mark.parametrize("rig", [False, True])
+def test_kb8_pair_entry_node_of_65_members(pkg, oracle, matcher, rig):
+    S = SC.scene(96, rig)
+    fv2, key = node_of_65(SC.bow(S["d2"], 4), SC.bow(S["d1"], 4))
+    answers = lambda f: kb8_check(pkg, oracle, matcher, S, 4, fv2=f, route=False)[1][:, 1]
+    fv2 = answer_in_the_last_place(fv2, key, answers)
+    assert kb8_check(pkg, oracle, matcher, S, 4, check_ori=True, fv2=fv2, route=False)[0] >= 1
 
 
 def test_two_handles_on_two_threads(pkg, oracle):

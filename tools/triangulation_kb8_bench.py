@@ -6,7 +6,8 @@ Builds the scene of tests/triangulation_kb8_scene.py at --points (2600 points: 2
 per third point, both cameras of the rig, 100 vocabulary nodes - DBoW2's level for levelsup = 4 holds about that many), writes it to a
 scratch file, compiles tools/triangulation_kb8_harness.c against liborbhip.so and runs it: both routes in one process, alternated over
 --rounds, wall time per call.  With --profile a second run of the harness, the device route only, goes under
-rocprofv3 --kernel-trace --stats and the device times of its kernels are added.  Exit status 1 if the routes disagree.  Prints text
+rocprofv3 --kernel-trace --stats and the device times of its kernels are added (the entry runs the one-call form's kernels with K = 1:
+k_triangulation_candidates_neighbours, k_triangulation_kb8_predicate_neighbours, k_triangulation_kb8_result_neighbours).  Exit status 1 if the routes disagree.  Prints text
 lines and one JSON line and writes them to --out.  Needs a GPU; there is no fallback.
 
     python tools/triangulation_kb8_bench.py [--points 2600] [--nodes 100] [--rounds 7] [--calls 200] [--profile] [--out profiles/triangulation_kb8_bench.txt]
@@ -100,7 +101,7 @@ def main():
         kernels = {}
         with open(stats[0]) as f:
             for r in csv.DictReader(f):
-                if "k_triangulation" in r["Name"]:
+                if "k_triangulation" in r["Name"] and "_neighbours" in r["Name"]:
                     name = r["Name"].split("(")[0].split()[-1]
                     kernels[name] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3, min_us=float(r["MinNs"]) / 1e3, max_us=float(r["MaxNs"]) / 1e3)
         shutil.rmtree(prof, ignore_errors=True)
