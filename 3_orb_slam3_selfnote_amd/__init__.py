@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "orbx_clahe", "orbx_clahe_device", "orbx_remap_linear", "orbx_remap_linear_device",
     "orbx_clahe_batch_device", "orbx_remap_linear_batch_device", "orbx_clahe_band_lut_rows",
     "orbm_create", "orbm_destroy", "orbm_last_error", "orbm_descriptor_distance", "orbm_search_by_projection",
-    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_two_view_reconstruct", "orbm_two_view_reconstruct_host", "orbm_two_view_host_error", "orbm_two_view_models", "orbm_two_view_models_host", "orbm_two_view_check_rt", "orbm_two_view_check_rt_host", "orbm_sim3_solve", "orbm_sim3_solve_host", "orbm_sim3_host_error", "orbm_sim3_hypotheses", "orbm_sim3_hypotheses_host", "orbm_sim3_check", "orbm_sim3_check_host", "orbm_sim3_ransac_iterations", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
+    "orbm_search_by_projection_batch_device", "orbm_search_by_projection_fisheye", "orbm_search_by_projection_last_frame_fisheye", "orbm_search_by_projection_last_frame_fisheye_batch_device", "orbm_rig_concat_batch_device", "orbm_unproject", "orbm_fisheye_ratio_test", "orbm_fisheye_triangulate", "orbm_fisheye_triangulate_device", "orbm_stereo_fisheye_matches_batch_device", "orbm_stereo_fisheye_matches", "orbm_search_by_projection_last_frame", "orbm_search_by_projection_last_frame_batch_device", "orbm_search_local_points", "orbm_search_local_points_batch_device", "orbm_search_local_points_fisheye", "orbm_search_local_points_fisheye_batch_device", "orbm_rig_right_camera", "orbm_search_by_projection_keyframe", "orbm_search_by_projection_sim3", "orbm_search_by_projection_sim3_cam", "orbm_fuse_sim3_cam", "orbm_search_for_triangulation", "orbm_triangulation_candidates", "orbm_search_for_triangulation_pred", "orbm_search_for_triangulation_kb8", "orbm_search_for_triangulation_neighbours", "orbm_search_for_triangulation_kb8_neighbours", "orbm_new_point_geometry", "orbm_new_point_geometry_device", "orbm_create_new_map_points", "orbm_create_new_map_points_kb8", "orbm_search_for_initialization", "orbm_search_by_bow", "orbm_search_by_bow_fisheye", "orbm_search_by_bow_keyframes", "orbm_search_by_bow_candidates", "orbm_search_by_bow_keyframes_candidates", "orbm_fuse", "orbm_fuse_sim3", "orbm_fuse_keyframes", "orbm_fuse_sim3_keyframes", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_update_map_points", "orbm_map_point_normal_depth", "orbm_keyframe_culling", "orbm_keyframe_culling_open", "orbm_keyframe_culling_step", "orbm_keyframe_culling_host", "orbm_keyframe_culling_host_error", "orbm_update_local_map", "orbm_update_local_map_device", "orbm_update_local_map_host", "orbm_update_local_map_host_error", "orbm_update_connections", "orbm_update_connections_host", "orbm_gather_local_map_device", "orbm_two_view_reconstruct", "orbm_two_view_reconstruct_host", "orbm_two_view_host_error", "orbm_two_view_models", "orbm_two_view_models_host", "orbm_two_view_check_rt", "orbm_two_view_check_rt_host", "orbm_sim3_solve", "orbm_sim3_solve_host", "orbm_sim3_host_error", "orbm_sim3_hypotheses", "orbm_sim3_hypotheses_host", "orbm_sim3_check", "orbm_sim3_check_host", "orbm_sim3_ransac_iterations", "orbm_knn_match2", "orbm_hamming_matrix", "orbm_three_maxima",
     "orbm_radius_by_viewing_cos", "orbm_project", "orbm_undistort_keypoints", "orbm_image_bounds", "orbm_undistort_keypoints_batch_device", "orbm_set_profiling", "orbm_set_scan_mode", "orbm_set_hamming_engine", "orbm_get_last_ms", "orbm_get_stage_ms",
 ]
 # the vocabulary's symbols (orbv_*), a list of their own: tests/test_abi.py holds ABI_SYMBOLS equal to the header's orbx_ / orbm_ names;
@@ -123,6 +123,106 @@ def keyframe_culling_host(scene, erasable=None):
         raise ValueError("orbm_keyframe_culling_host: bad argument (%s)" % L.orbm_keyframe_culling_host_error().decode())
     _check_free(rc, "orbm_keyframe_culling_host")
     return out[0][:c.K], out[1][:c.K], out[2][:c.K], out[3][:c.P], out[4][:c.P]
+
+
+class MapGraph(C.Structure):  # orbm_map_graph_t
+    _fields_ = [("G", C.c_int32), ("kf_rank", C.c_void_p), ("kf_bad", C.c_void_p), ("kf_map", C.c_void_p), ("kf_row_start", C.c_void_p),
+                ("row_point", C.c_void_p), ("kf_best", C.c_void_p), ("kf_child_start", C.c_void_p), ("kf_child", C.c_void_p),
+                ("kf_parent", C.c_void_p), ("kf_prev", C.c_void_p), ("P", C.c_int32), ("pt_bad", C.c_void_p), ("obs_start", C.c_void_p),
+                ("obs_kf", C.c_void_p)]
+
+
+MAP_MAX_KEYFRAMES = 16384  # ORBM_MAP_MAX_KEYFRAMES
+MAP_BEST = 10  # ORBM_MAP_BEST
+_GRAPH_TYPES = dict(kf_rank=np.int32, kf_bad=np.uint8, kf_map=np.int32, kf_row_start=np.int32, row_point=np.int32, kf_best=np.int32,
+                    kf_child_start=np.int32, kf_child=np.int32, kf_parent=np.int32, kf_prev=np.int32, pt_bad=np.uint8, obs_start=np.int32,
+                    obs_kf=np.int32)
+
+
+def map_graph(scene):
+    """(MapGraph, the arrays it points to) from a dict of the arrays of orbm_map_graph_t by name (G and P come from kf_row_start and
+    obs_start; kf_prev may be None)."""
+    A = {k: (None if scene.get(k) is None else np.ascontiguousarray(scene[k], dtype=t)) for k, t in _GRAPH_TYPES.items()}
+    g = MapGraph()
+    g.G, g.P = len(A["kf_row_start"]) - 1, len(A["obs_start"]) - 1
+    for k in _GRAPH_TYPES:
+        setattr(g, k, _p(A[k]))
+    return g, A
+
+
+def map_graph_device(scene, device=0):
+    """The same tables resident on the device: (MapGraph holding device addresses, the torch tensors that own them)."""
+    import torch
+    g, A = map_graph(scene)
+    keep = {}
+    for k, a in A.items():
+        if a is None:
+            setattr(g, k, None)
+            continue
+        keep[k] = torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to("cuda:%d" % device)
+        setattr(g, k, C.c_void_p(keep[k].data_ptr()))
+    return g, keep
+
+
+def _local_map_outputs(N, cap_kf, cap_pts):
+    return (np.zeros(max(cap_kf, 1), np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(max(N, 1), np.uint8),
+            np.zeros(max(cap_pts, 1), np.int32), np.zeros(1, np.int32))
+
+
+def _local_map_result(rc, out, N, what):
+    if rc == E_CAP:
+        raise OrbError("%s: a list does not fit (needs %d keyframes, %d points)" % (what, out[1][0], out[6][0]))
+    if rc < 0:
+        raise OrbError("%s rc=%d" % (what, rc))
+    return dict(local_kf=out[0][:out[1][0]].copy(), kf_max=int(out[2][0]), max_votes=int(out[3][0]), slot_bad=out[4][:N].copy(),
+                local_point=out[5][:out[6][0]].copy())
+
+
+def _local_map_caps(g, A, cap_kf, cap_pts):
+    return (g.G + 24 if cap_kf is None else int(cap_kf)), (min(g.P, len(A["row_point"])) if cap_pts is None else int(cap_pts))
+
+
+def update_local_map_host(scene, frame_point, inertial=False, last_kf=-1, cap_kf=None, cap_pts=None):
+    """Tracking::UpdateLocalMap (Tracking.cc:3542-3762) on the CPU with the kernels' own statement (orbm_update_local_map_host,
+    csrc/orb_ref_localmap.h).  Same arguments and results as ORBmatcher.UpdateLocalMap; not a fallback of it."""
+    L = load()
+    g, A = map_graph(scene)
+    fp = np.ascontiguousarray(frame_point, dtype=np.int32)
+    cap_kf, cap_pts = _local_map_caps(g, A, cap_kf, cap_pts)
+    out = _local_map_outputs(len(fp), cap_kf, cap_pts)
+    rc = L.orbm_update_local_map_host(C.byref(g), len(fp), _p(fp), int(bool(inertial)), int(last_kf), cap_kf, cap_pts, *[_p(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError("orbm_update_local_map_host: bad argument (%s)" % L.orbm_update_local_map_host_error().decode())
+    return _local_map_result(rc, out, len(fp), "orbm_update_local_map_host")
+
+
+def _connections_outputs(T, cap):
+    return (np.zeros(T + 1, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(T + 1, np.int32),
+            np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(T, 1), np.int32), np.zeros(max(T, 1), np.int32))
+
+
+def _connections_result(rc, out, T, what):
+    if rc == E_CAP:
+        raise OrbError("%s: the lists do not fit (needs %d)" % (what, out[0][T]))
+    if rc < 0:
+        raise OrbError("%s rc=%d" % (what, rc))
+    cs, os_ = out[0], out[3]
+    return [dict(conn_kf=out[1][cs[t]:cs[t + 1]].copy(), conn_w=out[2][cs[t]:cs[t + 1]].copy(), ord_kf=out[4][os_[t]:os_[t + 1]].copy(),
+                 ord_w=out[5][os_[t]:os_[t + 1]].copy(), kf_max=int(out[6][t]), nmax=int(out[7][t])) for t in range(T)]
+
+
+def update_connections_host(scene, targets, th=15, cap=None):
+    """KFcounter and the ordered lists of KeyFrame::UpdateConnections (KeyFrame.cc:407-492) for every keyframe of `targets`, on the CPU with
+    the kernels' own statement (orbm_update_connections_host).  Same arguments and results as ORBmatcher.UpdateConnections."""
+    L = load()
+    g, A = map_graph(scene)
+    tg = np.ascontiguousarray(targets, dtype=np.int32)
+    cap = len(tg) * g.G if cap is None else int(cap)
+    out = _connections_outputs(len(tg), cap)
+    rc = L.orbm_update_connections_host(C.byref(g), len(tg), _p(tg), int(th), cap, *[_p(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError("orbm_update_connections_host: bad argument (%s)" % L.orbm_update_local_map_host_error().decode())
+    return _connections_result(rc, out, len(tg), "orbm_update_connections_host")
 
 
 class TwoViewDetailsStruct(C.Structure):  # orbm_two_view_details_t
@@ -588,6 +688,14 @@ def load(build_if_needed=True):
     L.orbm_keyframe_culling_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.orbm_keyframe_culling_host_error.argtypes = []
     L.orbm_keyframe_culling_host_error.restype = C.c_char_p
+    L.orbm_update_local_map.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_update_local_map_device.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_update_local_map_host.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_update_local_map_host_error.argtypes = []
+    L.orbm_update_local_map_host_error.restype = C.c_char_p
+    L.orbm_update_connections.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_update_connections_host.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_gather_local_map_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     tv = [vp, i32, vp, i32, vp]   # keys1, n1, keys2, n2, matches12
     L.orbm_two_view_reconstruct.argtypes = [vp] + tv + [vp, f32, i32, vp, vp, vp, vp, vp, vp]
     L.orbm_two_view_reconstruct_host.argtypes = tv + [vp, f32, i32, vp, vp, vp, vp, vp, vp]
@@ -1598,6 +1706,55 @@ class ORBmatcher:
     def Sim3Check(self, prob, T12, T21):
         """The second device stage alone (orbm_sim3_check): CheckInliers for the caller's transforms T12, T21 [nhyp,4,4]."""
         return _sim3_check(self._tv_call(self.L.orbm_sim3_check), "orbm_sim3_check", self._tv_error, prob, T12, T21)
+
+    def UpdateLocalMap(self, scene, frame_point, inertial=False, last_kf=-1, cap_kf=None, cap_pts=None):
+        """Tracking::UpdateLocalMap (Tracking.cc:3542-3762) on the device from host tables (orbm_update_local_map).  scene: see map_graph;
+        frame_point [N] = the frame's mvpMapPoints as point indices, -1 = NULL.  Returns a dict: local_kf (mvpLocalKeyFrames), kf_max
+        (pKFmax or -1), max_votes, slot_bad [N] (the slots the reference sets to NULL), local_point (mvpLocalMapPoints).  The capacities
+        default to what always fits."""
+        g, A = map_graph(scene)
+        fp = np.ascontiguousarray(frame_point, dtype=np.int32)
+        cap_kf, cap_pts = _local_map_caps(g, A, cap_kf, cap_pts)
+        out = _local_map_outputs(len(fp), cap_kf, cap_pts)
+        rc = self.L.orbm_update_local_map(self.m, C.byref(g), len(fp), _p(fp), int(bool(inertial)), int(last_kf), cap_kf, cap_pts, *[_p(o) for o in out])
+        self._check(rc, "orbm_update_local_map")
+        return _local_map_result(rc, out, len(fp), "orbm_update_local_map")
+
+    def UpdateLocalMapDevice(self, d_graph, N, d_frame_point, inertial, last_kf, cap_kf, cap_pts, d_local_kf, d_n_local_kf, d_kf_max, d_max_votes,
+                             d_slot_bad, d_local_point, d_n_local_point, stream=None):
+        """The resident form (orbm_update_local_map_device): d_graph is a MapGraph holding device addresses (map_graph_device), every other
+        d_ argument a device address (int).  Asynchronous on `stream`; writes are clamped at the capacities, the counts say what was needed."""
+        rc = self.L.orbm_update_local_map_device(self.m, C.byref(d_graph), int(N), _dp(d_frame_point), int(bool(inertial)), int(last_kf), int(cap_kf),
+                                                 int(cap_pts), _dp(d_local_kf), _dp(d_n_local_kf), _dp(d_kf_max), _dp(d_max_votes), _dp(d_slot_bad),
+                                                 _dp(d_local_point), _dp(d_n_local_point), _dp(stream))
+        self._check(rc, "orbm_update_local_map_device")
+        if rc < 0:
+            raise OrbError("orbm_update_local_map_device rc=%d" % rc)
+
+    def UpdateConnections(self, scene, targets, th=15, cap=None):
+        """KFcounter and the ordered lists of KeyFrame::UpdateConnections (KeyFrame.cc:407-492) for every keyframe of `targets`, all counted
+        from the state at entry (CONNECTIONS RULE, include/orbhip.h), on the device (orbm_update_connections).  Returns one dict per target:
+        conn_kf / conn_w (mConnectedKeyFrameWeights in rank order), ord_kf / ord_w (mvpOrderedConnectedKeyFrames / mvOrderedWeights),
+        kf_max, nmax.  What the member writes on other keyframes stays the caller's.  cap defaults to T * G elements per list, which always
+        fits; the device block of a call grows as 20 * T * G bytes, so pass a long loop over a large map in chunks of targets."""
+        g, A = map_graph(scene)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        cap = len(tg) * g.G if cap is None else int(cap)
+        out = _connections_outputs(len(tg), cap)
+        rc = self.L.orbm_update_connections(self.m, C.byref(g), len(tg), _p(tg), int(th), cap, *[_p(o) for o in out])
+        self._check(rc, "orbm_update_connections")
+        return _connections_result(rc, out, len(tg), "orbm_update_connections")
+
+    def GatherLocalMapDevice(self, P, N, d_frame_point, d_local_point, d_n_local_point, cap, d_pt_bad, d_Xw, d_normal, d_max_dist, d_min_dist,
+                             d_mpdesc, d_obs, out, d_map_n, stream=None):
+        """orbm_gather_local_map_device: fills the device arrays of `out` (a LocalMapStruct of device addresses) from the local-point list
+        that UpdateLocalMapDevice left on the device and per-point tables; d_map_n receives the live count."""
+        rc = self.L.orbm_gather_local_map_device(self.m, int(P), int(N), _dp(d_frame_point), _dp(d_local_point), _dp(d_n_local_point), int(cap),
+                                                 _dp(d_pt_bad), _dp(d_Xw), _dp(d_normal), _dp(d_max_dist), _dp(d_min_dist), _dp(d_mpdesc), _dp(d_obs),
+                                                 C.byref(out), _dp(d_map_n), _dp(stream))
+        self._check(rc, "orbm_gather_local_map_device")
+        if rc < 0:
+            raise OrbError("orbm_gather_local_map_device rc=%d" % rc)
 
     def KeyFrameCullingOpen(self, scene):
         """Opens the stepwise walk (orbm_keyframe_culling_open): uploads the scene and computes the loop-entry status of every row.  An

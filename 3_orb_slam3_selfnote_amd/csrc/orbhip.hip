@@ -36,6 +36,7 @@
 #include "orb_bow_kernels.h"
 #include "orb_mappoint_kernels.h"
 #include "orb_culling_kernels.h"
+#include "orb_localmap_kernels.h"
 #include "orb_twoview_kernels.h"
 #include "orb_sim3_kernels.h"
 #include "orb_voc_kernels.h"
@@ -1355,6 +1356,10 @@ struct orbm_handle {
   CullParams cull{};  // its device addresses inside d_cull
   bool cull_open = false, cull_any = false;   // a walk is open; one of its erases has been applied
   int cull_next = 0, cull_pending = -1;       // the next keyframe to walk; the passing keyframe the last step returned, or -1
+  DevBuf d_lm, d_lm_flag;   // scratch of orbm_update_local_map_device (counters, per-point word, keyframe list) and of orbm_gather_local_map_device ([P] flags)
+  std::mutex lm_mu;         // held by the UpdateLocalMap / UpdateConnections / gather entries: threads may share a handle for THESE entries
+  std::vector<uint8_t> lm_back;   // orbm_update_connections: its outputs on the host (capacity only grows)
+  int vote_form = 0;        // k_covis_vote: 0 LDS table, 1 one global atomic per vote (ORBM_VOTE_FORM, measurements only)
   std::vector<BowCandItem> bow_items;   // host side of the one-call SearchByBoW, kept between calls (capacity only grows)
   std::vector<BowCand> bow_cands;
   std::vector<float> bow_ang;
@@ -1547,6 +1552,7 @@ orbm_t *orbm_create(int device) {
   m->device = device;
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return nullptr; }
   if (const char *e = getenv("ORBM_SCAN_MODE")) { const int v = atoi(e); if (v >= SCAN_AUTO && v <= SCAN_WALK) m->scan_mode = v; }   // measurements only; see orbm_set_scan_mode
+  if (const char *e = getenv("ORBM_VOTE_FORM")) m->vote_form = atoi(e) == 1;   // measurements only; DESIGN.md 6
   if (const char *e = getenv("ORBM_TRI_LAYOUT")) m->tri_layout = atoi(e) == 1;                                                                                           // measurements only; DESIGN.md 6
   if (const char *e = getenv("ORBM_HAMMING_ENGINE")) { const int v = atoi(e); if (v >= 0 && v <= 2) m->hamming_engine = v; }                                               // measurements only; see orbm_set_hamming_engine
   return m;
@@ -1556,7 +1562,7 @@ void orbm_destroy(orbm_t *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_knn, &m->d_partner, &m->d_tri_count, &m->d_tri_keys, &m->d_cull};
+  DevBuf *bufs[] = {&m->d_block, &m->d_topk, &m->d_rank, &m->d_cand, &m->d_lfq, &m->d_lmq, &m->d_knn, &m->d_partner, &m->d_tri_count, &m->d_tri_keys, &m->d_cull, &m->d_lm, &m->d_lm_flag};
   for (DevBuf *b : bufs) b->release();
   if (m->pin) (void)hipHostFree(m->pin);
   if (m->ev_ok)
@@ -4388,6 +4394,314 @@ int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable,
   }
   if (n_obs_out && NP) memcpy(n_obs_out, n_obs.data(), sizeof(int32_t) * NP);
   if (bad_out && NP) memcpy(bad_out, bad.data(), NP);
+  return 0;
+}
+
+// ---- Tracking::UpdateLocalMap (Tracking.cc:3542-3762) and KeyFrame::UpdateConnections (KeyFrame.cc:407-492): orb_ref_localmap.h,
+// orb_localmap_kernels.h ----
+// k_local_kf_walk and k_conn_walk sort up to 16384 8-byte keys in dynamic LDS
+static LdsOnce g_lm_lds;
+
+// What is refused of the tables before anything is uploaded, launched or written (include/orbhip.h); nullptr = accepted
+static const char *graph_refusal(const orbm_map_graph_t *g, bool inertial) {
+  if (!g) return "map graph: NULL struct";
+  if (g->G < 0 || g->P < 0) return "map graph: negative count";
+  if (g->G > ORBM_MAP_MAX_KEYFRAMES) return "map graph: G above ORBM_MAP_MAX_KEYFRAMES (16384)";
+  const int G = g->G, P = g->P;
+  if (G > 0 && (!g->kf_rank || !g->kf_bad || !g->kf_map || !g->kf_row_start || !g->kf_best || !g->kf_child_start || !g->kf_parent))
+    return "map graph: NULL keyframe array";
+  if (inertial && G > 0 && !g->kf_prev) return "map graph: inertial with kf_prev == NULL";
+  if (P > 0 && (!g->pt_bad || !g->obs_start)) return "map graph: NULL point array";
+  if (G > 0 && (g->kf_row_start[0] != 0 || g->kf_child_start[0] != 0)) return "map graph: kf_row_start[0] / kf_child_start[0] != 0";
+  if (P > 0 && g->obs_start[0] != 0) return "map graph: obs_start[0] != 0";
+  for (int k = 0; k < G; k++) {
+    const int64_t n = (int64_t)g->kf_row_start[k + 1] - (int64_t)g->kf_row_start[k];
+    if (n < 0) return "map graph: kf_row_start decreases";
+    if (n > ORBM_MAX_KEYPOINTS) return "map graph: more than ORBM_MAX_KEYPOINTS (15360) rows in one keyframe";
+    if (g->kf_child_start[k + 1] < g->kf_child_start[k]) return "map graph: kf_child_start decreases";
+  }
+  for (int p = 0; p < P; p++)
+    if (g->obs_start[p + 1] < g->obs_start[p]) return "map graph: obs_start decreases";
+  const int R = G ? g->kf_row_start[G] : 0, C = G ? g->kf_child_start[G] : 0, E = P ? g->obs_start[P] : 0;
+  if (R > 0 && !g->row_point) return "map graph: NULL row_point";
+  if (C > 0 && !g->kf_child) return "map graph: NULL kf_child";
+  if (E > 0 && !g->obs_kf) return "map graph: NULL obs_kf";
+  for (int i = 0; i < R; i++)
+    if (g->row_point[i] < -1 || g->row_point[i] >= P) return "map graph: row_point outside [-1, P)";
+  for (int i = 0; i < C; i++)
+    if (g->kf_child[i] < 0 || g->kf_child[i] >= G) return "map graph: kf_child outside [0, G)";
+  for (int i = 0; i < G * ORBM_MAP_BEST; i++)
+    if (g->kf_best[i] < -1 || g->kf_best[i] >= G) return "map graph: kf_best outside [-1, G)";
+  for (int k = 0; k < G; k++) {
+    if (g->kf_parent[k] < -1 || g->kf_parent[k] >= G) return "map graph: kf_parent outside [-1, G)";
+    if (g->kf_prev && (g->kf_prev[k] < -1 || g->kf_prev[k] >= G)) return "map graph: kf_prev outside [-1, G)";
+  }
+  std::vector<int32_t> ranks(g->kf_rank, g->kf_rank + G);
+  std::sort(ranks.begin(), ranks.end());
+  if (std::adjacent_find(ranks.begin(), ranks.end()) != ranks.end()) return "map graph: duplicate ranks";
+  std::vector<int32_t> seen((size_t)G, -1);   // seen[kf] = the last point that had an entry of keyframe kf
+  for (int p = 0; p < P; p++) {
+    if (g->pt_bad[p]) continue;               // the entries of a bad point are not read
+    for (int e = g->obs_start[p]; e < g->obs_start[p + 1]; e++) {
+      const int kf = g->obs_kf[e];
+      if (kf < 0 || kf >= G) return "map graph: obs_kf outside [0, G)";
+      if (seen[(size_t)kf] == p) return "map graph: two entries of one point with the same keyframe";
+      seen[(size_t)kf] = p;
+    }
+  }
+  return nullptr;
+}
+static const char *local_map_refusal(const orbm_map_graph_t *g, int N, const int32_t *frame_point, int inertial, int last_kf, int cap_kf, int cap_pts,
+                                     const void *local_kf, const void *n_local_kf, const void *kf_max, const void *max_votes, const void *slot_bad,
+                                     const void *local_point, const void *n_local_point, bool host_tables) {
+  if (!g) return "UpdateLocalMap: NULL struct";
+  if (N < 0 || cap_kf < 0 || cap_pts < 0) return "UpdateLocalMap: negative count or capacity";
+  if (!n_local_kf || !kf_max || !max_votes || !n_local_point) return "UpdateLocalMap: NULL output";
+  if ((cap_kf > 0 && !local_kf) || (cap_pts > 0 && !local_point)) return "UpdateLocalMap: NULL output list";
+  if (N > 0 && (!frame_point || !slot_bad)) return "UpdateLocalMap: NULL frame_point / slot_bad";
+  if (host_tables) {
+    if (const char *why = graph_refusal(g, inertial != 0)) return why;
+    for (int s = 0; s < N; s++)
+      if (frame_point[s] < -1 || frame_point[s] >= g->P) return "UpdateLocalMap: frame_point outside [-1, P)";
+  } else {
+    if (g->G < 0 || g->P < 0 || g->G > ORBM_MAP_MAX_KEYFRAMES) return "UpdateLocalMap: G or P out of range";
+    if (g->G > 0 && (!g->kf_rank || !g->kf_bad || !g->kf_map || !g->kf_row_start || !g->row_point || !g->kf_best || !g->kf_child_start || !g->kf_parent))
+      return "UpdateLocalMap: NULL keyframe array";
+    if (g->P > 0 && (!g->pt_bad || !g->obs_start || !g->obs_kf)) return "UpdateLocalMap: NULL point array";
+    if (inertial && g->G > 0 && !g->kf_prev) return "UpdateLocalMap: inertial with kf_prev == NULL";
+  }
+  if (last_kf < -1 || last_kf >= g->G) return "UpdateLocalMap: last_kf outside [-1, G)";
+  return nullptr;
+}
+static const char *connections_refusal(const orbm_map_graph_t *g, int T, const int32_t *targets, int cap, const void *conn_start, const void *conn_kf,
+                                       const void *conn_w, const void *ord_start, const void *ord_kf, const void *ord_w, const void *kf_max, const void *nmax) {
+  if (!g) return "UpdateConnections: NULL struct";
+  if (T < 0 || cap < 0) return "UpdateConnections: negative count or capacity";
+  if (const char *why = graph_refusal(g, false)) return why;
+  if (T == 0) return nullptr;
+  if (!targets || !conn_start || !ord_start || !kf_max || !nmax) return "UpdateConnections: NULL argument";
+  if (cap > 0 && (!conn_kf || !conn_w || !ord_kf || !ord_w)) return "UpdateConnections: NULL output list";
+  std::vector<uint8_t> listed((size_t)g->G, 0);
+  for (int t = 0; t < T; t++) {
+    if (targets[t] < 0 || targets[t] >= g->G) return "UpdateConnections: target outside [0, G)";
+    if (listed[(size_t)targets[t]]) return "UpdateConnections: a target listed twice";
+    listed[(size_t)targets[t]] = 1;
+  }
+  return nullptr;
+}
+static LmGraph lm_graph(const orbm_map_graph_t *g) {
+  return {g->G, g->kf_rank, g->kf_bad, g->kf_map, g->kf_row_start, g->row_point, g->kf_best, g->kf_child_start, g->kf_child, g->kf_parent, g->kf_prev,
+          g->P, g->pt_bad, g->obs_start, g->obs_kf};
+}
+static LmTables lm_tables(const orbm_map_graph_t *g) {   // a struct of device pointers
+  return {g->G, g->kf_rank, g->kf_bad, g->kf_map, g->kf_row_start, g->row_point, g->kf_best, g->kf_child_start, g->kf_child, g->kf_parent, g->kf_prev,
+          g->P, g->pt_bad, g->obs_start, g->obs_kf};
+}
+
+// The tables as parts of one staged block
+struct GraphParts {
+  PartOf<int32_t> rank, map, row_start, row_point, best, child_start, child, parent, prev, obs_start, obs_kf;
+  PartOf<uint8_t> kf_bad, pt_bad;
+};
+static GraphParts graph_add(Staging &S, const orbm_map_graph_t *g, bool with_prev) {
+  GraphParts H;
+  const size_t G = (size_t)g->G, P = (size_t)g->P;
+  const size_t R = G ? (size_t)g->kf_row_start[G] : 0, C = G ? (size_t)g->kf_child_start[G] : 0, E = P ? (size_t)g->obs_start[P] : 0;
+  H.rank = S.add(g->kf_rank, G); H.kf_bad = S.add(g->kf_bad, G); H.map = S.add(g->kf_map, G);
+  H.row_start = S.add(g->kf_row_start, G ? G + 1 : 0); H.row_point = S.add(g->row_point, R); H.best = S.add(g->kf_best, G * ORBM_MAP_BEST);
+  H.child_start = S.add(g->kf_child_start, G ? G + 1 : 0); H.child = S.add(g->kf_child, C); H.parent = S.add(g->kf_parent, G);
+  H.prev = S.add(g->kf_prev, with_prev ? G : 0);
+  H.pt_bad = S.add(g->pt_bad, P); H.obs_start = S.add(g->obs_start, P ? P + 1 : 0); H.obs_kf = S.add(g->obs_kf, E);
+  return H;
+}
+static LmTables graph_bind(const Staging &S, const GraphParts &H, const orbm_map_graph_t *g) {
+  return {g->G, S.dev(H.rank), S.dev(H.kf_bad), S.dev(H.map), S.dev(H.row_start), S.dev(H.row_point), S.dev(H.best), S.dev(H.child_start), S.dev(H.child),
+          S.dev(H.parent), S.dev(H.prev), g->P, S.dev(H.pt_bad), S.dev(H.obs_start), S.dev(H.obs_kf)};
+}
+static size_t lm_sort_lds(int G) {
+  size_t p2 = 2;
+  while (p2 < (size_t)G) p2 <<= 1;
+  return sizeof(uint64_t) * p2;
+}
+
+// The scratch of one UpdateLocalMap call: hdr, count, kf_count and pt_word are ONE span that is zero on entry
+struct LmScratch { int32_t *hdr, *count, *kf_count; uint32_t *pt_word; int32_t *list; };
+struct LmOutputs { int32_t *local_kf, *n_local_kf, *kf_max, *max_votes; uint8_t *slot_bad; int32_t *local_point, *n_local_point; };
+static int local_map_launch(orbm_t *m, hipStream_t s, const LmTables &M, const LmScratch &X, int N, const int32_t *d_frame_point, int inertial, int last_kf,
+                            int cap_kf, int cap_pts, const LmOutputs &O) {
+  MCHECK(m, raise_lds_once(g_lm_lds, m->device, {reinterpret_cast<const void *>(&k_local_kf_walk), reinterpret_cast<const void *>(&k_conn_walk)}));
+  VoteParams V{M, N, d_frame_point, nullptr, O.slot_bad, X.count, m->vote_form};
+  hipLaunchKernelGGL(k_covis_vote, dim3((unsigned)((N + 255) / 256), 1u), dim3(256), 0, s, V);
+  WalkParams W{M, X.count, inertial, last_kf, cap_kf, X.list, X.hdr, O.local_kf, O.n_local_kf, O.kf_max, O.max_votes, O.n_local_point};
+  hipLaunchKernelGGL(k_local_kf_walk, dim3(1), dim3(LM_WALK_THREADS), lm_sort_lds(M.G), s, W);
+  LpParams L{M, X.list, X.hdr, X.pt_word, X.kf_count, cap_pts, O.local_point, O.n_local_point};
+  hipLaunchKernelGGL(k_lp_first, dim3(LM_TILES_X, LM_KF_BLOCKS), dim3(256), 0, s, L);
+  hipLaunchKernelGGL(k_lp_count, dim3(LM_KF_BLOCKS), dim3(256), 0, s, L);
+  hipLaunchKernelGGL(k_lp_write, dim3(LM_KF_BLOCKS), dim3(256), 0, s, L);
+  MCHECK(m, hipGetLastError());
+  return 0;
+}
+
+int orbm_update_local_map(orbm_t *m, const orbm_map_graph_t *g, int N, const int32_t *frame_point, int inertial, int last_kf, int cap_kf, int cap_pts,
+                          int32_t *local_kf, int32_t *n_local_kf, int32_t *kf_max, int32_t *max_votes, uint8_t *slot_bad, int32_t *local_point,
+                          int32_t *n_local_point) {
+  if (!m) return ORBX_E_ARG;
+  std::lock_guard<std::mutex> lock(m->lm_mu);
+  if (const char *why = local_map_refusal(g, N, frame_point, inertial, last_kf, cap_kf, cap_pts, local_kf, n_local_kf, kf_max, max_votes, slot_bad, local_point,
+                                          n_local_point, true)) { m->err = why; return ORBX_E_ARG; }
+  if (N == 0) { *n_local_kf = 0; *n_local_point = 0; *kf_max = -1; *max_votes = 0; return 0; }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  const size_t G = (size_t)g->G, P = (size_t)g->P;
+  Staging S{m};   // one block up, five launches, the outputs down as one span of the block, one synchronisation
+  const GraphParts H = graph_add(S, g, inertial != 0);
+  const auto hfp = S.add(frame_point, (size_t)N);
+  const auto hhdr = S.out<int32_t>(LM_HDR), hcount = S.out<int32_t>(G), hkfc = S.out<int32_t>(G + 24);
+  const auto hword = S.out<uint32_t>(P);
+  const auto hlist = S.out<int32_t>(G + 24);
+  const auto hres = S.out<int32_t>(4), hlkf = S.out<int32_t>((size_t)cap_kf), hlpt = S.out<int32_t>((size_t)cap_pts);
+  const auto hsb = S.out<uint8_t>((size_t)N);
+  int rc = S.upload(s);
+  if (rc < 0) return rc;
+  MCHECK(m, S.fill(s, hhdr, hword, 0));
+  int32_t *res = S.dev(hres);
+  const LmScratch X{S.dev(hhdr), S.dev(hcount), S.dev(hkfc), S.dev(hword), S.dev(hlist)};
+  const LmOutputs O{S.dev(hlkf), res, res + 1, res + 2, S.dev(hsb), S.dev(hlpt), res + 3};
+  if ((rc = local_map_launch(m, s, graph_bind(S, H, g), X, N, S.dev(hfp), inertial, last_kf, cap_kf, cap_pts, O)) < 0) return rc;
+  MCHECK(m, S.download(s, hres, hsb));
+  MCHECK(m, hipStreamSynchronize(s));
+  const int32_t *r = S.host(hres);
+  *n_local_kf = r[0]; *kf_max = r[1]; *max_votes = r[2]; *n_local_point = r[3];
+  memcpy(slot_bad, S.host(hsb), (size_t)N);
+  if (r[0] > cap_kf || r[3] > cap_pts) { m->err = "UpdateLocalMap: a list does not fit its capacity"; return ORBX_E_CAP; }
+  if (r[0]) memcpy(local_kf, S.host(hlkf), sizeof(int32_t) * (size_t)r[0]);
+  if (r[3]) memcpy(local_point, S.host(hlpt), sizeof(int32_t) * (size_t)r[3]);
+  return 0;
+}
+
+int orbm_update_local_map_device(orbm_t *m, const orbm_map_graph_t *g, int N, const int32_t *d_frame_point, int inertial, int last_kf, int cap_kf,
+                                 int cap_pts, int32_t *d_local_kf, int32_t *d_n_local_kf, int32_t *d_kf_max, int32_t *d_max_votes, uint8_t *d_slot_bad,
+                                 int32_t *d_local_point, int32_t *d_n_local_point, void *stream) {
+  if (!m) return ORBX_E_ARG;
+  std::lock_guard<std::mutex> lock(m->lm_mu);
+  if (const char *why = local_map_refusal(g, N, d_frame_point, inertial, last_kf, cap_kf, cap_pts, d_local_kf, d_n_local_kf, d_kf_max, d_max_votes, d_slot_bad,
+                                          d_local_point, d_n_local_point, false)) { m->err = why; return ORBX_E_ARG; }
+  if (N == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t G = (size_t)g->G, P = (size_t)g->P;
+  const size_t zeroed = sizeof(int32_t) * (LM_HDR + G + (G + 24) + P), bytes = zeroed + sizeof(int32_t) * (G + 24);
+  MCHECK(m, m->d_lm.reserve(m->d_lm.bytes >= bytes ? bytes : 2 * bytes));
+  int32_t *base = (int32_t *)m->d_lm.p;
+  const LmScratch X{base, base + LM_HDR, base + LM_HDR + G, (uint32_t *)(base + LM_HDR + G + G + 24), base + LM_HDR + G + G + 24 + P};
+  MCHECK(m, hipMemsetAsync(base, 0, zeroed, s));
+  const LmOutputs O{d_local_kf, d_n_local_kf, d_kf_max, d_max_votes, d_slot_bad, d_local_point, d_n_local_point};
+  return local_map_launch(m, s, lm_tables(g), X, N, d_frame_point, inertial, last_kf, cap_kf, cap_pts, O);
+}
+
+static thread_local const char *g_lm_host_err = "";
+const char *orbm_update_local_map_host_error(void) { return g_lm_host_err; }
+
+int orbm_update_local_map_host(const orbm_map_graph_t *g, int N, const int32_t *frame_point, int inertial, int last_kf, int cap_kf, int cap_pts,
+                               int32_t *local_kf, int32_t *n_local_kf, int32_t *kf_max, int32_t *max_votes, uint8_t *slot_bad, int32_t *local_point,
+                               int32_t *n_local_point) {
+  if (const char *why = local_map_refusal(g, N, frame_point, inertial, last_kf, cap_kf, cap_pts, local_kf, n_local_kf, kf_max, max_votes, slot_bad, local_point,
+                                          n_local_point, true)) { g_lm_host_err = why; return ORBX_E_ARG; }
+  if (N == 0) { *n_local_kf = 0; *n_local_point = 0; *kf_max = -1; *max_votes = 0; return 0; }
+  std::vector<int32_t> kfs, pts;
+  int best, votes;
+  lm_update_local_map_host(lm_graph(g), N, frame_point, inertial != 0, last_kf, kfs, &best, &votes, slot_bad, pts);
+  *n_local_kf = (int32_t)kfs.size(); *n_local_point = (int32_t)pts.size(); *kf_max = best; *max_votes = votes;
+  if ((int)kfs.size() > cap_kf || (int)pts.size() > cap_pts) { g_lm_host_err = "UpdateLocalMap: a list does not fit its capacity"; return ORBX_E_CAP; }
+  if (!kfs.empty()) memcpy(local_kf, kfs.data(), sizeof(int32_t) * kfs.size());
+  if (!pts.empty()) memcpy(local_point, pts.data(), sizeof(int32_t) * pts.size());
+  return 0;
+}
+
+int orbm_update_connections(orbm_t *m, const orbm_map_graph_t *g, int T, const int32_t *targets, int th, int cap, int32_t *conn_start, int32_t *conn_kf,
+                            int32_t *conn_w, int32_t *ord_start, int32_t *ord_kf, int32_t *ord_w, int32_t *kf_max, int32_t *nmax) {
+  if (!m) return ORBX_E_ARG;
+  std::lock_guard<std::mutex> lock(m->lm_mu);
+  if (const char *why = connections_refusal(g, T, targets, cap, conn_start, conn_kf, conn_w, ord_start, ord_kf, ord_w, kf_max, nmax)) { m->err = why; return ORBX_E_ARG; }
+  if (T == 0) return 0;
+  MCHECK(m, hipSetDevice(m->device));
+  MCHECK(m, raise_lds_once(g_lm_lds, m->device, {reinterpret_cast<const void *>(&k_local_kf_walk), reinterpret_cast<const void *>(&k_conn_walk)}));
+  hipStream_t s = m->stream;
+  const size_t G = (size_t)g->G, nT = (size_t)T, TG = nT * G;
+  Staging S{m};   // one block up, three launches, the outputs down as one span of the block, one synchronisation
+  const GraphParts H = graph_add(S, g, false);
+  const auto htar = S.add(targets, nT);
+  const auto hcount = S.out<int32_t>(TG), hwork = S.out<int32_t>(4 * TG), hn = S.out<int32_t>(2 * nT);
+  const auto hcs = S.out<int32_t>(nT + 1), hos = S.out<int32_t>(nT + 1), hmax = S.out<int32_t>(2 * nT), hlists = S.out<int32_t>(4 * (size_t)cap);
+  int rc = S.upload(s, false);   // the mirror of the outputs is made below: the work arrays take no pinned memory
+  if (rc < 0) return rc;
+  MCHECK(m, S.fill(s, hcount, hcount, 0));
+  const LmTables M = graph_bind(S, H, g);
+  int most = 0;
+  for (int t = 0; t < T; t++) most = std::max(most, g->kf_row_start[targets[t] + 1] - g->kf_row_start[targets[t]]);
+  int32_t *work = S.dev(hwork), *lists = S.dev(hlists);
+  ConnParams C{M, S.dev(hcount), S.dev(htar), T, th, cap, work, work + TG, work + 2 * TG, work + 3 * TG, S.dev(hn), S.dev(hn) + nT,
+               S.dev(hcs), lists, lists + cap, S.dev(hos), lists + 2 * (size_t)cap, lists + 3 * (size_t)cap, S.dev(hmax), S.dev(hmax) + nT};
+  if (most > 0) {
+    VoteParams V{M, 0, nullptr, S.dev(htar), nullptr, S.dev(hcount), m->vote_form};
+    hipLaunchKernelGGL(k_covis_vote, dim3((unsigned)((most + 255) / 256), (unsigned)T), dim3(256), 0, s, V);
+  }
+  hipLaunchKernelGGL(k_conn_walk, dim3((unsigned)T), dim3(LM_WALK_THREADS), lm_sort_lds(g->G), s, C);
+  hipLaunchKernelGGL(k_conn_pack, dim3((unsigned)T), dim3(256), 0, s, C);
+  MCHECK(m, hipGetLastError());
+  const size_t out_bytes = S.span(hcs, hlists);
+  std::vector<uint8_t> &back = m->lm_back;
+  back.resize(out_bytes);
+  MCHECK(m, hipMemcpyAsync(back.data(), S.block() + S.offset(hcs), out_bytes, hipMemcpyDeviceToHost, s));
+  MCHECK(m, hipStreamSynchronize(s));
+  auto at = [&](auto h) { return (const int32_t *)(back.data() + (S.offset(h) - S.offset(hcs))); };
+  memcpy(conn_start, at(hcs), sizeof(int32_t) * (nT + 1)); memcpy(ord_start, at(hos), sizeof(int32_t) * (nT + 1));
+  memcpy(kf_max, at(hmax), sizeof(int32_t) * nT); memcpy(nmax, at(hmax) + nT, sizeof(int32_t) * nT);
+  if (conn_start[T] > cap) { m->err = "UpdateConnections: the lists do not fit cap"; return ORBX_E_CAP; }
+  const size_t nc = sizeof(int32_t) * (size_t)conn_start[T], no = sizeof(int32_t) * (size_t)ord_start[T];
+  if (nc) { memcpy(conn_kf, at(hlists), nc); memcpy(conn_w, at(hlists) + cap, nc); }
+  if (no) { memcpy(ord_kf, at(hlists) + 2 * (size_t)cap, no); memcpy(ord_w, at(hlists) + 3 * (size_t)cap, no); }
+  return 0;
+}
+
+int orbm_update_connections_host(const orbm_map_graph_t *g, int T, const int32_t *targets, int th, int cap, int32_t *conn_start, int32_t *conn_kf,
+                                 int32_t *conn_w, int32_t *ord_start, int32_t *ord_kf, int32_t *ord_w, int32_t *kf_max, int32_t *nmax) {
+  if (const char *why = connections_refusal(g, T, targets, cap, conn_start, conn_kf, conn_w, ord_start, ord_kf, ord_w, kf_max, nmax)) { g_lm_host_err = why; return ORBX_E_ARG; }
+  if (T == 0) return 0;
+  const LmGraph M = lm_graph(g);
+  std::vector<std::vector<int32_t>> ck((size_t)T), cw((size_t)T), ok((size_t)T), ow((size_t)T);
+  conn_start[0] = ord_start[0] = 0;
+  for (int t = 0; t < T; t++) {
+    conn_update_host(M, targets[t], th, ck[(size_t)t], cw[(size_t)t], ok[(size_t)t], ow[(size_t)t], &kf_max[t], &nmax[t]);
+    conn_start[t + 1] = conn_start[t] + (int32_t)ck[(size_t)t].size(); ord_start[t + 1] = ord_start[t] + (int32_t)ok[(size_t)t].size();
+  }
+  if (conn_start[T] > cap) { g_lm_host_err = "UpdateConnections: the lists do not fit cap"; return ORBX_E_CAP; }
+  for (int t = 0; t < T; t++) {
+    std::copy(ck[(size_t)t].begin(), ck[(size_t)t].end(), conn_kf + conn_start[t]); std::copy(cw[(size_t)t].begin(), cw[(size_t)t].end(), conn_w + conn_start[t]);
+    std::copy(ok[(size_t)t].begin(), ok[(size_t)t].end(), ord_kf + ord_start[t]); std::copy(ow[(size_t)t].begin(), ow[(size_t)t].end(), ord_w + ord_start[t]);
+  }
+  return 0;
+}
+
+int orbm_gather_local_map_device(orbm_t *m, int P, int N, const int32_t *d_frame_point, const int32_t *d_local_point, const int32_t *d_n_local_point, int cap,
+                                 const uint8_t *d_pt_bad, const float *d_Xw, const float *d_normal, const float *d_max_dist, const float *d_min_dist,
+                                 const uint8_t *d_mpdesc, const uint8_t *d_obs, const orbm_local_map_t *out, int32_t *d_map_n, void *stream) {
+  if (!m) return ORBX_E_ARG;
+  std::lock_guard<std::mutex> lock(m->lm_mu);
+  if (P < 0 || N < 0 || cap < 0) { m->err = "GatherLocalMap: negative count"; return ORBX_E_ARG; }
+  if (!d_n_local_point || !out || !d_map_n || (N > 0 && !d_frame_point)) { m->err = "GatherLocalMap: NULL argument"; return ORBX_E_ARG; }
+  if (cap > 0 && (!d_local_point || !d_pt_bad || !d_Xw || !d_normal || !d_max_dist || !d_min_dist || !d_mpdesc || !out->eligible || !out->Xw || !out->normal ||
+                  !out->max_dist || !out->min_dist || !out->mpdesc)) { m->err = "GatherLocalMap: NULL array"; return ORBX_E_ARG; }
+  MCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  MCHECK(m, m->d_lm_flag.reserve(std::max<size_t>((size_t)P, 256)));
+  GatherParams A{P, N, cap, d_frame_point, d_local_point, d_n_local_point, d_pt_bad, d_Xw, d_normal, d_max_dist, d_min_dist, d_mpdesc, d_obs,
+                 (uint8_t *)m->d_lm_flag.p, (uint8_t *)out->eligible, (float *)out->Xw, (float *)out->normal, (float *)out->max_dist, (float *)out->min_dist,
+                 (uint8_t *)out->mpdesc, (uint8_t *)out->obs, d_map_n};
+  if (P > 0) MCHECK(m, hipMemsetAsync(m->d_lm_flag.p, 0, (size_t)P, s));
+  if (N > 0 && P > 0) hipLaunchKernelGGL(k_gather_mark, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(k_gather_local_map, dim3((unsigned)std::max(1, (cap + 31) / 32)), dim3(256), 0, s, A);
+  MCHECK(m, hipGetLastError());
   return 0;
 }
 

@@ -1289,6 +1289,135 @@ int orbm_keyframe_culling_host(const orbm_culling_t *c, const uint8_t *erasable,
                                int32_t *n_obs_out, uint8_t *bad_out);
 const char *orbm_keyframe_culling_host_error(void);
 
+/* ---- void Tracking::UpdateLocalMap()  (Tracking.cc:3542-3553) = UpdateLocalKeyFrames (:3590-3762) + UpdateLocalPoints (:3559-3587),
+ * and the counter and ordered lists of void KeyFrame::UpdateConnections(bool)  (KeyFrame.cc:407-492) ----
+ * Both members are one vote: every row's map point gives one increment to each keyframe that observes it.  Every compare is a function
+ * of csrc/orb_ref_localmap.h, host and device; all results are integers.  Parity: exact against the literal model of
+ * tests/update_local_map_model.py; Tracking.cc and KeyFrame.cc are not compiled under oracle/_ref, so the reference text itself is unpinned.
+ *
+ * The tables, a flattened view of the map that both members read.  The plain entries take host pointers; the _device entry takes the
+ * same struct holding device pointers: the caller keeps the tables resident and rewrites what local mapping changed with copies of its
+ * own.  The library keeps no store.
+ *
+ * RANK RULE - next to the MASKING, SEQUENTIAL, INDEPENDENCE, FUSE, SEARCH-AND-FUSE, ORDER and SEQUENTIAL CULLING RULES above.  The
+ * reference iterates map<KeyFrame*,int> and set<KeyFrame*> and sorts pair<int,KeyFrame*>, so its results depend on pointer values, but
+ * only on their ORDER.  kf_rank[g] are distinct integers that order the keyframes as their addresses do, and that is all either member
+ * reads of them:
+ *   - iteration of keyframeCounter / KFcounter (Tracking.cc:3658, KeyFrame.cc:455): ascending rank, so kf_max is the lowest-ranked
+ *     keyframe among those with the largest count (the compare is a strict >);
+ *   - iteration of spChilds (Tracking.cc:3708): kf_child lists every keyframe's children in ascending rank;
+ *   - the ties of sort(vPairs) (KeyFrame.cc:477): (weight, pointer) ascending, reversed by push_front (:480-484), which gives
+ *     descending weight and, among equal weights, descending rank.
+ * Rank is apart from the slot g so that a new keyframe costs a rewrite of one array of G ints and no re-index of the observations.
+ *
+ * STAMP NOTE.  The reference marks keyframes and points with mnTrackReferenceForFrame = mCurrentFrame.mnId, and nothing but
+ * Tracking.cc:3577-3750 writes that member.  A fresh set of marks per call is therefore the same thing for every frame id that has not
+ * been through UpdateLocalMap before; id 0, the member's initial value, never reaches TrackLocalMap.  The adapter snippet still writes
+ * the stamps back on the live objects.
+ *
+ * CONNECTIONS RULE.  KFcounter of a keyframe reads mvpMapPoints, the observations, isBad() and GetMap(); UpdateConnections of any
+ * keyframe writes none of them (it writes mConnectedKeyFrameWeights, the two ordered vectors, mpParent / mspChildrens and, through
+ * AddConnection, the same of other keyframes).  So the rows of T targets may be counted from the state at loop entry, in one call.
+ * What the member WRITES stays the caller's, replayed in the loop's order: the target's own three tables, AddConnection on the others
+ * with the UpdateBestCovisibles re-sort it triggers (KeyFrame.cc:205-242), and mpParent / AddChild at the first connection (:501-527). */
+#define ORBM_MAP_MAX_KEYFRAMES 16384      /* G: what one workgroup sorts in LDS (csrc/orb_sort.h) */
+#define ORBM_MAP_BEST 10                  /* GetBestCovisibilityKeyFrames(10) (Tracking.cc:3690) */
+typedef struct {
+  int32_t G;                      /* keyframes; g is a stable slot, not an order */
+  const int32_t *kf_rank;         /* [G] distinct: the RANK RULE */
+  const uint8_t *kf_bad;          /* [G] KeyFrame::isBad() (Tracking.cc:3662, :3696, :3711; KeyFrame.cc:434) */
+  const int32_t *kf_map;          /* [G] an integer standing for GetMap() (KeyFrame.cc:434) */
+  const int32_t *kf_row_start;    /* [G+1] rows of keyframe g = its mvpMapPoints (Tracking.cc:3569, KeyFrame.cc:415), at most ORBM_MAX_KEYPOINTS */
+  const int32_t *row_point;       /* [R] index into the points, -1 = NULL */
+  const int32_t *kf_best;         /* [G][10] GetBestCovisibilityKeyFrames(10) in its order, padded with -1 (KeyFrame.cc:259-266) */
+  const int32_t *kf_child_start;  /* [G+1] */
+  const int32_t *kf_child;        /* GetChilds() in the set's iteration order (Tracking.cc:3707-3708) */
+  const int32_t *kf_parent;       /* [G] GetParent() or -1 (Tracking.cc:3723) */
+  const int32_t *kf_prev;         /* [G] mPrevKF or -1 (Tracking.cc:3751); may be NULL when inertial == 0 */
+  int32_t P;                      /* map points */
+  const uint8_t *pt_bad;          /* [P] MapPoint::isBad() */
+  const int32_t *obs_start;       /* [P+1] */
+  const int32_t *obs_kf;          /* [E] GetObservations(): one entry per observing keyframe, as slots; the entries of a bad point are not read */
+} orbm_map_graph_t;
+
+/* UpdateLocalMap for one frame.  frame_point[N] = mCurrentFrame.mvpMapPoints (or mLastFrame's, Tracking.cc:3596-3646) as point indices,
+ * -1 = NULL.  inertial = the sensor test of :3737, last_kf = mCurrentFrame.mpLastKeyFrame or -1.
+ *   - the vote (:3599-3646): every slot with a point that is not bad gives one vote per entry of the point, with no filter on the voted
+ *     keyframe; a point in two slots votes twice; slot_bad[s] = 1 where the reference sets the slot to NULL (the point is bad), else 0;
+ *   - the first list (:3649-3675): the voted keyframes in rank order without the bad ones; kf_max / max_votes = pKFmax and max (-1 / 0
+ *     when there is none: mpReferenceKF stays);
+ *   - the expansion (:3680-3733) over the first list only: at the top of a trip stop when the list holds more than 80 (so it can end at
+ *     81, 82 or 83); the first of kf_best that is not bad and not marked; the first child that is not bad and not marked; the parent if
+ *     there is one and it is not marked, WITHOUT an isBad test, and its break leaves the OUTER loop (:3724-3731);
+ *   - the temporal tail (:3737-3754) when inertial and the list is below 80: from last_kf, up to 20 trips, stop at -1; an unmarked
+ *     keyframe is appended and the walk steps to kf_prev; at a marked one the reference does not advance, so nothing more changes;
+ *   - local points (:3559-3587): the local keyframes in REVERSE list order, each one's rows in row order; NULL rows, marked points and
+ *     bad points are skipped, the rest appended and marked.
+ * local_kf [cap_kf] / *n_local_kf = mvpLocalKeyFrames, local_point [cap_pts] / *n_local_point = mvpLocalMapPoints.  One staged upload,
+ * k_covis_vote, k_local_kf_walk, k_lp_first, k_lp_count, k_lp_write, one download, one synchronisation.  Returns 0; ORBX_E_CAP when a
+ * list does not fit (the counts hold what is needed, the lists are not written).  N == 0 returns 0 without touching the device, with
+ * both counts 0, kf_max -1 and max_votes 0.
+ *
+ * ORBX_E_ARG with a message, nothing launched and no output written, for: a NULL handle (device forms), struct or output; a NULL
+ * array that is indexed (kf_prev only when inertial; kf_child, row_point and obs_kf only when they have elements); G, P, N, T or a
+ * capacity < 0; G above ORBM_MAP_MAX_KEYFRAMES; a start table that does not begin at 0 or that decreases; more rows in one keyframe
+ * than ORBM_MAX_KEYPOINTS; a row_point or frame_point outside [-1, P); an obs_kf, kf_child or target outside [0, G); a kf_best,
+ * kf_parent, kf_prev or last_kf outside [-1, G); duplicate ranks; two entries of one point with the same keyframe; a target listed
+ * twice; inertial with kf_prev == NULL. */
+int orbm_update_local_map(orbm_t *m, const orbm_map_graph_t *graph, int N, const int32_t *frame_point, int inertial, int last_kf,
+                          int cap_kf, int cap_pts, int32_t *local_kf, int32_t *n_local_kf, int32_t *kf_max, int32_t *max_votes,
+                          uint8_t *slot_bad /*[N]*/, int32_t *local_point, int32_t *n_local_point);
+/* The same with everything resident: *graph is a HOST struct holding DEVICE pointers, frame_point and every output are device arrays,
+ * the counts are device ints.  Asynchronous on `stream`, nothing touches the host.  Writes are clamped at the capacities and the
+ * counts report what was needed.  The tables cannot be looked at: only the scalars are checked (NULL pointers, G, P, N, capacities,
+ * last_kf); an index outside its table is the caller's error, though a point or keyframe index that is out of range is skipped where
+ * it is read.  The handle's scratch (counters, the per-point word, the whole keyframe list) is shared by the calls on one handle:
+ * they must follow each other on one stream.  The per-point word is cleared by a memset at the start of every call.  N == 0 launches
+ * nothing and writes nothing. */
+int orbm_update_local_map_device(orbm_t *m, const orbm_map_graph_t *d_graph, int N, const int32_t *d_frame_point, int inertial, int last_kf,
+                                 int cap_kf, int cap_pts, int32_t *d_local_kf, int32_t *d_n_local_kf, int32_t *d_kf_max,
+                                 int32_t *d_max_votes, uint8_t *d_slot_bad, int32_t *d_local_point, int32_t *d_n_local_point, void *stream);
+/* The CPU statement from the same header, one object at a time in the reference's order: no handle, same outputs, same refusals (the
+ * message: orbm_update_local_map_host_error, which serves orbm_update_connections_host too).  Not a fallback of the device forms. */
+int orbm_update_local_map_host(const orbm_map_graph_t *graph, int N, const int32_t *frame_point, int inertial, int last_kf, int cap_kf,
+                               int cap_pts, int32_t *local_kf, int32_t *n_local_kf, int32_t *kf_max, int32_t *max_votes,
+                               uint8_t *slot_bad, int32_t *local_point, int32_t *n_local_point);
+const char *orbm_update_local_map_host_error(void);
+
+/* KFcounter and the ordered lists of KeyFrame::UpdateConnections for the T keyframes targets[T], all counted from the state at entry
+ * (CONNECTIONS RULE).  For target t (KeyFrame.cc:409-484): every row with a point that is not bad gives one count to every entry k of
+ * the point unless k == t, kf_bad[k] or kf_map[k] != kf_map[t] (:434).  A rig point held in two rows of t counts twice; from the other
+ * side it counts by the other keyframe's rows, so the weights need not be symmetric.  An empty counter (:442) means the member returns
+ * having written nothing: n_conn = 0, kf_max -1, nmax 0.  Otherwise, in rank order: kf_max / nmax by a strict > (:459), the pairs
+ * with count >= th (:464; th = 15 in the reference), or if there are none the single pair (nmax, kf_max) (:471-475), sorted as the
+ * RANK RULE says.  Outputs: conn_kf / conn_w [conn_start[t] .. conn_start[t+1]) = mConnectedKeyFrameWeights in rank order;
+ * ord_kf / ord_w [ord_start[t] .. ord_start[t+1]) = mvpOrderedConnectedKeyFrames / mvOrderedWeights; kf_max[t], nmax[t].  cap = the
+ * elements of each of the four list arrays.  One staged upload, k_covis_vote, k_conn_walk, k_conn_pack, one download, one
+ * synchronisation.  Returns 0; ORBX_E_CAP when conn_start[T] exceeds cap (the start tables, kf_max and nmax are written, the lists
+ * are not); T == 0 returns 0 without touching the device; refusals as above.
+ * COST: the device block of one call holds the counters and four work strips at stride G per target, 20 * T * G bytes beside the
+ * tables (1.5 MB at T = 150, G = 500; 21 MB at T = 65, G = 16 384; about 5.4 GB at T = G = 16 384, which fails as that allocation
+ * would, with ORBX_E_HIP).  A loop over many keyframes of a large map is passed in chunks of targets; the chunks are independent
+ * (CONNECTIONS RULE). */
+int orbm_update_connections(orbm_t *m, const orbm_map_graph_t *graph, int T, const int32_t *targets, int th, int cap,
+                            int32_t *conn_start /*[T+1]*/, int32_t *conn_kf, int32_t *conn_w, int32_t *ord_start /*[T+1]*/,
+                            int32_t *ord_kf, int32_t *ord_w, int32_t *kf_max /*[T]*/, int32_t *nmax /*[T]*/);
+int orbm_update_connections_host(const orbm_map_graph_t *graph, int T, const int32_t *targets, int th, int cap, int32_t *conn_start,
+                                 int32_t *conn_kf, int32_t *conn_w, int32_t *ord_start, int32_t *ord_kf, int32_t *ord_w,
+                                 int32_t *kf_max, int32_t *nmax);
+
+/* The arrays of an orbm_local_map_t from the local-point list that orbm_update_local_map_device left on the device and caller-resident
+ * per-point tables (all device pointers, indexed by point: d_Xw / d_normal 3 floats, d_max_dist / d_min_dist, d_mpdesc 32 bytes at a
+ * 4-byte aligned address, d_obs or NULL = all 1).  Element i < min(*d_n_local_point, cap) of every array of *out (a HOST struct of
+ * device pointers, written although the type says const; obs may be NULL, Tcw and n are not touched) is the point d_local_point[i];
+ * eligible = !pt_bad && the point is in no slot of d_frame_point[N] (Tracking.cc:3453-3471, :3483-3487); *d_map_n = that count, which
+ * is what orbm_search_local_points_batch_device takes as d_map_n with npairs = 1.  Asynchronous on `stream`, nothing touches the host;
+ * uses the handle's scratch as orbm_update_local_map_device does.  ORBX_E_ARG for a NULL required pointer, P, N or cap < 0. */
+int orbm_gather_local_map_device(orbm_t *m, int P, int N, const int32_t *d_frame_point, const int32_t *d_local_point,
+                                 const int32_t *d_n_local_point, int cap, const uint8_t *d_pt_bad, const float *d_Xw, const float *d_normal,
+                                 const float *d_max_dist, const float *d_min_dist, const uint8_t *d_mpdesc, const uint8_t *d_obs,
+                                 const orbm_local_map_t *out, int32_t *d_map_n, void *stream);
+
 /* ---- bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated) ----
  * (TwoViewReconstruction.cc:39-127; what GeometricCamera::ReconstructWithTwoViews calls for both camera models, Pinhole.cpp:126-133,
  * KannalaBrandt8.cpp:211-234, from Tracking::MonocularInitialization, Tracking.cc:2492).  Every expression of the member and of what it
