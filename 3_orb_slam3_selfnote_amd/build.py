@@ -8,7 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liborbhip.so")
-SOURCES = ["orbhip.hip", "orb_kernels.h", "orb_fast_score.h", "orb_match_kernels.h", "orb_match_mfma.h", "orb_mfma_util.h", "orb_common.h", "orb_sincos.h", "orb_project_kernels.h", "orb_ref_geometry.h", "orb_atan2f.h", "orb_logf.h", "orb_stereo_kernels.h", "orb_depth_kernels.h", "orb_tanf.h", "orb_ref_triangulate.h", "orb_rig_stereo_kernels.h", "orb_ref_newpoints.h",
+SOURCES = ["orbhip.hip", "orb_kernels.h", "orb_fast_score.h", "orb_match_kernels.h", "orb_match_mfma.h", "orb_mfma_util.h", "orb_common.h", "orb_lds.h", "orb_sincos.h", "orb_project_kernels.h", "orb_ref_geometry.h", "orb_atan2f.h", "orb_logf.h", "orb_stereo_kernels.h", "orb_depth_kernels.h", "orb_tanf.h", "orb_ref_triangulate.h", "orb_rig_stereo_kernels.h", "orb_ref_newpoints.h",
            "orb_newpoints_kernels.h", "orb_fuse_kernels.h", "orb_fuse_sim3_kernels.h", "orb_bow_kernels.h", "orb_ref_mappoint.h", "orb_mappoint_kernels.h",
            "orb_sort.h", "orb_ref_voc.h", "orb_voc_kernels.h", "orb_ref_kfdb.h", "orb_kfdb_kernels.h", "orb_ref_culling.h", "orb_culling_kernels.h", "orb_ref_localmap.h", "orb_localmap_kernels.h", "orb_ref_twoview.h", "orb_twoview_kernels.h", "orb_ref_sim3.h", "orb_sim3_kernels.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

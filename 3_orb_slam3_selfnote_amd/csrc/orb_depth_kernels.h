@@ -131,8 +131,7 @@ __global__ __launch_bounds__(CLOSE_THREADS) void k_close_points(CloseParams P) {
   if (c) atomicAdd(&s_cnt[1], c);
   if (nt) atomicAdd(&s_cnt[2], nt);
   if (nn) atomicAdd(&s_cnt[3], nn);
-  int p2 = 2;
-  while (p2 < n) p2 <<= 1;
+  const int p2 = sort_p2(n);
   for (int i = n + tid; i < p2; i += CLOSE_THREADS) s_key[i] = ~0ull;
   __syncthreads();
   m = s_cnt[0]; c = s_cnt[1];

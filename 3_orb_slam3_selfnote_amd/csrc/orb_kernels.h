@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "orb_common.h"
+#include "orb_lds.h"
 #include "orb_fast_score.h"
 #include "orb_sincos.h"
 
@@ -192,6 +193,27 @@ __device__ __forceinline__ size_t resize_stamp_row(const FrameParams &P, int lev
 #define TSTAMP(i, rowExpr, lvl) do {} while (0)
 #endif
 #define RSTAMP(i) TSTAMP(i, resize_stamp_row(P, level), level)
+// k_resize's dynamic LDS.  Two-pass form (tPitch > 0): the tile's source rows, their horizontally interpolated rows, the tile record's
+// row part.  One-pass form (tPitch == 0): the level's x table alone.
+__host__ __device__ constexpr int resize_row_bytes(int srcW) { return (srcW + 4 + 15) & ~15; }   // a source row and the 4 bytes pass 1 reads past it, in chunks
+__host__ __device__ constexpr int resize_t_pitch(int wq) { return (wq * 2 + 7) & ~7; }           // 16 bits per column of the padded level width
+struct ResizeCarve {
+  LdsRegion<uint8_t> rows;     // [maxSrc][rowBytes]: whole 16-byte chunks land here by LDS-DMA
+  LdsRegion<uint8_t> t;        // [maxSrc][tPitch], u16 entries
+  LdsRegion<uint4> rowRec;     // [RESIZE_ROWS_MAX], 16-byte aligned for its ds_read_b128 / ds_write_b128 (tPitch is a multiple of 8 only)
+  LdsRegion<int2> xtab;        // one-pass: [wq]
+  int bytes;
+  __host__ __device__ static constexpr ResizeCarve of(int maxSrc, int rowBytes, int tPitch, int wq) {
+    LdsCarver c;
+    const bool two = tPitch > 0;
+    ResizeCarve r{c.take<uint8_t>(two ? maxSrc * rowBytes : 0, 16), c.take<uint8_t>(two ? maxSrc * tPitch : 0),
+                  c.take<uint4>(two ? RESIZE_ROWS_MAX : 0, 16), c.take<int2>(two ? 0 : wq), 0};
+    r.bytes = c.at;
+    return r;
+  }
+};
+#define RESIZE_LDS_MAX (ORB_LDS_LIMIT - 1024)   // either form: leaves 1 KiB for the kernel's static LDS (the one-pass form's y entries, 128 B)
+#define RESIZE_STAGE_MAX (64 * 1024)            // a 16-row tile's rows + T rows: two workgroups per CU beside everything else; else 8-row tiles
 __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int smemRowBytes, int tPitch, int maxSrc) {
   TSTAMP_BEGIN();
   extern __shared__ __align__(16) uint8_t smem_rs[];
@@ -215,11 +237,9 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
     const __attribute__((address_space(4))) uint32_t *rec = (const __attribute__((address_space(4))) uint32_t *)tileRec;
     const rec4_t gr = *reinterpret_cast<const __attribute__((address_space(4))) rec4_t *>(rec);
     const int syFirst = (int)gr[0], nsrc = (int)gr[1], nrows = (int)gr[2];   // source row span of this tile (at most maxSrc rows), its output rows
-    uint8_t *sRows = smem_rs;                                  // [maxSrc][smemRowBytes]
-    uint8_t *sT = sRows + (size_t)maxSrc * smemRowBytes;       // [maxSrc][tPitch] bytes, u16 entries
-    // [RESIZE_ROWS_MAX], 16-byte aligned for its ds_read_b128 / ds_write_b128 (tPitch is a multiple of 8 only; the host's LDS size
-    // counts the same padding)
-    uint4 *sRowRec = reinterpret_cast<uint4 *>(sT + (((size_t)maxSrc * tPitch + 15) & ~(size_t)15));
+    const auto lds = ResizeCarve::of(maxSrc, smemRowBytes, tPitch, wq);
+    uint8_t *sRows = lds.rows.in(smem_rs), *sT = lds.t.in(smem_rs);
+    uint4 *sRowRec = lds.rowRec.in(smem_rs);
     // this thread's first two column pairs of pass 1, loaded ahead of the staging (a level up to 1024 columns wide needs no more)
     const int4 *xtab4 = reinterpret_cast<const int4 *>(P.xtab + G.xtabBase);
     int4 xtPre[2];
@@ -369,7 +389,7 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
   // the tile's y-coefficients go through LDS: the row code below then has no global load in front of it
   __shared__ int2 sY[RESIZE_ROWS_MAX];
   if (tid < nrows) sY[tid] = P.ytab[G.ytabBase + dy0 + tid];
-  int2 *sX = reinterpret_cast<int2 *>(smem_rs);                       // [wq]
+  int2 *sX = ResizeCarve::of(0, 0, 0, wq).xtab.in(smem_rs);
   for (int i = tid; i < wq; i += 256) sX[i] = P.xtab[G.xtabBase + i];
   __syncthreads();
   // q / qw in float: (q + 0.5) / qw is at least 0.5 / qw >= 2^-11 away from an integer, the product's rounding error is
@@ -407,6 +427,21 @@ __global__ __launch_bounds__(256) void k_resize(FrameParams P, int level, int sm
 // is the same function of the same bytes whoever computes it, so the planes are byte-identical.  About 10x the arithmetic of
 // the level-by-level form, on a chip that a single frame leaves empty; batches keep k_resize.
 // ------------------------------------------------------------------------------------------------------------
+// Dynamic LDS: the two level buffers (even / odd levels; FrameParams::chainBuf0 / chainBuf1 bytes, multiples of 16), then per level
+// 1..L the x entries of rect[l] and its y entries - `tab` entries for the tile that has most (the host's count; the kernel, which only
+// needs where the table starts, passes 0).
+struct ChainCarve {
+  LdsRegion<uint8_t> buf0, buf1;
+  LdsRegion<int2> tab;
+  int bytes;
+  __host__ __device__ static constexpr ChainCarve of(int buf0, int buf1, int tab) {
+    LdsCarver c;
+    ChainCarve r{c.take<uint8_t>(buf0, 16), c.take<uint8_t>(buf1, 16), c.take<int2>(tab), 0};
+    r.bytes = c.at;
+    return r;
+  }
+};
+#define CHAIN_LDS_MAX (64 * 1024)   // what a kernel gets unasked, and two workgroups per CU; configurations beyond it keep the level-by-level form
 __global__ __launch_bounds__(CHAIN_NT) void k_pyramid_chain(FrameParams P) {
   extern __shared__ __align__(16) uint8_t smem_ch[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -418,8 +453,9 @@ __global__ __launch_bounds__(CHAIN_NT) void k_pyramid_chain(FrameParams P) {
   if (tid < (int)(sizeof(ChainTile) / 4)) reinterpret_cast<uint32_t *>(&T)[tid] = reinterpret_cast<const uint32_t *>(&P.chain[tile])[tid];
   __syncthreads();
   const int L = T.level;
-  uint8_t *buf[2] = {smem_ch, smem_ch + P.chainBuf0};
-  int2 *sTab = reinterpret_cast<int2 *>(smem_ch + P.chainBuf0 + P.chainBuf1);   // per level 1..L: x entries of rect[l], then y entries
+  const auto lds = ChainCarve::of(P.chainBuf0, P.chainBuf1, 0);
+  uint8_t *buf[2] = {lds.buf0.in(smem_ch), lds.buf1.in(smem_ch)};
+  int2 *sTab = lds.tab.in(smem_ch);
   // table slices of every stage, one memory latency for all of them
   {
     int off = 0;
@@ -791,6 +827,57 @@ __global__ __launch_bounds__(FAST_NT) void k_fast(FrameParams P) {
 #endif
 struct OctNode { short ulx, urx, uly, bry; };
 
+// k_octree's dynamic LDS for `cap` nodes: a head region of `head` bytes (FrameParams::octHead: a multiple of 16, at least the
+// OCT_HEAD_PER_NODE bytes per node of the per-key rounds' child tables), OCT_BODY_PER_NODE bytes per node of node tables, the scan
+// scratch of an NT-thread workgroup and, behind it, the level's cell offsets where the host keeps them in LDS (cells > 0).
+// Three things lie over others.  best (the winners' 64-bit atomicMax) over chcnt: it is used after the last round.  pyr - the code
+// form's counts, leaves first (OCT_PYR_OFF), with the leaf -> list position map over the leaf bins - over the whole head, and codeA /
+// codeB (depth << 13 | ix << 5 | iy of a node's cell) over npos: chcnt, chpos and npos are live only while keys are re-labelled per
+// round, which the code form does not do.
+#define OCT_HEAD_PER_NODE 32   // chcnt + chpos
+#define OCT_BODY_PER_NODE 40   // nodeA .. sflag
+#define OCT_SCAN_BYTES 128     // what every launch reserves for the scan scratch (NT = 1024 uses 72 bytes of it)
+struct OctreeCarve {
+  LdsRegion<uint32_t> chcnt;   // 4 per node: keys per child
+  LdsRegion<int32_t> chpos;    // 4 per node: list position of each child
+  LdsRegion<unsigned long long> best;
+  LdsRegion<uint16_t> pyr;
+  LdsRegion<OctNode> nodeA, nodeB;
+  LdsRegion<uint32_t> cntA, cntB;
+  LdsRegion<int32_t> npos, rankOf;
+  LdsRegion<uint16_t> codeA, codeB;
+  LdsRegion<uint32_t> incl;    // child counts by rank -> inclusive sums
+  LdsRegion<uint32_t> sflag;   // unprocessed flags -> exclusive sums
+  LdsRegion<uint32_t> sw;      // scan scratch
+  LdsRegion<uint32_t> cellOff; // cells + 1 offsets of the level's FAST cells
+  int bytes;
+  __host__ __device__ static constexpr OctreeCarve of(int cap, int head, int nt, int cells) {
+    LdsCarver c;
+    OctreeCarve o{};
+    o.chcnt = c.take<uint32_t>(4 * cap);
+    o.chpos = c.take<int32_t>(4 * cap);
+    o.best = LdsCarver::over<unsigned long long>(0, cap);
+    o.pyr = LdsCarver::over<uint16_t>(0, head / 2);
+    c.at = head;
+    o.nodeA = c.take<OctNode>(cap); o.nodeB = c.take<OctNode>(cap);
+    o.cntA = c.take<uint32_t>(cap); o.cntB = c.take<uint32_t>(cap);
+    o.npos = c.take<int32_t>(cap); o.rankOf = c.take<int32_t>(cap);
+    o.codeA = LdsCarver::over<uint16_t>(o.npos.off, cap); o.codeB = LdsCarver::over<uint16_t>(o.codeA.end(), cap);
+    o.incl = c.take<uint32_t>(cap); o.sflag = c.take<uint32_t>(cap);
+    o.sw = c.take<uint32_t>(nt / 64 + 2);
+    o.cellOff = c.take<uint32_t>(cells > 0 ? cells + 1 : 0);
+    o.bytes = o.sw.off + OCT_SCAN_BYTES + o.cellOff.size();
+    return o;
+  }
+};
+static_assert(OctreeCarve::of(1, OCT_HEAD_PER_NODE, 256, 0).chpos.end() == OCT_HEAD_PER_NODE && OctreeCarve::of(1, OCT_HEAD_PER_NODE, 256, 0).sw.off == OCT_HEAD_PER_NODE + OCT_BODY_PER_NODE,
+              "bytes per node");
+static_assert(4 * (1024 / 64 + 2) <= OCT_SCAN_BYTES, "scan scratch of the widest workgroup");
+// What orbx_configure admits.  The kernel's static LDS is 32 bytes.
+#define OCT_LDS_MAX (ORB_LDS_LIMIT - 256)   // node tables and scan scratch: nfeatures beyond it are refused
+#define OCT_CELLS_LDS_MAX (96 * 1024)       // the cell offsets join them in LDS while the launch stays within this, which leaves 64 KiB of the CU to other workgroups
+#define OCT_GROWN_HEAD_MAX (32 * 1024)      // a head enlarged for the code tables (few nodes): only while the whole state stays this small
+
 #ifndef OCT_REGKEYS
 #define OCT_REGKEYS 4096   // keys of a level held in registers (the rest goes through the global cand / knode arrays)
 #endif
@@ -802,26 +889,20 @@ FrameParams P, uint32_t *cellOffScratch) {
   long long ot0 = __builtin_readcyclecounter();
 #endif
   const int CAP = P.octCap;
-  // carve (all offsets multiples of 8)
-  unsigned long long *best = reinterpret_cast<unsigned long long *>(smem);          // aliases chcnt/chpos
-  uint32_t *chcnt = reinterpret_cast<uint32_t *>(smem);                               // 4*CAP
-  int32_t *chpos = reinterpret_cast<int32_t *>(smem + 16 * (size_t)CAP);              // 4*CAP
-  OctNode *nodeA = reinterpret_cast<OctNode *>(smem + (size_t)P.octHead);
-  OctNode *nodeB = nodeA + CAP;
-  uint32_t *cntA = reinterpret_cast<uint32_t *>(nodeB + CAP);
-  uint32_t *cntB = cntA + CAP;
-  int32_t *npos = reinterpret_cast<int32_t *>(cntB + CAP);
-  int32_t *rankOf = npos + CAP;
-  uint32_t *incl = reinterpret_cast<uint32_t *>(rankOf + CAP);  // child counts by rank -> inclusive sums
-  uint32_t *sflag = incl + CAP;                                  // unprocessed flags -> exclusive sums
-  uint32_t *sw = sflag + CAP;                                    // scan scratch (NT/64+2)
+  const auto lds = OctreeCarve::of(CAP, P.octHead, NT, 0);   // (the cell count only sizes cellOff)
+  unsigned long long *best = lds.best.in(smem);
+  uint32_t *chcnt = lds.chcnt.in(smem);
+  int32_t *chpos = lds.chpos.in(smem);
+  OctNode *nodeA = lds.nodeA.in(smem), *nodeB = lds.nodeB.in(smem);
+  uint32_t *cntA = lds.cntA.in(smem), *cntB = lds.cntB.in(smem);
+  int32_t *npos = lds.npos.in(smem), *rankOf = lds.rankOf.in(smem);
+  uint32_t *incl = lds.incl.in(smem), *sflag = lds.sflag.in(smem), *sw = lds.sw.in(smem);
   __shared__ int shI[8];
   // Code form (P.octTab): every key is looked up once - its leaf of the depth-OCT_D split grid - and counted
   // into a leaf histogram; the counts of the coarser cells are sums, the rounds run on the nodes alone (a node knows its cell and
   // reads its children's counts), and a leaf -> list position map gives the keys their node at the end.  Bins, sums and map take
   // the place of chcnt / chpos, the nodes' cells that of npos: none of those is live while no key is re-labelled.
-  uint16_t *pyr = reinterpret_cast<uint16_t *>(smem);            // counts, leaves first (OCT_PYR_OFF); the map lies over the leaf bins
-  uint16_t *codeA = reinterpret_cast<uint16_t *>(npos), *codeB = codeA + CAP;   // depth << 13 | ix << 5 | iy
+  uint16_t *pyr = lds.pyr.in(smem), *codeA = lds.codeA.in(smem), *codeB = lds.codeB.in(smem);
   bool codes = P.octTab != nullptr;                              // false from the round that has to split a depth-OCT_D node
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -865,7 +946,7 @@ FrameParams P, uint32_t *cellOffScratch) {
   const int ncell = G.nCols * G.nRows;
   const uint32_t *cellCnt = P.cellCnt + (size_t)frame * P.cell_fs + G.cellBase;
   uint32_t *cellOffG = cellOffScratch + (size_t)frame * P.cell_fs + G.cellBase;
-  uint32_t *cellOffL = sw + (NT / 64 + 2);          // ncell + 1 words behind the scan scratch (CELLS_LDS only)
+  uint32_t *cellOffL = lds.cellOff.in(smem);        // ncell + 1 words behind the scan scratch (CELLS_LDS only)
   uint32_t carry = 0;
   for (int base = 0; base < ncell; base += NT) {
     int i = base + tid;
@@ -931,7 +1012,7 @@ FrameParams P, uint32_t *cellOffScratch) {
   if (n > 65535) codes = false;   // the counts are 16 bits wide
   if (codes) {
     // the one pass over the keys: leaf code (root and x bits from the column table, y bits from the row table) and leaf histogram
-    uint32_t *bins = reinterpret_cast<uint32_t *>(smem);   // two 16-bit bins per word; no count passes n <= 65535
+    uint32_t *bins = reinterpret_cast<uint32_t *>(pyr);   // the carve's pyr, its leaf bins two to a word; no count passes n <= 65535
     for (int i = tid; i < (nIni << (2 * OCT_D - 1)); i += NT) bins[i] = 0u;
     if (tid == 0) shI[5] = 0;
     __syncthreads();
@@ -2072,11 +2153,23 @@ __device__ __forceinline__ uint32_t clahe_blend(const uint8_t *p1, const uint8_t
   return (uint32_t)min(max(__float2int_rn(res), 0), 255);
 }
 
+// Dynamic LDS of the two interpolation kernels: `rows` rows of the frame's table, tilesX * 256 bytes each, copied a dword at a time.
+struct ClaheCarve {
+  LdsRegion<uint8_t> lut;
+  int bytes;
+  __host__ __device__ static constexpr ClaheCarve of(int rows, int tilesX) {
+    LdsCarver c;
+    ClaheCarve r{c.take<uint8_t>(rows * tilesX * 256, 4), 0};
+    r.bytes = c.at;
+    return r;
+  }
+};
 // k_clahe_interp: the whole LUT (tilesX*tilesY*256 bytes, 16 KB for 8x8) sits in LDS; four pixels per thread.
 // Every product and sum is rounded on its own, as the reference's scalar float expression is (no fused multiply-add).
 __global__ __launch_bounds__(256) void k_clahe_interp(const uint8_t *src, int rows, int cols, size_t sstride, int tilesX, int tilesY, float inv_tw,
                                                       float inv_th, const uint8_t *lut, uint8_t *dst, size_t dstride, int rowsPerBlock) {
-  extern __shared__ uint8_t sLut[];
+  extern __shared__ uint8_t smem_lut[];
+  uint8_t *sLut = ClaheCarve::of(tilesY, tilesX).lut.in(smem_lut);
   const int nl = tilesX * tilesY * 256;
   for (int i = threadIdx.x * 4; i < nl; i += 1024) *reinterpret_cast<uint32_t *>(sLut + i) = *reinterpret_cast<const uint32_t *>(lut + i);
   __syncthreads();
@@ -2222,7 +2315,8 @@ __global__ __launch_bounds__(256) void k_clahe_lut_batch(ClaheBatch P) {
 // and walks down the band: the column terms are computed once per quad, the row terms once per row.  With fewer quads than threads
 // the threads split into row phases.
 __global__ __launch_bounds__(256) void k_clahe_interp_batch(ClaheBatch P) {
-  extern __shared__ uint8_t sLut[];
+  extern __shared__ uint8_t smem_lut[];
+  uint8_t *sLut = ClaheCarve::of(0, P.tilesX).lut.in(smem_lut);   // (the host's count is the most rows any band stages)
   const int yb = blockIdx.x * CLAHE_BAND_ROWS, ye = min(yb + CLAHE_BAND_ROWS, P.rows);
   int first, count;
   clahe_band_lut_rows(yb, ye - 1, P.inv_th, P.tilesY, first, count);

@@ -134,15 +134,15 @@ __device__ __forceinline__ int kfdb_block_scan(int v, int *s_scan, int tid, int 
   return incl - v;
 }
 
-// dynamic LDS: p2(n_slots) keys
+// dynamic LDS: SortCarve::of(n_slots)
 __global__ __launch_bounds__(KFDB_THREADS) void k_kfdb_order(KfdbParams P) {
-  extern __shared__ __align__(16) uint64_t s_kkey[];
+  extern __shared__ __align__(16) uint8_t smem_kkey[];
+  uint64_t *s_kkey = SortCarve::of(P.n_slots).keys.in(smem_kkey);
   __shared__ int s_scan[KFDB_THREADS];
   const int q = blockIdx.x, tid = threadIdx.x;
   const size_t at = (size_t)q * P.n_slots;
   const int32_t *cnt = P.cnt + at;
-  int p2 = 2;
-  while (p2 < P.n_slots) p2 <<= 1;
+  const int p2 = sort_p2(P.n_slots);
   const int per = p2 > KFDB_THREADS ? p2 / KFDB_THREADS : 1;   // consecutive sorted positions per lane
   int mine = 0;
   for (int i = tid; i < p2; i += KFDB_THREADS) {

@@ -119,8 +119,7 @@ __device__ __forceinline__ int lm_voted_in_rank_order(const LmTables &M, const i
     if (count[g] > 0) s_key[atomicAdd(s_n, 1)] = lm_rank_key(M.kf_rank[g], g);
   __syncthreads();
   const int n = *s_n;
-  int p2 = 2;
-  while (p2 < n) p2 <<= 1;
+  const int p2 = sort_p2(n);
   for (int i = n + tid; i < p2; i += LM_WALK_THREADS) s_key[i] = ~0ull;
   __syncthreads();
   bitonic_sort_lds<LM_WALK_THREADS>(s_key, p2, tid);
@@ -154,9 +153,10 @@ struct WalkParams {
   int32_t *n_local_kf, *kf_max, *max_votes, *n_local_point;
 };
 
-// dynamic LDS: p2(G) keys
+// dynamic LDS: SortCarve::of(G)
 __global__ __launch_bounds__(LM_WALK_THREADS) void k_local_kf_walk(WalkParams W) {
-  extern __shared__ __align__(16) uint64_t s_lkey[];
+  extern __shared__ __align__(16) uint8_t smem_lkey[];
+  uint64_t *s_lkey = SortCarve::of(W.M.G).keys.in(smem_lkey);
   __shared__ int s_scan[LM_WALK_THREADS];
   __shared__ uint32_t s_mark[512];                                               // a bit per keyframe, G <= 16384
   __shared__ unsigned long long s_best;
@@ -337,9 +337,10 @@ struct ConnParams {
   int32_t *kf_max, *nmax;       // [T]
 };
 
-// dynamic LDS: p2(G) keys
+// dynamic LDS: SortCarve::of(G)
 __global__ __launch_bounds__(LM_WALK_THREADS) void k_conn_walk(ConnParams C) {
-  extern __shared__ __align__(16) uint64_t s_ckey[];
+  extern __shared__ __align__(16) uint8_t smem_ckey[];
+  uint64_t *s_ckey = SortCarve::of(C.M.G).keys.in(smem_ckey);
   __shared__ unsigned long long s_best;
   __shared__ int s_n, s_pairs;
   const LmTables &M = C.M;
@@ -363,8 +364,7 @@ __global__ __launch_bounds__(LM_WALK_THREADS) void k_conn_walk(ConnParams C) {
   if (n > 0 && s_pairs == 0 && tid == 0) { s_ckey[0] = ((uint64_t)(uint32_t)(0x7fffffff - nmax) << 32) | (uint32_t)(0x7fffffff - best_at); s_pairs = 1; }
   __syncthreads();
   const int np = s_pairs;
-  int p2 = 2;
-  while (p2 < np) p2 <<= 1;
+  const int p2 = sort_p2(np);
   for (int i = np + tid; i < p2; i += LM_WALK_THREADS) s_ckey[i] = ~0ull;
   __syncthreads();
   bitonic_sort_lds<LM_WALK_THREADS>(s_ckey, p2, tid);

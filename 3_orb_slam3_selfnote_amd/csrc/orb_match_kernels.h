@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "orb_common.h"
+#include "orb_lds.h"
 #include "orb_mfma_util.h"
 #include "orb_ref_triangulate.h"
 
@@ -438,6 +439,26 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_scan(MatchProblemSet M, type
 #define WALK_LIST 16   // passing candidates a lane collects before it computes their distances
 struct WalkRec { float x, y; uint32_t w; };   // w = octave | gx << 4 | gy << 10 | usable << 16 | keypoint index << 17
 
+// k_match_walk's dynamic LDS (K: the key type).  Descriptors stay in global memory: only the few candidates that pass every test are
+// compared, and 32 more bytes per keypoint would halve the workgroups per CU.  At capn = WALK_MAX_N with every term: 60 KiB.
+__host__ __device__ constexpr bool walk_needs_ur(int mode) { return mode == SCAN_UR || mode == SCAN_FUSE; }
+template <typename K>
+struct WalkCarve {
+  LdsRegion<uint32_t> cell;   // cell starts of the counting sort: GRID_CELLS + 1 words, + 3 pad
+  LdsRegion<WalkRec> rec;     // per keypoint, IN CELL ORDER
+  LdsRegion<float> ur;        // its right coordinate: the modes that test it (walk_needs_ur; the host gives every u_right problem the room)
+  LdsRegion<uint16_t> list;   // [WALK_LIST][MATCH_NT]: per lane a short list of passing candidates
+  LdsRegion<K> merge;         // [MATCH_NT][MATCH_TOPK], LPQ > 1 only
+  int bytes;
+  __host__ __device__ static constexpr WalkCarve of(int capn, bool ur, int lpq) {
+    LdsCarver c;
+    WalkCarve w{c.take<uint32_t>(GRID_CELLS + 4), c.take<WalkRec>(capn), c.take<float>(ur ? capn : 0),
+                c.take<uint16_t>(WALK_LIST * MATCH_NT), c.take<K>(lpq > 1 ? MATCH_TOPK * MATCH_NT : 0), 0};
+    w.bytes = c.at;
+    return w;
+  }
+};
+
 // LPQ = lanes per query.  1: a batch (one lane walks a query's whole window).  4: few pairs in flight (single-frame calls) - the
 // columns of a window are dealt to four adjacent lanes, whose lists lane 0 merges: the walk is a serial chain per lane, and
 // a quarter of the columns is a quarter of the chain; four times the workgroups stage the frame, on CUs that are idle anyway.
@@ -445,7 +466,7 @@ template <typename KT, int MODE, int LPQ>
 __global__ __launch_bounds__(MATCH_NT) void k_match_walk(MatchProblemSet M, typename KT::T *topk, int force, int capn /* LDS rows: >= every n, <= WALK_MAX_N */,
                                                          int wqblocks /* query blocks of MATCH_NT / LPQ queries per pair */) {
   typedef typename KT::T K;
-  extern __shared__ __align__(16) uint32_t smem_walk[];
+  extern __shared__ __align__(16) uint8_t smem_walk[];
   __shared__ int sVote;
   __shared__ uint32_t sWaveSum[MATCH_NT / 64];
 #ifdef WALK_STAMPS
@@ -464,15 +485,13 @@ __global__ __launch_bounds__(MATCH_NT) void k_match_walk(MatchProblemSet M, type
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;
   const float *kp = M.kp + fo * 7;
   const uint4 *desc = reinterpret_cast<const uint4 *>(M.desc + fo * 32);
-  constexpr bool STEREO = MODE == SCAN_FISHEYE, UR = MODE == SCAN_UR, NEEDUR = MODE == SCAN_UR || MODE == SCAN_FUSE;
-  // LDS: cell starts (GRID_CELLS + 1 words, +3 pad); per keypoint IN CELL ORDER a 12-byte record (+ its right coordinate for the
-  // modes that test it); per lane a short list of passing candidates.  Descriptors stay in global memory: only the few
-  // candidates that pass every test are compared, and 32 more bytes per keypoint would halve the workgroups per CU.
-  uint32_t *sCell = smem_walk;
-  WalkRec *sRec = reinterpret_cast<WalkRec *>(smem_walk + GRID_CELLS + 4);
-  float *sUr = reinterpret_cast<float *>(sRec + capn);
-  uint16_t *sList = reinterpret_cast<uint16_t *>(sUr + (NEEDUR ? capn : 0));   // [WALK_LIST][MATCH_NT]
-  K *sMerge = reinterpret_cast<K *>(sList + WALK_LIST * MATCH_NT);              // [MATCH_NT][MATCH_TOPK], LPQ > 1 only
+  constexpr bool STEREO = MODE == SCAN_FISHEYE, UR = MODE == SCAN_UR, NEEDUR = walk_needs_ur(MODE);
+  const auto lds = WalkCarve<K>::of(capn, NEEDUR, LPQ);
+  uint32_t *sCell = lds.cell.in(smem_walk);
+  WalkRec *sRec = lds.rec.in(smem_walk);
+  float *sUr = lds.ur.in(smem_walk);
+  uint16_t *sList = lds.list.in(smem_walk);
+  K *sMerge = lds.merge.in(smem_walk);
   for (int c = tid; c < GRID_CELLS + 4; c += MATCH_NT) sCell[c] = 0u;
   __syncthreads();
   // ---- counting sort by cell: histogram (the atomic's return value is the keypoint's rank inside its cell) ...
@@ -774,13 +793,50 @@ __device__ __forceinline__ uint32_t decide(const MatchProblemSet &M, const typen
 // shares.  The same pass serves the (now rare) lists exhausted inside a chunk.  The keypoints sit at position = rank (records and
 // descriptors in the global table `cand`, seeds in LDS), so a key's low 11 bits are the position and sPerm gives the index.  What this replaces: the all-pairs scan kernel (0.23 ms per 256
 // frame pairs) and the 36 refresh passes per pair that re-scanned the frame on the vector ALU (70 % of k_match_resolve's 0.29 ms).
+// k_match_resolve's dynamic LDS, for frames of up to maxn keypoints, in its three forms: plain (cand = fused = false: 10 B per
+// keypoint, +2 with the partner table), LDSCAND (cand: + the octave bytes and, in sPerm order so that the refresh scan reads them
+// sequentially and conflict-free, records and descriptors: + 49 B) and FUSED (+ the octave bytes and the seeds: + 5 B; records and
+// descriptors live in global memory, `cand` of the kernel, which leaves most of the CU's LDS to the pipelines running beside it).
+struct ResolveCarve {
+  LdsRegion<uint4> desc;         // cand: the descriptors' two halves
+  LdsRegion<CandMeta> meta;      // cand: the records
+  LdsRegion<uint32_t> owner;     // claim words; word maxn is a dummy that stays free
+  LdsRegion<int32_t> slot;
+  LdsRegion<uint16_t> perm;      // keypoints sorted by grid column
+  LdsRegion<uint16_t> partner;   // has_partner: stereo partner of each keypoint, 0xffff = none
+  LdsRegion<uint8_t> oct;        // cand, fused: octave bytes
+  LdsRegion<uint32_t> rank;      // fused: accumulator seed of the keypoint at sorted position pos
+  int bytes;                        // + two spare words behind the last region, which every launch has always had
+  __host__ __device__ static constexpr ResolveCarve of(int n, bool has_partner, bool cand, bool fused) {
+    LdsCarver c;
+    ResolveCarve r{c.take<uint4>(cand ? 2 * n : 0), c.take<CandMeta>(cand ? n : 0), c.take<uint32_t>(n + 1), c.take<int32_t>(n),
+                   c.take<uint16_t>((n + 1) & ~1), c.take<uint16_t>(has_partner ? 2 * ((n + 1) / 2 + 1) : 0, 4),
+                   c.take<uint8_t>(cand || fused ? (n + 3) & ~3 : 0, 4), c.take<uint32_t>(fused ? n : 0), 0};
+    r.bytes = c.at + 8;
+    return r;
+  }
+};
+// What the host admits (search_batch).  The static LDS of the instance comes on top; tests/test_lds_carves.py adds the two up for
+// every instance from the compiler's metadata.
+#define RESOLVE_LDSCAND_MAX (136 * 1024)   // records in LDS while the carve leaves 24 KiB: Key32's wide list array (16 KiB), chunk lists, requests, shares
+#define RESOLVE_FUSED_MAX (138 * 1024)     // leaves 22 KiB for the fused instance's work areas (12 KiB) and lists; slack: Key32 frames stop at 31 KiB
+#define RESOLVE_LDS_MAX (152 * 1024)       // the plain form of Key64 frames: leaves 8 KiB for the chunk lists, requests and shares (6.5 KiB)
+// The form search_batch launches for frames of up to maxn keypoints (fused_ok: everything but LDS allows the fused form) and its carve;
+// bytes > RESOLVE_LDS_MAX: the call is refused.
+struct ResolveForm { bool ldscand, fused; int bytes; };
+constexpr ResolveForm resolve_form(int maxn, bool has_partner, bool fused_ok) {
+  const bool ldscand = ResolveCarve::of(maxn, has_partner, true, false).bytes <= RESOLVE_LDSCAND_MAX;
+  const bool fused = fused_ok && ResolveCarve::of(maxn, has_partner, false, true).bytes <= RESOLVE_FUSED_MAX;
+  return {ldscand, fused, ResolveCarve::of(maxn, has_partner, ldscand && !fused, fused).bytes};
+}
+
 template <typename KT, bool LDSCAND, bool FUSED = false>
 __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(MatchProblemSet M, const typename KT::T *topk, int maxn, int rforce,
                                                                    const uint32_t *rec = nullptr, const uint32_t *keyrec = nullptr, const uint32_t *pairflag = nullptr,
                                                                    uint4 *cand = nullptr /* FUSED: 3 * maxn records per pair, see the carve */) {
   constexpr int NW_ = RESOLVE_NW_OF(FUSED);   // wavefronts of this workgroup (see RESOLVE_NW_OF)
   typedef typename KT::T K;
-  extern __shared__ __align__(16) uint32_t smem_resolve[];
+  extern __shared__ __align__(16) uint8_t smem_resolve[];
   __shared__ K sTk[MATCH_TOPK * 64];
   __shared__ int sCol[66 + 66];  // column starts (65 bins + end), then the scatter cursors
   __shared__ int sCmd;           // number of refresh requests posted, -1 = exit
@@ -796,19 +852,17 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
   const uint32_t *desc = reinterpret_cast<const uint32_t *>(M.desc + fo * 32);
   int32_t *slot = M.slot + fo;
   uint8_t *slot_obs = M.slot_obs + fo;
-  // carve: [desc 8*maxn words][meta 4*maxn words] (LDSCAND only, both in sPerm order: the refresh scan then reads them
-  // sequentially, conflict-free, instead of at random) [owner maxn+1][slot maxn][perm: maxn u16][partner][octave: maxn u8 (LDSCAND only)]
-  // [seed maxn words (FUSED only)].  FUSED: descriptors and records, in the same sPerm order, live in global memory instead (`cand`: this
-  // pair's 2 * maxn descriptor halves, then maxn records, written once below and read back through L2 by the list builds), so the
-  // carve is 15 B per keypoint instead of 63 and the kernel leaves most of its CU's LDS to the pipelines running beside it.
-  uint4 *cDesc = FUSED ? cand + (size_t)p * 3 * maxn : reinterpret_cast<uint4 *>(smem_resolve);
-  CandMeta *cMeta = FUSED ? reinterpret_cast<CandMeta *>(cDesc + 2 * (size_t)maxn) : reinterpret_cast<CandMeta *>(smem_resolve + (LDSCAND ? 8 * (size_t)maxn : 0));
-  uint32_t *sOwner = smem_resolve + (LDSCAND && !FUSED ? 12 * (size_t)maxn : 0);
-  int32_t *sSlot = reinterpret_cast<int32_t *>(sOwner + maxn + 1);
-  uint16_t *sPerm = reinterpret_cast<uint16_t *>(sSlot + maxn);
-  uint16_t *sPartner = sPerm + ((maxn + 1) & ~1);   // stereo partner of each keypoint, 0xffff = none (only if M.partner)
-  uint8_t *sOct = reinterpret_cast<uint8_t *>(reinterpret_cast<uint32_t *>(sPartner) + (M.partner ? (maxn + 1) / 2 + 1 : 0));
-  uint32_t *sRank = reinterpret_cast<uint32_t *>(sOct + ((maxn + 3) & ~3));   // FUSED only: accumulator seed of the keypoint at sorted position pos
+  // FUSED: descriptors and records, in the carve's sPerm order, live in global memory (`cand`: this pair's 2 * maxn descriptor halves,
+  // then maxn records, written once below and read back through L2 by the list builds).
+  const auto lds = ResolveCarve::of(maxn, M.partner != nullptr, LDSCAND && !FUSED, FUSED);
+  uint4 *cDesc = FUSED ? cand + (size_t)p * 3 * maxn : lds.desc.in(smem_resolve);
+  CandMeta *cMeta = FUSED ? reinterpret_cast<CandMeta *>(cDesc + 2 * (size_t)maxn) : lds.meta.in(smem_resolve);
+  uint32_t *sOwner = lds.owner.in(smem_resolve);
+  int32_t *sSlot = lds.slot.in(smem_resolve);
+  uint16_t *sPerm = lds.perm.in(smem_resolve);
+  uint16_t *sPartner = lds.partner.in(smem_resolve);
+  uint8_t *sOct = lds.oct.in(smem_resolve);
+  uint32_t *sRank = lds.rank.in(smem_resolve);
   bool fusedPair = false;
   if constexpr (FUSED) fusedPair = pairflag[p] != 0u;
   int *sFill = sCol + 66;
@@ -1582,10 +1636,21 @@ __global__ __launch_bounds__(64 * RESOLVE_NW_OF(FUSED)) void k_match_resolve(Mat
 // Runs once per monocular initialisation attempt (Tracking.cc:2471), so one wavefront per problem is enough.
 // Output: match_of_query[q] = keypoint accepted AT q's turn (or -1), best_dist[q] = its distance; the caller replays the
 // steals (:781-785) and the rotation histogram, which need the accept-time pairs.
+// k_init_resolve's dynamic LDS: vMatchedDistance of every keypoint, 0xffff = INT_MAX (:733); + 16 spare bytes, as every launch has had.
+struct InitResolveCarve {
+  LdsRegion<uint16_t> vmd;
+  int bytes;
+  __host__ __device__ static constexpr InitResolveCarve of(int maxn) {
+    LdsCarver c;
+    InitResolveCarve r{c.take<uint16_t>(maxn), 0};
+    r.bytes = c.at + 16;
+    return r;
+  }
+};
 template <typename KT>
 __global__ __launch_bounds__(64) void k_init_resolve(MatchProblemSet M, const typename KT::T *topk, int th_low) {
   typedef typename KT::T K;
-  extern __shared__ __align__(16) uint32_t smem_init[];
+  extern __shared__ __align__(16) uint8_t smem_init[];
   __shared__ K sTk[MATCH_TOPK * 64];
   const int lane = threadIdx.x;
   const int p = blockIdx.x;
@@ -1594,7 +1659,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(MatchProblemSet M, const ty
   const size_t fo = (size_t)p * M.frame_stride, qo = (size_t)p * M.query_stride;
   const float *kp = M.kp + fo * 7;
   const uint32_t *desc = reinterpret_cast<const uint32_t *>(M.desc + fo * 32);
-  uint16_t *sVMD = reinterpret_cast<uint16_t *>(smem_init);  // vMatchedDistance, 0xffff = INT_MAX (:733)
+  uint16_t *sVMD = InitResolveCarve::of(n).vmd.in(smem_init);   // (n <= the host's maxn, which the kernel is not given: one region, the same offset)
   for (int i = lane; i < n; i += 64) sVMD[i] = 0xffff;
   __builtin_amdgcn_s_barrier();
   int nacc = 0;

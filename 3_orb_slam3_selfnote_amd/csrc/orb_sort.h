@@ -5,6 +5,23 @@
 // low bits and get a stable order by construction.
 #pragma once
 #include <stdint.h>
+#include "orb_lds.h"
+
+// The sort's length for n keys: the power of two >= max(n, 2).  The one definition, for the kernels and for the host.
+__host__ __device__ constexpr int sort_p2(int n) { int p2 = 2; while (p2 < n) p2 <<= 1; return p2; }
+
+// Dynamic LDS of a kernel that sorts up to `cap` keys in it (k_local_kf_walk, k_conn_walk, k_voc_collect, k_kfdb_order): the keys.
+// cap <= 16384 in all four (128 KiB), beside at most 3 KiB of static LDS.
+struct SortCarve {
+  LdsRegion<uint64_t> keys;
+  int bytes;
+  __host__ __device__ static constexpr SortCarve of(int cap) {
+    LdsCarver c;
+    SortCarve s{c.take<uint64_t>(sort_p2(cap)), 0};
+    s.bytes = c.at;
+    return s;
+  }
+};
 
 template <int THREADS>
 __device__ __forceinline__ void bitonic_sort_lds(uint64_t *s_key, int p2, int tid) {

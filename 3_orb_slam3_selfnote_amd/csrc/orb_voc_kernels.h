@@ -120,7 +120,8 @@ __device__ __forceinline__ int voc_block_scan(int v, int *s_scan, int tid, int *
 // Per word the value is built by ONE lane, feature after feature (voc_add), since k sequential adds of w are not k * w; the L1 sum
 // is walked by ONE lane in ascending word order (voc_l1_step), since its order is part of the result; then all lanes divide.
 __global__ __launch_bounds__(VOC_THREADS) void k_voc_collect(VocCollectParams P) {
-  extern __shared__ __align__(16) uint64_t s_vkey[];   // p2(cap) keys; afterwards the values as doubles
+  extern __shared__ __align__(16) uint8_t smem_vkey[];
+  uint64_t *s_vkey = SortCarve::of(P.cap).keys.in(smem_vkey);   // afterwards the values as doubles
   __shared__ int s_scan[VOC_THREADS];
   __shared__ int s_live;
   __shared__ double s_norm;
@@ -129,8 +130,7 @@ __global__ __launch_bounds__(VOC_THREADS) void k_voc_collect(VocCollectParams P)
   const size_t at = (size_t)p * P.cap;
   const int32_t *entry = P.entry + at;
   const uint32_t *node = P.node + at;
-  int p2 = 2;
-  while (p2 < n) p2 <<= 1;
+  const int p2 = sort_p2(n);
   const int per = p2 > VOC_THREADS ? p2 / VOC_THREADS : 1;   // consecutive sorted positions per lane
   const bool adds = voc_adds_weight(P.weighting);
 

@@ -165,8 +165,8 @@ static hipError_t join_last(orbx_handle *h) {
 // The dynamic-LDS limit is an attribute of the kernel FUNCTION (per device), not of a handle or a launch: handles on
 // several host threads (Tracking / LocalMapping / LoopClosing each own a matcher, stereo runs two extractors) would race
 // a per-launch "set to this launch's size" against each other's launches.  It is raised once per device, to the CU's whole
-// 160 KiB, for every kernel that can ask for more than the 64 KiB default; launches only check their own size against it.
-#define ORB_LDS_LIMIT (160 * 1024)
+// 160 KiB (ORB_LDS_LIMIT, orb_lds.h), for every kernel that can ask for more than the 64 KiB default; launches only check their own
+// size against it.
 struct LdsOnce { std::mutex mu; bool done[64] = {}; };   // the once-table of one kernel list
 static hipError_t raise_lds_once(LdsOnce &once, int device, std::initializer_list<const void *> fns) {
   std::lock_guard<std::mutex> lock(once.mu);
@@ -374,17 +374,14 @@ int orbx_debug_fast_stamps(void *d_buf) {
 
 int orbx_max_keypoints(const orbx_t *h) { return h ? h->maxKeypoints : ORBX_E_ARG; }
 
-// k_resize's form for level G from level Gs, and the dynamic LDS it takes.  Two-pass form (rows and their horizontal interpolation
-// staged in LDS) whenever a tile's source rows fit the stage and pass 1's precondition holds (two neighbouring columns' source bytes
-// inside one aligned 8-byte window: horizontal scale factor below 3): returns the pitch of the interpolated rows.  Otherwise the
-// one-pass form straight from global memory, which stages the x table only: returns 0.
-static int resize_form(const LevelGeom &G, const LevelGeom &Gs, size_t *lds) {
-  const int rowBytes = (int)align_up((size_t)Gs.w + 4, 16);
-  const int wq = (G.w + 3) & ~3;
-  const int tPitch2 = (int)align_up((size_t)wq * 2, 8);                  // horizontally interpolated rows, 16 bits per column
-  const size_t lds2 = (size_t)G.resizeSrcRows * rowBytes + align_up((size_t)G.resizeSrcRows * tPitch2, 16) + 16 * RESIZE_ROWS_MAX;   // + the row records, 16-byte aligned
-  const bool twoPass = G.resizeSrcRows <= RESIZE_MAXSRC && (double)Gs.w / G.w < 3.0 && lds2 <= ORB_LDS_LIMIT - 1024;   // (very wide images: one-pass)
-  *lds = twoPass ? lds2 : (size_t)wq * 8;
+// k_resize's form for level G from level Gs.  Two-pass form (rows and their horizontal interpolation staged in LDS) whenever a tile's
+// source rows fit the stage and pass 1's precondition holds (two neighbouring columns' source bytes inside one aligned 8-byte window:
+// horizontal scale factor below 3): returns the pitch of the interpolated rows.  Otherwise the one-pass form straight from global
+// memory, which stages the x table only: returns 0.
+static int resize_form(const LevelGeom &G, const LevelGeom &Gs) {
+  const int wq = (G.w + 3) & ~3, tPitch2 = resize_t_pitch(wq);
+  const bool twoPass = G.resizeSrcRows <= RESIZE_MAXSRC && (double)Gs.w / G.w < 3.0 &&
+                       ResizeCarve::of(G.resizeSrcRows, resize_row_bytes(Gs.w), tPitch2, wq).bytes <= RESIZE_LDS_MAX;   // (very wide images: one-pass)
   return twoPass ? tPitch2 : 0;
 }
 
@@ -496,13 +493,12 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
         }
         return m;
       };
-      const size_t rowStage = align_up((size_t)sw + 4, 16) + align_up((size_t)((G.w + 3) & ~3) * 2, 8);
+      const size_t rowStage = (size_t)resize_row_bytes(sw) + (size_t)resize_t_pitch((G.w + 3) & ~3);
       G.resizeRows = RESIZE_ROWS_MAX;
       G.resizeSrcRows = src_rows(G.resizeRows);
-      if ((size_t)G.resizeSrcRows * rowStage > 64 * 1024 || G.resizeSrcRows > RESIZE_MAXSRC) { G.resizeRows = 8; G.resizeSrcRows = src_rows(8); }
+      if ((size_t)G.resizeSrcRows * rowStage > RESIZE_STAGE_MAX || G.resizeSrcRows > RESIZE_MAXSRC) { G.resizeRows = 8; G.resizeSrcRows = src_rows(8); }
       // the level's form, and the record of every row tile (layout: orb_common.h), from the table entries above
-      size_t ldsUnused;
-      G.resizeTPitch = resize_form(G, g[l - 1], &ldsUnused);
+      G.resizeTPitch = resize_form(G, g[l - 1]);
       G.resizeRecBase = (int)(resizerec.size() / RESIZE_REC_WORDS);
       for (int dy0 = 0; dy0 < G.h; dy0 += G.resizeRows) {
         const int nrows = std::min(G.resizeRows, G.h - dy0);
@@ -597,7 +593,7 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
   for (int l = 0; l < nl; l++) {
     const LevelGeom &G = g[l];
     if (G.pitch > 65535 || G.bpitch > 65535) { h->err = "level pitch above 65535"; return ORBX_E_ARG; }
-    if (l > 0 && (size_t)((G.w + 3) & ~3) * 8 > ORB_LDS_LIMIT - 1024) { h->err = "pyramid level wider than 20000 columns"; return ORBX_E_ARG; }   // k_resize's x table
+    if (l > 0 && ResizeCarve::of(0, 0, 0, (G.w + 3) & ~3).bytes > RESIZE_LDS_MAX) { h->err = "pyramid level wider than 20000 columns"; return ORBX_E_ARG; }   // k_resize's x table
     for (int ty = 0; ty < G.tilesY; ty++)
       for (int tx = 0; tx < G.tilesX; tx++) {
         uint32_t *R = &tilerec[(size_t)(G.tileBase + ty * G.tilesX + tx) * 8];
@@ -681,11 +677,11 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
           tilesC.push_back(T);
         }
     b0 = align_up(b0, 16); b1 = align_up(b1, 16);
-    const size_t lds = b0 + b1 + sizeof(int2) * tabMax;
+    const size_t lds = ChainCarve::of((int)b0, (int)b1, (int)tabMax).bytes;
     // stage sizes stay below 2^14 pixels (the kernel's index split) and the whole state inside 64 KiB; otherwise (scale factors far
     // from 1.2) single-frame calls keep the level-by-level form
     h->chainTiles = 0;
-    if (!tilesC.empty() && lds <= 64 * 1024 && b1 <= 16384 && b0 <= 65536 && tilesC.size() < 65536) {
+    if (!tilesC.empty() && lds <= CHAIN_LDS_MAX && b1 <= 16384 && b0 <= 65536 && tilesC.size() < 65536) {
       bool ok = true;
       for (const ChainTile &T : tilesC)
         for (int l = 1; l <= T.level; l++) ok = ok && (size_t)T.w[l] * T.h[l] < 16384;
@@ -696,15 +692,17 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
       }
     }
   }
-  // k_octree LDS: node arrays (72 B per node) + scan scratch, plus the level's cell offsets when they fit
+  // k_octree LDS (OctreeCarve): node arrays (OCT_HEAD_PER_NODE + OCT_BODY_PER_NODE bytes per node) + scan scratch, plus the level's cell offsets when they fit
   int maxCells = 1;
   for (int l = 0; l < nl; l++) maxCells = std::max(maxCells, g[l].nCols * g[l].nRows);
+  // (what the check below refuses anyway, taken out before the carve's int arithmetic sees it)
+  if (octCap > OCT_LDS_MAX / (OCT_HEAD_PER_NODE + OCT_BODY_PER_NODE)) { h->err = "nfeatures too large for the LDS-resident octree"; return ORBX_E_ARG; }
   // k_octree's code form: per level one byte per column and per row of the detection rectangle - the root and
   // the OCT_D x bits, the OCT_D y bits of the key's path through DivideNode's splits (ORBextractor.cc:479-535), walked with the
   // kernel's own interval arithmetic.  A split line is ul + ((ur - ul + 1) >> 1) and a key goes right / down when it is not below
   // it; an interval of width 1 splits into widths 1 and 0, one of width 0 keeps itself as its right child: the walk just goes on,
   // the bits are what the comparisons give.  The leaf bins, the count pyramid and the leaf map live in the LDS of chcnt / chpos
-  // (32 * octCap bytes): where they fit there - the bench's configurations - octLds is what it is without them; a configuration
+  // (OCT_HEAD_PER_NODE * octCap bytes): where they fit there - the bench's configurations - octLds is what it is without them; a configuration
   // with fewer nodes gets that head region enlarged as long as the whole stays small (32 KiB), any other keeps the per-key rounds.
   {
     int maxIni = 0;
@@ -713,9 +711,9 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
     if (const char *e = getenv("ORBHIP_OCTREE_TABLE_LIMIT")) limit = (size_t)strtoul(e, nullptr, 10);   // tests: a bound the tables do not fit
     const size_t tabBytes = align_up(OCT_TABLE_BYTES(std::max(maxIni, 1)), 16);
     h->octCodes = maxIni >= 1 && (maxIni << OCT_D) <= 256 && octCap <= 65535 && tabBytes <= limit;
-    h->octHead = 32 * (size_t)octCap;
+    h->octHead = OCT_HEAD_PER_NODE * (size_t)octCap;
     if (h->octCodes && tabBytes > h->octHead) {
-      if (tabBytes + 40 * (size_t)octCap + 128 + 4 * ((size_t)maxCells + 1) <= 32 * 1024) h->octHead = tabBytes;
+      if (OctreeCarve::of(octCap, (int)tabBytes, 1024, maxCells).bytes <= OCT_GROWN_HEAD_MAX) h->octHead = tabBytes;
       else h->octCodes = false;
     }
     if (h->octCodes) {
@@ -747,11 +745,9 @@ int orbx_configure(orbx_t *h, int rows, int cols, int max_batch) {
       if (!tab.empty()) XCHECK(h, copy_on(h->stream, h->d_octTab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
     }
   }
-  size_t lds = h->octHead + 40 * (size_t)octCap + 128;
-  if (lds > 160 * 1024 - 256) { h->err = "nfeatures too large for the LDS-resident octree"; return ORBX_E_ARG; }
-  h->octCellsLds = lds + 4 * ((size_t)maxCells + 1) <= 96 * 1024;
-  if (h->octCellsLds) lds += 4 * ((size_t)maxCells + 1);
-  h->octLds = lds;
+  if (OctreeCarve::of(octCap, (int)h->octHead, 1024, 0).bytes > OCT_LDS_MAX) { h->err = "nfeatures too large for the LDS-resident octree"; return ORBX_E_ARG; }
+  h->octCellsLds = OctreeCarve::of(octCap, (int)h->octHead, 1024, maxCells).bytes <= OCT_CELLS_LDS_MAX;
+  const size_t lds = h->octLds = OctreeCarve::of(octCap, (int)h->octHead, 1024, h->octCellsLds ? maxCells : 0).bytes;
   if (lds > ORB_LDS_LIMIT) { h->err = "octree LDS state exceeds 160 KiB"; return ORBX_E_ARG; }   // limit raised once in orbx_create
   h->rows = rows;
   h->cols = cols;
@@ -863,12 +859,11 @@ int orbx_extract_batch_device(orbx_t *h, const uint8_t *d_images, int rows, int 
   else
   for (int l = 1; l < h->nlevels; l++) {
     const LevelGeom &G = h->geom[l], &Gs = h->geom[l - 1];
-    const int rowBytes = (int)align_up((size_t)Gs.w + 4, 16);
-    size_t lds;
-    (void)resize_form(G, Gs, &lds);
-    const int tPitch = G.resizeTPitch;   // orbx_configure built the row-tile records with it
+    const int rowBytes = resize_row_bytes(Gs.w);
+    const int tPitch = G.resizeTPitch;   // orbx_configure chose the form and built the row-tile records with it
     const bool twoPass = tPitch > 0;
-    hipLaunchKernelGGL(k_resize, dim3(((G.h + G.resizeRows - 1) / G.resizeRows) * nframes), dim3(256), lds, s, P, l, rowBytes, tPitch, G.resizeSrcRows);
+    hipLaunchKernelGGL(k_resize, dim3(((G.h + G.resizeRows - 1) / G.resizeRows) * nframes), dim3(256), ResizeCarve::of(G.resizeSrcRows, rowBytes, tPitch, (G.w + 3) & ~3).bytes, s, P,
+                       l, rowBytes, tPitch, G.resizeSrcRows);
     if (printForms) pyrForm += std::string(l > 1 ? "," : "") + (!twoPass ? "1p" : G.resizeRows == 16 ? "2p16" : "2p8");
   }
   if (prof) XCHECK(h, hipEventRecord(pev[1], s));
@@ -1056,7 +1051,7 @@ int orbx_clahe_device(const uint8_t *d_src, int rows, int cols, size_t src_strid
   hipLaunchKernelGGL(k_clahe_lut, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream, d_src, rows, cols, src_stride, tiles_x, tw, th, clipLimit,
                      lutScale, d_lut);
   const int rowsPerBlock = 4;
-  hipLaunchKernelGGL(k_clahe_interp, dim3((rows + rowsPerBlock - 1) / rowsPerBlock), dim3(256), (size_t)tiles_x * tiles_y * 256, (hipStream_t)stream, d_src,
+  hipLaunchKernelGGL(k_clahe_interp, dim3((rows + rowsPerBlock - 1) / rowsPerBlock), dim3(256), ClaheCarve::of(tiles_y, tiles_x).bytes, (hipStream_t)stream, d_src,
                      rows, cols, src_stride, tiles_x, tiles_y, 1.0f / (float)tw, 1.0f / (float)th, (const uint8_t *)d_lut, d_dst, dst_stride, rowsPerBlock);
   return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
 }
@@ -1179,7 +1174,7 @@ int orbx_clahe_batch_device(int nframes, const uint8_t *d_src, int rows, int col
   const int nq = (cols + 3) / 4;
   const int threads = nq >= 256 ? 256 : std::min(256, (nq * (256 / nq) + 63) / 64 * 64);
   hipLaunchKernelGGL(k_clahe_lut_batch, dim3(tiles_x * tiles_y, gridF), dim3(256), 0, (hipStream_t)stream, P);
-  hipLaunchKernelGGL(k_clahe_interp_batch, dim3(nbands, gridF), dim3(threads), (size_t)maxRows * tiles_x * 256, (hipStream_t)stream, P);
+  hipLaunchKernelGGL(k_clahe_interp_batch, dim3(nbands, gridF), dim3(threads), ClaheCarve::of(maxRows, tiles_x).bytes, (hipStream_t)stream, P);
   return hipGetLastError() == hipSuccess ? 0 : ORBX_E_HIP;
 }
 
@@ -1767,36 +1762,30 @@ static int search_batch(orbm_t *m, const orbm_frame_t *f, const Ragged &frame, c
   M.npairs = npairs; M.scan_qblocks = qblocks;
   const dim3 sgrid(8 * qblocks * ((npairs + 7) / 8), 1, nslices);   // XCD-aware 1-D order, see k_match_scan
   if (nslices > 1 && M.qany) MCHECK(m, hipMemsetAsync(M.qany, 0, (size_t)(npairs - 1) * query_stride + maxq, s));
-  // resolve LDS: owner words (n + 1 dummy), slot words, column-sorted keypoint list (u16), partner list, octave bytes; see k_match_resolve
-  const size_t small = sizeof(uint32_t) * (size_t)((maxn + 1) + maxn + (maxn + 1) / 2 + (M.partner ? (maxn + 1) / 2 + 1 : 0) + 2);
-  const size_t big = small + sizeof(uint32_t) * (size_t)((maxn + 3) / 4) + 48 * (size_t)maxn;   // + octave bytes, records, descriptors
-  const bool ldscand = big <= 136 * 1024;   // + the kernel's static LDS (Key32: wide list array 16 KiB, chunk lists, requests)
-  // fused form: octave bytes + one accumulator seed per keypoint (15 B per keypoint in all); its records and descriptors live in d_cand.
-  // Admission is what it was (the Key32 bound, 2048 keypoints, decides it: with the records in LDS the carve was 129 KB there), but the
-  // LDS condition is now slack: 31 KB at 2048 keypoints.  Serial / coupled problems never take the wide form.
-  const size_t fused_lds = small + sizeof(uint32_t) * (size_t)((maxn + 3) / 4) + sizeof(uint32_t) * (size_t)maxn;
-  const bool fused = mfma && m->hamming_engine >= 2 && o.init_th_low < 0 && !M.serial && M.couple == 0 && fused_lds <= 138 * 1024;
-  const size_t lds = fused ? fused_lds : ldscand ? big : small;
+  // resolve LDS (ResolveCarve, orb_match_kernels.h): records and descriptors in LDS where they fit; the fused form keeps them in d_cand.
+  // Serial / coupled problems never take the wide form.
+  const ResolveForm rform = resolve_form(maxn, M.partner != nullptr, mfma && m->hamming_engine >= 2 && o.init_th_low < 0 && !M.serial && M.couple == 0);
+  const bool ldscand = rform.ldscand, fused = rform.fused;
+  const size_t lds = (size_t)rform.bytes;
   // ORBHIP_PRINT_RESOLVE_LDS (measurements, tests/test_gpu_fused_footprint.py): the form and the dynamic LDS of every search launch
   if (getenv("ORBHIP_PRINT_RESOLVE_LDS")) fprintf(stderr, "orbhip: resolve maxn %d fused %d dynamic LDS %zu bytes\n", maxn, (int)fused, lds);
   if (fused && 3 * sizeof(uint4) * (size_t)maxn * (size_t)npairs > m->d_cand.bytes) {
     MCHECK(m, hipStreamSynchronize(s));
     MCHECK(m, m->d_cand.reserve(3 * sizeof(uint4) * (size_t)maxn * (size_t)npairs));
   }
-  if (lds > 152 * 1024) { m->err = "too many keypoints per frame for the search kernels' LDS state (fisheye-stereo frames: at most 13000)"; return ORBX_E_ARG; }
+  if (lds > RESOLVE_LDS_MAX) { m->err = "too many keypoints per frame for the search kernels' LDS state (fisheye-stereo frames: at most 13000)"; return ORBX_E_ARG; }
   const dim3 rblock(64 * RESOLVE_NW_OF(fused));
   // The walk's workgroups come first: they are the short ones.
   const int capn = std::min((maxn + 7) & ~7, WALK_MAX_N);
   // few pairs in flight: four lanes per query and four times the workgroups (see k_match_walk)
   const int lpq = (long long)npairs * qblocks <= 32 ? 4 : 1;
   const int wqblocks = (maxq + MATCH_NT / lpq - 1) / (MATCH_NT / lpq);
-  const size_t wlds = sizeof(uint32_t) * (GRID_CELLS + 4) + (12 + (o.fuse || M.u_right ? 4 : 0)) * (size_t)capn + 2 * WALK_LIST * MATCH_NT +
-                      (lpq > 1 ? sizeof(uint32_t) * MATCH_TOPK * MATCH_NT : 0);
+  const WalkCarve<Key32::T> wcarve = WalkCarve<Key32::T>::of(capn, o.fuse || M.u_right, lpq);
   const dim3 wgrid(8 * wqblocks * ((npairs + 7) / 8));
   auto walk = [&](auto kind) {
     constexpr int K = decltype(kind)::value;
-    if (lpq > 1) hipLaunchKernelGGL((k_match_walk<Key32, K, 4>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
-    else hipLaunchKernelGGL((k_match_walk<Key32, K, 1>), wgrid, dim3(MATCH_NT), wlds, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
+    if (lpq > 1) hipLaunchKernelGGL((k_match_walk<Key32, K, 4>), wgrid, dim3(MATCH_NT), wcarve.bytes, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
+    else hipLaunchKernelGGL((k_match_walk<Key32, K, 1>), wgrid, dim3(MATCH_NT), wcarve.bytes, s, M, (Key32::T *)m->d_topk.p, force, capn, wqblocks);
   };
   if (force != SCAN_DENSE) {
     if (o.fuse) walk(ScanKind<SCAN_FUSE>()); else if (M.qside) walk(ScanKind<SCAN_FISHEYE>()); else if (M.u_right) walk(ScanKind<SCAN_UR>()); else walk(ScanKind<SCAN_PLAIN>());
@@ -1825,7 +1814,7 @@ static int search_batch(orbm_t *m, const orbm_frame_t *f, const Ragged &frame, c
     }
     if (prof) MCHECK(m, hipEventRecord(pev[1], s));
     if (o.init_th_low >= 0)
-      hipLaunchKernelGGL((k_init_resolve<KT>), dim3(npairs), dim3(64), 2 * (size_t)maxn + 16, s, M, (const typename KT::T *)topk, o.init_th_low);
+      hipLaunchKernelGGL((k_init_resolve<KT>), dim3(npairs), dim3(64), InitResolveCarve::of(maxn).bytes, s, M, (const typename KT::T *)topk, o.init_th_low);
     else
       hipLaunchKernelGGL((k_match_resolve<KT, LC>), dim3(npairs), rblock, lds, s, M, (const typename KT::T *)topk, maxn, force, (const uint32_t *)nullptr,
                          (const uint32_t *)nullptr, (const uint32_t *)nullptr);
@@ -4518,11 +4507,6 @@ static LmTables graph_bind(const Staging &S, const GraphParts &H, const orbm_map
   return {g->G, S.dev(H.rank), S.dev(H.kf_bad), S.dev(H.map), S.dev(H.row_start), S.dev(H.row_point), S.dev(H.best), S.dev(H.child_start), S.dev(H.child),
           S.dev(H.parent), S.dev(H.prev), g->P, S.dev(H.pt_bad), S.dev(H.obs_start), S.dev(H.obs_kf)};
 }
-static size_t lm_sort_lds(int G) {
-  size_t p2 = 2;
-  while (p2 < (size_t)G) p2 <<= 1;
-  return sizeof(uint64_t) * p2;
-}
 
 // The scratch of one UpdateLocalMap call: hdr, count, kf_count and pt_word are ONE span that is zero on entry
 struct LmScratch { int32_t *hdr, *count, *kf_count; uint32_t *pt_word; int32_t *list; };
@@ -4533,7 +4517,7 @@ static int local_map_launch(orbm_t *m, hipStream_t s, const LmTables &M, const L
   VoteParams V{M, N, d_frame_point, nullptr, O.slot_bad, X.count, m->vote_form};
   hipLaunchKernelGGL(k_covis_vote, dim3((unsigned)((N + 255) / 256), 1u), dim3(256), 0, s, V);
   WalkParams W{M, X.count, inertial, last_kf, cap_kf, X.list, X.hdr, O.local_kf, O.n_local_kf, O.kf_max, O.max_votes, O.n_local_point};
-  hipLaunchKernelGGL(k_local_kf_walk, dim3(1), dim3(LM_WALK_THREADS), lm_sort_lds(M.G), s, W);
+  hipLaunchKernelGGL(k_local_kf_walk, dim3(1), dim3(LM_WALK_THREADS), SortCarve::of(M.G).bytes, s, W);
   LpParams L{M, X.list, X.hdr, X.pt_word, X.kf_count, cap_pts, O.local_point, O.n_local_point};
   hipLaunchKernelGGL(k_lp_first, dim3(LM_TILES_X, LM_KF_BLOCKS), dim3(256), 0, s, L);
   hipLaunchKernelGGL(k_lp_count, dim3(LM_KF_BLOCKS), dim3(256), 0, s, L);
@@ -4646,7 +4630,7 @@ int orbm_update_connections(orbm_t *m, const orbm_map_graph_t *g, int T, const i
     VoteParams V{M, 0, nullptr, S.dev(htar), nullptr, S.dev(hcount), m->vote_form};
     hipLaunchKernelGGL(k_covis_vote, dim3((unsigned)((most + 255) / 256), (unsigned)T), dim3(256), 0, s, V);
   }
-  hipLaunchKernelGGL(k_conn_walk, dim3((unsigned)T), dim3(LM_WALK_THREADS), lm_sort_lds(g->G), s, C);
+  hipLaunchKernelGGL(k_conn_walk, dim3((unsigned)T), dim3(LM_WALK_THREADS), SortCarve::of(g->G).bytes, s, C);
   hipLaunchKernelGGL(k_conn_pack, dim3((unsigned)T), dim3(256), 0, s, C);
   MCHECK(m, hipGetLastError());
   const size_t out_bytes = S.span(hcs, hlists);
@@ -5546,8 +5530,6 @@ static int voc_fail(const std::string &what) { g_voc_err = what; return ORBX_E_A
     }                                                                       \
   } while (0)
 
-static int voc_p2(int n) { int p2 = 2; while (p2 < n) p2 <<= 1; return p2; }
-
 // k_voc_collect sorts up to 16384 8-byte keys: 128 KiB of dynamic LDS, above the 64 KiB a kernel gets unasked.  Raised once per device.
 static LdsOnce g_voc_lds;
 
@@ -5585,7 +5567,7 @@ static void voc_launch(const orbv_handle *v, hipStream_t s, const uint8_t *d_q, 
   C.rec = v->d_rec; C.weight = v->d_weight; C.n = live; C.cap = cap; C.weighting = v->weighting; C.scoring = v->scoring;
   C.entry = d_entry; C.node = d_node; C.bow_id = d_bow_id; C.bow_val = d_bow_val; C.n_bow = d_n_bow;
   C.fv_node_id = d_fv_node_id; C.fv_start = d_fv_start; C.fv_idx = d_fv_idx; C.n_fv = d_n_fv;
-  hipLaunchKernelGGL(k_voc_collect, dim3((unsigned)nframes), dim3(VOC_THREADS), sizeof(uint64_t) * (size_t)voc_p2(cap), s, C);
+  hipLaunchKernelGGL(k_voc_collect, dim3((unsigned)nframes), dim3(VOC_THREADS), SortCarve::of(cap).bytes, s, C);
 }
 
 extern "C" {
@@ -6065,11 +6047,9 @@ static void kfdb_fill_params(const orbd_handle *d, KfdbParams *P) {
 
 static void kfdb_launch(const KfdbParams &P, int nq, hipStream_t s, bool unmark) {
   const unsigned gq = (unsigned)std::max(1, (P.cap + 255) / 256), gs = (unsigned)((P.n_slots + 3) / 4);
-  int p2 = 2;
-  while (p2 < P.n_slots) p2 <<= 1;
   hipLaunchKernelGGL(k_kfdb_mark, dim3(gq, (unsigned)nq), dim3(256), 0, s, P);
   hipLaunchKernelGGL(k_kfdb_count, dim3(gs, (unsigned)nq), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(k_kfdb_order, dim3((unsigned)nq), dim3(KFDB_THREADS), sizeof(uint64_t) * (size_t)p2, s, P);
+  hipLaunchKernelGGL(k_kfdb_order, dim3((unsigned)nq), dim3(KFDB_THREADS), SortCarve::of(P.n_slots).bytes, s, P);
   hipLaunchKernelGGL(k_kfdb_score, dim3(gs, (unsigned)nq), dim3(256), 0, s, P);
   if (unmark) hipLaunchKernelGGL(k_kfdb_unmark, dim3(gq, 1u), dim3(256), 0, s, P);
 }

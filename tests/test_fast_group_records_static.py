@@ -1,27 +1,17 @@
 """k_fast's memory round trips, read off the compiled device code (no GPU): the group record is fetched by scalar loads in front of
 the tile DMA, and nothing is loaded from memory between the workgroup barrier and the detection loop."""
-import importlib
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG
+from device_code import device_asm
 
 LOAD = re.compile(r"^\s*(global_load|flat_load|buffer_load|scratch_load|s_load|s_buffer_load)\w*\s")
 
 
 @pytest.fixture(scope="module")
-def k_fast_asm(tmp_path_factory):
-    build = importlib.import_module(PKG + ".build")
-    if not os.path.exists(build.HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("kfast") / "orbhip.s"
-    flags = [f for f in build.FLAGS if f != "-shared"]
-    subprocess.check_call([build.HIPCC] + flags + ["--offload-device-only", "-S", os.path.join(build.CSRC, "orbhip.hip"), "-o", str(out)],
-                          stderr=subprocess.DEVNULL)
-    lines = out.read_text().splitlines()
+def k_fast_asm():
+    lines = device_asm()
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z6k_fast\w*:", l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     return [l.split(";")[0].rstrip() for l in lines[start + 1:end]]
